@@ -14,9 +14,10 @@ autocast) - fp16-plane GEMMs carrying the error of an fp32 GEMM - documents in t
 exact fp32 MFMA kernel (asserted on the whole problem in every run: `parity`).
 
 Also reported on the same JSON line: `roofline` for the dominant kernel (dense_split_kernel<true>, the filter's
-upper-bound pass, 16-bit MFMA bound; durations from HIP events recorded around every launch inside the timed region),
-`cpu_baseline` (faiss's flat-IP algorithm - host BLAS sgemm blocks + a heap per query - on the host cores, bounded
-sample, rank 0 at N = 1 only), and the other stages / configs of the headline metric:
+upper-bound pass, 16-bit MFMA bound; durations from HIP events recorded around every launch inside the timed region).
+A plain run stops there: set-up, warm-up, the timed steps, the line.  With --full it goes on to the `parity` proof, the
+`breakdown` of a step, `cpu_baseline` (faiss's flat-IP algorithm - host BLAS sgemm blocks + a heap per query - on the host
+cores, bounded sample, rank 0 at N = 1 only), and the other stages / configs of the headline metric:
   `exact_kernel_mode`  the same step with every product on the fp32 MFMA pipe: the data-independent floor;
   `filter_robustness`  the search stage on anisotropic / near-duplicate corpora and queries drawn near documents (full shape),
                        each compared with the exact kernel on all queries, with the certified / re-done query counts;
@@ -34,7 +35,10 @@ sample, rank 0 at N = 1 only), and the other stages / configs of the headline me
   `small_batch`        1 and 16 queries (the HBM-bound regime), each also in the batch-invariant mode;
   `config5_8b`         BASELINE.json configs[4]: one GPU's share at Lion-DS-8B dims.
 
-  python bench.py --gpus 1 --steps 3 --warmup 1
+--dump-outputs DIR writes what the last timed step returned (top-k scores and ids) as DIR/*.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+
+  python bench.py --gpus 1 --steps 3 --warmup 1 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus 8 --steps 3 --warmup 1
 """
@@ -1066,6 +1070,66 @@ def config5_leg(args, device):
                                                    "unit": "GB/s", "frac": round(gbps / PEAK_HBM_GBPS, 4)}}}
 
 
+LEGS = ("roofline", "cpu_baseline", "parity", "exact_kernel_mode", "breakdown", "small_batch", "fp32_class_mode", "fast_mode",
+        "drop_in", "shard_1of8", "filter_robustness", "encode", "sparse", "config5_8b")
+
+
+def record(args, cfg, world, dt, ranks_info, **legs):
+    """The full record of a run: the headline figures of the timed steps and every leg that ran (None for the others)."""
+    assert set(legs) <= set(LEGS), sorted(set(legs) - set(LEGS))
+    drop_in, sparse, encode = legs.get("drop_in"), legs.get("sparse"), legs.get("encode")
+    H = cfg["hidden_size"]
+    res = {
+        "metric": "MSMARCO-Dev queries/sec end-to-end (query encode + dense brute-force top-1000)",
+        "value": round(args.n_queries * args.steps / dt, 2), "unit": "queries/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "Lion-DS-1B dense: 6980 Dev queries encoded (HIP LlamaBiDense, 1B dims, random init, fp32 regime as the reference: "
+                               "split-plane GEMMs with the error of an fp32 GEMM, fp32 attention) "
+                               f"+ brute-force fp32 top-{args.topk} over {args.n_docs} x {H} passage embeddings resident in HBM",
+                   "n_docs": args.n_docs, "n_queries": args.n_queries, "hidden": H, "topk": args.topk,
+                   "query_batch": args.query_batch, "layers": cfg["num_hidden_layers"],
+                   "query_encode_precision": "fp32 regime (two fp16 planes of power-of-two scaled rows per operand, 3 products, fp32 accumulate: "
+                                             "the error of an fp32 GEMM)",
+                   "doc_encode_precision": "bf16 autocast regime", "score_precision": "exact fp32 (k-ordered fmaf chain)" + ("" if args.exact_kernel else ": certified fp16 upper-bound filter + exact re-score of 1-2k candidates per query, "
+                                                                           "bit-identical to the exact kernel (parity field)"),
+                   "ranks": ranks_info,
+                   # the figures of the other legs a reader looks for first, where a record that keeps only `config` still has them
+                   "drop_in_retrieval_qps": (drop_in or {}).get("retrieval_task_with_run_json", {}).get("queries_per_s") if drop_in else None,
+                   "drop_in_search_knn_qps": (drop_in or {}).get("search_knn", {}).get("queries_per_s") if drop_in else None,
+                   "sparse_qps": sparse["value"] if sparse else None,
+                   "sparse_qps_exact_kernels": (sparse.get("exact_kernels") or {}).get("queries_per_s") if sparse else None,
+                   "sparse_index_passages_per_s": (sparse.get("sparse_index") or {}).get("passages_per_s") if sparse else None,
+                   "sparse_index_build_postings_per_s": (sparse.get("index_build") or {}).get("postings_per_s") if sparse else None,
+                   "encode_passages_per_s": (encode or {}).get("value") if encode else None,
+                   "parallelism": f"doc-shard x{world}" + (" (queries encoded 1/W per rank + all-gather of the 57 MB query matrix; "
+                                                                   "1 RCCL gather of per-shard top-k; merge on rank 0)" if world > 1 else "")},
+    }
+    res.update({k: legs.get(k) for k in LEGS})
+    return res
+
+
+DUMP_MAX_BYTES = 60_000_000      # scores + ids; the row list and the .npy headers stay within 64 MB with it
+
+
+def dump_outputs(path, scores, ids, n_docs):
+    """--dump-outputs: what a caller of the timed path receives from its last step - the top-k scores and passage ids of every
+    query - as DIR/scores.npy (float32) and DIR/ids.npy (float32 while every id < 2^24 is exact there, float64 beyond), with the
+    query rows they belong to in DIR/query_rows.npy (float64).  Larger than DUMP_MAX_BYTES: a fixed, seeded sample of the rows."""
+    os.makedirs(path, exist_ok=True)
+    s, i = scores.cpu().numpy(), ids.cpu().numpy()
+    id_dtype = np.float32 if n_docs <= (1 << 24) else np.float64
+    row_bytes = max(1, s.shape[1] * 4 + i.shape[1] * np.dtype(id_dtype).itemsize)
+    rows = np.arange(s.shape[0])
+    if len(rows) * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(len(rows), DUMP_MAX_BYTES // row_bytes, replace=False))
+    np.save(os.path.join(path, "scores.npy"), s[rows].astype(np.float32))
+    np.save(os.path.join(path, "ids.npy"), i[rows].astype(id_dtype))
+    np.save(os.path.join(path, "query_rows.npy"), rows.astype(np.float64))
+    log(f"[dump-outputs] {len(rows)} of {s.shape[0]} query rows -> {path}")
+
+
 def launch_ranks(n, argv, dry_run=False):
     """Start `n` ranks of this script on this node (one per GPU) through torch.distributed.run and relay rank 0's line.
     Returns the exit status: 0 only if every rank exited cleanly.  Called before any GPU call of this process."""
@@ -1137,7 +1201,14 @@ def main():
     ap.add_argument("--sparse-index-passages", type=int, default=131072, help="synthetic passages of the sparse_index leg")
     ap.add_argument("--print-launch", action="store_true", help="with --gpus N > 1 and no launcher: print the command that would start the ranks and exit")
     ap.add_argument("--no-robustness", action="store_true", help="skip the filter_robustness legs (anisotropic / near-duplicate corpora at full shape)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg as well (parity proof, breakdown, precision "
+                    "modes, small batches, CPU baseline, shard / robustness / drop_in / encode / sparse / config5 legs; the --no-* options "
+                    "trim them); without it a run is set-up, warm-up, the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (top-k scores and ids "
+                    "of every query) to DIR/*.npy, for comparing two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it starts the N ranks itself (before anything touches a GPU:
     # device_count() does not initialise one): one child `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>`,
@@ -1281,6 +1352,27 @@ def main():
                     "frac": round(achieved_tf / PEAK_F32_MFMA_TF, 4), "traffic": traffic,
                     "launches": int(n_l.value), "avg_launch_ms": round(ms.value / max(1, n_l.value), 4),
                     "flop_per_launch": fl.value / max(1, n_l.value), "kernel_share_of_step": round(ms.value * 1e-3 / dt, 3)}
+
+    # self-check of a multi-GPU run (VERDICT r03 item 7): what torch.distributed really set up, and what every rank holds
+    ranks_info = {"world_size": world, "backend": dist.get_backend() if world > 1 else None, "shard_docs": [n_local],
+                  "queries_encoded_per_rank": [q_rows[1] - q_rows[0]]}
+    if world > 1:
+        t = torch.tensor([n_local, q_rows[1] - q_rows[0], torch.cuda.current_device()], dtype=torch.int64, device="cpu" if share_gpu else device)
+        got = [torch.zeros_like(t) for _ in range(world)]
+        dist.all_gather(got, t)
+        ranks_info.update({"shard_docs": [int(x[0]) for x in got], "queries_encoded_per_rank": [int(x[1]) for x in got],
+                           "cuda_device_of_rank": [int(x[2]) for x in got]})
+        assert sum(ranks_info["shard_docs"]) == args.n_docs and sum(ranks_info["queries_encoded_per_rank"]) == args.n_queries
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *out, n_docs=args.n_docs)
+    if not args.full:
+        # a plain run ends here: set-up, warm-up, the timed steps and the headline's line; every other leg runs under --full
+        if rank == 0:
+            emit(record(args, cfg, world, dt, ranks_info, roofline=roofline))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- where a step's time goes (one extra pass of each stage, synchronised; not part of the timed region) ----
     torch.cuda.synchronize()
@@ -1613,47 +1705,10 @@ def main():
         torch.cuda.empty_cache()
         config5 = config5_leg(args, device)
 
-    # self-check of a multi-GPU run (VERDICT r03 item 7): what torch.distributed really set up, and what every rank holds
-    ranks_info = {"world_size": world, "backend": dist.get_backend() if world > 1 else None, "shard_docs": [n_local],
-                  "queries_encoded_per_rank": [q_rows[1] - q_rows[0]]}
-    if world > 1:
-        t = torch.tensor([n_local, q_rows[1] - q_rows[0], torch.cuda.current_device()], dtype=torch.int64, device="cpu" if share_gpu else device)
-        got = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(got, t)
-        ranks_info.update({"shard_docs": [int(x[0]) for x in got], "queries_encoded_per_rank": [int(x[1]) for x in got],
-                           "cuda_device_of_rank": [int(x[2]) for x in got]})
-        assert sum(ranks_info["shard_docs"]) == args.n_docs and sum(ranks_info["queries_encoded_per_rank"]) == args.n_queries
     if rank == 0:
-        res = {
-            "metric": "MSMARCO-Dev queries/sec end-to-end (query encode + dense brute-force top-1000)",
-            "value": round(args.n_queries * args.steps / dt, 2), "unit": "queries/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "Lion-DS-1B dense: 6980 Dev queries encoded (HIP LlamaBiDense, 1B dims, random init, fp32 regime as the reference: "
-                                   "split-plane GEMMs with the error of an fp32 GEMM, fp32 attention) "
-                                   f"+ brute-force fp32 top-{args.topk} over {args.n_docs} x {H} passage embeddings resident in HBM",
-                       "n_docs": args.n_docs, "n_queries": args.n_queries, "hidden": H, "topk": args.topk,
-                       "query_batch": args.query_batch, "layers": cfg["num_hidden_layers"],
-                       "query_encode_precision": "fp32 regime (two fp16 planes of power-of-two scaled rows per operand, 3 products, fp32 accumulate: "
-                                                 "the error of an fp32 GEMM)",
-                       "doc_encode_precision": "bf16 autocast regime", "score_precision": "exact fp32 (k-ordered fmaf chain)" + ("" if args.exact_kernel else ": certified fp16 upper-bound filter + exact re-score of 1-2k candidates per query, "
-                                                                               "bit-identical to the exact kernel (parity field)"),
-                       "ranks": ranks_info,
-                       # the figures of the other legs a reader looks for first, where a record that keeps only `config` still has them
-                       "drop_in_retrieval_qps": (drop_in or {}).get("retrieval_task_with_run_json", {}).get("queries_per_s") if drop_in else None,
-                       "drop_in_search_knn_qps": (drop_in or {}).get("search_knn", {}).get("queries_per_s") if drop_in else None,
-                       "sparse_qps": sparse["value"] if sparse else None,
-                       "sparse_qps_exact_kernels": (sparse.get("exact_kernels") or {}).get("queries_per_s") if sparse else None,
-                       "sparse_index_passages_per_s": (sparse.get("sparse_index") or {}).get("passages_per_s") if sparse else None,
-                       "sparse_index_build_postings_per_s": (sparse.get("index_build") or {}).get("postings_per_s") if sparse else None,
-                       "encode_passages_per_s": (encode or {}).get("value") if encode else None,
-                       "parallelism": f"doc-shard x{world}" + (" (queries encoded 1/W per rank + all-gather of the 57 MB query matrix; "
-                                                                       "1 RCCL gather of per-shard top-k; merge on rank 0)" if world > 1 else "")},
-            "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "exact_kernel_mode": exact_mode, "breakdown": breakdown, "small_batch": small, "fp32_class_mode": fp32_class, "fast_mode": fast,
-            "drop_in": drop_in, "shard_1of8": shard_leg, "filter_robustness": robustness, "encode": encode, "sparse": sparse, "config5_8b": config5,
-        }
-        emit(res)
+        emit(record(args, cfg, world, dt, ranks_info, roofline=roofline, cpu_baseline=cpu, parity=parity, exact_kernel_mode=exact_mode,
+                    breakdown=breakdown, small_batch=small, fp32_class_mode=fp32_class, fast_mode=fast, drop_in=drop_in, shard_1of8=shard_leg,
+                    filter_robustness=robustness, encode=encode, sparse=sparse, config5_8b=config5))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -70,3 +70,56 @@ def test_committed_bench_line_of_this_round():
     assert d["sparse"]["traffic"] is None or d["sparse"]["traffic"] > 0
     assert d["sparse"]["sweep"]["cells"] >= 12 and d["sparse"]["sweep"]["all_bit_exact"] is True
     assert d["encode"]["padded_128_passages_per_s"] > 0
+
+
+def _import_bench():
+    sys.path.insert(0, ROOT)
+    argv, sys.argv = sys.argv, ["bench.py"]
+    try:
+        import bench
+    finally:
+        sys.argv = argv
+    return bench
+
+
+def test_plain_run_record_gives_a_strict_line_with_the_headline_fields():
+    """A run without --full emits the record of the timed steps alone: the headline fields and `roofline`, every other leg null."""
+    import argparse
+    bench = _import_bench()
+    with open(os.path.join(ROOT, "profiles", "r05_bench_line.json")) as f:
+        full = json.load(f)
+    args = argparse.Namespace(n_queries=6980, steps=3, warmup=1, topk=1000, n_docs=8_841_823, query_batch=6980, exact_kernel=False)
+    ranks = {"world_size": 1, "backend": None, "shard_docs": [8_841_823], "queries_encoded_per_rank": [6980]}
+    res = bench.record(args, dict(bench.LION_1B), 1, 1.5, ranks, roofline=full["roofline"])
+    assert all(res[k] is None for k in bench.LEGS if k != "roofline")
+    text = bench.contract_line(res)
+    assert "\n" not in text and len(text) < bench.CONTRACT_LINE_MAX
+    d = json.loads(text, parse_constant=_reject_constant)
+    assert d["metric"] == full["metric"] and d["unit"] == "queries/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["ms_per_step"] == 500.0 and abs(d["value"] - 6980 / 0.5) < 1e-6
+    assert d["roofline"]["bound"] == "mfma" and d["cpu_baseline"] is None and d["sparse"] is None
+
+
+def test_dump_outputs_writes_every_row_within_64_mb_and_samples_a_larger_output(tmp_path):
+    import numpy as np
+    import torch
+    bench = _import_bench()
+    g = torch.Generator().manual_seed(0)
+    s = torch.randn((6980, 1000), generator=g)
+    i = torch.randint(0, 8_841_823, (6980, 1000), generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), s, i, n_docs=8_841_823)
+    files = {f: np.load(tmp_path / "a" / f) for f in ("scores.npy", "ids.npy", "query_rows.npy")}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    assert files["scores.npy"].dtype == np.float32 and files["ids.npy"].dtype == np.float32 and files["query_rows.npy"].dtype == np.float64
+    assert np.array_equal(files["scores.npy"], s.numpy()) and np.array_equal(files["ids.npy"].astype(np.int64), i.numpy())
+    assert np.array_equal(files["query_rows.npy"], np.arange(6980))
+    # ids beyond 2^24 need float64: the 6 980 rows no longer fit, a fixed sample of them is written, the same one every time
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), s, i + (1 << 24), n_docs=1 << 25)
+    rows = np.load(tmp_path / "b" / "query_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 6980 and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 64_000_000
+    ids = np.load(tmp_path / "b" / "ids.npy")
+    assert ids.dtype == np.float64 and np.array_equal(ids.astype(np.int64), i.numpy()[rows] + (1 << 24))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))

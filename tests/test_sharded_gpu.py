@@ -67,7 +67,7 @@ def test_bench_multi_rank_path_dry_run():
     env.pop("WORLD_SIZE", None)
     # no launcher on the command line: `bench.py --gpus 2` starts its two ranks itself (the driver's command shape)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--n-docs", "300000",
-           "--encode-passages", "4096", "--layers", "2", "--no-cpu-baseline", "--sparse-docs", "200000"]
+           "--encode-passages", "4096", "--layers", "2", "--no-cpu-baseline", "--sparse-docs", "200000", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -11,7 +11,7 @@ cd $R
 cd /tmp && export TMPDIR=/tmp
 T="timeout -s KILL 600"
 # 2. kernel statistics of the headline step + the sparse leg
-BENCH="python3 $R/bench.py --no-cpu-baseline --no-fast-mode --no-encode --no-config5 --no-robustness --no-shard-leg --no-drop-in --no-sparse-sweep --no-sparse-index --sparse-cpu-queries 4"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline --no-fast-mode --no-encode --no-config5 --no-robustness --no-shard-leg --no-drop-in --no-sparse-sweep --no-sparse-index --sparse-cpu-queries 4"
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -o bench -- $BENCH --steps 3 --warmup 1 > $O/bench_under_rocprof.json 2> $O/bench_stats.err
 # 3. the dense headline's traffic + MFMA counters (as in round 4)
 DENSE="$BENCH --no-sparse"
@@ -44,7 +44,7 @@ python3 tools/pmc_counters.py $O/pmc_sp? --out $O/pmc_sparse.json --match cert_s
 # 6. the bench line itself (what the driver runs), AFTER the counter passes: its sparse leg reads profiles/r06_pmc_sparse_traffic.json, which
 #    the collector ties to the sha256 of the kernel source that was profiled above
 python3 tools/profile_r06_collect.py > $O/collect_on_box.log 2>&1
-python3 bench.py > $O/bench_line.json 2> $O/bench.log || echo "bench failed"
+python3 bench.py --full > $O/bench_line.json 2> $O/bench.log || echo "bench failed"
 cp gpurun_out/bench_detail.json $O/bench_detail.json
 # 7. the GPU suite on the same box
 python3 -m pytest tests -m gpu -q 2>&1 | tail -3 > $O/gpu_suite.txt
