@@ -37,7 +37,9 @@ typedef void* sr_stream; /* hipStream_t; NULL = default stream */
 
 const char* sr_last_error(void);
 int sr_version(void);
-/* Largest k supported by the fused top-k (LDS sort width). */
+/* Largest k served by the in-LDS top-k path (4096).  Not a limit on k: every search and merge below accepts
+ * 1 <= k <= 2^30 (the dense search: see sr_dense_search); a larger k goes through a top-k in global memory with the same
+ * results (any other k: SR_ERR_INVALID). */
 int sr_max_topk(void);
 
 /* ------------------------------------------------------------------ dense ---
@@ -56,8 +58,14 @@ int sr_dense_index_create(sr_dense_index** out, int dim);
 int sr_dense_index_add(sr_dense_index* idx, const float* d_rows, int64_t n_rows,
                        int64_t id_base, int64_t id_stride);
 int64_t sr_dense_index_ntotal(const sr_dense_index* idx);
-/* d_queries: fp32 [nq, dim] on device.  d_out_scores fp32 [nq, k],
- * d_out_ids int64 [nq, k] (global doc indices).                              */
+/* d_queries: fp32 [nq, dim] on device.  1 <= k <= 2^30, and a k above sr_max_topk() at most sr_max_topk() beyond the
+ * index's document count (k <= ntotal + 4096: rows of at most 4096 padding entries; a larger k is SR_ERR_INVALID, as any
+ * k > 4096 was before).  The caller provides d_out_scores fp32 [nq, k] and
+ * d_out_ids int64 [nq, k] (global doc indices).  For k > sr_max_topk() the running top-k (16 k bytes per query) and the
+ * select's buffers (4 k bytes per query) count against the workspace limit next to the candidate buffer; a call that does not
+ * fit runs in query sub-batches of more than 64 queries each (same bits as one batch).  If even the smallest such batch does
+ * not fit, the call returns SR_ERR_NOMEM (the byte count in sr_last_error()) and writes nothing.  The certified filter of
+ * SR_PRECISION_FP32_FILTERED needs k + 64 candidates in the in-LDS path: a larger k runs the exact kernel.               */
 int sr_dense_search(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
                     float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
 /* Arithmetic of the score kernel for query batches > 64:
@@ -91,12 +99,14 @@ int sr_dense_index_set_precision(sr_dense_index* idx, int mode);
  * d_threshold and re-scores only the candidates that can reach the GLOBAL top-k (about k / share of them instead of k).  The
  * shard's [nq, k] output then holds those (padding: score -FLT_MAX, id -1); sr_topk_merge of the shards' outputs is the global
  * top-k, bit for bit what one index over all documents returns.  When the certified filter does not apply, d_lower is -inf and
- * _finish is a plain sr_dense_search (d_threshold may be null).  Do not interleave other searches on the handle between the two. */
+ * _finish is a plain sr_dense_search (d_threshold may be null); that is always the case for k > sr_max_topk() - 64.  k as for
+ * sr_dense_search.  Do not interleave other searches on the handle between the two. */
 int sr_dense_search_begin(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, int share,
                           float* d_lower, sr_stream stream);
 int sr_dense_search_finish(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const float* d_threshold,
                            float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
-/* searches of more than 64 queries answered by the filter alone / with some (or all) queries re-done by the exact kernel */
+/* searches of more than 64 queries answered by the filter alone / with some (or all) queries re-done by the exact kernel.  A
+ * search with k > sr_max_topk() is counted in neither: the filter is never eligible for it.                               */
 int sr_dense_index_filter_stats(sr_dense_index* idx, int64_t* n_filtered, int64_t* n_fallback);
 /* the same per query: queries certified by the filter / re-done by the exact kernel so far */
 int sr_dense_index_filter_query_stats(sr_dense_index* idx, int64_t* n_certified, int64_t* n_redone);
@@ -135,7 +145,9 @@ int sr_sparse_index_create(sr_sparse_index** out, const int64_t* d_indptr,
 /* Queries as CSR: d_q_indptr int64 [nq+1] (non-decreasing), d_q_cols int32, d_q_vals fp32 (term
  * order inside a query = accumulation order).  A term id outside [0, n_terms) is an
  * empty posting list, as in the reference's vocabulary-filled dict (indexer.py:364-370).  Outputs [nq, k] padded with
- * (0, -1); d_out_counts int32 [nq] = number of valid entries per row.
+ * (0, -1); d_out_counts int32 [nq] = number of valid entries per row.  1 <= k <= 2^30: the caller provides [nq, k]
+ * outputs; for k > sr_max_topk() the query batches shrink so that the running top-k (20 k bytes per query with the select's
+ * buffers) and one 8 192-doc tile of candidates per query fit the workspace limit, SR_ERR_NOMEM if one query does not.
  * Global doc index = id_base + doc * id_stride.                              */
 int sr_sparse_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
                      const float* d_q_vals, int64_t nq, int k, float threshold,
@@ -217,7 +229,8 @@ int sr_sparse_csr_build(const int32_t* d_rows, const int32_t* d_cols, const floa
  * The one exchange step of doc-sharded retrieval: merge `n_lists` per-shard
  * top-k lists (after the RCCL gather) into the global top-k per query.
  * d_scores fp32 [n_lists, nq, k], d_ids int64 [n_lists, nq, k] (ids < 0 = pad).
- * Outputs as sr_dense_search (pad_score fills unused slots).                  */
+ * Outputs as sr_dense_search (pad_score fills unused slots).  1 <= k <= 2^30 with n_lists * k < 2^31; the library's workspace
+ * holds n_lists * k candidates and, for k > sr_max_topk(), 2k + k / 2 more 8-byte words per query.                        */
 int sr_topk_merge(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t nq, int k,
                   float pad_score, float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
 

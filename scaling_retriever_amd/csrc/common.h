@@ -150,6 +150,10 @@ struct TopkWS {
     unsigned char* seg_cnt = nullptr;   // [nq_cap, seg_n]
     int64_t seg_off = 0;
     int seg_n = 0;
+    // k > SR_MAX_TOPK only (topk_large.hip): the select's per-query state, 256 digit bins and list of k slots to refill
+    void* l_state = nullptr;                // [nq_cap]
+    unsigned long long* l_hist = nullptr;   // [nq_cap, 256]
+    uint32_t* l_holes = nullptr;            // [nq_cap, k]
     int ensure(int64_t nq, int k, int64_t cand_cap);
     int ensure_segments(int64_t nq, int k, int64_t dense_cap, int seg_n);     // cand_cap = dense_cap + seg_n * SR_SEG_P
     void release();
@@ -164,12 +168,21 @@ int topk_compact(TopkWS& ws, int64_t nq, int k, hipStream_t s);
 // by the caller's protocol: a query whose compaction only appends keeps its previous value
 // select_over in [k, 2 k]: the running set is cut back to k (and tau, tau2 refreshed) once it holds more keys than this - 2 k fills the
 // slots before it pays for a select, k selects in every call that brought a candidate
-int topk_compact2(TopkWS& ws, int64_t nq, int k, int k2, float* d_tau2, int select_over, hipStream_t s);
+int topk_compact2(TopkWS& ws, int64_t nq, int k, int k2, float* d_tau2, int64_t select_over, hipStream_t s);
 // sort the running top-k descending and write [nq, k] outputs (+ optional counts)
 int topk_finalize(TopkWS& ws, int64_t nq, int k, float pad_score, float* d_out_scores,
                   int64_t* d_out_ids, int32_t* d_out_counts, hipStream_t s);
 
+// Largest k of the in-LDS select and sort (topk.hip).  A larger k, up to SR_MAX_TOPK_LARGE, takes the global-memory path of
+// topk_large.hip behind the same calls; k2 / d_tau2 are not available there.
 #define SR_MAX_TOPK 4096
+#define SR_MAX_TOPK_LARGE (1 << 30)
+// device bytes per query of the large path's running set and select buffers (the candidate buffer comes on top)
+int64_t topk_large_bytes_per_query(int k);
+int topk_large_alloc(TopkWS& ws, int64_t nq, int k);
+int topk_large_compact(TopkWS& ws, int64_t nq, int k, int64_t select_over, hipStream_t s);
+int topk_large_finalize(TopkWS& ws, int64_t nq, int k, float pad_score, float* d_out_scores, int64_t* d_out_ids,
+                        int32_t* d_out_counts, hipStream_t s);
 
 // ---- per-launch HIP event log (measurement hook of the search handles) ----
 #include <vector>

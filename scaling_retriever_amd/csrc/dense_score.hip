@@ -594,6 +594,32 @@ extern "C" int sr_dense_index_set_precision(sr_dense_index* idx, int mode) {
 // one pass in the given arithmetic (SR_PRECISION_FP32 | _BF16X3 | _BF16X6); caller holds idx->mu
 static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, float* d_out_scores,
                              int64_t* d_out_ids, int precision, hipStream_t s, bool force_tiled = false, int k_inner = 0) {
+    // k > SR_MAX_TOPK: the running set (2k keys per query) and the select's buffers count against the workspace limit next to
+    // the candidate buffer (at least one 256-doc tile per query).  A call that does not fit runs in query sub-batches of more
+    // than 64 queries each, so that every query stays in the kernel family (and k order) of the unsplit call: the bits do not
+    // depend on the limit.
+    const int64_t large_bytes = k > SR_MAX_TOPK ? topk_large_bytes_per_query(k) : 0;
+    if (k > SR_MAX_TOPK) {
+        const int64_t per_q = large_bytes + 8 * 256;
+        const int64_t b_max = idx->ws_limit / per_q;
+        if (b_max < nq) {
+            int64_t nb = b_max >= 1 ? ceil_div64(nq, b_max) : 0;
+            if (nb == 0 || nq / nb <= 64) {
+                const int64_t smallest = nq <= 128 ? nq : 65;
+                sr_set_error("dense search: k = %d needs %lld bytes of workspace for a batch of %lld queries (limit %lld bytes)", k,
+                             (long long)(smallest * per_q), (long long)smallest, (long long)idx->ws_limit);
+                return SR_ERR_NOMEM;
+            }
+            for (int64_t b = 0, q0 = 0; b < nb; ++b) {            // balanced: every batch holds floor(nq / nb) or one more queries
+                const int64_t nqb = nq / nb + (b < nq % nb ? 1 : 0);
+                SR_TRY(dense_search_pass(idx, d_queries + q0 * idx->dim, nqb, k, d_out_scores + q0 * k, d_out_ids + q0 * k, precision,
+                                         s, force_tiled, k_inner));
+                q0 += nqb;
+            }
+            return SR_OK;
+        }
+    }
+    const int64_t cand_limit = idx->ws_limit - nq * large_bytes;   // candidate buffer budget
     const bool pass16 = (planes_of(precision) || precision == SR_PASS_FILTER) && nq > 64;
     // the re-do of a few queries and the 16-bit passes keep their own (differently shaped) workspaces
     TopkWS& ws = force_tiled ? idx->ws3 : (pass16 ? idx->wsf : idx->ws);
@@ -619,7 +645,7 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
     // compactions, 0.7606 -> 0.7417 ms per 14 rounds, search -2 % (same results; tools/split_ab.py SR_DENSE_LAUNCH_WGS=...)
     const int64_t launch_wgs = env_wgs ? atoll(env_wgs) : (pass16 ? 7168 : 2048);
     int64_t chunk = TM * unit * ceil_div64(launch_wgs, unit * qtiles);
-    int64_t max_cap = idx->ws_limit / (8 * nq);
+    int64_t max_cap = cand_limit / (8 * nq);
     max_cap = (max_cap / TM) * TM;
     if (max_cap < TM) max_cap = TM;
     if (chunk > max_cap) chunk = max_cap;
@@ -708,7 +734,7 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
     const bool use_stream = variant != 9 && !force_tiled && !idx->batch_invariant && dense_stream_supports((int)nq, idx->dim);
     if (use_stream) {
         // HBM-bound regime: D straight to registers, chunks grow geometrically (64 Ki docs, x2 per launch)
-        int64_t cap = idx->ws_limit / (8 * nq);
+        int64_t cap = cand_limit / (8 * nq);
         if (cap > (1ll << 22)) cap = 1ll << 22;
         cap = (cap / 128) * 128;
         if (cap < 128) cap = 128;
@@ -803,6 +829,7 @@ static int filter_segs_of(sr_dense_index* idx, FilterSegs& fs) {
 // filter does not apply to this index / batch.
 static int dense_filtered_candidates(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, hipStream_t s, bool* done) {
     *done = false;
+    if (k > SR_MAX_TOPK) return SR_OK;                         // no room for k + 64 candidates in the in-LDS top-k
     int kp = 3 * k > k + 2048 ? 3 * k : k + 2048;            // candidates per query: k = 1000 -> 3072
     if (const char* e = sr_dev_getenv("SR_FILTER_KP")) kp = atoi(e);
     if (kp > SR_MAX_TOPK) kp = SR_MAX_TOPK;
@@ -892,11 +919,17 @@ static int dense_search_filtered(sr_dense_index* idx, const float* d_queries, in
     return dense_filtered_finish(idx, d_queries, nq, k, nullptr, d_out_scores, d_out_ids, s);
 }
 
+// A k above SR_MAX_TOPK is served while the rows it asks for hold at most SR_MAX_TOPK entries of padding (k <= ntotal + SR_MAX_TOPK):
+// a search of more rows than the index holds documents is still rejected there, as it was before the large-k path existed.
+static bool dense_k_fits(const sr_dense_index* idx, int k) { return k <= SR_MAX_TOPK || (int64_t)k - SR_MAX_TOPK <= idx->ntotal; }
+
 extern "C" int sr_dense_search(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, float* d_out_scores,
                                int64_t* d_out_ids, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_search: null index");
     SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search: bad nq=%lld", (long long)nq);
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK, "sr_dense_search: k=%d outside [1, %d]", k, SR_MAX_TOPK);
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_dense_search: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_REQUIRE(dense_k_fits(idx, k), "sr_dense_search: k=%d exceeds %d by more than the index's %lld documents", k, SR_MAX_TOPK,
+               (long long)idx->ntotal);
     if (nq == 0) return SR_OK;
     SR_REQUIRE(d_queries && d_out_scores && d_out_ids, "sr_dense_search: null pointer");
     SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search: queries must be 16-byte aligned");
@@ -907,7 +940,7 @@ extern "C" int sr_dense_search(sr_dense_index* idx, const float* d_queries, int6
         bool done = false;
         SR_TRY(dense_search_filtered(idx, d_queries, nq, k, d_out_scores, d_out_ids, s, &done));
         if (done) return SR_OK;
-        if (nq > 64) { ++idx->n_fallback; idx->nq_redone += nq; }
+        if (nq > 64 && k <= SR_MAX_TOPK) { ++idx->n_fallback; idx->nq_redone += nq; }   // a larger k was never eligible
         return dense_search_pass(idx, d_queries, nq, k, d_out_scores, d_out_ids, SR_PRECISION_FP32, s);
     }
     return dense_search_pass(idx, d_queries, nq, k, d_out_scores, d_out_ids, idx->precision, s);
@@ -923,7 +956,9 @@ extern "C" int sr_dense_search(sr_dense_index* idx, const float* d_queries, int6
 extern "C" int sr_dense_search_begin(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, int share, float* d_lower,
                                      sr_stream stream) {
     SR_REQUIRE(idx && d_lower, "sr_dense_search_begin: null argument");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30) && k >= 1 && k <= SR_MAX_TOPK && share >= 1, "sr_dense_search_begin: bad argument");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30) && k >= 1 && k <= SR_MAX_TOPK_LARGE && share >= 1, "sr_dense_search_begin: bad argument");
+    SR_REQUIRE(dense_k_fits(idx, k), "sr_dense_search_begin: k=%d exceeds %d by more than the index's %lld documents", k, SR_MAX_TOPK,
+               (long long)idx->ntotal);
     if (nq == 0) return SR_OK;
     SR_REQUIRE(d_queries && ((uintptr_t)d_queries & 15) == 0, "sr_dense_search_begin: queries must be non-null and 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;

@@ -1225,8 +1225,21 @@ static int sparse_exact_search(sr_sparse_index* idx, const int64_t* d_q_indptr, 
     // query batches bound the candidate workspace: cap (slots per query) = docs per launch
     int64_t q_batch_max = 1024;
     if (const char* e = sr_dev_getenv("SR_SPARSE_QBATCH")) q_batch_max = atoll(e) >= 4 ? atoll(e) / 4 * 4 : 4;
-    const int64_t q_batch = nq < q_batch_max ? nq : q_batch_max;
-    int64_t max_tiles = idx->ws_limit / (8 * q_batch * SP_TILE);
+    int64_t q_batch = nq < q_batch_max ? nq : q_batch_max;
+    // k > SR_MAX_TOPK: the running set and the select's buffers (topk_large.hip) count against the limit as well, next to at
+    // least one tile of candidate slots per query; the batch shrinks to fit (the bits do not depend on it)
+    const int64_t large_bytes = k > SR_MAX_TOPK ? topk_large_bytes_per_query(k) : 0;
+    if (k > SR_MAX_TOPK) {
+        const int64_t per_q = large_bytes + 8 * (int64_t)SP_TILE;
+        const int64_t b_max = idx->ws_limit / per_q;
+        if (b_max < 1) {
+            sr_set_error("sr_sparse_search: k = %d needs %lld bytes of workspace per query (limit %lld bytes)", k, (long long)per_q,
+                         (long long)idx->ws_limit);
+            return SR_ERR_NOMEM;
+        }
+        if (q_batch > b_max) q_batch = b_max;
+    }
+    int64_t max_tiles = (idx->ws_limit - q_batch * large_bytes) / (8 * q_batch * SP_TILE);
     if (max_tiles < 1) max_tiles = 1;
     if (max_tiles > 64) max_tiles = 64;
     if (max_tiles > idx->n_tiles) max_tiles = idx->n_tiles;
@@ -1502,7 +1515,7 @@ extern "C" int sr_sparse_search(sr_sparse_index* idx, const int64_t* d_q_indptr,
                                 sr_stream stream) {
     SR_REQUIRE(idx, "sr_sparse_search: null index");
     SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search: bad nq");
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK, "sr_sparse_search: k=%d outside [1, %d]", k, SR_MAX_TOPK);
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
     SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
                "sr_sparse_search: global doc index exceeds 32 bits");
     if (nq == 0) return SR_OK;

@@ -431,6 +431,16 @@ int TopkWS::ensure(int64_t nq, int kk, int64_t cc) {
         sr_set_error("top-k workspace: out of device memory (%lld queries, k = %d, %lld candidate slots each)", (long long)nq, kk, (long long)cc);
         return SR_ERR_NOMEM;
     }
+    if (kk > SR_MAX_TOPK) {
+        const int rc = topk_large_alloc(*this, nq, kk);
+        if (rc != SR_OK) {
+            release();
+            if (rc == SR_ERR_NOMEM)
+                sr_set_error("top-k workspace: out of device memory for the select of k = %d (%lld queries, %lld bytes)", kk, (long long)nq,
+                             (long long)(nq * topk_large_bytes_per_query(kk)));
+            return rc;
+        }
+    }
     nq_cap = nq;
     k = kk;
     cand_cap = cc;
@@ -444,6 +454,12 @@ void TopkWS::release() {
     if (cand_keys) (void)hipFree(cand_keys);
     if (cand_count) (void)hipFree(cand_count);
     if (seg_cnt) (void)hipFree(seg_cnt);
+    if (l_state) (void)hipFree(l_state);
+    if (l_hist) (void)hipFree(l_hist);
+    if (l_holes) (void)hipFree(l_holes);
+    l_state = nullptr;
+    l_hist = nullptr;
+    l_holes = nullptr;
     seg_cnt = nullptr;
     seg_n = 0;
     seg_off = 0;
@@ -465,23 +481,27 @@ int topk_reset(TopkWS& ws, int64_t nq, hipStream_t s) {
 
 // NOTE: kernels index run_keys with stride 2 * k (k = the logical k of this search, at most the allocated ws.k) and
 // cand_keys with stride ws.cand_cap.
-int topk_compact(TopkWS& ws, int64_t nq, int k, hipStream_t s) { return topk_compact2(ws, nq, k, 0, nullptr, 2 * k, s); }
+int topk_compact(TopkWS& ws, int64_t nq, int k, hipStream_t s) { return topk_compact2(ws, nq, k, 0, nullptr, 2 * (int64_t)k, s); }
 
-int topk_compact2(TopkWS& ws, int64_t nq, int k, int k2, float* d_tau2, int select_over, hipStream_t s) {
-    select_over = select_over < k ? k : (select_over > 2 * k ? 2 * k : select_over);
+int topk_compact2(TopkWS& ws, int64_t nq, int k, int k2, float* d_tau2, int64_t select_over, hipStream_t s) {
+    select_over = select_over < k ? k : (select_over > 2 * (int64_t)k ? 2 * (int64_t)k : select_over);
     if (nq == 0) return SR_OK;
-    const size_t lds = sizeof(int) * (256 + 256 + 8) + sizeof(uint32_t) * 2 * (size_t)k;
     if (ws.seg_n > 0) {
         hipLaunchKernelGGL(topk_gather_segments_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, ws.cand_keys, ws.cand_count,
                            ws.cand_cap, ws.seg_cnt, ws.seg_n, ws.seg_off, nq);
         SR_CHECK_LAUNCH();
     }
+    if (k > SR_MAX_TOPK) {          // global-memory select (topk_large.hip); no second rank there
+        SR_REQUIRE(k2 == 0 && k <= SR_MAX_TOPK_LARGE, "topk_compact2: k = %d with k2 = %d", k, k2);
+        return topk_large_compact(ws, nq, k, select_over, s);
+    }
+    const size_t lds = sizeof(int) * (256 + 256 + 8) + sizeof(uint32_t) * 2 * (size_t)k;
     if (k2 > 0 && 2 * k + 1024 <= 256 * 20)
         hipLaunchKernelGGL(topk_compact_kernel<20>, dim3((unsigned)nq), dim3(256), lds, s, ws.run_keys, ws.run_count, ws.tau,
-                           ws.cand_keys, ws.cand_count, k, ws.cand_cap, k2, d_tau2, select_over);
+                           ws.cand_keys, ws.cand_count, k, ws.cand_cap, k2, d_tau2, (int)select_over);
     else
         hipLaunchKernelGGL(topk_compact_kernel<28>, dim3((unsigned)nq), dim3(256), lds, s, ws.run_keys, ws.run_count, ws.tau,
-                           ws.cand_keys, ws.cand_count, k, ws.cand_cap, k2, d_tau2, select_over);
+                           ws.cand_keys, ws.cand_count, k, ws.cand_cap, k2, d_tau2, (int)select_over);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }
@@ -489,6 +509,7 @@ int topk_compact2(TopkWS& ws, int64_t nq, int k, int k2, float* d_tau2, int sele
 int topk_finalize(TopkWS& ws, int64_t nq, int k, float pad_score, float* d_out_scores, int64_t* d_out_ids,
                   int32_t* d_out_counts, hipStream_t s) {
     if (nq == 0) return SR_OK;
+    if (k > SR_MAX_TOPK) return topk_large_finalize(ws, nq, k, pad_score, d_out_scores, d_out_ids, d_out_counts, s);
     const int P = next_pow2(2 * k);
     static DeviceOnce lds_set;      // k = 4096: 8192 keys = the whole 64 KB
     if (bool* slot = lds_set.pending()) {
@@ -507,8 +528,8 @@ static TopkWS g_merge_ws;
 
 extern "C" int sr_topk_merge(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t nq, int k,
                              float pad_score, float* d_out_scores, int64_t* d_out_ids, sr_stream stream) {
-    SR_REQUIRE(n_lists >= 1 && nq >= 0 && k >= 1 && k <= SR_MAX_TOPK, "sr_topk_merge: bad sizes (n_lists=%d nq=%lld k=%d)",
-               n_lists, (long long)nq, k);
+    SR_REQUIRE(n_lists >= 1 && nq >= 0 && k >= 1 && k <= SR_MAX_TOPK_LARGE && (int64_t)n_lists * k <= 0x7fffffffll,
+               "sr_topk_merge: bad sizes (n_lists=%d nq=%lld k=%d)", n_lists, (long long)nq, k);
     SR_REQUIRE(d_scores && d_ids && d_out_scores && d_out_ids, "sr_topk_merge: null pointer");
     if (nq == 0) return SR_OK;
     hipStream_t s = (hipStream_t)stream;

@@ -644,8 +644,9 @@ class SparseRetrieval:
     def numba_score_float(inverted_index_ids, inverted_index_floats, indexes_to_retrieve, query_values, threshold,
                           size_collection):
         """Same signature/returns as the reference: (doc indexes with score > threshold ascending int64,
-        NEGATED scores fp32).  Scores come from the HIP scorer with k = all candidates capped at the top-k
-        width, so use SparseRetrieval.retrieve for bulk work; this entry point exists for drop-in callers."""
+        NEGATED scores fp32), every such document.  Scores come from the HIP scorer with k = the number of documents
+        that can score at all (min(size_collection, summed posting-list lengths of the query terms)), so use
+        SparseRetrieval.retrieve for bulk work; this entry point exists for drop-in callers."""
         cache = SparseRetrieval._static_cache
         if cache is not None and cache[0] is inverted_index_ids and cache[3] == size_collection:
             hit = cache[1]
@@ -661,8 +662,9 @@ class SparseRetrieval:
             dev = torch.device("cuda", torch.cuda.current_device())
             hit = SparseIndexHIP(*_csr_sorted_by_doc(indptr, ids, vals, dev), size_collection, device=dev)
             SparseRetrieval._static_cache = (inverted_index_ids, hit, V, size_collection)
-        k = _lib.load().sr_max_topk()
         cols = np.asarray(indexes_to_retrieve, np.int32)
+        postings = sum(len(inverted_index_ids[int(t)]) for t in cols if int(t) in inverted_index_ids)
+        k = max(1, min(int(size_collection), postings))
         s, i, c = hit.search(np.array([0, len(cols)], np.int64), cols, np.asarray(query_values, np.float32), k,
                              threshold=float(threshold))
         c = int(c.item())
