@@ -265,8 +265,14 @@ int sr_model_create(sr_model** out, const sr_model_config* cfg);
  * model's internal layout.  dtype = SR_DTYPE_F32 or SR_DTYPE_BF16.           */
 int sr_model_set_weight(sr_model* m, const char* name, const void* d_ptr, int dtype,
                         int64_t rows, int64_t cols, sr_stream stream);
-/* Verifies all tensors were provided. */
+/* Verifies all tensors were provided and fixes the weights' layout: with fp32_planes = 16, a matrix whose low fp16 plane is
+ * all zero (e.g. bf16-valued weights) drops that plane's segment, so its GEMMs run 2 plane products instead of 3 with the
+ * same result bits.  sr_model_set_weight on a finalized model fails (SR_ERR_INVALID).                                    */
 int sr_model_finalize(sr_model* m);
+/* K segments of each fp32-regime weight matrix of a finalized model: 4 per layer (qkv, o_proj, gate-up, down_proj), then the
+ * lm_head if the model has one; *n = their number (4 num_layers + has_lm_head), min(capacity, *n) of them are written to the
+ * host array out.  fp32_planes = 16: 2 or 3 per matrix (see sr_model_finalize); 2 / 3: 3 / 6 everywhere; 0: 0.          */
+int sr_model_weight_segments(sr_model* m, int32_t* out, int64_t capacity, int64_t* n);
 /* d_input_ids / d_attention_mask: int64 [B, L] on device (the tokenizer
  * collator's output, data_collator.py:177-190).  d_out: fp32 [B, hidden].    */
 int sr_encode_dense(sr_model* m, const int64_t* d_input_ids, const int64_t* d_attention_mask,

@@ -344,10 +344,11 @@ __global__ __launch_bounds__(256) void rmsnorm_split_kernel(float* __restrict__ 
 }
 
 // ---- fp16-plane regime (cfg.fp32_planes == SR_FP32_PLANES_F16): rows scaled by a power of two, two fp16 planes ----
-// weights: dst[row_map(r)] = [g0 | g1 | g0] (kernels.h split_map_w), w_inv[row_map(r)] = 1 / scale of that row
+// weights: dst[row_map(r)] = [g0 | g1 | g0] (kernels.h split_map_w), w_inv[row_map(r)] = 1 / scale of that row; *lo_nz = 1 if
+// any g1 of the row is nonzero (sr_model_finalize drops the all-zero g1 segment of a matrix, see pack_f16_weights)
 __global__ __launch_bounds__(256) void convert_rows_split_h_kernel(const void* __restrict__ src, int src_dtype, int64_t rows, int64_t cols,
                                                                    bf16_t* __restrict__ dst, float* __restrict__ w_inv,
-                                                                   int64_t dst_row_base, int interleave) {
+                                                                   int64_t dst_row_base, int interleave, int* __restrict__ lo_nz) {
     __shared__ float red[4];
     const int64_t r = blockIdx.x;
     int64_t dr = r;
@@ -366,20 +367,37 @@ __global__ __launch_bounds__(256) void convert_rows_split_h_kernel(const void* _
     const float sc = row_scale_pow2(mx);
     if (threadIdx.x == 0) w_inv[dr] = 1.0f / sc;
     bf16_t* drow = dst + dr * cols * 3;
+    bool nz = false;
     for (int64_t c = threadIdx.x; c < cols; c += 256) {
         unsigned short f0, f1;
         split_f16x2(at(c) * sc, f0, f1);
         drow[c] = f0; drow[cols + c] = f1; drow[2 * cols + c] = f0;
+        nz |= (f1 & 0x7fff) != 0;
+    }
+    if (nz) *lo_nz = 1;
+}
+
+// [N, 3K] = [g0 | g1 | g0] with g1 all zero -> [N, 2K] = [g0 | g0]: one workgroup per row, 16 bytes per lane and store
+__global__ __launch_bounds__(256) void pack_rows_2seg_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int64_t K) {
+    const int64_t r = blockIdx.x;
+    const uint4* s0 = reinterpret_cast<const uint4*>(src + r * 3 * K);
+    uint4* d = reinterpret_cast<uint4*>(dst + r * 2 * K);
+    const int64_t kv = K / 8;
+    for (int64_t i = threadIdx.x; i < kv; i += 256) {
+        const uint4 v = s0[i];
+        d[i] = v;
+        d[kv + i] = v;
     }
 }
 
-// activations: one wave per row of src fp32 [T, K] -> [f1 | f0 | f0] (split_map_a) + a_inv[t]; with w: the RMSNorm of the row
+// activations: one wave per row of src fp32 [T, K] -> [f1 | f0 | f0] (split_map_a; nseg = 3) or [f1 | f0] (nseg = 2: the consumer's
+// weights have an all-zero g1 segment) + a_inv[t]; with w: the RMSNorm of the row
 // first (x = embed[tok] if embed; y = (x * rsqrt(mean(x^2) + eps)) * w), i.e. rmsnorm_split_kernel on fp16 planes
 __global__ __launch_bounds__(256) void rows_split_h_kernel(float* __restrict__ x, const float* __restrict__ embed,
                                                            const int* __restrict__ tok_id, const float* __restrict__ w,
                                                            bf16_t* __restrict__ xs, float* __restrict__ a_inv, int T, int K, float eps,
                                                            const float* __restrict__ gu_cmax, float* __restrict__ act_sc,
-                                                           float* __restrict__ act_inv) {
+                                                           float* __restrict__ act_inv, int nseg) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (t >= T) return;
@@ -416,7 +434,7 @@ __global__ __launch_bounds__(256) void rows_split_h_kernel(float* __restrict__ x
         const float osc = row_scale_pow2(s2 * *gu_cmax * 1.02f);
         if (lane == 0) { act_sc[t] = osc; act_inv[t] = 1.0f / osc; }
     }
-    bf16_t* orow = xs + (int64_t)t * K * 3;
+    bf16_t* orow = xs + (int64_t)t * K * nseg;
     for (int i = lane * 4; i < K; i += 256) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(src + i);
         f32x4 g = {1.f, 1.f, 1.f, 1.f};
@@ -430,7 +448,7 @@ __global__ __launch_bounds__(256) void rows_split_h_kernel(float* __restrict__ x
         }
         *reinterpret_cast<bf16x4*>(orow + i) = p1;
         *reinterpret_cast<bf16x4*>(orow + K + i) = p0;
-        *reinterpret_cast<bf16x4*>(orow + 2 * K + i) = p0;
+        if (nseg == 3) *reinterpret_cast<bf16x4*>(orow + 2 * K + i) = p0;
     }
 }
 
@@ -441,7 +459,7 @@ __global__ __launch_bounds__(256) void rows_split_h_reg_kernel(float* __restrict
                                                                const int* __restrict__ tok_id, const float* __restrict__ w,
                                                                bf16_t* __restrict__ xs, float* __restrict__ a_inv, int T, float eps,
                                                                const float* __restrict__ gu_cmax, float* __restrict__ act_sc,
-                                                               float* __restrict__ act_inv) {
+                                                               float* __restrict__ act_inv, int nseg) {
     constexpr int K = 256 * NV;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -485,7 +503,7 @@ __global__ __launch_bounds__(256) void rows_split_h_reg_kernel(float* __restrict
         const float osc = row_scale_pow2(s2 * *gu_cmax * 1.02f);
         if (lane == 0) { act_sc[t] = osc; act_inv[t] = 1.0f / osc; }
     }
-    bf16_t* orow = xs + (int64_t)t * K * 3;
+    bf16_t* orow = xs + (int64_t)t * K * nseg;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         bf16x4 p0, p1;
@@ -498,27 +516,29 @@ __global__ __launch_bounds__(256) void rows_split_h_reg_kernel(float* __restrict
         const int i = lane * 4 + 256 * j;
         *reinterpret_cast<bf16x4*>(orow + i) = p1;
         *reinterpret_cast<bf16x4*>(orow + K + i) = p0;
-        *reinterpret_cast<bf16x4*>(orow + 2 * K + i) = p0;
+        if (nseg == 3) *reinterpret_cast<bf16x4*>(orow + 2 * K + i) = p0;
     }
 }
 
-// gu_cmax (device float) / act_sc / act_inv: the row scales of the SwiGLU output this row will produce
+// nseg: the segment count of the consuming GEMM's weights (2 or 3); gu_cmax (device float) / act_sc / act_inv: the row scales of
+// the SwiGLU output this row will produce
 static void launch_rows_split_h(float* x, const float* embed, const int* tok, const float* w, bf16_t* xs, float* inv, int T, int K,
-                                float eps, hipStream_t s, const float* gu_cmax = nullptr, float* act_sc = nullptr,
+                                float eps, int nseg, hipStream_t s, const float* gu_cmax = nullptr, float* act_sc = nullptr,
                                 float* act_inv = nullptr) {
     const dim3 grid((unsigned)ceil_div64(T, 4)), block(256);
     switch (K) {
-        case 2048: hipLaunchKernelGGL(rows_split_h_reg_kernel<8>, grid, block, 0, s, x, embed, tok, w, xs, inv, T, eps, gu_cmax, act_sc, act_inv); break;
-        case 4096: hipLaunchKernelGGL(rows_split_h_reg_kernel<16>, grid, block, 0, s, x, embed, tok, w, xs, inv, T, eps, gu_cmax, act_sc, act_inv); break;
-        case 8192: hipLaunchKernelGGL(rows_split_h_reg_kernel<32>, grid, block, 0, s, x, embed, tok, w, xs, inv, T, eps, gu_cmax, act_sc, act_inv); break;
-        default: hipLaunchKernelGGL(rows_split_h_kernel, grid, block, 0, s, x, embed, tok, w, xs, inv, T, K, eps, gu_cmax, act_sc, act_inv);
+        case 2048: hipLaunchKernelGGL(rows_split_h_reg_kernel<8>, grid, block, 0, s, x, embed, tok, w, xs, inv, T, eps, gu_cmax, act_sc, act_inv, nseg); break;
+        case 4096: hipLaunchKernelGGL(rows_split_h_reg_kernel<16>, grid, block, 0, s, x, embed, tok, w, xs, inv, T, eps, gu_cmax, act_sc, act_inv, nseg); break;
+        case 8192: hipLaunchKernelGGL(rows_split_h_reg_kernel<32>, grid, block, 0, s, x, embed, tok, w, xs, inv, T, eps, gu_cmax, act_sc, act_inv, nseg); break;
+        default: hipLaunchKernelGGL(rows_split_h_kernel, grid, block, 0, s, x, embed, tok, w, xs, inv, T, K, eps, gu_cmax, act_sc, act_inv, nseg);
     }
 }
 
-// max over the MLP's feature pairs j of |w_gate_j| |w_up_j|, from the fp16 plane segments [w0 | w1 | w0] of the interleaved
-// gate/up matrix (gate rows and up rows alternate in 16-row blocks) and the rows' inverse scales: one wave per pair
+// max over the MLP's feature pairs j of |w_gate_j| |w_up_j|, from the fp16 plane segments [w0 | w1 | w0] (nseg = 3) or [w0 | w0]
+// (nseg = 2, w1 = 0) of the interleaved gate/up matrix (gate rows and up rows alternate in 16-row blocks) and the rows' inverse
+// scales: one wave per pair
 __global__ __launch_bounds__(256) void gu_cmax_kernel(const bf16_t* __restrict__ wgu_s, const float* __restrict__ wgu_i, int I, int K,
-                                                      float* __restrict__ cmax) {
+                                                      int nseg, float* __restrict__ cmax) {
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (j >= I) return;
@@ -526,10 +546,11 @@ __global__ __launch_bounds__(256) void gu_cmax_kernel(const bf16_t* __restrict__
     float n2[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const bf16_t* row = wgu_s + (h ? ru : rg) * 3 * (int64_t)K;
+        const bf16_t* row = wgu_s + (h ? ru : rg) * nseg * (int64_t)K;
         float ss = 0.f;
         for (int i = lane; i < K; i += 64) {
-            const float v = (float)__builtin_bit_cast(_Float16, row[i]) + (float)__builtin_bit_cast(_Float16, row[K + i]);
+            const float v = (float)__builtin_bit_cast(_Float16, row[i]) +
+                            (nseg == 3 ? (float)__builtin_bit_cast(_Float16, row[K + i]) : 0.f);
             ss += v * v;
         }
         for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
@@ -608,6 +629,9 @@ struct LayerW {
     // fp16-plane regime: inverse power-of-two scale of every weight row
     float *wqkv_i = nullptr, *wo_i = nullptr, *wgu_i = nullptr, *wdown_i = nullptr;
     float* gu_cmax = nullptr;   // fp16-plane regime: max_j |w_gate_j||w_up_j| (device float), see gu_cmax_kernel
+    // fp16-plane regime: K segments of wqkv_s, wo_s, wgu_s, wdown_s - 3 = [g0 | g1 | g0], 2 = [g0 | g0] (g1 all zero, dropped by
+    // sr_model_finalize); the activations feeding each GEMM are split to the same count
+    int qkv_seg = 3, o_seg = 3, gu_seg = 3, down_seg = 3;
 };
 
 struct sr_model {
@@ -618,6 +642,9 @@ struct sr_model {
     bf16_t* lm_head = nullptr; // bf16 [V, H] (sparse head)
     bf16_t* lm_head_s = nullptr;   // fp32 regime: [V, n_seg * H] plane segments
     float* lm_head_i = nullptr;    // fp16-plane regime: [V] inverse row scales
+    int lm_head_seg = 3;           // fp16-plane regime: K segments of lm_head_s (see LayerW::qkv_seg)
+    int* lo_nz = nullptr;          // fp16-plane regime: [4 num_layers + 1] device flags, 1 = the matrix has a nonzero g1 plane
+                                   // (layer l: 4 l + 0 qkv, 1 o, 2 gate-up, 3 down; 4 num_layers: lm_head)
     float *attn_f = nullptr, *act_f = nullptr;                  // fp16-plane regime: fp32 attention / SwiGLU outputs before the row split
     float *xs_i = nullptr, *attn_i = nullptr, *act_i = nullptr; // ... and the inverse row scales of xs / attn_s / act_s
     float* act_sc = nullptr;                                     // forward row scales of the fused SwiGLU split
@@ -651,7 +678,7 @@ static void model_free(sr_model* m) {
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(m->embed); F(m->lm_head); F(m->norm_w); F(m->rope_cos); F(m->rope_sin);
     F(m->lm_head_s); F(m->xs); F(m->qkv_f); F(m->attn_s); F(m->act_s);
-    F(m->lm_head_i); F(m->attn_f); F(m->act_f); F(m->xs_i); F(m->attn_i); F(m->act_i); F(m->act_sc);
+    F(m->lm_head_i); F(m->lo_nz); F(m->attn_f); F(m->act_f); F(m->xs_i); F(m->attn_i); F(m->act_i); F(m->act_sc);
     for (auto& l : m->layers) {
         F(l.wqkv); F(l.wo); F(l.wgu); F(l.wdown); F(l.ln1); F(l.ln2); F(l.wqkv_s); F(l.wo_s); F(l.wgu_s); F(l.wdown_s);
         F(l.wqkv_i); F(l.wo_i); F(l.wgu_i); F(l.wdown_i); F(l.gu_cmax);
@@ -732,6 +759,10 @@ extern "C" int sr_model_create(sr_model** out, const sr_model_config* cfg) {
     const bool f16p = c.fp32_planes == SR_FP32_PLANES_F16;
     if (c.has_lm_head && nsg) SR_ALLOC(m->lm_head_s, V * H * 2 * nsg);
     if (c.has_lm_head && f16p) SR_ALLOC(m->lm_head_i, V * 4);
+    if (f16p) {
+        SR_ALLOC(m->lo_nz, (4 * (int64_t)c.num_layers + 1) * 4);
+        (void)hipMemset(m->lo_nz, 0, (size_t)(4 * c.num_layers + 1) * 4);
+    }
     SR_ALLOC(m->norm_w, H * 4);
     for (auto& l : m->layers) {
         SR_ALLOC(l.wqkv, (nq + 2 * nkv) * H * 2);
@@ -803,12 +834,13 @@ extern "C" int sr_model_destroy(sr_model* m) {
 }
 
 static int convert_rows(const void* src, int dtype, int64_t rows, int64_t cols, bf16_t* dbf, float* df32, int64_t base,
-                        int interleave, hipStream_t s, bf16_t* dsplit = nullptr, int planes = 0, float* w_inv = nullptr) {
+                        int interleave, hipStream_t s, bf16_t* dsplit = nullptr, int planes = 0, float* w_inv = nullptr,
+                        int* lo_nz = nullptr) {
     hipLaunchKernelGGL(convert_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, src, dtype, rows, cols, dbf, df32, base,
                        interleave);
     if (dsplit && planes == SR_FP32_PLANES_F16)
         hipLaunchKernelGGL(convert_rows_split_h_kernel, dim3((unsigned)rows), dim3(256), 0, s, src, dtype, rows, cols, dsplit, w_inv, base,
-                           interleave);
+                           interleave, lo_nz);
     else if (dsplit && planes)
         hipLaunchKernelGGL(convert_rows_split_kernel, dim3((unsigned)rows), dim3(256), 0, s, src, dtype, rows, cols, dsplit, base,
                            interleave, split_map_w(planes));
@@ -822,8 +854,13 @@ extern "C" int sr_model_set_weight(sr_model* m, const char* name, const void* d_
     SR_REQUIRE(dtype == SR_DTYPE_F32 || dtype == SR_DTYPE_BF16, "sr_model_set_weight: dtype %d not supported", dtype);
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(m->mu);
+    // finalize fixes the plane layout of every matrix (pack_f16_weights): a later weight would not fit it
+    SR_REQUIRE(!m->finalized, "sr_model_set_weight: the model is already finalized; weights are fixed from then on");
     const sr_model_config& c = m->cfg;
     const int64_t H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size;
+    int* const lo_nz = m->lo_nz;     // null outside the fp16-plane regime
+    auto lo_flag = [&](int64_t i) { return lo_nz ? lo_nz + i : nullptr; };
+    const int64_t lo_lm = 4 * (int64_t)c.num_layers;
     const int64_t nq = (int64_t)c.num_heads * c.head_dim, nkv = (int64_t)c.num_kv_heads * c.head_dim;
     std::string n(name);
     auto shape_is = [&](int64_t r, int64_t cc) { return rows == r && cols == cc; };
@@ -831,7 +868,8 @@ extern "C" int sr_model_set_weight(sr_model* m, const char* name, const void* d_
     if (n == "model.embed_tokens.weight") {
         SHAPE_REQ(V, H);
         SR_TRY(convert_rows(d_ptr, dtype, V, H, (c.has_lm_head && c.tie_word_embeddings) ? m->lm_head : nullptr, m->embed, 0, 0, s,
-                            (c.has_lm_head && c.tie_word_embeddings) ? m->lm_head_s : nullptr, c.fp32_planes, m->lm_head_i));
+                            (c.has_lm_head && c.tie_word_embeddings) ? m->lm_head_s : nullptr, c.fp32_planes, m->lm_head_i,
+                            lo_flag(lo_lm)));
         m->have_embed = true;
         if (c.has_lm_head && c.tie_word_embeddings) m->have_lm_head = true;
         return SR_OK;
@@ -839,7 +877,7 @@ extern "C" int sr_model_set_weight(sr_model* m, const char* name, const void* d_
     if (n == "lm_head.weight") {
         SR_REQUIRE(c.has_lm_head, "sr_model_set_weight: model was created without an lm_head");
         SHAPE_REQ(V, H);
-        SR_TRY(convert_rows(d_ptr, dtype, V, H, m->lm_head, nullptr, 0, 0, s, m->lm_head_s, c.fp32_planes, m->lm_head_i));
+        SR_TRY(convert_rows(d_ptr, dtype, V, H, m->lm_head, nullptr, 0, 0, s, m->lm_head_s, c.fp32_planes, m->lm_head_i, lo_flag(lo_lm)));
         m->have_lm_head = true;
         return SR_OK;
     }
@@ -854,18 +892,41 @@ extern "C" int sr_model_set_weight(sr_model* m, const char* name, const void* d_
     if (sscanf(name, "model.layers.%d.%127s", &li, rest) == 2 && li >= 0 && li < c.num_layers) {
         LayerW& l = m->layers[li];
         std::string r(rest);
-        if (r == "self_attn.q_proj.weight") { SHAPE_REQ(nq, H); SR_TRY(convert_rows(d_ptr, dtype, nq, H, l.wqkv, nullptr, 0, 0, s, l.wqkv_s, c.fp32_planes, l.wqkv_i)); l.have |= 1; return SR_OK; }
-        if (r == "self_attn.k_proj.weight") { SHAPE_REQ(nkv, H); SR_TRY(convert_rows(d_ptr, dtype, nkv, H, l.wqkv, nullptr, nq, 0, s, l.wqkv_s, c.fp32_planes, l.wqkv_i)); l.have |= 2; return SR_OK; }
-        if (r == "self_attn.v_proj.weight") { SHAPE_REQ(nkv, H); SR_TRY(convert_rows(d_ptr, dtype, nkv, H, l.wqkv, nullptr, nq + nkv, 0, s, l.wqkv_s, c.fp32_planes, l.wqkv_i)); l.have |= 4; return SR_OK; }
-        if (r == "self_attn.o_proj.weight") { SHAPE_REQ(H, nq); SR_TRY(convert_rows(d_ptr, dtype, H, nq, l.wo, nullptr, 0, 0, s, l.wo_s, c.fp32_planes, l.wo_i)); l.have |= 8; return SR_OK; }
-        if (r == "mlp.gate_proj.weight") { SHAPE_REQ(I, H); SR_TRY(convert_rows(d_ptr, dtype, I, H, l.wgu, nullptr, 0, 1, s, l.wgu_s, c.fp32_planes, l.wgu_i)); l.have |= 16; return SR_OK; }
-        if (r == "mlp.up_proj.weight") { SHAPE_REQ(I, H); SR_TRY(convert_rows(d_ptr, dtype, I, H, l.wgu, nullptr, 0, 2, s, l.wgu_s, c.fp32_planes, l.wgu_i)); l.have |= 32; return SR_OK; }
-        if (r == "mlp.down_proj.weight") { SHAPE_REQ(H, I); SR_TRY(convert_rows(d_ptr, dtype, H, I, l.wdown, nullptr, 0, 0, s, l.wdown_s, c.fp32_planes, l.wdown_i)); l.have |= 64; return SR_OK; }
+        if (r == "self_attn.q_proj.weight") { SHAPE_REQ(nq, H); SR_TRY(convert_rows(d_ptr, dtype, nq, H, l.wqkv, nullptr, 0, 0, s, l.wqkv_s, c.fp32_planes, l.wqkv_i, lo_flag(4 * li + 0))); l.have |= 1; return SR_OK; }
+        if (r == "self_attn.k_proj.weight") { SHAPE_REQ(nkv, H); SR_TRY(convert_rows(d_ptr, dtype, nkv, H, l.wqkv, nullptr, nq, 0, s, l.wqkv_s, c.fp32_planes, l.wqkv_i, lo_flag(4 * li + 0))); l.have |= 2; return SR_OK; }
+        if (r == "self_attn.v_proj.weight") { SHAPE_REQ(nkv, H); SR_TRY(convert_rows(d_ptr, dtype, nkv, H, l.wqkv, nullptr, nq + nkv, 0, s, l.wqkv_s, c.fp32_planes, l.wqkv_i, lo_flag(4 * li + 0))); l.have |= 4; return SR_OK; }
+        if (r == "self_attn.o_proj.weight") { SHAPE_REQ(H, nq); SR_TRY(convert_rows(d_ptr, dtype, H, nq, l.wo, nullptr, 0, 0, s, l.wo_s, c.fp32_planes, l.wo_i, lo_flag(4 * li + 1))); l.have |= 8; return SR_OK; }
+        if (r == "mlp.gate_proj.weight") { SHAPE_REQ(I, H); SR_TRY(convert_rows(d_ptr, dtype, I, H, l.wgu, nullptr, 0, 1, s, l.wgu_s, c.fp32_planes, l.wgu_i, lo_flag(4 * li + 2))); l.have |= 16; return SR_OK; }
+        if (r == "mlp.up_proj.weight") { SHAPE_REQ(I, H); SR_TRY(convert_rows(d_ptr, dtype, I, H, l.wgu, nullptr, 0, 2, s, l.wgu_s, c.fp32_planes, l.wgu_i, lo_flag(4 * li + 2))); l.have |= 32; return SR_OK; }
+        if (r == "mlp.down_proj.weight") { SHAPE_REQ(H, I); SR_TRY(convert_rows(d_ptr, dtype, H, I, l.wdown, nullptr, 0, 0, s, l.wdown_s, c.fp32_planes, l.wdown_i, lo_flag(4 * li + 3))); l.have |= 64; return SR_OK; }
         if (r == "input_layernorm.weight") { SHAPE_REQ(H, 1); SR_TRY(convert_rows(d_ptr, dtype, H, 1, nullptr, l.ln1, 0, 0, s)); l.have |= 128; return SR_OK; }
         if (r == "post_attention_layernorm.weight") { SHAPE_REQ(H, 1); SR_TRY(convert_rows(d_ptr, dtype, H, 1, nullptr, l.ln2, 0, 0, s)); l.have |= 256; return SR_OK; }
     }
     sr_set_error("sr_model_set_weight: unknown tensor name '%s'", name);
     return SR_ERR_INVALID;
+}
+
+// fp16-plane regime: a matrix whose g1 plane is all zero (bf16-valued weights: 8 significand bits always fit the fp16 plane g0
+// of their power-of-two scaled row, unless they lie ~2^-31 below the row maximum) is re-packed from [N, 3K] = [g0 | g1 | g0] to
+// [N, 2K] = [g0 | g0], out of place.  The GEMM's middle product f0 . g1 only added exact zeros to the fp32 accumulators (an MFMA
+// does not flush its C input), so the 2-segment GEMM - same k order for what remains - gives the same bits with 2/3 of the work.
+static int pack_f16_weights(bf16_t*& w, int& nseg, bool lo_nz, int64_t rows, int64_t K) {
+    if (nseg == 2 || lo_nz) return SR_OK;
+    bf16_t* p = nullptr;
+    SR_CHECK_HIP(hipMalloc((void**)&p, (size_t)(rows * 2 * K * 2)));
+    hipLaunchKernelGGL(pack_rows_2seg_kernel, dim3((unsigned)rows), dim3(256), 0, nullptr, w, p, K);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        sr_set_error("sr_model_finalize: re-packing a [%lld, %lld] weight matrix failed: %s", (long long)rows, (long long)K,
+                     hipGetErrorString(e));
+        return SR_ERR_HIP;
+    }
+    SR_CHECK_HIP(hipFree(w));
+    w = p;
+    nseg = 2;
+    return SR_OK;
 }
 
 extern "C" int sr_model_finalize(sr_model* m) {
@@ -878,18 +939,54 @@ extern "C" int sr_model_finalize(sr_model* m) {
     // sr_model_set_weight converted the planes on the CALLER's streams; a non-blocking stream does not order with the null
     // stream the reduction below runs on, and a cmax read from half-written planes would let EPI_SWIGLU_SPLIT_H overflow fp16
     SR_CHECK_HIP(hipDeviceSynchronize());
-    if (m->cfg.fp32_planes == SR_FP32_PLANES_F16) {      // row bound of every layer's SwiGLU output (EPI_SWIGLU_SPLIT_H)
-        for (int i = 0; i < m->cfg.num_layers; ++i) {
+    if (m->cfg.fp32_planes == SR_FP32_PLANES_F16) {
+        const sr_model_config& c = m->cfg;
+        const int64_t H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size;
+        const int64_t nq = (int64_t)c.num_heads * c.head_dim, nkv = (int64_t)c.num_kv_heads * c.head_dim;
+        std::vector<int> nz((size_t)(4 * c.num_layers + 1));
+        SR_CHECK_HIP(hipMemcpy(nz.data(), m->lo_nz, nz.size() * 4, hipMemcpyDeviceToHost));
+        // dev switch SR_F16_WEIGHT_SEGS=3: keep [g0 | g1 | g0] everywhere (A/B, and the reference of the bit-identity tests)
+        const char* env_seg = sr_dev_getenv("SR_F16_WEIGHT_SEGS");
+        if (!(env_seg && *env_seg == '3')) {
+            for (int i = 0; i < c.num_layers; ++i) {
+                LayerW& l = m->layers[i];
+                SR_TRY(pack_f16_weights(l.wqkv_s, l.qkv_seg, nz[4 * i + 0] != 0, nq + 2 * nkv, H));
+                SR_TRY(pack_f16_weights(l.wo_s, l.o_seg, nz[4 * i + 1] != 0, H, nq));
+                SR_TRY(pack_f16_weights(l.wgu_s, l.gu_seg, nz[4 * i + 2] != 0, 2 * I, H));
+                SR_TRY(pack_f16_weights(l.wdown_s, l.down_seg, nz[4 * i + 3] != 0, H, I));
+            }
+            if (c.has_lm_head) SR_TRY(pack_f16_weights(m->lm_head_s, m->lm_head_seg, nz[4 * c.num_layers] != 0, V, H));
+        }
+        // row bound of every layer's SwiGLU output (EPI_SWIGLU_SPLIT_H)
+        for (int i = 0; i < c.num_layers; ++i) {
             LayerW& l = m->layers[i];
             if (!l.gu_cmax) SR_CHECK_HIP(hipMalloc((void**)&l.gu_cmax, 4));
             SR_CHECK_HIP(hipMemsetAsync(l.gu_cmax, 0, 4, nullptr));
-            hipLaunchKernelGGL(gu_cmax_kernel, dim3((unsigned)ceil_div64(m->cfg.intermediate_size, 4)), dim3(256), 0, nullptr, l.wgu_s, l.wgu_i,
-                               m->cfg.intermediate_size, m->cfg.hidden_size, l.gu_cmax);
+            hipLaunchKernelGGL(gu_cmax_kernel, dim3((unsigned)ceil_div64(I, 4)), dim3(256), 0, nullptr, l.wgu_s, l.wgu_i, (int)I, (int)H,
+                               l.gu_seg, l.gu_cmax);
         }
         SR_CHECK_LAUNCH();
     }
     SR_CHECK_HIP(hipDeviceSynchronize());
     m->finalized = true;
+    return SR_OK;
+}
+
+extern "C" int sr_model_weight_segments(sr_model* m, int32_t* out, int64_t capacity, int64_t* n) {
+    SR_REQUIRE(m && n, "sr_model_weight_segments: null argument");
+    SR_REQUIRE(m->finalized, "sr_model_weight_segments: sr_model_finalize was not called");
+    const sr_model_config& c = m->cfg;
+    std::vector<int32_t> v;
+    const bool f16p = c.fp32_planes == SR_FP32_PLANES_F16;
+    const int32_t plain = c.fp32_planes ? split_map_w(c.fp32_planes).n_seg : 0;
+    for (const LayerW& l : m->layers) {
+        v.push_back(f16p ? l.qkv_seg : plain); v.push_back(f16p ? l.o_seg : plain);
+        v.push_back(f16p ? l.gu_seg : plain); v.push_back(f16p ? l.down_seg : plain);
+    }
+    if (c.has_lm_head) v.push_back(f16p ? m->lm_head_seg : plain);
+    *n = (int64_t)v.size();
+    SR_REQUIRE(capacity >= 0 && (capacity == 0 || out), "sr_model_weight_segments: bad output buffer");
+    for (int64_t i = 0; i < capacity && i < (int64_t)v.size(); ++i) out[i] = v[(size_t)i];
     return SR_OK;
 }
 
@@ -973,18 +1070,20 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
 
     if (prec == PREC_FP32 && c.fp32_planes == SR_FP32_PLANES_F16) {
         // fp16 planes: every GEMM input is split by ONE kernel that sees whole rows (norm + split, or split of an fp32
-        // buffer), because the power-of-two scale is per row; 3 plane products per GEMM
-        auto split_rows = [&](float* src, const float* embed, const int* tok, const float* w, bf16_t* dst, float* inv, int K) {
-            launch_rows_split_h(src, embed, tok, w, dst, inv, T, K, c.rms_norm_eps, s);
+        // buffer), because the power-of-two scale is per row; 3 plane products per GEMM, 2 where the weights' g1 plane is zero
+        // (the split writes the segment count of its consumer's weights, K' = nseg K)
+        auto split_rows = [&](float* src, const float* embed, const int* tok, const float* w, bf16_t* dst, float* inv, int K, int nseg) {
+            launch_rows_split_h(src, embed, tok, w, dst, inv, T, K, c.rms_norm_eps, nseg, s);
         };
         // dev switch SR_FP32_FUSED_ACT=0: SwiGLU output as fp32 + a separate row-split pass (A/B, and the reference of the test)
         const char* env_fa = sr_dev_getenv("SR_FP32_FUSED_ACT");
         const bool fused_act = m->layers[0].gu_cmax && !(env_fa && *env_fa == '0');
         for (int li = 0; li < c.num_layers; ++li) {
             LayerW& l = m->layers[li];
-            split_rows(m->x, li == 0 ? m->embed : (const float*)nullptr, li == 0 ? m->tok_id : (const int*)nullptr, l.ln1, m->xs, m->xs_i, H);
+            split_rows(m->x, li == 0 ? m->embed : (const float*)nullptr, li == 0 ? m->tok_id : (const int*)nullptr, l.ln1, m->xs, m->xs_i, H,
+                       l.qkv_seg);
             GemmArgs g{};
-            g.A = m->xs; g.W = l.wqkv_s; g.M = T; g.N = nq + 2 * nkv; g.K = 3 * H; g.C = m->qkv_f; g.a_scale = m->xs_i; g.w_scale = l.wqkv_i;
+            g.A = m->xs; g.W = l.wqkv_s; g.M = T; g.N = nq + 2 * nkv; g.K = l.qkv_seg * H; g.C = m->qkv_f; g.a_scale = m->xs_i; g.w_scale = l.wqkv_i;
             g.pos = m->pos; g.rope_cos = m->rope_cos; g.rope_sin = m->rope_sin; g.n_rope = nq + nkv; g.head_dim = c.head_dim;
             SR_TRY(launch_gemm_bf16(EPI_QKV_ROPE_F32_H, g, s));
             AttnF32Args a{};
@@ -992,27 +1091,28 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
             a.B = B; a.nh = c.num_heads; a.nkv = c.num_kv_heads; a.hd = c.head_dim;
             a.scale = 1.0f / sqrtf((float)c.head_dim); a.max_seqlen = max_len;
             SR_TRY(launch_attention_f32(a, s));
-            split_rows(m->attn_f, nullptr, nullptr, nullptr, m->attn_s, m->attn_i, nq);
+            split_rows(m->attn_f, nullptr, nullptr, nullptr, m->attn_s, m->attn_i, nq, l.o_seg);
             g = GemmArgs{};
-            g.A = m->attn_s; g.W = l.wo_s; g.M = T; g.N = H; g.K = 3 * nq; g.C = m->x; g.a_scale = m->attn_i; g.w_scale = l.wo_i;
+            g.A = m->attn_s; g.W = l.wo_s; g.M = T; g.N = H; g.K = l.o_seg * nq; g.C = m->x; g.a_scale = m->attn_i; g.w_scale = l.wo_i;
             SR_TRY(launch_gemm_bf16(EPI_RESID_F32_H, g, s));
             if (fused_act) {
                 // the norm kernel also fixes the scale of the row's SwiGLU output (a rigorous bound, no overflow), so the
                 // gate-up GEMM writes the down_proj's fp16 plane segments itself: no fp32 intermediate, no split pass
-                launch_rows_split_h(m->x, nullptr, nullptr, l.ln2, m->xs, m->xs_i, T, H, c.rms_norm_eps, s, l.gu_cmax, m->act_sc, m->act_i);
+                launch_rows_split_h(m->x, nullptr, nullptr, l.ln2, m->xs, m->xs_i, T, H, c.rms_norm_eps, l.gu_seg, s, l.gu_cmax, m->act_sc,
+                                    m->act_i);
                 g = GemmArgs{};
-                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = 3 * H; g.C = m->act_s; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
-                g.out_scale = m->act_sc;
+                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = l.gu_seg * H; g.C = m->act_s; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
+                g.out_scale = m->act_sc; g.out_nseg = l.down_seg;
                 SR_TRY(launch_gemm_bf16(EPI_SWIGLU_SPLIT_H, g, s));
             } else {
-                split_rows(m->x, nullptr, nullptr, l.ln2, m->xs, m->xs_i, H);
+                split_rows(m->x, nullptr, nullptr, l.ln2, m->xs, m->xs_i, H, l.gu_seg);
                 g = GemmArgs{};
-                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = 3 * H; g.C = m->act_f; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
+                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = l.gu_seg * H; g.C = m->act_f; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
                 SR_TRY(launch_gemm_bf16(EPI_SWIGLU_F32_H, g, s));
-                split_rows(m->act_f, nullptr, nullptr, nullptr, m->act_s, m->act_i, I);
+                split_rows(m->act_f, nullptr, nullptr, nullptr, m->act_s, m->act_i, I, l.down_seg);
             }
             g = GemmArgs{};
-            g.A = m->act_s; g.W = l.wdown_s; g.M = T; g.N = H; g.K = 3 * I; g.C = m->x; g.a_scale = m->act_i; g.w_scale = l.wdown_i;
+            g.A = m->act_s; g.W = l.wdown_s; g.M = T; g.N = H; g.K = l.down_seg * I; g.C = m->x; g.a_scale = m->act_i; g.w_scale = l.wdown_i;
             SR_TRY(launch_gemm_bf16(EPI_RESID_F32_H, g, s));
         }
         SR_CHECK_LAUNCH();
@@ -1112,8 +1212,8 @@ static int head_sparse(sr_model* m, int B, int T, int prec, float* d_out, hipStr
     GemmEpilogue epi = EPI_SEGMAX;
     if (prec == PREC_FP32 && m->cfg.fp32_planes == SR_FP32_PLANES_F16) {
         launch_rows_split_h(m->x, (const float*)nullptr, (const int*)nullptr, (const float*)m->norm_w, m->xs, m->xs_i, T, H,
-                            m->cfg.rms_norm_eps, s);
-        g.A = m->xs; g.W = m->lm_head_s; g.K = 3 * H; g.a_scale = m->xs_i; g.w_scale = m->lm_head_i;
+                            m->cfg.rms_norm_eps, m->lm_head_seg, s);
+        g.A = m->xs; g.W = m->lm_head_s; g.K = m->lm_head_seg * H; g.a_scale = m->xs_i; g.w_scale = m->lm_head_i;
         epi = EPI_SEGMAX_H;
     } else if (prec == PREC_FP32) {
         const SplitMap ma = split_map_a(m->cfg.fp32_planes);

@@ -750,11 +750,12 @@ void gemm_bf16_kernel(GemmArgs g) {
             }
         }
     } else if constexpr (KL == 1 && BEPI == EPI_SWIGLU_SPLITH_BASE) {
-        // fp32 regime, SwiGLU output as fp16 plane segments [f1 | f0 | f0] (see the direct-store version below), staged: a token
-        // row of this wave is 64 output features = 128 B per plane; a buffer holds 16 rows x (f1 | f0) = 4 KB
+        // fp32 regime, SwiGLU output as fp16 plane segments [f1 | f0 | f0] or [f1 | f0] (see the direct-store version below),
+        // staged: a token row of this wave is 64 output features = 128 B per plane; a buffer holds 16 rows x (f1 | f0) = 4 KB
         unsigned char* const stg0 = smem + 2 * STAGE_BYTES + wave * 8192;
         const int half_n = g.N >> 1;
-        const int64_t ldc = 3 * (int64_t)half_n;
+        const bool seg3 = g.out_nseg == 3;
+        const int64_t ldc = (int64_t)g.out_nseg * half_n;
         const int nb = (n0 >> 1) + wn * 64;
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
@@ -788,8 +789,8 @@ void gemm_bf16_kernel(GemmArgs g) {
                     if (pl == 0) {
                         *reinterpret_cast<sr_i32x4*>(crow) = v;                    // f1
                     } else {
-                        *reinterpret_cast<sr_i32x4*>(crow + half_n) = v;           // f0, twice
-                        *reinterpret_cast<sr_i32x4*>(crow + 2 * half_n) = v;
+                        *reinterpret_cast<sr_i32x4*>(crow + half_n) = v;           // f0 (twice with 3 segments)
+                        if (seg3) *reinterpret_cast<sr_i32x4*>(crow + 2 * half_n) = v;
                     }
                 }
             }
@@ -906,10 +907,12 @@ void gemm_bf16_kernel(GemmArgs g) {
         }
     } else if constexpr (BEPI == EPI_SWIGLU_SPLITH_BASE) {
         // fp32 regime on fp16 planes: silu(gate) * up (accurate exp, true division), scaled by the row's power of two and
-        // stored as [f1 | f0 | f0]: the fp32 intermediate and its row-split pass (112 -> 48 bytes of traffic per token and
-        // feature) are gone.  out_scale[m] comes from the bound |silu(g) u| <= |xn|^2 max_j |wg_j||wu_j|: no overflow.
+        // stored as [f1 | f0 | f0] (out_nseg = 3) or [f1 | f0] (2): the fp32 intermediate and its row-split pass (112 -> 48
+        // bytes of traffic per token and feature) are gone.  out_scale[m] comes from the bound |silu(g) u| <= |xn|^2
+        // max_j |wg_j||wu_j|: no overflow.
         const int half_n = g.N >> 1;
-        const int64_t ldc = 3 * (int64_t)half_n;
+        const bool seg3 = g.out_nseg == 3;
+        const int64_t ldc = (int64_t)g.out_nseg * half_n;
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
             const int m = m0 + wm * MB * 16 + j * 16 + frow;
@@ -931,7 +934,7 @@ void gemm_bf16_kernel(GemmArgs g) {
                 bf16_t* crow = reinterpret_cast<bf16_t*>(g.C) + (int64_t)m * ldc + n;
                 *reinterpret_cast<bf16x4*>(crow) = p1;
                 *reinterpret_cast<bf16x4*>(crow + half_n) = p0;
-                *reinterpret_cast<bf16x4*>(crow + 2 * half_n) = p0;
+                if (seg3) *reinterpret_cast<bf16x4*>(crow + 2 * half_n) = p0;
             }
         }
     } else if constexpr (BEPI == EPI_SWIGLU_SPLIT) {
@@ -1182,7 +1185,7 @@ static GemmArgs rows_from(const GemmArgs& g, int row0) {
     t.A = g.A + (int64_t)row0 * g.K;
     t.M = g.M - row0;
     const int64_t ldc = (EPI == EPI_SWIGLU || EPI == EPI_SWIGLU_F32 || EPI == EPI_SWIGLU_F32_H)
-                            ? g.N / 2 : (EPI == EPI_SWIGLU_SPLIT ? (int64_t)g.out_map.n_seg * (g.N / 2) : (EPI == EPI_SWIGLU_SPLIT_H ? 3 * (int64_t)(g.N / 2) : g.N));
+                            ? g.N / 2 : (EPI == EPI_SWIGLU_SPLIT ? (int64_t)g.out_map.n_seg * (g.N / 2) : (EPI == EPI_SWIGLU_SPLIT_H ? (int64_t)g.out_nseg * (g.N / 2) : g.N));
     const int64_t esz = (EPI == EPI_STORE_F32 || EPI == EPI_RESID_F32 || EPI == EPI_QKV_ROPE_F32 || EPI == EPI_SWIGLU_F32 ||
                          (EPI >= EPI_H_FIRST && EPI != EPI_SWIGLU_SPLIT_H)) ? 4 : 2;
     if constexpr (EPI != EPI_SEGMAX && EPI != EPI_SEGMAX_H) t.C = reinterpret_cast<unsigned char*>(g.C) + (int64_t)row0 * ldc * esz;
@@ -1246,6 +1249,8 @@ int launch_gemm_bf16(GemmEpilogue epi, const GemmArgs& g, hipStream_t s) {
     SR_REQUIRE(g.K % G_BK == 0, "gemm: K=%d must be a multiple of %d", g.K, G_BK);
     const bool swiglu = epi == EPI_SWIGLU || epi == EPI_SWIGLU_SPLIT || epi == EPI_SWIGLU_F32 || epi == EPI_SWIGLU_F32_H || epi == EPI_SWIGLU_SPLIT_H;
     SR_REQUIRE(epi != EPI_SWIGLU_SPLIT_H || g.out_scale, "gemm(swiglu split, fp16 planes): missing output row scales");
+    SR_REQUIRE(epi != EPI_SWIGLU_SPLIT_H || g.out_nseg == 2 || g.out_nseg == 3, "gemm(swiglu split, fp16 planes): out_nseg %d is not 2 or 3",
+               g.out_nseg);
     SR_REQUIRE(g.N % 16 == 0 && (!swiglu || g.N % 32 == 0), "gemm: N=%d must be a multiple of 16 (32 for SwiGLU)", g.N);
     SR_REQUIRE(epi < EPI_H_FIRST || (g.a_scale && g.w_scale), "gemm(fp16 planes): missing row scales");
     SR_REQUIRE(epi != EPI_SWIGLU_SPLIT || (g.out_map.n_seg >= 1 && g.out_map.n_seg <= SR_MAX_SEG), "gemm(swiglu split): bad segment map");

@@ -381,6 +381,17 @@ class HipLlamaBackbone(torch.nn.Module):
                                                       _lib.stream_ptr()), "sr_model_last_hidden")
         return buf[:n.value]
 
+    def weight_segments(self):
+        """K segments of the fp32-regime GEMM weights (sr_model_weight_segments): a list of 4 per layer (qkv, o_proj, gate-up,
+        down_proj), then the lm_head's if the model has one.  fp16 planes: 2 where the low plane is all zero, else 3."""
+        if self._h is None:
+            raise _lib.SrHipError("the model has no engine yet (call .to(device) first)")
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.sr_model_weight_segments(self._h, None, 0, ctypes.byref(n)), "sr_model_weight_segments")
+        out = (ctypes.c_int32 * max(n.value, 1))()
+        _lib.check(self._lib.sr_model_weight_segments(self._h, out, n.value, ctypes.byref(n)), "sr_model_weight_segments")
+        return [int(v) for v in out[:n.value]]
+
     def __del__(self):
         try:
             if self._h is not None and self._lib is not None:
