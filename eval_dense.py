@@ -87,7 +87,7 @@ def write_doc_embeds(args):
     from scaling_retriever_amd.dataset.data_collator import LlamaDenseCollectionCollator
     from scaling_retriever_amd.dataset.dataset import CollectionDataset
     from scaling_retriever_amd.indexer import store_embs
-    from scaling_retriever_amd.modeling.llm_encoder import LlamaBiDense
+    from scaling_retriever_amd.modeling.llm_encoder import retriever_class
     from scaling_retriever_amd.utils.utils import is_first_worker
     if is_first_worker():
         os.makedirs(args.doc_embed_dir, exist_ok=True)
@@ -110,7 +110,7 @@ def write_doc_embeds(args):
         sampler = DistributedSampler(dataset, shuffle=False) if args.world_size > 1 else None
         loader = DataLoader(dataset, batch_size=args.eval_batch_size, shuffle=False, num_workers=1, sampler=sampler,
                             collate_fn=LlamaDenseCollectionCollator(tokenizer=tokenizer, max_length=args.doc_max_length))
-    model = LlamaBiDense.load_from_lora(args.model_name_or_path, access_token=args.access_token)
+    model = retriever_class(args.model_name_or_path, "dense").load_from_lora(args.model_name_or_path, access_token=args.access_token)
     model.to(args.local_rank)
     model.eval()
     # file names carry the rank (= LOCAL_RANK on the single node the reference runs on, eval_dense.py:188)
@@ -226,14 +226,14 @@ def retrieval(args):
     from scaling_retriever_amd.dataset.data_collator import LlamaDenseCollectionCollator
     from scaling_retriever_amd.dataset.dataset import MSMARCOQueryDataset
     from scaling_retriever_amd.distributed import gather_topk, sharded_dense_search
-    from scaling_retriever_amd.modeling.llm_encoder import LlamaBiDense
+    from scaling_retriever_amd.modeling.llm_encoder import retriever_class
     from scaling_retriever_amd.scoring import DenseIndexHIP, topk_merge
     from scaling_retriever_amd.utils.utils import obtain_doc_vec_dir_files
     rank, world = (dist.get_rank(), dist.get_world_size()) if args.world_size > 1 else (0, 1)
     device = torch.device("cuda", args.local_rank)
     if rank == 0:
         os.makedirs(args.out_dir, exist_ok=True)
-    model = LlamaBiDense.load_from_lora(args.model_name_or_path, access_token=args.access_token)
+    model = retriever_class(args.model_name_or_path, "dense").load_from_lora(args.model_name_or_path, access_token=args.access_token)
     model.to(device)
     model.eval()
     tokenizer = _tokenizer(args.model_name_or_path, args.access_token)

@@ -95,10 +95,10 @@ def _collection_dataset(args):
 def sparse_index(args):
     from scaling_retriever_amd.dataset.data_collator import LlamaSparseCollectionCollator
     from scaling_retriever_amd.indexer import SparseIndexer
-    from scaling_retriever_amd.modeling.llm_encoder import LlamaBiSparse
+    from scaling_retriever_amd.modeling.llm_encoder import retriever_class
     tokenizer = _tokenizer(args.model_name_or_path)
     collection = _collection_dataset(args)
-    model = LlamaBiSparse.load_from_lora(args.model_name_or_path)
+    model = retriever_class(args.model_name_or_path, "sparse").load_from_lora(args.model_name_or_path)
     if args.token_budget > 0:
         from scaling_retriever_amd.dataset.pipeline import TokenBudgetCollectionLoader
         loader = TokenBudgetCollectionLoader(collection, tokenizer, max_length=args.doc_max_length, max_tokens=args.token_budget,
@@ -120,10 +120,10 @@ def sparse_index(args):
 def sparse_retrieval(args):
     from scaling_retriever_amd.dataset.data_collator import LlamaSparseCollectionCollator
     from scaling_retriever_amd.indexer import SparseRetrieval
-    from scaling_retriever_amd.modeling.llm_encoder import LlamaBiSparse
+    from scaling_retriever_amd.modeling.llm_encoder import retriever_class
     tokenizer = _tokenizer(args.model_name_or_path)
     queries = _query_dataset(args)
-    model = LlamaBiSparse.load_from_lora(args.model_name_or_path)
+    model = retriever_class(args.model_name_or_path, "sparse").load_from_lora(args.model_name_or_path)
     collate = LlamaSparseCollectionCollator(tokenizer=tokenizer, max_length=args.query_max_length)
     os.makedirs(args.out_dir, exist_ok=True)
     config = {"index_dir": args.index_dir, "out_dir": args.out_dir}
@@ -160,7 +160,7 @@ def main(argv=None):
     if args.task_name not in ["evaluate_msmarco", "evaluate_beir"]:
         with open(os.path.join(args.model_name_or_path, "config.json")) as f:
             model_type = json.load(f).get("model_type", "llama")
-        assert model_type == "llama", model_type                   # the HIP path implements the Llama family only
+        assert model_type in ("llama", "qwen2"), model_type        # the HIP path implements the Llama and Qwen2 families
         ddp_setup(args)
     if args.task_name == "indexing":
         sparse_index(args)

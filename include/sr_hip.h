@@ -238,7 +238,10 @@ int sr_topk_merge(const float* d_scores, const int64_t* d_ids, int n_lists, int6
  * Replaces LlamaBiDense / LlamaBiSparse .encode / .query_encode / .doc_encode
  * (scaling_retriever/modeling/llm_encoder.py:66-70,186-196,424-443) and the
  * LlamaBiModel forward they call (modeling/bidirectional_llama.py:67-188 over
- * transformers' LlamaModel).                                                  */
+ * transformers' LlamaModel), and the same for Qwen2BiDense / Qwen2BiSparse
+ * (llm_encoder.py:204-209,528-533) over Qwen2BiModel (modeling/bidrectional_qwen2.py:68-101
+ * over transformers' Qwen2Model): a Llama layer whose q_proj / k_proj / v_proj carry a bias
+ * (attention_bias below).                                                     */
 typedef struct sr_model sr_model;
 
 typedef struct {
@@ -257,12 +260,17 @@ typedef struct {
                                          fp16 planes of power-of-two scaled rows (22 significand bits, 3 plane products
                                          per GEMM: truncation below the fp32 accumulation's own rounding); 3 = three bf16
                                          planes (24 bits, 6 products); 2 = two bf16 planes (3 products, ~2^-17)        */
+    int32_t attention_bias;           /* 1: q_proj / k_proj / v_proj carry a bias, added before the rotation (Qwen2:
+                                         modeling/bidrectional_qwen2.py:68-101, llm_encoder.py:204-209,528-533); the model then
+                                         needs model.layers.N.self_attn.{q,k,v}_proj.bias.  0 (Llama): those names are unknown */
 } sr_model_config;
 
 int sr_model_create(sr_model** out, const sr_model_config* cfg);
 /* Copies one checkpoint tensor (HF Llama naming, e.g.
  * "model.layers.3.self_attn.q_proj.weight") from device memory into the
- * model's internal layout.  dtype = SR_DTYPE_F32 or SR_DTYPE_BF16.           */
+ * model's internal layout.  dtype = SR_DTYPE_F32 or SR_DTYPE_BF16.  A 1-D tensor (norm weights, and with
+ * attention_bias = 1 the q / k / v biases) is passed as [rows, 1].  The fp32 regime adds a bias as it is, the
+ * autocast regime its bf16 rounding (autocast casts an nn.Linear's bias to bf16).                            */
 int sr_model_set_weight(sr_model* m, const char* name, const void* d_ptr, int dtype,
                         int64_t rows, int64_t cols, sr_stream stream);
 /* Verifies all tensors were provided and fixes the weights' layout: with fp32_planes = 16, a matrix whose low fp16 plane is
@@ -378,6 +386,12 @@ int sr_gemm_f16_scaled(const void* d_A, const void* d_W, int32_t M, int32_t N, i
 int sr_gemm_qkv_rope(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, void* d_C,
                      const int32_t* d_pos, const float* d_rope_cos, const float* d_rope_sin,
                      int32_t n_rope, int32_t head_dim, sr_stream stream);
+/* The same with a bias (Qwen2's q_proj / k_proj / v_proj, modeling/bidrectional_qwen2.py:68-101): d_bias fp32 [N], q rows then k
+ * rows then v rows like d_W, added to the fp32 accumulator before the rotation; NULL = no bias (then the bits of
+ * sr_gemm_qkv_rope).  fp32_out = 0: C bf16 [M,N]; 1: C fp32 [M,N], the epilogue of the fp32 regime's bf16-plane GEMM.      */
+int sr_gemm_qkv_rope_bias(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, void* d_C,
+                          const int32_t* d_pos, const float* d_rope_cos, const float* d_rope_sin,
+                          int32_t n_rope, int32_t head_dim, const float* d_bias, int32_t fp32_out, sr_stream stream);
 int sr_attention_varlen(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, const int32_t* d_pos,
                         const uint8_t* d_key_valid, const float* d_rope_cos, const float* d_rope_sin,
                         int32_t B, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim, sr_stream stream);

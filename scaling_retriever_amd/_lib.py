@@ -26,6 +26,7 @@ class SrModelConfig(ctypes.Structure):
         ("rope_factor", c_float), ("rope_low_freq_factor", c_float), ("rope_high_freq_factor", c_float),
         ("rope_original_max_pos", c_int32), ("tie_word_embeddings", c_int32), ("has_lm_head", c_int32),
         ("max_batch_tokens", c_int32), ("max_batch_seqs", c_int32), ("fp32_planes", c_int32),
+        ("attention_bias", c_int32),      # 1: q / k / v projections carry a bias (Qwen2); ctypes zero-fills it when not given
     ]
 
 
@@ -90,6 +91,8 @@ SIGNATURES = {
     "sr_gemm_f16_scaled": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_gemm_qkv_rope": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int32, c_int32, c_void_p]),
+    "sr_gemm_qkv_rope_bias": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "sr_attention_varlen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                     c_int32, c_int32, c_int32, c_void_p]),
     "sr_sparse_compact": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,

@@ -55,6 +55,18 @@ extern "C" int sr_gemm_qkv_rope(const void* d_A, const void* d_W, int32_t M, int
     return launch_gemm_bf16(EPI_QKV_ROPE, g, (hipStream_t)stream);
 }
 
+extern "C" int sr_gemm_qkv_rope_bias(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, void* d_C, const int32_t* d_pos,
+                                     const float* d_rope_cos, const float* d_rope_sin, int32_t n_rope, int32_t head_dim,
+                                     const float* d_bias, int32_t fp32_out, sr_stream stream) {
+    SR_REQUIRE(d_A && d_W && d_C && d_pos && d_rope_cos && d_rope_sin, "sr_gemm_qkv_rope_bias: null pointer");
+    SR_REQUIRE(fp32_out == 0 || fp32_out == 1, "sr_gemm_qkv_rope_bias: fp32_out must be 0 or 1");
+    GemmArgs g{};
+    g.A = (const bf16_t*)d_A; g.W = (const bf16_t*)d_W; g.M = M; g.N = N; g.K = K; g.C = d_C;
+    g.pos = d_pos; g.rope_cos = d_rope_cos; g.rope_sin = d_rope_sin; g.n_rope = n_rope; g.head_dim = head_dim;
+    g.bias = d_bias;
+    return launch_gemm_bf16(fp32_out ? EPI_QKV_ROPE_F32 : EPI_QKV_ROPE, g, (hipStream_t)stream);
+}
+
 extern "C" int sr_attention_varlen(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, const int32_t* d_pos,
                                    const uint8_t* d_key_valid, const float* d_rope_cos, const float* d_rope_sin, int32_t B,
                                    int32_t num_heads, int32_t num_kv_heads, int32_t head_dim, sr_stream stream) {

@@ -289,6 +289,16 @@ __global__ void convert_rows_kernel(const void* __restrict__ src, int src_dtype,
     }
 }
 
+// q / k / v bias (cfg.attention_bias): the values as fp32 and their bf16 roundings as fp32 (see LayerW::bqkv)
+__global__ void convert_bias_kernel(const void* __restrict__ src, int src_dtype, int64_t n, float* __restrict__ dst_f32,
+                                    float* __restrict__ dst_bf16r) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = src_dtype == SR_DTYPE_F32 ? reinterpret_cast<const float*>(src)[i] : bf16_to_f32(reinterpret_cast<const bf16_t*>(src)[i]);
+    dst_f32[i] = v;
+    dst_bf16r[i] = bf16_to_f32(f32_to_bf16(v));
+}
+
 // fp32 regime: the same rows as split-bf16 plane segments, dst[row_map(r)][sg * cols + c] = plane_{map.plane[sg]}(src[r][c])
 __global__ void convert_rows_split_kernel(const void* __restrict__ src, int src_dtype, int64_t rows, int64_t cols,
                                           bf16_t* __restrict__ dst, int64_t dst_row_base, int interleave, SplitMap map) {
@@ -632,6 +642,11 @@ struct LayerW {
     // fp16-plane regime: K segments of wqkv_s, wo_s, wgu_s, wdown_s - 3 = [g0 | g1 | g0], 2 = [g0 | g0] (g1 all zero, dropped by
     // sr_model_finalize); the activations feeding each GEMM are split to the same count
     int qkv_seg = 3, o_seg = 3, gu_seg = 3, down_seg = 3;
+    // cfg.attention_bias (Qwen2): bias of the q, k and v rows, [(nh + 2 nkv) hd] fp32 in the order of wqkv, added by the QKV + RoPE
+    // epilogues.  bqkv = the checkpoint's values (fp32 regime), bqkv_r = their bf16 roundings held as fp32 (bf16 regime: autocast
+    // casts an nn.Linear's bias to bf16)
+    float *bqkv = nullptr, *bqkv_r = nullptr;
+    unsigned have_bias = 0;   // bit per bias: q k v
 };
 
 struct sr_model {
@@ -681,7 +696,7 @@ static void model_free(sr_model* m) {
     F(m->lm_head_i); F(m->lo_nz); F(m->attn_f); F(m->act_f); F(m->xs_i); F(m->attn_i); F(m->act_i); F(m->act_sc);
     for (auto& l : m->layers) {
         F(l.wqkv); F(l.wo); F(l.wgu); F(l.wdown); F(l.ln1); F(l.ln2); F(l.wqkv_s); F(l.wo_s); F(l.wgu_s); F(l.wdown_s);
-        F(l.wqkv_i); F(l.wo_i); F(l.wgu_i); F(l.wdown_i); F(l.gu_cmax);
+        F(l.wqkv_i); F(l.wo_i); F(l.wgu_i); F(l.wdown_i); F(l.gu_cmax); F(l.bqkv); F(l.bqkv_r);
     }
     F(m->x); F(m->xn); F(m->qkv); F(m->attn); F(m->act); F(m->delta);
     F(m->span_start); F(m->span_len); F(m->pool_start); F(m->row_len); F(m->cu);
@@ -745,6 +760,7 @@ extern "C" int sr_model_create(sr_model** out, const sr_model_config* cfg) {
     SR_REQUIRE(c.max_batch_tokens > 0 && c.max_batch_seqs > 0 && c.max_batch_seqs <= 65536, "sr_model_create: bad workspace sizes");
     SR_REQUIRE(c.fp32_planes == 0 || c.fp32_planes == 2 || c.fp32_planes == 3 || c.fp32_planes == SR_FP32_PLANES_F16,
                "sr_model_create: fp32_planes must be 0, 2, 3 or 16");
+    SR_REQUIRE(c.attention_bias == 0 || c.attention_bias == 1, "sr_model_create: attention_bias must be 0 or 1");
     sr_model* m = new sr_model();
     m->cfg = c;
     m->Tm = (int)(ceil_div64(c.max_batch_tokens, 128) * 128);
@@ -783,6 +799,10 @@ extern "C" int sr_model_create(sr_model** out, const sr_model_config* cfg) {
         }
         SR_ALLOC(l.ln1, H * 4);
         SR_ALLOC(l.ln2, H * 4);
+        if (c.attention_bias) {
+            SR_ALLOC(l.bqkv, (nq + 2 * nkv) * 4);
+            SR_ALLOC(l.bqkv_r, (nq + 2 * nkv) * 4);
+        }
     }
     SR_ALLOC(m->rope_cos, (int64_t)m->max_pos * (c.head_dim / 2) * 4);
     SR_ALLOC(m->rope_sin, (int64_t)m->max_pos * (c.head_dim / 2) * 4);
@@ -899,6 +919,16 @@ extern "C" int sr_model_set_weight(sr_model* m, const char* name, const void* d_
         if (r == "mlp.gate_proj.weight") { SHAPE_REQ(I, H); SR_TRY(convert_rows(d_ptr, dtype, I, H, l.wgu, nullptr, 0, 1, s, l.wgu_s, c.fp32_planes, l.wgu_i, lo_flag(4 * li + 2))); l.have |= 16; return SR_OK; }
         if (r == "mlp.up_proj.weight") { SHAPE_REQ(I, H); SR_TRY(convert_rows(d_ptr, dtype, I, H, l.wgu, nullptr, 0, 2, s, l.wgu_s, c.fp32_planes, l.wgu_i, lo_flag(4 * li + 2))); l.have |= 32; return SR_OK; }
         if (r == "mlp.down_proj.weight") { SHAPE_REQ(H, I); SR_TRY(convert_rows(d_ptr, dtype, H, I, l.wdown, nullptr, 0, 0, s, l.wdown_s, c.fp32_planes, l.wdown_i, lo_flag(4 * li + 3))); l.have |= 64; return SR_OK; }
+        if (c.attention_bias && (r == "self_attn.q_proj.bias" || r == "self_attn.k_proj.bias" || r == "self_attn.v_proj.bias")) {
+            const int which = r[10] == 'q' ? 0 : (r[10] == 'k' ? 1 : 2);
+            const int64_t n_b = which == 0 ? nq : nkv, base = which == 0 ? 0 : (which == 1 ? nq : nq + nkv);
+            SHAPE_REQ(n_b, 1);
+            hipLaunchKernelGGL(convert_bias_kernel, dim3((unsigned)ceil_div64(n_b, 256)), dim3(256), 0, s, d_ptr, dtype, n_b, l.bqkv + base,
+                               l.bqkv_r + base);
+            SR_CHECK_LAUNCH();
+            l.have_bias |= 1u << which;
+            return SR_OK;
+        }
         if (r == "input_layernorm.weight") { SHAPE_REQ(H, 1); SR_TRY(convert_rows(d_ptr, dtype, H, 1, nullptr, l.ln1, 0, 0, s)); l.have |= 128; return SR_OK; }
         if (r == "post_attention_layernorm.weight") { SHAPE_REQ(H, 1); SR_TRY(convert_rows(d_ptr, dtype, H, 1, nullptr, l.ln2, 0, 0, s)); l.have |= 256; return SR_OK; }
     }
@@ -936,6 +966,11 @@ extern "C" int sr_model_finalize(sr_model* m) {
     SR_REQUIRE(!m->cfg.has_lm_head || m->have_lm_head, "sr_model_finalize: lm_head.weight missing");
     for (int i = 0; i < m->cfg.num_layers; ++i)
         SR_REQUIRE(m->layers[i].have == 511, "sr_model_finalize: layer %d is missing tensors (mask 0x%x)", i, m->layers[i].have);
+    if (m->cfg.attention_bias)
+        for (int i = 0; i < m->cfg.num_layers; ++i)
+            SR_REQUIRE(m->layers[i].have_bias == 7,
+                       "sr_model_finalize: layer %d is missing self_attn.{q,k,v}_proj.bias (attention_bias = 1; mask 0x%x)", i,
+                       m->layers[i].have_bias);
     // sr_model_set_weight converted the planes on the CALLER's streams; a non-blocking stream does not order with the null
     // stream the reduction below runs on, and a cmax read from half-written planes would let EPI_SWIGLU_SPLIT_H overflow fp16
     SR_CHECK_HIP(hipDeviceSynchronize());
@@ -1085,6 +1120,7 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
             GemmArgs g{};
             g.A = m->xs; g.W = l.wqkv_s; g.M = T; g.N = nq + 2 * nkv; g.K = l.qkv_seg * H; g.C = m->qkv_f; g.a_scale = m->xs_i; g.w_scale = l.wqkv_i;
             g.pos = m->pos; g.rope_cos = m->rope_cos; g.rope_sin = m->rope_sin; g.n_rope = nq + nkv; g.head_dim = c.head_dim;
+            g.bias = l.bqkv;
             SR_TRY(launch_gemm_bf16(EPI_QKV_ROPE_F32_H, g, s));
             AttnF32Args a{};
             a.qkv = m->qkv_f; a.out_f32 = m->attn_f; a.out = nullptr; a.cu_seqlens = m->cu; a.key_valid = m->key_valid;
@@ -1129,6 +1165,7 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
             GemmArgs g{};
             g.A = m->xs; g.W = l.wqkv_s; g.M = T; g.N = nq + 2 * nkv; g.K = nsg * H; g.C = m->qkv_f;
             g.pos = m->pos; g.rope_cos = m->rope_cos; g.rope_sin = m->rope_sin; g.n_rope = nq + nkv; g.head_dim = c.head_dim;
+            g.bias = l.bqkv;
             SR_TRY(launch_gemm_bf16(EPI_QKV_ROPE_F32, g, s));
             AttnF32Args a{};
             a.qkv = m->qkv_f; a.out = m->attn_s; a.cu_seqlens = m->cu; a.key_valid = m->key_valid;
@@ -1162,6 +1199,7 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
         GemmArgs g{};
         g.A = m->xn; g.W = l.wqkv; g.M = T; g.N = nq + 2 * nkv; g.K = H; g.C = m->qkv;
         g.pos = m->pos; g.rope_cos = m->rope_cos; g.rope_sin = m->rope_sin; g.n_rope = nq + nkv; g.head_dim = c.head_dim;
+        g.bias = l.bqkv_r;
         SR_TRY(launch_gemm_bf16(EPI_QKV_ROPE, g, s));
         AttnArgs a{};
         a.qkv = m->qkv; a.out = m->attn; a.cu_seqlens = m->cu; a.pos = m->pos; a.key_valid = m->key_valid;

@@ -628,6 +628,25 @@ void gemm_bf16_kernel(GemmArgs g) {
     // -> 670 ms).  The staged epilogues therefore see the lane coordinates through an opaque asm: nothing of them can be hoisted.
     [[maybe_unused]] int frow_e = frow, fg_e = fg, lane_e = lane;
     if constexpr (KL == 1) asm volatile("" : "+v"(frow_e), "+v"(fg_e), "+v"(lane_e));
+    if constexpr ((BEPI == EPI_QKV_ROPE || BEPI == EPI_QKV_ROPE_F32) && !KL_STAGED) {
+        // Qwen2: q_proj / k_proj / v_proj carry a bias.  It is added in fp32 to every accumulator BEFORE the rotation (a rotation partner
+        // gets its own element: each block i adds bias[n(i) ..]) and, on fp16 planes, after the row scales above - the bias lives in the
+        // unscaled domain.  One pass in front of the direct-store epilogue of every tile configuration; the staged epilogue of the
+        // four-wave loop adds the same elements where it reads an accumulator (a pass over its 256 pinned accumulators spills).  The
+        // pointer is wave-uniform: without a bias (Llama) nothing is added, not even + 0.f (which would turn -0 into +0), and the bits
+        // are those of the kernel without this block.
+        if (g.bias != nullptr) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const int n = n0 + wn * NB * 16 + i * 16 + fg_e * 4;
+                f32x4 b = {0.f, 0.f, 0.f, 0.f};
+                if (n < g.N) b = *reinterpret_cast<const f32x4*>(g.bias + n);
+#pragma unroll
+                for (int j = 0; j < MB; ++j) acc[i][j] += b;
+            }
+        }
+    }
     if constexpr (KL_STAGED) {
         // The bf16 outputs of the four-wave tile leave through LDS.  Stored straight from the accumulator layout a lane_e writes
         // 8 bytes and an instruction 16 rows x 32 bytes: 4 096 32-byte fragments per tile and CU, 256 CUs finishing their tiles
@@ -649,6 +668,20 @@ void gemm_bf16_kernel(GemmArgs g) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = (short)f32_to_bf16(v[r]);
             *reinterpret_cast<bf16x4*>(stg + frow_e * ROWB + (((f_local >> 3) ^ (frow_e & (NP - 1))) << 4) + ((f_local & 4) << 1)) = o;
+        };
+        // QKV + RoPE with a bias (Qwen2; g.bias is wave-uniform): every accumulator read adds its 4 bias elements first - the rotation
+        // partner its own.  The epilogue's code exists twice, chosen once per tile, so that without a bias not an instruction is added.
+        // The bias loads sit behind the previous column's stores: nothing of them is carried through the k-loop.
+        auto staged = [&](auto with_bias) {
+        [[maybe_unused]] auto ld = [&](int i, int j) -> f32x4 {
+            f32x4 x = acc[i][j];
+            if constexpr (decltype(with_bias)::value) {
+                // a block of 16 features past N (never stored) reads the last 4 elements instead of a branch
+                int n = n0 + wn * NB * 16 + i * 16 + fg_e * 4;
+                n = n < g.N ? n : g.N - 4;
+                x += *reinterpret_cast<const f32x4*>(g.bias + n);
+            }
+            return x;
         };
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
@@ -672,34 +705,34 @@ void gemm_bf16_kernel(GemmArgs g) {
                 // at a multiple of 128, so d = n % head_dim needs no division and the rotation partner of block i is block i + head_dim / 32 of
                 // the same lane.  Two table loads (L2-resident, 16 bytes each) per pair of blocks; nothing here is invariant in the tile loop
                 // except through frow_e / fg_e, which are opaque.
-                const int mtok = mrow + frow_e;
-                const int pos_t = mtok < g.M ? g.pos[mtok] : 0;
-                const int hd2 = g.head_dim >> 1;
-                const float* ct = g.rope_cos + (int64_t)pos_t * hd2 + fg_e * 4;
-                const float* st = g.rope_sin + (int64_t)pos_t * hd2 + fg_e * 4;
-                if (n0 + wn * NB * 16 < g.n_rope) {
-                    if (g.head_dim == 64) {
+                    const int mtok = mrow + frow_e;
+                    const int pos_t = mtok < g.M ? g.pos[mtok] : 0;
+                    const int hd2 = g.head_dim >> 1;
+                    const float* ct = g.rope_cos + (int64_t)pos_t * hd2 + fg_e * 4;
+                    const float* st = g.rope_sin + (int64_t)pos_t * hd2 + fg_e * 4;
+                    if (n0 + wn * NB * 16 < g.n_rope) {
+                        if (g.head_dim == 64) {
 #pragma unroll
-                        for (int i = 0; i < NB; ++i) {
-                            if ((i & 2) != 0) continue;                  // blocks 2, 3, 6, 7: written with their partners 0, 1, 4, 5
-                            const f32x4 c = *reinterpret_cast<const f32x4*>(ct + (i & 1) * 16), sn = *reinterpret_cast<const f32x4*>(st + (i & 1) * 16);
-                            const f32x4 x1 = acc[i][j], x2 = acc[i + 2][j];
-                            put(i * 16 + fg_e * 4, sr_rope_lo(x1, x2, c, sn));
-                            put((i + 2) * 16 + fg_e * 4, sr_rope_hi(x1, x2, c, sn));
+                            for (int i = 0; i < NB; ++i) {
+                                if ((i & 2) != 0) continue;                  // blocks 2, 3, 6, 7: written with their partners 0, 1, 4, 5
+                                const f32x4 c = *reinterpret_cast<const f32x4*>(ct + (i & 1) * 16), sn = *reinterpret_cast<const f32x4*>(st + (i & 1) * 16);
+                                const f32x4 x1 = ld(i, j), x2 = ld(i + 2, j);
+                                put(i * 16 + fg_e * 4, sr_rope_lo(x1, x2, c, sn));
+                                put((i + 2) * 16 + fg_e * 4, sr_rope_hi(x1, x2, c, sn));
+                            }
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < NB / 2; ++i) {
+                                const f32x4 c = *reinterpret_cast<const f32x4*>(ct + i * 16), sn = *reinterpret_cast<const f32x4*>(st + i * 16);
+                                const f32x4 x1 = ld(i, j), x2 = ld(i + 4, j);
+                                put(i * 16 + fg_e * 4, sr_rope_lo(x1, x2, c, sn));
+                                put((i + 4) * 16 + fg_e * 4, sr_rope_hi(x1, x2, c, sn));
+                            }
                         }
                     } else {
 #pragma unroll
-                        for (int i = 0; i < NB / 2; ++i) {
-                            const f32x4 c = *reinterpret_cast<const f32x4*>(ct + i * 16), sn = *reinterpret_cast<const f32x4*>(st + i * 16);
-                            const f32x4 x1 = acc[i][j], x2 = acc[i + 4][j];
-                            put(i * 16 + fg_e * 4, sr_rope_lo(x1, x2, c, sn));
-                            put((i + 4) * 16 + fg_e * 4, sr_rope_hi(x1, x2, c, sn));
-                        }
+                        for (int i = 0; i < NB; ++i) put(i * 16 + fg_e * 4, ld(i, j));
                     }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < NB; ++i) put(i * 16 + fg_e * 4, acc[i][j]);
-                }
             }
             // rows back out: lane_e -> (token row, 16-byte piece)
             constexpr int LPR = OUT_F * 2 / 16;          // lanes per row (16 or 8)
@@ -712,6 +745,13 @@ void gemm_bf16_kernel(GemmArgs g) {
                 if (m < g.M && n < ldc) *reinterpret_cast<sr_i32x4*>(reinterpret_cast<bf16_t*>(g.C) + (int64_t)m * ldc + n) = v;
             }
             __builtin_amdgcn_sched_barrier(0);       // one block column at a time (bounds what the scheduler keeps in flight)
+        }
+        };
+        if constexpr (BEPI == EPI_QKV_ROPE) {
+            if (g.bias != nullptr) staged(std::true_type{});
+            else staged(std::false_type{});
+        } else {
+            staged(std::false_type{});
         }
     } else if constexpr (KL == 1 && (BEPI == EPI_STORE_F32 || BEPI == EPI_RESID_F32)) {
         // fp32 outputs of the four-wave tile (the fp32 regime's residual adds), staged through LDS like the
@@ -1253,6 +1293,8 @@ int launch_gemm_bf16(GemmEpilogue epi, const GemmArgs& g, hipStream_t s) {
                g.out_nseg);
     SR_REQUIRE(g.N % 16 == 0 && (!swiglu || g.N % 32 == 0), "gemm: N=%d must be a multiple of 16 (32 for SwiGLU)", g.N);
     SR_REQUIRE(epi < EPI_H_FIRST || (g.a_scale && g.w_scale), "gemm(fp16 planes): missing row scales");
+    SR_REQUIRE(!g.bias || epi == EPI_QKV_ROPE || epi == EPI_QKV_ROPE_F32 || epi == EPI_QKV_ROPE_F32_H,
+               "gemm: epilogue %d takes no bias (only the QKV + RoPE epilogues add one)", (int)epi);
     SR_REQUIRE(epi != EPI_SWIGLU_SPLIT || (g.out_map.n_seg >= 1 && g.out_map.n_seg <= SR_MAX_SEG), "gemm(swiglu split): bad segment map");
     switch (epi) {
         case EPI_STORE_BF16: return launch_one<EPI_STORE_BF16>(g, s);

@@ -63,6 +63,8 @@ struct GemmArgs {
     const float* rope_sin;
     int n_rope;             // features [0, n_rope) are rotated (q heads then k heads), the rest (v) stored as is
     int head_dim;           // 64 or 128
+    const float* bias;      // QKV + RoPE epilogues only: [N] fp32 bias of the q, k and v rows (the order of W), added to the fp32 accumulator
+                            // before the rotation (Qwen2: nn.Linear(bias=True) on q_proj / k_proj / v_proj); null = no bias (Llama)
     unsigned long long* stamps;  // diagnostics only (tools/micro): 4 s_memrealtime stamps (100 MHz) per workgroup-tile, else null
     const float* a_scale;   // _H epilogues: [M] inverse scale of each activation row (a power of two)
     const float* w_scale;   // _H epilogues: [N] inverse scale of each weight row

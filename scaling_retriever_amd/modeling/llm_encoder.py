@@ -3,7 +3,7 @@
 Same names, arguments and error behaviour as
 /root/reference/scaling_retriever/modeling/llm_encoder.py (LLM2Retriever :14-150,
 DecoderOnlyBiSparse :175-196, DecoderOnlyBiDense :370-520, LlamaBiSparse :199-201,
-LlamaBiDense :523-525) for the inference path: load / load_from_lora / encode /
+LlamaBiDense :523-525, Qwen2BiSparse :204-209, Qwen2BiDense :528-533) for the inference path: load / load_from_lora / encode /
 query_encode / doc_encode, attributes vocab_size / hidden_size / T / base_model.config.
 
 All arithmetic runs in libsr_hip.so (csrc/encoder.hip, gemm_bf16.hip, attention.hip).
@@ -42,6 +42,18 @@ class LlamaConfigLite(SimpleNamespace):
         d.setdefault("rope_theta", 10000.0)
         d.setdefault("tie_word_embeddings", False)
         d.setdefault("rope_scaling", None)
+        d.setdefault("model_type", "llama")
+        # Qwen2 (modeling/bidrectional_qwen2.py:68-101 over HF Qwen2Attention): q_proj / k_proj / v_proj carry a bias, nothing else
+        # does, and Qwen2Config has no field for it; the engine adds it in the QKV epilogue.  What HF would also change and the
+        # engine does not implement is refused here instead of dropping tensors at load.
+        qwen2 = d["model_type"] == "qwen2"
+        if d.get("mlp_bias"):
+            raise NotImplementedError("mlp_bias: biases on the MLP projections are not supported")
+        if not qwen2 and d.get("attention_bias"):
+            raise NotImplementedError("attention_bias on a Llama config also puts a bias on o_proj, which is not supported")
+        if d.get("use_sliding_window"):
+            raise NotImplementedError("use_sliding_window: sliding-window attention is not supported")
+        d["attention_bias"] = bool(d["attention_bias"]) if d.get("attention_bias") is not None else qwen2
         return cls(**d)
 
     def to_dict(self):
@@ -172,7 +184,8 @@ class HipLlamaBackbone(torch.nn.Module):
             head_dim=c.head_dim, rms_norm_eps=float(c.rms_norm_eps), rope_theta=theta, rope_llama3=llama3,
             rope_factor=fac, rope_low_freq_factor=lo, rope_high_freq_factor=hi, rope_original_max_pos=old,
             tie_word_embeddings=int(bool(c.tie_word_embeddings)), has_lm_head=int(self.has_lm_head),
-            max_batch_tokens=self.max_batch_tokens, max_batch_seqs=self.max_batch_seqs, fp32_planes=self.fp32_planes)
+            max_batch_tokens=self.max_batch_tokens, max_batch_seqs=self.max_batch_seqs, fp32_planes=self.fp32_planes,
+            attention_bias=int(bool(getattr(c, "attention_bias", False))))
 
     def build_engine(self, device):
         _lib.require_gpu()
@@ -405,6 +418,7 @@ class HipLlamaBackbone(torch.nn.Module):
 class LLM2Retriever(torch.nn.Module):
     """llm_encoder.py:14-150 (inference surface)."""
     TRANSFORMER_CLS = None      # name of the reference's backbone class (checked against adapter auto_mapping)
+    MODEL_TYPE = None           # config.json's model_type of the family the class loads ("llama" / "qwen2"); None = any
     TARGET_MODULES = TARGET_MODULES
     HAS_LM_HEAD = False
     _tied_weights_keys = None
@@ -503,6 +517,7 @@ class LLM2Retriever(torch.nn.Module):
         base_dir = _resolve_dir(model_name_or_path, access_token)
         with open(os.path.join(base_dir, "config.json")) as f:
             config = LlamaConfigLite.from_dict(json.load(f))
+        cls._check_family(config, base_dir)
         weights = _read_checkpoint(base_dir)
         if lora is not None:
             extra = lora.pop("extra")
@@ -519,6 +534,14 @@ class LLM2Retriever(torch.nn.Module):
             raise ValueError("checkpoint has no lm_head.weight and tie_word_embeddings is false")
         backbone = HipLlamaBackbone(config, weights, has_lm_head=cls.HAS_LM_HEAD, lora=lora)
         return cls._make(backbone, **make_kw)
+
+    @classmethod
+    def _check_family(cls, config, where):
+        """A class loads its own family only: the other one's checkpoint would fail on a tensor name deep in build_engine
+        (a Qwen2 bias the Llama engine does not know) or, worse, load with its biases missing."""
+        if cls.MODEL_TYPE is not None and config.model_type != cls.MODEL_TYPE:
+            raise ValueError(f"{cls.__name__} loads model_type '{cls.MODEL_TYPE}' checkpoints, {where} is "
+                             f"model_type '{config.model_type}'")
 
     @classmethod
     def load(cls, model_name_or_path, lora_name_or_path=None, merge_peft=True, is_trainable=False, access_token=None):
@@ -542,6 +565,11 @@ class LLM2Retriever(torch.nn.Module):
                      **make_kw):
         """Build from an in-memory state dict (HF Llama names -> numpy/torch tensors)."""
         weights = {_canonical_name(k): v for k, v in weights.items()}
+        if cls.MODEL_TYPE is not None and not isinstance(config, LlamaConfigLite):
+            config = dict(config)
+            config.setdefault("model_type", cls.MODEL_TYPE)
+        config = config if isinstance(config, LlamaConfigLite) else LlamaConfigLite.from_dict(config)
+        cls._check_family(config, "the given config")
         backbone = HipLlamaBackbone(config, weights, has_lm_head=cls.HAS_LM_HEAD, max_batch_tokens=max_batch_tokens,
                                     max_batch_seqs=max_batch_seqs, precision=precision, fp32_planes=fp32_planes)
         return cls._make(backbone, **make_kw)
@@ -603,6 +631,14 @@ class DecoderOnlyBiDense(LLM2Retriever):
 
 class LlamaBiSparse(DecoderOnlyBiSparse):
     TRANSFORMER_CLS = "LlamaBiForMNTP"
+    MODEL_TYPE = "llama"
+
+
+class Qwen2BiSparse(DecoderOnlyBiSparse):
+    """llm_encoder.py:204-206."""
+    TRANSFORMER_CLS = "Qwen2BiForMNTP"
+    TARGET_MODULES = ["q_proj", "v_proj", "o_proj", "k_proj", "down_proj", "up_proj", "gate_proj"]
+    MODEL_TYPE = "qwen2"
 
 
 class DecoderOnlyBiHybrid(DecoderOnlyBiSparse):
@@ -628,11 +664,48 @@ class DecoderOnlyBiHybrid(DecoderOnlyBiSparse):
 
 class LlamaBiHybrid(DecoderOnlyBiHybrid):
     TRANSFORMER_CLS = "LlamaBiForMNTP"
+    MODEL_TYPE = "llama"
+
+
+class Qwen2BiHybrid(DecoderOnlyBiHybrid):
+    TRANSFORMER_CLS = "Qwen2BiForMNTP"
+    TARGET_MODULES = ["q_proj", "v_proj", "o_proj", "k_proj", "down_proj", "up_proj", "gate_proj"]
+    MODEL_TYPE = "qwen2"
 
 
 class LlamaBiDense(DecoderOnlyBiDense):
     TRANSFORMER_CLS = "LlamaBiModel"
+    MODEL_TYPE = "llama"
+
+
+class Qwen2BiDense(DecoderOnlyBiDense):
+    """llm_encoder.py:528-530."""
+    TRANSFORMER_CLS = "Qwen2BiModel"
+    TARGET_MODULES = ["q_proj", "v_proj", "o_proj", "k_proj", "down_proj", "up_proj", "gate_proj"]
+    MODEL_TYPE = "qwen2"
 
 
 LlamaBiSparseForNCE = LlamaBiSparse
 LlamaBiDenseForNCE = LlamaBiDense
+Qwen2BiSparseForNCE = Qwen2BiSparse
+Qwen2BiDenseForNCE = Qwen2BiDense
+
+
+def retriever_class(model_dir, head):
+    """The class of the drivers' `load_from_lora` calls for the checkpoint in model_dir: its config.json's model_type picks the
+    family ("qwen2" -> Qwen2Bi*, anything else -> LlamaBi*, whose loader refuses what it cannot run), head "dense" / "sparse" /
+    "hybrid" the class.  An adapter directory without a config.json is looked up through its base model."""
+    classes = {"dense": (LlamaBiDense, Qwen2BiDense), "sparse": (LlamaBiSparse, Qwen2BiSparse),
+               "hybrid": (LlamaBiHybrid, Qwen2BiHybrid)}[head]
+    cfg_path = os.path.join(model_dir, "config.json")
+    if not os.path.exists(cfg_path):
+        ad = os.path.join(model_dir, "adapter_config.json")
+        if os.path.exists(ad):
+            with open(ad) as f:
+                base = json.load(f).get("base_model_name_or_path") or ""
+            cfg_path = os.path.join(base, "config.json")
+    model_type = None
+    if os.path.exists(cfg_path):
+        with open(cfg_path) as f:
+            model_type = json.load(f).get("model_type")
+    return classes[1] if model_type == "qwen2" else classes[0]
