@@ -395,6 +395,15 @@ int sr_gemm_qkv_rope_bias(const void* d_A, const void* d_W, int32_t M, int32_t N
 int sr_attention_varlen(const void* d_qkv, void* d_out, const int32_t* d_cu_seqlens, const int32_t* d_pos,
                         const uint8_t* d_key_valid, const float* d_rope_cos, const float* d_rope_sin,
                         int32_t B, int32_t num_heads, int32_t num_kv_heads, int32_t head_dim, sr_stream stream);
+/* The attention of the encoder's fp32 regime: d_qkv fp32 [T,(nh+2nkv)*hd] with q / k already rotated, fp32 scores, softmax and
+ * P.V.  Exactly one output: d_out_f32 fp32 [T,nh*hd] (what fp32_planes = 16 uses), or d_out_planes bf16 [T, n_seg*nh*hd] = the
+ * bf16 plane segments the o_proj GEMM consumes, fp32_planes = 3 (6 segments: planes 2 0 1 1 0 0) or 2 (3 segments: 1 0 0);
+ * fp32_planes is ignored with d_out_f32.  max_seqlen = the longest sequence of the batch (it sizes the grids and the LDS of the
+ * short-sequence kernel: never pass less).  head_dim 64 or 128, else SR_ERR_UNSUPPORTED and nothing is launched.  The kernel is
+ * chosen per sequence (<= 64 tokens at 4 q heads per kv head: fp32 MFMA), so a sequence's bits do not depend on its batch. */
+int sr_attention_varlen_f32(const float* d_qkv, float* d_out_f32, void* d_out_planes, int32_t fp32_planes,
+                            const int32_t* d_cu_seqlens, const uint8_t* d_key_valid, int32_t B, int32_t num_heads,
+                            int32_t num_kv_heads, int32_t head_dim, int32_t max_seqlen, sr_stream stream);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,8 @@ SIGNATURES = {
                                       c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "sr_attention_varlen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                     c_int32, c_int32, c_int32, c_void_p]),
+    "sr_attention_varlen_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                        c_int32, c_int32, c_void_p]),
     "sr_sparse_compact": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                   ctypes.POINTER(c_int64), c_void_p]),
 }

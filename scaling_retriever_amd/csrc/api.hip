@@ -89,6 +89,23 @@ extern "C" int sr_attention_varlen(const void* d_qkv, void* d_out, const int32_t
     return launch_attention(a, (hipStream_t)stream);
 }
 
+// fp32 attention of the encoder's fp32 regime (attention_f32.hip), exported for the per-kernel parity test: the arguments
+// the encoder fills, both output forms.  max_seqlen sizes the grids and the MFMA kernel's LDS: the batch's true maximum.
+extern "C" int sr_attention_varlen_f32(const float* d_qkv, float* d_out_f32, void* d_out_planes, int32_t fp32_planes,
+                                       const int32_t* d_cu_seqlens, const uint8_t* d_key_valid, int32_t B, int32_t num_heads,
+                                       int32_t num_kv_heads, int32_t head_dim, int32_t max_seqlen, sr_stream stream) {
+    SR_REQUIRE(d_qkv && d_cu_seqlens && d_key_valid, "sr_attention_varlen_f32: null pointer");
+    SR_REQUIRE((d_out_f32 != nullptr) != (d_out_planes != nullptr), "sr_attention_varlen_f32: pass exactly one of d_out_f32 / d_out_planes");
+    SR_REQUIRE(d_out_f32 || fp32_planes == 2 || fp32_planes == 3, "sr_attention_varlen_f32: fp32_planes %d (2 or 3 for plane output)", fp32_planes);
+    SR_REQUIRE(B >= 0 && max_seqlen >= 0 && num_heads > 0 && num_kv_heads > 0 && head_dim > 0, "sr_attention_varlen_f32: bad sizes");
+    AttnF32Args a{};
+    a.qkv = d_qkv; a.out_f32 = d_out_f32; a.out = (bf16_t*)d_out_planes; a.cu_seqlens = d_cu_seqlens; a.key_valid = d_key_valid;
+    a.B = B; a.nh = num_heads; a.nkv = num_kv_heads; a.hd = head_dim;
+    a.scale = 1.0f / sqrtf((float)head_dim); a.max_seqlen = max_seqlen;
+    if (!d_out_f32) a.out_map = split_map_a(fp32_planes);
+    return launch_attention_f32(a, (hipStream_t)stream);
+}
+
 // fp16-plane GEMM of the encoder's fp32 regime, exported for the per-kernel parity test: C fp32 [M, N] += (A' @ W'^T) *
 // a_scale[m] * w_scale[n], A' / W' = [rows, K] fp16 plane segments.
 extern "C" int sr_gemm_f16_scaled(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, const float* d_a_scale,

@@ -18,6 +18,16 @@
 #define AF_RPW 4      // q rows per wave
 #define AF_ROWS 16    // q rows per workgroup
 
+// The FMA kernels below promise the same bits from both of them, and plane segments that are the split of the very value the
+// fp32 output form stores.  Both used to rest on what hipcc happened to contract: it built the last four products of a score
+// with packed multiplies and plain adds in attention_f32_kernel (a fused chain in attention_f32_gqa_kernel), and it fused
+// o * inv into split_bf16x3's first residual (fma(o, inv, -p0): planes of the unrounded product).  So every multiply-add of
+// the two kernels is an explicit fmaf, and the output value is rounded to fp32 once, here, before it is stored or split.
+__device__ inline float af_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 template <int HD>
 __global__ __launch_bounds__(256) void attention_f32_kernel(AttnF32Args a) {
     constexpr int DPL = HD / 64;                     // head dims per lane
@@ -63,7 +73,7 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(AttnF32Args a) {
             const int row = wave * AF_RPW + r;      // wave-uniform
             if (row >= nrows) break;
             float s = 0.f;
-            for (int d = 0; d < HD; ++d) s += qs[row][d] * Ks[lane][d];
+            for (int d = 0; d < HD; ++d) s = fmaf(qs[row][d], Ks[lane][d], s);
             s = valid ? s * a.scale : -INFINITY;
             float mx = s;
             for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
@@ -73,7 +83,7 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(AttnF32Args a) {
             const float p = valid ? expf(s - m_new) : 0.f;
             float sum = p;
             for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-            l[r] = l[r] * corr + sum;
+            l[r] = fmaf(l[r], corr, sum);
             m[r] = m_new;
             ps[row][lane] = p;                      // same wave writes and reads this row: no barrier needed
             __builtin_amdgcn_wave_barrier();
@@ -84,10 +94,10 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(AttnF32Args a) {
                 const float pk = ps[row][k];
                 const float* vrow = a.qkv + (int64_t)(t0 + k0 + k) * ld + voff;
 #pragma unroll
-                for (int e = 0; e < DPL; ++e) acc[e] += pk * vrow[lane + 64 * e];
+                for (int e = 0; e < DPL; ++e) acc[e] = fmaf(pk, vrow[lane + 64 * e], acc[e]);
             }
 #pragma unroll
-            for (int e = 0; e < DPL; ++e) o[r][e] = o[r][e] * corr + acc[e];
+            for (int e = 0; e < DPL; ++e) o[r][e] = fmaf(o[r][e], corr, acc[e]);
         }
     }
     const int64_t ldo = (int64_t)a.out_map.n_seg * a.nh * HD;
@@ -98,14 +108,14 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(AttnF32Args a) {
         const float inv = l[r] > 0.f ? 1.0f / l[r] : 0.f;
         if (a.out_f32) {
 #pragma unroll
-            for (int e = 0; e < DPL; ++e) a.out_f32[(int64_t)(t0 + r0 + row) * a.nh * HD + h * HD + lane + 64 * e] = o[r][e] * inv;
+            for (int e = 0; e < DPL; ++e) a.out_f32[(int64_t)(t0 + r0 + row) * a.nh * HD + h * HD + lane + 64 * e] = af_mul_rn(o[r][e], inv);
             continue;
         }
         bf16_t* orow = a.out + (int64_t)(t0 + r0 + row) * ldo;
 #pragma unroll
         for (int e = 0; e < DPL; ++e) {
             unsigned short p[3];
-            split_bf16x3(o[r][e] * inv, p[0], p[1], p[2]);
+            split_bf16x3(af_mul_rn(o[r][e], inv), p[0], p[1], p[2]);
             const int col = h * HD + lane + 64 * e;
             for (int sg = 0; sg < a.out_map.n_seg; ++sg) orow[(int64_t)sg * a.nh * HD + col] = p[a.out_map.plane[sg]];
         }
@@ -167,7 +177,7 @@ __global__ __launch_bounds__(64 * G) void attention_f32_gqa_kernel(AttnF32Args a
                 for (int e = 0; e < DPL; ++e) qs[wave][lane + 64 * e] = a.qkv[(int64_t)(t0 + r0 + row) * ld + h * HD + lane + 64 * e];
                 __builtin_amdgcn_wave_barrier();        // the wave's own row: LDS operations of one wave execute in order
                 float s = 0.f;
-                for (int d = 0; d < HD; ++d) s += qs[wave][d] * Ks[lane][d];
+                for (int d = 0; d < HD; ++d) s = fmaf(qs[wave][d], Ks[lane][d], s);
                 s = valid ? s * a.scale : -INFINITY;
                 float mx = s;
                 for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
@@ -177,7 +187,7 @@ __global__ __launch_bounds__(64 * G) void attention_f32_gqa_kernel(AttnF32Args a
                 const float p = valid ? expf(s - m_new) : 0.f;
                 float sum = p;
                 for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-                l[r] = l[r] * corr + sum;
+                l[r] = fmaf(l[r], corr, sum);
                 m[r] = m_new;
                 ps[wave][lane] = p;
                 __builtin_amdgcn_wave_barrier();
@@ -187,15 +197,15 @@ __global__ __launch_bounds__(64 * G) void attention_f32_gqa_kernel(AttnF32Args a
                 for (int k = 0; k < nk; ++k) {
                     const float pk = ps[wave][k];
                     if constexpr (V_LDS) {               // one dependent global load per key was the kernel's critical path
-                        acc[0] += pk * Vs[k][lane];
+                        acc[0] = fmaf(pk, Vs[k][lane], acc[0]);
                     } else {
                         const float* vrow = a.qkv + (int64_t)(t0 + k0 + k) * ld + voff;
 #pragma unroll
-                        for (int e = 0; e < DPL; ++e) acc[e] += pk * vrow[lane + 64 * e];
+                        for (int e = 0; e < DPL; ++e) acc[e] = fmaf(pk, vrow[lane + 64 * e], acc[e]);
                     }
                 }
 #pragma unroll
-                for (int e = 0; e < DPL; ++e) o[r][e] = o[r][e] * corr + acc[e];
+                for (int e = 0; e < DPL; ++e) o[r][e] = fmaf(o[r][e], corr, acc[e]);
             }
         }
 #pragma unroll
@@ -205,14 +215,14 @@ __global__ __launch_bounds__(64 * G) void attention_f32_gqa_kernel(AttnF32Args a
             const float inv = l[r] > 0.f ? 1.0f / l[r] : 0.f;
             if (a.out_f32) {
 #pragma unroll
-                for (int e = 0; e < DPL; ++e) a.out_f32[(int64_t)(t0 + r0 + row) * a.nh * HD + h * HD + lane + 64 * e] = o[r][e] * inv;
+                for (int e = 0; e < DPL; ++e) a.out_f32[(int64_t)(t0 + r0 + row) * a.nh * HD + h * HD + lane + 64 * e] = af_mul_rn(o[r][e], inv);
                 continue;
             }
             bf16_t* orow = a.out + (int64_t)(t0 + r0 + row) * ldo;
 #pragma unroll
             for (int e = 0; e < DPL; ++e) {
                 unsigned short p[3];
-                split_bf16x3(o[r][e] * inv, p[0], p[1], p[2]);
+                split_bf16x3(af_mul_rn(o[r][e], inv), p[0], p[1], p[2]);
                 const int col = h * HD + lane + 64 * e;
                 for (int sg = 0; sg < a.out_map.n_seg; ++sg) orow[(int64_t)sg * a.nh * HD + col] = p[a.out_map.plane[sg]];
             }

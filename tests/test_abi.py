@@ -40,6 +40,24 @@ def test_status_codes_and_error_strings_without_gpu():
     assert lib.sr_dense_index_destroy(h) == 0
 
 
+def test_attention_f32_hook_validates_before_it_launches():
+    """sr_attention_varlen_f32 rejects what it cannot run with SR_ERR_INVALID before anything touches a device: the pointers
+    below are never dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(4096)
+    ok = dict(qkv=p, f32=p, planes=None, fp32_planes=0, cu=p, kv=p, B=1, nh=4, nkv=1, hd=64, max_seqlen=8)
+    for change, text in [(dict(qkv=None), b"null pointer"), (dict(cu=None), b"null pointer"), (dict(kv=None), b"null pointer"),
+                         (dict(planes=p, fp32_planes=3), b"exactly one"), (dict(f32=None), b"exactly one"),
+                         (dict(f32=None, planes=p, fp32_planes=16), b"fp32_planes 16"), (dict(f32=None, planes=p, fp32_planes=0), b"fp32_planes 0"),
+                         (dict(B=-1), b"bad sizes"), (dict(max_seqlen=-1), b"bad sizes"), (dict(nkv=0), b"bad sizes"),
+                         (dict(nh=6, nkv=4), b"not a multiple")]:
+        a = dict(ok, **change)
+        rc = lib.sr_attention_varlen_f32(a["qkv"], a["f32"], a["planes"], a["fp32_planes"], a["cu"], a["kv"], a["B"], a["nh"], a["nkv"],
+                                         a["hd"], a["max_seqlen"], None)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
+
+
 def test_missing_extension_fails_loudly(monkeypatch, tmp_path):
     from scaling_retriever_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

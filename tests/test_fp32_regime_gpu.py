@@ -206,10 +206,12 @@ def test_eval_dense_query_vecs_run_in_fp32(golden_dir):
 
 
 # ---------------------------------------------------------------- fp32 attention kernel, longer and ragged sequences
-@pytest.mark.parametrize("hd,heads,kv", [(64, 4, 2), (128, 2, 1)])
+@pytest.mark.parametrize("hd,heads,kv", [(64, 4, 2), (128, 2, 1), (64, 4, 1), (128, 4, 1)])
 def test_fp32_regime_long_ragged_sequences(hd, heads, kv):
     """Sequences beyond one 64-key chunk (online softmax across chunks) and beyond one 16-row q block, right padding
-    with masked keys inside the batch, vs the numpy oracle in fp32."""
+    with masked keys inside the batch, vs the numpy oracle in fp32.  The 4:1 configurations run the kernels the product
+    uses (fp32 MFMA up to 64 tokens, the grouped FMA kernel above: the batch crosses that border), the 2:1 ones the
+    per-head FMA kernel."""
     from scaling_retriever_amd.modeling.llm_encoder import LlamaBiDense, LlamaBiSparse
     cfg = dict(vocab_size=320, hidden_size=heads * hd, intermediate_size=384, num_hidden_layers=2, num_attention_heads=heads,
                num_key_value_heads=kv, head_dim=hd, rms_norm_eps=1e-5, rope_theta=500000.0, tie_word_embeddings=False)
