@@ -118,6 +118,22 @@ int sr_dense_index_set_workspace_limit(sr_dense_index* idx, int64_t bytes);
  * but differ in the last bit - as faiss's IndexFlatIP.search does between its small-batch loop and its sgemm path (the switch at
  * 20 queries that /root/reference/scaling_retriever/indexer.py:211 inherits).                                                     */
 int sr_dense_index_set_batch_invariant(sr_dense_index* idx, int on);
+/* Scores of GIVEN (query, document) pairs from the rows the index already holds.  Replaces DecoderOnlyBiDense.rerank_forward
+ * (scaling_retriever/modeling/llm_encoder.py:593-615: `(query_rep * doc_rep).sum(dim=-1)` after encoding both sides of every
+ * pair again) behind eval_reranker.py:107-160 for documents that are in the index.  Candidates as CSR over the queries:
+ * d_cand_indptr int64 [nq + 1] (starts at 0, never decreases; total = d_cand_indptr[nq]), d_cand_ids int64 [total] = global doc
+ * indices as sr_dense_search returns them (id_base + row * id_stride of a segment); lists may be empty, may repeat a document and
+ * have no length limit.  d_out_scores fp32 [total]: out[p] for d_cand_indptr[q] <= p < d_cand_indptr[q + 1] is the fp32 fmaf chain
+ * of query q and that document in the k order of the exact score kernel (per 8 columns k = 8s + j, then 8s + 4 + j, j = 0..3), for
+ * EVERY nq: a pair's score does not depend on what else is in the call.  It therefore equals, bit for bit, the score sr_dense_search
+ * returns for that pair whenever the search accumulates in that order - more than 64 queries, or dim % 256 != 0, or
+ * sr_dense_index_set_batch_invariant(idx, 1) - in every precision mode whose results are the exact kernel's (SR_PRECISION_FP32,
+ * SR_PRECISION_FP32_FILTERED).  An id that is in no segment: SR_ERR_INVALID, sr_last_error() names the first such pair (found on
+ * the device); d_out_scores then holds NaN at the offending pairs and scores elsewhere - do not use it.  A d_cand_indptr that does
+ * not start at 0 or decreases: SR_ERR_INVALID, nothing written.  The work is queued on `stream`; the call then waits for it once,
+ * to read that status back (no other host synchronisation, no size read-back before the launch).                              */
+int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries, int64_t nq, const int64_t* d_cand_indptr,
+                         const int64_t* d_cand_ids, float* d_out_scores, sr_stream stream);
 int sr_dense_index_destroy(sr_dense_index* idx);
 /* Measurement hook: while enabled, every launch of the score kernel is bracketed by HIP
  * events on the search stream.  _read synchronises those events and returns the number
@@ -155,6 +171,19 @@ int sr_sparse_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int3
                      float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
                      sr_stream stream);
 int sr_sparse_index_set_workspace_limit(sr_sparse_index* idx, int64_t bytes);
+/* Scores of GIVEN (query, document) pairs.  Replaces DecoderOnlyBiSparse.rerank_forward (scaling_retriever/modeling/llm_encoder.py:
+ * 593-615 as inherited by the sparse classes: both sides encoded again, then the product summed over the vocabulary) behind
+ * eval_reranker.py:107-160.  Queries as for sr_sparse_search, candidates as for sr_dense_score_pairs; d_cand_ids = document positions
+ * in [0, n_docs) (what sr_sparse_search returns with id_base 0, id_stride 1).  out[p] = scores[doc] of numba_score_float
+ * (scaling_retriever/indexer.py:324-340): for each query term in the order given - repeated terms each time they appear, term ids
+ * outside [0, n_terms) skipped - an unfused fp32 multiply then add, from +0.0f.  No threshold: a pair without a common term scores
+ * 0.0f.  Any query and any index sr_sparse_search accepts; the bits do not depend on the route (the forward index of the certified
+ * scorer where the index has one and the query's terms are valid and strictly ascending, the posting lists otherwise; dev switch
+ * SR_PAIR_SPARSE_ROUTE=postings forces the latter).  Errors, d_out_scores after an error and synchronisation: as
+ * sr_dense_score_pairs.                                                                                                         */
+int sr_sparse_score_pairs(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                          int64_t nq, const int64_t* d_cand_indptr, const int64_t* d_cand_ids, float* d_out_scores,
+                          sr_stream stream);
 int sr_sparse_index_destroy(sr_sparse_index* idx);
 /* Measurement hook as for the dense index; algorithmic bytes = 8 B per posting of the
  * query terms that falls in the launched doc tiles (computed on the device).       */

@@ -16,6 +16,7 @@
 #include "dense_stream.h"
 #include "dense_split.h"
 #include "dense_filter.h"
+#include "pair_score.h"
 #include <mutex>
 #include <stdlib.h>
 #include <vector>
@@ -418,6 +419,9 @@ struct sr_dense_index {
     int64_t n_filtered = 0, n_fallback = 0;   // searches answered by the filter alone / with queries (or all) redone by the exact kernel
     int64_t nq_certified = 0, nq_redone = 0;  // queries answered by the filter / re-done by the exact kernel
     int64_t pend_nq = 0; int pend_k = 0; const float* pend_q = nullptr;   // sr_dense_search_begin ran for this batch
+    // sr_dense_score_pairs (pair_score.hip): the segments as a device table (rebuilt when a segment was added), the call's status words
+    PairSeg* pair_segs = nullptr; size_t pair_segs_n = 0;
+    PairStatus* pair_status = nullptr;
 };
 
 // bf16 planes of every segment a score mode needs (the certified filter keeps its own fp16 plane, filter_prepare_segment)
@@ -571,6 +575,8 @@ extern "C" int sr_dense_index_destroy(sr_dense_index* idx) {
     if (idx->a_scores) (void)hipFree(idx->a_scores);
     if (idx->a_ids) (void)hipFree(idx->a_ids);
     if (idx->flags) (void)hipFree(idx->flags);
+    if (idx->pair_segs) (void)hipFree(idx->pair_segs);
+    if (idx->pair_status) (void)hipFree(idx->pair_status);
     delete idx;
     return SR_OK;
 }
@@ -1000,6 +1006,35 @@ extern "C" int sr_dense_search_finish(sr_dense_index* idx, const float* d_querie
         }
     }
     return sr_dense_search(idx, d_queries, nq, k, d_out_scores, d_out_ids, stream);
+}
+
+extern "C" int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries, int64_t nq, const int64_t* d_cand_indptr,
+                                    const int64_t* d_cand_ids, float* d_out_scores, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_score_pairs: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_score_pairs: bad nq=%lld", (long long)nq);
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_queries && d_cand_indptr && d_cand_ids && d_out_scores, "sr_dense_score_pairs: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder::Scope in_order(idx->order, s);
+    if (idx->pair_segs_n != idx->segs.size()) {           // segments are only ever added
+        std::vector<PairSeg> h;
+        for (const DenseSegment& seg : idx->segs) h.push_back(PairSeg{seg.rows, seg.n, seg.id_base, seg.id_stride});
+        if (idx->pair_segs) (void)hipFree(idx->pair_segs);    // waits for the calls that read it
+        idx->pair_segs = nullptr; idx->pair_segs_n = 0;
+        if (hipMalloc((void**)&idx->pair_segs, sizeof(PairSeg) * h.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            idx->pair_segs = nullptr;
+            sr_set_error("sr_dense_score_pairs: out of device memory for the table of %zu segments", h.size());
+            return SR_ERR_NOMEM;
+        }
+        SR_CHECK_HIP(hipMemcpy(idx->pair_segs, h.data(), sizeof(PairSeg) * h.size(), hipMemcpyHostToDevice));
+        idx->pair_segs_n = h.size();
+    }
+    SR_TRY(pair_status_begin(&idx->pair_status, d_cand_indptr, nq, s));
+    SR_TRY(launch_dense_pairs(idx->pair_segs, (int)idx->pair_segs_n, d_queries, nq, idx->dim, d_cand_indptr, d_cand_ids, d_out_scores,
+                              idx->pair_status, s));
+    return pair_status_end(idx->pair_status, d_cand_ids, "sr_dense_score_pairs", s);
 }
 
 extern "C" int sr_dense_index_filter_stats(sr_dense_index* idx, int64_t* n_filtered, int64_t* n_fallback) {

@@ -1,0 +1,23 @@
+// Pair scoring on the resident indexes (pair_score.hip): exact scores of caller-supplied (query, document) pairs.
+#pragma once
+#include "common.h"
+
+struct PairSeg {                    // one dense segment: global doc index = id_base + row * id_stride
+    const float* rows;
+    int64_t n;
+    int64_t id_base, id_stride;
+};
+struct PairStatus {                 // device word pair of a call: what the kernels found wrong
+    unsigned long long first_bad;   // smallest pair position whose candidate id is not in the index (~0: none)
+    int indptr_bad;                 // cand_indptr does not start at 0 or decreases somewhere: nothing was scored
+    int pad;
+};
+
+// *d_status: the handle's PairStatus (allocated on first use), reset on the stream; then cand_indptr is checked
+int pair_status_begin(PairStatus** d_status, const int64_t* d_cand_indptr, int64_t nq, hipStream_t s);
+// the call's one read-back: waits for the stream; SR_ERR_INVALID with the first offender named (who = entry point)
+int pair_status_end(PairStatus* d_status, const int64_t* d_cand_ids, const char* who, hipStream_t s);
+
+// out[p] = fp32 fmaf chain of Q[q] . row(cand_ids[p]) in dense_score.hip's k order, for cand_indptr[q] <= p < cand_indptr[q + 1]
+int launch_dense_pairs(const PairSeg* d_segs, int n_segs, const float* Q, int64_t nq, int H, const int64_t* d_cand_indptr,
+                       const int64_t* d_cand_ids, float* d_out, PairStatus* d_status, hipStream_t s);

@@ -230,6 +230,13 @@ __global__ __launch_bounds__(256) void cert_fwd_sort_kernel(const int64_t* __res
     for (int i = lane; i < n; i += 64) fwd_tv[b + i] = keys[i];
 }
 
+bool sparse_cert_forward_index(const SparseCert* c, const int64_t** fwd_indptr, const uint64_t** fwd_tv) {
+    if (!c || !c->fwd_indptr || !c->fwd_tv) return false;
+    *fwd_indptr = c->fwd_indptr;
+    *fwd_tv = c->fwd_tv;
+    return true;
+}
+
 void sparse_cert_destroy(SparseCert* c) {
     if (!c) return;
     if (c->d_stamps) {          // diagnostic: mean cycles per tile step of the sampled waves

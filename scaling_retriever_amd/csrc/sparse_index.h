@@ -5,6 +5,7 @@
 #include <mutex>
 
 struct SparseCert;      // sparse_cert.hip
+struct PairStatus;      // pair_score.h
 
 struct sr_sparse_index {
     const int64_t* indptr = nullptr;
@@ -44,6 +45,8 @@ struct sr_sparse_index {
     SparseCert* cert = nullptr;
     int64_t n_cert_no_memory = 0;       // query batches served by the exact kernels because the certified scorer's buffers did not fit
     int64_t n_cert_retries = 0;         // sub-batches of handed-back queries sent through the scorer again with the widest band
+    uint8_t* pair_qflags = nullptr; int64_t pair_qflags_cap = 0;   // sr_sparse_score_pairs: per query, may the forward route serve it
+    PairStatus* pair_status = nullptr;  // sr_sparse_score_pairs: the call's status words (pair_score.hip)
     std::mutex mu;
 };
 
@@ -52,6 +55,9 @@ struct sr_sparse_index {
 // SR_OK with idx->cert == nullptr when the index does not qualify (a negative or non-finite value, too few docs, no memory).
 int sparse_cert_build(sr_sparse_index* idx, hipStream_t s);
 void sparse_cert_destroy(SparseCert* c);
+// the doc-major forward index (row d = postings [fwd_indptr[d], fwd_indptr[d + 1]) of fwd_tv, term << 32 | value bits, terms ascending);
+// false (pointers untouched) when c is null or was built without it
+bool sparse_cert_forward_index(const SparseCert* c, const int64_t** fwd_indptr, const uint64_t** fwd_tv);
 // Scores every query; d_uncert[q] = 1 marks the queries whose result rows were NOT written and must be served by the exact
 // kernels (query outside the fast path's preconditions, or its candidate set could not be certified).  *n_uncert = their number
 // (the call synchronises the stream once to read it).  *no_memory = true (with SR_OK): the per-call buffers of this batch did not fit

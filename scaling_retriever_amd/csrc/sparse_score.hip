@@ -1159,6 +1159,8 @@ extern "C" int sr_sparse_index_destroy(sr_sparse_index* idx) {
     if (idx->d_postings) (void)hipFree(idx->d_postings);
     if (idx->d_counters) (void)hipFree(idx->d_counters);
     if (idx->seg_cnt) (void)hipFree(idx->seg_cnt);
+    if (idx->pair_status) (void)hipFree(idx->pair_status);
+    if (idx->pair_qflags) (void)hipFree(idx->pair_qflags);
     delete idx;
     return SR_OK;
 }

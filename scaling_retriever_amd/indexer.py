@@ -314,6 +314,32 @@ class DenseFlatIndexer(DenseIndexer):
         scores, indexes = self.index.search(q, top_docs)
         return to_host(scores), to_host(indexes)
 
+    def inverse_id_map(self):
+        """str(db id) -> index position, cached with the id table (rebuilt when the list grew)."""
+        from .rerank import InverseIdMap
+        self.id_table()                                   # refreshes the stamp; a changed list drops the cache below
+        stamp = self._id_table_stamp
+        if getattr(self, "_inverse", None) is None or self._inverse[0] != stamp:
+            self._inverse = (stamp, InverseIdMap(self.index_id_to_db_id))
+        return self._inverse[1]
+
+    def score_candidates(self, query_reps, doc_id_lists, qids=None):
+        """Exact scores of given candidates (what eval_reranker.py computes by re-encoding every pair): query_reps [nq, dim],
+        doc_id_lists = nq lists of database ids (what run.json holds); an id the index does not hold raises KeyError naming it.
+        Returns a RunResult (rows sorted by score descending, ties by index position ascending; `.dump(path)` writes run.json).
+        The scores are DenseIndexHIP.score_pairs's: the bits a search of more than 64 queries returns for the pair."""
+        from .rerank import ranked_run
+        if isinstance(query_reps, torch.Tensor):
+            q = query_reps.to(device=self.index.device, dtype=torch.float32)
+        else:
+            q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
+        assert len(doc_id_lists) == q.shape[0], (len(doc_id_lists), q.shape[0])
+        indptr, positions = self.inverse_id_map().positions(doc_id_lists)
+        pos_t = torch.from_numpy(positions).to(self.index.device)
+        indptr_t = torch.from_numpy(indptr).to(self.index.device)
+        scores = self.index.score_pairs(q, indptr, pos_t)       # index positions are the global doc indices (segments are added in order)
+        return ranked_run(list(range(q.shape[0])) if qids is None else qids, scores, pos_t, pos_t, indptr_t, self.run_table())
+
     def get_index_name(self):
         return "flat_index"
 
@@ -693,6 +719,27 @@ class SparseRetrieval:
                             torch.zeros(0, dtype=torch.float32, device=dev)), qids
         return QueryCSR.cat(parts), qids
 
+    def inverse_id_map(self):
+        """str(collection id) -> document position of the inverted index, built once."""
+        if getattr(self, "_inverse", None) is None:
+            from .rerank import InverseIdMap
+            self._inverse = InverseIdMap(self.doc_ids)
+        return self._inverse
+
+    def score_candidates(self, sparse_query_vecs, qids, doc_id_lists):
+        """Exact scores of given candidates: sparse_query_vecs as _generate_query_vecs returns them (QueryCSR or the reference's list
+        of (cols, vals) pairs), doc_id_lists = one list of collection ids per query; an unknown id raises KeyError naming it (the
+        inverted index knows the documents that have a posting, doc_ids.pkl: one without any is unknown to it - HybridRetriever,
+        which also has the dense index's id table, scores such a document 0.0 instead).  No threshold: a candidate that shares no term with its query is kept with score 0.0.  Returns a RunResult sorted by (score
+        descending, document position ascending)."""
+        from .rerank import ranked_run
+        q = _as_query_csr(sparse_query_vecs, self._dev)
+        assert len(doc_id_lists) == len(q) == len(qids), (len(doc_id_lists), len(q), len(qids))
+        indptr, positions = self.inverse_id_map().positions(doc_id_lists)
+        pos_t = torch.from_numpy(positions).to(self._dev)
+        scores = self.hip_index.score_pairs(q.row_ptr, q.cols, q.vals, indptr, pos_t)
+        return ranked_run(qids, scores, pos_t, pos_t, torch.from_numpy(indptr).to(self._dev), self.doc_id_table())
+
     def doc_id_table(self):
         if getattr(self, "_doc_table", None) is None:
             self._doc_table = IdTable(_doc_id_table(self.doc_ids, self.sparse_index.nb_docs()))
@@ -910,7 +957,8 @@ class HybridRetriever(SparseRetrieval):
     def _sparse_retrieve(self, sparse_query_vecs, qids, threshold=0., topk=1000):
         return self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk)
 
-    def retrieve(self, q_loader, topk, id_dict=False, threshold=0.):
+    def _retrieve_both(self, q_loader, topk, threshold):
+        """The two searches and their files (sparse/run.json + q_stats.json, dense/run.json): shared by retrieve and retrieve_fused."""
         sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
         sparse_res, sparse_stats = self._sparse_retrieve(sparse_query_vecs, qids, threshold=threshold, topk=topk)
         dense_res = self._dense_retrieve(dense_query_vecs, qids, topk=topk)
@@ -918,4 +966,77 @@ class HybridRetriever(SparseRetrieval):
             json.dump(sparse_stats, handler)
         sparse_res.dump(os.path.join(self.sparse_out_dir, "run.json"))
         dense_res.dump(os.path.join(self.dense_out_dir, "run.json"))
-        return sparse_res, dense_res
+        return sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res
+
+    def retrieve(self, q_loader, topk, id_dict=False, threshold=0.):
+        return self._retrieve_both(q_loader, topk, threshold)[3:]
+
+    def _position_maps(self):
+        """The two indexes number documents independently: (dense position -> sparse position, -1 where the inverted index has no
+        such document, i.e. it has no posting), as a device tensor, built once."""
+        if getattr(self, "_d2s", None) is None:
+            inv = self.inverse_id_map()
+            d2s = np.fromiter((inv.get(d) for d in self.dense_index.index_id_to_db_id), dtype=np.int64,
+                              count=len(self.dense_index.index_id_to_db_id))
+            s2d = np.full(max(1, self.sparse_index.nb_docs(), int(d2s.max(initial=-1)) + 1), -1, np.int64)
+            s2d[d2s[d2s >= 0]] = np.nonzero(d2s >= 0)[0]
+            self._d2s = torch.from_numpy(d2s).to(self._dev)
+            self._s2d = torch.from_numpy(s2d).to(self._dev)
+        return self._d2s, self._s2d
+
+    def retrieve_fused(self, q_loader, topk, weights=(1.0, 1.0), threshold=0.):
+        """`retrieve` (the same two runs, the same bytes) plus {out_dir}/fused/run.json: per query the UNION of the two top-k lists,
+        taken over database ids, is scored by BOTH heads with the pair kernels (a document only one search found gets its other
+        score exactly, not a zero) and ranked by fused = float32(w_d * dense) + float32(w_s * sparse), top-k by (fused descending,
+        sparse-index position ascending; a document without a posting has sparse score 0.0 and sorts after every indexed one).
+        Every document of the inverted index must be in the dense index.  Returns (sparse_res, dense_res, fused_res)."""
+        from .rerank import fused_scores, ranked_run
+        sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res = self._retrieve_both(q_loader, topk, threshold)
+        dev, nq = self._dev, len(qids)
+        d2s, s2d = self._position_maps()
+        n_dense = int(d2s.numel())
+        sp = torch.from_numpy(sparse_res.positions).to(dev)
+        sp_valid = (sp >= 0) & (torch.arange(sp.shape[1], device=dev)[None, :] < torch.from_numpy(sparse_res.counts).to(dev)[:, None])
+        dp = torch.from_numpy(dense_res.positions).to(dev)
+        rows_s = torch.arange(nq, device=dev)[:, None].expand_as(sp)[sp_valid]
+        sp_as_dense = s2d[sp[sp_valid]]
+        if bool((sp_as_dense < 0).any()):
+            raise KeyError("retrieve_fused: the inverted index holds a document the dense index does not")
+        rows_d = torch.arange(nq, device=dev)[:, None].expand_as(dp)[dp >= 0]
+        keys = torch.unique(torch.cat([rows_s * n_dense + sp_as_dense, rows_d * n_dense + dp[dp >= 0]]))     # sorted: by query, then dense position
+        row, dpos = keys // max(1, n_dense), keys % max(1, n_dense)
+        indptr = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        indptr[1:] = torch.cumsum(torch.bincount(row, minlength=nq), 0)
+        q_dense = dense_query_vecs.to(device=dev, dtype=torch.float32)
+        dense_s = self.dense_index.index.score_pairs(q_dense, indptr, dpos)
+        spos = d2s[dpos]
+        sparse_s = self.hip_index.score_pairs(sparse_query_vecs.row_ptr, sparse_query_vecs.cols, sparse_query_vecs.vals, indptr,
+                                              torch.clamp(spos, min=0))
+        sparse_s = torch.where(spos >= 0, sparse_s, torch.zeros_like(sparse_s))
+        tie = torch.where(spos >= 0, spos, int(s2d.numel()) + dpos)
+        fused_res = ranked_run(qids, fused_scores(dense_s, sparse_s, weights), dpos, tie, indptr, self.dense_index.run_table(), topk=topk)
+        fused_dir = os.path.join(os.path.dirname(self.sparse_out_dir), "fused")
+        os.makedirs(fused_dir, exist_ok=True)
+        fused_res.dump(os.path.join(fused_dir, "run.json"))
+        return sparse_res, dense_res, fused_res
+
+    def score_candidates(self, sparse_query_vecs, qids, doc_id_lists, dense_query_vecs=None, weights=(1.0, 1.0)):
+        """With dense_query_vecs: both heads score the given candidates (database ids; each index is given its own positions) and
+        the rows are ranked by the fused score of retrieve_fused, ties by sparse-index position.  A document the dense index holds
+        but the inverted index does not (it has no posting) gets sparse score 0.0 and sorts after the indexed ones at equal score,
+        exactly as in retrieve_fused; an id the dense index does not hold is a KeyError.  Without dense_query_vecs: the sparse head
+        alone (SparseRetrieval.score_candidates)."""
+        if dense_query_vecs is None:
+            return super().score_candidates(sparse_query_vecs, qids, doc_id_lists)
+        from .rerank import fused_scores, ranked_run
+        q = _as_query_csr(sparse_query_vecs, self._dev)
+        indptr, dpos = self.dense_index.inverse_id_map().positions(doc_id_lists)      # KeyError: an id neither index knows
+        dpos_t = torch.from_numpy(dpos).to(self._dev)
+        d2s, s2d = self._position_maps()
+        spos_t = d2s[dpos_t]
+        dense_s = self.dense_index.index.score_pairs(dense_query_vecs.to(device=self._dev, dtype=torch.float32), indptr, dpos_t)
+        sparse_s = self.hip_index.score_pairs(q.row_ptr, q.cols, q.vals, indptr, torch.clamp(spos_t, min=0))
+        sparse_s = torch.where(spos_t >= 0, sparse_s, torch.zeros_like(sparse_s))     # no posting: no common term, 0.0 (as retrieve_fused)
+        tie = torch.where(spos_t >= 0, spos_t, int(s2d.numel()) + dpos_t)
+        return ranked_run(qids, fused_scores(dense_s, sparse_s, weights), dpos_t, tie, torch.from_numpy(indptr).to(self._dev),
+                          self.dense_index.run_table())

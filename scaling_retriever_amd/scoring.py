@@ -16,6 +16,32 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _to_dev(x, dt, device):
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    elif not torch.is_tensor(x):
+        x = torch.as_tensor(x)
+    return x.to(device=device, dtype=dt).contiguous()
+
+
+def _candidates(cand_indptr, cand_ids, nq, device):
+    """(indptr int64 [nq + 1], ids int64 [max(1, total)], total) on the device; the shape of the lists is checked on the host side
+    only where it is free (lengths), their content by the kernels."""
+    cand_indptr = _to_dev(cand_indptr, torch.int64, device)
+    cand_ids = _to_dev(cand_ids, torch.int64, device)
+    if cand_indptr.dim() != 1 or cand_indptr.numel() != nq + 1:
+        raise ValueError(f"expected cand_indptr of {nq + 1} entries, got {tuple(cand_indptr.shape)}")
+    if cand_ids.dim() != 1:
+        raise ValueError(f"expected 1-D cand_ids, got {tuple(cand_ids.shape)}")
+    total = cand_ids.numel()
+    # the kernels trust cand_indptr[nq] for the size of cand_ids and of the output: the one thing checked here
+    if int(cand_indptr[-1]) != total:
+        raise ValueError(f"cand_indptr ends at {int(cand_indptr[-1])}, cand_ids holds {total} ids")
+    if total == 0:
+        cand_ids = torch.zeros(1, dtype=torch.int64, device=device)      # keep a valid pointer
+    return cand_indptr, cand_ids, total
+
+
 class DenseIndexHIP:
     """Flat inner-product index resident in HBM (segments of fp32 [n, dim] rows)."""
 
@@ -190,6 +216,24 @@ class DenseIndexHIP:
                                                 _lib.stream_ptr()), "sr_dense_search")
         return scores, ids
 
+    def score_pairs(self, queries, cand_indptr, cand_ids):
+        """Exact scores of given (query, document) pairs: queries fp32 cuda [nq, dim]; the candidates of query q are
+        cand_ids[cand_indptr[q]:cand_indptr[q + 1]] (int64, the ids `search` returns; ragged, empty lists and repeats allowed, any
+        length).  Returns fp32 cuda [total] - for every nq the fmaf chain of the exact score kernel, i.e. what `search` returns for
+        that pair with more than 64 queries (include/sr_hip.h sr_dense_score_pairs).  An id outside the index: ValueError."""
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
+        if not queries.is_cuda or queries.device != self.device:
+            raise ValueError(f"queries must live on {self.device}")
+        queries = queries.contiguous()
+        nq = queries.shape[0]
+        cand_indptr, cand_ids, total = _candidates(cand_indptr, cand_ids, nq, self.device)
+        out = torch.empty((max(1, total),), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sr_dense_score_pairs(self._h, _ptr(queries), nq, _ptr(cand_indptr), _ptr(cand_ids), _ptr(out),
+                                                     _lib.stream_ptr()), "sr_dense_score_pairs")
+        return out[:total]
+
     def search_begin(self, queries, k, share):
         """First half of a doc-sharded search (include/sr_hip.h sr_dense_search_begin): returns lower [nq] fp32 (cuda) - per
         query a value at least ceil(k / share) documents of this index reach exactly (-inf where the filter does not apply).
@@ -326,6 +370,24 @@ class SparseIndexHIP:
                                                  float(threshold), int(id_base), int(id_stride), _ptr(scores), _ptr(ids),
                                                  _ptr(counts), _lib.stream_ptr()), "sr_sparse_search")
         return scores, ids, counts
+
+    def score_pairs(self, q_indptr, q_cols, q_vals, cand_indptr, cand_ids):
+        """Exact scores of given (query, document) pairs: queries as for `search`, candidates as for DenseIndexHIP.score_pairs (ids =
+        document positions).  Returns fp32 cuda [total]: the reference's term-serial chain, no threshold, 0.0 where nothing matches
+        (include/sr_hip.h sr_sparse_score_pairs).  An id outside [0, n_docs): ValueError."""
+        q_indptr = _to_dev(q_indptr, torch.int64, self.device)
+        q_cols = _to_dev(q_cols, torch.int32, self.device)
+        q_vals = _to_dev(q_vals, torch.float32, self.device)
+        nq = q_indptr.numel() - 1
+        if q_cols.numel() == 0:
+            q_cols = torch.zeros(1, dtype=torch.int32, device=self.device)
+            q_vals = torch.zeros(1, dtype=torch.float32, device=self.device)
+        cand_indptr, cand_ids, total = _candidates(cand_indptr, cand_ids, nq, self.device)
+        out = torch.empty((max(1, total),), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sr_sparse_score_pairs(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(cand_indptr),
+                                                      _ptr(cand_ids), _ptr(out), _lib.stream_ptr()), "sr_sparse_score_pairs")
+        return out[:total]
 
     def close(self):
         if self._h:
