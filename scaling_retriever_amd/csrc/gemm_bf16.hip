@@ -57,6 +57,29 @@ typedef __attribute__((address_space(1))) const void* gbl_void_ptr;
 
 #define G_BK 64
 
+// ---- the facts about an epilogue, for the kernel and for the launch code (kernels.h documents the enum) ----
+template <int EPI>
+struct EpiTraits {
+    // fp16 plane operands + row scales (fp32 regime), see kernels.h
+    static constexpr bool F16 = EPI >= EPI_H_FIRST && EPI != EPI_SWIGLU_SPLITH_BASE;
+    // base behaviour: what runs on the accumulators once the row scales are undone (a base behaviour is its own)
+    static constexpr int BASE = !F16 ? EPI : (EPI == EPI_QKV_ROPE_F32_H ? EPI_QKV_ROPE_F32 : (EPI == EPI_RESID_F32_H ? EPI_RESID_F32
+                                      : (EPI == EPI_SWIGLU_F32_H ? EPI_SWIGLU_F32 : (EPI == EPI_SWIGLU_SPLIT_H ? EPI_SWIGLU_SPLITH_BASE : EPI_SEGMAX))));
+    static constexpr bool QKV_ROPE = BASE == EPI_QKV_ROPE || BASE == EPI_QKV_ROPE_F32;
+    static constexpr bool SWIGLU = BASE == EPI_SWIGLU || BASE == EPI_SWIGLU_F32 || BASE == EPI_SWIGLU_SPLIT || BASE == EPI_SWIGLU_SPLITH_BASE;
+    static constexpr bool SEGMAX = BASE == EPI_SEGMAX;       // folds into out[seq_of[m]] with atomics: no C rows of its own
+    static constexpr int OUT_BYTES = (BASE == EPI_STORE_F32 || BASE == EPI_RESID_F32 || BASE == EPI_QKV_ROPE_F32 || BASE == EPI_SWIGLU_F32 || SEGMAX) ? 4 : 2;
+    // the four-wave loop (KL = 1) has an epilogue staged through LDS for these; no other epilogue runs behind it
+    static constexpr bool STAGED_4W = BASE == EPI_STORE_BF16 || BASE == EPI_SWIGLU || BASE == EPI_QKV_ROPE || BASE == EPI_STORE_F32 ||
+                                      BASE == EPI_RESID_F32 || BASE == EPI_SWIGLU_SPLITH_BASE;
+    // output features per segment and segments per row of C: SwiGLU halves N, the split variants repeat it per plane
+    static __host__ __device__ __forceinline__ int out_features(const GemmArgs& g) { return SWIGLU ? (g.N >> 1) : g.N; }
+    static __host__ __device__ __forceinline__ int out_segments(const GemmArgs& g) {
+        return BASE == EPI_SWIGLU_SPLIT ? g.out_map.n_seg : (BASE == EPI_SWIGLU_SPLITH_BASE ? g.out_nseg : 1);
+    }
+    static __host__ __device__ __forceinline__ int64_t out_ld(const GemmArgs& g) { return (int64_t)out_segments(g) * out_features(g); }
+};
+
 // WAVES_N x WAVES_M waves; each wave owns (16 * NB) features x (16 * MB) tokens.
 // PIPE: fragment double-buffering - the ds_reads of the next half k-step are in flight while the MFMAs of the current
 // half run, stages are issued two k-steps ahead, still one barrier per k-step (placed between the two halves).
@@ -66,9 +89,9 @@ typedef int sr_i32x4 __attribute__((ext_vector_type(4)));
 template <int EPI, int WAVES_N, int WAVES_M, int NB, int MB, bool PIPE = false, int NS = 2, int KL = 0>
 __global__ __launch_bounds__(64 * WAVES_N * WAVES_M, KL == 1 ? 1 : (WAVES_N * WAVES_M) / 4 * (WAVES_N * WAVES_M == 4 ? 2 : 1))
 void gemm_bf16_kernel(GemmArgs g) {
-    constexpr bool F16 = EPI >= EPI_H_FIRST;          // fp16 plane operands + row scales (fp32 regime), see kernels.h
-    constexpr int BEPI = !F16 ? EPI : (EPI == EPI_QKV_ROPE_F32_H ? EPI_QKV_ROPE_F32 : (EPI == EPI_RESID_F32_H ? EPI_RESID_F32
-                                      : (EPI == EPI_SWIGLU_F32_H ? EPI_SWIGLU_F32 : (EPI == EPI_SWIGLU_SPLIT_H ? EPI_SWIGLU_SPLITH_BASE : EPI_SEGMAX))));
+    using E = EpiTraits<EPI>;
+    constexpr bool F16 = E::F16;
+    constexpr int BEPI = E::BASE;
     constexpr int NW = WAVES_N * WAVES_M;
     constexpr int BN = 16 * NB * WAVES_N, BM = 16 * MB * WAVES_M;
     constexpr int W_BYTES = BN * 128, A_BYTES = BM * 128, STAGE_BYTES = W_BYTES + A_BYTES;
@@ -80,7 +103,6 @@ void gemm_bf16_kernel(GemmArgs g) {
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
     const int n_tiles = tiles_n * tiles_m;
     const int K = g.K;
-    constexpr bool CROSS_PREFETCH = true;
 
     // ---- staging addresses: wave w moves rows [w*R, (w+1)*R) of each tile, 8 rows per instruction
     const int srow = lane >> 3;                       // row inside an 8-row piece
@@ -205,6 +227,27 @@ void gemm_bf16_kernel(GemmArgs g) {
             for (int j = 0; j < MB; ++j)
                 acc[i][j] = sr_mma<F16>(wf[i], af[j], acc[i][j]);
     };
+    // the pipelined loops work on half of the wave's feature blocks at a time: fragments of k-half kk, half h of the feature blocks /
+    // all of the token blocks, and the MFMAs of one such phase
+    constexpr int HB = NB / 2;
+    [[maybe_unused]] auto load_w = [&](int st, int kk, int h, mfma_bf16x8 (&wf)[HB]) {
+        const unsigned char* wt = smem + st * STAGE_BYTES;
+        const int pos = ((4 * kk + fg) ^ (frow & 7)) * 16;
+#pragma unroll
+        for (int i = 0; i < HB; ++i)
+            wf[i] = *reinterpret_cast<const mfma_bf16x8*>(wt + (wn * NB * 16 + (h * HB + i) * 16 + frow) * 128 + pos);
+    };
+    [[maybe_unused]] auto load_a = [&](int st, int kk, mfma_bf16x8 (&af)[MB]) {
+        const unsigned char* at = smem + st * STAGE_BYTES + W_BYTES;
+        const int pos = ((4 * kk + fg) ^ (frow & 7)) * 16;
+#pragma unroll
+        for (int j = 0; j < MB; ++j)
+            af[j] = *reinterpret_cast<const mfma_bf16x8*>(at + (wm * MB * 16 + j * 16 + frow) * 128 + pos);
+    };
+#define SR_MFMA_HALF(H, WF, AF)                                                                              \
+        _Pragma("unroll") for (int i = 0; i < HB; ++i)                                                       \
+            _Pragma("unroll") for (int j = 0; j < MB; ++j)                                                   \
+                acc[(H) * HB + i][j] = sr_mma<F16>(WF[i], AF[j], acc[(H) * HB + i][j]);
     if constexpr (KL == 1) {
         const uint32_t lds0 = (uint32_t)(size_t)(lds_void_ptr)smem;
         const int wave_s = __builtin_amdgcn_readfirstlane(wave);
@@ -232,7 +275,7 @@ void gemm_bf16_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < MB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     int sj[MB];      // EPI_SEGMAX: sequence ids of this lane's token rows, fetched here so that the k-loop covers the latency
-    if constexpr (BEPI == EPI_SEGMAX) {
+    if constexpr (E::SEGMAX) {
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
             const int m = m0 + wm * MB * 16 + j * 16 + frow;
@@ -297,13 +340,11 @@ void gemm_bf16_kernel(GemmArgs g) {
         //   reads of the next k-step's k-half 0 (other stage): one per KL_RD2_EVERY MFMAs; lgkmcnt(0) at the end.
         // The LDS pipe is 75 % busy over a k-step (128 KB of fragment reads + 64 KB of landing pieces against 2 048 MFMA cycles),
         // so where the reads sit matters: clustered reads make the wait in front of a barrier stall the MFMA stream.
-#ifndef KL_RD1_EVERY
 #define KL_RD1_EVERY 2
 #define KL_B1_AT 39
 #define KL_DMA_EVERY 3
 #define KL_B2_AT 87
 #define KL_RD2_EVERY 2
-#endif
         static_assert(16 * KL_RD1_EVERY - 1 <= KL_B1_AT && KL_B1_AT + 16 * KL_DMA_EVERY <= KL_B2_AT && KL_B2_AT + 16 * KL_RD2_EVERY <= 127,
                       "k-step schedule");
         auto kstep = [&]() {
@@ -400,31 +441,18 @@ void gemm_bf16_kernel(GemmArgs g) {
 #undef KL_MMA_N
 #undef KL_MMA_G
 #undef KL_DSR_N
+#undef KL_RD1_EVERY
+#undef KL_B1_AT
+#undef KL_DMA_EVERY
+#undef KL_B2_AT
+#undef KL_RD2_EVERY
     } else if constexpr (PIPE && NS > 2) {
         // NS LDS stages (small tiles, where a workgroup has a CU's MFMA pipe to itself or shares it with one other):
         // the LDS-DMA of k-step kt + NS is issued when k-step kt's stage is released, so a piece has NS - 1 k-steps to
         // land and the wait before the barrier only covers pieces issued NS - 1 k-steps ago (counted vmcnt; the barrier is
         // a bare s_barrier - __syncthreads() would drain every outstanding piece).  Same four phases as below.
-        constexpr int HB = NB / 2, PIECES = W_INSTR + A_INSTR;
+        constexpr int PIECES = W_INSTR + A_INSTR;
         mfma_bf16x8 wx[HB], wy[HB], a0[MB], a1[MB];
-        auto load_w = [&](int st, int kk, int h, mfma_bf16x8 (&wf)[HB]) {
-            const unsigned char* wt = smem + st * STAGE_BYTES;
-            const int pos = ((4 * kk + fg) ^ (frow & 7)) * 16;
-#pragma unroll
-            for (int i = 0; i < HB; ++i)
-                wf[i] = *reinterpret_cast<const mfma_bf16x8*>(wt + (wn * NB * 16 + (h * HB + i) * 16 + frow) * 128 + pos);
-        };
-        auto load_a = [&](int st, int kk, mfma_bf16x8 (&af)[MB]) {
-            const unsigned char* at = smem + st * STAGE_BYTES + W_BYTES;
-            const int pos = ((4 * kk + fg) ^ (frow & 7)) * 16;
-#pragma unroll
-            for (int j = 0; j < MB; ++j)
-                af[j] = *reinterpret_cast<const mfma_bf16x8*>(at + (wm * MB * 16 + j * 16 + frow) * 128 + pos);
-        };
-#define SR_MFMA_HALF(H, WF, AF)                                                                              \
-        _Pragma("unroll") for (int i = 0; i < HB; ++i)                                                       \
-            _Pragma("unroll") for (int j = 0; j < MB; ++j)                                                   \
-                acc[(H) * HB + i][j] = sr_mma<F16>(WF[i], AF[j], acc[(H) * HB + i][j]);
         load_w(buf, 0, 0, wx);
         load_a(buf, 0, a0);
         int kt = 0;
@@ -481,32 +509,12 @@ void gemm_bf16_kernel(GemmArgs g) {
             SR_MFMA_HALF(1, wy, a1)
             buf = nxt;
         }
-#undef SR_MFMA_HALF
     } else if constexpr (PIPE) {
         // 4 phases per k-step: (kk, half of the wave's feature blocks).  While a phase's 16 MFMAs run, the fragments of the
         // next phase are being read from LDS (rolling wx / wy, a0 / a1).  The k-step barrier sits before the LAST phase's
         // MFMAs: by then every read of stage `buf` has been issued and waited for, so the stage can be refilled (k-step
         // kt + 2) and the next k-step's first fragments can be requested from stage buf ^ 1 under those MFMAs.
-        constexpr int HB = NB / 2;
         mfma_bf16x8 wx[HB], wy[HB], a0[MB], a1[MB];
-        auto load_w = [&](int st, int kk, int h, mfma_bf16x8 (&wf)[HB]) {
-            const unsigned char* wt = smem + st * STAGE_BYTES;
-            const int pos = ((4 * kk + fg) ^ (frow & 7)) * 16;
-#pragma unroll
-            for (int i = 0; i < HB; ++i)
-                wf[i] = *reinterpret_cast<const mfma_bf16x8*>(wt + (wn * NB * 16 + (h * HB + i) * 16 + frow) * 128 + pos);
-        };
-        auto load_a = [&](int st, int kk, mfma_bf16x8 (&af)[MB]) {
-            const unsigned char* at = smem + st * STAGE_BYTES + W_BYTES;
-            const int pos = ((4 * kk + fg) ^ (frow & 7)) * 16;
-#pragma unroll
-            for (int j = 0; j < MB; ++j)
-                af[j] = *reinterpret_cast<const mfma_bf16x8*>(at + (wm * MB * 16 + j * 16 + frow) * 128 + pos);
-        };
-#define SR_MFMA_HALF(H, WF, AF)                                                                              \
-        _Pragma("unroll") for (int i = 0; i < HB; ++i)                                                       \
-            _Pragma("unroll") for (int j = 0; j < MB; ++j)                                                   \
-                acc[(H) * HB + i][j] = sr_mma<F16>(WF[i], AF[j], acc[(H) * HB + i][j]);
         load_w(buf, 0, 0, wx);
         load_a(buf, 0, a0);
         int kt = 0;
@@ -576,12 +584,11 @@ void gemm_bf16_kernel(GemmArgs g) {
             SR_MFMA_HALF(1, wy, a1)
             buf ^= 1;
         }
-#undef SR_MFMA_HALF
     } else {
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + 1 < nk) {
             stage(buf ^ 1, (kt + 1) * G_BK);
-        } else if (CROSS_PREFETCH && has_next) {
+        } else if (has_next) {
             set_tile(tile_next);
             stage(buf ^ 1, 0);
         }
@@ -596,6 +603,7 @@ void gemm_bf16_kernel(GemmArgs g) {
     }
     }
 
+#undef SR_MFMA_HALF
     if (stamp && titer < 16) stp[titer * 4 + 2] = __builtin_amdgcn_s_memrealtime();
     if (stamp && titer == 1) stp[63] = __builtin_amdgcn_s_memtime();        // ... and at its end: clock = d(memtime) / d(realtime) * 100 MHz
     if constexpr (F16) {       // undo the power-of-two row scales of both operands (exact)
@@ -617,18 +625,15 @@ void gemm_bf16_kernel(GemmArgs g) {
         }
     }
     // ---- epilogues: lane owns token m = .. + (lane & 15), features n = .. + 4 * (lane >> 4) + r
-#ifdef KL_NO_STAGING
-    constexpr bool KL_STAGED = false;
-#else
-    constexpr bool KL_STAGED = KL == 1 && (BEPI == EPI_STORE_BF16 || BEPI == EPI_SWIGLU || BEPI == EPI_QKV_ROPE);
-#endif
+    static_assert(KL == 0 || E::STAGED_4W, "the four-wave loop has no staged epilogue for this one");
+    constexpr bool KL_STAGED = KL == 1 && (BEPI == EPI_STORE_BF16 || BEPI == EPI_SWIGLU || BEPI == EPI_QKV_ROPE);      // the bf16 outputs share one staged epilogue
     // The workgroup is persistent: whatever an epilogue computes from the lane index alone (feature offsets, n % head_dim, swizzled
     // LDS offsets ...) is invariant in the TILE loop, and hipcc hoists it above the k-loop and carries it through - behind the
     // asm-pinned four-wave loop that meant accumulators spilled to scratch INSIDE the k-loop (QKV + RoPE epilogues: query encode 300
     // -> 670 ms).  The staged epilogues therefore see the lane coordinates through an opaque asm: nothing of them can be hoisted.
     [[maybe_unused]] int frow_e = frow, fg_e = fg, lane_e = lane;
     if constexpr (KL == 1) asm volatile("" : "+v"(frow_e), "+v"(fg_e), "+v"(lane_e));
-    if constexpr ((BEPI == EPI_QKV_ROPE || BEPI == EPI_QKV_ROPE_F32) && !KL_STAGED) {
+    if constexpr (E::QKV_ROPE && !KL_STAGED) {
         // Qwen2: q_proj / k_proj / v_proj carry a bias.  It is added in fp32 to every accumulator BEFORE the rotation (a rotation partner
         // gets its own element: each block i adds bias[n(i) ..]) and, on fp16 planes, after the row scales above - the bias lives in the
         // unscaled domain.  One pass in front of the direct-store epilogue of every tile configuration; the staged epilogue of the
@@ -654,14 +659,14 @@ void gemm_bf16_kernel(GemmArgs g) {
         // wave lays the 16 token rows of one block column into LDS behind the two stages and reads them back as whole rows - 16
         // bytes per lane_e, 4 rows x 256 bytes (SwiGLU: 8 rows x 128 bytes) per store instruction: full cache lines, a quarter of
         // the store instructions (8 -> 4.2 us, +6 % on the layer's GEMMs).  LDS operations of one wave execute in order: no barrier.
-        constexpr int OUT_F = BEPI == EPI_SWIGLU ? 64 : 128;           // output features per token row of this wave
+        constexpr int OUT_F = E::SWIGLU ? 64 : 128;           // output features per token row of this wave
         constexpr int ROWB = OUT_F * 2, NP = ROWB / 16;                // bytes and 16-byte pieces per staged row
         // two 4 KB buffers per wave (block columns alternate: the conversion and writes of column j + 1 do not wait for the
         // reads of column j), rows unpadded with the 16-byte pieces XOR-swizzled by the row: 2 x 4 x 4 KB = the 32 KB the two
         // stages leave of the CU's 160 KB
         unsigned char* const stg0 = smem + 2 * STAGE_BYTES + wave * 8192;
-        const int ldc = BEPI == EPI_SWIGLU ? (g.N >> 1) : g.N;
-        const int nb = (BEPI == EPI_SWIGLU ? (n0 >> 1) : n0) + wn * OUT_F;      // first output feature of this wave
+        const int ldc = E::out_features(g);
+        const int nb = (E::SWIGLU ? (n0 >> 1) : n0) + wn * OUT_F;      // first output feature of this wave
         unsigned char* stg = stg0;
         auto put = [&](int f_local, const f32x4& v) {                          // 4 consecutive output features of token row frow_e
             bf16x4 o;
@@ -795,7 +800,7 @@ void gemm_bf16_kernel(GemmArgs g) {
         unsigned char* const stg0 = smem + 2 * STAGE_BYTES + wave * 8192;
         const int half_n = g.N >> 1;
         const bool seg3 = g.out_nseg == 3;
-        const int64_t ldc = (int64_t)g.out_nseg * half_n;
+        const int64_t ldc = E::out_ld(g);
         const int nb = (n0 >> 1) + wn * 64;
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
@@ -852,9 +857,6 @@ void gemm_bf16_kernel(GemmArgs g) {
                     o[1] = (short)f32_to_bf16(v[1]);
                     o[2] = (short)f32_to_bf16(v[2]);
                     o[3] = (short)f32_to_bf16(v[3]);
-#ifdef KL_DIAG_NOSTORE      // timing diagnostic (variant builds only): the epilogue without its stores (one lane keeps the values alive)
-                    if (o[0] == 12345 && o[1] == 23456 && lane == 77)
-#endif
                     *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(g.C) + (int64_t)m * g.N + n) = o;
                 } else if constexpr (BEPI == EPI_STORE_F32) {
                     *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.C) + (int64_t)m * g.N + n) = v;
@@ -866,12 +868,12 @@ void gemm_bf16_kernel(GemmArgs g) {
                 }
             }
         }
-    } else if constexpr (BEPI == EPI_QKV_ROPE || BEPI == EPI_QKV_ROPE_F32) {
+    } else if constexpr (E::QKV_ROPE) {
         // q/k heads: out[d] = x[d] cos - x[d + hd/2] sin, out[d + hd/2] = x[d + hd/2] cos + x[d] sin (HF rotate_half),
         // in fp32 on the accumulators; both halves of a head live in this lane (blocks i and i + hd/32).
         // A wave's feature range (16 * NB) covers whole heads: NB * 16 % head_dim == 0 is checked at launch.
         // EPI_QKV_ROPE_F32 (fp32 regime) stores the rotated fp32 values as they are.
-        constexpr bool F32OUT = BEPI == EPI_QKV_ROPE_F32;
+        constexpr bool F32OUT = E::OUT_BYTES == 4;
         const int hd = g.head_dim, hb = hd / 32;   // hb = block distance between rotation partners
         auto put = [&](int64_t off, const f32x4& v) {
             if constexpr (F32OUT) {
@@ -952,7 +954,7 @@ void gemm_bf16_kernel(GemmArgs g) {
         // max_j |wg_j||wu_j|: no overflow.
         const int half_n = g.N >> 1;
         const bool seg3 = g.out_nseg == 3;
-        const int64_t ldc = (int64_t)g.out_nseg * half_n;
+        const int64_t ldc = E::out_ld(g);
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
             const int m = m0 + wm * MB * 16 + j * 16 + frow;
@@ -982,7 +984,7 @@ void gemm_bf16_kernel(GemmArgs g) {
         // segments the down_proj GEMM consumes: C [M, n_seg * N/2], segment sg holds plane out_map.plane[sg]
         const int half_n = g.N >> 1;
         const int nsg = g.out_map.n_seg;
-        const int64_t ldc = (int64_t)nsg * half_n;
+        const int64_t ldc = E::out_ld(g);
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
             const int m = m0 + wm * MB * 16 + j * 16 + frow;
@@ -1101,11 +1103,10 @@ static int launch_cfg(const GemmArgs& g_in, hipStream_t s) {
     g.xcd_order = 1;
     if (const char* e = sr_dev_getenv("SR_GEMM_XCD")) g.xcd_order = atoi(e);       // A/B switch
     int64_t tiles = ceil_div64(g.N, BN) * ceil_div64(g.M, BM);
-    const char* env = sr_dev_getenv("SR_GEMM_PERSIST");            // A/B switch: 0 = one workgroup per tile
     // resident workgroups on 256 CUs: one 8-wave workgroup, up to 3 of 4 waves, up to 8 single-wave ones (LDS permitting)
     constexpr int64_t by_lds = (160 * 1024) / lds;
     const int64_t slots = 256 * (WAVES_N * WAVES_M == 4 ? (by_lds > 3 ? 3 : by_lds) : (WAVES_N * WAVES_M == 1 ? (by_lds > 8 ? 8 : by_lds) : 1));
-    if (!(env && *env == '0') && tiles > slots) tiles = slots;
+    if (tiles > slots) tiles = slots;      // persistent workgroups: at most one round of them
     hipLaunchKernelGGL((gemm_bf16_kernel<EPI, WAVES_N, WAVES_M, NB, MB, PIPE, NS, KL>), dim3((unsigned)tiles), dim3(64 * WAVES_N * WAVES_M), lds,
                        s, g);
     SR_CHECK_LAUNCH();
@@ -1159,18 +1160,8 @@ static int plan_big_rows(const GemmArgs& g, bool small_allowed) {
 
 template <int EPI>
 static int launch_big(const GemmArgs& g, hipStream_t s) {
-    if constexpr (EPI == EPI_STORE_BF16 || EPI == EPI_SWIGLU || EPI == EPI_QKV_ROPE) {
-        // A/B switch: SR_GEMM_BIG=s3 -> 256 x 128 tile, 8 waves, THREE 48 KB LDS stages (LDS-DMA issued three k-steps ahead)
-        const char* big = sr_dev_getenv("SR_GEMM_BIG");
-        if (big && big[0] == 's' && big[1] == '3' && g.K / G_BK >= 4) {
-            if constexpr (EPI == EPI_QKV_ROPE) {
-                if (g.head_dim == 64) return launch_cfg<EPI, 2, 4, 8, 2, true, 3>(g, s);
-            } else {
-                return launch_cfg<EPI, 2, 4, 8, 2, true, 3>(g, s);
-            }
-        }
-    }
-    const char* env = sr_dev_getenv("SR_GEMM_PIPE");   // A/B switch: 0 = plain double-buffered loop
+    using E = EpiTraits<EPI>;
+    const bool pipe = g.K / G_BK >= 4;      // the pipelined k-loops need >= 4 k-steps
     {
         // The four-wave loop is the default for the bf16 regime's plain-store / residual / SwiGLU GEMMs (o_proj, down_proj, gate-up:
         // 88 % of a layer's GEMM work; +7-10 % on those, corpus encode 7 590 -> 8 390 passages/s).  SR_GEMM_BIG=8w: the 8-wave loop
@@ -1183,37 +1174,27 @@ static int launch_big(const GemmArgs& g, hipStream_t s) {
         // rows with 32-bit byte offsets: 256 rows x 2 K bytes must stay below 2^31.
         const char* big = sr_dev_getenv("SR_GEMM_BIG");
         const bool want8 = big && big[0] == '8', want4 = big && big[0] == '4';
-        constexpr bool STAGED_BF16 = EPI == EPI_STORE_BF16 || EPI == EPI_SWIGLU || EPI == EPI_STORE_F32 || EPI == EPI_RESID_F32 || EPI == EPI_QKV_ROPE;
-        constexpr bool STAGED_F16 = EPI == EPI_RESID_F32_H || EPI == EPI_SWIGLU_SPLIT_H;
-        if constexpr (STAGED_BF16 || STAGED_F16) {
+        if constexpr (E::STAGED_4W) {
             // QKV + RoPE: a wave's 128 features must lie on one side of n_rope (two heads of 64 per wave)
-            const bool rope_ok = EPI != EPI_QKV_ROPE || g.n_rope % 128 == 0;
-            if (g.K / G_BK >= 4 && (int64_t)g.K * 512 < (1ll << 31) && !want8 && (STAGED_BF16 || want4) && rope_ok && !(env && *env == '0'))
+            const bool rope_ok = !E::QKV_ROPE || g.n_rope % 128 == 0;
+            if (pipe && (int64_t)g.K * 512 < (1ll << 31) && !want8 && (!E::F16 || want4) && rope_ok)
                 return launch_cfg<EPI, 2, 2, 8, 8, true, 2, 1>(g, s);
         }
     }
-    if (g.K / G_BK >= 4 && !(env && *env == '0')) return launch_cfg<EPI, 2, 4, 8, 4, true>(g, s);
+    if (pipe) return launch_cfg<EPI, 2, 4, 8, 4, true>(g, s);
     return launch_cfg<EPI, 2, 4, 8, 4, false>(g, s);
-}
-
-static bool env_off(const char* name) {
-    const char* e = sr_dev_getenv(name);
-    return e && *e == '0';
 }
 
 template <int EPI>
 static int launch_small(const GemmArgs& g, hipStream_t s) {
-    const bool pipe = g.K / G_BK >= 4 && !env_off("SR_GEMM_PIPE");      // the pipelined k-loop needs >= 4 k-steps
-    if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_F32 || EPI == EPI_QKV_ROPE_F32_H) {
+    const bool pipe = g.K / G_BK >= 4;      // the pipelined k-loops need >= 4 k-steps
+    if constexpr (EpiTraits<EPI>::QKV_ROPE) {
         if (g.head_dim == 128) return launch_cfg<EPI, 1, 4, 8, 2>(g, s);        // 128 x 128 tile, wave = 128 features x 32 tokens
-    }
-    if constexpr (EPI != EPI_QKV_ROPE && EPI != EPI_QKV_ROPE_F32 && EPI != EPI_QKV_ROPE_F32_H) {
+    } else {
         // few 128^2 tiles (a short tail behind the 256^2 rounds, or a small problem): halve the token tile so that two or
         // three workgroups share every CU instead of one 4-wave workgroup idling half its MFMA pipe
         const int64_t t128 = ceil_div64(g.N, 128) * ceil_div64(g.M, 128);
-        if (t128 < 384 && g.M > 64 && !env_off("SR_GEMM_TAIL64"))
-            return pipe ? (env_off("SR_GEMM_NS3") ? launch_cfg<EPI, 2, 2, 4, 2, true>(g, s) : launch_cfg<EPI, 2, 2, 4, 2, true, 3>(g, s))
-                        : launch_cfg<EPI, 2, 2, 4, 2>(g, s);
+        if (t128 < 384 && g.M > 64) return pipe ? launch_cfg<EPI, 2, 2, 4, 2, true, 3>(g, s) : launch_cfg<EPI, 2, 2, 4, 2>(g, s);
     }
     return pipe ? launch_cfg<EPI, 2, 2, 4, 4, true>(g, s) : launch_cfg<EPI, 2, 2, 4, 4>(g, s);
 }
@@ -1224,11 +1205,8 @@ static GemmArgs rows_from(const GemmArgs& g, int row0) {
     GemmArgs t = g;
     t.A = g.A + (int64_t)row0 * g.K;
     t.M = g.M - row0;
-    const int64_t ldc = (EPI == EPI_SWIGLU || EPI == EPI_SWIGLU_F32 || EPI == EPI_SWIGLU_F32_H)
-                            ? g.N / 2 : (EPI == EPI_SWIGLU_SPLIT ? (int64_t)g.out_map.n_seg * (g.N / 2) : (EPI == EPI_SWIGLU_SPLIT_H ? (int64_t)g.out_nseg * (g.N / 2) : g.N));
-    const int64_t esz = (EPI == EPI_STORE_F32 || EPI == EPI_RESID_F32 || EPI == EPI_QKV_ROPE_F32 || EPI == EPI_SWIGLU_F32 ||
-                         (EPI >= EPI_H_FIRST && EPI != EPI_SWIGLU_SPLIT_H)) ? 4 : 2;
-    if constexpr (EPI != EPI_SEGMAX && EPI != EPI_SEGMAX_H) t.C = reinterpret_cast<unsigned char*>(g.C) + (int64_t)row0 * ldc * esz;
+    using E = EpiTraits<EPI>;
+    if constexpr (!E::SEGMAX) t.C = reinterpret_cast<unsigned char*>(g.C) + (int64_t)row0 * E::out_ld(g) * E::OUT_BYTES;
     if (g.a_scale) t.a_scale = g.a_scale + row0;
     if (g.out_scale) t.out_scale = g.out_scale + row0;
     if (g.seq_of) t.seq_of = g.seq_of + row0;
@@ -1246,20 +1224,24 @@ static int skinny_max_rows() {
 
 template <int EPI>
 static int launch_one(const GemmArgs& g, hipStream_t s) {
-    if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_F32 || EPI == EPI_QKV_ROPE_F32_H) {
+    using E = EpiTraits<EPI>;
+    SR_REQUIRE(g.N % 16 == 0 && (!E::SWIGLU || g.N % 32 == 0), "gemm: N=%d must be a multiple of 16 (32 for SwiGLU)", g.N);
+    SR_REQUIRE(!E::F16 || (g.a_scale && g.w_scale), "gemm(fp16 planes): missing row scales");
+    SR_REQUIRE(!g.bias || E::QKV_ROPE, "gemm: epilogue %d takes no bias (only the QKV + RoPE epilogues add one)", EPI);
+    if constexpr (E::QKV_ROPE) {
         SR_REQUIRE(g.head_dim == 64 || g.head_dim == 128, "gemm(qkv+rope): head_dim %d not supported", g.head_dim);
         SR_REQUIRE(g.pos && g.rope_cos && g.rope_sin && g.n_rope % g.head_dim == 0 && g.n_rope <= g.N && g.N % g.head_dim == 0,
                    "gemm(qkv+rope): bad rope arguments");
     }
     if (g.M <= skinny_max_rows() && g.K / G_BK >= 4) {
         if (g.M > 32) {
-            if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_F32 || EPI == EPI_QKV_ROPE_F32_H) {
+            if constexpr (E::QKV_ROPE) {
                 if (g.head_dim == 128) return launch_cfg<EPI, 1, 1, 8, 4, true, 3>(g, s);
             }
             return launch_cfg<EPI, 1, 1, 4, 4, true, 4>(g, s);
         }
         if (g.M > 16) {
-            if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_F32 || EPI == EPI_QKV_ROPE_F32_H) {
+            if constexpr (E::QKV_ROPE) {
                 if (g.head_dim == 128) return launch_cfg<EPI, 1, 1, 8, 2, true, 4>(g, s);
             }
             return launch_cfg<EPI, 1, 1, 4, 2, true, 4>(g, s);
@@ -1267,7 +1249,7 @@ static int launch_one(const GemmArgs& g, hipStream_t s) {
         // A handful of tokens (online queries): the work is streaming W once.  One WAVE per workgroup owns 64 features x 16
         // tokens (N / 64 independent workgroups instead of N / 128 four-wave ones idling on a 16-token tile), four 10 KB LDS
         // stages keep three k-steps of weights in flight per wave.  Same MFMA chain per output element as every other tile.
-        if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_F32 || EPI == EPI_QKV_ROPE_F32_H) {
+        if constexpr (E::QKV_ROPE) {
             if (g.head_dim == 128) return launch_cfg<EPI, 1, 1, 8, 1, true, 4>(g, s);
         }
         return launch_cfg<EPI, 1, 1, 4, 1, true, 4>(g, s);
@@ -1287,18 +1269,12 @@ int launch_gemm_bf16(GemmEpilogue epi, const GemmArgs& g, hipStream_t s) {
     SR_REQUIRE(g.M >= 0 && g.N > 0 && g.K > 0, "gemm: bad shape M=%d N=%d K=%d", g.M, g.N, g.K);
     if (g.M == 0) return SR_OK;
     SR_REQUIRE(g.K % G_BK == 0, "gemm: K=%d must be a multiple of %d", g.K, G_BK);
-    const bool swiglu = epi == EPI_SWIGLU || epi == EPI_SWIGLU_SPLIT || epi == EPI_SWIGLU_F32 || epi == EPI_SWIGLU_F32_H || epi == EPI_SWIGLU_SPLIT_H;
     SR_REQUIRE(epi != EPI_SWIGLU_SPLIT_H || g.out_scale, "gemm(swiglu split, fp16 planes): missing output row scales");
     SR_REQUIRE(epi != EPI_SWIGLU_SPLIT_H || g.out_nseg == 2 || g.out_nseg == 3, "gemm(swiglu split, fp16 planes): out_nseg %d is not 2 or 3",
                g.out_nseg);
-    SR_REQUIRE(g.N % 16 == 0 && (!swiglu || g.N % 32 == 0), "gemm: N=%d must be a multiple of 16 (32 for SwiGLU)", g.N);
-    SR_REQUIRE(epi < EPI_H_FIRST || (g.a_scale && g.w_scale), "gemm(fp16 planes): missing row scales");
-    SR_REQUIRE(!g.bias || epi == EPI_QKV_ROPE || epi == EPI_QKV_ROPE_F32 || epi == EPI_QKV_ROPE_F32_H,
-               "gemm: epilogue %d takes no bias (only the QKV + RoPE epilogues add one)", (int)epi);
     SR_REQUIRE(epi != EPI_SWIGLU_SPLIT || (g.out_map.n_seg >= 1 && g.out_map.n_seg <= SR_MAX_SEG), "gemm(swiglu split): bad segment map");
     switch (epi) {
         case EPI_STORE_BF16: return launch_one<EPI_STORE_BF16>(g, s);
-#ifndef SR_GEMM_VARIANT_BUILD      // tools/micro/gemm_variants.sh: k-step schedule variants of the plain-store GEMM only (seconds to build)
         case EPI_RESID_F32: return launch_one<EPI_RESID_F32>(g, s);
         case EPI_SWIGLU: return launch_one<EPI_SWIGLU>(g, s);
         case EPI_SEGMAX: return launch_one<EPI_SEGMAX>(g, s);
@@ -1312,7 +1288,6 @@ int launch_gemm_bf16(GemmEpilogue epi, const GemmArgs& g, hipStream_t s) {
         case EPI_SWIGLU_F32_H: return launch_one<EPI_SWIGLU_F32_H>(g, s);
         case EPI_SEGMAX_H: return launch_one<EPI_SEGMAX_H>(g, s);
         case EPI_SWIGLU_SPLIT_H: return launch_one<EPI_SWIGLU_SPLIT_H>(g, s);
-#endif
         default: break;
     }
     sr_set_error("gemm: unknown epilogue %d", (int)epi);

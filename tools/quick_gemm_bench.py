@@ -25,10 +25,9 @@ if __name__ == "__main__":
     shapes = [("qkv", 3072, 2048, 0), ("o", 2048, 2048, 0), ("gate_up", 16384, 2048, 2), ("down", 2048, 8192, 0)]
     for M in Ms:
         for tile in ("128", "256", "auto"):
-            for persist in ("1",):
-                os.environ["SR_GEMM_TILE"] = "" if tile == "auto" else tile; os.environ["SR_GEMM_PERSIST"] = persist
-                tot_ms, tot_fl, row = 0, 0, {}
-                for name, N, K, epi in shapes:
-                    ms, tf = run(M, N, K, epi)
-                    row[name] = round(tf, 1); tot_ms += ms; tot_fl += 2.0 * M * N * K
-                print(json.dumps({"M": M, "tile": tile, "persist": persist, "TF": row, "layer_TF": round(tot_fl / tot_ms / 1e9, 1)}), flush=True)
+            os.environ["SR_GEMM_TILE"] = "" if tile == "auto" else tile
+            tot_ms, tot_fl, row = 0, 0, {}
+            for name, N, K, epi in shapes:
+                ms, tf = run(M, N, K, epi)
+                row[name] = round(tf, 1); tot_ms += ms; tot_fl += 2.0 * M * N * K
+            print(json.dumps({"M": M, "tile": tile, "TF": row, "layer_TF": round(tot_fl / tot_ms / 1e9, 1)}), flush=True)
