@@ -47,6 +47,9 @@ def parse_args(argv=None):
                     help="real tokens per doc_encode batch (length-bucketed, multi-worker tokenisation); 0 = the reference's "
                          "loader: eval_batch_size passages padded to the longest, one worker (eval_dense.py:171-179)")
     ap.add_argument("--tokenize_workers", type=int, default=4)
+    ap.add_argument("--index_dtype", choices=["fp32", "fp16"], default="fp32",
+                    help="retrieval: how the flat index keeps its rows. fp16 rounds the (fp32) shard files once, at ingest, and "
+                         "holds half the bytes; the shard files themselves are not changed")
     args = ap.parse_args(argv)
     if args.eval_metric:
         args.eval_metric = ast.literal_eval(args.eval_metric)     # the reference uses eval() (eval_dense.py:70)
@@ -251,7 +254,7 @@ def retrieval(args):
     # (eval_dense.py:113-121); every retrieval rank takes a round-robin subset of the FILES as HBM segments.
     sizes = [int(np.load(f, mmap_mode="r").shape[0]) for f in id_files]
     offsets = np.concatenate([[0], np.cumsum(sizes)])
-    index = DenseIndexHIP(model.hidden_size, device=device)
+    index = DenseIndexHIP(model.hidden_size, device=device, row_dtype=args.index_dtype)
     if model.hidden_size % 64 == 0:
         index.set_precision("fp32_filtered")          # exact results, ~3x faster for the whole query set (csrc/dense_filter.hip)
     for fi in range(rank, len(vec_files), world):

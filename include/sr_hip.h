@@ -32,6 +32,7 @@ extern "C" {
 
 #define SR_DTYPE_F32 0
 #define SR_DTYPE_BF16 1
+#define SR_DTYPE_F16 2 /* IEEE binary16: row storage of a dense index (sr_dense_index_add_f16) */
 
 typedef void* sr_stream; /* hipStream_t; NULL = default stream */
 
@@ -57,6 +58,29 @@ int sr_dense_index_create(sr_dense_index** out, int dim);
  * indexer.py:262).  Global indices must fit in 32 bits.                      */
 int sr_dense_index_add(sr_dense_index* idx, const float* d_rows, int64_t n_rows,
                        int64_t id_base, int64_t id_stride);
+/* The same for rows stored as IEEE binary16 (half the HBM bytes of the index, half the bytes every search streams): a
+ * non-owning view of row-major binary16 [n_rows, dim] in device memory, 16-byte aligned; id rules as above.  An index holds
+ * EITHER fp32 rows OR fp16 rows - its first non-empty add decides; adding the other kind returns SR_ERR_INVALID and leaves
+ * the index unchanged.
+ * Contract: on an fp16 index every entry point below (sr_dense_search, _begin / _finish, sr_dense_score_pairs, any k,
+ * batch-invariant on or off, SR_PRECISION_FP32 and SR_PRECISION_FP32_FILTERED) returns BIT FOR BIT what the same call returns
+ * on an fp32 index whose rows are those binary16 values widened to fp32 (widening is exact; subnormals, +-0, inf and NaN
+ * included).  The kernels read the fp16 rows and widen them in registers, in the k order of the fp32 kernels; the library never
+ * keeps an fp32 copy of the rows (sr_dense_index_owned_bytes).  The only loss of information is the caller's one rounding at
+ * ingest, fp32 -> binary16 to nearest even: for |x| in the normal range of binary16 the score of a pair then differs from the
+ * score of the unrounded row by at most 2^-11 * sum_i |q_i d_i| <= 2^-11 |q| |d| (plus the fp32 chain's own rounding).
+ * SR_PRECISION_BF16X3 and SR_PRECISION_BF16X6 are not available on an fp16 index (an 11-bit significand does not fit one bf16
+ * plane): sr_dense_index_set_precision returns SR_ERR_UNSUPPORTED for them, and so does this call on an index in one of
+ * these two modes.                                                                                                             */
+int sr_dense_index_add_f16(sr_dense_index* idx, const void* d_rows_f16, int64_t n_rows,
+                           int64_t id_base, int64_t id_stride);
+/* SR_DTYPE_F32 or SR_DTYPE_F16: what the index's rows are stored as (an empty index: SR_DTYPE_F32; a null index: -1). */
+int sr_dense_index_row_dtype(const sr_dense_index* idx);
+/* *out = device bytes the LIBRARY holds per segment, summed over the segments: the bf16 planes of the split precisions and the
+ * certified filter's fp16 plane with its per-document (x, y) terms and their per-128-document maxima.  The rows themselves
+ * belong to the caller and workspaces (candidate buffers, query planes) are not counted.  0 for an index that was only ever
+ * searched in SR_PRECISION_FP32 - whatever its row type: no mode keeps a widened copy of fp16 rows.                        */
+int sr_dense_index_owned_bytes(sr_dense_index* idx, int64_t* out);
 int64_t sr_dense_index_ntotal(const sr_dense_index* idx);
 /* d_queries: fp32 [nq, dim] on device.  1 <= k <= 2^30, and a k above sr_max_topk() at most sr_max_topk() beyond the
  * index's document count (k <= ntotal + 4096: rows of at most 4096 padding entries; a larger k is SR_ERR_INVALID, as any
@@ -138,7 +162,7 @@ int sr_dense_index_destroy(sr_dense_index* idx);
 /* Measurement hook: while enabled, every launch of the score kernel is bracketed by HIP
  * events on the search stream.  _read synchronises those events and returns the number
  * of launches, their summed duration (ms) and the algorithmic work they covered
- * (2*nq*rows*dim FLOP, rows*dim*4 bytes of D), then clears the log.              */
+ * (2*nq*rows*dim FLOP, rows*dim*4 bytes of D - *2 for fp16-stored rows), then clears the log. */
 int sr_dense_index_profile(sr_dense_index* idx, int enable);
 int sr_dense_index_profile_read(sr_dense_index* idx, int64_t* n_launches, double* total_ms,
                                 double* total_flop, double* total_d_bytes);

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SR_HIP_LIB") or os.path.join(_HERE, "libsr_hip.so")     # SR_HIP_LIB: diagnostic builds (tools/micro)
 
 SR_OK, SR_ERR_INVALID, SR_ERR_HIP, SR_ERR_NOMEM, SR_ERR_UNSUPPORTED = 0, 1, 2, 3, 4
-SR_DTYPE_F32, SR_DTYPE_BF16 = 0, 1
+SR_DTYPE_F32, SR_DTYPE_BF16, SR_DTYPE_F16 = 0, 1, 2
 
 c_void_p, c_int, c_int32, c_int64, c_float, c_char_p = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
                                                          ctypes.c_int64, ctypes.c_float, ctypes.c_char_p)
@@ -37,6 +37,9 @@ SIGNATURES = {
     "sr_max_topk": (c_int, []),
     "sr_dense_index_create": (c_int, [ctypes.POINTER(c_void_p), c_int]),
     "sr_dense_index_add": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64]),
+    "sr_dense_index_add_f16": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64]),
+    "sr_dense_index_row_dtype": (c_int, [c_void_p]),
+    "sr_dense_index_owned_bytes": (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
     "sr_dense_index_ntotal": (c_int64, [c_void_p]),
     "sr_dense_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "sr_dense_index_set_workspace_limit": (c_int, [c_void_p, c_int64]),

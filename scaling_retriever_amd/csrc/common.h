@@ -79,6 +79,24 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+// ---- row storage of a dense index: fp32 (float) or IEEE binary16 (_Float16), SR_DTYPE_F32 / SR_DTYPE_F16 ----
+// Every dense kernel that reads document rows is a template on the row type and fetches them through sr_load_row4: four
+// consecutive elements as fp32.  binary16 -> fp32 is exact (v_cvt_f32_f16; subnormals are kept, the f16 denormal mode is
+// never flush), so a kernel over fp16 rows runs the arithmetic of the same kernel over those values stored as fp32.
+template <typename T> struct SrRow;                 // V: four consecutive row elements as loaded; widen: the same as fp32
+template <> struct SrRow<float> {
+    typedef f32x4 V;
+    static __device__ inline f32x4 widen(f32x4 v) { return v; }
+};
+template <> struct SrRow<_Float16> {
+    typedef f16x4 V;                                // one 8-byte load
+    static __device__ inline f32x4 widen(f16x4 h) { return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]}; }
+};
+template <typename T>
+__device__ inline f32x4 sr_load_row4(const T* p) { return SrRow<T>::widen(*reinterpret_cast<const typename SrRow<T>::V*>(p)); }
+static inline size_t sr_dtype_size(int dtype) { return dtype == SR_DTYPE_F16 ? 2 : 4; }
 
 // ---- order-preserving float <-> uint32 (larger float => larger uint) ----
 __host__ __device__ inline uint32_t sr_f2ord(float f) {

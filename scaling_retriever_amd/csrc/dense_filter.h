@@ -5,25 +5,29 @@
 #define SR_FILTER_MAX_SEGS 64
 #define SR_FILTER_MAX_SHIFT 40     // the power-of-two scales of segments and queries are 2^t with |t| <= 40
 struct FilterSegs {                 // where a global doc index lives: row = (gid - id_base) / id_stride of segment s
-    const float* rows[SR_FILTER_MAX_SEGS];
+    const void* rows[SR_FILTER_MAX_SEGS];     // rows of `dtype` (SR_DTYPE_F32 | SR_DTYPE_F16), the same for every segment
     const float* xy[SR_FILTER_MAX_SEGS];      // [n, 2] per-document error terms of the segment's fp16 plane (scaled domain)
     float isd[SR_FILTER_MAX_SEGS];            // inverse of the segment's scale
     int64_t n[SR_FILTER_MAX_SEGS];
     uint32_t id_base[SR_FILTER_MAX_SEGS], id_stride[SR_FILTER_MAX_SEGS];
     int count;
+    int dtype;
 };
 
+// Row storage: launch_filter_absmax / _plane / _rescore / _lower_bound read the documents' rows, stored as fp32 or as binary16
+// (`dtype`); the fp16 instantiations widen in registers (exact) and then run the fp32 instantiation's arithmetic, so plane, error
+// terms and re-scored bits are those of the widened rows.
 // sigma(H): the share of |q||d| the two fp32 summations (the exact fmaf chain and the MFMA's accumulation of the plane
 // product) can differ by, with slack for the epilogue's own roundings
 double sr_filter_sigma(int H);
 // *d_absmax_bits = max(*d_absmax_bits, bits of max |x| over the rows); a NaN or an infinity shows up as bits >= 0x7f800000
-int launch_filter_absmax(const float* rows, int64_t n, int H, unsigned int* d_absmax_bits, hipStream_t s);
+int launch_filter_absmax(const void* rows, int dtype, int64_t n, int H, unsigned int* d_absmax_bits, hipStream_t s);
 // the power-of-two scale that puts absmax into [2^14, 2^15) (clamped to 2^+-SR_FILTER_MAX_SHIFT); false when absmax is not
 // finite or the clamp would let a scaled value overflow fp16
 bool sr_filter_scale_of(float absmax, float* scale, float* inv_scale);
 // fp16 plane of a segment: plane[r, i] = fp16(rows[r, i] * sd), and per document, in the scaled domain,
 //   xy[r] = ((|rows_r sd - plane_r| + sigma |rows_r sd|) * 1.001, |plane_r| * 1.001);  *d_bad |= 1 on any non-finite value
-int launch_filter_plane(const float* rows, int64_t n, int H, float sd, double sigma, unsigned short* plane, float* xy, int* d_bad,
+int launch_filter_plane(const void* rows, int dtype, int64_t n, int H, float sd, double sigma, unsigned short* plane, float* xy, int* d_bad,
                         hipStream_t s);
 // gmax[g] = (max x, max y) over the documents [128 g, 128 g + 128) of xy [n, 2]: what the upper-bound pass tests a whole block of
 // accumulators against before it forms a single per-pair bound (dense_split.hip split_epilogue)

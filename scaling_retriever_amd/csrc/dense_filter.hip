@@ -36,10 +36,11 @@
 
 double sr_filter_sigma(int H) { return 1.25 * (3.0 * (double)H * ldexp(1.0, -24)) + 1.0e-5; }
 
-__global__ __launch_bounds__(256) void filter_absmax_kernel(const float* __restrict__ rows, int64_t n4, unsigned int* __restrict__ out) {
+template <typename T>
+__global__ __launch_bounds__(256) void filter_absmax_kernel(const T* __restrict__ rows, int64_t n4, unsigned int* __restrict__ out) {
     unsigned int mx = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const f32x4 v = reinterpret_cast<const f32x4*>(rows)[i];
+        const f32x4 v = sr_load_row4<T>(rows + 4 * i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const unsigned int b = __float_as_uint(v[e]) & 0x7fffffffu;     // |x| as bits: ordered like the magnitudes, NaN on top
@@ -50,12 +51,15 @@ __global__ __launch_bounds__(256) void filter_absmax_kernel(const float* __restr
     if ((threadIdx.x & 63) == 0 && mx) atomicMax(out, mx);
 }
 
-int launch_filter_absmax(const float* rows, int64_t n, int H, unsigned int* d_absmax_bits, hipStream_t s) {
+int launch_filter_absmax(const void* rows, int dtype, int64_t n, int H, unsigned int* d_absmax_bits, hipStream_t s) {
     const int64_t n4 = n * (int64_t)H / 4;
     if (n4 == 0) return SR_OK;
     int64_t blocks = ceil_div64(n4, 256 * 8);
     if (blocks > (1 << 16)) blocks = 1 << 16;
-    hipLaunchKernelGGL(filter_absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, rows, n4, d_absmax_bits);
+    if (dtype == SR_DTYPE_F16)
+        hipLaunchKernelGGL(filter_absmax_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const _Float16*>(rows), n4, d_absmax_bits);
+    else
+        hipLaunchKernelGGL(filter_absmax_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const float*>(rows), n4, d_absmax_bits);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }
@@ -75,19 +79,19 @@ bool sr_filter_scale_of(float absmax, float* scale, float* inv_scale) {
 }
 
 // one wave per row; a row of H <= 8192 floats passes through registers once
-template <bool QUERY>
-__global__ __launch_bounds__(256) void filter_plane_kernel(const float* __restrict__ rows, int64_t n, int H, float sd, float sigma,
+template <bool QUERY, typename T = float>
+__global__ __launch_bounds__(256) void filter_plane_kernel(const T* __restrict__ rows, int64_t n, int H, float sd, float sigma,
                                                            unsigned short* __restrict__ plane, float* __restrict__ out, int* __restrict__ d_bad) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {
-        const float* p = rows + r * H;
+        const T* p = rows + r * H;
         float scale = sd, inv = 1.f;
         bool ok = true;
         if (QUERY) {                          // its own power-of-two scale
             unsigned int mx = 0;
             for (int i = lane * 4; i < H; i += 256) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(p + i);
+                const f32x4 v = sr_load_row4<T>(p + i);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const unsigned int b = __float_as_uint(v[e]) & 0x7fffffffu; mx = b > mx ? b : mx; }
             }
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(256) void filter_plane_kernel(const float* __restri
         }
         float s_n = 0.f, s_0 = 0.f, s_r = 0.f;
         for (int i = lane * 4; i < H; i += 256) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(p + i);
+            const f32x4 v = sr_load_row4<T>(p + i);
             bf16x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -143,12 +147,17 @@ __global__ __launch_bounds__(256) void filter_plane_kernel(const float* __restri
     }
 }
 
-int launch_filter_plane(const float* rows, int64_t n, int H, float sd, double sigma, unsigned short* plane, float* xy, int* d_bad,
+int launch_filter_plane(const void* rows, int dtype, int64_t n, int H, float sd, double sigma, unsigned short* plane, float* xy, int* d_bad,
                         hipStream_t s) {
     if (n == 0) return SR_OK;
     int64_t blocks = ceil_div64(n, 4);
     if (blocks > (1 << 20)) blocks = 1 << 20;
-    hipLaunchKernelGGL(filter_plane_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, rows, n, H, sd, (float)sigma, plane, xy, d_bad);
+    if (dtype == SR_DTYPE_F16)
+        hipLaunchKernelGGL((filter_plane_kernel<false, _Float16>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const _Float16*>(rows), n, H,
+                           sd, (float)sigma, plane, xy, d_bad);
+    else
+        hipLaunchKernelGGL((filter_plane_kernel<false, float>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const float*>(rows), n, H, sd,
+                           (float)sigma, plane, xy, d_bad);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }
@@ -215,7 +224,7 @@ int launch_filter_tau(const float* tau, const float* tau2, const float* slack, f
 
 int launch_filter_queries(const float* Q, int64_t nq, int H, unsigned short* plane, float* qa, hipStream_t s) {
     if (nq == 0) return SR_OK;
-    hipLaunchKernelGGL(filter_plane_kernel<true>, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, s, Q, nq, H, 1.0f, 0.0f, plane, qa,
+    hipLaunchKernelGGL((filter_plane_kernel<true, float>), dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, s, Q, nq, H, 1.0f, 0.0f, plane, qa,
                        (int*)nullptr);
     SR_CHECK_LAUNCH();
     return SR_OK;
@@ -285,6 +294,7 @@ __global__ void filter_lower_exact_kernel(const unsigned int* __restrict__ xmin,
 // broadcast read, and every lane runs the fp32 fmaf chain of ITS candidate in dense_score_pipe_kernel's k order: per
 // group of 8 columns, k = 8s + j then 8s + 4 + j for j = 0..3.
 #define RS_KC 64
+template <typename T>
 __global__ __launch_bounds__(64) void filter_rescore_kernel(FilterSegs segs, const float* __restrict__ Q, const float* __restrict__ u_scores,
                                                             const int64_t* __restrict__ u_ids, const float* __restrict__ qa,
                                                             int k, int kp, int H, uint64_t* __restrict__ cand_keys,
@@ -294,7 +304,7 @@ __global__ __launch_bounds__(64) void filter_rescore_kernel(FilterSegs segs, con
 #pragma clang fp contract(off)
     __shared__ float tile[64][RS_KC + 1];
     __shared__ float qs[RS_KC];
-    __shared__ const float* rowp[64];
+    __shared__ const T* rowp[64];
     const int lane = threadIdx.x;
     const int64_t q = blockIdx.x;
     const int j0 = j_begin + blockIdx.y * 64;
@@ -314,14 +324,14 @@ __global__ __launch_bounds__(64) void filter_rescore_kernel(FilterSegs segs, con
     if (u_scores[q * kp + j0] < need) return;           // the whole wave
     int64_t gid = j < j_end ? u_ids[q * kp + j] : -1;
     if (gid >= 0 && u_scores[q * kp + j] < need) gid = -1;
-    const float* row = nullptr;
+    const T* row = nullptr;
     double e2 = 0.0;                                     // 2 e(q, j) in the true domain
     if (gid >= 0) {
         for (int sgi = 0; sgi < segs.count; ++sgi) {
             const int64_t off = gid - (int64_t)segs.id_base[sgi];
             if (off >= 0 && off % segs.id_stride[sgi] == 0 && off / segs.id_stride[sgi] < segs.n[sgi]) {
                 const int64_t r = off / segs.id_stride[sgi];
-                row = segs.rows[sgi] + r * (int64_t)H;
+                row = static_cast<const T*>(segs.rows[sgi]) + r * (int64_t)H;
                 e2 = 2.0 * ((double)qa[q * 4] * (double)segs.xy[sgi][r * 2] + (double)qa[q * 4 + 1] * (double)segs.xy[sgi][r * 2 + 1]) *
                      (double)qa[q * 4 + 3] * (double)segs.isd[sgi];
                 break;
@@ -334,14 +344,14 @@ __global__ __launch_bounds__(64) void filter_rescore_kernel(FilterSegs segs, con
     // 64 rows x 256 B per chunk: 16 lanes per row, 4 rows per instruction.  All 16 loads of a chunk are issued together
     // (interleaved with the LDS stores each one was waited for before the next went out: one memory latency per 4 rows),
     // and the loads of chunk k + 1 fly while chunk k goes through LDS and the fmaf chain.
-    const float* myp[16];
+    const T* myp[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) myp[i] = rowp[i * 4 + (lane >> 4)];
     auto fetch = [&](int k0, f32x4 (&v)[16], float& qv) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (myp[i]) v[i] = *reinterpret_cast<const f32x4*>(myp[i] + k0 + (lane & 15) * 4);
+            if (myp[i]) v[i] = sr_load_row4<T>(myp[i] + k0 + (lane & 15) * 4);
         }
         qv = Q[q * H + k0 + lane];
     };
@@ -385,6 +395,13 @@ __global__ __launch_bounds__(64) void filter_rescore_kernel(FilterSegs segs, con
     }
 }
 
+// the row type of the segments picks the instantiation
+#define SR_RESCORE_LAUNCH(GRID, ...)                                                                                   \
+    do {                                                                                                               \
+        if (segs.dtype == SR_DTYPE_F16) hipLaunchKernelGGL(filter_rescore_kernel<_Float16>, GRID, dim3(64), 0, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL(filter_rescore_kernel<float>, GRID, dim3(64), 0, s, __VA_ARGS__);                      \
+    } while (0)
+
 int launch_filter_rescore(const FilterSegs& segs, const float* Q, const float* u_scores, const int64_t* u_ids, const float* qa,
                           int64_t nq, int k, int kp, int H, uint64_t* cand_keys, int* cand_count, int64_t cand_cap, int* flags,
                           unsigned int* xmin, const float* thr, hipStream_t s) {
@@ -394,12 +411,12 @@ int launch_filter_rescore(const FilterSegs& segs, const float* Q, const float* u
     // rest, pruned against xmin.  When stage 1 saw fewer than k documents there is nothing left for stage 2.
     SR_CHECK_HIP(hipMemsetAsync(xmin, 0xff, (size_t)nq * 4, s));
     const int k1 = k < kp ? k : kp;
-    hipLaunchKernelGGL(filter_rescore_kernel, dim3((unsigned)nq, (unsigned)ceil_div64(k1, 64)), dim3(64), 0, s, segs, Q, u_scores, u_ids,
-                       qa, k, kp, H, cand_keys, cand_count, cand_cap, flags, 0, xmin, thr, 0);
+    SR_RESCORE_LAUNCH(dim3((unsigned)nq, (unsigned)ceil_div64(k1, 64)), segs, Q, u_scores, u_ids, qa, k, kp, H, cand_keys, cand_count, cand_cap,
+                      flags, 0, xmin, thr, 0);
     SR_CHECK_LAUNCH();
     if (kp > k1) {
-        hipLaunchKernelGGL(filter_rescore_kernel, dim3((unsigned)nq, (unsigned)ceil_div64(kp - k1, 64)), dim3(64), 0, s, segs, Q, u_scores,
-                           u_ids, qa, k, kp, H, cand_keys, cand_count, cand_cap, flags, k1, xmin, thr, 0);
+        SR_RESCORE_LAUNCH(dim3((unsigned)nq, (unsigned)ceil_div64(kp - k1, 64)), segs, Q, u_scores, u_ids, qa, k, kp, H, cand_keys, cand_count,
+                          cand_cap, flags, k1, xmin, thr, 0);
         SR_CHECK_LAUNCH();
     }
     return SR_OK;
@@ -410,8 +427,8 @@ int launch_filter_lower_bound(const FilterSegs& segs, const float* Q, const floa
     SR_REQUIRE(j >= 1 && j <= kp, "filter(lower bound): j = %d outside [1, %d]", j, kp);
     SR_REQUIRE(H % RS_KC == 0, "filter(lower bound): dim %d must be a multiple of %d", H, RS_KC);
     SR_CHECK_HIP(hipMemsetAsync(xmin, 0xff, (size_t)nq * 4, s));
-    hipLaunchKernelGGL(filter_rescore_kernel, dim3((unsigned)nq, (unsigned)ceil_div64(j, 64)), dim3(64), 0, s, segs, Q, u_scores, u_ids,
-                       qa, j, kp, H, (uint64_t*)nullptr, (int*)nullptr, (int64_t)0, flags, 0, xmin, (const float*)nullptr, j);
+    SR_RESCORE_LAUNCH(dim3((unsigned)nq, (unsigned)ceil_div64(j, 64)), segs, Q, u_scores, u_ids, qa, j, kp, H, (uint64_t*)nullptr, (int*)nullptr,
+                      (int64_t)0, flags, 0, xmin, (const float*)nullptr, j);
     hipLaunchKernelGGL(filter_lower_exact_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, s, xmin, u_ids, qa, flags, nq, kp, j,
                        lower);
     SR_CHECK_LAUNCH();

@@ -22,7 +22,7 @@
 #include <vector>
 
 struct DenseArgs {
-    const float* D;       // segment base
+    const void* D;        // segment base: rows of `dtype`
     const float* Q;
     int64_t row_begin;    // first doc row of this launch (within the segment)
     int64_t row_end;      // one past the last doc row of this launch
@@ -33,12 +33,16 @@ struct DenseArgs {
     int* cand_count;
     int64_t cand_cap;
     uint32_t id_base, id_stride;
+    int dtype;            // SR_DTYPE_F32 | SR_DTYPE_F16: how the rows are stored (the launch picks the instantiation)
 };
 
+// Row type T (common.h SrRow): float, or _Float16 for an index of fp16-stored rows - the doc tile is then fetched as 8-byte pieces
+// (four halves per former 16-byte chunk) and widened to the f32x4 the stage write stores: LDS layout, MFMA loop and epilogue are the
+// fp32 kernel's, and so is every result bit over the widened values.
 // Tile = (32*WM*WAVES_M docs) x (32*WN*WAVES_N queries), 4 or 8 waves, BK = 16.
 // 8 waves = 2 per SIMD: while one wave sits at the k-step barrier or waits for its LDS fragments,
 // its SIMD partner keeps the (64-cycle) fp32 MFMA pipe busy.
-template <int WAVES_M, int WAVES_N, int WM, int WN, int BK = 16, int OCC = (WAVES_M * WAVES_N) / 4>
+template <typename T, int WAVES_M, int WAVES_N, int WM, int WN, int BK = 16, int OCC = (WAVES_M * WAVES_N) / 4>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void dense_score_kernel(DenseArgs a) {
     static_assert(WAVES_M * WAVES_N == 4 || WAVES_M * WAVES_N == 8 || WAVES_M * WAVES_N == 16, "4, 8 or 16 waves per workgroup");
     constexpr int NT = 64 * WAVES_M * WAVES_N;
@@ -55,6 +59,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void dense_score_kerne
     const int q0 = blockIdx.y * TN;
     const int H = a.H;
 
+    const T* const D = static_cast<const T*>(a.D);
     f32x4 ra[A_PER_T], rb[B_PER_T];
     auto gload = [&](int k0) {
 #pragma unroll
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void dense_score_kerne
             const int r = c / KC, kc = c % KC;
             const int64_t row = row0 + r;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (c < A_CHUNKS && row < a.row_end) v = *reinterpret_cast<const f32x4*>(a.D + row * H + k0 + kc * 4);
+            if (c < A_CHUNKS && row < a.row_end) v = sr_load_row4<T>(D + row * H + k0 + kc * 4);
             ra[i] = v;
         }
 #pragma unroll
@@ -173,8 +178,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void dense_score_kerne
 // PREVIOUS barrier - under the last MFMAs of step kt.  One barrier per k-step remains, with MFMAs issued right up to
 // it and right after it.  Same k order per accumulator as dense_score_kernel: bit-identical scores.
 // WN = 32-query blocks per wave: 2 -> 256 docs x 256 queries (wave tile 128 x 64), 1 -> 256 x 128 for 65-128 queries.
-template <int WN>
+template <int WN, typename T>
 __global__ __launch_bounds__(512, 2) void dense_score_pipe_kernel(DenseArgs a) {
+    typedef typename SrRow<T>::V RowV;
     constexpr int WAVES_N = 4, WM = 4, BK = 16;
     constexpr int NT = 512, TM = 256, TN = 32 * WN * WAVES_N, LDK = BK + 4, KC = BK / 4, NSTAGE = 3;
     constexpr int PER_T = TM * KC / NT;                 // 16-B chunks per thread of the doc tile (= 2)
@@ -193,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void dense_score_pipe_kernel(DenseArgs a) {
 
     // staging: thread t moves chunks t and t + 512 of each operand tile (row = chunk / 4, k-chunk = chunk % 4);
     // rows past the end are clamped (their scores are never emitted)
-    const float* asrc[PER_T];
+    const T* asrc[PER_T];
     const float* bsrc[PER_TB];
     int soff[PER_T];
 #pragma unroll
@@ -205,7 +211,7 @@ __global__ __launch_bounds__(512, 2) void dense_score_pipe_kernel(DenseArgs a) {
         const int r = (grp >> 2) * 8 + (grp & 3) + 4 * ((c >> 2) & 1);
         int64_t row = row0 + r;
         row = row < a.row_end ? row : a.row_end - 1;
-        asrc[i] = a.D + row * H + kc * 4;
+        asrc[i] = static_cast<const T*>(a.D) + row * H + kc * 4;
         soff[i] = r * LDK + kc * 4;
         if (i < PER_TB) {
             int q = q0 + r;
@@ -213,16 +219,17 @@ __global__ __launch_bounds__(512, 2) void dense_score_pipe_kernel(DenseArgs a) {
             bsrc[i] = a.Q + (int64_t)q * H + kc * 4;
         }
     }
-    f32x4 ra[PER_T], rb[PER_TB];
+    RowV ra[PER_T];
+    f32x4 rb[PER_TB];
     auto gload = [&](int k0) {
 #pragma unroll
-        for (int i = 0; i < PER_T; ++i) ra[i] = *reinterpret_cast<const f32x4*>(asrc[i] + k0);
+        for (int i = 0; i < PER_T; ++i) ra[i] = *reinterpret_cast<const RowV*>(asrc[i] + k0);
 #pragma unroll
         for (int i = 0; i < PER_TB; ++i) rb[i] = *reinterpret_cast<const f32x4*>(bsrc[i] + k0);
     };
     auto sstore = [&](int st) {
 #pragma unroll
-        for (int i = 0; i < PER_T; ++i) *reinterpret_cast<f32x4*>(&As[st * TM * LDK + soff[i]]) = ra[i];
+        for (int i = 0; i < PER_T; ++i) *reinterpret_cast<f32x4*>(&As[st * TM * LDK + soff[i]]) = SrRow<T>::widen(ra[i]);
 #pragma unroll
         for (int i = 0; i < PER_TB; ++i) *reinterpret_cast<f32x4*>(&Bs[st * TN * LDK + soff[i]]) = rb[i];
     };
@@ -252,12 +259,13 @@ __global__ __launch_bounds__(512, 2) void dense_score_pipe_kernel(DenseArgs a) {
     const int nk = H / BK;
     {   // prologue: the first three k-steps' loads are all in flight before the first stage is written (one memory
         // latency instead of three)
-        f32x4 pa[2][PER_T], pb[2][PER_TB];
+        RowV pa[2][PER_T];
+        f32x4 pb[2][PER_TB];
 #pragma unroll
         for (int st0 = 0; st0 < 2; ++st0) {
             const int k0 = (st0 < nk ? st0 : 0) * BK;
 #pragma unroll
-            for (int i = 0; i < PER_T; ++i) pa[st0][i] = *reinterpret_cast<const f32x4*>(asrc[i] + k0);
+            for (int i = 0; i < PER_T; ++i) pa[st0][i] = *reinterpret_cast<const RowV*>(asrc[i] + k0);
 #pragma unroll
             for (int i = 0; i < PER_TB; ++i) pb[st0][i] = *reinterpret_cast<const f32x4*>(bsrc[i] + k0);
         }
@@ -265,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void dense_score_pipe_kernel(DenseArgs a) {
 #pragma unroll
         for (int st0 = 0; st0 < 2; ++st0) {
 #pragma unroll
-            for (int i = 0; i < PER_T; ++i) *reinterpret_cast<f32x4*>(&As[st0 * TM * LDK + soff[i]]) = pa[st0][i];
+            for (int i = 0; i < PER_T; ++i) *reinterpret_cast<f32x4*>(&As[st0 * TM * LDK + soff[i]]) = SrRow<T>::widen(pa[st0][i]);
 #pragma unroll
             for (int i = 0; i < PER_TB; ++i) *reinterpret_cast<f32x4*>(&Bs[st0 * TN * LDK + soff[i]]) = pb[st0][i];
         }
@@ -354,26 +362,31 @@ __global__ __launch_bounds__(512, 2) void dense_score_pipe_kernel(DenseArgs a) {
     }
 }
 
-template <int WN>
-static int launch_dense_pipe(const DenseArgs& a, int64_t rows, hipStream_t s) {
+template <int WN, typename T>
+static int launch_dense_pipe_t(const DenseArgs& a, int64_t rows, hipStream_t s) {
     constexpr int TN = 128 * WN;
     constexpr size_t lds = sizeof(float) * 3 * (256 + TN) * (16 + 4);
     static DeviceOnce attr_once;
     bool* attr_slot = attr_once.pending();
     if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_score_pipe_kernel<WN>),
+        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_score_pipe_kernel<WN, T>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         *attr_slot = true;
     }
     dim3 grid((unsigned)ceil_div64(rows, 256), (unsigned)ceil_div64(a.nq, TN));
-    hipLaunchKernelGGL(dense_score_pipe_kernel<WN>, grid, dim3(512), lds, s, a);
+    hipLaunchKernelGGL((dense_score_pipe_kernel<WN, T>), grid, dim3(512), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;
+}
+template <int WN>
+static int launch_dense_pipe(const DenseArgs& a, int64_t rows, hipStream_t s) {
+    return a.dtype == SR_DTYPE_F16 ? launch_dense_pipe_t<WN, _Float16>(a, rows, s) : launch_dense_pipe_t<WN, float>(a, rows, s);
 }
 
 // --------------------------------------------------------------------- host ---
 struct DenseSegment {
-    const float* rows;
+    const void* rows;                   // caller's rows, fp32 or binary16 (sr_dense_index::row_dtype): never copied, never widened
+
     int64_t n;
     int64_t id_base, id_stride;
     unsigned short* pl[3] = {nullptr, nullptr, nullptr};   // library-owned bf16 planes (bf16x3 / bf16x6 score modes only)
@@ -394,6 +407,7 @@ struct sr_dense_index {
     int64_t ntotal = 0;
     int64_t ws_limit = 4ll << 30;
     int precision = SR_PRECISION_FP32;
+    int row_dtype = SR_DTYPE_F32;          // SR_DTYPE_F32 | SR_DTYPE_F16: decided by the first non-empty add, then fixed
     bool batch_invariant = false;          // sr_dense_index_set_batch_invariant: batches <= 64 run the tiled kernels (one k order)
     unsigned short* qpl[3] = {nullptr, nullptr, nullptr};   // query planes for the split precisions
     int64_t q_cap = 0;
@@ -440,7 +454,7 @@ static int filter_prepare_segment(sr_dense_index* idx, DenseSegment& seg) {
     if (!idx->f_scratch && hipMalloc((void**)&idx->f_scratch, 8) != hipSuccess) { (void)hipGetLastError(); idx->f_scratch = nullptr; return SR_OK; }
     unsigned int h[2] = {0, 0};
     SR_CHECK_HIP(hipMemsetAsync(idx->f_scratch, 0, 8, nullptr));
-    SR_TRY(launch_filter_absmax(seg.rows, seg.n, idx->dim, idx->f_scratch, nullptr));
+    SR_TRY(launch_filter_absmax(seg.rows, idx->row_dtype, seg.n, idx->dim, idx->f_scratch, nullptr));
     SR_CHECK_HIP(hipMemcpy(h, idx->f_scratch, 8, hipMemcpyDeviceToHost));
     float absmax;
     memcpy(&absmax, &h[0], 4);
@@ -452,7 +466,7 @@ static int filter_prepare_segment(sr_dense_index* idx, DenseSegment& seg) {
         seg.fpl = nullptr; seg.fxy = nullptr;
         return SR_OK;
     }
-    SR_TRY(launch_filter_plane(seg.rows, seg.n, idx->dim, seg.fsd, sr_filter_sigma(idx->dim), seg.fpl, seg.fxy,
+    SR_TRY(launch_filter_plane(seg.rows, idx->row_dtype, seg.n, idx->dim, seg.fsd, sr_filter_sigma(idx->dim), seg.fpl, seg.fxy,
                                reinterpret_cast<int*>(idx->f_scratch) + 1, nullptr));
     SR_TRY(launch_filter_group_max(seg.fxy, seg.n, seg.fxy + 2 * seg.n, nullptr));
     SR_CHECK_HIP(hipMemcpy(h, idx->f_scratch, 8, hipMemcpyDeviceToHost));
@@ -487,27 +501,32 @@ static int split_segment(sr_dense_index* idx, DenseSegment& seg, int want) {
         }
     }
     // (re)compute all planes: cheap next to one search, and keeps the planes consistent
-    SR_TRY(launch_split_bf16(seg.rows, seg.pl[0], want >= 2 ? seg.pl[1] : nullptr, want == 3 ? seg.pl[2] : nullptr, seg.n * (int64_t)idx->dim, nullptr));
+    SR_TRY(launch_split_bf16(static_cast<const float*>(seg.rows), seg.pl[0], want >= 2 ? seg.pl[1] : nullptr, want == 3 ? seg.pl[2] : nullptr, seg.n * (int64_t)idx->dim, nullptr));
     SR_CHECK_HIP(hipStreamSynchronize(nullptr));
     seg.n_planes = want;
     return SR_OK;
 }
 
-template <int WAVES_M, int WAVES_N, int WM, int WN, int BK = 16, int OCC = (WAVES_M * WAVES_N) / 4>
-static int launch_dense(const DenseArgs& a, int64_t rows, hipStream_t s) {
+template <typename T, int WAVES_M, int WAVES_N, int WM, int WN, int BK, int OCC>
+static int launch_dense_t(const DenseArgs& a, int64_t rows, hipStream_t s) {
     constexpr int TM = 32 * WM * WAVES_M, TN = 32 * WN * WAVES_N;
     constexpr size_t lds = sizeof(float) * 2 * (TM + TN) * (BK + 4);
     static DeviceOnce attr_once;
     bool* attr_slot = attr_once.pending();
     if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_score_kernel<WAVES_M, WAVES_N, WM, WN, BK, OCC>),
+        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_score_kernel<T, WAVES_M, WAVES_N, WM, WN, BK, OCC>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         *attr_slot = true;
     }
     dim3 grid((unsigned)ceil_div64(rows, TM), (unsigned)ceil_div64(a.nq, TN));
-    hipLaunchKernelGGL((dense_score_kernel<WAVES_M, WAVES_N, WM, WN, BK, OCC>), grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a);
+    hipLaunchKernelGGL((dense_score_kernel<T, WAVES_M, WAVES_N, WM, WN, BK, OCC>), grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;
+}
+template <int WAVES_M, int WAVES_N, int WM, int WN, int BK = 16, int OCC = (WAVES_M * WAVES_N) / 4>
+static int launch_dense(const DenseArgs& a, int64_t rows, hipStream_t s) {
+    return a.dtype == SR_DTYPE_F16 ? launch_dense_t<_Float16, WAVES_M, WAVES_N, WM, WN, BK, OCC>(a, rows, s)
+                                   : launch_dense_t<float, WAVES_M, WAVES_N, WM, WN, BK, OCC>(a, rows, s);
 }
 
 extern "C" int sr_dense_index_create(sr_dense_index** out, int dim) {
@@ -518,21 +537,58 @@ extern "C" int sr_dense_index_create(sr_dense_index** out, int dim) {
     return SR_OK;
 }
 
-extern "C" int sr_dense_index_add(sr_dense_index* idx, const float* d_rows, int64_t n_rows, int64_t id_base,
-                                  int64_t id_stride) {
-    SR_REQUIRE(idx, "sr_dense_index_add: null index");
-    SR_REQUIRE(n_rows >= 0 && id_stride >= 1 && id_base >= 0, "sr_dense_index_add: bad sizes");
+// one segment of rows stored as `dtype`; every check comes before the index is touched
+static int dense_index_add_rows(sr_dense_index* idx, const void* d_rows, int dtype, int64_t n_rows, int64_t id_base, int64_t id_stride,
+                                const char* who) {
+    SR_REQUIRE(idx, "%s: null index", who);
+    SR_REQUIRE(n_rows >= 0 && id_stride >= 1 && id_base >= 0, "%s: bad sizes", who);
     if (n_rows == 0) return SR_OK;
-    SR_REQUIRE(d_rows, "sr_dense_index_add: null rows");
-    SR_REQUIRE(((uintptr_t)d_rows & 15) == 0, "sr_dense_index_add: rows must be 16-byte aligned");
-    SR_REQUIRE(id_base + (n_rows - 1) * id_stride < 0xffffffffll, "sr_dense_index_add: global doc index exceeds 32 bits");
+    SR_REQUIRE(d_rows, "%s: null rows", who);
+    SR_REQUIRE(((uintptr_t)d_rows & 15) == 0, "%s: rows must be 16-byte aligned", who);
+    SR_REQUIRE(id_base + (n_rows - 1) * id_stride < 0xffffffffll, "%s: global doc index exceeds 32 bits", who);
     std::lock_guard<std::mutex> lock(idx->mu);
+    SR_REQUIRE(idx->segs.empty() || idx->row_dtype == dtype, "%s: the index holds %s rows; an index holds fp32 rows or fp16 rows, not both", who,
+               idx->row_dtype == SR_DTYPE_F16 ? "fp16" : "fp32");
+    if (dtype == SR_DTYPE_F16 && planes_of(idx->precision)) {
+        sr_set_error("%s: the split-bf16 precisions are not available for fp16-stored rows", who);
+        return SR_ERR_UNSUPPORTED;
+    }
     DenseSegment seg;
     seg.rows = d_rows; seg.n = n_rows; seg.id_base = id_base; seg.id_stride = id_stride;
-    if (planes_of(idx->precision)) SR_TRY(split_segment(idx, seg, planes_of(idx->precision)));
-    if (idx->precision == SR_PRECISION_FP32_FILTERED) SR_TRY(filter_prepare_segment(idx, seg));
+    const int dtype_before = idx->row_dtype;
+    idx->row_dtype = dtype;                  // the segment's preparation reads it
+    int rc = SR_OK;
+    if (planes_of(idx->precision)) rc = split_segment(idx, seg, planes_of(idx->precision));
+    if (rc == SR_OK && idx->precision == SR_PRECISION_FP32_FILTERED) rc = filter_prepare_segment(idx, seg);
+    if (rc != SR_OK) { idx->row_dtype = dtype_before; return rc; }
     idx->segs.push_back(seg);
     idx->ntotal += n_rows;
+    return SR_OK;
+}
+
+extern "C" int sr_dense_index_add(sr_dense_index* idx, const float* d_rows, int64_t n_rows, int64_t id_base,
+                                  int64_t id_stride) {
+    return dense_index_add_rows(idx, d_rows, SR_DTYPE_F32, n_rows, id_base, id_stride, "sr_dense_index_add");
+}
+
+extern "C" int sr_dense_index_add_f16(sr_dense_index* idx, const void* d_rows_f16, int64_t n_rows, int64_t id_base,
+                                      int64_t id_stride) {
+    return dense_index_add_rows(idx, d_rows_f16, SR_DTYPE_F16, n_rows, id_base, id_stride, "sr_dense_index_add_f16");
+}
+
+extern "C" int sr_dense_index_row_dtype(const sr_dense_index* idx) { return idx ? idx->row_dtype : -1; }
+
+extern "C" int sr_dense_index_owned_bytes(sr_dense_index* idx, int64_t* out) {
+    SR_REQUIRE(idx && out, "sr_dense_index_owned_bytes: null argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    int64_t bytes = 0;
+    for (const DenseSegment& seg : idx->segs) {
+        const int64_t plane = seg.n * (int64_t)idx->dim * 2;
+        bytes += plane * seg.n_planes;                                                   // split_segment
+        if (seg.fpl) bytes += plane;                                                     // filter_prepare_segment
+        if (seg.fxy) bytes += (seg.n + ceil_div64(seg.n, 128)) * 8;
+    }
+    *out = bytes;
     return SR_OK;
 }
 
@@ -587,6 +643,10 @@ extern "C" int sr_dense_index_set_precision(sr_dense_index* idx, int mode) {
                    mode == SR_PRECISION_FP32_FILTERED,
                "sr_dense_index_set_precision: unknown mode %d", mode);
     std::lock_guard<std::mutex> lock(idx->mu);
+    if (planes_of(mode) && idx->row_dtype == SR_DTYPE_F16) {
+        sr_set_error("sr_dense_index_set_precision: the split-bf16 precisions are not available for fp16-stored rows");
+        return SR_ERR_UNSUPPORTED;
+    }
     if (planes_of(mode)) {
         SR_REQUIRE(idx->dim % 64 == 0, "split precisions need dim %% 64 == 0 (dim = %d)", idx->dim);
         for (DenseSegment& seg : idx->segs) SR_TRY(split_segment(idx, seg, planes_of(mode)));
@@ -754,9 +814,10 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
                 a.D = seg.rows; a.Q = d_queries; a.row_begin = r0; a.row_end = r1; a.H = idx->dim; a.nq = (int)nq;
                 a.tau = ws.tau; a.cand_keys = ws.cand_keys; a.cand_count = ws.cand_count;
                 a.cand_cap = ws.cand_cap; a.id_base = (uint32_t)seg.id_base; a.id_stride = (uint32_t)seg.id_stride;
+                a.dtype = idx->row_dtype;
                 idx->prof.begin(s);
                 SR_TRY(launch_dense_stream(a, s));
-                idx->prof.end(s, 2.0 * (double)nq * (double)(r1 - r0) * idx->dim, (double)(r1 - r0) * idx->dim * 4.0);
+                idx->prof.end(s, 2.0 * (double)nq * (double)(r1 - r0) * idx->dim, (double)(r1 - r0) * idx->dim * (double)sr_dtype_size(idx->row_dtype));
                 SR_TRY(topk_compact(ws, nq, k, s));
                 r0 = r1;
                 step = step * 2 < cap ? step * 2 : cap;
@@ -793,6 +854,7 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
             a.cand_cap = ws.cand_cap;
             a.id_base = (uint32_t)seg.id_base;
             a.id_stride = (uint32_t)seg.id_stride;
+            a.dtype = idx->row_dtype;
             idx->prof.begin(s);
             switch (cfg) {
                 case 0:
@@ -810,7 +872,7 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
                 case 2: SR_TRY((launch_dense<4, 1, 2, 2>(a, r1 - r0, s))); break;
                 default: SR_TRY((launch_dense<4, 1, 2, 1>(a, r1 - r0, s))); break;
             }
-            idx->prof.end(s, 2.0 * (double)nq * (double)(r1 - r0) * idx->dim, (double)(r1 - r0) * idx->dim * 4.0);
+            idx->prof.end(s, 2.0 * (double)nq * (double)(r1 - r0) * idx->dim, (double)(r1 - r0) * idx->dim * (double)sr_dtype_size(idx->row_dtype));
             SR_TRY(topk_compact(ws, nq, k, s));
             r0 = r0_next;
         }
@@ -823,6 +885,7 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
 // the batch has to go through the exact kernel as a whole (filter not applicable to this index / batch).
 static int filter_segs_of(sr_dense_index* idx, FilterSegs& fs) {
     fs.count = (int)idx->segs.size();
+    fs.dtype = idx->row_dtype;
     for (int i = 0; i < fs.count; ++i) {
         fs.rows[i] = idx->segs[i].rows; fs.n[i] = idx->segs[i].n;
         fs.xy[i] = idx->segs[i].fxy; fs.isd[i] = idx->segs[i].fisd;
@@ -1017,7 +1080,7 @@ extern "C" int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries,
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
-    if (idx->pair_segs_n != idx->segs.size()) {           // segments are only ever added
+    if (idx->pair_segs_n != idx->segs.size()) {           // segments are only ever added, all of one row type
         std::vector<PairSeg> h;
         for (const DenseSegment& seg : idx->segs) h.push_back(PairSeg{seg.rows, seg.n, seg.id_base, seg.id_stride});
         if (idx->pair_segs) (void)hipFree(idx->pair_segs);    // waits for the calls that read it
@@ -1032,7 +1095,7 @@ extern "C" int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries,
         idx->pair_segs_n = h.size();
     }
     SR_TRY(pair_status_begin(&idx->pair_status, d_cand_indptr, nq, s));
-    SR_TRY(launch_dense_pairs(idx->pair_segs, (int)idx->pair_segs_n, d_queries, nq, idx->dim, d_cand_indptr, d_cand_ids, d_out_scores,
+    SR_TRY(launch_dense_pairs(idx->pair_segs, (int)idx->pair_segs_n, idx->row_dtype, d_queries, nq, idx->dim, d_cand_indptr, d_cand_ids, d_out_scores,
                               idx->pair_status, s));
     return pair_status_end(idx->pair_status, d_cand_ids, "sr_dense_score_pairs", s);
 }

@@ -16,20 +16,29 @@
 #define DS_TM (4 * DS_R * 16)     // docs per workgroup = 128
 #define DS_PF 8                   // 16-k groups per prefetch step (8 x float4 per lane per doc block)
 
-template <int NQB>  // number of 16-query blocks (1 or 2)
+// Row type T (common.h sr_load_row4): float, or _Float16 for an index of fp16-stored rows.  The fp16 instantiation keeps the lane
+// -> k map of the fp32 one (lane group g holds k = 16s + 4g + jj of 16-k group s), so a lane's piece of a row is 4 halves = ONE
+// 8-byte load, widened in registers right in front of the MFMA that consumes it: the chain per accumulator - and with it every
+// result bit - is that of the fp32 kernel over the widened values.  It prefetches twice the k per step (PF = 16 groups = one
+// whole query slab), so that a lane has the same 256 bytes per doc block in flight as the fp32 kernel and the same 64 registers
+// hold nxt / cur.
+
+template <int NQB, typename T = float>  // NQB: number of 16-query blocks (1 to 4)
 __global__ __launch_bounds__(256) void dense_stream_kernel(DenseStreamArgs a) {
+    typedef typename SrRow<T>::V RowV;
+    constexpr int PF = DS_PF * (4 / (int)sizeof(T));   // 16-k groups per prefetch step: 256 bytes per lane and doc block
     extern __shared__ __attribute__((aligned(16))) float Qs[];   // [NQB * 16][DS_LDQ]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int H = a.H;
     const int64_t row0 = a.row_begin + (int64_t)blockIdx.x * DS_TM + wave * (DS_R * 16);
 
-    const float* drow[DS_R];
+    const T* drow[DS_R];
 #pragma unroll
     for (int r = 0; r < DS_R; ++r) {
         int64_t row = row0 + r * 16 + li;
         row = row < a.row_end ? row : a.row_end - 1;   // clamp: results of padded rows are never emitted
-        drow[r] = a.D + row * H + 4 * g;
+        drow[r] = static_cast<const T*>(a.D) + row * H + 4 * g;
     }
     f32x4 acc[DS_R][NQB];
 #pragma unroll
@@ -37,21 +46,21 @@ __global__ __launch_bounds__(256) void dense_stream_kernel(DenseStreamArgs a) {
 #pragma unroll
         for (int b = 0; b < NQB; ++b) acc[r][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    f32x4 nxt[DS_R][DS_PF], cur[DS_R][DS_PF];
+    RowV nxt[DS_R][PF], cur[DS_R][PF];
     auto gload = [&](int k0) {
 #pragma unroll
         for (int r = 0; r < DS_R; ++r)
 #pragma unroll
-            for (int s = 0; s < DS_PF; ++s) nxt[r][s] = *reinterpret_cast<const f32x4*>(drow[r] + k0 + 16 * s);
+            for (int s = 0; s < PF; ++s) nxt[r][s] = *reinterpret_cast<const RowV*>(drow[r] + k0 + 16 * s);
     };
-    const int nsteps = H / (16 * DS_PF);          // prefetch steps of 128 k
-    constexpr int STEPS_PER_SLAB = DS_KS / (16 * DS_PF);
+    const int nsteps = H / (16 * PF);          // prefetch steps of 16 PF k (128; fp16 rows: 256)
+    constexpr int STEPS_PER_SLAB = DS_KS / (16 * PF);
     gload(0);
     for (int step = 0; step < nsteps; ++step) {
         if (step % STEPS_PER_SLAB == 0) {
             // stage the next query slab: Q[q][slab*KS .. +KS) -> Qs[q][0..KS)
             __syncthreads();
-            const int k0 = step * 16 * DS_PF;
+            const int k0 = step * 16 * PF;
             for (int c = tid; c < NQB * 16 * (DS_KS / 4); c += 256) {
                 const int q = c / (DS_KS / 4), kc = c % (DS_KS / 4);
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -63,11 +72,11 @@ __global__ __launch_bounds__(256) void dense_stream_kernel(DenseStreamArgs a) {
 #pragma unroll
         for (int r = 0; r < DS_R; ++r)
 #pragma unroll
-            for (int s = 0; s < DS_PF; ++s) cur[r][s] = nxt[r][s];
-        if (step + 1 < nsteps) gload((step + 1) * 16 * DS_PF);
-        const int kslab = (step % STEPS_PER_SLAB) * 16 * DS_PF;
+            for (int s = 0; s < PF; ++s) cur[r][s] = nxt[r][s];
+        if (step + 1 < nsteps) gload((step + 1) * 16 * PF);
+        const int kslab = (step % STEPS_PER_SLAB) * 16 * PF;
 #pragma unroll
-        for (int s = 0; s < DS_PF; ++s) {
+        for (int s = 0; s < PF; ++s) {
             f32x4 qf[NQB];
 #pragma unroll
             for (int b = 0; b < NQB; ++b)
@@ -78,7 +87,7 @@ __global__ __launch_bounds__(256) void dense_stream_kernel(DenseStreamArgs a) {
                 for (int r = 0; r < DS_R; ++r)
 #pragma unroll
                     for (int b = 0; b < NQB; ++b)
-                        acc[r][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur[r][s][jj], qf[b][jj], acc[r][b], 0, 0, 0);
+                        acc[r][b] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)cur[r][s][jj], qf[b][jj], acc[r][b], 0, 0, 0);
         }
     }
 
@@ -111,7 +120,15 @@ __global__ __launch_bounds__(256) void dense_stream_kernel(DenseStreamArgs a) {
     }
 }
 
+template <typename T>
+static int launch_dense_stream_t(const DenseStreamArgs& a, hipStream_t s);
+
 int launch_dense_stream(const DenseStreamArgs& a, hipStream_t s) {
+    return a.dtype == SR_DTYPE_F16 ? launch_dense_stream_t<_Float16>(a, s) : launch_dense_stream_t<float>(a, s);
+}
+
+template <typename T>
+static int launch_dense_stream_t(const DenseStreamArgs& a, hipStream_t s) {
     const int64_t rows = a.row_end - a.row_begin;
     if (rows <= 0) return SR_OK;
     SR_REQUIRE(a.nq >= 1 && a.nq <= 64, "dense_stream: nq=%d outside [1, 64]", a.nq);
@@ -122,17 +139,17 @@ int launch_dense_stream(const DenseStreamArgs& a, hipStream_t s) {
     static DeviceOnce attr_once;
     bool* attr_slot = attr_once.pending();
     if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stream_kernel<3>),
+        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stream_kernel<3, T>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 16 * DS_LDQ * 4));
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stream_kernel<4>),
+        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stream_kernel<4, T>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 16 * DS_LDQ * 4));
         *attr_slot = true;
     }
     switch (nqb) {
-        case 1: hipLaunchKernelGGL(dense_stream_kernel<1>, grid, dim3(256), lds, s, a); break;
-        case 2: hipLaunchKernelGGL(dense_stream_kernel<2>, grid, dim3(256), lds, s, a); break;
-        case 3: hipLaunchKernelGGL(dense_stream_kernel<3>, grid, dim3(256), lds, s, a); break;
-        default: hipLaunchKernelGGL(dense_stream_kernel<4>, grid, dim3(256), lds, s, a); break;
+        case 1: hipLaunchKernelGGL((dense_stream_kernel<1, T>), grid, dim3(256), lds, s, a); break;
+        case 2: hipLaunchKernelGGL((dense_stream_kernel<2, T>), grid, dim3(256), lds, s, a); break;
+        case 3: hipLaunchKernelGGL((dense_stream_kernel<3, T>), grid, dim3(256), lds, s, a); break;
+        default: hipLaunchKernelGGL((dense_stream_kernel<4, T>), grid, dim3(256), lds, s, a); break;
     }
     SR_CHECK_LAUNCH();
     return SR_OK;

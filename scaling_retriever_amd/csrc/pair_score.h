@@ -3,7 +3,7 @@
 #include "common.h"
 
 struct PairSeg {                    // one dense segment: global doc index = id_base + row * id_stride
-    const float* rows;
+    const void* rows;               // fp32 or binary16 rows: the index's row type, passed to launch_dense_pairs
     int64_t n;
     int64_t id_base, id_stride;
 };
@@ -19,5 +19,6 @@ int pair_status_begin(PairStatus** d_status, const int64_t* d_cand_indptr, int64
 int pair_status_end(PairStatus* d_status, const int64_t* d_cand_ids, const char* who, hipStream_t s);
 
 // out[p] = fp32 fmaf chain of Q[q] . row(cand_ids[p]) in dense_score.hip's k order, for cand_indptr[q] <= p < cand_indptr[q + 1]
-int launch_dense_pairs(const PairSeg* d_segs, int n_segs, const float* Q, int64_t nq, int H, const int64_t* d_cand_indptr,
+// dtype = SR_DTYPE_F32 | SR_DTYPE_F16: how the segments' rows are stored (fp16 rows are widened in registers: the same chain)
+int launch_dense_pairs(const PairSeg* d_segs, int n_segs, int dtype, const float* Q, int64_t nq, int H, const int64_t* d_cand_indptr,
                        const int64_t* d_cand_ids, float* d_out, PairStatus* d_status, hipStream_t s);

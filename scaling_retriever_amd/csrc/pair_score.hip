@@ -63,20 +63,21 @@ __device__ inline int64_t pair_query_of(const int64_t* __restrict__ indptr, int6
 // consecutive tiles, each reading its query chunk once (a broadcast LDS read in the chain); a tile that straddles lists runs one
 // pass per list with the other lists' lanes idle (their rows are not fetched).  The workgroups stride over the tiles.
 #define PS_KC 64
+template <typename T>
 __global__ __launch_bounds__(64) void dense_pairs_kernel(const PairSeg* __restrict__ segs, int n_segs, const float* __restrict__ Q,
                                                          int64_t nq, int H, const int64_t* __restrict__ cand_indptr,
                                                          const int64_t* __restrict__ cand_ids, float* __restrict__ out,
                                                          PairStatus* __restrict__ st) {
     __shared__ float tile[64][PS_KC + 1];
     __shared__ float qs[PS_KC];
-    __shared__ const float* rowp[64];
+    __shared__ const T* rowp[64];
     if (st->indptr_bad) return;
     const int lane = threadIdx.x;
     const int64_t total = cand_indptr[nq];
     const int nch = (H + PS_KC - 1) / PS_KC;
     for (int64_t t0 = (int64_t)blockIdx.x * 64; t0 < total; t0 += (int64_t)gridDim.x * 64) {
         const int64_t p = t0 + lane;
-        const float* row = nullptr;
+        const T* row = nullptr;
         if (p < total) {
             const int64_t gid = cand_ids[p];
             for (int sgi = 0; sgi < n_segs; ++sgi) {
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(64) void dense_pairs_kernel(const PairSeg* __restri
                     in_seg = in_seg && r * stride == off;
                 }
                 if (in_seg && r < segs[sgi].n) {
-                    row = segs[sgi].rows + r * (int64_t)H;
+                    row = static_cast<const T*>(segs[sgi].rows) + r * (int64_t)H;
                     break;
                 }
             }
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(64) void dense_pairs_kernel(const PairSeg* __restri
             __syncthreads();                                  // the previous pass has read rowp
             rowp[lane] = mine ? row : nullptr;
             __syncthreads();
-            const float* myp[16];
+            const T* myp[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) myp[i] = rowp[i * 4 + (lane >> 4)];
             const float* qrow = Q + q * (int64_t)H;
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(64) void dense_pairs_kernel(const PairSeg* __restri
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (myp[i] && col < H) v[i] = *reinterpret_cast<const f32x4*>(myp[i] + col);
+                    if (myp[i] && col < H) v[i] = sr_load_row4<T>(myp[i] + col);
                 }
                 qv = k0 + lane < H ? qrow[k0 + lane] : 0.f;
             };
@@ -163,11 +164,15 @@ __global__ __launch_bounds__(64) void dense_pairs_kernel(const PairSeg* __restri
     }
 }
 
-int launch_dense_pairs(const PairSeg* d_segs, int n_segs, const float* Q, int64_t nq, int H, const int64_t* d_cand_indptr,
+int launch_dense_pairs(const PairSeg* d_segs, int n_segs, int dtype, const float* Q, int64_t nq, int H, const int64_t* d_cand_indptr,
                        const int64_t* d_cand_ids, float* d_out, PairStatus* d_status, hipStream_t s) {
     // 8 one-wave workgroups per compute unit: 8 x 16 KB of rows in flight per unit, LDS 17 KB each
-    hipLaunchKernelGGL(dense_pairs_kernel, dim3((unsigned)(sr_cu_count() * 8)), dim3(64), 0, s, d_segs, n_segs, Q, nq, H, d_cand_indptr,
-                       d_cand_ids, d_out, d_status);
+    if (dtype == SR_DTYPE_F16)
+        hipLaunchKernelGGL(dense_pairs_kernel<_Float16>, dim3((unsigned)(sr_cu_count() * 8)), dim3(64), 0, s, d_segs, n_segs, Q, nq, H,
+                           d_cand_indptr, d_cand_ids, d_out, d_status);
+    else
+        hipLaunchKernelGGL(dense_pairs_kernel<float>, dim3((unsigned)(sr_cu_count() * 8)), dim3(64), 0, s, d_segs, n_segs, Q, nq, H,
+                           d_cand_indptr, d_cand_ids, d_out, d_status);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }

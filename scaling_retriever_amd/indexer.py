@@ -237,9 +237,12 @@ class DenseFlatIndexer(DenseIndexer):
         super().__init__(buffer_size)
         self.hidden_dim = None
 
-    def init_index(self, hidden_dim):
+    def init_index(self, hidden_dim, storage="fp32"):
+        """storage="fp16": the rows are kept as float16 (fp32 input is rounded once, at ingest; half the HBM, and every result is bit
+        for bit that of an fp32 index over the rounded rows: DenseIndexHIP).  float16 input is stored as it is under either setting."""
         self.hidden_dim = int(hidden_dim)
-        self.index = DenseIndexHIP(self.hidden_dim)
+        self.storage = storage
+        self.index = DenseIndexHIP(self.hidden_dim, row_dtype=storage)
         # IndexFlatIP's exact results (bit-identical to the exact fp32 kernel) through the certified bf16 filter + exact
         # re-score; the library uses the exact kernel by itself when HBM has no room for the filter's bf16 planes
         if self.hidden_dim % 64 == 0:
@@ -249,7 +252,7 @@ class DenseFlatIndexer(DenseIndexer):
         assert len(doc_reps) == len(doc_ids)
         n = len(doc_reps)
         if isinstance(doc_reps, torch.Tensor) and doc_reps.is_cuda:
-            self.index.add_device_rows(doc_reps.float())
+            self.index.add_device_rows(doc_reps if doc_reps.dtype == torch.float16 else doc_reps.float())
         else:
             self.index.add_host_rows(doc_reps if isinstance(doc_reps, np.ndarray) else np.asarray(doc_reps), buffer_size=self.buffer_size)
         n_total = self._update_id_mapping(list(doc_ids))
@@ -344,8 +347,8 @@ class DenseFlatIndexer(DenseIndexer):
         return "flat_index"
 
     def serialize(self, file: str):
-        """indexer.py:145-159 writes a faiss file; here the same two files hold the raw fp32 rows (npy) +
-        the pickled id map (faiss' binary format is not reproduced)."""
+        """indexer.py:145-159 writes a faiss file; here the same two files hold the raw rows as they are stored (an fp32 or a
+        float16 npy) + the pickled id map (faiss' binary format is not reproduced)."""
         if os.path.isdir(file):
             index_file, meta_file = os.path.join(file, "index.dpr"), os.path.join(file, "index_meta.dpr")
         else:
@@ -362,7 +365,7 @@ class DenseFlatIndexer(DenseIndexer):
             index_file, meta_file = path + ".index.dpr", path + ".index_meta.dpr"
         with open(index_file, "rb") as f:
             rows = np.load(f)
-        self.init_index(rows.shape[1])
+        self.init_index(rows.shape[1], storage="fp16" if rows.dtype == np.float16 else "fp32")
         self.index.add_host_rows(rows, buffer_size=self.buffer_size)
         with open(meta_file, "rb") as reader:
             self.index_id_to_db_id = pickle.load(reader)

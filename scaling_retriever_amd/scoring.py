@@ -43,9 +43,18 @@ def _candidates(cand_indptr, cand_ids, nq, device):
 
 
 class DenseIndexHIP:
-    """Flat inner-product index resident in HBM (segments of fp32 [n, dim] rows)."""
+    """Flat inner-product index resident in HBM (segments of [n, dim] rows, all fp32 or all fp16).
 
-    def __init__(self, dim, device=None):
+    row_dtype="fp32" (default): rows are kept as fp32.  A float16 tensor / array / .npy shard added to such an index (as its first
+    rows) makes it an fp16 index all the same - the stored type follows the data.  row_dtype="fp16": fp32 input is rounded to
+    float16 (to nearest even) on the device before it is added, and a finite value that does not fit float16 raises ValueError.
+    An fp16 index holds half the bytes and streams half the bytes per small-batch search; every search / score_pairs result is
+    bit for bit what an fp32 index over `rows.half().float()` returns (include/sr_hip.h sr_dense_index_add_f16)."""
+
+    def __init__(self, dim, device=None, row_dtype="fp32"):
+        if row_dtype not in ("fp32", "fp16"):
+            raise ValueError(f"row_dtype must be 'fp32' or 'fp16', got {row_dtype!r}")
+        self.row_dtype = row_dtype
         _lib.require_gpu()
         self.lib = _lib.load()
         self.dim = int(dim)
@@ -56,21 +65,68 @@ class DenseIndexHIP:
         _lib.check(self.lib.sr_dense_index_create(ctypes.byref(self._h), self.dim), "sr_dense_index_create")
         self._segments = []  # keeps the device tensors alive (the C side holds non-owning views)
 
+    @staticmethod
+    def _round_to_f16(rows, row0=0):
+        """fp32 cuda rows -> float16 (round to nearest even, on the device); ValueError naming the first row in which a finite
+        value leaves the float16 range (|x| >= 65520 rounds to infinity)."""
+        half = rows.to(torch.float16)
+        bad = (torch.isinf(half) & torch.isfinite(rows)).any(dim=1)
+        if bool(bad.any()):
+            r = int(torch.nonzero(bad)[0])
+            raise ValueError(f"row {row0 + r} holds a finite value ({float(rows[r].abs().max()):.6g} at most) that float16 cannot "
+                             "represent (largest finite value 65504): such rows cannot be stored as fp16")
+        return half
+
     def add_device_rows(self, rows, id_base=None, id_stride=1):
-        """rows: fp32 cuda tensor [n, dim] (kept alive by this object, not copied)."""
-        if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != self.dim:
-            raise ValueError(f"expected float32 [n, {self.dim}] rows, got {rows.dtype} {tuple(rows.shape)}")
+        """rows: fp32 or fp16 cuda tensor [n, dim] (kept alive by this object, not copied).  With row_dtype="fp16" an fp32 tensor is
+        rounded to float16 on the device first (that copy is what the index keeps)."""
+        if rows.dtype not in (torch.float32, torch.float16) or rows.dim() != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"expected float32 or float16 [n, {self.dim}] rows, got {rows.dtype} {tuple(rows.shape)}")
         if not rows.is_cuda:
             raise ValueError("add_device_rows needs a cuda tensor")
+        if rows.device != self.device:
+            raise ValueError(f"rows live on {rows.device}, the index on {self.device}")
+        if rows.dtype == torch.float32 and self.row_dtype == "fp16":
+            rows = self._round_to_f16(rows)
         rows = rows.contiguous()
         if id_base is None:
             id_base = self.ntotal
-        if rows.device != self.device:
-            raise ValueError(f"rows live on {rows.device}, the index on {self.device}")
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_index_add(self._h, _ptr(rows), rows.shape[0], int(id_base), int(id_stride)),
-                       "sr_dense_index_add")
+            if rows.dtype == torch.float16:
+                _lib.check(self.lib.sr_dense_index_add_f16(self._h, _ptr(rows), rows.shape[0], int(id_base), int(id_stride)),
+                           "sr_dense_index_add_f16")
+            else:
+                _lib.check(self.lib.sr_dense_index_add(self._h, _ptr(rows), rows.shape[0], int(id_base), int(id_stride)),
+                           "sr_dense_index_add")
         self._segments.append(rows)
+
+    def stored_dtype(self):
+        """"fp32" or "fp16": what the index's rows are stored as (an empty index: "fp32")."""
+        return "fp16" if self.lib.sr_dense_index_row_dtype(self._h) == _lib.SR_DTYPE_F16 else "fp32"
+
+    def owned_bytes(self):
+        """Device bytes the library holds for the segments next to the caller's rows (bf16 planes, the certified filter's fp16
+        plane and error terms); workspaces are not counted."""
+        out = ctypes.c_int64(0)
+        _lib.check(self.lib.sr_dense_index_owned_bytes(self._h, ctypes.byref(out)), "sr_dense_index_owned_bytes")
+        return out.value
+
+    def _staging(self, src_dtype, n):
+        """(element type of the pinned staging ring and of the H2D copies, the HBM segment [n, dim], convert) for host rows of
+        `src_dtype`: float16 sources travel and stay as float16; float32 sources travel as float32 and, under row_dtype="fp16", are
+        rounded on the device piece by piece into a float16 segment (convert = True: no fp32 copy of the segment ever exists)."""
+        if src_dtype == np.float16:
+            return torch.float16, torch.empty((n, self.dim), dtype=torch.float16, device=self.device), False
+        convert = self.row_dtype == "fp16"
+        return torch.float32, torch.empty((n, self.dim), dtype=torch.float16 if convert else torch.float32, device=self.device), convert
+
+    def _h2d_piece(self, dev, r0, r1, pinned, convert):
+        """Queue the copy of a staged piece into rows [r0, r1) of the segment on the current (side) stream."""
+        if not convert:
+            dev[r0:r1].copy_(pinned, non_blocking=True)
+            return
+        tmp = pinned.to(self.device, non_blocking=True)
+        dev[r0:r1].copy_(self._round_to_f16(tmp, r0))
 
     def add_host_rows(self, rows, buffer_size=50000, id_base=None, id_stride=1, piece_bytes=64 << 20, n_buffers=8, n_threads=8):
         """rows: np.float32 [n, dim] - an in-memory array or an np.load(..., mmap_mode="r") view of a shard file.
@@ -82,23 +138,23 @@ class DenseIndexHIP:
         `buffer_size` (rows per add, indexer.py:198-208) is accepted for signature compatibility."""
         import threading
         from concurrent.futures import ThreadPoolExecutor
-        if rows.dtype != np.float32 or rows.ndim != 2 or rows.shape[1] != self.dim:
+        if rows.dtype not in (np.float32, np.float16) or rows.ndim != 2 or rows.shape[1] != self.dim:
             if rows.ndim != 2 or rows.shape[1] != self.dim:
                 raise ValueError(f"expected [n, {self.dim}] rows, got {rows.shape}")
             rows = np.asarray(rows, dtype=np.float32)
         n = rows.shape[0]
-        dev = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+        stage_dt, dev, convert = self._staging(rows.dtype, n)
         if n == 0:
             self.add_device_rows(dev, id_base=id_base, id_stride=id_stride)
             return
-        piece_rows = max(1, int(piece_bytes) // (4 * self.dim))
+        piece_rows = max(1, int(piece_bytes) // ((2 if stage_dt == torch.float16 else 4) * self.dim))
         pieces = [(r0, min(n, r0 + piece_rows)) for r0 in range(0, n, piece_rows)]
         n_buffers = max(1, min(n_buffers, len(pieces)))
         with torch.cuda.device(self.device):
             side = torch.cuda.Stream()
             # `dev` came from the caching allocator on the current stream: a recycled block may still have kernels queued there
             side.wait_stream(torch.cuda.current_stream(self.device))
-            bufs = [torch.empty((piece_rows, self.dim), dtype=torch.float32, pin_memory=True) for _ in range(n_buffers)]
+            bufs = [torch.empty((piece_rows, self.dim), dtype=stage_dt, pin_memory=True) for _ in range(n_buffers)]
             free = [torch.cuda.Event() for _ in range(n_buffers)]
             locks = [threading.Lock() for _ in range(n_buffers)]
 
@@ -109,7 +165,7 @@ class DenseIndexHIP:
                     free[b].synchronize()               # its previous H2D copy has left the buffer
                     np.copyto(bufs[b].numpy()[:r1 - r0], rows[r0:r1])
                     with torch.cuda.device(self.device), torch.cuda.stream(side):
-                        dev[r0:r1].copy_(bufs[b][:r1 - r0], non_blocking=True)
+                        self._h2d_piece(dev, r0, r1, bufs[b][:r1 - r0], convert)
                         free[b].record(side)
             with ThreadPoolExecutor(max_workers=max(1, min(n_threads, n_buffers))) as pool:
                 list(pool.map(move, range(len(pieces))))
@@ -125,14 +181,14 @@ class DenseIndexHIP:
         import threading
         from concurrent.futures import ThreadPoolExecutor
         arr = np.load(path, mmap_mode="r")              # header only: shape, dtype, data offset
-        if arr.dtype != np.float32 or arr.ndim != 2 or arr.shape[1] != self.dim or not arr.flags["C_CONTIGUOUS"]:
+        if arr.dtype not in (np.float32, np.float16) or arr.ndim != 2 or arr.shape[1] != self.dim or not arr.flags["C_CONTIGUOUS"]:
             return self.add_host_rows(np.ascontiguousarray(arr, dtype=np.float32), id_base=id_base, id_stride=id_stride)
         n, offset0 = arr.shape[0], arr.offset
+        stage_dt, dev, convert = self._staging(arr.dtype, n)        # a float16 shard moves half the bytes, file to HBM
         del arr
-        dev = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
         if n == 0:
             return self.add_device_rows(dev, id_base=id_base, id_stride=id_stride)
-        row_bytes = 4 * self.dim
+        row_bytes = (2 if stage_dt == torch.float16 else 4) * self.dim
         piece_rows = max(1, int(piece_bytes) // row_bytes)
         pieces = [(r0, min(n, r0 + piece_rows)) for r0 in range(0, n, piece_rows)]
         n_buffers = max(1, min(n_buffers, len(pieces)))
@@ -141,7 +197,7 @@ class DenseIndexHIP:
             with torch.cuda.device(self.device):
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream(self.device))      # see add_host_rows
-                bufs = [torch.empty((piece_rows, self.dim), dtype=torch.float32, pin_memory=True) for _ in range(n_buffers)]
+                bufs = [torch.empty((piece_rows, self.dim), dtype=stage_dt, pin_memory=True) for _ in range(n_buffers)]
                 free = [torch.cuda.Event() for _ in range(n_buffers)]
                 locks = [threading.Lock() for _ in range(n_buffers)]
 
@@ -158,7 +214,7 @@ class DenseIndexHIP:
                                 raise IOError(f"{path}: short read at row {r0}")
                             got += k
                         with torch.cuda.device(self.device), torch.cuda.stream(side):
-                            dev[r0:r1].copy_(bufs[b][:r1 - r0], non_blocking=True)
+                            self._h2d_piece(dev, r0, r1, bufs[b][:r1 - r0], convert)
                             free[b].record(side)
                 with ThreadPoolExecutor(max_workers=max(1, min(n_threads, n_buffers))) as pool:
                     list(pool.map(move, range(len(pieces))))
@@ -182,7 +238,7 @@ class DenseIndexHIP:
     def set_precision(self, mode):
         """"fp32" (default: the exact kernel), "fp32_filtered" (the same results bit for bit through a certified fp16 filter +
         exact re-score, ~7x faster for batches > 64 queries, one fp16 plane of the corpus in HBM), "bf16x3" / "bf16x6"
-        (split-bf16 scores, not bit-identical)."""
+        (split-bf16 scores, not bit-identical; not available on an index of fp16 rows: SrHipError)."""
         code = {"fp32": 0, "bf16x3": 1, "bf16x6": 2, "fp32_filtered": 3}[mode]
         with torch.cuda.device(self.device):
             _lib.check(self.lib.sr_dense_index_set_precision(self._h, code), "sr_dense_index_set_precision")

@@ -1,0 +1,87 @@
+"""CPU: the fp16-row entry points of the dense index (include/sr_hip.h sr_dense_index_add_f16, _row_dtype, _owned_bytes) are
+declared, exported and bound; the arguments they validate before any device call give the documented status; and the fp16
+instantiations of the dense kernels in the built objects use no scratch."""
+import ctypes
+import os
+import re
+
+import pytest
+
+from test_abi import _kernel_metadata
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("sr_dense_index_add_f16", "sr_dense_index_row_dtype", "sr_dense_index_owned_bytes")
+
+
+def test_fp16_symbols_declared_exported_and_bound():
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "sr_hip.h")).read()
+    assert re.search(r"#define\s+SR_DTYPE_F16\s+2\b", header) and _lib.SR_DTYPE_F16 == 2
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for name in NEW:
+        assert re.search(r"\b%s\s*\(" % name, code), f"{name} is not declared in sr_hip.h"
+        assert hasattr(lib, name) and name in _lib.SIGNATURES
+    for doc in ("INTEGRATION.md", "DESIGN.md"):           # the contract's bound is stated where users and maintainers look
+        text = open(os.path.join(ROOT, doc)).read()
+        assert "sr_dense_index_add_f16" in text and "2^-11" in text, doc
+    assert "2^-11" in header
+
+
+def test_fp16_bad_arguments_without_a_device():
+    """Everything here is rejected (or answered) before the library touches a device: the pointers are never dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(4096)
+    out = ctypes.c_int64(-7)
+    assert lib.sr_dense_index_row_dtype(None) == -1
+    assert lib.sr_dense_index_add_f16(None, p, 4, 0, 1) == _lib.SR_ERR_INVALID and b"null index" in lib.sr_last_error()
+    assert lib.sr_dense_index_owned_bytes(None, ctypes.byref(out)) == _lib.SR_ERR_INVALID
+    h = ctypes.c_void_p()
+    assert lib.sr_dense_index_create(ctypes.byref(h), 64) == 0
+    assert lib.sr_dense_index_row_dtype(h) == _lib.SR_DTYPE_F32                      # an empty index
+    assert lib.sr_dense_index_owned_bytes(h, None) == _lib.SR_ERR_INVALID
+    assert lib.sr_dense_index_owned_bytes(h, ctypes.byref(out)) == 0 and out.value == 0
+    for args, text in [((None, 4, 0, 1), b"null rows"), ((p, -1, 0, 1), b"bad sizes"), ((p, 4, 0, 0), b"bad sizes"),
+                       ((p, 4, -1, 1), b"bad sizes"), ((ctypes.c_void_p(4098), 4, 0, 1), b"16-byte aligned"),
+                       ((p, 4, 0xffffffff, 1), b"32 bits")]:
+        rc = lib.sr_dense_index_add_f16(h, *args)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error() and b"sr_dense_index_add_f16" in lib.sr_last_error(), (args, rc)
+    assert lib.sr_dense_index_add_f16(h, None, 0, 0, 1) == 0                        # no rows: nothing to look at
+    assert lib.sr_dense_index_ntotal(h) == 0 and lib.sr_dense_index_row_dtype(h) == _lib.SR_DTYPE_F32
+    # an index in a split-bf16 mode refuses fp16 rows (an empty index: set_precision has no segment to prepare)
+    assert lib.sr_dense_index_set_precision(h, 1) == 0
+    assert lib.sr_dense_index_add_f16(h, p, 4, 0, 1) == _lib.SR_ERR_UNSUPPORTED and b"fp16" in lib.sr_last_error()
+    assert lib.sr_dense_index_ntotal(h) == 0
+    assert lib.sr_dense_index_destroy(h) == 0
+
+
+def test_python_front_end_rejects_unknown_row_dtype_before_the_gpu():
+    from scaling_retriever_amd.scoring import DenseIndexHIP
+    with pytest.raises(ValueError, match="row_dtype"):
+        DenseIndexHIP(64, row_dtype="bf16")
+
+
+def test_fp16_dense_kernels_use_no_scratch(tmp_path):
+    """The fp16 instantiations hold the same operands as their fp32 twins (narrower loads, widened in registers): none may spill.
+    Checked for every instantiation the default dispatch reaches; dense_score_kernel<2, 2, 4, 4> (a development-switch variant whose
+    fp32 instantiation already keeps one register in scratch) is not one of them."""
+    csrc = os.path.join(ROOT, "scaling_retriever_amd", "csrc")
+    want = {"dense_stream.o": [("dense_stream_kernelILi%dEDF16_" % n, 1) for n in (1, 2, 3, 4)],
+            "dense_score.o": [("dense_score_pipe_kernelILi1EDF16_", 1), ("dense_score_pipe_kernelILi2EDF16_", 1),
+                              ("dense_score_kernelIDF16_Li4ELi1ELi2ELi2E", 1), ("dense_score_kernelIDF16_Li4ELi1ELi2ELi1E", 1)],
+            "dense_filter.o": [("filter_absmax_kernelIDF16_", 1), ("filter_plane_kernelILb0EDF16_", 1), ("filter_rescore_kernelIDF16_", 1)],
+            "pair_score.o": [("dense_pairs_kernelIDF16_", 1)]}
+    for obj, kernels in want.items():
+        meta = _kernel_metadata(os.path.join(csrc, obj), tmp_path)
+        for part, count in kernels:
+            hit = {k: v for k, v in meta.items() if part in k}
+            assert len(hit) == count, (obj, part, sorted(meta))
+            for name, m in hit.items():
+                assert m[".private_segment_fixed_size:"] == 0 and m[".vgpr_spill_count:"] == 0 and m[".sgpr_spill_count:"] == 0, (name, m)
+    # the fp16 streaming kernel keeps the fp32 kernel's register budget (the same 256 bytes per lane and doc block in flight)
+    meta = _kernel_metadata(os.path.join(csrc, "dense_stream.o"), tmp_path)
+    for n in (1, 2, 3, 4):
+        f16 = [v for k, v in meta.items() if "dense_stream_kernelILi%dEDF16_" % n in k][0]
+        f32 = [v for k, v in meta.items() if "dense_stream_kernelILi%dEfE" % n in k][0]
+        assert f16[".vgpr_count:"] <= f32[".vgpr_count:"], (n, f16, f32)
