@@ -40,6 +40,9 @@ def parse_args(argv=None):
                     help="real tokens per encode batch of the indexing task (length-bucketed, multi-worker tokenisation); "
                          "0 = the reference's loader (eval_sparse.py:94-97)")
     ap.add_argument("--tokenize_workers", type=int, default=4)
+    # term budgets (no counterpart in the reference's SparseArguments): keep only the largest terms of a row, 0 = all of them
+    ap.add_argument("--doc_max_terms", type=int, default=0, help="indexing task: terms indexed per document (index size)")
+    ap.add_argument("--query_max_terms", type=int, default=0, help="retrieval task: terms searched per query (latency)")
     args = ap.parse_args(argv)
     if args.eval_metric:
         args.eval_metric = ast.literal_eval(args.eval_metric)
@@ -111,7 +114,8 @@ def sparse_index(args):
     index_dir = args.index_dir[:-1] if args.index_dir.endswith("/") else args.index_dir
     if args.world_size > 1:
         index_dir = f"{index_dir}_{dist.get_rank()}"               # eval_sparse.py:98-100
-    indexer = SparseIndexer(model, index_dir=index_dir, compute_stats=True, dim_voc=model.vocab_size, device=args.local_rank)
+    indexer = SparseIndexer(model, index_dir=index_dir, compute_stats=True, dim_voc=model.vocab_size, device=args.local_rank,
+                            doc_max_terms=args.doc_max_terms)
     indexer.index(loader)
     if args.world_size > 1:
         dist.barrier()
@@ -137,12 +141,13 @@ def sparse_retrieval(args):
         q_loader = DataLoader(Subset(queries, range(lo, hi)), batch_size=args.eval_batch_size, shuffle=False, num_workers=0,
                               collate_fn=collate)
         retriever = ShardedSparseRetrieval(config=config, model=model, compute_stats=True, dim_voc=model.vocab_size,
-                                           device=args.local_rank)
+                                           device=args.local_rank, query_max_terms=args.query_max_terms)
         res = retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0)
         dist.barrier()
         return res
     q_loader = DataLoader(queries, batch_size=args.eval_batch_size, shuffle=False, num_workers=0, collate_fn=collate)
-    retriever = SparseRetrieval(config=config, model=model, compute_stats=True, dim_voc=model.vocab_size, device=args.local_rank)
+    retriever = SparseRetrieval(config=config, model=model, compute_stats=True, dim_voc=model.vocab_size, device=args.local_rank,
+                                query_max_terms=args.query_max_terms)
     return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0)
 
 

@@ -388,6 +388,16 @@ int sr_lora_merge(float* d_W, const float* d_A, const float* d_B, int64_t out_fe
 int sr_sparse_compact(const float* d_reps, int64_t B, int64_t V, int64_t* d_row_ptr,
                       int32_t* d_cols, float* d_vals, int64_t capacity, int64_t* h_nnz,
                       sr_stream stream);
+/* The same compaction under a per-row term budget.  NO reference counterpart: the reference keeps every non-zero
+ * (indexer.py:259-260, :393-399); this extends those two places.  max_terms == 0: no limit, exactly sr_sparse_compact.
+ * Otherwise a row keeps its min(max_terms, nnz) largest non-zeros - ordered by value descending as fp32 numbers (negative values
+ * rank below every positive one; -0.0 is zero and never an entry), ties to the LOWER column - and emits them with cols ascending,
+ * values unchanged; a row with nnz <= max_terms comes out as from sr_sparse_compact.  Inputs are finite (NaN: unspecified).
+ * Capacity, SR_ERR_NOMEM and *h_nnz as sr_sparse_compact (the needed size is at most B * min(max_terms, V)); the call
+ * synchronises the stream.  max_terms < 0 is SR_ERR_INVALID, checked before any device call.                                    */
+int sr_sparse_compact_topm(const float* d_reps, int64_t B, int64_t V, int64_t max_terms,
+                           int64_t* d_row_ptr, int32_t* d_cols, float* d_vals,
+                           int64_t capacity, int64_t* h_nnz, sr_stream stream);
 
 /* run.json of the retrieval drivers, written straight from the result arrays (HOST function: every pointer is host memory).
  * Replaces the per-hit Python loops + json.dump of eval_dense.py:225-241 (`qid_to_rankdata[str(qid)][str(docid)] = float(score)`)

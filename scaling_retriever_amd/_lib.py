@@ -104,6 +104,8 @@ SIGNATURES = {
                                         c_int32, c_int32, c_void_p]),
     "sr_sparse_compact": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                   ctypes.POINTER(c_int64), c_void_p]),
+    "sr_sparse_compact_topm": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                       ctypes.POINTER(c_int64), c_void_p]),
 }
 
 _lib = None

@@ -374,13 +374,27 @@ class DenseFlatIndexer(DenseIndexer):
 
 
 # ======================================================================= sparse reps
-def sparse_reps_to_csr(reps):
+def sparse_reps_to_csr(reps, max_terms=0):
     """[B, V] fp32 cuda tensor -> (row_ptr int64 [B+1], cols int32 [nnz], vals fp32 [nnz]) cuda tensors in
-    torch.nonzero order (indexer.py:259-260, :393-399), via sr_sparse_compact."""
+    torch.nonzero order (indexer.py:259-260, :393-399), via sr_sparse_compact.
+    max_terms > 0 (no reference counterpart): a row keeps only its max_terms largest non-zeros - value descending, ties to the
+    lower column, still emitted with cols ascending and values unchanged (sr_sparse_compact_topm); 0 = every non-zero."""
     lib = _lib.load()
     reps = reps.contiguous().float()
     B, V = reps.shape
     row_ptr = torch.empty(B + 1, dtype=torch.int64, device=reps.device)
+    max_terms = int(max_terms)
+    if max_terms != 0:
+        if max_terms < 0:
+            raise ValueError(f"max_terms must be >= 0 (0 = no limit), got {max_terms}")
+        cap = max(1, min(B * V, B * max_terms))          # the budget bounds the output: no retry
+        n = ctypes.c_int64(0)
+        with torch.cuda.device(reps.device):
+            cols = torch.empty(cap, dtype=torch.int32, device=reps.device)
+            vals = torch.empty(cap, dtype=torch.float32, device=reps.device)
+            _lib.check(lib.sr_sparse_compact_topm(reps.data_ptr(), B, V, max_terms, row_ptr.data_ptr(), cols.data_ptr(), vals.data_ptr(),
+                                                  cap, ctypes.byref(n), _lib.stream_ptr()), "sr_sparse_compact_topm")
+        return row_ptr, cols[:n.value], vals[:n.value]
     cap = max(1, min(B * V, 1 << 22))
     n = ctypes.c_int64(0)
     with torch.cuda.device(reps.device):
@@ -410,10 +424,15 @@ class SparseIndexer:
     as arrays (no per-posting Python loop)."""
 
     def __init__(self, model, index_dir, device, compute_stats=False, dim_voc=None, force_new=True,
-                 filename="array_index.h5py", **kwargs):
+                 filename="array_index.h5py", doc_max_terms=0, **kwargs):
         self.model = model
         self.model.eval()
         self.index_dir = index_dir
+        # per-document term budget (no reference counterpart): only the doc_max_terms largest terms of a document are indexed
+        # (sparse_reps_to_csr); 0 = all of them, the reference's behaviour
+        self.doc_max_terms = int(doc_max_terms)
+        if self.doc_max_terms < 0:
+            raise ValueError(f"doc_max_terms must be >= 0 (0 = no limit), got {doc_max_terms}")
         self.sparse_index = IndexDictOfArray(self.index_dir, dim_voc=dim_voc, force_new=force_new, filename=filename)
         self.compute_stats = compute_stats
         self.device = device
@@ -474,8 +493,10 @@ class SparseIndexer:
                     batch_documents = self._encode_batch(inputs, batch_ids)      # [bz, vocab_size] fp32 on device
             if self.compute_stats:
                 stats["L0_d"] += self.l0(batch_documents).item()
-            row_ptr, col, data = sparse_reps_to_csr(batch_documents)
+            row_ptr, col, data = sparse_reps_to_csr(batch_documents, self.doc_max_terms)
             nnz_per_row = (row_ptr[1:] - row_ptr[:-1])
+            if self.compute_stats and self.doc_max_terms:
+                stats["L0_d_kept"] += float(col.numel()) / max(1, len(nnz_per_row))      # L0_d stays the full representation's
             row = torch.repeat_interleave(torch.arange(len(nnz_per_row), device=row_ptr.device), nnz_per_row) + count
             if (count + len(nnz_per_row)) * self.world_size + self.local_rank >= 2 ** 31:
                 raise OverflowError("global document index exceeds int32 (the posting lists hold int32 doc ids, inverted_index.py:22-55)")
@@ -622,9 +643,14 @@ class SparseRetrieval:
     _static_cache = None      # (the caller's dict - held, so its id cannot be recycled -, device index, n_terms)
 
     def __init__(self, model, config, dim_voc, device, dataset_name=None, index_d=None, compute_stats=False,
-                 is_beir=False, **kwargs):
+                 is_beir=False, query_max_terms=0, **kwargs):
         self.model = model
         self.model.eval()
+        # per-query term budget (no reference counterpart): a query is searched with its query_max_terms largest terms only
+        # (sparse_reps_to_csr); 0 = all of them, the reference's behaviour
+        self.query_max_terms = int(query_max_terms)
+        if self.query_max_terms < 0:
+            raise ValueError(f"query_max_terms must be >= 0 (0 = no limit), got {query_max_terms}")
         assert ("index_dir" in config and index_d is None) or ("index_dir" not in config and index_d is not None)
         if "index_dir" in config:
             self.sparse_index, self.doc_ids = self._open_index(config["index_dir"], dim_voc)
@@ -714,7 +740,7 @@ class SparseRetrieval:
                 reps = encode_group(self.model, group, self.device)
             for batch in group:
                 qids.extend(batch["ids"] if isinstance(batch["ids"], list) else to_list(batch["ids"]))
-            parts.append(QueryCSR(*sparse_reps_to_csr(reps)))
+            parts.append(QueryCSR(*sparse_reps_to_csr(reps, self.query_max_terms)))
             del reps
         if not parts:
             dev = self._dev
@@ -787,7 +813,7 @@ class SparseRetrieval:
             for gi, group in enumerate(groups):
                 with torch.inference_mode(), torch.autocast("cuda", dtype=torch.bfloat16):  # indexer.py:390-391
                     reps = encode_group(self.model, group, self.device)
-                q = QueryCSR(*sparse_reps_to_csr(reps))
+                q = QueryCSR(*sparse_reps_to_csr(reps, self.query_max_terms))
                 del reps
                 nnz += int(q.cols.numel())
                 scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold)
@@ -875,9 +901,9 @@ class HybridIndexer(SparseIndexer):
     (sparse reps [B, V], dense reps [B, H]) from one backbone pass (LlamaBiHybrid -> sr_encode_both)."""
 
     def __init__(self, model, sparse_index_dir, dense_index_dir, device, chunk_size=2_000_000, compute_stats=False,
-                 dim_voc=None, force_new=True, filename="array_index.h5py", **kwargs):
+                 dim_voc=None, force_new=True, filename="array_index.h5py", doc_max_terms=0, **kwargs):
         super().__init__(model, sparse_index_dir, device, compute_stats=compute_stats, dim_voc=dim_voc, force_new=force_new,
-                         filename=filename)
+                         filename=filename, doc_max_terms=doc_max_terms)
         self.sparse_index_dir, self.dense_index_dir, self.chunk_size = sparse_index_dir, dense_index_dir, chunk_size
         os.makedirs(dense_index_dir, exist_ok=True)
         self._dense, self._dense_ids, self._chunk_idx = [], [], 0
@@ -920,9 +946,10 @@ class HybridRetriever(SparseRetrieval):
     """indexer.py:859-1019: queries are encoded once (both heads), scored against the inverted index and against the flat
     dense index; writes {out_dir}/sparse/run.json + q_stats.json and {out_dir}/dense/run.json."""
 
-    def __init__(self, model, sparse_index_dir, dense_index_dir, out_dir, dim_voc, device, **kwargs):
+    def __init__(self, model, sparse_index_dir, dense_index_dir, out_dir, dim_voc, device, query_max_terms=0, **kwargs):
         from .utils.utils import obtain_doc_vec_dir_files
-        super().__init__(model, {"index_dir": sparse_index_dir, "out_dir": out_dir}, dim_voc, device, compute_stats=True)
+        super().__init__(model, {"index_dir": sparse_index_dir, "out_dir": out_dir}, dim_voc, device, compute_stats=True,
+                         query_max_terms=query_max_terms)
         self.sparse_out_dir, self.dense_out_dir = os.path.join(out_dir, "sparse"), os.path.join(out_dir, "dense")
         if is_first_worker():
             os.makedirs(self.sparse_out_dir, exist_ok=True)
@@ -945,7 +972,7 @@ class HybridRetriever(SparseRetrieval):
             for batch in group:
                 qids.extend(batch["ids"] if isinstance(batch["ids"], list) else to_list(batch["ids"]))
             dense_query_vecs.append(batch_dense_reps)
-            parts.append(QueryCSR(*sparse_reps_to_csr(batch_sparse_reps)))
+            parts.append(QueryCSR(*sparse_reps_to_csr(batch_sparse_reps, self.query_max_terms)))
             del batch_sparse_reps
         sparse_query_vecs = QueryCSR.cat(parts)
         dense_query_vecs = torch.cat(dense_query_vecs)
