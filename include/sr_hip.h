@@ -436,7 +436,11 @@ int64_t sr_run_writer_mapped_rounds(void);
  *   RoPE rotation fused; d_qkv bf16 [T,(nh+2nkv)*hd], d_out bf16 [T,nh*hd],
  *   d_cu_seqlens int32 [B+1], d_pos int32 [T], d_key_valid uint8 [T],
  *   d_rope_cos/sin fp32 [max_pos, hd/2]; pass NULL for both when d_qkv is already
- *   rotated (sr_gemm_qkv_rope output) - that is the form sr_encode_* uses.      */
+ *   rotated (sr_gemm_qkv_rope output) - that is the form sr_encode_* uses.  For that
+ *   form the call fetches d_cu_seqlens and picks the kernel by the longest sequence, as
+ *   sr_encode_* does from its own lengths: internally max_seqlen = 0 with apply_rope = 0
+ *   does not occur unless every sequence is empty, and then nothing is launched.
+ *   B = 0 returns SR_OK; num_heads % num_kv_heads != 0 is SR_ERR_INVALID.         */
 int sr_gemm_bf16(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, int32_t epilogue,
                  void* d_C, const int32_t* d_seq_of, sr_stream stream);
 /* QKV projection with the RoPE rotation fused into the epilogue (fp32, HF rotate_half layout):

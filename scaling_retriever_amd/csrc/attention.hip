@@ -601,8 +601,6 @@ static int launch_hd(const AttnArgs& a, hipStream_t s) {
     if (attr_slot) {
         SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_kernel<HD, true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_kernel<HD, false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         *attr_slot = true;
     }
     if constexpr (HD == 128) {
@@ -621,9 +619,11 @@ static int launch_hd(const AttnArgs& a, hipStream_t s) {
         return launch_small<HD, 8>(a, s);
     }
     if (!a.apply_rope && a.max_seqlen > AT_KC) return launch_long<HD, 8>(a, s);
+    // pre-rotated q/k always come with max_seqlen (the encoder passes it, the API hook computes it), so max_seqlen = 0 there means
+    // that every sequence is empty: nothing to write.  Only the rope form runs attention_kernel.
+    if (!a.apply_rope) return SR_OK;
     const dim3 grid((unsigned)a.B, (unsigned)a.nkv);
-    if (a.apply_rope) hipLaunchKernelGGL((attention_kernel<HD, true>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((attention_kernel<HD, false>), grid, dim3(256), lds, s, a);
+    hipLaunchKernelGGL((attention_kernel<HD, true>), grid, dim3(256), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }

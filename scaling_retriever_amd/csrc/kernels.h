@@ -91,7 +91,9 @@ struct AttnArgs {
     int B, nh, nkv, hd;
     float scale;            // 1/sqrt(hd)
     int apply_rope;         // 1: rotate q/k while loading (qkv holds raw projections); 0: qkv is already rotated
-    int max_seqlen;         // longest sequence of the batch (host side), 0 = unknown; <= 256 enables the fast path
+    int max_seqlen;         // longest sequence of the batch (host side); <= 256 enables the fast path.  0 = unknown is for apply_rope = 1
+                            // only: max_seqlen = 0 with apply_rope = 0 does not occur for a batch with a non-empty sequence (every
+                            // caller knows the lengths); there it means that all sequences are empty and nothing is launched
 };
 // Bidirectional (non-causal) GQA attention over packed var-len sequences.
 int launch_attention(const AttnArgs& a, hipStream_t s);

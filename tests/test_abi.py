@@ -58,6 +58,18 @@ def test_attention_f32_hook_validates_before_it_launches():
         assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
 
 
+def test_attention_bf16_hook_empty_batch_and_head_geometry():
+    """sr_attention_varlen: B = 0 is SR_OK, and num_heads that is no multiple of num_kv_heads is SR_ERR_INVALID - both before
+    anything touches a device: the pointers below are never dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(4096)
+    for hd in (64, 128):
+        assert lib.sr_attention_varlen(p, p, p, None, p, None, None, 0, 4, 1, hd, None) == _lib.SR_OK
+        rc = lib.sr_attention_varlen(p, p, p, None, p, None, None, 0, 6, 4, hd, None)
+        assert rc == _lib.SR_ERR_INVALID and b"not a multiple" in lib.sr_last_error(), (rc, lib.sr_last_error())
+
+
 def test_missing_extension_fails_loudly(monkeypatch, tmp_path):
     from scaling_retriever_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
