@@ -47,6 +47,8 @@ def parse_args(argv=None):
                     help="real tokens per doc_encode batch (length-bucketed, multi-worker tokenisation); 0 = the reference's "
                          "loader: eval_batch_size passages padded to the longest, one worker (eval_dense.py:171-179)")
     ap.add_argument("--tokenize_workers", type=int, default=4)
+    ap.add_argument("--allowed_ids_file", type=str, default=None,
+                    help="retrieval task: rank only the documents whose ids this file lists, one id per line (any order, repeats allowed)")
     ap.add_argument("--index_dtype", choices=["fp32", "fp16"], default="fp32",
                     help="retrieval: how the flat index keeps its rows. fp16 rounds the (fp32) shard files once, at ingest, and "
                          "holds half the bytes; the shard files themselves are not changed")
@@ -225,7 +227,22 @@ class LocalFaissDenseRetriever(DenseRetriever):
         return nq, size
 
 
+def allowed_subset_positions(path, id_files, world=1):
+    """--allowed_ids_file: the file's ids (one per line) as sorted unique index positions (the rows of the id files in plan order).  An
+    unknown id: ValueError naming it.  The doc-sharded retrieval has no allow-list."""
+    if world > 1:
+        raise NotImplementedError("--allowed_ids_file is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
+    from scaling_retriever_amd.rerank import InverseIdMap
+    from scaling_retriever_amd.scoring import allowed_positions, read_allowed_ids_file
+    inv = InverseIdMap(np.concatenate([np.load(f) for f in id_files]).tolist())
+    return allowed_positions(read_allowed_ids_file(path), lambda d: inv.pos.get(str(d)))
+
+
 def retrieval(args):
+    if args.allowed_ids_file and args.world_size > 1:           # before the model and the index shards are loaded
+        raise NotImplementedError("--allowed_ids_file is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaDenseCollectionCollator
     from scaling_retriever_amd.dataset.dataset import MSMARCOQueryDataset
     from scaling_retriever_amd.distributed import gather_topk, sharded_dense_search
@@ -259,8 +276,12 @@ def retrieval(args):
         index.set_precision("fp32_filtered")          # exact results, ~3x faster for the whole query set (csrc/dense_filter.hip)
     for fi in range(rank, len(vec_files), world):
         index.add_npy_file(vec_files[fi], id_base=int(offsets[fi]))        # mmap -> pinned ring -> async H2D
+    subset = allowed_subset_positions(args.allowed_ids_file, id_files, world) if args.allowed_ids_file else None
     q_reps, qids = generate_query_vecs(model, q_loader, device)
-    scores, idx = sharded_dense_search(index, q_reps, args.top_k, world)
+    if subset is not None:
+        scores, idx = index.search(q_reps.contiguous(), args.top_k, subset=subset)      # positions = the files' rows in plan order
+    else:
+        scores, idx = sharded_dense_search(index, q_reps, args.top_k, world)
     if world > 1:
         gs, gi = gather_topk(scores, idx, dst=0)
         if gs is not None:

@@ -41,6 +41,8 @@ def parse_args(argv=None):
                          "0 = the reference's loader (eval_sparse.py:94-97)")
     ap.add_argument("--tokenize_workers", type=int, default=4)
     # term budgets (no counterpart in the reference's SparseArguments): keep only the largest terms of a row, 0 = all of them
+    ap.add_argument("--allowed_ids_file", type=str, default=None,
+                    help="retrieval task: rank only the documents whose ids this file lists, one id per line (any order, repeats allowed)")
     ap.add_argument("--doc_max_terms", type=int, default=0, help="indexing task: terms indexed per document (index size)")
     ap.add_argument("--query_max_terms", type=int, default=0, help="retrieval task: terms searched per query (latency)")
     args = ap.parse_args(argv)
@@ -122,6 +124,9 @@ def sparse_index(args):
 
 
 def sparse_retrieval(args):
+    if args.allowed_ids_file and args.world_size > 1:           # before the model and the index shards are loaded
+        raise NotImplementedError("--allowed_ids_file is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaSparseCollectionCollator
     from scaling_retriever_amd.indexer import SparseRetrieval
     from scaling_retriever_amd.modeling.llm_encoder import retriever_class
@@ -131,6 +136,10 @@ def sparse_retrieval(args):
     collate = LlamaSparseCollectionCollator(tokenizer=tokenizer, max_length=args.query_max_length)
     os.makedirs(args.out_dir, exist_ok=True)
     config = {"index_dir": args.index_dir, "out_dir": args.out_dir}
+    allowed_ids = None
+    if args.allowed_ids_file:
+        from scaling_retriever_amd.scoring import read_allowed_ids_file
+        allowed_ids = read_allowed_ids_file(args.allowed_ids_file)
     if args.world_size > 1:
         # The reference asserts world_size == 1 here (eval_sparse.py:114) and needs merge_indexes first.  Doc-sharded: each rank
         # scores the index_dir_{rank} it built, encodes its block of the queries, ONE gather of per-shard top-k.
@@ -142,13 +151,13 @@ def sparse_retrieval(args):
                               collate_fn=collate)
         retriever = ShardedSparseRetrieval(config=config, model=model, compute_stats=True, dim_voc=model.vocab_size,
                                            device=args.local_rank, query_max_terms=args.query_max_terms)
-        res = retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0)
+        res = retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids)      # NotImplementedError with a list
         dist.barrier()
         return res
     q_loader = DataLoader(queries, batch_size=args.eval_batch_size, shuffle=False, num_workers=0, collate_fn=collate)
     retriever = SparseRetrieval(config=config, model=model, compute_stats=True, dim_voc=model.vocab_size, device=args.local_rank,
                                 query_max_terms=args.query_max_terms)
-    return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0)
+    return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids)
 
 
 def evaluate_msmarco(args):

@@ -158,6 +158,25 @@ int sr_dense_index_set_batch_invariant(sr_dense_index* idx, int on);
  * to read that status back (no other host synchronisation, no size read-back before the launch).                              */
 int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries, int64_t nq, const int64_t* d_cand_indptr,
                          const int64_t* d_cand_ids, float* d_out_scores, sr_stream stream);
+/* Top-k within a SUBSET of the documents: one allow-list shared by all queries of the call (what faiss offers as IDSelector on a
+ * flat index).  No reference counterpart: DenseFlatIndexer.search_knn (scaling_retriever/indexer.py:191-217) always ranks the whole
+ * index; this extends it.  d_subset int64 [m] on the device, STRICTLY ASCENDING global doc indices as sr_dense_search returns them
+ * (id_base + row * id_stride of a segment; fp32- and fp16-stored rows alike), m >= 0.  The result is what sr_dense_search with
+ * k = ntotal returns after the documents outside the subset are removed and the list is cut to k: order, tie order (ascending doc
+ * index) and padding (-FLT_MAX, -1; every row when m = 0) as there.  k as for sr_dense_search with m in place of the document count
+ * (k <= m + 4096).  Scores: the fp32 fmaf chain in the exact kernel's k order for EVERY nq - the contract of sr_dense_score_pairs, so a
+ * returned score equals the score sr_dense_score_pairs gives that (query, document), bit for bit, and the score of sr_dense_search
+ * whenever that search accumulates in the same order (see there); it does not depend on m, on nq or on what else is in the subset.
+ * A tile of 64 subset rows is gathered once per block of 16 queries: a row is read from HBM at most ceil(nq / 16) times.  Nothing
+ * of size nq x m is allocated: the subset goes through in slabs, and the queries in sub-batches, sized from the handle's workspace
+ * limit (8 bytes per query and slab entry; for k > sr_max_topk() the large select's buffers as in sr_dense_search) with the same
+ * bits; SR_ERR_NOMEM if one query with a slab of 64 entries does not fit.  Errors: an entry that is in no segment, or is not above
+ * its predecessor: SR_ERR_INVALID, found on the device, sr_last_error() names the first offending position; every output row is
+ * then padding.  Synchronisation as sr_dense_score_pairs: the work is queued on `stream`, the call waits for it once to read the
+ * status back, no size is read back before the launches.                                                                        */
+int sr_dense_search_subset(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
+                           const int64_t* d_subset, int64_t m,
+                           float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
 int sr_dense_index_destroy(sr_dense_index* idx);
 /* Measurement hook: while enabled, every launch of the score kernel is bracketed by HIP
  * events on the search stream.  _read synchronises those events and returns the number
@@ -208,6 +227,20 @@ int sr_sparse_index_set_workspace_limit(sr_sparse_index* idx, int64_t bytes);
 int sr_sparse_score_pairs(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                           int64_t nq, const int64_t* d_cand_indptr, const int64_t* d_cand_ids, float* d_out_scores,
                           sr_stream stream);
+/* sr_sparse_search within a SUBSET of the documents, one allow-list shared by all queries.  No reference counterpart: it extends
+ * SparseRetrieval.numba_score_float + select_topk (scaling_retriever/indexer.py:315-344), which score the whole collection.
+ * d_subset int64 [m] on the device, STRICTLY ASCENDING document positions in [0, n_docs) (as for sr_sparse_score_pairs), m >= 0.
+ * Queries, threshold, id_base / id_stride, outputs, padding (0, -1) and d_out_counts as sr_sparse_search, 1 <= k <= 2^30: the result is
+ * what sr_sparse_search with k = n_docs returns after the documents outside the subset are removed and the list is cut to k.  Scores
+ * are the term-serial unfused chain of sr_sparse_search / sr_sparse_score_pairs and do not depend on m, nq or the rest of the subset.
+ * Two routes, the same bits: one wave per (query, subset document) on the chains of sr_sparse_score_pairs for m < n_docs / 16, the
+ * score array per 8 192-document tile with a gathered select over the subset's entries above that (dev switch
+ * SR_SUBSET_SPARSE_ROUTE=pairs|array forces one).  Workspace, errors (a position outside [0, n_docs) or not above its predecessor)
+ * and synchronisation as sr_dense_search_subset.                                                                                */
+int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
+                            const float* d_q_vals, int64_t nq, int k, float threshold,
+                            const int64_t* d_subset, int64_t m, int64_t id_base, int64_t id_stride,
+                            float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream);
 int sr_sparse_index_destroy(sr_sparse_index* idx);
 /* Measurement hook as for the dense index; algorithmic bytes = 8 B per posting of the
  * query terms that falls in the launched doc tiles (computed on the device).       */

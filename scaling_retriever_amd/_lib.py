@@ -45,6 +45,7 @@ SIGNATURES = {
     "sr_dense_index_set_workspace_limit": (c_int, [c_void_p, c_int64]),
     "sr_dense_index_set_batch_invariant": (c_int, [c_void_p, c_int]),
     "sr_dense_score_pairs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_dense_search_subset": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sr_dense_index_set_precision": (c_int, [c_void_p, c_int]),
     "sr_dense_search_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "sr_dense_search_finish": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -64,6 +65,8 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_sparse_index_set_workspace_limit": (c_int, [c_void_p, c_int64]),
     "sr_sparse_score_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_sparse_search_subset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int64, c_int64,
+                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_sparse_index_block_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
                                             ctypes.POINTER(c_int64)]),
     "sr_sparse_index_destroy": (c_int, [c_void_p]),

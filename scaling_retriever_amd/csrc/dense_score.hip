@@ -17,6 +17,7 @@
 #include "dense_split.h"
 #include "dense_filter.h"
 #include "pair_score.h"
+#include "subset_search.h"
 #include <mutex>
 #include <stdlib.h>
 #include <vector>
@@ -1071,6 +1072,25 @@ extern "C" int sr_dense_search_finish(sr_dense_index* idx, const float* d_querie
     return sr_dense_search(idx, d_queries, nq, k, d_out_scores, d_out_ids, stream);
 }
 
+// the segments as a device table for the gather kernels (pair_score.hip, subset_search.hip), rebuilt when a segment was added; caller holds idx->mu
+static int dense_pair_segs(sr_dense_index* idx, const char* who) {
+    if (idx->pair_segs_n != idx->segs.size()) {           // segments are only ever added, all of one row type
+        std::vector<PairSeg> h;
+        for (const DenseSegment& seg : idx->segs) h.push_back(PairSeg{seg.rows, seg.n, seg.id_base, seg.id_stride});
+        if (idx->pair_segs) (void)hipFree(idx->pair_segs);    // waits for the calls that read it
+        idx->pair_segs = nullptr; idx->pair_segs_n = 0;
+        if (hipMalloc((void**)&idx->pair_segs, sizeof(PairSeg) * h.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            idx->pair_segs = nullptr;
+            sr_set_error("%s: out of device memory for the table of %zu segments", who, h.size());
+            return SR_ERR_NOMEM;
+        }
+        SR_CHECK_HIP(hipMemcpy(idx->pair_segs, h.data(), sizeof(PairSeg) * h.size(), hipMemcpyHostToDevice));
+        idx->pair_segs_n = h.size();
+    }
+    return SR_OK;
+}
+
 extern "C" int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries, int64_t nq, const int64_t* d_cand_indptr,
                                     const int64_t* d_cand_ids, float* d_out_scores, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_score_pairs: null index");
@@ -1080,24 +1100,57 @@ extern "C" int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries,
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
-    if (idx->pair_segs_n != idx->segs.size()) {           // segments are only ever added, all of one row type
-        std::vector<PairSeg> h;
-        for (const DenseSegment& seg : idx->segs) h.push_back(PairSeg{seg.rows, seg.n, seg.id_base, seg.id_stride});
-        if (idx->pair_segs) (void)hipFree(idx->pair_segs);    // waits for the calls that read it
-        idx->pair_segs = nullptr; idx->pair_segs_n = 0;
-        if (hipMalloc((void**)&idx->pair_segs, sizeof(PairSeg) * h.size()) != hipSuccess) {
-            (void)hipGetLastError();
-            idx->pair_segs = nullptr;
-            sr_set_error("sr_dense_score_pairs: out of device memory for the table of %zu segments", h.size());
-            return SR_ERR_NOMEM;
-        }
-        SR_CHECK_HIP(hipMemcpy(idx->pair_segs, h.data(), sizeof(PairSeg) * h.size(), hipMemcpyHostToDevice));
-        idx->pair_segs_n = h.size();
-    }
+    SR_TRY(dense_pair_segs(idx, "sr_dense_score_pairs"));
     SR_TRY(pair_status_begin(&idx->pair_status, d_cand_indptr, nq, s));
     SR_TRY(launch_dense_pairs(idx->pair_segs, (int)idx->pair_segs_n, idx->row_dtype, d_queries, nq, idx->dim, d_cand_indptr, d_cand_ids, d_out_scores,
                               idx->pair_status, s));
     return pair_status_end(idx->pair_status, d_cand_ids, "sr_dense_score_pairs", s);
+}
+
+// Top-k within a subset of the documents (subset_search.hip): scores are the pair scorer's chains, the select is the searches' own
+extern "C" int sr_dense_search_subset(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const int64_t* d_subset, int64_t m,
+                                      float* d_out_scores, int64_t* d_out_ids, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_search_subset: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search_subset: bad nq=%lld", (long long)nq);
+    SR_REQUIRE(m >= 0 && m <= idx->ntotal, "sr_dense_search_subset: a strictly ascending subset of %lld documents holds at most that many, not m=%lld",
+               (long long)idx->ntotal, (long long)m);
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_dense_search_subset: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_REQUIRE(k <= SR_MAX_TOPK || (int64_t)k - SR_MAX_TOPK <= m, "sr_dense_search_subset: k=%d exceeds %d by more than the subset's %lld documents", k,
+               SR_MAX_TOPK, (long long)m);
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_dense_search_subset: null pointer");
+    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_subset: queries must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder::Scope in_order(idx->order, s);
+    int64_t nq_batch = 0, slab = 0;
+    SR_TRY(subset_plan(idx->ws_limit, nq, k, m, 64, &nq_batch, &slab, "sr_dense_search_subset"));
+    if (m > 0) SR_TRY(dense_pair_segs(idx, "sr_dense_search_subset"));
+    SR_TRY(subset_status_begin(&idx->pair_status, s));
+    SR_TRY(launch_subset_check_dense(idx->pair_segs, (int)idx->pair_segs_n, d_subset, m, idx->pair_status, s));
+    for (int64_t qb = 0; qb < nq; qb += nq_batch) {
+        const int64_t nqb = nq - qb < nq_batch ? nq - qb : nq_batch;
+        SR_TRY(idx->ws.ensure(nqb, k, slab));
+        SR_TRY(topk_reset(idx->ws, nqb, s));
+        // short first slabs, doubled: until k rows were seen every one is a candidate (as the searches' first launches)
+        int64_t step = ceil_div64((int64_t)k + 1024, 64) * 64;
+        for (int64_t j0 = 0; j0 < m;) {
+            if (step > slab) step = slab;
+            const int64_t n = m - j0 < step ? m - j0 : step;
+            DenseSubsetArgs a;
+            a.segs = idx->pair_segs; a.n_segs = (int)idx->pair_segs_n; a.dtype = idx->row_dtype;
+            a.Q = d_queries + qb * idx->dim; a.nq = (int)nqb; a.H = idx->dim;
+            a.subset = d_subset + j0; a.n_slab = n;
+            a.tau = idx->ws.tau; a.cand_keys = idx->ws.cand_keys; a.cand_count = idx->ws.cand_count; a.cand_cap = idx->ws.cand_cap;
+            a.st = idx->pair_status;
+            SR_TRY(launch_dense_subset(a, s));
+            SR_TRY(topk_compact(idx->ws, nqb, k, s));
+            j0 += n;
+            step *= 2;
+        }
+        SR_TRY(topk_finalize(idx->ws, nqb, k, -3.402823466e38f, d_out_scores + qb * k, d_out_ids + qb * k, nullptr, s));
+    }
+    return subset_status_end(idx->pair_status, d_subset, "sr_dense_search_subset", "doc index", s);
 }
 
 extern "C" int sr_dense_index_filter_stats(sr_dense_index* idx, int64_t* n_filtered, int64_t* n_fallback) {

@@ -22,3 +22,9 @@ int pair_status_end(PairStatus* d_status, const int64_t* d_cand_ids, const char*
 // dtype = SR_DTYPE_F32 | SR_DTYPE_F16: how the segments' rows are stored (fp16 rows are widened in registers: the same chain)
 int launch_dense_pairs(const PairSeg* d_segs, int n_segs, int dtype, const float* Q, int64_t nq, int H, const int64_t* d_cand_indptr,
                        const int64_t* d_cand_ids, float* d_out, PairStatus* d_status, hipStream_t s);
+
+// sparse pair route: idx->pair_qflags[q] := the terms of query q are valid and strictly ascending (the forward index may serve it), for the nq
+// queries of a call; the buffer grows on demand (who = entry point, for the message of SR_ERR_NOMEM)
+struct sr_sparse_index;
+int sparse_pair_query_flags(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, int64_t nq, const char* who,
+                            hipStream_t s);

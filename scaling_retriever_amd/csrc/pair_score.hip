@@ -5,6 +5,7 @@
 // the pairs, so that no size has to come back to the host before the launch.
 #include "pair_score.h"
 #include "sparse_index.h"
+#include "sparse_pair_chain.h"
 #include <math.h>
 
 // ---------------------------------------------------------------------------------------------------- status ---
@@ -213,6 +214,26 @@ __global__ void sparse_pairs_query_kernel(const int64_t* __restrict__ q_indptr, 
     q_ascending[q] = ok ? 1 : 0;
 }
 
+// idx->pair_qflags[q] for the nq queries of a call (grown on demand): may the forward route serve query q
+int sparse_pair_query_flags(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, int64_t nq, const char* who,
+                            hipStream_t s) {
+    if (idx->pair_qflags_cap < nq) {
+        if (idx->pair_qflags) (void)hipFree(idx->pair_qflags);
+        idx->pair_qflags = nullptr; idx->pair_qflags_cap = 0;
+        if (hipMalloc((void**)&idx->pair_qflags, (size_t)nq) != hipSuccess) {
+            (void)hipGetLastError();
+            idx->pair_qflags = nullptr;
+            sr_set_error("%s: out of device memory for %lld query flags", who, (long long)nq);
+            return SR_ERR_NOMEM;
+        }
+        idx->pair_qflags_cap = nq;
+    }
+    hipLaunchKernelGGL(sparse_pairs_query_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, s, d_q_indptr, d_q_cols, nq,
+                       idx->n_terms, idx->pair_qflags);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
 __global__ __launch_bounds__(256) void sparse_pairs_kernel(SparsePairArgs a) {
 #pragma clang fp contract(off)
     if (a.st->indptr_bad) return;
@@ -231,59 +252,8 @@ __global__ __launch_bounds__(256) void sparse_pairs_kernel(SparsePairArgs a) {
         const int64_t q = pair_query_of(a.cand_indptr, a.nq, p);
         const int64_t tb = a.q_indptr[q], te = a.q_indptr[q + 1];
         const bool forward = a.fwd_indptr != nullptr && a.q_ascending[q] != 0;
-        float s = 0.f;
-        auto ordered_add = [&](bool m, float prod) {
-            uint64_t mm = __ballot(m);
-            while (mm) {
-                const int i = __builtin_ctzll(mm);
-                mm &= mm - 1;
-                s = s + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(prod), i));
-            }
-        };
-        if (forward) {
-            const int64_t b = a.fwd_indptr[doc], e = a.fwd_indptr[doc + 1];
-            for (int64_t c = b; c < e; c += 64) {
-                const int64_t i = c + lane;
-                bool m = false;
-                float prod = 0.f;
-                if (i < e) {
-                    const uint64_t tv = a.fwd_tv[i];
-                    const int32_t t = (int32_t)(tv >> 32);
-                    int64_t lo = tb, hi = te;
-                    while (lo < hi) {
-                        const int64_t mid = (lo + hi) >> 1;
-                        if (a.q_cols[mid] < t) lo = mid + 1; else hi = mid;
-                    }
-                    if (lo < te && a.q_cols[lo] == t) {
-                        m = true;
-                        prod = a.q_vals[lo] * __uint_as_float((uint32_t)tv);
-                    }
-                }
-                ordered_add(m, prod);
-            }
-        } else {
-            for (int64_t c = tb; c < te; c += 64) {
-                const int64_t i = c + lane;
-                bool m = false;
-                float prod = 0.f;
-                if (i < te) {
-                    const int32_t t = a.q_cols[i];
-                    if (t >= 0 && t < a.n_terms) {
-                        const int64_t pe = a.indptr[t + 1];
-                        int64_t lo = a.indptr[t], hi = pe;
-                        while (lo < hi) {
-                            const int64_t mid = (lo + hi) >> 1;
-                            if ((int64_t)a.doc_ids[mid] < doc) lo = mid + 1; else hi = mid;
-                        }
-                        if (lo < pe && (int64_t)a.doc_ids[lo] == doc) {
-                            m = true;
-                            prod = a.q_vals[i] * a.vals[lo];
-                        }
-                    }
-                }
-                ordered_add(m, prod);
-            }
-        }
+        const SparseChainIndex x{a.indptr, a.doc_ids, a.vals, a.n_terms, a.fwd_indptr, a.fwd_tv};
+        const float s = sparse_pair_chain(x, a.q_cols, a.q_vals, tb, te, forward, doc, lane);
         if (lane == 0) a.out[p] = s;
     }
 }
@@ -308,20 +278,7 @@ extern "C" int sr_sparse_score_pairs(sr_sparse_index* idx, const int64_t* d_q_in
     if (!(route && strcmp(route, "postings") == 0)) sparse_cert_forward_index(idx->cert, &a.fwd_indptr, &a.fwd_tv);
     a.q_ascending = nullptr;
     if (a.fwd_indptr) {
-        if (idx->pair_qflags_cap < nq) {
-            if (idx->pair_qflags) (void)hipFree(idx->pair_qflags);
-            idx->pair_qflags = nullptr; idx->pair_qflags_cap = 0;
-            if (hipMalloc((void**)&idx->pair_qflags, (size_t)nq) != hipSuccess) {
-                (void)hipGetLastError();
-                idx->pair_qflags = nullptr;
-                sr_set_error("sr_sparse_score_pairs: out of device memory for %lld query flags", (long long)nq);
-                return SR_ERR_NOMEM;
-            }
-            idx->pair_qflags_cap = nq;
-        }
-        hipLaunchKernelGGL(sparse_pairs_query_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, s, d_q_indptr, d_q_cols, nq,
-                           idx->n_terms, idx->pair_qflags);
-        SR_CHECK_LAUNCH();
+        SR_TRY(sparse_pair_query_flags(idx, d_q_indptr, d_q_cols, nq, "sr_sparse_score_pairs", s));
         a.q_ascending = idx->pair_qflags;
     }
     a.q_indptr = d_q_indptr; a.q_cols = d_q_cols; a.q_vals = d_q_vals; a.nq = nq;

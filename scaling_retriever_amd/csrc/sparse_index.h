@@ -7,6 +7,12 @@
 struct SparseCert;      // sparse_cert.hip
 struct PairStatus;      // pair_score.h
 
+// Geometry of sr_sparse_index::skip (built by sparse_score.hip, which checks these against its own tile constants): the exact scorer's
+// doc tiles hold SR_SPARSE_TILE_DOCS documents (n_tiles of them), and skip[t * (n_sub + 1) + b] = number of postings of term t with
+// doc id < b * SR_SPARSE_SKIP_DOCS for b = 0 .. n_sub, n_sub = n_tiles * (SR_SPARSE_TILE_DOCS / SR_SPARSE_SKIP_DOCS).
+#define SR_SPARSE_TILE_DOCS 8192
+#define SR_SPARSE_SKIP_DOCS 4096
+
 struct sr_sparse_index {
     const int64_t* indptr = nullptr;
     const int32_t* doc_ids = nullptr;

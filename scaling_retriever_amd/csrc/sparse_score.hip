@@ -979,6 +979,7 @@ __global__ void sparse_validate_kernel(const int64_t* __restrict__ indptr, const
 }
 
 #include "sparse_index.h"
+static_assert(SP_TILE == SR_SPARSE_TILE_DOCS && SP_SUB == SR_SPARSE_SKIP_DOCS, "sparse_index.h states the skip table's geometry");
 
 // postings of the batch's query terms inside tiles [tile_begin, tile_begin + n_t): one thread per query term
 __global__ void sparse_count_postings_kernel(const int32_t* __restrict__ skip, int n_tiles, int64_t n_terms,

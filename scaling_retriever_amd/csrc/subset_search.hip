@@ -1,0 +1,455 @@
+// Search within a document subset (gfx950): the top-k of sr_dense_search / sr_sparse_search restricted to ONE allow-list of documents
+// shared by all queries of the call - what faiss offers as IDSelector on a flat index.  The reference has no counterpart: it extends
+// DenseFlatIndexer.search_knn (scaling_retriever/indexer.py:191-217) and SparseRetrieval.numba_score_float + select_topk
+// (scaling_retriever/indexer.py:315-344), which always rank the whole collection.
+//
+// Dense.  The pair scorer (pair_score.hip) fetches a document row once per pair: nq fetches of every row of a shared list.  Here a
+// workgroup (one wave) gathers a tile of 64 subset rows ONCE for a block of SS_QB = 16 queries: every subset row is read from HBM at
+// most ceil(nq / 16) times, not nq times.  Layout as dense_pairs_kernel: lane = row, the rows fetched 64 columns at a time as coalesced
+// 256-byte pieces (16 lanes per row), transposed through a padded LDS tile, the next chunk's loads in flight while this one is
+// processed; the query block's chunk [16][64] is staged in LDS next to it and read as broadcasts.  Every lane keeps 16 running fmaf
+// chains, one per query of the block, each in the exact kernel's k order (per 8 columns k = 8s + j, then 8s + 4 + j): a (query,
+// document) score is the bits of sr_dense_score_pairs and depends on nothing else in the call.  Scores never go to memory as an
+// [nq, m] array: survivors of score >= tau[query] are appended as keys (score, doc index) to the handle's candidate buffer, one slab
+// of the subset at a time, and folded into the running top-k by the select code every search uses (topk.hip, topk_large.hip) - the
+// key holds the doc index of subset entry j itself, so ties fall as in sr_dense_search.
+//
+// Sparse.  Two routes, the same bits (the reference's term-serial unfused chain):
+//   pairs  one wave per (query, subset document): sparse_pair_chain (sparse_pair_chain.h), the chain of sr_sparse_score_pairs.
+//   array  one workgroup per (query, tile of 8 192 documents that holds a subset entry): the tile's slice of the reference's score
+//          array in LDS, the query's terms applied one after the other with a barrier between them, then a gathered select over
+//          scores[subset[j]] for the subset entries of the tile, compacted in ascending position order.
+// Both keep score > threshold and score >= tau[query] and feed the same top-k.
+#include "subset_search.h"
+#include "sparse_index.h"
+#include "sparse_pair_chain.h"
+#include <math.h>
+#include <mutex>
+
+// ---------------------------------------------------------------------------------------------------- status ---
+int subset_status_begin(PairStatus** d_status, hipStream_t s) {
+    if (!*d_status) {
+        if (hipMalloc((void**)d_status, sizeof(PairStatus)) != hipSuccess) {
+            (void)hipGetLastError();
+            *d_status = nullptr;
+            sr_set_error("subset search: out of device memory for %zu status bytes", sizeof(PairStatus));
+            return SR_ERR_NOMEM;
+        }
+    }
+    SR_CHECK_HIP(hipMemsetAsync(&(*d_status)->first_bad, 0xff, sizeof(unsigned long long), s));
+    SR_CHECK_HIP(hipMemsetAsync(&(*d_status)->indptr_bad, 0, 2 * sizeof(int), s));
+    return SR_OK;
+}
+
+int subset_status_end(PairStatus* d_status, const int64_t* d_subset, const char* who, const char* what_id, hipStream_t s) {
+    PairStatus h;
+    SR_CHECK_HIP(hipMemcpyAsync(&h, d_status, sizeof(h), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    if (h.first_bad != ~0ull) {
+        int64_t v[2] = {0, 0};
+        const bool has_prev = h.first_bad > 0;
+        SR_CHECK_HIP(hipMemcpy(v, d_subset + h.first_bad - (has_prev ? 1 : 0), sizeof(int64_t) * (has_prev ? 2 : 1), hipMemcpyDeviceToHost));
+        if (has_prev && v[1] <= v[0])
+            sr_set_error("%s: subset must be strictly ascending: position %llu holds %lld after %lld (nothing was searched)", who, h.first_bad,
+                         (long long)v[1], (long long)v[0]);
+        else
+            sr_set_error("%s: subset position %llu: %s %lld is not in the index (nothing was searched)", who, h.first_bad, what_id,
+                         (long long)v[has_prev ? 1 : 0]);
+        return SR_ERR_INVALID;
+    }
+    return SR_OK;
+}
+
+int subset_plan(int64_t ws_limit, int64_t nq, int k, int64_t m, int64_t min_slab, int64_t* nq_batch, int64_t* slab, const char* who) {
+    const int64_t large_bytes = k > SR_MAX_TOPK ? topk_large_bytes_per_query(k) : 0;
+    const int64_t mm = m > 0 ? m : 1;
+    const int64_t smallest = mm < min_slab ? mm : min_slab;
+    const int64_t per_q = large_bytes + 8 * smallest;
+    const int64_t b_max = ws_limit / per_q;
+    if (b_max < 1) {
+        sr_set_error("%s: k = %d and a slab of %lld subset entries need %lld bytes of workspace per query (limit %lld bytes)", who, k,
+                     (long long)smallest, (long long)per_q, (long long)ws_limit);
+        return SR_ERR_NOMEM;
+    }
+    int64_t b = nq < b_max ? nq : b_max;
+    if (b < nq && b >= 16) b = b / 16 * 16;               // whole query blocks of the dense kernel
+    int64_t sl = (ws_limit / b - large_bytes) / 8;
+    if (sl >= 64) sl = sl / 64 * 64;                      // whole row tiles
+    if (sl > (1ll << 20)) sl = 1ll << 20;
+    if (const char* e = sr_dev_getenv("SR_SUBSET_MAX_SLAB")) {        // dev switch: several slabs on inputs far below any workspace limit (tests)
+        const int64_t cap = atoll(e);
+        if (cap >= 1 && sl > cap) sl = cap;
+    }
+    if (sl < smallest) sl = smallest;
+    if (sl > mm) sl = mm;
+    *nq_batch = b;
+    *slab = sl;
+    return SR_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------- dense ---
+// the segment row of global doc index gid, as dense_pairs_kernel finds it; false: in no segment
+__device__ inline bool subset_dense_row(const PairSeg* __restrict__ segs, int n_segs, int64_t gid, int* seg, int64_t* row) {
+    for (int sgi = 0; sgi < n_segs; ++sgi) {
+        const int64_t off = gid - segs[sgi].id_base, stride = segs[sgi].id_stride;
+        int64_t r = off;                                  // stride 1 (every segment of DenseFlatIndexer): no 64-bit divide
+        bool in_seg = off >= 0;
+        if (stride != 1) {
+            r = off / stride;
+            in_seg = in_seg && r * stride == off;
+        }
+        if (in_seg && r < segs[sgi].n) {
+            *seg = sgi;
+            *row = r;
+            return true;
+        }
+    }
+    return false;
+}
+
+__global__ void subset_check_dense_kernel(const PairSeg* __restrict__ segs, int n_segs, const int64_t* __restrict__ subset, int64_t m,
+                                          PairStatus* __restrict__ st) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int64_t gid = subset[j];
+    int seg;
+    int64_t row;
+    bool ok = subset_dense_row(segs, n_segs, gid, &seg, &row);
+    if (j > 0 && subset[j - 1] >= gid) ok = false;
+    if (!ok) atomicMin(&st->first_bad, (unsigned long long)j);
+}
+
+int launch_subset_check_dense(const PairSeg* d_segs, int n_segs, const int64_t* d_subset, int64_t m, PairStatus* d_status, hipStream_t s) {
+    if (m == 0) return SR_OK;
+    hipLaunchKernelGGL(subset_check_dense_kernel, dim3((unsigned)ceil_div64(m, 256)), dim3(256), 0, s, d_segs, n_segs, d_subset, m, d_status);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+#define SS_QB 16        // queries per workgroup: a subset row is fetched ceil(nq / SS_QB) times
+#define SS_KC 64        // columns per chunk
+template <typename T>
+__global__ __launch_bounds__(64) void dense_subset_kernel(DenseSubsetArgs a) {
+    __shared__ float tile[64][SS_KC + 1];
+    __shared__ __attribute__((aligned(16))) float qs[SS_QB][SS_KC];
+    __shared__ const T* rowp[64];
+    if (a.st->first_bad != ~0ull) return;                 // the check ran before this launch on the same stream
+    const int lane = threadIdx.x;
+    const int H = a.H;
+    const int n_qblk = (a.nq + SS_QB - 1) / SS_QB;
+    const int q0 = (int)(blockIdx.x % (unsigned)n_qblk) * SS_QB;      // the query blocks of one tile run side by side: its rows come from L2
+    const int64_t j = (int64_t)(blockIdx.x / (unsigned)n_qblk) * 64 + lane;
+    const T* row = nullptr;
+    uint32_t gid = 0;
+    if (j < a.n_slab) {
+        const int64_t g = a.subset[j];
+        int seg;
+        int64_t r;
+        if (subset_dense_row(a.segs, a.n_segs, g, &seg, &r)) {
+            row = static_cast<const T*>(a.segs[seg].rows) + r * (int64_t)H;
+            gid = (uint32_t)g;
+        }
+    }
+    rowp[lane] = row;
+    __syncthreads();
+    const T* myp[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) myp[i] = rowp[i * 4 + (lane >> 4)];
+    const int nch = (H + SS_KC - 1) / SS_KC;
+    float acc[SS_QB];
+#pragma unroll
+    for (int qi = 0; qi < SS_QB; ++qi) acc[qi] = 0.f;
+    auto fetch = [&](int k0, f32x4 (&v)[16], f32x4 (&qv)[SS_QB / 4]) {
+        const int col = k0 + (lane & 15) * 4;             // H % 16 == 0: a 16-byte piece is inside the row or beyond it
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (myp[i] && col < H) v[i] = sr_load_row4<T>(myp[i] + col);
+        }
+#pragma unroll
+        for (int i = 0; i < SS_QB / 4; ++i) {             // query i * 4 + (lane >> 4) of the block, the same 16-byte piece
+            const int q = q0 + i * 4 + (lane >> 4);
+            qv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (q < a.nq && col < H) qv[i] = *reinterpret_cast<const f32x4*>(a.Q + (int64_t)q * H + col);
+        }
+    };
+    auto chunk = [&](const f32x4 (&v)[16], const f32x4 (&qv)[SS_QB / 4], int k0) {
+        __syncthreads();                                  // the previous chunk is consumed
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            float* t = &tile[i * 4 + (lane >> 4)][(lane & 15) * 4];
+            t[0] = v[i][0]; t[1] = v[i][1]; t[2] = v[i][2]; t[3] = v[i][3];
+        }
+#pragma unroll
+        for (int i = 0; i < SS_QB / 4; ++i) *reinterpret_cast<f32x4*>(&qs[i * 4 + (lane >> 4)][(lane & 15) * 4]) = qv[i];
+        __syncthreads();
+        const int ncol = H - k0 >= SS_KC ? SS_KC : H - k0;    // the last chunk of a dim that is not a multiple of 64: its columns only
+        if (ncol == SS_KC) {
+#pragma unroll
+            for (int s8 = 0; s8 < SS_KC; s8 += 8)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const float d0 = tile[lane][s8 + jj], d1 = tile[lane][s8 + 4 + jj];
+#pragma unroll
+                    for (int qi = 0; qi < SS_QB; ++qi) {
+                        acc[qi] = __builtin_fmaf(qs[qi][s8 + jj], d0, acc[qi]);
+                        acc[qi] = __builtin_fmaf(qs[qi][s8 + 4 + jj], d1, acc[qi]);
+                    }
+                }
+        } else {
+            for (int s8 = 0; s8 < ncol; s8 += 8)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const float d0 = tile[lane][s8 + jj], d1 = tile[lane][s8 + 4 + jj];
+#pragma unroll
+                    for (int qi = 0; qi < SS_QB; ++qi) {
+                        acc[qi] = __builtin_fmaf(qs[qi][s8 + jj], d0, acc[qi]);
+                        acc[qi] = __builtin_fmaf(qs[qi][s8 + 4 + jj], d1, acc[qi]);
+                    }
+                }
+        }
+    };
+    f32x4 va[16], vb[16], qa[SS_QB / 4], qb[SS_QB / 4];
+    fetch(0, va, qa);
+    for (int c = 0; c < nch; c += 2) {
+        if (c + 1 < nch) fetch((c + 1) * SS_KC, vb, qb);
+        chunk(va, qa, c * SS_KC);
+        if (c + 1 >= nch) break;
+        if (c + 2 < nch) fetch((c + 2) * SS_KC, va, qa);
+        chunk(vb, qb, (c + 1) * SS_KC);
+    }
+    if (!row) return;
+#pragma unroll
+    for (int qi = 0; qi < SS_QB; ++qi) {
+        const int q = q0 + qi;
+        if (q < a.nq && acc[qi] >= a.tau[q]) {
+            const int pos = atomicAdd(&a.cand_count[q], 1);
+            if (pos < a.cand_cap) a.cand_keys[(int64_t)q * a.cand_cap + pos] = sr_make_key(acc[qi], gid);
+        }
+    }
+}
+
+int launch_dense_subset(const DenseSubsetArgs& a, hipStream_t s) {
+    if (a.n_slab == 0 || a.nq == 0) return SR_OK;
+    const int64_t blocks = ceil_div64(a.n_slab, 64) * ceil_div64(a.nq, SS_QB);
+    SR_REQUIRE(blocks < (1ll << 31), "subset search: %lld workgroups in one launch", (long long)blocks);
+    if (a.dtype == SR_DTYPE_F16) hipLaunchKernelGGL(dense_subset_kernel<_Float16>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(dense_subset_kernel<float>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- sparse ---
+__global__ void subset_check_sparse_kernel(const int64_t* __restrict__ subset, int64_t m, int64_t n_docs, PairStatus* __restrict__ st) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int64_t d = subset[j];
+    if (d < 0 || d >= n_docs || (j > 0 && subset[j - 1] >= d)) atomicMin(&st->first_bad, (unsigned long long)j);
+}
+
+struct SparseSubsetArgs {
+    SparseChainIndex x;
+    int64_t n_docs;
+    const uint8_t* q_ascending;     // pairs route with a forward index: [nq of the call], indexed like q_indptr
+    const int64_t* q_indptr; const int32_t* q_cols; const float* q_vals;      // q_indptr points at the batch's first query
+    int64_t nq;                     // queries of the batch
+    const int64_t* subset;          // pairs: the slab; array: the whole list
+    int64_t n_sub;
+    int tile_begin;                 // array: first tile of this launch
+    const int32_t* skip; int skip_n;      // array: the index's skip table (sparse_index.h), skip_n + 1 entries per term
+    float threshold;
+    const float* tau; uint64_t* cand_keys; int* cand_count; int64_t cand_cap;
+    uint32_t id_base, id_stride;
+    const PairStatus* st;
+};
+
+__global__ __launch_bounds__(256) void sparse_subset_pairs_kernel(SparseSubsetArgs a) {
+    if (a.st->first_bad != ~0ull) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t total = a.nq * a.n_sub;
+    const int64_t n_waves = (int64_t)gridDim.x * 4;
+    for (int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); p < total; p += n_waves) {
+        const int64_t j = p / a.nq, q = p - j * a.nq;     // the waves of a workgroup share a document's row
+        const int64_t doc = a.subset[j];
+        const int64_t tb = a.q_indptr[q], te = a.q_indptr[q + 1];
+        const bool forward = a.x.fwd_indptr != nullptr && a.q_ascending[q] != 0;
+        const float s = sparse_pair_chain(a.x, a.q_cols, a.q_vals, tb, te, forward, doc, lane);
+        if (lane == 0 && s > a.threshold && s >= a.tau[q]) {
+            const int pos = atomicAdd(&a.cand_count[q], 1);
+            if (pos < a.cand_cap) a.cand_keys[q * a.cand_cap + pos] = sr_make_key(s, a.id_base + (uint32_t)doc * a.id_stride);
+        }
+    }
+}
+
+#define SS_TILE SR_SPARSE_TILE_DOCS      // the exact scorer's doc tiles: the index's skip table gives a term's run inside one
+// first i in [lo, hi) with v[i] >= x (hi: none)
+template <typename V>
+__device__ inline int64_t subset_lower_bound(const V* __restrict__ v, int64_t lo, int64_t hi, int64_t x) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)v[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void sparse_subset_array_kernel(SparseSubsetArgs a) {
+#pragma clang fp contract(off)
+    __shared__ float sc[SS_TILE];
+    __shared__ int wave_tot[4];
+    __shared__ int s_base;
+    if (a.st->first_bad != ~0ull) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t q = blockIdx.x;
+    const int tile = a.tile_begin + (int)blockIdx.y;
+    const int64_t doc0 = (int64_t)tile * SS_TILE;
+    const int n_here = (int)((a.n_docs - doc0) < SS_TILE ? (a.n_docs - doc0) : SS_TILE);
+    // the subset entries of this tile (the same in every thread)
+    const int64_t jb = subset_lower_bound(a.subset, 0, a.n_sub, doc0);
+    const int64_t je = subset_lower_bound(a.subset, jb, a.n_sub, doc0 + n_here);
+    if (jb == je) return;
+    for (int d = tid; d < SS_TILE; d += 256) sc[d] = 0.f;
+    __syncthreads();
+    // the reference's loop (scaling_retriever/indexer.py:324-340): for each query term in the query's order, scores[doc] += q_t * v
+    for (int64_t i = a.q_indptr[q]; i < a.q_indptr[q + 1]; ++i) {
+        const int64_t t = a.q_cols[i];
+        if (t < 0 || t >= a.x.n_terms) continue;          // an unknown term is an empty posting list
+        const float w = a.q_vals[i];
+        const int32_t* sk = a.skip + t * (a.skip_n + 1) + (int64_t)tile * (SS_TILE / SR_SPARSE_SKIP_DOCS);
+        const int64_t pb = a.x.indptr[t] + sk[0], pe = a.x.indptr[t] + sk[SS_TILE / SR_SPARSE_SKIP_DOCS];     // the term's run inside this tile
+        for (int64_t p = pb + tid; p < pe; p += 256) {    // docs are unique inside one posting list
+            const int d = (int)((int64_t)a.x.doc_ids[p] - doc0);
+            const float prod = w * a.x.vals[p];
+            sc[d] = sc[d] + prod;
+        }
+        __syncthreads();                                  // term-serial: the next term may touch the same docs
+    }
+    // gathered select: the tile's subset entries with score > threshold and score >= tau, in ascending position order
+    const float tq = a.tau[q], thr = a.threshold;
+    const int n_sub_here = (int)(je - jb);                // <= SS_TILE: the entries are distinct docs of the tile
+    const int per_t = (n_sub_here + 255) / 256;           // thread tid owns entries [tid * per_t, + per_t)
+    int cnt = 0;
+    for (int e = tid * per_t; e < (tid + 1) * per_t && e < n_sub_here; ++e) {
+        const int d = (int)(a.subset[jb + e] - doc0);
+        const float s = sc[d];
+        cnt += (s > thr && s >= tq) ? 1 : 0;
+    }
+    int incl = cnt;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int wbase = 0, total = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) wbase += wave_tot[w];
+        total += wave_tot[w];
+    }
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(&a.cand_count[q], total);
+    __syncthreads();
+    int pos = s_base + wbase + incl - cnt;
+    uint64_t* dst = a.cand_keys + q * a.cand_cap;
+    for (int e = tid * per_t; e < (tid + 1) * per_t && e < n_sub_here; ++e) {
+        const int64_t doc = a.subset[jb + e];
+        const float s = sc[(int)(doc - doc0)];
+        if (s > thr && s >= tq) {
+            if (pos < a.cand_cap) dst[pos] = sr_make_key(s, a.id_base + (uint32_t)doc * a.id_stride);
+            ++pos;
+        }
+    }
+}
+
+// Route rule.  The pair route costs one wave and a binary search per posting of every (query, subset document); the array route streams
+// the postings of the query's terms once per tile whatever m is, and a streamed posting costs roughly a sixteenth of a searched one.  So
+// the array route serves subsets of at least a sixteenth of the collection, the pair route smaller ones (unmeasured).  Dev switch
+// SR_SUBSET_SPARSE_ROUTE=pairs|array forces one (tests compare the two).
+static bool subset_sparse_use_array(int64_t m, int64_t n_docs) {
+    if (const char* route = sr_dev_getenv("SR_SUBSET_SPARSE_ROUTE")) {
+        if (strcmp(route, "array") == 0) return true;
+        if (strcmp(route, "pairs") == 0) return false;
+    }
+    return m * 16 >= n_docs;
+}
+
+extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                       int64_t nq, int k, float threshold, const int64_t* d_subset, int64_t m, int64_t id_base,
+                                       int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
+                                       sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_search_subset: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_subset: bad nq");
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_subset: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_REQUIRE(m >= 0 && m <= idx->n_docs, "sr_sparse_search_subset: a strictly ascending subset of %lld documents holds at most that many, not m=%lld",
+               (long long)idx->n_docs, (long long)m);
+    SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
+               "sr_sparse_search_subset: global doc index exceeds 32 bits");
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_sparse_search_subset: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder::Scope in_order(idx->order, s);
+    const bool array = subset_sparse_use_array(m, idx->n_docs);
+    int64_t nq_batch = 0, slab = 0;
+    SR_TRY(subset_plan(idx->ws_limit, nq, k, m, array ? SS_TILE : 64, &nq_batch, &slab, "sr_sparse_search_subset"));
+    SR_TRY(subset_status_begin(&idx->pair_status, s));
+    if (m > 0) {
+        hipLaunchKernelGGL(subset_check_sparse_kernel, dim3((unsigned)ceil_div64(m, 256)), dim3(256), 0, s, d_subset, m, idx->n_docs,
+                           idx->pair_status);
+        SR_CHECK_LAUNCH();
+    }
+    SparseSubsetArgs a;
+    a.x = SparseChainIndex{idx->indptr, idx->doc_ids, idx->vals, idx->n_terms, nullptr, nullptr};
+    a.n_docs = idx->n_docs;
+    a.q_ascending = nullptr;
+    if (!array && m > 0) {
+        // the pair route's own two ways to the postings, as in sr_sparse_score_pairs (dev switch SR_PAIR_SPARSE_ROUTE=postings)
+        const char* route = sr_dev_getenv("SR_PAIR_SPARSE_ROUTE");
+        if (!(route && strcmp(route, "postings") == 0)) sparse_cert_forward_index(idx->cert, &a.x.fwd_indptr, &a.x.fwd_tv);
+        if (a.x.fwd_indptr) SR_TRY(sparse_pair_query_flags(idx, d_q_indptr, d_q_cols, nq, "sr_sparse_search_subset", s));
+    }
+    a.q_cols = d_q_cols; a.q_vals = d_q_vals;
+    a.skip = idx->skip; a.skip_n = idx->n_tiles * (SR_SPARSE_TILE_DOCS / SR_SPARSE_SKIP_DOCS);
+    a.threshold = threshold;
+    a.id_base = (uint32_t)id_base; a.id_stride = (uint32_t)id_stride;
+    a.st = idx->pair_status;
+    const int n_tiles = idx->n_tiles;
+    // a launch appends at most min(m, its docs) keys per query; slab < m only with slab >= SS_TILE (subset_plan: min_slab)
+    int tiles_per_launch = slab >= m || slab < SS_TILE ? n_tiles : (int)(slab / SS_TILE);
+    if (tiles_per_launch > 65535) tiles_per_launch = 65535;                   // the grid's second dimension
+    for (int64_t qb = 0; qb < nq; qb += nq_batch) {
+        const int64_t nqb = nq - qb < nq_batch ? nq - qb : nq_batch;
+        SR_TRY(idx->ws.ensure(nqb, k, slab));
+        SR_TRY(topk_reset(idx->ws, nqb, s));
+        a.q_indptr = d_q_indptr + qb;
+        a.q_ascending = a.x.fwd_indptr ? idx->pair_qflags + qb : nullptr;
+        a.nq = nqb;
+        a.tau = idx->ws.tau; a.cand_keys = idx->ws.cand_keys; a.cand_count = idx->ws.cand_count; a.cand_cap = idx->ws.cand_cap;
+        if (m > 0 && array) {
+            a.subset = d_subset; a.n_sub = m;
+            for (int t0 = 0; t0 < n_tiles; t0 += tiles_per_launch) {
+                const int nt = n_tiles - t0 < tiles_per_launch ? n_tiles - t0 : tiles_per_launch;
+                a.tile_begin = t0;
+                hipLaunchKernelGGL(sparse_subset_array_kernel, dim3((unsigned)nqb, (unsigned)nt), dim3(256), 0, s, a);
+                SR_CHECK_LAUNCH();
+                SR_TRY(topk_compact(idx->ws, nqb, k, s));
+            }
+        } else if (m > 0) {
+            // short first slabs, doubled: until k entries were seen every one is a candidate (as the searches' first launches)
+            int64_t step = ceil_div64((int64_t)k + 1024, 64) * 64;
+            for (int64_t j0 = 0; j0 < m;) {
+                if (step > slab) step = slab;
+                const int64_t n = m - j0 < step ? m - j0 : step;
+                a.subset = d_subset + j0; a.n_sub = n; a.tile_begin = 0;
+                const int64_t waves = nqb * n;
+                const int64_t grid = ceil_div64(waves, 4) < (int64_t)sr_cu_count() * 8 ? ceil_div64(waves, 4) : (int64_t)sr_cu_count() * 8;
+                hipLaunchKernelGGL(sparse_subset_pairs_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
+                SR_CHECK_LAUNCH();
+                SR_TRY(topk_compact(idx->ws, nqb, k, s));
+                j0 += n;
+                step *= 2;
+            }
+        }
+        SR_TRY(topk_finalize(idx->ws, nqb, k, 0.f, d_out_scores + qb * k, d_out_ids + qb * k, d_out_counts ? d_out_counts + qb : nullptr, s));
+    }
+    return subset_status_end(idx->pair_status, d_subset, "sr_sparse_search_subset", "position", s);
+}

@@ -238,9 +238,11 @@ class ShardedSparseRetriever:
             assert torch.equal(indptr2, indptr_t)
         self.index = SparseIndexHIP(indptr_t, local, vals_t, self.n_local, device=device)
 
-    def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, dst=0):
+    def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, dst=0, subset=None):
         """Queries replicated on every rank (CSR).  Returns (scores [nq, k], global ids [nq, k], counts [nq]) on rank dst,
-        (None, None, None) elsewhere; rows padded with (0, -1) like sr_sparse_search."""
+        (None, None, None) elsewhere; rows padded with (0, -1) like sr_sparse_search.  subset: not supported on a doc-sharded index."""
+        if subset is not None:
+            raise NotImplementedError("ShardedSparseRetriever.search: an allow-list (subset) is not supported on a doc-sharded index")
         from .scoring import topk_merge
         s, i, c = self.index.search(q_indptr, q_cols, q_vals, k, threshold=threshold, id_base=self.rank, id_stride=self.world_size)
         gs, gi = gather_topk(s, i, dst=dst)
@@ -267,8 +269,11 @@ class ShardedDenseRetriever:
         """rows: fp32 cuda tensor [n_local, H] = the embeddings of dataset rows rank, rank+W, ..."""
         self.index.add_device_rows(rows, id_base=self.rank, id_stride=self.world_size)
 
-    def search(self, queries, k, dst=0):
-        """queries replicated on every rank.  Returns (scores, global ids) on rank dst, (None, None) elsewhere."""
+    def search(self, queries, k, dst=0, subset=None):
+        """queries replicated on every rank.  Returns (scores, global ids) on rank dst, (None, None) elsewhere.  subset: not supported on
+        a doc-sharded index."""
+        if subset is not None:
+            raise NotImplementedError("ShardedDenseRetriever.search: an allow-list (subset) is not supported on a doc-sharded index")
         from .scoring import topk_merge
         s, i = sharded_dense_search(self.index, queries, k, self.world_size)
         gs, gi = gather_topk(s, i, dst=dst)

@@ -271,8 +271,17 @@ class DenseFlatIndexer(DenseIndexer):
 
     KNN_CHUNKS = 2          # search_knn pipelines the query set in this many pieces when it is large (>= 1 024 queries)
 
-    def search_knn(self, query_reps, top_docs: int):
-        """indexer.py:210-214: (list of db-id lists, fp32 scores [nq, k]); label -1 (fewer than k vectors) -> None.  The lists come
+    def allowed_subset(self, allowed_ids):
+        """External database ids (any order, duplicates allowed) -> the sorted unique index positions as an int64 tensor on the index's
+        device: the allow-list of search_knn / search_arrays, uploaded once per call.  An unknown id: ValueError naming it."""
+        from .scoring import allowed_positions
+        inv = self.inverse_id_map()
+        return torch.from_numpy(allowed_positions(allowed_ids, lambda d: inv.pos.get(str(d)))).to(self.index.device)
+
+    def search_knn(self, query_reps, top_docs: int, allowed_ids=None):
+        """indexer.py:210-214: (list of db-id lists, fp32 scores [nq, k]); label -1 (fewer than k vectors) -> None.  allowed_ids (None:
+        the whole index): database ids, any order, duplicates allowed - only these documents are ranked (DenseIndexHIP.search, subset).
+        The lists come
         from id_lists (csrc/host_lists.c).  A large query set is searched in KNN_CHUNKS pieces, the GPU working on piece c + 1 (in a
         worker thread: the C call releases the GIL) while this thread builds the lists of piece c - the exact results do not depend
         on how the queries are batched (pieces stay above 64 queries: one kernel family, one k order)."""
@@ -281,9 +290,10 @@ class DenseFlatIndexer(DenseIndexer):
         else:
             q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
         nq = q.shape[0]
+        subset = None if allowed_ids is None else self.allowed_subset(allowed_ids)
         n_chunks = self.KNN_CHUNKS if nq >= 1024 else 1
         if n_chunks == 1:
-            scores, indexes = self.search_arrays(q, top_docs)
+            scores, indexes = self.search_arrays(q, top_docs, _subset=subset)
             return self.id_lists(indexes), scores
         from concurrent.futures import ThreadPoolExecutor
         per = (nq + n_chunks - 1) // n_chunks
@@ -295,7 +305,7 @@ class DenseFlatIndexer(DenseIndexer):
         def gpu(c):
             with torch.cuda.device(dev):
                 torch.cuda.current_stream(dev).wait_event(ready)          # the worker thread's current stream is the default one
-                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs)
+                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs, _subset=subset)
         top_doc_ids, score_parts = [], []
         with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(gpu, 0)
@@ -307,14 +317,17 @@ class DenseFlatIndexer(DenseIndexer):
                 score_parts.append(scores)
         return top_doc_ids, np.concatenate(score_parts)
 
-    def search_arrays(self, query_reps, top_docs: int):
+    def search_arrays(self, query_reps, top_docs: int, allowed_ids=None, _subset=None):
         """(scores fp32 [nq, k], index positions int64 [nq, k]; -1 = fewer than k vectors) as host arrays: what search_knn maps
-        to db ids, and what the run.json writer takes as they are (utils/run_file.py)."""
+        to db ids, and what the run.json writer takes as they are (utils/run_file.py).  allowed_ids as for search_knn (_subset: its
+        positions, already on the device)."""
+        if allowed_ids is not None:
+            _subset = self.allowed_subset(allowed_ids)
         if isinstance(query_reps, torch.Tensor):
             q = query_reps.to(device=self.index.device, dtype=torch.float32)
         else:
             q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
-        scores, indexes = self.index.search(q, top_docs)
+        scores, indexes = self.index.search(q, top_docs, subset=_subset)
         return to_host(scores), to_host(indexes)
 
     def inverse_id_map(self):
@@ -774,12 +787,22 @@ class SparseRetrieval:
             self._doc_table = IdTable(_doc_id_table(self.doc_ids, self.sparse_index.nb_docs()))
         return self._doc_table
 
-    def _sparse_retrieve_multithreaded(self, sparse_query_vecs, qids, threshold=0., topk=1000):
-        """indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
+    def allowed_subset(self, allowed_ids):
+        """Collection ids (any order, duplicates allowed) -> the sorted unique document positions of the inverted index as an int64
+        tensor on its device: the allow-list of retrieve, uploaded once per call.  An unknown id: ValueError naming it."""
+        from .scoring import allowed_positions
+        inv = self.inverse_id_map()
+        return torch.from_numpy(allowed_positions(allowed_ids, lambda d: inv.pos.get(str(d)))).to(self._dev)
+
+    def _sparse_retrieve_multithreaded(self, sparse_query_vecs, qids, threshold=0., topk=1000, allowed_ids=None, _subset=None):
+        """allowed_ids (None: every document): collection ids - only these documents are ranked (_subset: their positions, already on
+        the device).  indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
         whole query set is one batched HIP search (the doc space is tiled across workgroups instead) and `res` is a RunResult
         over the result arrays: the same mapping, without 7 M dict insertions."""
         q = _as_query_csr(sparse_query_vecs, self._dev)
-        scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold)
+        if allowed_ids is not None:
+            _subset = self.allowed_subset(allowed_ids)
+        scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=_subset)
         res = RunResult(qids, to_host(scores), to_host(ids), self.doc_id_table(), to_host(counts))
         stats = defaultdict(float)
         stats["L0_q"] = q.mean_l0()
@@ -792,8 +815,10 @@ class SparseRetrieval:
                 json.dump(stats, handler)
         res.dump(os.path.join(self.out_dir, "run.json"))        # sr_write_run_json: the bytes json.dump(res) writes
 
-    def retrieve(self, q_loader, topk, threshold=0.):
-        """indexer.py:530-540.  Query groups of QUERY_GROUP_ROWS rows go through encode -> search one after the other while a worker
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None):
+        """allowed_ids (None: every document): collection ids, any order, duplicates allowed - only these documents are ranked; an unknown
+        id raises ValueError before anything is encoded.  run.json and q_stats.json keep their format.
+        indexer.py:530-540.  Query groups of QUERY_GROUP_ROWS rows go through encode -> search one after the other while a worker
         thread writes the previous group's piece of run.json (sr_write_run_json_part): formatting and the page-cache copy of a Dev-sized
         file take as long as the encode, and nothing in them needs the GPU.  A query's rows do not depend on the batch it is searched in
         (certified or exact: the same bits), and the file is the one-call file byte for byte (tests/test_boundary_gpu.py)."""
@@ -801,9 +826,10 @@ class SparseRetrieval:
         group_qids = [[x for batch in g for x in (batch["ids"] if isinstance(batch["ids"], list) else to_list(batch["ids"]))] for g in groups]
         qids = [x for g in group_qids for x in g]
         table = self.doc_id_table()
+        subset = None if allowed_ids is None else self.allowed_subset(allowed_ids)
         if len(groups) < 2 or not (id_table(qids).distinct and id_table(table).distinct):
             sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
-            res, stats = self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk)
+            res, stats = self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=subset)
             self._write_outputs(res, stats)
             return res
         os.makedirs(self.out_dir, exist_ok=True)
@@ -816,7 +842,7 @@ class SparseRetrieval:
                 q = QueryCSR(*sparse_reps_to_csr(reps, self.query_max_terms))
                 del reps
                 nnz += int(q.cols.numel())
-                scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold)
+                scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=subset)
                 piece = (to_host(scores), to_host(ids), to_host(counts))
                 pieces.append(piece)
                 writer.add(group_qids[gi], piece[0], piece[1], table, piece[2], last=gi + 1 == len(groups))
@@ -870,9 +896,12 @@ class ShardedSparseRetrieval(SparseRetrieval):
                 ids.update(pickle.load(f))
         return ids
 
-    def retrieve(self, q_loader, topk, threshold=0.):
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when
         `q_loader.replicated` is set."""
+        if allowed_ids is not None:
+            raise NotImplementedError("ShardedSparseRetrieval.retrieve: an allow-list (allowed_ids) is not supported on a doc-sharded "
+                                      "index; search one merged index with SparseRetrieval instead")
         from .distributed import all_gather_query_csr
         import torch.distributed as dist
         q, qids = self._generate_query_vecs(q_loader)
@@ -979,27 +1008,40 @@ class HybridRetriever(SparseRetrieval):
         assert len(sparse_query_vecs) == len(dense_query_vecs) == len(qids)
         return sparse_query_vecs, dense_query_vecs, qids
 
-    def _dense_retrieve(self, query_reps, qids, topk=1000):
+    def _dense_retrieve(self, query_reps, qids, topk=1000, _subset=None):
         """indexer.py:973-982, as a RunResult over the result arrays (label -1 rows = fewer than k vectors are skipped)."""
-        scores, positions = self.dense_index.search_arrays(query_reps, topk)
+        scores, positions = self.dense_index.search_arrays(query_reps, topk, _subset=_subset)
         return RunResult(qids, scores, positions, self.dense_index.run_table())
 
-    def _sparse_retrieve(self, sparse_query_vecs, qids, threshold=0., topk=1000):
-        return self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk)
+    def _sparse_retrieve(self, sparse_query_vecs, qids, threshold=0., topk=1000, _subset=None):
+        return self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=_subset)
 
-    def _retrieve_both(self, q_loader, topk, threshold):
+    def allowed_subsets(self, allowed_ids):
+        """(dense positions, sparse positions) of an allow-list of database ids, each sorted, unique and on the device.  The two indexes
+        number documents independently.  Every id must be in the dense index (ValueError naming it otherwise); one without a posting is
+        unknown to the inverted index and is simply not in its list (it shares no term with any query)."""
+        from .scoring import allowed_positions
+        dense = self.dense_index.allowed_subset(allowed_ids)
+        inv = self.inverse_id_map()
+        known = [d for d in allowed_ids if inv.pos.get(str(d)) is not None]
+        sparse = torch.from_numpy(allowed_positions(known, lambda d: inv.pos.get(str(d)))).to(self._dev)
+        return dense, sparse
+
+    def _retrieve_both(self, q_loader, topk, threshold, allowed_ids=None):
         """The two searches and their files (sparse/run.json + q_stats.json, dense/run.json): shared by retrieve and retrieve_fused."""
+        d_subset, s_subset = (None, None) if allowed_ids is None else self.allowed_subsets(allowed_ids)
         sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
-        sparse_res, sparse_stats = self._sparse_retrieve(sparse_query_vecs, qids, threshold=threshold, topk=topk)
-        dense_res = self._dense_retrieve(dense_query_vecs, qids, topk=topk)
+        sparse_res, sparse_stats = self._sparse_retrieve(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=s_subset)
+        dense_res = self._dense_retrieve(dense_query_vecs, qids, topk=topk, _subset=d_subset)
         with open(os.path.join(self.sparse_out_dir, "q_stats.json"), "w") as handler:
             json.dump(sparse_stats, handler)
         sparse_res.dump(os.path.join(self.sparse_out_dir, "run.json"))
         dense_res.dump(os.path.join(self.dense_out_dir, "run.json"))
         return sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res
 
-    def retrieve(self, q_loader, topk, id_dict=False, threshold=0.):
-        return self._retrieve_both(q_loader, topk, threshold)[3:]
+    def retrieve(self, q_loader, topk, id_dict=False, threshold=0., allowed_ids=None):
+        """allowed_ids (None: every document): database ids - both heads rank only these documents (allowed_subsets)."""
+        return self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids)[3:]
 
     def _position_maps(self):
         """The two indexes number documents independently: (dense position -> sparse position, -1 where the inverted index has no
@@ -1014,14 +1056,15 @@ class HybridRetriever(SparseRetrieval):
             self._s2d = torch.from_numpy(s2d).to(self._dev)
         return self._d2s, self._s2d
 
-    def retrieve_fused(self, q_loader, topk, weights=(1.0, 1.0), threshold=0.):
+    def retrieve_fused(self, q_loader, topk, weights=(1.0, 1.0), threshold=0., allowed_ids=None):
         """`retrieve` (the same two runs, the same bytes) plus {out_dir}/fused/run.json: per query the UNION of the two top-k lists,
         taken over database ids, is scored by BOTH heads with the pair kernels (a document only one search found gets its other
         score exactly, not a zero) and ranked by fused = float32(w_d * dense) + float32(w_s * sparse), top-k by (fused descending,
         sparse-index position ascending; a document without a posting has sparse score 0.0 and sorts after every indexed one).
-        Every document of the inverted index must be in the dense index.  Returns (sparse_res, dense_res, fused_res)."""
+        Every document of the inverted index must be in the dense index.  allowed_ids (None: every document): database ids - both
+        heads, and with them the union that is fused, are restricted to these documents.  Returns (sparse_res, dense_res, fused_res)."""
         from .rerank import fused_scores, ranked_run
-        sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res = self._retrieve_both(q_loader, topk, threshold)
+        sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res = self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids)
         dev, nq = self._dev, len(qids)
         d2s, s2d = self._position_maps()
         n_dense = int(d2s.numel())

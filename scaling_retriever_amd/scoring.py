@@ -42,6 +42,37 @@ def _candidates(cand_indptr, cand_ids, nq, device):
     return cand_indptr, cand_ids, total
 
 
+def _subset(subset, device):
+    """(int64 device tensor with a valid pointer, m) of an allow-list for the *_search_subset entry points; its order and content are
+    checked by the kernels."""
+    subset = _to_dev(subset, torch.int64, device)
+    if subset.dim() != 1:
+        raise ValueError(f"expected a 1-D subset, got {tuple(subset.shape)}")
+    m = subset.numel()
+    if m == 0:
+        subset = torch.zeros(1, dtype=torch.int64, device=device)        # keep a valid pointer
+    return subset, m
+
+
+def allowed_positions(allowed_ids, position_of, what="document id"):
+    """External document ids (any order, duplicates allowed) -> sorted unique positions, np.int64: the allow-list the subset searches take.
+    position_of maps an id to its position (a dict's .get, or any callable that returns None for an unknown id); an unknown id raises
+    ValueError naming it."""
+    out = set()
+    for d in allowed_ids:
+        p = position_of(d)
+        if p is None:
+            raise ValueError(f"allowed_ids: unknown {what} {d!r}")
+        out.add(int(p))
+    return np.fromiter(sorted(out), dtype=np.int64, count=len(out))
+
+
+def read_allowed_ids_file(path):
+    """One document id per line (surrounding white space and empty lines ignored) -> list of str, in file order."""
+    with open(path) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
 class DenseIndexHIP:
     """Flat inner-product index resident in HBM (segments of [n, dim] rows, all fp32 or all fp16).
 
@@ -255,8 +286,11 @@ class DenseIndexHIP:
         _lib.check(self.lib.sr_dense_index_filter_query_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
-    def search(self, queries, k):
-        """queries: fp32 cuda tensor [nq, dim] -> (scores fp32 [nq,k], ids int64 [nq,k]) cuda tensors."""
+    def search(self, queries, k, subset=None):
+        """queries: fp32 cuda tensor [nq, dim] -> (scores fp32 [nq,k], ids int64 [nq,k]) cuda tensors.  subset (None: the whole
+        index): strictly ascending int64 ids as this method returns them, one allow-list for all queries - the result is the full
+        ranking with every other document removed, cut to k (include/sr_hip.h sr_dense_search_subset); an id outside the index or
+        out of order: ValueError naming its position."""
         if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
         if not queries.is_cuda:
@@ -267,6 +301,12 @@ class DenseIndexHIP:
         ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
         if queries.device != self.device:
             raise ValueError(f"queries live on {queries.device}, the index on {self.device}")
+        if subset is not None:
+            subset, m = _subset(subset, self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_dense_search_subset(self._h, _ptr(queries), nq, int(k), _ptr(subset), m, _ptr(scores), _ptr(ids),
+                                                           _lib.stream_ptr()), "sr_dense_search_subset")
+            return scores, ids
         with torch.cuda.device(self.device):      # the library allocates its workspace on the current device
             _lib.check(self.lib.sr_dense_search(self._h, _ptr(queries), nq, int(k), _ptr(scores), _ptr(ids),
                                                 _lib.stream_ptr()), "sr_dense_search")
@@ -405,8 +445,10 @@ class SparseIndexHIP:
         keys = ("dense_columns_loaded", "dense_column_applications", "light_postings", "grouped_postings", "plan_entries", "workgroup_tiles")
         return {k_: int(v) for k_, v in zip(keys, out)}
 
-    def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, id_base=0, id_stride=1):
-        """Queries as CSR tensors. Returns (scores [nq,k], ids [nq,k], counts [nq]) cuda tensors."""
+    def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, id_base=0, id_stride=1, subset=None):
+        """Queries as CSR tensors. Returns (scores [nq,k], ids [nq,k], counts [nq]) cuda tensors.  subset (None: every document):
+        strictly ascending int64 document positions in [0, n_docs), one allow-list for all queries (include/sr_hip.h
+        sr_sparse_search_subset); a position outside the index or out of order: ValueError naming it."""
         def to_dev(x, dt):
             if isinstance(x, np.ndarray):
                 x = torch.from_numpy(np.ascontiguousarray(x))
@@ -421,6 +463,14 @@ class SparseIndexHIP:
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         counts = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        if subset is not None:
+            subset, m = _subset(subset, self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_sparse_search_subset(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, int(k),
+                                                            float(threshold), _ptr(subset), m, int(id_base), int(id_stride),
+                                                            _ptr(scores), _ptr(ids), _ptr(counts), _lib.stream_ptr()),
+                           "sr_sparse_search_subset")
+            return scores, ids, counts
         with torch.cuda.device(self.device):
             _lib.check(self.lib.sr_sparse_search(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, int(k),
                                                  float(threshold), int(id_base), int(id_stride), _ptr(scores), _ptr(ids),
