@@ -177,6 +177,44 @@ int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries, int64_t nq
 int sr_dense_search_subset(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
                            const int64_t* d_subset, int64_t m,
                            float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
+/* Two routes serve sr_dense_search_subset, with the same bits.  gather: the kernel described above.  mask: on an index in
+ * SR_PRECISION_FP32_FILTERED, under the conditions the unrestricted filtered search has (nq > 64, max(3k, k + 2048) <= sr_max_topk()
+ * candidates - k <= 1 365; the unrestricted search cuts a longer list to sr_max_topk() instead - with room for k + 64, dim % 64 == 0
+ * and >= 128, every segment filterable), the list is turned into a bitmap and the
+ * certified filter's upper-bound pass runs over ALL rows on the MFMA pipe with one bit test where a pair would become a key: a
+ * document whose bit is clear never becomes a key, so the thresholds and the certificate are quantities over the allowed set and the
+ * filter's argument holds for that set word for word.  Candidates are re-scored by the exact chain as in sr_dense_search; queries left
+ * without a certificate are re-done by the gather route over the list, those alone (more than half the batch: all of it) - its chains
+ * are the exact kernel's, so no masked exact kernel exists.  sr_dense_index_filter_stats / _filter_query_stats count such a search like
+ * any other.  Rule: the mask route where it applies and nq * m >= 6 980 * 130 000 (where the two met on one box); dev switch
+ * SR_SUBSET_DENSE_ROUTE=gather|mask forces one (read per call; `mask` where it does not apply is served by gather).  The mask route
+ * reads the call's status once BEFORE its pass instead of at the end; a bad list is then handled by the gather route as above.  The
+ * handle keeps the bitmap (id_end / 8 bytes), allocated on first use.  Not under a mask: the sparse head, doc-sharded search,
+ * per-query masks, the streaming / bf16x3 / bf16x6 passes, batches of <= 64 queries (gather).                                    */
+/* The largest document index of any segment, plus one (not ntotal: segments have id_base / id_stride); 0 for an empty index, -1 for a
+ * null one.  The length in bits of a document bitmap of this index.                                                              */
+int64_t sr_dense_index_id_end(const sr_dense_index* idx);
+/* Document bitmaps: bit (i & 31) of word i >> 5 stands for global doc index i (what faiss calls IDSelectorBitmap).
+ * sr_doc_mask_from_list: d_words uint32 [ceil(n_bits / 32)] := 0, then the bit of every entry of d_list int64 [m] set (any order,
+ * repeats allowed).  An entry outside [0, n_bits) sets nothing: SR_ERR_INVALID after the other entries were set.  Waits for the
+ * stream once to read that status.
+ * sr_doc_list_from_mask: the set bits below n_bits as an ascending list (popcount per word, scan, ordered expand) into d_list int64
+ * [capacity]; *d_count (device) = the number of set bits, written even when it exceeds capacity (the list then holds the first
+ * `capacity` of them).  Bits of the last word at or beyond n_bits are ignored.  Waits for the stream (its scan scratch is freed).    */
+int sr_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t* d_words, int64_t n_bits, sr_stream stream);
+int sr_doc_list_from_mask(const uint32_t* d_words, int64_t n_bits, int64_t* d_list, int64_t capacity,
+                          int64_t* d_count, sr_stream stream);
+/* sr_dense_search_subset with the allow-list given as a bitmap: d_mask_words uint32 [ceil(n_bits / 32)] on the device, n_bits ==
+ * sr_dense_index_id_end(idx) (anything else: SR_ERR_INVALID before any device work).  Returns EXACTLY what sr_dense_search_subset
+ * returns for the ascending list of the set bits - ids, score bits, tie order, padding, limits on k (with m = the number of set bits) -
+ * whichever route served the call.  The bitmap is expanded to that list on the device (8 m bytes on the handle, sized by one 8-byte
+ * read-back of the count), the list goes through the check of sr_dense_search_subset, then the same two routes and route rule.  A
+ * set bit that names no document (a gap of a strided segment): SR_ERR_INVALID, sr_last_error() names the first such bit; the
+ * status is read once, every output row is then padding (for any k) and the index stays usable.  The call waits for the stream twice
+ * before any scoring (the count, then the status), and on the mask route once more for the certificate's flags.                   */
+int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
+                           const uint32_t* d_mask_words, int64_t n_bits,
+                           float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
 int sr_dense_index_destroy(sr_dense_index* idx);
 /* Measurement hook: while enabled, every launch of the score kernel is bracketed by HIP
  * events on the search stream.  _read synchronises those events and returns the number

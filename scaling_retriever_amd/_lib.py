@@ -46,6 +46,10 @@ SIGNATURES = {
     "sr_dense_index_set_batch_invariant": (c_int, [c_void_p, c_int]),
     "sr_dense_score_pairs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_dense_search_subset": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_dense_index_id_end": (c_int64, [c_void_p]),
+    "sr_doc_mask_from_list": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "sr_doc_list_from_mask": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sr_dense_search_masked": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sr_dense_index_set_precision": (c_int, [c_void_p, c_int]),
     "sr_dense_search_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "sr_dense_search_finish": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -18,6 +18,7 @@
 #include "dense_filter.h"
 #include "pair_score.h"
 #include "subset_search.h"
+#include "doc_mask.h"
 #include <mutex>
 #include <stdlib.h>
 #include <vector>
@@ -437,6 +438,10 @@ struct sr_dense_index {
     // sr_dense_score_pairs (pair_score.hip): the segments as a device table (rebuilt when a segment was added), the call's status words
     PairSeg* pair_segs = nullptr; size_t pair_segs_n = 0;
     PairStatus* pair_status = nullptr;
+    // sr_dense_search_subset / _masked hold both forms of the filter (doc_mask.hip); allocated on first use, reused
+    uint32_t* mask_words = nullptr; int64_t mask_words_cap = 0;      // the bitmap of a list: id_end / 8 bytes
+    int64_t* mask_list = nullptr; int64_t mask_list_cap = 0;         // the list of a bitmap: 8 m bytes
+    int64_t* mask_blocks = nullptr; int64_t mask_blocks_cap = 0;     // per-workgroup counts of the bitmap -> list scan, + 1: the count
 };
 
 // bf16 planes of every segment a score mode needs (the certified filter keeps its own fp16 plane, filter_prepare_segment)
@@ -634,6 +639,9 @@ extern "C" int sr_dense_index_destroy(sr_dense_index* idx) {
     if (idx->flags) (void)hipFree(idx->flags);
     if (idx->pair_segs) (void)hipFree(idx->pair_segs);
     if (idx->pair_status) (void)hipFree(idx->pair_status);
+    if (idx->mask_words) (void)hipFree(idx->mask_words);
+    if (idx->mask_list) (void)hipFree(idx->mask_list);
+    if (idx->mask_blocks) (void)hipFree(idx->mask_blocks);
     delete idx;
     return SR_OK;
 }
@@ -659,8 +667,10 @@ extern "C" int sr_dense_index_set_precision(sr_dense_index* idx, int mode) {
 }
 
 // one pass in the given arithmetic (SR_PRECISION_FP32 | _BF16X3 | _BF16X6); caller holds idx->mu
+// d_mask (SR_PASS_FILTER only, nullable): the document bitmap of a masked search - only documents whose bit is set become keys
 static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, float* d_out_scores,
-                             int64_t* d_out_ids, int precision, hipStream_t s, bool force_tiled = false, int k_inner = 0) {
+                             int64_t* d_out_ids, int precision, hipStream_t s, bool force_tiled = false, int k_inner = 0,
+                             const uint32_t* d_mask = nullptr) {
     // k > SR_MAX_TOPK: the running set (2k keys per query) and the select's buffers count against the workspace limit next to
     // the candidate buffer (at least one 256-doc tile per query).  A call that does not fit runs in query sub-batches of more
     // than 64 queries each, so that every query stays in the kernel family (and k order) of the unsplit call: the bits do not
@@ -680,7 +690,7 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
             for (int64_t b = 0, q0 = 0; b < nb; ++b) {            // balanced: every batch holds floor(nq / nb) or one more queries
                 const int64_t nqb = nq / nb + (b < nq % nb ? 1 : 0);
                 SR_TRY(dense_search_pass(idx, d_queries + q0 * idx->dim, nqb, k, d_out_scores + q0 * k, d_out_ids + q0 * k, precision,
-                                         s, force_tiled, k_inner));
+                                         s, force_tiled, k_inner, d_mask));
                 q0 += nqb;
             }
             return SR_OK;
@@ -768,6 +778,7 @@ static int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_
                     a.upper_bound = 1;
                     a.dxy = seg.fxy; a.qa = idx->qa; a.sd = seg.fsd; a.isd = seg.fisd;
                     a.dxy_gmax = seg.fxy + 2 * seg.n;
+                    a.mask = d_mask;
                 } else if (np == 2) {     // (d plane, q plane), smallest products first
                     a.n_pairs = 3;
                     const int pd[3] = {1, 0, 0}, pq[3] = {0, 1, 0};
@@ -897,17 +908,34 @@ static int filter_segs_of(sr_dense_index* idx, FilterSegs& fs) {
 
 // First half: the kp documents with the largest upper bounds U per query (idx->a_scores / a_ids / qa).  *done = false: the
 // filter does not apply to this index / batch.
-static int dense_filtered_candidates(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, hipStream_t s, bool* done) {
-    *done = false;
+// Whether the certified filter can serve this index and batch, and with how many candidates per query (*kp).  The mask route of the
+// subset searches applies under these conditions with full_kp: there max(3k, k + 2048) candidates must fit SR_MAX_TOPK as they are
+// (k <= 1 365), where the unrestricted search goes on with a list cut to SR_MAX_TOPK - a k beyond that is served by the gather route.
+static int dense_filter_applies(sr_dense_index* idx, int64_t nq, int k, int* kp_out, bool* applies, bool full_kp = false) {
+    *applies = false;
     if (k > SR_MAX_TOPK) return SR_OK;                         // no room for k + 64 candidates in the in-LDS top-k
     int kp = 3 * k > k + 2048 ? 3 * k : k + 2048;            // candidates per query: k = 1000 -> 3072
     if (const char* e = sr_dev_getenv("SR_FILTER_KP")) kp = atoi(e);
+    if (full_kp && kp > SR_MAX_TOPK) return SR_OK;
     if (kp > SR_MAX_TOPK) kp = SR_MAX_TOPK;
     if (nq <= 64 || kp < k + 64 || idx->dim % 64 != 0 || idx->dim < 128 || (int)idx->segs.size() > SR_FILTER_MAX_SEGS) return SR_OK;
     for (DenseSegment& seg : idx->segs) {
         if (seg.f_state == 0) SR_TRY(filter_prepare_segment(idx, seg));
         if (seg.f_state != 1) return SR_OK;                   // not filterable / no room for the plane: exact kernel
     }
+    *kp_out = kp;
+    *applies = true;
+    return SR_OK;
+}
+
+// d_mask (nullable): a document bitmap over [0, id_end) - the candidates are then the kp largest upper bounds among the allowed documents
+static int dense_filtered_candidates(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, hipStream_t s, bool* done,
+                                     const uint32_t* d_mask = nullptr) {
+    *done = false;
+    int kp = 0;
+    bool applies = false;
+    SR_TRY(dense_filter_applies(idx, nq, k, &kp, &applies));
+    if (!applies) return SR_OK;
     if (idx->fq_cap < nq || idx->fkp != kp) {
         auto F = [](void* p) { if (p) (void)hipFree(p); };
         F(idx->qa); F(idx->a_scores); F(idx->a_ids); F(idx->flags);
@@ -923,15 +951,19 @@ static int dense_filtered_candidates(sr_dense_index* idx, const float* d_queries
     }
     SR_CHECK_HIP(hipMemsetAsync(idx->flags, 0, (size_t)nq * 4, s));
     // 1. the kp documents with the largest upper bounds U (the query planes and constants are made by the pass)
-    SR_TRY(dense_search_pass(idx, d_queries, nq, kp, idx->a_scores, idx->a_ids, SR_PASS_FILTER, s, false, k));
+    SR_TRY(dense_search_pass(idx, d_queries, nq, kp, idx->a_scores, idx->a_ids, SR_PASS_FILTER, s, false, k, d_mask));
     *done = true;
     return SR_OK;
 }
 
 // Second half: exact re-score of the candidates that can still be in the top-k, certificate, exact re-do of the queries without
 // one.  d_thr (nullable, doc-sharded search): per query a value proven not to exceed the GLOBAL k-th exact score.
+static int dense_subset_gather(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const int64_t* d_subset, int64_t m,
+                               float* d_out_scores, int64_t* d_out_ids, hipStream_t s, const char* who);
+// d_list / m (masked search; d_list null otherwise): the allowed documents as an ascending list - queries without a certificate are then
+// re-done by the gather kernel over that list, whose chains are the exact kernel's (subset_search.hip): the same bits, no masked exact kernel.
 static int dense_filtered_finish(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const float* d_thr, float* d_out_scores,
-                                 int64_t* d_out_ids, hipStream_t s) {
+                                 int64_t* d_out_ids, hipStream_t s, const int64_t* d_list = nullptr, int64_t m = 0) {
     const int kp = idx->fkp;
     FilterSegs fs;
     SR_TRY(filter_segs_of(idx, fs));
@@ -957,6 +989,7 @@ static int dense_filtered_finish(sr_dense_index* idx, const float* d_queries, in
     if (nf == 0) { ++idx->n_filtered; return SR_OK; }
     ++idx->n_fallback;
     if (nf * 2 > nq) {                                         // most of the batch: redo all of it in place
+        if (d_list) return dense_subset_gather(idx, d_queries, nq, k, d_list, m, d_out_scores, d_out_ids, s, "dense search (masked)");
         return dense_search_pass(idx, d_queries, nq, k, d_out_scores, d_out_ids, SR_PRECISION_FP32, s);
     }
     if (idx->redo_cap < nf || idx->redo_k != k) {
@@ -975,7 +1008,8 @@ static int dense_filtered_finish(sr_dense_index* idx, const float* d_queries, in
     SR_CHECK_HIP(hipMemcpyAsync(idx->redo_idx, redo.data(), (size_t)nf * 8, hipMemcpyHostToDevice, s));
     SR_TRY(launch_filter_gather_rows(d_queries, idx->redo_idx, nf, idx->dim, idx->redo_q, false, s));
     // the tiled kernels whatever the count: one k order for the whole batch (the streaming kernel accumulates in another)
-    SR_TRY(dense_search_pass(idx, idx->redo_q, nf, k, idx->redo_scores, idx->redo_ids, SR_PRECISION_FP32, s, true));
+    if (d_list) SR_TRY(dense_subset_gather(idx, idx->redo_q, nf, k, d_list, m, idx->redo_scores, idx->redo_ids, s, "dense search (masked)"));
+    else SR_TRY(dense_search_pass(idx, idx->redo_q, nf, k, idx->redo_scores, idx->redo_ids, SR_PRECISION_FP32, s, true));
     SR_TRY(launch_filter_gather_rows(idx->redo_scores, idx->redo_idx, nf, k, d_out_scores, true, s));
     SR_TRY(launch_filter_gather_rows(idx->redo_ids, idx->redo_idx, nf, 2 * (int64_t)k, d_out_ids, true, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));                    // `redo` (pageable host memory) is the source of an async copy
@@ -1107,27 +1141,12 @@ extern "C" int sr_dense_score_pairs(sr_dense_index* idx, const float* d_queries,
     return pair_status_end(idx->pair_status, d_cand_ids, "sr_dense_score_pairs", s);
 }
 
-// Top-k within a subset of the documents (subset_search.hip): scores are the pair scorer's chains, the select is the searches' own
-extern "C" int sr_dense_search_subset(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const int64_t* d_subset, int64_t m,
-                                      float* d_out_scores, int64_t* d_out_ids, sr_stream stream) {
-    SR_REQUIRE(idx, "sr_dense_search_subset: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search_subset: bad nq=%lld", (long long)nq);
-    SR_REQUIRE(m >= 0 && m <= idx->ntotal, "sr_dense_search_subset: a strictly ascending subset of %lld documents holds at most that many, not m=%lld",
-               (long long)idx->ntotal, (long long)m);
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_dense_search_subset: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
-    SR_REQUIRE(k <= SR_MAX_TOPK || (int64_t)k - SR_MAX_TOPK <= m, "sr_dense_search_subset: k=%d exceeds %d by more than the subset's %lld documents", k,
-               SR_MAX_TOPK, (long long)m);
-    if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_dense_search_subset: null pointer");
-    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_subset: queries must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(idx->mu);
-    StreamOrder::Scope in_order(idx->order, s);
+// The gather route of a subset search (subset_search.hip): scores are the pair scorer's chains, the select is the searches' own.  The
+// caller has run the check kernel on the list (idx->pair_status) and set up idx->pair_segs; nothing is scored once the check found an offender.
+static int dense_subset_gather(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const int64_t* d_subset, int64_t m,
+                               float* d_out_scores, int64_t* d_out_ids, hipStream_t s, const char* who) {
     int64_t nq_batch = 0, slab = 0;
-    SR_TRY(subset_plan(idx->ws_limit, nq, k, m, 64, &nq_batch, &slab, "sr_dense_search_subset"));
-    if (m > 0) SR_TRY(dense_pair_segs(idx, "sr_dense_search_subset"));
-    SR_TRY(subset_status_begin(&idx->pair_status, s));
-    SR_TRY(launch_subset_check_dense(idx->pair_segs, (int)idx->pair_segs_n, d_subset, m, idx->pair_status, s));
+    SR_TRY(subset_plan(idx->ws_limit, nq, k, m, 64, &nq_batch, &slab, who));
     for (int64_t qb = 0; qb < nq; qb += nq_batch) {
         const int64_t nqb = nq - qb < nq_batch ? nq - qb : nq_batch;
         SR_TRY(idx->ws.ensure(nqb, k, slab));
@@ -1150,7 +1169,170 @@ extern "C" int sr_dense_search_subset(sr_dense_index* idx, const float* d_querie
         }
         SR_TRY(topk_finalize(idx->ws, nqb, k, -3.402823466e38f, d_out_scores + qb * k, d_out_ids + qb * k, nullptr, s));
     }
+    return SR_OK;
+}
+
+// the largest document index of any segment, plus one: the length of a document bitmap
+static int64_t dense_id_end(const sr_dense_index* idx) {
+    int64_t end = 0;
+    for (const DenseSegment& seg : idx->segs)
+        if (seg.n > 0 && seg.id_base + (seg.n - 1) * seg.id_stride + 1 > end) end = seg.id_base + (seg.n - 1) * seg.id_stride + 1;
+    return end;
+}
+extern "C" int64_t sr_dense_index_id_end(const sr_dense_index* idx) { return idx ? dense_id_end(idx) : -1; }
+
+// Route rule of the subset searches.  gather: one fmaf chain per (query, allowed row) on the vector ALU, cost ~ nq x m (2.0 ms per
+// 1 000 rows at 6 980 queries).  mask: the certified filter's pass over ALL rows on the MFMA pipe with the bitmap in its epilogue, cost
+// ~ nq x ntotal whatever m is (229 - 262 ms at 6 980 queries x 8.84 M rows).  auto takes the mask route where it applies and nq x m
+// reaches SR_SUBSET_DENSE_CROSSOVER: measured with both routes forced at 6 980 queries (tools/bench_subset.py --legs dense_routes,
+// profiles/subset_search.json) the two meet near m = 130 000 (gather 203 ms at 100 000 and 1 988 ms at 1 000 000, mask
+// 262 and 245 ms) - one box, one collection size, an estimate.  The constant holds only near that point (nq = 6 980, ntotal = 8.84 M):
+// by the cost model above the routes really meet at a FRACTION m / ntotal (about 1.5 % here) that does not depend on nq, so a batch
+// ten times larger takes the mask route at a tenth of the m, where gather would still be the cheaper, and a collection ten times
+// smaller keeps gather up to ten times the fraction.  The product form is the rule as specified; a rule in m / id_end is the next
+// step once a second collection size has been measured.  Dev switch SR_SUBSET_DENSE_ROUTE=gather|mask forces one, read per call;
+// `mask` where the filter does not apply is served by gather.
+#define SR_SUBSET_DENSE_CROSSOVER (6980ll * 130000ll)
+static bool subset_dense_wants_mask(int64_t nq, int64_t m) {
+    if (const char* route = sr_dev_getenv("SR_SUBSET_DENSE_ROUTE")) {
+        if (strcmp(route, "mask") == 0) return true;
+        if (strcmp(route, "gather") == 0) return false;
+    }
+    return nq * m >= SR_SUBSET_DENSE_CROSSOVER;
+}
+
+template <typename T>
+static int dense_mask_scratch(T** p, int64_t* cap, int64_t want, const char* who) {
+    if (*cap >= want) return SR_OK;
+    if (*p) (void)hipFree(*p);                            // waits for the calls that read it
+    *p = nullptr; *cap = 0;
+    if (hipMalloc((void**)p, (size_t)want * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        sr_set_error("%s: out of device memory for %lld bytes of filter scratch", who, (long long)(want * (int64_t)sizeof(T)));
+        return SR_ERR_NOMEM;
+    }
+    *cap = want;
+    return SR_OK;
+}
+
+// The mask route: both forms of the filter are at hand and d_list has passed the check kernel.  Caller holds idx->mu.
+static int dense_search_restricted(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const int64_t* d_list, int64_t m,
+                                   const uint32_t* d_words, float* d_out_scores, int64_t* d_out_ids, hipStream_t s, const char* who) {
+    bool done = false;
+    SR_TRY(dense_filtered_candidates(idx, d_queries, nq, k, s, &done, d_words));
+    if (!done) return dense_subset_gather(idx, d_queries, nq, k, d_list, m, d_out_scores, d_out_ids, s, who);     // e.g. no room for the candidate lists
+    return dense_filtered_finish(idx, d_queries, nq, k, nullptr, d_out_scores, d_out_ids, s, d_list, m);
+}
+
+// Top-k within a subset of the documents: the gather route (subset_search.hip), or - for large nq x m on an index the certified filter
+// serves - the filter's pass under the list's bitmap (the mask route).  The same bits either way.
+extern "C" int sr_dense_search_subset(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const int64_t* d_subset, int64_t m,
+                                      float* d_out_scores, int64_t* d_out_ids, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_search_subset: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search_subset: bad nq=%lld", (long long)nq);
+    SR_REQUIRE(m >= 0 && m <= idx->ntotal, "sr_dense_search_subset: a strictly ascending subset of %lld documents holds at most that many, not m=%lld",
+               (long long)idx->ntotal, (long long)m);
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_dense_search_subset: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_REQUIRE(k <= SR_MAX_TOPK || (int64_t)k - SR_MAX_TOPK <= m, "sr_dense_search_subset: k=%d exceeds %d by more than the subset's %lld documents", k,
+               SR_MAX_TOPK, (long long)m);
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_dense_search_subset: null pointer");
+    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_subset: queries must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder::Scope in_order(idx->order, s);
+    int64_t nq_batch = 0, slab = 0;
+    SR_TRY(subset_plan(idx->ws_limit, nq, k, m, 64, &nq_batch, &slab, "sr_dense_search_subset"));       // a call that cannot run fails before any launch
+    if (m > 0) SR_TRY(dense_pair_segs(idx, "sr_dense_search_subset"));
+    SR_TRY(subset_status_begin(&idx->pair_status, s));
+    SR_TRY(launch_subset_check_dense(idx->pair_segs, (int)idx->pair_segs_n, d_subset, m, idx->pair_status, s));
+    int kp = 0;
+    bool mask_route = idx->precision == SR_PRECISION_FP32_FILTERED && subset_dense_wants_mask(nq, m);
+    if (mask_route) SR_TRY(dense_filter_applies(idx, nq, k, &kp, &mask_route, true));
+    if (mask_route) {
+        // the list gets its bitmap once the check kernel has accepted it: the mask route reads the call's status here, not at the end (a
+        // bad list goes on to the gather route, which writes the padding rows and reports it)
+        const int64_t n_bits = dense_id_end(idx);
+        mask_route = subset_status_end(idx->pair_status, d_subset, "sr_dense_search_subset", "doc index", s) == SR_OK;
+        if (mask_route) {
+            SR_TRY(dense_mask_scratch(&idx->mask_words, &idx->mask_words_cap, doc_mask_words(n_bits) > 0 ? doc_mask_words(n_bits) : 1, "sr_dense_search_subset"));
+            SR_TRY(launch_doc_mask_from_list(d_subset, m, idx->mask_words, n_bits, idx->pair_status, nullptr, s));
+            return dense_search_restricted(idx, d_queries, nq, k, d_subset, m, idx->mask_words, d_out_scores, d_out_ids, s, "sr_dense_search_subset");
+        }
+    }
+    SR_TRY(dense_subset_gather(idx, d_queries, nq, k, d_subset, m, d_out_scores, d_out_ids, s, "sr_dense_search_subset"));
     return subset_status_end(idx->pair_status, d_subset, "sr_dense_search_subset", "doc index", s);
+}
+
+// every output entry := (-FLT_MAX, -1): what the selects write for a query without a candidate
+__global__ void dense_pad_rows_kernel(float* __restrict__ scores, int64_t* __restrict__ ids, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        scores[i] = -3.402823466e38f;
+        ids[i] = -1;
+    }
+}
+
+// The same search with the filter given as a bitmap.  The bitmap is expanded to the ascending list of its set bits, which goes through
+// the check kernel of sr_dense_search_subset (a set bit that names no document is found there); then the same two routes.
+extern "C" int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const uint32_t* d_mask_words,
+                                      int64_t n_bits, float* d_out_scores, int64_t* d_out_ids, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_search_masked: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search_masked: bad nq=%lld", (long long)nq);
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_dense_search_masked: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    const int64_t id_end = dense_id_end(idx);
+    SR_REQUIRE(n_bits == id_end, "sr_dense_search_masked: the mask holds n_bits=%lld bits, the index's document indices end at %lld", (long long)n_bits,
+               (long long)id_end);
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && (d_mask_words || n_bits == 0), "sr_dense_search_masked: null pointer");
+    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_masked: queries must be 16-byte aligned");
+    StreamOrder::Scope in_order(idx->order, s);
+    // the list of the set bits: count (one 8-byte read-back: it sizes the list and the slabs), then expand
+    const int64_t n_blocks = doc_mask_blocks(n_bits);
+    SR_TRY(dense_mask_scratch(&idx->mask_blocks, &idx->mask_blocks_cap, n_blocks + 1, "sr_dense_search_masked"));
+    int64_t* d_count = idx->mask_blocks + n_blocks;
+    SR_TRY(launch_doc_mask_count(d_mask_words, n_bits, idx->mask_blocks, d_count, s));
+    int64_t m = 0;
+    SR_CHECK_HIP(hipMemcpyAsync(&m, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    SR_TRY(dense_mask_scratch(&idx->mask_list, &idx->mask_list_cap, m > 0 ? m : 1, "sr_dense_search_masked"));
+    SR_TRY(launch_doc_mask_expand(d_mask_words, n_bits, idx->mask_blocks, idx->mask_list, m, s));
+    if (m > 0) SR_TRY(dense_pair_segs(idx, "sr_dense_search_masked"));
+    SR_TRY(subset_status_begin(&idx->pair_status, s));
+    SR_TRY(launch_subset_check_dense(idx->pair_segs, (int)idx->pair_segs_n, idx->mask_list, m, idx->pair_status, s));
+    // The list is ascending by construction: an offender is a bit in a gap of a strided segment or past a short segment's end.  The
+    // call's one read of the status: the mask route needs it before its pass, and the limit on k needs a list that stands.
+    PairStatus h;
+    SR_CHECK_HIP(hipMemcpyAsync(&h, idx->pair_status, sizeof(h), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    const bool bad = h.first_bad != ~0ull;
+    const bool k_fits = k <= SR_MAX_TOPK || (int64_t)k - SR_MAX_TOPK <= m;
+    if (!bad) {
+        SR_REQUIRE(k_fits, "sr_dense_search_masked: k=%d exceeds %d by more than the mask's %lld documents", k, SR_MAX_TOPK, (long long)m);
+        int kp = 0;
+        bool mask_route = idx->precision == SR_PRECISION_FP32_FILTERED && subset_dense_wants_mask(nq, m);
+        if (mask_route) SR_TRY(dense_filter_applies(idx, nq, k, &kp, &mask_route, true));
+        if (mask_route)
+            return dense_search_restricted(idx, d_queries, nq, k, idx->mask_list, m, d_mask_words, d_out_scores, d_out_ids, s, "sr_dense_search_masked");
+    }
+    // the gather route; after an offender it scores nothing and every output row is padding
+    if (k_fits) SR_TRY(dense_subset_gather(idx, d_queries, nq, k, idx->mask_list, m, d_out_scores, d_out_ids, s, "sr_dense_search_masked"));
+    if (bad) {
+        if (!k_fits) {                                    // a k no valid mask of this count could have: the rows are padded here
+            const int64_t n = nq * (int64_t)k;
+            const int64_t blocks = ceil_div64(n, 256) < 65536 ? ceil_div64(n, 256) : 65536;
+            hipLaunchKernelGGL(dense_pad_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_out_scores, d_out_ids, n);
+            SR_CHECK_LAUNCH();
+            SR_CHECK_HIP(hipStreamSynchronize(s));
+        }
+        int64_t bit = -1;
+        SR_CHECK_HIP(hipMemcpy(&bit, idx->mask_list + h.first_bad, sizeof(int64_t), hipMemcpyDeviceToHost));
+        sr_set_error("sr_dense_search_masked: mask bit %lld is set but names no document of the index (nothing was searched)", (long long)bit);
+        return SR_ERR_INVALID;
+    }
+    return SR_OK;
 }
 
 extern "C" int sr_dense_index_filter_stats(sr_dense_index* idx, int64_t* n_filtered, int64_t* n_fallback) {

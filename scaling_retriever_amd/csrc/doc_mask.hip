@@ -1,0 +1,161 @@
+// Document bitmaps (gfx950): list -> bitmap by an atomic-or scatter, bitmap -> ascending list by popcount per word, a scan and an
+// ordered expand.  The reference has no counterpart (DenseFlatIndexer.search_knn, scaling_retriever/indexer.py:191-217, always ranks
+// the whole index); the bitmap is the form faiss offers as IDSelectorBitmap.  sr_dense_search_masked / _subset (dense_score.hip) hold
+// both forms of a filter: the bitmap feeds the certified filter's masked pass (dense_split_kernel.h), the list the gather kernel.
+#include "doc_mask.h"
+
+#define DM_THREADS 256
+
+__global__ __launch_bounds__(DM_THREADS) void doc_mask_scatter_kernel(const int64_t* __restrict__ list, int64_t m, uint32_t* __restrict__ words,
+                                                                       int64_t n_bits, const PairStatus* __restrict__ st, int* __restrict__ bad) {
+    const int64_t j = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    if (j >= m) return;
+    if (st && st->first_bad != ~0ull) return;             // the check ran before this launch on the same stream
+    const int64_t id = list[j];
+    if (id < 0 || id >= n_bits) {                         // never a write outside the words
+        if (bad) atomicOr(bad, 1);
+        return;
+    }
+    atomicOr(&words[id >> 5], 1u << (unsigned)(id & 31));
+}
+
+int launch_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t* d_words, int64_t n_bits, const PairStatus* st, int* d_bad,
+                              hipStream_t s) {
+    if (n_bits > 0) SR_CHECK_HIP(hipMemsetAsync(d_words, 0, (size_t)doc_mask_words(n_bits) * 4, s));
+    if (m == 0) return SR_OK;
+    hipLaunchKernelGGL(doc_mask_scatter_kernel, dim3((unsigned)ceil_div64(m, DM_THREADS)), dim3(DM_THREADS), 0, s, d_list, m, d_words, n_bits,
+                       st, d_bad);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+// word w of the bitmap with the bits at or beyond n_bits cleared; 0 beyond the last word
+__device__ __forceinline__ uint32_t doc_mask_word(const uint32_t* __restrict__ words, int64_t w, int64_t n_words, int64_t n_bits) {
+    if (w >= n_words) return 0u;
+    uint32_t v = words[w];
+    const unsigned tail = (unsigned)(n_bits & 31);
+    if (w == n_words - 1 && tail != 0) v &= (1u << tail) - 1u;
+    return v;
+}
+
+// inclusive scan of one int per thread over the workgroup's DM_THREADS threads; *total = the sum (the same in every thread)
+__device__ __forceinline__ int doc_mask_block_scan(int v, int* wave_tot, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    __syncthreads();                                      // wave_tot of a previous call is consumed
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int base = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < DM_THREADS / 64; ++w) {
+        if (w < wave) base += wave_tot[w];
+        sum += wave_tot[w];
+    }
+    *total = sum;
+    return incl + base;
+}
+
+__global__ __launch_bounds__(DM_THREADS) void doc_mask_count_kernel(const uint32_t* __restrict__ words, int64_t n_words, int64_t n_bits,
+                                                                     int64_t* __restrict__ blocks) {
+    __shared__ int wave_tot[DM_THREADS / 64];
+    const int64_t w = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    int total;
+    (void)doc_mask_block_scan(__popc(doc_mask_word(words, w, n_words, n_bits)), wave_tot, &total);
+    if (threadIdx.x == 0) blocks[blockIdx.x] = total;
+}
+
+// one workgroup: blocks[b] := sum of blocks[0 .. b), *count = the sum of all
+__global__ __launch_bounds__(DM_THREADS) void doc_mask_scan_kernel(int64_t* __restrict__ blocks, int64_t n_blocks, int64_t* __restrict__ count) {
+    __shared__ int wave_tot[DM_THREADS / 64];
+    int64_t carry = 0;
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += DM_THREADS) {
+        const int64_t b = b0 + threadIdx.x;
+        const int v = b < n_blocks ? (int)blocks[b] : 0;      // <= 8 192 each, <= 2^21 per round
+        int total;
+        const int incl = doc_mask_block_scan(v, wave_tot, &total);
+        if (b < n_blocks) blocks[b] = carry + (incl - v);
+        carry += total;
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+
+__global__ __launch_bounds__(DM_THREADS) void doc_mask_expand_kernel(const uint32_t* __restrict__ words, int64_t n_words, int64_t n_bits,
+                                                                      const int64_t* __restrict__ blocks, int64_t* __restrict__ list,
+                                                                      int64_t capacity) {
+    __shared__ int wave_tot[DM_THREADS / 64];
+    const int64_t w = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    uint32_t v = doc_mask_word(words, w, n_words, n_bits);
+    const int c = __popc(v);
+    int total;
+    const int incl = doc_mask_block_scan(c, wave_tot, &total);
+    int64_t pos = blocks[blockIdx.x] + (incl - c);
+    while (v) {
+        const int b = __ffs((int)v) - 1;
+        if (pos < capacity) list[pos] = w * 32 + b;
+        ++pos;
+        v &= v - 1u;
+    }
+}
+
+int launch_doc_mask_count(const uint32_t* d_words, int64_t n_bits, int64_t* d_blocks, int64_t* d_count, hipStream_t s) {
+    if (n_bits == 0) {
+        SR_CHECK_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+        return SR_OK;
+    }
+    const int64_t n_blocks = doc_mask_blocks(n_bits);
+    SR_REQUIRE(n_blocks < (1ll << 31), "doc mask: %lld bits are too many for one launch", (long long)n_bits);
+    hipLaunchKernelGGL(doc_mask_count_kernel, dim3((unsigned)n_blocks), dim3(DM_THREADS), 0, s, d_words, doc_mask_words(n_bits), n_bits, d_blocks);
+    SR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(doc_mask_scan_kernel, dim3(1), dim3(DM_THREADS), 0, s, d_blocks, n_blocks, d_count);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+int launch_doc_mask_expand(const uint32_t* d_words, int64_t n_bits, const int64_t* d_blocks, int64_t* d_list, int64_t capacity, hipStream_t s) {
+    if (n_bits == 0 || capacity == 0) return SR_OK;
+    hipLaunchKernelGGL(doc_mask_expand_kernel, dim3((unsigned)doc_mask_blocks(n_bits)), dim3(DM_THREADS), 0, s, d_words, doc_mask_words(n_bits),
+                       n_bits, d_blocks, d_list, capacity);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+extern "C" int sr_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t* d_words, int64_t n_bits, sr_stream stream) {
+    SR_REQUIRE(m >= 0 && n_bits >= 0 && n_bits <= (1ll << 32), "sr_doc_mask_from_list: bad sizes m=%lld n_bits=%lld", (long long)m, (long long)n_bits);
+    SR_REQUIRE((d_list || m == 0) && (d_words || n_bits == 0), "sr_doc_mask_from_list: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    int* d_bad = nullptr;
+    SR_CHECK_HIP(hipMalloc((void**)&d_bad, sizeof(int)));
+    int h_bad = 0;
+    int rc = hipMemsetAsync(d_bad, 0, sizeof(int), s) == hipSuccess ? SR_OK : SR_ERR_HIP;
+    if (rc == SR_OK) rc = launch_doc_mask_from_list(d_list, m, d_words, n_bits, nullptr, d_bad, s);
+    if (rc == SR_OK && (hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
+        sr_set_error("sr_doc_mask_from_list: reading the status back failed");
+        rc = SR_ERR_HIP;
+    }
+    (void)hipFree(d_bad);
+    SR_TRY(rc);
+    SR_REQUIRE(h_bad == 0, "sr_doc_mask_from_list: the list holds an entry outside [0, %lld) (the other entries were set)", (long long)n_bits);
+    return SR_OK;
+}
+
+extern "C" int sr_doc_list_from_mask(const uint32_t* d_words, int64_t n_bits, int64_t* d_list, int64_t capacity, int64_t* d_count,
+                                     sr_stream stream) {
+    SR_REQUIRE(n_bits >= 0 && n_bits <= (1ll << 32) && capacity >= 0, "sr_doc_list_from_mask: bad sizes n_bits=%lld capacity=%lld",
+               (long long)n_bits, (long long)capacity);
+    SR_REQUIRE((d_words || n_bits == 0) && (d_list || capacity == 0) && d_count, "sr_doc_list_from_mask: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    int64_t* d_blocks = nullptr;
+    if (n_bits > 0) SR_CHECK_HIP(hipMalloc((void**)&d_blocks, (size_t)doc_mask_blocks(n_bits) * sizeof(int64_t)));
+    int rc = launch_doc_mask_count(d_words, n_bits, d_blocks, d_count, s);
+    if (rc == SR_OK) rc = launch_doc_mask_expand(d_words, n_bits, d_blocks, d_list, capacity, s);
+    if (d_blocks) {
+        if (rc == SR_OK && hipStreamSynchronize(s) != hipSuccess) { sr_set_error("sr_doc_list_from_mask: the stream failed"); rc = SR_ERR_HIP; }
+        (void)hipFree(d_blocks);                          // the per-workgroup counts: scratch of this call
+    }
+    return rc;
+}

@@ -269,11 +269,11 @@ class ShardedDenseRetriever:
         """rows: fp32 cuda tensor [n_local, H] = the embeddings of dataset rows rank, rank+W, ..."""
         self.index.add_device_rows(rows, id_base=self.rank, id_stride=self.world_size)
 
-    def search(self, queries, k, dst=0, subset=None):
-        """queries replicated on every rank.  Returns (scores, global ids) on rank dst, (None, None) elsewhere.  subset: not supported on
-        a doc-sharded index."""
-        if subset is not None:
-            raise NotImplementedError("ShardedDenseRetriever.search: an allow-list (subset) is not supported on a doc-sharded index")
+    def search(self, queries, k, dst=0, subset=None, mask=None):
+        """queries replicated on every rank.  Returns (scores, global ids) on rank dst, (None, None) elsewhere.  subset / mask: not
+        supported on a doc-sharded index."""
+        if subset is not None or mask is not None:
+            raise NotImplementedError("ShardedDenseRetriever.search: an allow-list (subset / mask) is not supported on a doc-sharded index")
         from .scoring import topk_merge
         s, i = sharded_dense_search(self.index, queries, k, self.world_size)
         gs, gi = gather_topk(s, i, dst=dst)

@@ -278,9 +278,19 @@ class DenseFlatIndexer(DenseIndexer):
         inv = self.inverse_id_map()
         return torch.from_numpy(allowed_positions(allowed_ids, lambda d: inv.pos.get(str(d)))).to(self.index.device)
 
-    def search_knn(self, query_reps, top_docs: int, allowed_ids=None):
+    def allowed_mask_words(self, allowed_mask):
+        """A boolean array / tensor over index positions (length = the number of indexed vectors) -> the packed bitmap on the index's
+        device, uploaded and packed once per call (scoring.pack_doc_mask)."""
+        from .scoring import pack_doc_mask
+        flags = allowed_mask if isinstance(allowed_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allowed_mask, dtype=bool))
+        if flags.dim() != 1 or flags.numel() != self.index.id_end:
+            raise ValueError(f"allowed_mask must hold one flag per index position ({self.index.id_end}), got {tuple(flags.shape)}")
+        return pack_doc_mask(flags.to(device=self.index.device, dtype=torch.bool))
+
+    def search_knn(self, query_reps, top_docs: int, allowed_ids=None, allowed_mask=None):
         """indexer.py:210-214: (list of db-id lists, fp32 scores [nq, k]); label -1 (fewer than k vectors) -> None.  allowed_ids (None:
         the whole index): database ids, any order, duplicates allowed - only these documents are ranked (DenseIndexHIP.search, subset).
+        allowed_mask: the same filter as a boolean array over index positions (DenseIndexHIP.search, mask); not both.
         The lists come
         from id_lists (csrc/host_lists.c).  A large query set is searched in KNN_CHUNKS pieces, the GPU working on piece c + 1 (in a
         worker thread: the C call releases the GIL) while this thread builds the lists of piece c - the exact results do not depend
@@ -290,10 +300,13 @@ class DenseFlatIndexer(DenseIndexer):
         else:
             q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
         nq = q.shape[0]
+        if allowed_ids is not None and allowed_mask is not None:
+            raise ValueError("search_knn: pass allowed_ids or allowed_mask, not both")
         subset = None if allowed_ids is None else self.allowed_subset(allowed_ids)
+        mask = None if allowed_mask is None else self.allowed_mask_words(allowed_mask)
         n_chunks = self.KNN_CHUNKS if nq >= 1024 else 1
         if n_chunks == 1:
-            scores, indexes = self.search_arrays(q, top_docs, _subset=subset)
+            scores, indexes = self.search_arrays(q, top_docs, _subset=subset, _mask=mask)
             return self.id_lists(indexes), scores
         from concurrent.futures import ThreadPoolExecutor
         per = (nq + n_chunks - 1) // n_chunks
@@ -305,7 +318,7 @@ class DenseFlatIndexer(DenseIndexer):
         def gpu(c):
             with torch.cuda.device(dev):
                 torch.cuda.current_stream(dev).wait_event(ready)          # the worker thread's current stream is the default one
-                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs, _subset=subset)
+                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs, _subset=subset, _mask=mask)
         top_doc_ids, score_parts = [], []
         with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(gpu, 0)
@@ -317,17 +330,21 @@ class DenseFlatIndexer(DenseIndexer):
                 score_parts.append(scores)
         return top_doc_ids, np.concatenate(score_parts)
 
-    def search_arrays(self, query_reps, top_docs: int, allowed_ids=None, _subset=None):
+    def search_arrays(self, query_reps, top_docs: int, allowed_ids=None, _subset=None, allowed_mask=None, _mask=None):
         """(scores fp32 [nq, k], index positions int64 [nq, k]; -1 = fewer than k vectors) as host arrays: what search_knn maps
-        to db ids, and what the run.json writer takes as they are (utils/run_file.py).  allowed_ids as for search_knn (_subset: its
-        positions, already on the device)."""
+        to db ids, and what the run.json writer takes as they are (utils/run_file.py).  allowed_ids / allowed_mask as for search_knn
+        (_subset: the positions, already on the device; _mask: the packed bitmap, already on the device)."""
+        if allowed_ids is not None and allowed_mask is not None:
+            raise ValueError("search_arrays: pass allowed_ids or allowed_mask, not both")
         if allowed_ids is not None:
             _subset = self.allowed_subset(allowed_ids)
+        if allowed_mask is not None:
+            _mask = self.allowed_mask_words(allowed_mask)
         if isinstance(query_reps, torch.Tensor):
             q = query_reps.to(device=self.index.device, dtype=torch.float32)
         else:
             q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
-        scores, indexes = self.index.search(q, top_docs, subset=_subset)
+        scores, indexes = self.index.search(q, top_docs, subset=_subset, mask=_mask)
         return to_host(scores), to_host(indexes)
 
     def inverse_id_map(self):

@@ -54,6 +54,76 @@ def _subset(subset, device):
     return subset, m
 
 
+def pack_doc_mask(allowed):
+    """A boolean array over document indices -> the bitmap the masked search takes: bit (i & 31) of word i >> 5 is allowed[i], the unused
+    bits of the last word are 0 (include/sr_hip.h sr_dense_search_masked).  A numpy array is packed on the host and comes back as
+    np.uint32 [ceil(n / 32)]; a torch tensor is packed on its own device and comes back as int32 words (torch has no arithmetic on
+    uint32; the bits are the same)."""
+    if torch.is_tensor(allowed):
+        if allowed.dim() != 1:
+            raise ValueError(f"expected a 1-D boolean mask, got {tuple(allowed.shape)}")
+        n = allowed.numel()
+        bits = torch.zeros(((n + 31) // 32) * 32, dtype=torch.int64, device=allowed.device)
+        bits[:n] = allowed.to(torch.bool)
+        weights = torch.ones(32, dtype=torch.int64, device=allowed.device) << torch.arange(32, dtype=torch.int64, device=allowed.device)
+        return (bits.view(-1, 32) * weights).sum(dim=1).to(torch.int32)      # int64 -> int32 keeps the low 32 bits
+    allowed = np.asarray(allowed)
+    if allowed.ndim != 1:
+        raise ValueError(f"expected a 1-D boolean mask, got {allowed.shape}")
+    n_words = (allowed.size + 31) // 32
+    raw = np.zeros(4 * n_words, dtype=np.uint8)
+    packed = np.packbits(allowed.astype(bool), bitorder="little")         # bit i & 7 of byte i >> 3
+    raw[:packed.size] = packed
+    return raw.view("<u4").astype(np.uint32)                              # little-endian words: bit i & 31 of word i >> 5
+
+
+def doc_mask_from_list(ids, n_bits, device=None):
+    """Document indices (int64, any order, repeats allowed; tensor / array / list) -> the bitmap over [0, n_bits) as int32 words on the
+    device (sr_doc_mask_from_list).  An entry outside [0, n_bits): ValueError."""
+    _lib.require_gpu()
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    ids, m = _subset(ids, device)
+    words = torch.empty((max(1, (int(n_bits) + 31) // 32),), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().sr_doc_mask_from_list(_ptr(ids), m, _ptr(words), int(n_bits), _lib.stream_ptr()), "sr_doc_mask_from_list")
+    return words[:(int(n_bits) + 31) // 32]
+
+
+def doc_list_from_mask(words, n_bits, capacity=None):
+    """The set bits below n_bits of a packed bitmap (int32 / uint32 words, tensor or array) as an ascending int64 tensor on the device
+    (sr_doc_list_from_mask).  capacity (None: room for every bit): at most that many entries are written; returns (list, count) with
+    count = the number of set bits whatever the capacity."""
+    _lib.require_gpu()
+    words = _mask_words(words, torch.device("cuda", torch.cuda.current_device()) if not (torch.is_tensor(words) and words.is_cuda) else words.device)
+    n_bits = int(n_bits)
+    if words.numel() < (n_bits + 31) // 32:
+        raise ValueError(f"{n_bits} bits need {(n_bits + 31) // 32} words, got {words.numel()}")
+    cap = n_bits if capacity is None else int(capacity)
+    out = torch.empty((max(1, cap),), dtype=torch.int64, device=words.device)
+    count = torch.zeros(1, dtype=torch.int64, device=words.device)
+    if words.numel() == 0:
+        words = torch.zeros(1, dtype=torch.int32, device=words.device)
+    with torch.cuda.device(words.device):
+        _lib.check(_lib.load().sr_doc_list_from_mask(_ptr(words), n_bits, _ptr(out), cap, _ptr(count), _lib.stream_ptr()), "sr_doc_list_from_mask")
+    c = int(count.item())
+    return out[:min(c, cap)], c
+
+
+def _mask_words(words, device):
+    """Packed bitmap words (np.uint32 / np.int32 array, or an int32 / uint32 tensor) -> a contiguous int32 tensor on the device."""
+    if isinstance(words, np.ndarray):
+        if words.dtype not in (np.uint32, np.int32):
+            raise ValueError(f"packed mask words must be uint32 or int32, got {words.dtype}")
+        words = torch.from_numpy(np.ascontiguousarray(words).view(np.int32))
+    elif words.dtype == getattr(torch, "uint32", None):
+        words = words.view(torch.int32)
+    elif words.dtype != torch.int32:
+        raise ValueError(f"packed mask words must be uint32 or int32, got {words.dtype}")
+    if words.dim() != 1:
+        raise ValueError(f"expected 1-D mask words, got {tuple(words.shape)}")
+    return words.to(device).contiguous()
+
+
 def allowed_positions(allowed_ids, position_of, what="document id"):
     """External document ids (any order, duplicates allowed) -> sorted unique positions, np.int64: the allow-list the subset searches take.
     position_of maps an id to its position (a dict's .get, or any callable that returns None for an unknown id); an unknown id raises
@@ -258,6 +328,11 @@ class DenseIndexHIP:
     def ntotal(self):
         return int(self.lib.sr_dense_index_ntotal(self._h))
 
+    @property
+    def id_end(self):
+        """The largest document index of any segment, plus one: the length of a document mask (not ntotal: segments may be strided)."""
+        return int(self.lib.sr_dense_index_id_end(self._h))
+
     def set_workspace_limit(self, nbytes):
         _lib.check(self.lib.sr_dense_index_set_workspace_limit(self._h, int(nbytes)))
 
@@ -286,11 +361,15 @@ class DenseIndexHIP:
         _lib.check(self.lib.sr_dense_index_filter_query_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
-    def search(self, queries, k, subset=None):
+    def search(self, queries, k, subset=None, mask=None):
         """queries: fp32 cuda tensor [nq, dim] -> (scores fp32 [nq,k], ids int64 [nq,k]) cuda tensors.  subset (None: the whole
         index): strictly ascending int64 ids as this method returns them, one allow-list for all queries - the result is the full
         ranking with every other document removed, cut to k (include/sr_hip.h sr_dense_search_subset); an id outside the index or
-        out of order: ValueError naming its position."""
+        out of order: ValueError naming its position.  mask: the same filter as a bitmap over [0, id_end) - a bool tensor / array
+        of length id_end (packed on the device), or int32 / uint32 words already packed (pack_doc_mask) - with exactly the result
+        of `subset` = the set positions (sr_dense_search_masked); a set bit that names no document: ValueError naming it.  Not both."""
+        if subset is not None and mask is not None:
+            raise ValueError("search: pass subset or mask, not both")
         if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
         if not queries.is_cuda:
@@ -306,6 +385,26 @@ class DenseIndexHIP:
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.sr_dense_search_subset(self._h, _ptr(queries), nq, int(k), _ptr(subset), m, _ptr(scores), _ptr(ids),
                                                            _lib.stream_ptr()), "sr_dense_search_subset")
+            return scores, ids
+        if mask is not None:
+            packed = (isinstance(mask, np.ndarray) and mask.dtype in (np.uint32, np.int32)) or \
+                (torch.is_tensor(mask) and mask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
+            if packed:
+                n_bits = self.id_end
+                words = _mask_words(mask, self.device)
+                if words.numel() != (n_bits + 31) // 32:
+                    raise ValueError(f"a packed mask of this index holds {(n_bits + 31) // 32} words (id_end = {n_bits}), got {words.numel()}")
+            else:
+                flags = _to_dev(mask, torch.bool, self.device)
+                if flags.dim() != 1:
+                    raise ValueError(f"expected a 1-D mask, got {tuple(flags.shape)}")
+                n_bits = flags.numel()            # the library compares it with id_end
+                words = pack_doc_mask(flags)
+            if words.numel() == 0:
+                words = torch.zeros(1, dtype=torch.int32, device=self.device)      # keep a valid pointer
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_dense_search_masked(self._h, _ptr(queries), nq, int(k), _ptr(words), n_bits, _ptr(scores), _ptr(ids),
+                                                           _lib.stream_ptr()), "sr_dense_search_masked")
             return scores, ids
         with torch.cuda.device(self.device):      # the library allocates its workspace on the current device
             _lib.check(self.lib.sr_dense_search(self._h, _ptr(queries), nq, int(k), _ptr(scores), _ptr(ids),

@@ -102,6 +102,54 @@ def dense_leg(a, dev):
     return out
 
 
+def dense_routes_leg(a, dev):
+    """The two routes of the dense subset search, each forced (SR_SUBSET_DENSE_ROUTE), for nq in {64, 6 980} and m in {100 000, 1 000 000,
+    half the collection, all documents}, next to the unrestricted search of the same index in the same process (k = 1 000: the unchanged
+    instantiation of the filter's pass - the yardstick of the mask route at "all documents allowed").  The filter is given as a packed
+    bitmap (sr_dense_search_masked), so the gather route's time includes the bitmap -> list expansion and the mask route's the same.
+    A route whose warm-up run takes longer than --slow-ms is timed with --slow-reps runs."""
+    from scaling_retriever_amd.scoring import DenseIndexHIP, pack_doc_mask
+    os.environ["SR_DEV_SWITCHES"] = "1"
+    N = max(2 * a.k, int(a.n_docs * a.scale))
+    D = dense_rows("gauss", N, a.hidden, dev, 1)
+    idx = DenseIndexHIP(a.hidden, device=dev)
+    idx.add_device_rows(D)
+    idx.set_precision("fp32_filtered")
+    rows = []
+    for nq in a.route_nqs:
+        Q = dense_queries("gauss", nq, a.hidden, dev, 2)
+        _, full = timed(lambda: idx.search(Q, a.k), a.reps)
+        for m in [x for x in a.route_ms if x < N // 2] + [N // 2, N]:
+            flags = torch.zeros(N, dtype=torch.bool, device=dev)
+            flags[draw_subset(N, m, dev, m)] = True
+            words = pack_doc_mask(flags)
+            row = {"m": m, "nq": nq, "k": a.k, "unrestricted_search": full}
+            outs = {}
+            for route in ("mask", "gather"):
+                os.environ["SR_SUBSET_DENSE_ROUTE"] = route
+                before = idx.filter_stats()
+                t0 = time.perf_counter()
+                idx.search(Q, a.k, mask=words)
+                torch.cuda.synchronize()
+                first_ms = (time.perf_counter() - t0) * 1e3
+                outs[route], row[route] = timed(lambda: idx.search(Q, a.k, mask=words), a.slow_reps if first_ms > a.slow_ms else a.reps, warmup=0)
+                after = idx.filter_stats()
+                row[route]["served_by_the_filter_pass"] = after[0] + after[1] > before[0] + before[1]
+            os.environ.pop("SR_SUBSET_DENSE_ROUTE", None)
+            row["routes_equal_bit_for_bit"] = bool(torch.equal(outs["mask"][1], outs["gather"][1]) and
+                                                    torch.equal(outs["mask"][0].view(torch.int32), outs["gather"][0].view(torch.int32)))
+            row["mask_over_unrestricted"] = round(row["mask"]["median_ms"] / full["median_ms"], 4)
+            rows.append(row)
+            print("[dense routes]", json.dumps(row), file=sys.stderr, flush=True)
+            del flags, words, outs
+        del Q
+    out = {"n_docs": N, "hidden": a.hidden, "kernel": "dense_split_kernel<true, true> (mask) / dense_subset_kernel (gather)", "rows": rows}
+    idx.close()
+    del D, idx
+    torch.cuda.empty_cache()
+    return out
+
+
 def sparse_leg(a, dev):
     from scaling_retriever_amd.scoring import SparseIndexHIP
     N = max(8 * (a.k + 1024), int(a.n_docs * a.scale))
@@ -149,11 +197,17 @@ def main():
     ap.add_argument("--k", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=7, help="timed runs per figure after one warm-up run (median reported)")
     ap.add_argument("--pairs-limit", type=int, default=500_000_000, help="largest nq x m the pair-scorer baseline is run for (12 bytes each)")
-    ap.add_argument("--legs", type=str, default="dense,sparse")
+    ap.add_argument("--legs", type=str, default="dense,sparse", help="dense, sparse, dense_routes (both routes of the dense search forced)")
+    ap.add_argument("--route-nqs", type=str, default="64,6980")
+    ap.add_argument("--route-ms", type=str, default="100000,1000000", help="dense_routes: these, then half the collection and all of it")
+    ap.add_argument("--slow-ms", type=float, default=1000.0, help="dense_routes: a search slower than this is timed with --slow-reps runs")
+    ap.add_argument("--slow-reps", type=int, default=1)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "subset_search.json"))
     a = ap.parse_args()
     a.nqs = [int(x) for x in a.nqs.split(",")]
     a.ms = [int(x) for x in a.ms.split(",")]
+    a.route_nqs = [int(x) for x in a.route_nqs.split(",")]
+    a.route_ms = [int(x) for x in a.route_ms.split(",")]
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     t0 = time.time()
@@ -164,7 +218,7 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             earlier = json.load(f)
-    for leg, fn in (("dense", dense_leg), ("sparse", sparse_leg)):
+    for leg, fn in (("dense", dense_leg), ("sparse", sparse_leg), ("dense_routes", dense_routes_leg)):
         if leg in a.legs.split(","):
             res[leg] = fn(a, dev)
         elif isinstance(earlier.get(leg), dict) and earlier.get("scale") == a.scale:
