@@ -536,9 +536,15 @@ int sr_attention_varlen(const void* d_qkv, void* d_out, const int32_t* d_cu_seql
 /* The attention of the encoder's fp32 regime: d_qkv fp32 [T,(nh+2nkv)*hd] with q / k already rotated, fp32 scores, softmax and
  * P.V.  Exactly one output: d_out_f32 fp32 [T,nh*hd] (what fp32_planes = 16 uses), or d_out_planes bf16 [T, n_seg*nh*hd] = the
  * bf16 plane segments the o_proj GEMM consumes, fp32_planes = 3 (6 segments: planes 2 0 1 1 0 0) or 2 (3 segments: 1 0 0);
- * fp32_planes is ignored with d_out_f32.  max_seqlen = the longest sequence of the batch (it sizes the grids and the LDS of the
+ * fp32_planes is ignored with d_out_f32.  d_qkv and d_out_f32 must be 16-byte aligned, d_out_planes 8-byte aligned (else
+ * SR_ERR_INVALID).  max_seqlen = the longest sequence of the batch (it sizes the grids and the LDS of the
  * short-sequence kernel: never pass less).  head_dim 64 or 128, else SR_ERR_UNSUPPORTED and nothing is launched.  The kernel is
- * chosen per sequence (<= 64 tokens at 4 q heads per kv head: fp32 MFMA), so a sequence's bits do not depend on its batch. */
+ * chosen per sequence (<= 64 tokens at 4 q heads per kv head: fp32 MFMA), so a sequence's bits do not depend on its batch.
+ * Launch plan of the <= 64-token kernel: a sequence needs LDS for its own ceil(S / 16) blocks of 16 keys, and the encoder, which holds
+ * cu_seqlens on the host, runs one launch per such class (1..4) that has a sequence.  This entry point does not know the classes: it
+ * runs ONE launch with LDS for max_seqlen's class, which serves every shorter sequence too (one that needs more is skipped, never
+ * overrun).  The bits are the same on every route.  Dev switch SR_ATTN_F32_LAYOUT (read per call): 0 = the form before the plan (LDS by
+ * max_seqlen, q staged through LDS, element stores), 2 = a launch per class up to max_seqlen's even here (tests). */
 int sr_attention_varlen_f32(const float* d_qkv, float* d_out_f32, void* d_out_planes, int32_t fp32_planes,
                             const int32_t* d_cu_seqlens, const uint8_t* d_key_valid, int32_t B, int32_t num_heads,
                             int32_t num_kv_heads, int32_t head_dim, int32_t max_seqlen, sr_stream stream);

@@ -4,6 +4,7 @@ The product path has NO fallback: if the HIP library is missing or a call fails,
 this module raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
 or `make -C scaling_retriever_amd/csrc`.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -123,26 +124,45 @@ class SrHipError(RuntimeError):
     pass
 
 
+def _bind(path):
+    if not os.path.exists(path):
+        raise SrHipError(
+            f"{path} not found: the HIP extension is not built. There is no CPU fallback; "
+            "run `make -C scaling_retriever_amd/csrc` (needs hipcc, targets gfx950).")
+    # torch first: it ships its own libamdhip64; were the system runtime pulled in by our DT_NEEDED before torch's, the
+    # process would hold two HIP runtimes and the second would find "no ROCm-capable device"
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load():
     """Load libsr_hip.so and bind every entry point.  Raises if the library is missing."""
     global _lib
     with _lock:
-        if _lib is not None:
-            return _lib
-        if not os.path.exists(LIB_PATH):
-            raise SrHipError(
-                f"{LIB_PATH} not found: the HIP extension is not built. There is no CPU fallback; "
-                "run `make -C scaling_retriever_amd/csrc` (needs hipcc, targets gfx950).")
-        # torch first: it ships its own libamdhip64; were the system runtime pulled in by our DT_NEEDED before torch's, the
-        # process would hold two HIP runtimes and the second would find "no ROCm-capable device"
-        import torch  # noqa: F401
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _lib = lib
-        return lib
+        if _lib is None:
+            _lib = _bind(LIB_PATH)
+        return _lib
+
+
+@contextlib.contextmanager
+def library(path):
+    """Development aid (same-process A/B of two builds, tools/quick_query_encode.py --ab-lib): inside the block load() returns the
+    build at `path`; an object created there keeps that build (a backbone holds the handle it was created with), and the
+    process-wide library is restored on exit."""
+    global _lib
+    other = _bind(os.path.abspath(path))
+    with _lock:
+        keep, _lib = _lib, other
+    try:
+        yield other
+    finally:
+        with _lock:
+            _lib = keep
 
 
 def check(rc, what=""):

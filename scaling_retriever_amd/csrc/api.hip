@@ -98,6 +98,9 @@ extern "C" int sr_attention_varlen_f32(const float* d_qkv, float* d_out_f32, voi
     SR_REQUIRE((d_out_f32 != nullptr) != (d_out_planes != nullptr), "sr_attention_varlen_f32: pass exactly one of d_out_f32 / d_out_planes");
     SR_REQUIRE(d_out_f32 || fp32_planes == 2 || fp32_planes == 3, "sr_attention_varlen_f32: fp32_planes %d (2 or 3 for plane output)", fp32_planes);
     SR_REQUIRE(B >= 0 && max_seqlen >= 0 && num_heads > 0 && num_kv_heads > 0 && head_dim > 0, "sr_attention_varlen_f32: bad sizes");
+    // the short-sequence kernel loads q / k / v and stores the fp32 output 16 bytes, the plane segments 8 bytes at a time
+    SR_REQUIRE((uintptr_t)d_qkv % 16 == 0 && (uintptr_t)d_out_f32 % 16 == 0 && (uintptr_t)d_out_planes % 8 == 0,
+               "sr_attention_varlen_f32: d_qkv and d_out_f32 must be 16-byte aligned, d_out_planes 8-byte aligned");
     AttnF32Args a{};
     a.qkv = d_qkv; a.out_f32 = d_out_f32; a.out = (bf16_t*)d_out_planes; a.cu_seqlens = d_cu_seqlens; a.key_valid = d_key_valid;
     a.B = B; a.nh = num_heads; a.nkv = num_kv_heads; a.hd = head_dim;

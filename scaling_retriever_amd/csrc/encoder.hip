@@ -1094,7 +1094,13 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
     int max_len = 0;
     // a row whose attention_mask is all zero packs to zero tokens: every kernel skips it and both heads return the
     // zero vector for it (the reference's sparse head gives exactly that; its dense head would average garbage)
-    for (int b = 0; b < B; ++b) max_len = (m->h_cu[b + 1] - m->h_cu[b]) > max_len ? (m->h_cu[b + 1] - m->h_cu[b]) : max_len;
+    // + the fp32 attention's launch plan: sequences of at most 64 tokens by key-block count ceil(S / 16) (attention_f32.hip)
+    int attn_class[4] = {0, 0, 0, 0};
+    for (int b = 0; b < B; ++b) {
+        const int len = m->h_cu[b + 1] - m->h_cu[b];
+        max_len = len > max_len ? len : max_len;
+        if (len >= 1 && len <= 64) ++attn_class[(len - 1) >> 4];
+    }
     SR_REQUIRE(T <= m->Tm, "encode: batch packs to %d tokens, workspace holds %d (raise max_batch_tokens or split the batch)", T, m->Tm);
     *T_out = T;
     m->last_T = T;
@@ -1118,7 +1124,7 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
             split_rows(m->x, li == 0 ? m->embed : (const float*)nullptr, li == 0 ? m->tok_id : (const int*)nullptr, l.ln1, m->xs, m->xs_i, H,
                        l.qkv_seg);
             GemmArgs g{};
-            g.A = m->xs; g.W = l.wqkv_s; g.M = T; g.N = nq + 2 * nkv; g.K = l.qkv_seg * H; g.C = m->qkv_f; g.a_scale = m->xs_i; g.w_scale = l.wqkv_i;
+            g.A = m->xs; g.W = l.wqkv_s; g.M = T; g.N = nq + 2 * nkv; g.K = l.qkv_seg * H; g.a_nseg = l.qkv_seg; g.C = m->qkv_f; g.a_scale = m->xs_i; g.w_scale = l.wqkv_i;
             g.pos = m->pos; g.rope_cos = m->rope_cos; g.rope_sin = m->rope_sin; g.n_rope = nq + nkv; g.head_dim = c.head_dim;
             g.bias = l.bqkv;
             SR_TRY(launch_gemm_bf16(EPI_QKV_ROPE_F32_H, g, s));
@@ -1126,10 +1132,12 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
             a.qkv = m->qkv_f; a.out_f32 = m->attn_f; a.out = nullptr; a.cu_seqlens = m->cu; a.key_valid = m->key_valid;
             a.B = B; a.nh = c.num_heads; a.nkv = c.num_kv_heads; a.hd = c.head_dim;
             a.scale = 1.0f / sqrtf((float)c.head_dim); a.max_seqlen = max_len;
+            a.have_classes = 1;
+            for (int n = 0; n < 4; ++n) a.class_seqs[n] = attn_class[n];
             SR_TRY(launch_attention_f32(a, s));
             split_rows(m->attn_f, nullptr, nullptr, nullptr, m->attn_s, m->attn_i, nq, l.o_seg);
             g = GemmArgs{};
-            g.A = m->attn_s; g.W = l.wo_s; g.M = T; g.N = H; g.K = l.o_seg * nq; g.C = m->x; g.a_scale = m->attn_i; g.w_scale = l.wo_i;
+            g.A = m->attn_s; g.W = l.wo_s; g.M = T; g.N = H; g.K = l.o_seg * nq; g.a_nseg = l.o_seg; g.C = m->x; g.a_scale = m->attn_i; g.w_scale = l.wo_i;
             SR_TRY(launch_gemm_bf16(EPI_RESID_F32_H, g, s));
             if (fused_act) {
                 // the norm kernel also fixes the scale of the row's SwiGLU output (a rigorous bound, no overflow), so the
@@ -1137,18 +1145,18 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
                 launch_rows_split_h(m->x, nullptr, nullptr, l.ln2, m->xs, m->xs_i, T, H, c.rms_norm_eps, l.gu_seg, s, l.gu_cmax, m->act_sc,
                                     m->act_i);
                 g = GemmArgs{};
-                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = l.gu_seg * H; g.C = m->act_s; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
+                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = l.gu_seg * H; g.a_nseg = l.gu_seg; g.C = m->act_s; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
                 g.out_scale = m->act_sc; g.out_nseg = l.down_seg;
                 SR_TRY(launch_gemm_bf16(EPI_SWIGLU_SPLIT_H, g, s));
             } else {
                 split_rows(m->x, nullptr, nullptr, l.ln2, m->xs, m->xs_i, H, l.gu_seg);
                 g = GemmArgs{};
-                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = l.gu_seg * H; g.C = m->act_f; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
+                g.A = m->xs; g.W = l.wgu_s; g.M = T; g.N = 2 * I; g.K = l.gu_seg * H; g.a_nseg = l.gu_seg; g.C = m->act_f; g.a_scale = m->xs_i; g.w_scale = l.wgu_i;
                 SR_TRY(launch_gemm_bf16(EPI_SWIGLU_F32_H, g, s));
                 split_rows(m->act_f, nullptr, nullptr, nullptr, m->act_s, m->act_i, I, l.down_seg);
             }
             g = GemmArgs{};
-            g.A = m->act_s; g.W = l.wdown_s; g.M = T; g.N = H; g.K = l.down_seg * I; g.C = m->x; g.a_scale = m->act_i; g.w_scale = l.wdown_i;
+            g.A = m->act_s; g.W = l.wdown_s; g.M = T; g.N = H; g.K = l.down_seg * I; g.a_nseg = l.down_seg; g.C = m->x; g.a_scale = m->act_i; g.w_scale = l.wdown_i;
             SR_TRY(launch_gemm_bf16(EPI_RESID_F32_H, g, s));
         }
         SR_CHECK_LAUNCH();
@@ -1171,6 +1179,8 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
             a.qkv = m->qkv_f; a.out = m->attn_s; a.cu_seqlens = m->cu; a.key_valid = m->key_valid;
             a.B = B; a.nh = c.num_heads; a.nkv = c.num_kv_heads; a.hd = c.head_dim;
             a.scale = 1.0f / sqrtf((float)c.head_dim); a.max_seqlen = max_len; a.out_map = ma;
+            a.have_classes = 1;
+            for (int n = 0; n < 4; ++n) a.class_seqs[n] = attn_class[n];
             SR_TRY(launch_attention_f32(a, s));
             g = GemmArgs{};
             g.A = m->attn_s; g.W = l.wo_s; g.M = T; g.N = H; g.K = nsg * nq; g.C = m->x;
@@ -1251,7 +1261,7 @@ static int head_sparse(sr_model* m, int B, int T, int prec, float* d_out, hipStr
     if (prec == PREC_FP32 && m->cfg.fp32_planes == SR_FP32_PLANES_F16) {
         launch_rows_split_h(m->x, (const float*)nullptr, (const int*)nullptr, (const float*)m->norm_w, m->xs, m->xs_i, T, H,
                             m->cfg.rms_norm_eps, m->lm_head_seg, s);
-        g.A = m->xs; g.W = m->lm_head_s; g.K = m->lm_head_seg * H; g.a_scale = m->xs_i; g.w_scale = m->lm_head_i;
+        g.A = m->xs; g.W = m->lm_head_s; g.K = m->lm_head_seg * H; g.a_nseg = m->lm_head_seg; g.a_scale = m->xs_i; g.w_scale = m->lm_head_i;
         epi = EPI_SEGMAX_H;
     } else if (prec == PREC_FP32) {
         const SplitMap ma = split_map_a(m->cfg.fp32_planes);

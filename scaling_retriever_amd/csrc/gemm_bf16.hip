@@ -72,6 +72,11 @@ struct EpiTraits {
     // the four-wave loop (KL = 1) has an epilogue staged through LDS for these; no other epilogue runs behind it
     static constexpr bool STAGED_4W = BASE == EPI_STORE_BF16 || BASE == EPI_SWIGLU || BASE == EPI_QKV_ROPE || BASE == EPI_STORE_F32 ||
                                       BASE == EPI_RESID_F32 || BASE == EPI_SWIGLU_SPLITH_BASE;
+    // fp16-plane epilogues whose GEMM takes the four-wave loop when its operands have 2 plane segments (K' = 2 K); at 3 segments
+    // all of them stay on the eight-wave loop.  Decided per epilogue from kernel times at the bench shape (60 841 tokens, table in
+    // DESIGN 4.4): gate-up (SwiGLU split) is 2.0 % faster on it; the residual epilogue is not (o_proj 4.8 % slower, down_proj
+    // 0.6 % faster, together 0.4 % slower) and keeps the eight-wave loop.
+    static constexpr bool FOUR_WAVE_AT_2SEG = F16 && STAGED_4W && BASE == EPI_SWIGLU_SPLITH_BASE;
     // output features per segment and segments per row of C: SwiGLU halves N, the split variants repeat it per plane
     static __host__ __device__ __forceinline__ int out_features(const GemmArgs& g) { return SWIGLU ? (g.N >> 1) : g.N; }
     static __host__ __device__ __forceinline__ int out_segments(const GemmArgs& g) {
@@ -79,6 +84,13 @@ struct EpiTraits {
     }
     static __host__ __device__ __forceinline__ int64_t out_ld(const GemmArgs& g) { return (int64_t)out_segments(g) * out_features(g); }
 };
+
+// a kernel argument read from the kernel-argument segment where it is used (see LATE_ARGS in the kernel)
+template <typename T>
+__device__ __forceinline__ T sr_late_arg(__attribute__((address_space(4))) const char* kargs, size_t off) {
+    typedef __attribute__((address_space(4))) const T* ptr_t;
+    return *(ptr_t)(kargs + off);
+}
 
 // WAVES_N x WAVES_M waves; each wave owns (16 * NB) features x (16 * MB) tokens.
 // PIPE: fragment double-buffering - the ds_reads of the next half k-step are in flight while the MFMAs of the current
@@ -606,18 +618,32 @@ void gemm_bf16_kernel(GemmArgs g) {
 #undef SR_MFMA_HALF
     if (stamp && titer < 16) stp[titer * 4 + 2] = __builtin_amdgcn_s_memrealtime();
     if (stamp && titer == 1) stp[63] = __builtin_amdgcn_s_memtime();        // ... and at its end: clock = d(memtime) / d(realtime) * 100 MHz
+    // The four-wave SwiGLU-split kernel reads the pointers only its epilogue needs (row scales, output, output scales) from the
+    // kernel-argument segment per tile, through a pointer made opaque here: hipcc otherwise loads them at entry, carries them
+    // through the tile loop and, out of scalar registers, parks 9 of them in lanes of a vector register.
+    constexpr bool LATE_ARGS = KL == 1 && BEPI == EPI_SWIGLU_SPLITH_BASE;
+    typedef __attribute__((address_space(4))) const char* sr_kernarg_ptr;
+    [[maybe_unused]] sr_kernarg_ptr kargs = nullptr;
+    if constexpr (LATE_ARGS) {
+        kargs = (sr_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kargs));
+    }
+#define SR_LATE_ARG(type, field) sr_late_arg<type>(kargs, offsetof(GemmArgs, field))
     if constexpr (F16) {       // undo the power-of-two row scales of both operands (exact)
+        const float* a_scale = g.a_scale;
+        const float* w_scale = g.w_scale;
+        if constexpr (LATE_ARGS) { a_scale = SR_LATE_ARG(const float*, a_scale); w_scale = SR_LATE_ARG(const float*, w_scale); }
         float sa[MB];
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
             const int m = m0 + wm * MB * 16 + j * 16 + frow;
-            sa[j] = m < g.M ? g.a_scale[m] : 0.f;
+            sa[j] = m < g.M ? a_scale[m] : 0.f;
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int n = n0 + wn * NB * 16 + i * 16 + fg * 4;
             f32x4 sw = {0.f, 0.f, 0.f, 0.f};
-            if (n < g.N) sw = *reinterpret_cast<const f32x4*>(g.w_scale + n);
+            if (n < g.N) sw = *reinterpret_cast<const f32x4*>(w_scale + n);
 #pragma unroll
             for (int j = 0; j < MB; ++j)
 #pragma unroll
@@ -799,14 +825,17 @@ void gemm_bf16_kernel(GemmArgs g) {
         // staged: a token row of this wave is 64 output features = 128 B per plane; a buffer holds 16 rows x (f1 | f0) = 4 KB
         unsigned char* const stg0 = smem + 2 * STAGE_BYTES + wave * 8192;
         const int half_n = g.N >> 1;
-        const bool seg3 = g.out_nseg == 3;
-        const int64_t ldc = E::out_ld(g);
+        const int out_nseg = SR_LATE_ARG(int, out_nseg);
+        const float* const out_scale = SR_LATE_ARG(const float*, out_scale);
+        bf16_t* const out_c = reinterpret_cast<bf16_t*>(SR_LATE_ARG(void*, C));
+        const bool seg3 = out_nseg == 3;
+        const int64_t ldc = (int64_t)out_nseg * half_n;        // = E::out_ld(g)
         const int nb = (n0 >> 1) + wn * 64;
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
             const int mrow = m0 + wm * MB * 16 + j * 16;
             unsigned char* stg = stg0 + (j & 1) * 4096;
-            const float osc = (mrow + frow_e) < g.M ? g.out_scale[mrow + frow_e] : 0.f;
+            const float osc = (mrow + frow_e) < g.M ? out_scale[mrow + frow_e] : 0.f;
 #pragma unroll
             for (int i = 0; i < NB; i += 2) {
                 const f32x4 gt = acc[i][j], up = acc[i + 1][j];
@@ -830,7 +859,7 @@ void gemm_bf16_kernel(GemmArgs g) {
                 const sr_i32x4 v = *reinterpret_cast<const sr_i32x4*>(stg + tok * 256 + pl * 128 + ((pc ^ (tok & 7)) << 4));
                 const int m = mrow + tok, n = nb + pc * 8;
                 if (m < g.M && n < half_n) {
-                    bf16_t* crow = reinterpret_cast<bf16_t*>(g.C) + (int64_t)m * ldc + n;
+                    bf16_t* crow = out_c + (int64_t)m * ldc + n;
                     if (pl == 0) {
                         *reinterpret_cast<sr_i32x4*>(crow) = v;                    // f1
                     } else {
@@ -1165,9 +1194,11 @@ static int launch_big(const GemmArgs& g, hipStream_t s) {
     {
         // The four-wave loop is the default for the bf16 regime's plain-store / residual / SwiGLU GEMMs (o_proj, down_proj, gate-up:
         // 88 % of a layer's GEMM work; +7-10 % on those, corpus encode 7 590 -> 8 390 passages/s).  SR_GEMM_BIG=8w: the 8-wave loop
-        // everywhere (A/B); SR_GEMM_BIG=4w: the four-wave loop also for the fp32 regime's fp16-plane GEMMs, which have staged
-        // epilogues too but measure 2 % SLOWER on it (query encode 300 -> 307 ms: K' = 3 K k-steps per tile, the epilogue does
-        // not matter there and the 8-wave loop's second wave per SIMD does) - tests force it to keep that path covered.
+        // everywhere (A/B); SR_GEMM_BIG=4w: the four-wave loop for every fp16-plane GEMM with a staged epilogue (tests, A/B).  Those
+        // GEMMs of the fp32 regime choose by GemmArgs::a_nseg and EpiTraits::FOUR_WAVE_AT_2SEG: at K' = 3 K the four-wave loop is 2-4 %
+        // SLOWER (query encode 300 -> 307 ms: that many k-steps per tile, the epilogue does not matter and the 8-wave loop's second
+        // wave per SIMD does); at K' = 2 K (weights without a low plane) the gate-up GEMM is 2 % faster on it and takes it.  A caller
+        // that does not state the count gets the 8-wave loop.
         // The bf16 regime's QKV + RoPE epilogue (12 % of a layer's GEMM work) joined in round 6: rotation on the accumulators, staged
         // through LDS like the plain store.  The fp32 regime's QKV epilogues (fp32 output, fp16-plane operands) stay on the 8-wave loop.
         // tests/test_abi.py holds every four-wave instantiation to zero scratch.  The loop's buffer descriptors address a tile's
@@ -1177,7 +1208,9 @@ static int launch_big(const GemmArgs& g, hipStream_t s) {
         if constexpr (E::STAGED_4W) {
             // QKV + RoPE: a wave's 128 features must lie on one side of n_rope (two heads of 64 per wave)
             const bool rope_ok = !E::QKV_ROPE || g.n_rope % 128 == 0;
-            if (pipe && (int64_t)g.K * 512 < (1ll << 31) && !want8 && (!E::F16 || want4) && rope_ok)
+            // fp16 planes: by the segment count of the operands and the epilogue's entry in the table of DESIGN 4.4
+            const bool f16_four = want4 || (g.a_nseg == 2 && E::FOUR_WAVE_AT_2SEG);
+            if (pipe && (int64_t)g.K * 512 < (1ll << 31) && !want8 && (!E::F16 || f16_four) && rope_ok)
                 return launch_cfg<EPI, 2, 2, 8, 8, true, 2, 1>(g, s);
         }
     }

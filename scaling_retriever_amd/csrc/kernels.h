@@ -69,6 +69,8 @@ struct GemmArgs {
     const float* a_scale;   // _H epilogues: [M] inverse scale of each activation row (a power of two)
     const float* w_scale;   // _H epilogues: [N] inverse scale of each weight row
     const float* out_scale; // EPI_SWIGLU_SPLIT_H: [M] forward scale of each output row
+    int a_nseg;             // _H epilogues: plane segments of A and W per row (K = a_nseg x features), 2 or 3; 0 = not stated.  launch_big
+                            // picks the 256 x 256 loop by it (gemm_bf16.hip)
     int out_nseg;           // EPI_SWIGLU_SPLIT_H: 3 = C [M, 3 N/2] = [f1 | f0 | f0], 2 = [f1 | f0] (down_proj weights without a g1 plane)
     SplitMap out_map;  // EPI_SWIGLU_SPLIT: plane of each output segment; C is [M, n_seg * N/2] bf16
     int m_fastest;     // tile order, chosen by launch_gemm_bf16: 1 = token tiles fastest (W far larger than the caches)
@@ -113,5 +115,11 @@ struct AttnF32Args {
     // set by launch_attention_f32: a kernel serves the sequences with only_gt < S and (only_le == 0 or S <= only_le), so the kernel
     // - and with it the bits - of a sequence depends on ITS length, never on what else shares the batch
     int only_le = 0, only_gt = 0;
+    // launch plan of the <= 64-token kernel (attention_f32.hip): class_seqs[n - 1] = sequences of the batch with ceil(S / 16) = n key
+    // blocks, n = 1..4, counted by a caller that holds cu_seqlens on the host (have_classes = 1: classes without a sequence are not
+    // launched).  have_classes = 0: not known, one launch sized by max_seqlen serves every class.  nkb_only is set per launch
+    // (0 = every class the launch has room for).
+    int have_classes = 0, class_seqs[4] = {0, 0, 0, 0};
+    int nkb_only = 0;
 };
 int launch_attention_f32(const AttnF32Args& a, hipStream_t s);

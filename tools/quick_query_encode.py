@@ -5,7 +5,11 @@ come from the model (sr_model_weight_segments): with fp16 planes, 2 for a matrix
 bf16-valued weights), else 3.
 python tools/quick_query_encode.py [planes ...]
 python tools/quick_query_encode.py --ab N     fp16 planes, batch 6 980, fp32 regime: N alternating rounds of a model forced to
-                                              3 segments (SR_F16_WEIGHT_SEGS=3) and the default model, same weights"""
+                                              3 segments (SR_F16_WEIGHT_SEGS=3) and the default model, same weights
+python tools/quick_query_encode.py --ab-lib N OTHER.so [OUT.json]
+                                              fp16 planes, batch 6 980, fp32 regime: N alternating rounds of a model on another build
+                                              of the library (tools/build_variant.sh) and a model on the product build, same process,
+                                              same weights; the rounds are written to OUT.json"""
 import os
 import sys
 import time
@@ -77,6 +81,39 @@ if len(sys.argv) > 2 and sys.argv[1] == "--ab":
     for name, ts in times.items():
         ts = sorted(ts)
         print(f"{name:8s}: median {ts[len(ts) // 2]:8.1f} ms  min {ts[0]:8.1f}  max {ts[-1]:8.1f}  ({int(lens.sum())} tokens)", flush=True)
+    sys.exit(0)
+
+if len(sys.argv) > 3 and sys.argv[1] == "--ab-lib":
+    import json
+
+    from scaling_retriever_amd import _lib
+    rounds, other = int(sys.argv[2]), os.path.abspath(sys.argv[3])
+    with _lib.library(other):               # a model keeps the library it was built on
+        models = {"other": make(16)}
+    models["product"] = make(16)
+    batches, lens = bench.synth_batches(6980, 6980, 2.1, 0.35, 4, 64, cfg["vocab_size"], 2, dev)
+    outs = {}
+    for name, model in models.items():
+        timed(model, batches, "fp32")       # warm-up (workspace allocation)
+        i, m = batches[0]
+        outs[name] = model.query_encode(input_ids=i, attention_mask=m)
+    same = bool(torch.equal(outs["other"], outs["product"]))
+    print(f"query rows of the two builds bit-identical: {same}", flush=True)
+    times = {k: [] for k in models}
+    for r in range(rounds):
+        for name, model in models.items():
+            dt = timed(model, batches, "fp32")
+            times[name].append(round(dt * 1e3, 3))
+            print(f"round {r} {name:8s}: {dt * 1e3:8.2f} ms", flush=True)
+    spread = max(max(ts) - min(ts) for ts in times.values())
+    gain = min(times["other"]) - max(times["product"])
+    res = {"tool": "quick_query_encode.py --ab-lib", "other_lib": os.path.basename(other), "queries": 6980, "tokens": int(lens.sum()),
+           "rounds_ms": times, "bit_identical_query_rows": same, "larger_spread_ms": round(spread, 3),
+           "other_fastest_minus_product_slowest_ms": round(gain, 3), "counts_as_faster": bool(gain > 5 * spread)}
+    print(json.dumps(res), flush=True)
+    if len(sys.argv) > 4:
+        with open(sys.argv[4], "w") as f:
+            json.dump(res, f, indent=1)
     sys.exit(0)
 
 for planes in [int(a) for a in sys.argv[1:]] or [16]:
