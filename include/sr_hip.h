@@ -215,6 +215,32 @@ int sr_doc_list_from_mask(const uint32_t* d_words, int64_t n_bits, int64_t* d_li
 int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
                            const uint32_t* d_mask_words, int64_t n_bits,
                            float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
+/* Range search: EVERY document whose score exceeds a per-query threshold, as CSR - faiss's IndexFlatIP.range_search(x, thresh) ->
+ * (lims, D, I) with one threshold per query, and on the dense head what the reference's sparse scorer does with its threshold
+ * (numba_score_float, scaling_retriever/indexer.py:315-344: every document with score > threshold).  Two calls, because the size of
+ * the result is not known before the scores are:
+ *   sr_dense_range_count  d_thresholds fp32 [nq] on the device.  Writes d_lims int64 [nq + 1] (device; lims[0] = 0, lims[q + 1] -
+ *       lims[q] = the number of documents with score > thr[q]) and *total (host) = lims[nq]; it waits for the stream once, to read
+ *       those 8 bytes.  The handle keeps a table of per-chunk prefixes (4 bytes per query and chunk of rows, at most 1 024 chunks,
+ *       counted against the workspace limit: fewer, longer chunks under a small limit, SR_ERR_NOMEM with the byte count when one chunk
+ *       per segment does not fit), nq and a stamp of the segment list.
+ *   sr_dense_range_fill   the same queries, thresholds and d_lims.  For query q, d_out_scores fp32 / d_out_ids int64 [capacity] hold at
+ *       lims[q] .. lims[q + 1] every indexed document with score > thr[q] and nothing else, in (segment, row) order - ascending doc index
+ *       whenever the segments cover ascending id ranges.  Needs a preceding sr_dense_range_count on this handle with the same nq and an
+ *       unchanged index, and capacity >= that count's total: anything else is SR_ERR_INVALID and nothing is written.  Queued on
+ *       `stream`, no read-back.  As with _begin / _finish, do not interleave other range calls on the handle.  With queries or
+ *       thresholds other than the count's the lists are not meaningful, but no entry outside its query's segment of the output (and
+ *       none at or beyond capacity) is ever written.
+ * A hit is score > thr[q], strict; a NaN score or threshold is never a hit, +inf returns nothing, -inf every document with a score
+ * above -inf.  nq = 0 or an empty index: lims all zero, total 0.  Scores: the exact fp32 chain of sr_dense_score_pairs (per 8 columns
+ * k = 8s + j, then 8s + 4 + j) for EVERY nq, 1 included, whatever sr_dense_index_set_precision says: a returned score equals
+ * sr_dense_score_pairs of that pair bit for bit, and sr_dense_search's wherever that search accumulates in this order.  fp32 and fp16
+ * rows alike (the twin contract of sr_dense_index_add_f16).  No atomics: two calls return the same bytes.  Not offered: a range
+ * search under a subset or mask, doc-sharded, or on the certified filter's 16-bit pass.                           */
+int sr_dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                         int64_t* d_lims, int64_t* total, sr_stream stream);
+int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                        const int64_t* d_lims, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream);
 int sr_dense_index_destroy(sr_dense_index* idx);
 /* Measurement hook: while enabled, every launch of the score kernel is bracketed by HIP
  * events on the search stream.  _read synchronises those events and returns the number

@@ -51,6 +51,8 @@ SIGNATURES = {
     "sr_doc_mask_from_list": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "sr_doc_list_from_mask": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "sr_dense_search_masked": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_dense_range_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    "sr_dense_range_fill": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sr_dense_index_set_precision": (c_int, [c_void_p, c_int]),
     "sr_dense_search_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "sr_dense_search_finish": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1,0 +1,31 @@
+// Dense range search (dense_range.hip): every document whose exact score exceeds a per-query threshold, as CSR.
+#pragma once
+#include "common.h"
+
+#define SR_RANGE_MAX_CHUNKS 1024   // rows of the (chunk, query) table: 4 KiB per query at most
+
+// One launch = one segment: grid (query tiles, chunks of the segment).  A chunk is chunk_rows consecutive rows (a multiple of 256; the
+// segment's last chunk may be shorter), walked by ONE workgroup in ascending row order.
+struct DenseRangeArgs {
+    const void* D;            // segment base: rows of `dtype`
+    const float* Q;           // [nq, H]
+    const float* thr;         // [nq]
+    int64_t seg_rows;         // rows of the segment
+    int64_t chunk_rows;
+    int chunk_base;           // table row of the segment's first chunk
+    int H, nq;
+    int dtype;                // SR_DTYPE_F32 | SR_DTYPE_F16
+    int64_t id_base, id_stride;
+    uint32_t* table;          // [n_chunks, nq]: count kernel writes the hits of (chunk, query); the scan turns them into exclusive prefixes over the chunks
+    // fill only
+    const int64_t* lims;      // [nq + 1]
+    float* out_scores;
+    int64_t* out_ids;
+    int64_t capacity;
+};
+// query tile: 256 wide for nq > 128, 128 wide below (as dense_search_pass picks its pipelined kernels)
+static inline int dense_range_query_tile(int64_t nq) { return nq > 128 ? 256 : 128; }
+int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
+int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
+// table[c][q] := sum of table[c'][q] over c' < c (in place); lims[0] = 0, lims[q + 1] = hits of queries 0..q
+int launch_dense_range_scan(uint32_t* table, int n_chunks, int64_t nq, int64_t* d_lims, hipStream_t s);

@@ -269,6 +269,22 @@ class DenseFlatIndexer(DenseIndexer):
         positions = np.ascontiguousarray(positions, dtype=np.int64)
         return _host_lists.take_rows(table.ctypes.data, len(table) - 1, positions.ctypes.data, positions.shape[0], positions.shape[1])
 
+    def range_search(self, query_reps, thresholds, sort=True):
+        """Every document scoring above a threshold (faiss's IndexFlatIP.range_search; the dense counterpart of the threshold of
+        numba_score_float, indexer.py:315-344): (list of db-id lists, list of fp32 score arrays), one pair per query, of the documents
+        with score > thresholds (a float, or one value per query).  sort=True: best first, ties by index position, so a list is a
+        prefix of what search_knn ranks; False: index order.  The ids go through id_table in one numpy take (the ragged counterpart
+        of id_lists)."""
+        if isinstance(query_reps, torch.Tensor):
+            q = query_reps.to(device=self.index.device, dtype=torch.float32)
+        else:
+            q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
+        lims, scores, positions = self.index.range_search(q, thresholds, sort=sort)
+        lims, scores = lims.cpu().numpy(), scores.cpu().numpy()
+        flat = self.id_table()[positions.cpu().numpy()]
+        return ([flat[a:b].tolist() for a, b in zip(lims[:-1], lims[1:])],
+                [scores[a:b] for a, b in zip(lims[:-1], lims[1:])])
+
     KNN_CHUNKS = 2          # search_knn pipelines the query set in this many pieces when it is large (>= 1 024 queries)
 
     def allowed_subset(self, allowed_ids):

@@ -143,6 +143,23 @@ def read_allowed_ids_file(path):
         return [line.strip() for line in f if line.strip()]
 
 
+def range_sort(lims, scores, ids):
+    """Reorders every list of a range result (lims int64 [nq + 1], scores fp32 [total], ids int64 [total]; any device) by score
+    descending, ties by ascending id - the order of `search`, whose 64-bit key it sorts by (order-preserving score bits, then the
+    complement of the id; ids below 2^32) - so that a list is a prefix of its query's full ranking.  Returns (scores, ids); lims holds."""
+    total = scores.numel()
+    if total == 0:
+        return scores, ids
+    bits = scores.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    order = torch.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)          # larger score -> larger value
+    key = ((order - 0x80000000) << 32) | (0xFFFFFFFF - ids)
+    counts = lims[1:] - lims[:-1]
+    query = torch.repeat_interleave(torch.arange(counts.numel(), device=scores.device), counts, output_size=total)
+    by_key = torch.argsort(key, descending=True)
+    perm = by_key[torch.argsort(query[by_key], stable=True)]
+    return scores[perm], ids[perm]
+
+
 class DenseIndexHIP:
     """Flat inner-product index resident in HBM (segments of [n, dim] rows, all fp32 or all fp16).
 
@@ -410,6 +427,39 @@ class DenseIndexHIP:
             _lib.check(self.lib.sr_dense_search(self._h, _ptr(queries), nq, int(k), _ptr(scores), _ptr(ids),
                                                 _lib.stream_ptr()), "sr_dense_search")
         return scores, ids
+
+    def range_search(self, queries, thresholds, sort=False):
+        """Every document scoring above a threshold (faiss's IndexFlatIP.range_search; include/sr_hip.h sr_dense_range_count / _fill):
+        queries fp32 cuda [nq, dim]; thresholds a float for all queries, or a tensor / array [nq].  Returns (lims int64 [nq + 1],
+        scores fp32 [total], ids int64 [total]) as cuda tensors: the documents of query q with score > thresholds[q] are entries
+        lims[q]:lims[q + 1], in (segment, row) order - ascending id for segments added in id order.  Scores are the exact chain of
+        `score_pairs` for every nq.  sort=True: each list by score descending, ties by ascending id (range_sort)."""
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
+        if not queries.is_cuda or queries.device != self.device:
+            raise ValueError(f"queries must live on {self.device}")
+        queries = queries.contiguous()
+        nq = queries.shape[0]
+        if isinstance(thresholds, (int, float)):
+            thr = torch.full((nq,), float(thresholds), dtype=torch.float32, device=self.device)
+        else:
+            thr = _to_dev(thresholds, torch.float32, self.device)
+            if thr.dim() != 1 or thr.numel() != nq:
+                raise ValueError(f"expected {nq} thresholds, got {tuple(thr.shape)}")
+        lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
+        total = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sr_dense_range_count(self._h, _ptr(queries), nq, _ptr(thr), _ptr(lims), ctypes.byref(total),
+                                                     _lib.stream_ptr()), "sr_dense_range_count")
+            n = total.value
+            scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
+            ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.sr_dense_range_fill(self._h, _ptr(queries), nq, _ptr(thr), _ptr(lims), _ptr(scores), _ptr(ids), n,
+                                                    _lib.stream_ptr()), "sr_dense_range_fill")
+        scores, ids = scores[:n], ids[:n]
+        if sort:
+            scores, ids = range_sort(lims, scores, ids)
+        return lims, scores, ids
 
     def score_pairs(self, queries, cand_indptr, cand_ids):
         """Exact scores of given (query, document) pairs: queries fp32 cuda [nq, dim]; the candidates of query q are
