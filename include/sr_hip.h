@@ -305,6 +305,36 @@ int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, con
                             const float* d_q_vals, int64_t nq, int k, float threshold,
                             const int64_t* d_subset, int64_t m, int64_t id_base, int64_t id_stride,
                             float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream);
+/* Range search: EVERY document whose score exceeds a per-query threshold, as CSR.  This is what the reference's scorer computes before
+ * select_topk cuts it (numba_score_float, scaling_retriever/indexer.py:324-344: the score array starts at zero, every query term is
+ * scatter-added in term order, then every document with score > threshold is returned in document order), with one threshold per query;
+ * the reference's scalar is the special case.  Two calls, because the size of the result is not known before the scores are:
+ *   sr_sparse_range_count  queries as for sr_sparse_search (term order = accumulation order, a repeated term counts each time, a term
+ *       id outside [0, n_terms) is an empty list), 0 <= nq < 2^24 per call (a larger nq: SR_ERR_INVALID); d_thresholds fp32 [nq] on the device.  Writes d_lims int64 [nq + 1] (device; lims[0] =
+ *       0, lims[q + 1] - lims[q] = the number of documents with score > thr[q]) and *total (host) = lims[nq]; it waits for the stream
+ *       once, to read those 8 bytes.  The handle keeps a table of 4 bytes per (query, chunk of doc tiles) - one 8 192-document tile per
+ *       chunk by default, counted against sr_sparse_index_set_workspace_limit: where 4 * nq * tiles exceeds the limit a chunk grows to
+ *       the smallest number of tiles that fits, SR_ERR_NOMEM with the byte count when one chunk per query does not - together with nq,
+ *       the chunk size and the total.
+ *   sr_sparse_range_fill   the same queries, thresholds and d_lims.  For query q, d_out_scores fp32 / d_out_ids int64 [capacity] hold at
+ *       lims[q] .. lims[q + 1] every hit and nothing else, in ascending document position d; ids = id_base + d * id_stride in int64
+ *       (id_base >= 0, id_stride >= 1; no 32-bit limit, no key is packed).  Needs a preceding sr_sparse_range_count on this handle with
+ *       the same nq, and capacity >= that count's total: anything else is SR_ERR_INVALID and nothing is written.  Queued on `stream`, no
+ *       read-back.  Do not interleave other range calls on the handle.  Every store is guarded by p < min(lims[q + 1], capacity): with
+ *       queries or thresholds other than the count's the lists are not meaningful, but no entry outside its query's segment of the
+ *       output (and none at or beyond capacity) is ever written.
+ * A hit is score > thr[q], strict, over every document position in [0, n_docs).  A document that shares no term with the query has score
+ * +0.0f and is a hit exactly when thr[q] < 0, as in the reference.  A NaN score or threshold is never a hit, +inf returns nothing, -inf
+ * every document with a score above -inf.  nq = 0 or n_docs = 0: lims all zero, total 0.  Scores: the term-serial chain
+ * of sr_sparse_search / sr_sparse_score_pairs - an unfused fp32 multiply then add, in the query's term order, from +0.0f - so a returned
+ * score equals sr_sparse_score_pairs of that pair bit for bit.  No global atomic takes part in placing a result: two calls return the
+ * same bytes.  Not offered: a range search under a subset or mask, doc-sharded, or on the certified scorer's 16-bit stage
+ * (DESIGN.md 4.15).                                                                                                                  */
+int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                          int64_t nq, const float* d_thresholds, int64_t* d_lims, int64_t* total, sr_stream stream);
+int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                         int64_t nq, const float* d_thresholds, const int64_t* d_lims, int64_t id_base, int64_t id_stride,
+                         float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream);
 int sr_sparse_index_destroy(sr_sparse_index* idx);
 /* Measurement hook as for the dense index; algorithmic bytes = 8 B per posting of the
  * query terms that falls in the launched doc tiles (computed on the device).       */

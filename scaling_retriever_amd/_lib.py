@@ -74,6 +74,9 @@ SIGNATURES = {
     "sr_sparse_score_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_sparse_search_subset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int64, c_int64,
                                         c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_sparse_range_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    "sr_sparse_range_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                     c_void_p, c_int64, c_void_p]),
     "sr_sparse_index_block_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
                                             ctypes.POINTER(c_int64)]),
     "sr_sparse_index_destroy": (c_int, [c_void_p]),

@@ -1,6 +1,7 @@
 // Dense range search (dense_range.hip): every document whose exact score exceeds a per-query threshold, as CSR.
 #pragma once
 #include "common.h"
+#include "range_scan.h"      // the (chunk, query) scan, shared with the sparse range search
 
 #define SR_RANGE_MAX_CHUNKS 1024   // rows of the (chunk, query) table: 4 KiB per query at most
 
@@ -27,5 +28,3 @@ struct DenseRangeArgs {
 static inline int dense_range_query_tile(int64_t nq) { return nq > 128 ? 256 : 128; }
 int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
 int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
-// table[c][q] := sum of table[c'][q] over c' < c (in place); lims[0] = 0, lims[q + 1] = hits of queries 0..q
-int launch_dense_range_scan(uint32_t* table, int n_chunks, int64_t nq, int64_t* d_lims, hipStream_t s);

@@ -338,7 +338,7 @@ static int launch_dense_range(const DenseRangeArgs& a, int n_chunks_seg, hipStre
 int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) { return launch_dense_range<false>(a, n_chunks_seg, s); }
 int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) { return launch_dense_range<true>(a, n_chunks_seg, s); }
 
-int launch_dense_range_scan(uint32_t* table, int n_chunks, int64_t nq, int64_t* d_lims, hipStream_t s) {
+int launch_range_scan(uint32_t* table, int n_chunks, int64_t nq, int64_t* d_lims, hipStream_t s) {
     hipLaunchKernelGGL(dense_range_scan_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, s, table, n_chunks, nq, d_lims);
     SR_CHECK_LAUNCH();
     hipLaunchKernelGGL(dense_range_lims_kernel, dim3(1), dim3(1024), 0, s, d_lims, nq);

@@ -1273,7 +1273,7 @@ extern "C" int sr_dense_range_count(sr_dense_index* idx, const float* d_queries,
         idx->prof.end(s, 2.0 * (double)nq * (double)seg.n * idx->dim, (double)seg.n * idx->dim * (double)sr_dtype_size(idx->row_dtype));
         chunk_base += n_seg;
     }
-    SR_TRY(launch_dense_range_scan(idx->range_tab, n_chunks, nq, d_lims, s));
+    SR_TRY(launch_range_scan(idx->range_tab, n_chunks, nq, d_lims, s));
     int64_t h_total = 0;
     SR_CHECK_HIP(hipMemcpyAsync(&h_total, d_lims + nq, 8, hipMemcpyDeviceToHost, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));

@@ -53,6 +53,11 @@ struct sr_sparse_index {
     int64_t n_cert_retries = 0;         // sub-batches of handed-back queries sent through the scorer again with the widest band
     uint8_t* pair_qflags = nullptr; int64_t pair_qflags_cap = 0;   // sr_sparse_score_pairs: per query, may the forward route serve it
     PairStatus* pair_status = nullptr;  // sr_sparse_score_pairs: the call's status words (pair_score.hip)
+    // sr_sparse_range_count / _fill (sparse_range.hip): the (chunk, query) table of the last count - hits per cell, turned into exclusive
+    // prefixes over the chunks by the scan - and what it was made for.  A chunk is range_chunk_tiles consecutive doc tiles
+    int32_t* range_tab = nullptr; int64_t range_tab_cap = 0;          // [range_chunks, range_nq] int32
+    int64_t range_nq = -1, range_total = 0;                           // range_nq = -1: no count to fill from
+    int range_chunk_tiles = 0, range_chunks = 0;
     std::mutex mu;
 };
 

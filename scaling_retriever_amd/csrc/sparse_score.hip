@@ -998,9 +998,12 @@ __global__ void sparse_count_postings_kernel(const int32_t* __restrict__ skip, i
 
 static void sparse_free_device(sr_sparse_index* idx) {
     void* ptrs[] = {idx->skip, idx->dense, idx->dense_slot, idx->plan_term, idx->plan_w, idx->plan_n, idx->plan_ok, idx->plan_bad,
-                    idx->plan_off, idx->plan_perm, idx->q_done};
+                    idx->plan_off, idx->plan_perm, idx->q_done, idx->range_tab};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    idx->range_tab = nullptr;
+    idx->range_tab_cap = 0;
+    idx->range_nq = -1;
     idx->skip = nullptr;
     idx->dense = nullptr;
     idx->dense_slot = nullptr;

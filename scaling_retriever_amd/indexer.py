@@ -745,9 +745,10 @@ class SparseRetrieval:
     def numba_score_float(inverted_index_ids, inverted_index_floats, indexes_to_retrieve, query_values, threshold,
                           size_collection):
         """Same signature/returns as the reference: (doc indexes with score > threshold ascending int64,
-        NEGATED scores fp32), every such document.  Scores come from the HIP scorer with k = the number of documents
-        that can score at all (min(size_collection, summed posting-list lengths of the query terms)), so use
-        SparseRetrieval.retrieve for bulk work; this entry point exists for drop-in callers."""
+        NEGATED scores fp32), every such document - documents without a common term included when the threshold is negative, as in
+        the reference, whose score array starts at zero.  The list is one range search on the HIP index (SparseIndexHIP.range_search:
+        count, scan, fill), which already comes in document order; use SparseRetrieval.retrieve or range_search for bulk work, this
+        entry point exists for drop-in callers."""
         cache = SparseRetrieval._static_cache
         if cache is not None and cache[0] is inverted_index_ids and cache[3] == size_collection:
             hit = cache[1]
@@ -764,15 +765,8 @@ class SparseRetrieval:
             hit = SparseIndexHIP(*_csr_sorted_by_doc(indptr, ids, vals, dev), size_collection, device=dev)
             SparseRetrieval._static_cache = (inverted_index_ids, hit, V, size_collection)
         cols = np.asarray(indexes_to_retrieve, np.int32)
-        postings = sum(len(inverted_index_ids[int(t)]) for t in cols if int(t) in inverted_index_ids)
-        k = max(1, min(int(size_collection), postings))
-        s, i, c = hit.search(np.array([0, len(cols)], np.int64), cols, np.asarray(query_values, np.float32), k,
-                             threshold=float(threshold))
-        c = int(c.item())
-        idx = i[0, :c].cpu().numpy()
-        sc = s[0, :c].cpu().numpy()
-        order = np.argsort(idx, kind="stable")
-        return idx[order].astype(np.int64), -sc[order]
+        _, sc, idx = hit.range_search(np.array([0, len(cols)], np.int64), cols, np.asarray(query_values, np.float32), float(threshold))
+        return idx.cpu().numpy(), -sc.cpu().numpy()
 
     QUERY_GROUP_ROWS = 2048      # rows per encode_batches call: the [rows, V] fp32 reps of a group live in HBM (1 GB at V = 128 256)
 
@@ -819,6 +813,29 @@ class SparseRetrieval:
         if getattr(self, "_doc_table", None) is None:
             self._doc_table = IdTable(_doc_id_table(self.doc_ids, self.sparse_index.nb_docs()))
         return self._doc_table
+
+    def range_search(self, sparse_query_vecs, thresholds=0., sort=True):
+        """Every document scoring above a threshold - the full list of numba_score_float (indexer.py:324-344) for a whole query set,
+        the counterpart of DenseFlatIndexer.range_search: (list of collection-id lists, list of fp32 score arrays), one pair per query,
+        of the documents with score > thresholds (a float, or one value per query).  sparse_query_vecs as _generate_query_vecs returns
+        them (QueryCSR) or the reference's list of (cols, vals) pairs.  sort=True: best first, ties by document position, so a list is
+        a prefix of what retrieve ranks; False: document order.  The ids go through doc_id_table in one numpy take.
+        A document without any posting has no collection id (doc_ids.pkl does not list it; the reference's doc_ids[id_] raises
+        KeyError for it).  It scores 0.0 and so passes a negative threshold: such documents are left out of the lists here, their
+        placeholders of doc_id_table never come back.  SparseIndexHIP.range_search returns them, by position."""
+        q = _as_query_csr(sparse_query_vecs, self._dev)
+        lims, scores, positions = self.hip_index.range_search(q.row_ptr, q.cols, q.vals, thresholds, sort=sort)
+        lims, scores, positions = lims.cpu().numpy(), scores.cpu().numpy(), positions.cpu().numpy()
+        table = self.doc_id_table()
+        if len(self.doc_ids) < table.n:                      # some document has no id: drop its entries, list by list
+            has_id = np.zeros(table.n, dtype=bool)
+            has_id[np.fromiter(self.doc_ids.keys(), dtype=np.int64, count=len(self.doc_ids))] = True
+            keep = has_id[positions]
+            lims = np.concatenate([[0], np.cumsum(keep)])[lims]
+            scores, positions = scores[keep], positions[keep]
+        flat = table.take(positions)
+        return ([flat[a:b].tolist() for a, b in zip(lims[:-1], lims[1:])],
+                [scores[a:b] for a, b in zip(lims[:-1], lims[1:])])
 
     def allowed_subset(self, allowed_ids):
         """Collection ids (any order, duplicates allowed) -> the sorted unique document positions of the inverted index as an int64
@@ -928,6 +945,10 @@ class ShardedSparseRetrieval(SparseRetrieval):
             with open(os.path.join(f"{self._base_dir}_{r}", "doc_ids.pkl"), "rb") as f:
                 ids.update(pickle.load(f))
         return ids
+
+    def range_search(self, sparse_query_vecs, thresholds=0., sort=True):
+        raise NotImplementedError("ShardedSparseRetrieval.range_search: a range search is not offered on a doc-sharded index; "
+                                  "search one merged index with SparseRetrieval instead")
 
     def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when

@@ -626,6 +626,44 @@ class SparseIndexHIP:
                                                  _ptr(counts), _lib.stream_ptr()), "sr_sparse_search")
         return scores, ids, counts
 
+    def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False):
+        """Every document scoring above a threshold - the full list of numba_score_float (scaling_retriever/indexer.py:324-344;
+        include/sr_hip.h sr_sparse_range_count / _fill): queries as CSR as for `search`; thresholds a float for all queries, or a
+        tensor / array [nq].  Returns (lims int64 [nq + 1], scores fp32 [total], ids int64 [total]) as cuda tensors: the documents of
+        query q with score > thresholds[q] are entries lims[q]:lims[q + 1], in ascending document position, ids = id_base + position *
+        id_stride.  A document without a common term scores 0.0 and is returned exactly under a negative threshold.  Scores are the
+        chain of `score_pairs`.  sort=True: each list by score descending, ties by ascending id (range_sort)."""
+        q_indptr = _to_dev(q_indptr, torch.int64, self.device)
+        q_cols = _to_dev(q_cols, torch.int32, self.device)
+        q_vals = _to_dev(q_vals, torch.float32, self.device)
+        nq = q_indptr.numel() - 1
+        if q_cols.numel() == 0:
+            q_cols = torch.zeros(1, dtype=torch.int32, device=self.device)
+            q_vals = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if isinstance(thresholds, (int, float, np.floating, np.integer)):
+            thr = torch.full((max(1, nq),), float(thresholds), dtype=torch.float32, device=self.device)
+        else:
+            thr = _to_dev(thresholds, torch.float32, self.device)
+            if thr.dim() != 1 or thr.numel() != nq:
+                raise ValueError(f"expected {nq} thresholds, got {tuple(thr.shape)}")
+        if sort and int(id_base) + (self.n_docs - 1) * int(id_stride) >= 1 << 32:
+            raise ValueError("sort=True orders by the search's 64-bit key, which holds ids below 2^32; sort the lists of larger ids yourself")
+        lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
+        total = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sr_sparse_range_count(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
+                                                      ctypes.byref(total), _lib.stream_ptr()), "sr_sparse_range_count")
+            n = total.value
+            scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
+            ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
+            _lib.check(self.lib.sr_sparse_range_fill(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
+                                                     int(id_base), int(id_stride), _ptr(scores), _ptr(ids), n, _lib.stream_ptr()),
+                       "sr_sparse_range_fill")
+        scores, ids = scores[:n], ids[:n]
+        if sort:
+            scores, ids = range_sort(lims, scores, ids)
+        return lims, scores, ids
+
     def score_pairs(self, q_indptr, q_cols, q_vals, cand_indptr, cand_ids):
         """Exact scores of given (query, document) pairs: queries as for `search`, candidates as for DenseIndexHIP.score_pairs (ids =
         document positions).  Returns fp32 cuda [total]: the reference's term-serial chain, no threshold, 0.0 where nothing matches

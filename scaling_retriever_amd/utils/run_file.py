@@ -109,6 +109,11 @@ class IdTable:
             return self.fixed[i].decode("ascii")
         return json.loads(b'"' + self.blob[self.off[i]:self.off[i + 1]] + b'"')
 
+    def take(self, positions):
+        """The keys themselves (not their str) at an int array of positions, as a numpy array: ints for an int64 table, the
+        caller's objects otherwise."""
+        return np.asarray(self._keys)[positions]
+
     def keys_of(self, positions):
         """[str] for an int array of positions."""
         if self.kind == "i64":
