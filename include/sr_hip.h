@@ -461,6 +461,11 @@ int sr_model_finalize(sr_model* m);
  * lm_head if the model has one; *n = their number (4 num_layers + has_lm_head), min(capacity, *n) of them are written to the
  * host array out.  fp32_planes = 16: 2 or 3 per matrix (see sr_model_finalize); 2 / 3: 3 / 6 everywhere; 0: 0.          */
 int sr_model_weight_segments(sr_model* m, int32_t* out, int64_t capacity, int64_t* n);
+/* fp32_planes = 16: which layers of a finalized model run the fused SwiGLU split (the gate-up GEMM writes the down_proj's fp16
+ * planes under a row scale from the bound |xn|^2 max_j |w_gate_j||w_up_j|): out[i] = 1, or 0 for a layer whose weights make that
+ * bound loose (hidden_size max_j p_j >= 2^16 median_j p_j, p_j = |w_gate_j||w_up_j|) and which takes the fp32 SwiGLU output + row
+ * split instead.  *n = num_layers (0 for any other fp32_planes); min(capacity, *n) values are written to the host array out.   */
+int sr_model_fused_act_layers(sr_model* m, int32_t* out, int64_t capacity, int64_t* n);
 /* d_input_ids / d_attention_mask: int64 [B, L] on device (the tokenizer
  * collator's output, data_collator.py:177-190).  d_out: fp32 [B, hidden].    */
 int sr_encode_dense(sr_model* m, const int64_t* d_input_ids, const int64_t* d_attention_mask,
@@ -577,6 +582,31 @@ int sr_gemm_bf16(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t
  * scaled by powers of two, d_a_scale [M] / d_w_scale [N] the inverse scales; C fp32 [M, N] += (A W^T) a_scale[m] w_scale[n]. */
 int sr_gemm_f16_scaled(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, const float* d_a_scale,
                        const float* d_w_scale, float* d_C, sr_stream stream);
+/* Test-only hooks: the other launches of the fp16-plane layer loop, each with the arguments the encoder fills.  Every call
+ * validates its arguments before it touches a device (SR_ERR_INVALID).
+ * sr_rows_split_f16: rows of d_src fp32 [T, K] -> d_planes fp16 [T, nseg K] = [f1 | f0 | f0] (nseg = 3) or [f1 | f0] (2) of
+ *   row * sc, sc the power of two that puts the row's largest magnitude into [2^14, 2^15) (1 for a zero row), d_a_inv [T] = 1 / sc.
+ *   d_norm_w [K] (or NULL): the row is RMS-normalised first, y = (x rsqrt(mean(x^2) + eps)) w.  d_embed + d_tok_id (with d_norm_w
+ *   only): row t is gathered from d_embed[d_tok_id[t]] and written back to d_src.  d_gu_cmax (device float, or NULL) with
+ *   d_act_sc / d_act_inv [T]: the forward and inverse power-of-two scale of the row's SwiGLU output from the bound
+ *   B = |y|^2 cmax 1.02, B act_sc in [2^14, 2^15).  K % 4 == 0; K = 2048 / 4096 / 8192 run the register kernels.
+ * sr_gu_cmax_f16: *d_cmax = max_j |w_gate_j||w_up_j| 1.001 over the I feature pairs of an interleaved gate/up matrix (gate and up
+ *   rows alternate in blocks of 16) given as fp16 plane segments [2 I, nseg K] ([w0 | w1 | w0] or [w0 | w0]) and inverse row scales.
+ * sr_gemm_f16_planes: the fp16-plane GEMM with any of its epilogues, K = a_nseg x features (a_nseg 2 or 3 picks the 256 x 256 loop
+ *   as in the encoder).  epilogue 9: QKV + bias + RoPE, C fp32 [M, N] (d_pos, tables, n_rope, head_dim, optional d_bias);
+ *   10: C fp32 [M, N] += y (= sr_gemm_f16_scaled);  11: SwiGLU, C fp32 [M, N/2];  12: per-sequence max, C fp32 [n_seq, N]
+ *   pre-zeroed, d_seq_of [M] ascending, -2 = masked row;  13: SwiGLU scaled by d_out_scale[m] and written as fp16 planes
+ *   C [M, out_nseg N/2] = [f1 | f0 | f0] or [f1 | f0].  Arguments an epilogue does not use are ignored.                        */
+int sr_rows_split_f16(float* d_src, const float* d_embed, const int32_t* d_tok_id, const float* d_norm_w, float eps,
+                      int32_t T, int32_t K, int32_t nseg, void* d_planes, float* d_a_inv, const float* d_gu_cmax,
+                      float* d_act_sc, float* d_act_inv, sr_stream stream);
+int sr_gu_cmax_f16(const void* d_wgu_planes, const float* d_wgu_inv, int32_t I, int32_t K, int32_t nseg, float* d_cmax,
+                   sr_stream stream);
+int sr_gemm_f16_planes(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t a_nseg,
+                       const float* d_a_scale, const float* d_w_scale, void* d_C, const int32_t* d_pos,
+                       const float* d_rope_cos, const float* d_rope_sin, int32_t n_rope, int32_t head_dim,
+                       const float* d_bias, const int32_t* d_seq_of, const float* d_out_scale, int32_t out_nseg,
+                       sr_stream stream);
 int sr_gemm_qkv_rope(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, void* d_C,
                      const int32_t* d_pos, const float* d_rope_cos, const float* d_rope_sin,
                      int32_t n_rope, int32_t head_dim, sr_stream stream);

@@ -118,3 +118,56 @@ extern "C" int sr_gemm_f16_scaled(const void* d_A, const void* d_W, int32_t M, i
     g.A = (const bf16_t*)d_A; g.W = (const bf16_t*)d_W; g.M = M; g.N = N; g.K = K; g.C = d_C; g.a_scale = d_a_scale; g.w_scale = d_w_scale;
     return launch_gemm_bf16(EPI_RESID_F32_H, g, (hipStream_t)stream);
 }
+
+// The other launches of the fp16-plane layer loop (model_forward, encoder.hip), exported for tests/test_fp32_planes_gpu.py: thin
+// calls into the launch functions with the arguments the encoder fills.  Everything is validated before a device is touched.
+extern "C" int sr_rows_split_f16(float* d_src, const float* d_embed, const int32_t* d_tok_id, const float* d_norm_w, float eps,
+                                 int32_t T, int32_t K, int32_t nseg, void* d_planes, float* d_a_inv, const float* d_gu_cmax,
+                                 float* d_act_sc, float* d_act_inv, sr_stream stream) {
+    SR_REQUIRE(d_src && d_planes && d_a_inv, "sr_rows_split_f16: null pointer");
+    SR_REQUIRE((d_embed == nullptr) == (d_tok_id == nullptr), "sr_rows_split_f16: pass both d_embed and d_tok_id or neither");
+    SR_REQUIRE(!d_embed || d_norm_w, "sr_rows_split_f16: the embedding gather is part of the norm kernel and needs d_norm_w");
+    SR_REQUIRE(!d_gu_cmax || (d_act_sc && d_act_inv), "sr_rows_split_f16: d_gu_cmax needs d_act_sc and d_act_inv");
+    SR_REQUIRE(nseg == 2 || nseg == 3, "sr_rows_split_f16: nseg %d is not 2 or 3", nseg);
+    SR_REQUIRE(T >= 0 && K > 0 && K % 4 == 0, "sr_rows_split_f16: bad sizes T=%d K=%d (K must be a multiple of 4)", T, K);
+    SR_REQUIRE((uintptr_t)d_src % 16 == 0 && (uintptr_t)d_embed % 16 == 0 && (uintptr_t)d_norm_w % 16 == 0 && (uintptr_t)d_planes % 8 == 0,
+               "sr_rows_split_f16: d_src, d_embed and d_norm_w must be 16-byte aligned, d_planes 8-byte aligned");
+    if (T == 0) return SR_OK;
+    return launch_rows_split_f16(d_src, d_embed, d_tok_id, d_norm_w, (bf16_t*)d_planes, d_a_inv, T, K, eps, nseg, d_gu_cmax, d_act_sc,
+                                 d_act_inv, (hipStream_t)stream);
+}
+
+extern "C" int sr_gu_cmax_f16(const void* d_wgu_planes, const float* d_wgu_inv, int32_t I, int32_t K, int32_t nseg, float* d_cmax,
+                              sr_stream stream) {
+    SR_REQUIRE(d_wgu_planes && d_wgu_inv && d_cmax, "sr_gu_cmax_f16: null pointer");
+    SR_REQUIRE(nseg == 2 || nseg == 3, "sr_gu_cmax_f16: nseg %d is not 2 or 3", nseg);
+    SR_REQUIRE(I > 0 && I % 16 == 0 && K > 0, "sr_gu_cmax_f16: bad sizes I=%d K=%d (gate / up rows alternate in blocks of 16)", I, K);
+    return launch_gu_cmax((const bf16_t*)d_wgu_planes, d_wgu_inv, I, K, nseg, d_cmax, (hipStream_t)stream);
+}
+
+extern "C" int sr_gemm_f16_planes(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t a_nseg,
+                                  const float* d_a_scale, const float* d_w_scale, void* d_C, const int32_t* d_pos,
+                                  const float* d_rope_cos, const float* d_rope_sin, int32_t n_rope, int32_t head_dim,
+                                  const float* d_bias, const int32_t* d_seq_of, const float* d_out_scale, int32_t out_nseg,
+                                  sr_stream stream) {
+    SR_REQUIRE(d_A && d_W && d_C && d_a_scale && d_w_scale, "sr_gemm_f16_planes: null pointer");
+    SR_REQUIRE(epilogue == EPI_QKV_ROPE_F32_H || epilogue == EPI_RESID_F32_H || epilogue == EPI_SWIGLU_F32_H || epilogue == EPI_SEGMAX_H ||
+                   epilogue == EPI_SWIGLU_SPLIT_H, "sr_gemm_f16_planes: unknown epilogue %d (9 .. 13)", epilogue);
+    SR_REQUIRE(a_nseg == 2 || a_nseg == 3, "sr_gemm_f16_planes: a_nseg %d is not 2 or 3", a_nseg);
+    SR_REQUIRE(M >= 0 && N > 0 && K > 0 && K % 64 == 0 && K % a_nseg == 0,
+               "sr_gemm_f16_planes: bad shape M=%d N=%d K=%d (K = a_nseg x features, a multiple of 64)", M, N, K);
+    SR_REQUIRE(epilogue != EPI_QKV_ROPE_F32_H || (d_pos && d_rope_cos && d_rope_sin), "sr_gemm_f16_planes: epilogue 9 needs d_pos and both rope tables");
+    SR_REQUIRE(epilogue == EPI_QKV_ROPE_F32_H || !d_bias, "sr_gemm_f16_planes: only epilogue 9 takes a bias");
+    SR_REQUIRE(epilogue != EPI_SEGMAX_H || d_seq_of, "sr_gemm_f16_planes: epilogue 12 needs d_seq_of");
+    SR_REQUIRE(epilogue != EPI_SWIGLU_SPLIT_H || d_out_scale, "sr_gemm_f16_planes: epilogue 13 needs d_out_scale");
+    SR_REQUIRE(epilogue != EPI_SWIGLU_SPLIT_H || out_nseg == 2 || out_nseg == 3, "sr_gemm_f16_planes: out_nseg %d is not 2 or 3", out_nseg);
+    GemmArgs g{};
+    g.A = (const bf16_t*)d_A; g.W = (const bf16_t*)d_W; g.M = M; g.N = N; g.K = K; g.a_nseg = a_nseg; g.C = d_C;
+    g.a_scale = d_a_scale; g.w_scale = d_w_scale;
+    if (epilogue == EPI_QKV_ROPE_F32_H) {
+        g.pos = d_pos; g.rope_cos = d_rope_cos; g.rope_sin = d_rope_sin; g.n_rope = n_rope; g.head_dim = head_dim; g.bias = d_bias;
+    }
+    if (epilogue == EPI_SEGMAX_H) { g.seq_of = d_seq_of; g.out_ld = N; }
+    if (epilogue == EPI_SWIGLU_SPLIT_H) { g.out_scale = d_out_scale; g.out_nseg = out_nseg; }
+    return launch_gemm_bf16((GemmEpilogue)epilogue, g, (hipStream_t)stream);
+}

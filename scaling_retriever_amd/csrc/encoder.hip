@@ -18,6 +18,7 @@
 // holed masks stay literal (pad query rows are computed, masked as keys).
 #include "kernels.h"
 #include <math.h>
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -570,6 +571,20 @@ __global__ __launch_bounds__(256) void gu_cmax_kernel(const bf16_t* __restrict__
     if (lane == 0) atomicMax(reinterpret_cast<unsigned int*>(cmax), __float_as_uint(sqrtf(n2[0]) * sqrtf(n2[1]) * 1.001f));
 }
 
+int launch_gu_cmax(const bf16_t* wgu_s, const float* wgu_i, int I, int K, int nseg, float* cmax, hipStream_t s) {
+    SR_CHECK_HIP(hipMemsetAsync(cmax, 0, 4, s));
+    hipLaunchKernelGGL(gu_cmax_kernel, dim3((unsigned)ceil_div64(I, 4)), dim3(256), 0, s, wgu_s, wgu_i, I, K, nseg, cmax);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+int launch_rows_split_f16(float* x, const float* embed, const int* tok, const float* w, bf16_t* xs, float* inv, int T, int K, float eps,
+                          int nseg, const float* gu_cmax, float* act_sc, float* act_inv, hipStream_t s) {
+    launch_rows_split_h(x, embed, tok, w, xs, inv, T, K, eps, nseg, s, gu_cmax, act_sc, act_inv);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
 // ---- LoRA merge: W += scale * B @ A -----------------------------------------------------
 __global__ void lora_merge_kernel(float* __restrict__ W, const float* __restrict__ A, const float* __restrict__ Bm,
                                   int64_t out_f, int64_t in_f, int r, float scale) {
@@ -639,6 +654,9 @@ struct LayerW {
     // fp16-plane regime: inverse power-of-two scale of every weight row
     float *wqkv_i = nullptr, *wo_i = nullptr, *wgu_i = nullptr, *wdown_i = nullptr;
     float* gu_cmax = nullptr;   // fp16-plane regime: max_j |w_gate_j||w_up_j| (device float), see gu_cmax_kernel
+    // fp16-plane regime, decided by sr_model_finalize: the gate-up GEMM writes the down_proj's planes itself (EPI_SWIGLU_SPLIT_H).
+    // false = the row bound is loose for these weights: fp32 SwiGLU output + row split, which scales by the row's maximum
+    bool fused_act = true;
     // fp16-plane regime: K segments of wqkv_s, wo_s, wgu_s, wdown_s - 3 = [g0 | g1 | g0], 2 = [g0 | g0] (g1 all zero, dropped by
     // sr_model_finalize); the activations feeding each GEMM are split to the same count
     int qkv_seg = 3, o_seg = 3, gu_seg = 3, down_seg = 3;
@@ -992,15 +1010,40 @@ extern "C" int sr_model_finalize(sr_model* m) {
             }
             if (c.has_lm_head) SR_TRY(pack_f16_weights(m->lm_head_s, m->lm_head_seg, nz[4 * c.num_layers] != 0, V, H));
         }
-        // row bound of every layer's SwiGLU output (EPI_SWIGLU_SPLIT_H)
-        for (int i = 0; i < c.num_layers; ++i) {
-            LayerW& l = m->layers[i];
-            if (!l.gu_cmax) SR_CHECK_HIP(hipMalloc((void**)&l.gu_cmax, 4));
-            SR_CHECK_HIP(hipMemsetAsync(l.gu_cmax, 0, 4, nullptr));
-            hipLaunchKernelGGL(gu_cmax_kernel, dim3((unsigned)ceil_div64(I, 4)), dim3(256), 0, nullptr, l.wgu_s, l.wgu_i, (int)I, (int)H,
-                               l.gu_seg, l.gu_cmax);
-        }
-        SR_CHECK_LAUNCH();
+        // row bound of every layer's SwiGLU output (EPI_SWIGLU_SPLIT_H), and whether the layer may use it.  The bound B = |xn|^2 cmax
+        // fixes the row's scale before the GEMM runs; the low fp16 plane has an absolute floor of 2^-39 B, which stays below the
+        // 2^-22 of the split relative to the row's largest element r only while B / r <= 2^17.  Typically r ~ |xn|^2 median_j(p_j) / H
+        // with p_j = |w_gate_j||w_up_j| (the cosines of a random direction are ~ H^-1/2), so B / r ~ H cmax / median(p): a layer runs
+        // fused while that is below 2^16 (one bit for silu(g) ~ g / 2), else unfused.  The median comes from up to 256
+        // evenly spaced pairs, each through gu_cmax_kernel on its own two rows (I = 1 at the pair's row of its 32-row block).
+        const int ns = (int)(I < 256 ? I : 256);
+        float* d_p = nullptr;
+        SR_CHECK_HIP(hipMalloc((void**)&d_p, (size_t)(ns + 1) * 4));
+        std::vector<float> p((size_t)ns + 1);
+        auto decide = [&]() -> int {
+            for (int i = 0; i < c.num_layers; ++i) {
+                LayerW& l = m->layers[i];
+                if (!l.gu_cmax) SR_CHECK_HIP(hipMalloc((void**)&l.gu_cmax, 4));
+                SR_TRY(launch_gu_cmax(l.wgu_s, l.wgu_i, (int)I, (int)H, l.gu_seg, l.gu_cmax, nullptr));
+                SR_CHECK_HIP(hipMemsetAsync(d_p, 0, (size_t)ns * 4, nullptr));
+                for (int k = 0; k < ns; ++k) {
+                    const int64_t j = (int64_t)k * I / ns, row = (j / 16) * 32 + j % 16;
+                    hipLaunchKernelGGL(gu_cmax_kernel, dim3(1), dim3(256), 0, nullptr, l.wgu_s + row * l.gu_seg * H, l.wgu_i + row, 1, (int)H,
+                                       l.gu_seg, d_p + k);
+                }
+                SR_CHECK_LAUNCH();
+                SR_CHECK_HIP(hipMemcpyAsync(d_p + ns, l.gu_cmax, 4, hipMemcpyDeviceToDevice, nullptr));
+                SR_CHECK_HIP(hipMemcpy(p.data(), d_p, (size_t)(ns + 1) * 4, hipMemcpyDeviceToHost));
+                const float cmax = p[(size_t)ns];
+                std::nth_element(p.begin(), p.begin() + ns / 2, p.begin() + ns);
+                const float med = p[(size_t)(ns / 2)];
+                l.fused_act = !(cmax > 0.f) || (float)H * cmax < 65536.f * med;
+            }
+            return SR_OK;
+        };
+        const int rc = decide();
+        (void)hipFree(d_p);
+        SR_TRY(rc);
     }
     SR_CHECK_HIP(hipDeviceSynchronize());
     m->finalized = true;
@@ -1022,6 +1065,16 @@ extern "C" int sr_model_weight_segments(sr_model* m, int32_t* out, int64_t capac
     *n = (int64_t)v.size();
     SR_REQUIRE(capacity >= 0 && (capacity == 0 || out), "sr_model_weight_segments: bad output buffer");
     for (int64_t i = 0; i < capacity && i < (int64_t)v.size(); ++i) out[i] = v[(size_t)i];
+    return SR_OK;
+}
+
+extern "C" int sr_model_fused_act_layers(sr_model* m, int32_t* out, int64_t capacity, int64_t* n) {
+    SR_REQUIRE(m && n, "sr_model_fused_act_layers: null argument");
+    SR_REQUIRE(m->finalized, "sr_model_fused_act_layers: sr_model_finalize was not called");
+    const bool f16p = m->cfg.fp32_planes == SR_FP32_PLANES_F16;
+    *n = f16p ? (int64_t)m->layers.size() : 0;
+    SR_REQUIRE(capacity >= 0 && (capacity == 0 || out), "sr_model_fused_act_layers: bad output buffer");
+    for (int64_t i = 0; i < capacity && i < *n; ++i) out[i] = m->layers[(size_t)i].fused_act ? 1 : 0;
     return SR_OK;
 }
 
@@ -1118,9 +1171,11 @@ static int model_forward(sr_model* m, const int64_t* d_ids, const int64_t* d_mas
         };
         // dev switch SR_FP32_FUSED_ACT=0: SwiGLU output as fp32 + a separate row-split pass (A/B, and the reference of the test)
         const char* env_fa = sr_dev_getenv("SR_FP32_FUSED_ACT");
-        const bool fused_act = m->layers[0].gu_cmax && !(env_fa && *env_fa == '0');
+        // (= 1: the fused route in every layer, whatever sr_model_finalize decided - to measure what the fallback rule avoids)
+        const bool fused_on = !(env_fa && *env_fa == '0'), fused_all = env_fa && *env_fa == '1';
         for (int li = 0; li < c.num_layers; ++li) {
             LayerW& l = m->layers[li];
+            const bool fused_act = fused_on && l.gu_cmax && (l.fused_act || fused_all);      // per layer: sr_model_finalize
             split_rows(m->x, li == 0 ? m->embed : (const float*)nullptr, li == 0 ? m->tok_id : (const int*)nullptr, l.ln1, m->xs, m->xs_i, H,
                        l.qkv_seg);
             GemmArgs g{};

@@ -82,6 +82,13 @@ struct GemmArgs {
 // A/W/C 16-byte aligned.
 int launch_gemm_bf16(GemmEpilogue epi, const GemmArgs& g, hipStream_t s);
 
+// fp16-plane regime, for the test hooks of api.hip (the encoder launches the same kernels, encoder.hip): norm + split of fp32 rows
+// [T, K] into [f1 | f0 | f0] / [f1 | f0] plane segments + inverse row scales, and the gate/up bound max_j |w_gate_j||w_up_j|
+// (cmax is zeroed first)
+int launch_rows_split_f16(float* x, const float* embed, const int* tok, const float* w, bf16_t* xs, float* inv, int T, int K, float eps,
+                          int nseg, const float* gu_cmax, float* act_sc, float* act_inv, hipStream_t s);
+int launch_gu_cmax(const bf16_t* wgu_s, const float* wgu_i, int I, int K, int nseg, float* cmax, hipStream_t s);
+
 struct AttnArgs {
     const bf16_t* qkv;      // [T, (nh + 2*nkv) * hd] packed tokens, q heads then k heads then v heads
     bf16_t* out;            // [T, nh * hd]

@@ -405,6 +405,18 @@ class HipLlamaBackbone(torch.nn.Module):
         _lib.check(self._lib.sr_model_weight_segments(self._h, out, n.value, ctypes.byref(n)), "sr_model_weight_segments")
         return [int(v) for v in out[:n.value]]
 
+    def fused_act_layers(self):
+        """fp16 planes: per layer, True if the gate-up GEMM writes the down_proj's planes itself (the default), False if
+        sr_model_finalize found the SwiGLU row bound loose for the layer's weights and it runs the fp32 output + row split
+        (sr_model_fused_act_layers).  Empty for the other plane modes."""
+        if self._h is None:
+            raise _lib.SrHipError("the model has no engine yet (call .to(device) first)")
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.sr_model_fused_act_layers(self._h, None, 0, ctypes.byref(n)), "sr_model_fused_act_layers")
+        out = (ctypes.c_int32 * max(n.value, 1))()
+        _lib.check(self._lib.sr_model_fused_act_layers(self._h, out, n.value, ctypes.byref(n)), "sr_model_fused_act_layers")
+        return [bool(v) for v in out[:n.value]]
+
     def __del__(self):
         try:
             if self._h is not None and self._lib is not None:

@@ -58,6 +58,57 @@ def test_attention_f32_hook_validates_before_it_launches():
         assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
 
 
+def test_fp16_plane_hooks_validate_before_they_launch():
+    """sr_rows_split_f16, sr_gu_cmax_f16 and sr_gemm_f16_planes reject what they cannot run with SR_ERR_INVALID before anything
+    touches a device: the pointers below are never dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(4096)
+
+    def split(**kw):
+        a = dict(dict(src=p, embed=None, tok=None, w=p, eps=1e-5, T=4, K=64, nseg=3, planes=p, inv=p, cmax=None, sc=None, si=None), **kw)
+        return lib.sr_rows_split_f16(a["src"], a["embed"], a["tok"], a["w"], a["eps"], a["T"], a["K"], a["nseg"], a["planes"], a["inv"],
+                                     a["cmax"], a["sc"], a["si"], None)
+    for change, text in [(dict(src=None), b"null pointer"), (dict(planes=None), b"null pointer"), (dict(inv=None), b"null pointer"),
+                         (dict(embed=p), b"both d_embed and d_tok_id"), (dict(tok=p), b"both d_embed and d_tok_id"),
+                         (dict(embed=p, tok=p, w=None), b"needs d_norm_w"), (dict(cmax=p), b"needs d_act_sc"),
+                         (dict(cmax=p, sc=p), b"needs d_act_sc"), (dict(nseg=1), b"nseg 1"), (dict(nseg=4), b"nseg 4"),
+                         (dict(K=66), b"multiple of 4"), (dict(K=0), b"bad sizes"), (dict(T=-1), b"bad sizes"),
+                         (dict(src=ctypes.c_void_p(4100)), b"aligned"), (dict(planes=ctypes.c_void_p(4100)), b"aligned")]:
+        rc = split(**change)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
+    assert split(T=0) == _lib.SR_OK
+
+    for args, text in [((None, p, 32, 64, 3, p), b"null pointer"), ((p, None, 32, 64, 3, p), b"null pointer"),
+                       ((p, p, 32, 64, 3, None), b"null pointer"), ((p, p, 32, 64, 4, p), b"nseg 4"), ((p, p, 32, 64, 0, p), b"nseg 0"),
+                       ((p, p, 24, 64, 3, p), b"bad sizes"), ((p, p, 32, 0, 3, p), b"bad sizes")]:
+        rc = lib.sr_gu_cmax_f16(*args, None)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (args, rc, lib.sr_last_error())
+
+    def gemm(**kw):
+        a = dict(dict(A=p, W=p, M=8, N=128, K=192, epi=10, a_nseg=3, a_sc=p, w_sc=p, C=p, pos=None, cos=None, sin=None, n_rope=0, hd=64,
+                      bias=None, seq=None, osc=None, out_nseg=0), **kw)
+        return lib.sr_gemm_f16_planes(a["A"], a["W"], a["M"], a["N"], a["K"], a["epi"], a["a_nseg"], a["a_sc"], a["w_sc"], a["C"],
+                                      a["pos"], a["cos"], a["sin"], a["n_rope"], a["hd"], a["bias"], a["seq"], a["osc"], a["out_nseg"], None)
+    for change, text in [(dict(A=None), b"null pointer"), (dict(W=None), b"null pointer"), (dict(C=None), b"null pointer"),
+                         (dict(a_sc=None), b"null pointer"), (dict(w_sc=None), b"null pointer"),
+                         (dict(epi=8), b"unknown epilogue 8"), (dict(epi=14), b"unknown epilogue 14"), (dict(epi=1), b"unknown epilogue 1"),
+                         (dict(a_nseg=0), b"a_nseg 0"), (dict(a_nseg=4), b"a_nseg 4"), (dict(K=200), b"bad shape"),
+                         (dict(K=128), b"bad shape"), (dict(M=-1), b"bad shape"), (dict(N=0), b"bad shape"),
+                         (dict(epi=9), b"needs d_pos"), (dict(epi=9, pos=p, cos=p), b"needs d_pos"), (dict(bias=p), b"takes a bias"),
+                         (dict(epi=12), b"needs d_seq_of"), (dict(epi=13, out_nseg=3), b"needs d_out_scale"),
+                         (dict(epi=13, osc=p, out_nseg=1), b"out_nseg 1"), (dict(epi=13, osc=p, out_nseg=4), b"out_nseg 4"),
+                         (dict(epi=9, pos=p, cos=p, sin=p, hd=96, n_rope=96), b"head_dim 96"),
+                         (dict(epi=9, pos=p, cos=p, sin=p, hd=64, n_rope=32), b"bad rope arguments"),
+                         (dict(epi=11, N=144), b"multiple of 16 (32 for SwiGLU)")]:
+        rc = gemm(**change)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
+    assert gemm(M=0) == _lib.SR_OK
+    n = ctypes.c_int64(0)
+    rc = lib.sr_model_fused_act_layers(None, None, 0, ctypes.byref(n))
+    assert rc == _lib.SR_ERR_INVALID and b"null argument" in lib.sr_last_error()
+
+
 def test_attention_bf16_hook_empty_batch_and_head_geometry():
     """sr_attention_varlen: B = 0 is SR_OK, and num_heads that is no multiple of num_kv_heads is SR_ERR_INVALID - both before
     anything touches a device: the pointers below are never dereferenced."""
