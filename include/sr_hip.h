@@ -297,13 +297,36 @@ int sr_sparse_score_pairs(sr_sparse_index* idx, const int64_t* d_q_indptr, const
  * Queries, threshold, id_base / id_stride, outputs, padding (0, -1) and d_out_counts as sr_sparse_search, 1 <= k <= 2^30: the result is
  * what sr_sparse_search with k = n_docs returns after the documents outside the subset are removed and the list is cut to k.  Scores
  * are the term-serial unfused chain of sr_sparse_search / sr_sparse_score_pairs and do not depend on m, nq or the rest of the subset.
- * Two routes, the same bits: one wave per (query, subset document) on the chains of sr_sparse_score_pairs for m < n_docs / 16, the
- * score array per 8 192-document tile with a gathered select over the subset's entries above that (dev switch
- * SR_SUBSET_SPARSE_ROUTE=pairs|array forces one).  Workspace, errors (a position outside [0, n_docs) or not above its predecessor)
- * and synchronisation as sr_dense_search_subset.                                                                                */
+ * Three routes, the same bits.  pairs: one wave per (query, subset document) on the chains of sr_sparse_score_pairs, for m < n_docs /
+ * 16.  array: the score array per 8 192-document tile with a gathered select over the subset's entries, above that.  mask: where
+ * sr_sparse_search would run the certified scorer (the index has one, k + 1 024 <= sr_max_topk(), n_docs >= 8 (k + 1 024)), the list is
+ * turned into a bitmap and the scorer's pass runs over the whole collection with one bit test where a document would become a
+ * stage-1 key; its certificate then holds for the allowed documents alone, the candidates are re-scored by the exact chain from the
+ * forward index, and queries it hands back are re-done by pairs / array over the list.  Rule: the mask route where it applies and
+ * nq * m >= 64 * 1 000 000 (where it met the faster list route on one box at 8.84 M documents, for 64 and for 6 980 queries:
+ * DESIGN.md 4.16), else pairs / array as above.  Dev switch SR_SUBSET_SPARSE_ROUTE=pairs|array|mask forces one (read per call; mask
+ * where the scorer does not apply, or for an empty list, is served by the pairs / array rule); the mask route reads the
+ * call's status once BEFORE its pass instead of at the end, and then waits for the stream as sr_sparse_search does.  Workspace, errors
+ * (a position outside [0, n_docs) or not above its predecessor) and synchronisation otherwise as sr_dense_search_subset.          */
 int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
                             const float* d_q_vals, int64_t nq, int k, float threshold,
                             const int64_t* d_subset, int64_t m, int64_t id_base, int64_t id_stride,
+                            float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream);
+/* sr_sparse_search_subset with the allow-list given as a bitmap (what faiss calls IDSelectorBitmap): d_mask_words uint32
+ * [ceil(n_bits / 32)] on the device, bit (i & 31) of word i >> 5 stands for document position i, n_bits == n_docs (anything else:
+ * SR_ERR_INVALID before any device work).  Bits of the last word at or beyond n_bits are ignored, as in sr_doc_list_from_mask, and the
+ * library never reads past that word.  Every position names a document, so a set bit is never invalid.  Returns EXACTLY what
+ * sr_sparse_search_subset returns for the ascending list of the set bits - ids, score bits, tie order, padding (0, -1), counts,
+ * threshold semantics, id_base / id_stride, limits on k, workspace errors (with m = the number of set bits) - whichever route served
+ * the call; the routes, the route rule and its dev switch are those of sr_sparse_search_subset.  The list is expanded on the device
+ * (8 m bytes on the handle) only where pairs / array serve the call or re-do queries the mask route hands back; the mask route keeps
+ * a copy of the bitmap in the length its kernel walks (n_docs / 8 bytes rounded up to whole 1 024-document tiles, counted against the
+ * workspace limit).  sr_sparse_index_cert_stats counts a masked pass like any other.  The call waits for the stream once for the
+ * count of set bits, then on the mask route as sr_sparse_search does (twice per batch of 8 192 queries, and once more per batch with
+ * handed-back queries); on the list routes not again.  Not under a mask: doc-sharded search, per-query masks, range search.      */
+int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
+                            const float* d_q_vals, int64_t nq, int k, float threshold,
+                            const uint32_t* d_mask_words, int64_t n_bits, int64_t id_base, int64_t id_stride,
                             float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream);
 /* Range search: EVERY document whose score exceeds a per-query threshold, as CSR.  This is what the reference's scorer computes before
  * select_topk cuts it (numba_score_float, scaling_retriever/indexer.py:324-344: the score array starts at zero, every query term is

@@ -96,6 +96,7 @@ struct SparseCert {
     int64_t dump_nq = 0;
     bool want_dump = false;
     unsigned long long* d_stamps = nullptr;   // dev switch SR_CERT_STAMPS
+    uint32_t* mask_pad = nullptr;     // [n_tiles * SC_MB] a search's document bitmap as the masked score kernel walks it (sparse_cert_mask_pad), allocated on first use
 };
 
 // ------------------------------------------------------------------------------------------------------- build ---
@@ -262,7 +263,7 @@ void sparse_cert_destroy(SparseCert* c) {
         (void)hipFree(c->d_stamps);
     }
     void* ptrs[] = {c->dslot, c->vmax, c->d16, c->P, c->S, c->E, c->fwd_indptr, c->fwd_tv, c->bfrag, c->rare_term, c->rare_w,
-                    c->cq, c->sq, c->n_rare, c->n_qt, c->n_drop, c->tau2, c->elig, c->overflow, c->m_count, c->d_n_uncert, c->d_uncert, c->ap_ids, c->dump};
+                    c->cq, c->sq, c->n_rare, c->n_qt, c->n_drop, c->tau2, c->elig, c->overflow, c->m_count, c->d_n_uncert, c->d_uncert, c->ap_ids, c->dump, c->mask_pad};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->ws.release();
@@ -564,6 +565,7 @@ struct CertArgs {
     int stamps_from;              // SR_CERT_STAMPS=<first tile>: only launches that begin at this tile or later are sampled
     unsigned long long* stamps;   // dev switch SR_CERT_STAMPS: [8] cycle sums per phase of sampled waves
     int64_t dump_stride;
+    const uint32_t* mask;    // MASKED launches: [n_tiles * SC_MB] words, bit b of word tile * SC_MB + block = may doc tile * SC_DT + block * 32 + b become a key; null otherwise
 };
 
 // low half of a packed posting: byte offset of the doc's word inside a query row of the LDS tile | doc parity (SC_POST_LO)
@@ -745,7 +747,11 @@ constexpr int sc_ring_depth(int nl) {
     return d;
 }
 
-template <int KS>
+// MASKED: the search runs under a document bitmap (sr_sparse_search_masked).  A matrix wave finishes one 32-aligned block of 32 docs at a
+// time, so one mask word covers the block at a wave-uniform address; a doc whose bit is clear never becomes a candidate, and everything
+// downstream (tau, tau2, the band cut, the certificate) is a quantity over the allowed docs alone.  MASKED = false compiles to the kernel
+// without any of it.
+template <int KS, bool MASKED>
 __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
     extern __shared__ uint32_t slots[];                          // 2 x [SC_QB][SC_PITCH_W] | B fragments | mark buffers
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -812,6 +818,9 @@ __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
         for (int tile = tile0; tile < tile1; ++tile) {
             const int tnext = tile + 1 < tile1 ? tile + 1 : tile;    // past the end: re-reads this tile (no branch around the loads)
             uint32_t* const buf = slots + (tile & 1) * SC_SLOT_WORDS;
+            // the mask words of the wave's four blocks: one 16-byte read at a wave-uniform address, issued in front of the tile's MFMA chains
+            uint4 mw = make_uint4(0u, 0u, 0u, 0u);
+            if constexpr (MASKED) mw = *reinterpret_cast<const uint4*>(a.mask + ((int64_t)tile * SC_MB + wave_u * 4));
 #pragma unroll
             for (int mbi = 0; mbi < 4; ++mbi) {
                 const int mb = mbi;
@@ -865,10 +874,15 @@ __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
                     if (SC_STAMPS && st_wg && wave == 1 && __builtin_amdgcn_ballot_w64(any != 0) != 0 && lane == 0) atomicAdd(&a.stamps[5], 1ull);
                 }
                 if (SC_DIAG & 128) any = 0;                      // timing only: no candidates
+                const uint32_t mword = mbi == 0 ? mw.x : (mbi == 1 ? mw.y : (mbi == 2 ? mw.z : mw.w));
+                if constexpr (MASKED) { if (mword == 0u) any = 0; }      // wave-uniform: a block without an allowed doc has no candidate
                 if (any != 0) {                                  // one block in two at the MSMARCO shape once the threshold has risen (46 % in the launches from tile 2 000 on)
+                    // the bit of the doc at offset o = 8 (g / 2) + 4 h + 2 (g % 2) (+ 1: the high half) of the block, behind the score test
+                    const uint32_t mh = MASKED ? mword >> (4 * h) : 0u;
+                    auto allowed = [&](int g, int half) -> bool { return !MASKED || ((mh >> (8 * (g >> 1) + 2 * (g & 1) + half)) & 1u) != 0u; };
                     int cnt = 0;
 #pragma unroll
-                    for (int g = 0; g < 8; ++g) cnt += ((key[g] & 0xffffu) > cutm1 ? 1 : 0) + ((key[g] >> 16) > cutm1 ? 1 : 0);
+                    for (int g = 0; g < 8; ++g) cnt += ((key[g] & 0xffffu) > cutm1 && allowed(g, 0) ? 1 : 0) + ((key[g] >> 16) > cutm1 && allowed(g, 1) ? 1 : 0);
                     int pos = atomicAdd(&a.cand_count[q], cnt);
                     if ((int64_t)pos + cnt > a.cand_cap) a.overflow[q] = 1;
                     uint64_t* dst = a.cand_keys + q * a.cand_cap;
@@ -876,8 +890,8 @@ __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
                     for (int g = 0; g < 8; ++g) {
                         const uint32_t doc = (uint32_t)tile * SC_DT + (uint32_t)((wave * 4 + mb) * 32 + 8 * (g >> 1) + 4 * h + 2 * (g & 1));
                         const uint32_t lo = key[g] & 0xffffu, hi = key[g] >> 16;
-                        if (lo > cutm1) { if (pos < a.cand_cap) dst[pos] = sr_make_key((float)lo, doc); ++pos; }
-                        if (hi > cutm1) { if (pos < a.cand_cap) dst[pos] = sr_make_key((float)hi, doc + 1u); ++pos; }
+                        if (lo > cutm1 && allowed(g, 0)) { if (pos < a.cand_cap) dst[pos] = sr_make_key((float)lo, doc); ++pos; }
+                        if (hi > cutm1 && allowed(g, 1)) { if (pos < a.cand_cap) dst[pos] = sr_make_key((float)hi, doc + 1u); ++pos; }
                     }
                 }
                 if (mbi == 0) SC_STAMP(3);                       // end of the first block's filter
@@ -1462,23 +1476,57 @@ uint8_t* sparse_cert_uncert_buffer(SparseCert* c, int64_t nq) {
     return c->d_uncert;
 }
 
-template <int KS>
-static int cert_launch_score(const CertArgs& a, unsigned grid, hipStream_t s) {
-    static DeviceOnce lds_set;
+template <int KS, bool MASKED>
+static int cert_launch_score_as(const CertArgs& a, unsigned grid, hipStream_t s) {
+    static DeviceOnce lds_set;                               // one per (KS, MASKED) instantiation
     static_assert(1024 * KS <= SC_BREGION, "B fragments");
     const int lds = (int)(sizeof(uint32_t) * 2 * SC_SLOT_WORDS + SC_BREGION + SC_TAIL_LDS + (a.stamps ? 256 : 0));
     if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)cert_score_kernel<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        SR_CHECK_HIP(hipFuncSetAttribute((const void*)cert_score_kernel<KS, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         *slot = true;
     }
-    hipLaunchKernelGGL(cert_score_kernel<KS>, dim3(grid), dim3(1024), lds, s, a);
+    hipLaunchKernelGGL((cert_score_kernel<KS, MASKED>), dim3(grid), dim3(1024), lds, s, a);
     SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+template <int KS>
+static int cert_launch_score(const CertArgs& a, unsigned grid, hipStream_t s) {
+    return a.mask != nullptr ? cert_launch_score_as<KS, true>(a, grid, s) : cert_launch_score_as<KS, false>(a, grid, s);
+}
+
+// The bitmap of a masked search as the score kernel walks it: n_tiles * SC_MB words.  A caller's bitmap holds ceil(n_docs / 32) words and
+// its last word may carry set bits at or beyond n_docs; the kernel must neither read past the caller's buffer nor see those bits.
+__global__ void cert_mask_pad_kernel(const uint32_t* __restrict__ words, int64_t n_words, int64_t n_docs, uint32_t* __restrict__ pad, int64_t n_pad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    uint32_t v = i < n_words ? words[i] : 0u;
+    const unsigned tail = (unsigned)(n_docs & 31);
+    if (i == n_words - 1 && tail != 0) v &= (1u << tail) - 1u;
+    pad[i] = v;
+}
+
+int64_t sparse_cert_mask_pad_bytes(const SparseCert* c) { return (int64_t)c->n_tiles * SC_MB * (int64_t)sizeof(uint32_t); }
+
+int sparse_cert_mask_pad(sr_sparse_index* idx, const uint32_t* d_words, const uint32_t** d_mask_pad, hipStream_t s) {
+    SparseCert* c = idx->cert;
+    const int64_t n_pad = (int64_t)c->n_tiles * SC_MB;
+    *d_mask_pad = nullptr;
+    if (!c->mask_pad && hipMalloc((void**)&c->mask_pad, sizeof(uint32_t) * (size_t)n_pad) != hipSuccess) {
+        (void)hipGetLastError();
+        c->mask_pad = nullptr;
+        return SR_OK;
+    }
+    hipLaunchKernelGGL(cert_mask_pad_kernel, dim3((unsigned)ceil_div64(n_pad, 256)), dim3(256), 0, s, d_words, ceil_div64(idx->n_docs, 32), idx->n_docs,
+                       c->mask_pad, n_pad);
+    SR_CHECK_LAUNCH();
+    *d_mask_pad = c->mask_pad;
     return SR_OK;
 }
 
 int sparse_cert_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
                        int k, float threshold, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids,
-                       int32_t* d_out_counts, uint8_t* d_uncert, int64_t* n_uncert, bool* no_memory, int band_keys, int* band_used, hipStream_t s) {
+                       int32_t* d_out_counts, uint8_t* d_uncert, int64_t* n_uncert, bool* no_memory, int band_keys, int* band_used,
+                       const uint32_t* d_mask_pad, hipStream_t s) {
     SparseCert* c = idx->cert;
     const int64_t nq_pad = ceil_div64(nq, SC_QB) * SC_QB;
     const int n_qblocks = (int)(nq_pad / SC_QB);
@@ -1562,6 +1610,7 @@ int sparse_cert_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const in
     a.stamps_from = 0;
     if (SC_STAMPS) { if (const char* e = sr_dev_getenv("SR_CERT_STAMPS")) a.stamps_from = atoi(e); }
     a.dump_stride = dump_stride;
+    a.mask = d_mask_pad;
     int64_t step = k_eff / SC_DT + 1;      // the first launch covers just over k + band docs (no threshold exists before that many keys are held), then doubling
     if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_STEP0")) step = std::max(1, atoi(e));
     bool band_filter = true;               // dev switch SR_SPARSE_CERT_BAND=0: filter with the (k + band)-th best key only

@@ -1165,6 +1165,9 @@ extern "C" int sr_sparse_index_destroy(sr_sparse_index* idx) {
     if (idx->seg_cnt) (void)hipFree(idx->seg_cnt);
     if (idx->pair_status) (void)hipFree(idx->pair_status);
     if (idx->pair_qflags) (void)hipFree(idx->pair_qflags);
+    if (idx->filt_words) (void)hipFree(idx->filt_words);
+    if (idx->filt_blocks) (void)hipFree(idx->filt_blocks);
+    if (idx->filt_list) (void)hipFree(idx->filt_list);
     delete idx;
     return SR_OK;
 }
@@ -1442,11 +1445,12 @@ __global__ void sparse_sub_scatter_kernel(const int64_t* __restrict__ sel, int k
 
 // wide_band > 0 (and at least SR_CERT_RETRY_MIN queries handed back): the sub-batch first goes through the certified scorer once more with
 // that many keys beyond k - a certificate that failed for want of room is then usually given - and only what it hands back again reaches
-// the exact kernels.
+// the exact kernels.  filt (null: the whole collection): the search runs under a document filter - the second pass under its bitmap, and
+// the exact kernels are the list routes of sr_sparse_search_subset over its list, which rank the allowed documents only.
 #define SR_CERT_RETRY_MIN 256
 static int sparse_redo_exact(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
                              int k, float threshold, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids,
-                             int32_t* d_out_counts, const uint8_t* d_uncert, hipStream_t s, int wide_band = 0) {
+                             int32_t* d_out_counts, const uint8_t* d_uncert, hipStream_t s, int wide_band = 0, SparseDocFilter* filt = nullptr) {
     std::vector<uint8_t> h_un((size_t)nq);
     std::vector<int64_t> h_ip((size_t)nq + 1);
     SR_CHECK_HIP(hipMemcpyAsync(h_un.data(), d_uncert, (size_t)nq, hipMemcpyDeviceToHost, s));
@@ -1460,6 +1464,7 @@ static int sparse_redo_exact(sr_sparse_index* idx, const int64_t* d_q_indptr, co
         }
     const int64_t ns = (int64_t)sel.size();
     if (ns == 0) return SR_OK;
+    if (filt) SR_TRY(sparse_filter_need_list(idx, filt, s));
     const int64_t nnz = sub_ip.back();
     int64_t *d_sel = nullptr, *d_sip = nullptr, *d_ids = nullptr;
     int32_t *d_cols = nullptr, *d_cnt = nullptr;
@@ -1485,12 +1490,12 @@ static int sparse_redo_exact(sr_sparse_index* idx, const int64_t* d_q_indptr, co
                 bool no_memory = false;
                 int band_used = 0;
                 rc = sparse_cert_search(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, d_un2, &n_un2, &no_memory,
-                                        wide_band, &band_used, s);
+                                        wide_band, &band_used, filt ? filt->mask_pad : nullptr, s);
                 if (rc == SR_OK && !no_memory) {
                     ++idx->n_cert_retries;
                     sparse_cert_count_retry(idx->cert, ns);
                     if (n_un2 > 0)
-                        rc = sparse_redo_exact(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, d_un2, s);
+                        rc = sparse_redo_exact(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, d_un2, s, 0, filt);
                     done = true;
                 }
                 if (hipStreamSynchronize(s) != hipSuccess && rc == SR_OK) rc = SR_ERR_HIP;
@@ -1500,7 +1505,9 @@ static int sparse_redo_exact(sr_sparse_index* idx, const int64_t* d_q_indptr, co
             }
         }
         if (rc == SR_OK && !done)
-            rc = sparse_exact_search(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, s);
+            rc = filt ? sparse_subset_lists(idx, d_sip, d_cols, d_vals, ns, k, threshold, filt->list, filt->m, subset_sparse_use_array(filt->m, idx->n_docs),
+                                            id_base, id_stride, d_sc, d_ids, d_cnt, s, filt->who)
+                      : sparse_exact_search(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, s);
     }
     if (rc == SR_OK) {
         hipLaunchKernelGGL(sparse_sub_scatter_kernel, dim3((unsigned)ns), dim3(256), 0, s, d_sel, k, d_sc, d_ids, d_cnt, d_out_scores, d_out_ids,
@@ -1513,6 +1520,58 @@ static int sparse_redo_exact(sr_sparse_index* idx, const int64_t* d_q_indptr, co
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     return rc;
+}
+
+// certified two-stage scorer (sparse_cert.hip) where the index has one and k leaves room for its band of extra keys.  Dev switch
+// SR_SPARSE_CERT_SEARCH=0: exact kernels only (A/B)
+bool sparse_cert_applies(const sr_sparse_index* idx, int k) {
+    bool use_cert = idx->cert != nullptr && k + 1024 <= SR_MAX_TOPK;
+    {
+        const char* forced = sr_dev_getenv("SR_SPARSE_CERT");        // 1: also on collections too small for it to pay (tests)
+        if (!(forced && atoi(forced) == 1)) use_cert = use_cert && idx->n_docs >= 8ll * (k + 1024);
+    }
+    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_SEARCH")) use_cert = use_cert && atoi(e) != 0;
+    return use_cert;
+}
+
+int sparse_certified_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq, int k,
+                            float threshold, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
+                            SparseDocFilter* filt, hipStream_t s) {
+    // The scorer's workspace is ~200 KB per query: the query set goes through in batches (a whole MSMARCO-Dev set is one batch), and
+    // a batch whose buffers do not fit in device memory is served by the exact kernels instead of failing the call; the queries it
+    // cannot certify are re-done by the exact kernels.
+    int64_t batch = SR_CERT_QUERY_BATCH;
+    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_BATCH")) batch = std::max<int64_t>(32, atoll(e) / 32 * 32);   // tests: several batches on small inputs
+    uint8_t* d_uncert = sparse_cert_uncert_buffer(idx->cert, nq < batch ? nq : batch);
+    for (int64_t qb = 0; qb < nq; qb += batch) {
+        const int64_t nqb = nq - qb < batch ? nq - qb : batch;
+        float* o_s = d_out_scores + qb * k;
+        int64_t* o_i = d_out_ids + qb * k;
+        int32_t* o_c = d_out_counts ? d_out_counts + qb : nullptr;
+        int64_t n_un = 0;
+        bool no_memory = d_uncert == nullptr || (filt && filt->mask_pad == nullptr);
+        if (sr_dev_getenv("SR_SPARSE_CERT_FAKE_OOM")) no_memory = true;          // tests: the fallback below
+        int band_used = 0;
+        if (!no_memory)
+            SR_TRY(sparse_cert_search(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, d_uncert,
+                                      &n_un, &no_memory, 0, &band_used, filt ? filt->mask_pad : nullptr, s));
+        if (no_memory) {
+            ++idx->n_cert_no_memory;
+            if (filt) {
+                SR_TRY(sparse_filter_need_list(idx, filt, s));
+                SR_TRY(sparse_subset_lists(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, filt->list, filt->m,
+                                           subset_sparse_use_array(filt->m, idx->n_docs), id_base, id_stride, o_s, o_i, o_c, s, filt->who));
+            } else {
+                SR_TRY(sparse_exact_search(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, s));
+            }
+        } else if (n_un > 0) {
+            // many queries handed back under a band that could still grow: once more through the scorer with the widest band, then the exact kernels
+            const int widest = SR_MAX_TOPK - k;                // worth a second pass only if it at least doubles the band
+            SR_TRY(sparse_redo_exact(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, d_uncert, s,
+                                     2 * band_used <= widest ? widest : 0, filt));
+        }
+    }
+    return SR_OK;
 }
 
 extern "C" int sr_sparse_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
@@ -1529,44 +1588,9 @@ extern "C" int sr_sparse_search(sr_sparse_index* idx, const int64_t* d_q_indptr,
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
-    // certified two-stage scorer (sparse_cert.hip) where the index has one and k leaves room for its band of extra keys; the
-    // queries it cannot certify are re-done by the exact kernels.  Dev switch SR_SPARSE_CERT_SEARCH=0: exact kernels only (A/B)
-    bool use_cert = idx->cert != nullptr && k + 1024 <= SR_MAX_TOPK;
-    {
-        const char* forced = sr_dev_getenv("SR_SPARSE_CERT");        // 1: also on collections too small for it to pay (tests)
-        if (!(forced && atoi(forced) == 1)) use_cert = use_cert && idx->n_docs >= 8ll * (k + 1024);
-    }
-    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_SEARCH")) use_cert = use_cert && atoi(e) != 0;
-    if (use_cert) {
-        // The scorer's workspace is ~200 KB per query: the query set goes through in batches (a whole MSMARCO-Dev set is one batch), and
-        // a batch whose buffers do not fit in device memory is served by the exact kernels instead of failing the call.
-        int64_t batch = SR_CERT_QUERY_BATCH;
-        if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_BATCH")) batch = std::max<int64_t>(32, atoll(e) / 32 * 32);   // tests: several batches on small inputs
-        uint8_t* d_uncert = sparse_cert_uncert_buffer(idx->cert, nq < batch ? nq : batch);
-        for (int64_t qb = 0; qb < nq; qb += batch) {
-            const int64_t nqb = nq - qb < batch ? nq - qb : batch;
-            float* o_s = d_out_scores + qb * k;
-            int64_t* o_i = d_out_ids + qb * k;
-            int32_t* o_c = d_out_counts ? d_out_counts + qb : nullptr;
-            int64_t n_un = 0;
-            bool no_memory = d_uncert == nullptr;
-            if (sr_dev_getenv("SR_SPARSE_CERT_FAKE_OOM")) no_memory = true;          // tests: the fallback below
-            int band_used = 0;
-            if (!no_memory)
-                SR_TRY(sparse_cert_search(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, d_uncert,
-                                          &n_un, &no_memory, 0, &band_used, s));
-            if (no_memory) {
-                ++idx->n_cert_no_memory;
-                SR_TRY(sparse_exact_search(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, s));
-            } else if (n_un > 0) {
-                // many queries handed back under a band that could still grow: once more through the scorer with the widest band, then the exact kernels
-                const int widest = SR_MAX_TOPK - k;                // worth a second pass only if it at least doubles the band
-                SR_TRY(sparse_redo_exact(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, d_uncert, s,
-                                         2 * band_used <= widest ? widest : 0));
-            }
-        }
-        return SR_OK;
-    }
+    if (sparse_cert_applies(idx, k))
+        return sparse_certified_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids,
+                                       d_out_counts, nullptr, s);
     return sparse_exact_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids,
                                d_out_counts, s);
 }

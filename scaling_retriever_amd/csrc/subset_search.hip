@@ -14,13 +14,16 @@
 // of the subset at a time, and folded into the running top-k by the select code every search uses (topk.hip, topk_large.hip) - the
 // key holds the doc index of subset entry j itself, so ties fall as in sr_dense_search.
 //
-// Sparse.  Two routes, the same bits (the reference's term-serial unfused chain):
+// Sparse.  Three routes, the same bits (the reference's term-serial unfused chain):
 //   pairs  one wave per (query, subset document): sparse_pair_chain (sparse_pair_chain.h), the chain of sr_sparse_score_pairs.
 //   array  one workgroup per (query, tile of 8 192 documents that holds a subset entry): the tile's slice of the reference's score
 //          array in LDS, the query's terms applied one after the other with a barrier between them, then a gathered select over
 //          scores[subset[j]] for the subset entries of the tile, compacted in ascending position order.
-// Both keep score > threshold and score >= tau[query] and feed the same top-k.
+//   mask   the certified scorer's pass over the whole collection under the filter's bitmap (sparse_cert.hip): a document whose bit is
+//          clear never becomes a stage-1 key; the re-score from the forward index returns the same chain.
+// pairs and array keep score > threshold and score >= tau[query] and feed the same top-k.
 #include "subset_search.h"
+#include "doc_mask.h"
 #include "sparse_index.h"
 #include "sparse_pair_chain.h"
 #include <math.h>
@@ -362,41 +365,65 @@ __global__ __launch_bounds__(256) void sparse_subset_array_kernel(SparseSubsetAr
 
 // Route rule.  The pair route costs one wave and a binary search per posting of every (query, subset document); the array route streams
 // the postings of the query's terms once per tile whatever m is, and a streamed posting costs roughly a sixteenth of a searched one.  So
-// the array route serves subsets of at least a sixteenth of the collection, the pair route smaller ones (unmeasured).  Dev switch
-// SR_SUBSET_SPARSE_ROUTE=pairs|array forces one (tests compare the two).
-static bool subset_sparse_use_array(int64_t m, int64_t n_docs) {
+// between the two list routes the array route serves subsets of at least a sixteenth of the collection, the pair route smaller ones.
+// The third route, mask, runs the certified scorer's pass over the whole collection under the filter's bitmap (sparse_cert.hip,
+// cert_score_kernel<KS, true>) where sr_sparse_search would use the scorer; its cost hardly depends on m (41.5 - 71.9 ms for 6 980 queries
+// at the config-3 shape).  Dev switch SR_SUBSET_SPARSE_ROUTE=pairs|array|mask forces one (tests compare the three); mask where the
+// scorer does not apply is served by the list rule.
+bool subset_sparse_use_array(int64_t m, int64_t n_docs) {
     if (const char* route = sr_dev_getenv("SR_SUBSET_SPARSE_ROUTE")) {
         if (strcmp(route, "array") == 0) return true;
         if (strcmp(route, "pairs") == 0) return false;
     }
     return m * 16 >= n_docs;
 }
-
-extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
-                                       int64_t nq, int k, float threshold, const int64_t* d_subset, int64_t m, int64_t id_base,
-                                       int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
-                                       sr_stream stream) {
-    SR_REQUIRE(idx, "sr_sparse_search_subset: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_subset: bad nq");
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_subset: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
-    SR_REQUIRE(m >= 0 && m <= idx->n_docs, "sr_sparse_search_subset: a strictly ascending subset of %lld documents holds at most that many, not m=%lld",
-               (long long)idx->n_docs, (long long)m);
-    SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
-               "sr_sparse_search_subset: global doc index exceeds 32 bits");
-    if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_sparse_search_subset: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(idx->mu);
-    StreamOrder::Scope in_order(idx->order, s);
-    const bool array = subset_sparse_use_array(m, idx->n_docs);
-    int64_t nq_batch = 0, slab = 0;
-    SR_TRY(subset_plan(idx->ws_limit, nq, k, m, array ? SS_TILE : 64, &nq_batch, &slab, "sr_sparse_search_subset"));
-    SR_TRY(subset_status_begin(&idx->pair_status, s));
-    if (m > 0) {
-        hipLaunchKernelGGL(subset_check_sparse_kernel, dim3((unsigned)ceil_div64(m, 256)), dim3(256), 0, s, d_subset, m, idx->n_docs,
-                           idx->pair_status);
-        SR_CHECK_LAUNCH();
+// Where the mask route takes over, as a product bound on nq x m like the dense one (dense_score.hip).  Measured on one MI355X at the config-3
+// shape, 8.84 M documents, k = 1 000 (profiles/subset_search.json, key sparse_routes.rows): the smallest measured m at which the forced
+// mask route beats both list routes, and does so at every larger measured m, is m = 10 000 for nq = 6 980 (mask 43.3 ms, pairs 55.6 ms;
+// at m = 1 000 pairs wins with 7.06 against 41.5 ms) and m = 1 000 000 for nq = 64 (mask 7.72 ms, array 15.7 ms; at m = 100 000 pairs wins
+// with 6.15 against 7.41 ms).  Both crossings lie at nq x m of 6.4e7 - 7.0e7; the constant is the smaller of the two products, so that the
+// rule sends each measured nq to the mask route from its own crossing on.  One box, one collection size.
+#define SR_SUBSET_SPARSE_MASK_CROSSOVER (64ll * 1000000ll)
+// The one rule of sr_sparse_search_subset and sr_sparse_search_masked: does a call with nq queries, this k and m allowed documents take the mask route
+static bool subset_sparse_use_mask(const sr_sparse_index* idx, int64_t nq, int k, int64_t m) {
+    bool wants = nq * m >= SR_SUBSET_SPARSE_MASK_CROSSOVER;
+    if (const char* route = sr_dev_getenv("SR_SUBSET_SPARSE_ROUTE")) {
+        if (strcmp(route, "array") == 0 || strcmp(route, "pairs") == 0) wants = false;
+        if (strcmp(route, "mask") == 0) wants = true;
     }
+    // an empty filter has nothing to scan for; the scorer's copy of the bitmap counts against the workspace limit
+    return wants && m > 0 && sparse_cert_applies(idx, k) && sparse_cert_mask_pad_bytes(idx->cert) <= idx->ws_limit;
+}
+
+template <typename T>
+static int sparse_filter_scratch(T** p, int64_t* cap, int64_t want, const char* who) {
+    if (*cap >= want) return SR_OK;
+    if (*p) (void)hipFree(*p);                            // waits for the calls that read it
+    *p = nullptr; *cap = 0;
+    if (hipMalloc((void**)p, (size_t)want * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        sr_set_error("%s: out of device memory for %lld bytes of filter scratch", who, (long long)(want * (int64_t)sizeof(T)));
+        return SR_ERR_NOMEM;
+    }
+    *cap = want;
+    return SR_OK;
+}
+
+int sparse_filter_need_list(sr_sparse_index* idx, SparseDocFilter* f, hipStream_t s) {
+    if (f->list_ready) return SR_OK;
+    SR_TRY(sparse_filter_scratch(&idx->filt_list, &idx->filt_list_cap, f->m > 0 ? f->m : 1, f->who));
+    SR_TRY(launch_doc_mask_expand(f->words, idx->n_docs, idx->filt_blocks, idx->filt_list, f->m, s));
+    f->list = idx->filt_list;
+    f->list_ready = true;
+    return SR_OK;
+}
+
+int sparse_subset_lists(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq, int k,
+                        float threshold, const int64_t* d_subset, int64_t m, bool array, int64_t id_base, int64_t id_stride, float* d_out_scores,
+                        int64_t* d_out_ids, int32_t* d_out_counts, hipStream_t s, const char* who) {
+    int64_t nq_batch = 0, slab = 0;
+    SR_TRY(subset_plan(idx->ws_limit, nq, k, m, array ? SS_TILE : 64, &nq_batch, &slab, who));
     SparseSubsetArgs a;
     a.x = SparseChainIndex{idx->indptr, idx->doc_ids, idx->vals, idx->n_terms, nullptr, nullptr};
     a.n_docs = idx->n_docs;
@@ -405,7 +432,7 @@ extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_
         // the pair route's own two ways to the postings, as in sr_sparse_score_pairs (dev switch SR_PAIR_SPARSE_ROUTE=postings)
         const char* route = sr_dev_getenv("SR_PAIR_SPARSE_ROUTE");
         if (!(route && strcmp(route, "postings") == 0)) sparse_cert_forward_index(idx->cert, &a.x.fwd_indptr, &a.x.fwd_tv);
-        if (a.x.fwd_indptr) SR_TRY(sparse_pair_query_flags(idx, d_q_indptr, d_q_cols, nq, "sr_sparse_search_subset", s));
+        if (a.x.fwd_indptr) SR_TRY(sparse_pair_query_flags(idx, d_q_indptr, d_q_cols, nq, who, s));
     }
     a.q_cols = d_q_cols; a.q_vals = d_q_vals;
     a.skip = idx->skip; a.skip_n = idx->n_tiles * (SR_SPARSE_TILE_DOCS / SR_SPARSE_SKIP_DOCS);
@@ -451,5 +478,91 @@ extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_
         }
         SR_TRY(topk_finalize(idx->ws, nqb, k, 0.f, d_out_scores + qb * k, d_out_ids + qb * k, d_out_counts ? d_out_counts + qb : nullptr, s));
     }
+    return SR_OK;
+}
+
+extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                       int64_t nq, int k, float threshold, const int64_t* d_subset, int64_t m, int64_t id_base,
+                                       int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
+                                       sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_search_subset: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_subset: bad nq");
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_subset: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_REQUIRE(m >= 0 && m <= idx->n_docs, "sr_sparse_search_subset: a strictly ascending subset of %lld documents holds at most that many, not m=%lld",
+               (long long)idx->n_docs, (long long)m);
+    SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
+               "sr_sparse_search_subset: global doc index exceeds 32 bits");
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_sparse_search_subset: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder::Scope in_order(idx->order, s);
+    const bool array = subset_sparse_use_array(m, idx->n_docs);
+    {   // a call that cannot run fails before any launch, whichever route serves it
+        int64_t nq_batch = 0, slab = 0;
+        SR_TRY(subset_plan(idx->ws_limit, nq, k, m, array ? SS_TILE : 64, &nq_batch, &slab, "sr_sparse_search_subset"));
+    }
+    SR_TRY(subset_status_begin(&idx->pair_status, s));
+    if (m > 0) {
+        hipLaunchKernelGGL(subset_check_sparse_kernel, dim3((unsigned)ceil_div64(m, 256)), dim3(256), 0, s, d_subset, m, idx->n_docs,
+                           idx->pair_status);
+        SR_CHECK_LAUNCH();
+    }
+    // The mask route reads the call's status here, not at the end: the list gets its bitmap once the check kernel has accepted it (a bad
+    // list goes on to the list routes, which score nothing, write the padding rows and report it)
+    if (subset_sparse_use_mask(idx, nq, k, m) && subset_status_end(idx->pair_status, d_subset, "sr_sparse_search_subset", "position", s) == SR_OK) {
+        const int64_t n_words = doc_mask_words(idx->n_docs);
+        SR_TRY(sparse_filter_scratch(&idx->filt_words, &idx->filt_words_cap, n_words > 0 ? n_words : 1, "sr_sparse_search_subset"));
+        SR_TRY(launch_doc_mask_from_list(d_subset, m, idx->filt_words, idx->n_docs, idx->pair_status, nullptr, s));
+        SparseDocFilter f;
+        f.words = idx->filt_words; f.list = d_subset; f.m = m; f.list_ready = true; f.who = "sr_sparse_search_subset";
+        SR_TRY(sparse_cert_mask_pad(idx, f.words, &f.mask_pad, s));
+        return sparse_certified_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts,
+                                       &f, s);
+    }
+    SR_TRY(sparse_subset_lists(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, d_subset, m, array, id_base, id_stride, d_out_scores, d_out_ids,
+                               d_out_counts, s, "sr_sparse_search_subset"));
     return subset_status_end(idx->pair_status, d_subset, "sr_sparse_search_subset", "position", s);
+}
+
+// The same search with the filter given as a bitmap.  The count of the set bits (one 8-byte read-back) feeds the route rule; the ascending
+// list is expanded only where a list route or a hand-back of the mask route needs its entries.  Every sparse position names a document,
+// so a set bit below n_bits is never invalid and the list needs no check.
+extern "C" int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                       int64_t nq, int k, float threshold, const uint32_t* d_mask_words, int64_t n_bits, int64_t id_base,
+                                       int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_search_masked: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_masked: bad nq");
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_masked: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_search_masked: the mask holds n_bits=%lld bits, the index %lld documents", (long long)n_bits,
+               (long long)idx->n_docs);
+    SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
+               "sr_sparse_search_masked: global doc index exceeds 32 bits");
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && (d_mask_words || n_bits == 0), "sr_sparse_search_masked: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder::Scope in_order(idx->order, s);
+    const int64_t n_blocks = doc_mask_blocks(n_bits);
+    SR_TRY(sparse_filter_scratch(&idx->filt_blocks, &idx->filt_blocks_cap, n_blocks + 1, "sr_sparse_search_masked"));
+    int64_t* d_count = idx->filt_blocks + n_blocks;
+    SR_TRY(launch_doc_mask_count(d_mask_words, n_bits, idx->filt_blocks, d_count, s));
+    SparseDocFilter f;
+    f.words = d_mask_words;
+    SR_CHECK_HIP(hipMemcpyAsync(&f.m, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    const bool array = subset_sparse_use_array(f.m, idx->n_docs);
+    {   // the workspace errors of sr_sparse_search_subset for a list of this length, before any scoring
+        int64_t nq_batch = 0, slab = 0;
+        SR_TRY(subset_plan(idx->ws_limit, nq, k, f.m, array ? SS_TILE : 64, &nq_batch, &slab, "sr_sparse_search_masked"));
+    }
+    SR_TRY(subset_status_begin(&idx->pair_status, s));        // the list kernels read it; nothing here can raise it
+    if (subset_sparse_use_mask(idx, nq, k, f.m)) {
+        SR_TRY(sparse_cert_mask_pad(idx, f.words, &f.mask_pad, s));
+        return sparse_certified_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts,
+                                       &f, s);
+    }
+    SR_TRY(sparse_filter_need_list(idx, &f, s));
+    return sparse_subset_lists(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, f.list, f.m, array, id_base, id_stride, d_out_scores, d_out_ids,
+                               d_out_counts, s, "sr_sparse_search_masked");
 }

@@ -844,15 +844,31 @@ class SparseRetrieval:
         inv = self.inverse_id_map()
         return torch.from_numpy(allowed_positions(allowed_ids, lambda d: inv.pos.get(str(d)))).to(self._dev)
 
-    def _sparse_retrieve_multithreaded(self, sparse_query_vecs, qids, threshold=0., topk=1000, allowed_ids=None, _subset=None):
+    def allowed_mask_words(self, allowed_mask):
+        """A boolean array / tensor over the document positions of the inverted index (one flag per document) -> the packed bitmap on
+        its device, uploaded and packed once per call (scoring.pack_doc_mask)."""
+        from .scoring import pack_doc_mask
+        flags = allowed_mask if isinstance(allowed_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allowed_mask, dtype=bool))
+        n_docs = self.hip_index.n_docs
+        if flags.dim() != 1 or flags.numel() != n_docs:
+            raise ValueError(f"allowed_mask must hold one flag per document position ({n_docs}), got {tuple(flags.shape)}")
+        return pack_doc_mask(flags.to(device=self._dev, dtype=torch.bool))
+
+    def _sparse_retrieve_multithreaded(self, sparse_query_vecs, qids, threshold=0., topk=1000, allowed_ids=None, _subset=None,
+                                       allowed_mask=None, _mask=None):
         """allowed_ids (None: every document): collection ids - only these documents are ranked (_subset: their positions, already on
-        the device).  indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
+        the device).  allowed_mask: the same filter as a boolean array over document positions (_mask: its packed bitmap, already on
+        the device); not both.  indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
         whole query set is one batched HIP search (the doc space is tiled across workgroups instead) and `res` is a RunResult
         over the result arrays: the same mapping, without 7 M dict insertions."""
+        if allowed_ids is not None and allowed_mask is not None:
+            raise ValueError("_sparse_retrieve_multithreaded: pass allowed_ids or allowed_mask, not both")
         q = _as_query_csr(sparse_query_vecs, self._dev)
         if allowed_ids is not None:
             _subset = self.allowed_subset(allowed_ids)
-        scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=_subset)
+        if allowed_mask is not None:
+            _mask = self.allowed_mask_words(allowed_mask)
+        scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=_subset, mask=_mask)
         res = RunResult(qids, to_host(scores), to_host(ids), self.doc_id_table(), to_host(counts))
         stats = defaultdict(float)
         stats["L0_q"] = q.mean_l0()
@@ -865,21 +881,25 @@ class SparseRetrieval:
                 json.dump(stats, handler)
         res.dump(os.path.join(self.out_dir, "run.json"))        # sr_write_run_json: the bytes json.dump(res) writes
 
-    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None):
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None):
         """allowed_ids (None: every document): collection ids, any order, duplicates allowed - only these documents are ranked; an unknown
-        id raises ValueError before anything is encoded.  run.json and q_stats.json keep their format.
+        id raises ValueError before anything is encoded.  allowed_mask: the same filter as a boolean array over the document positions
+        of the inverted index (SparseIndexHIP.search, mask); not both.  run.json and q_stats.json keep their format.
         indexer.py:530-540.  Query groups of QUERY_GROUP_ROWS rows go through encode -> search one after the other while a worker
         thread writes the previous group's piece of run.json (sr_write_run_json_part): formatting and the page-cache copy of a Dev-sized
         file take as long as the encode, and nothing in them needs the GPU.  A query's rows do not depend on the batch it is searched in
         (certified or exact: the same bits), and the file is the one-call file byte for byte (tests/test_boundary_gpu.py)."""
+        if allowed_ids is not None and allowed_mask is not None:
+            raise ValueError("retrieve: pass allowed_ids or allowed_mask, not both")
         groups = list(batch_groups(q_loader, self.QUERY_GROUP_ROWS))
         group_qids = [[x for batch in g for x in (batch["ids"] if isinstance(batch["ids"], list) else to_list(batch["ids"]))] for g in groups]
         qids = [x for g in group_qids for x in g]
         table = self.doc_id_table()
         subset = None if allowed_ids is None else self.allowed_subset(allowed_ids)
+        mask = None if allowed_mask is None else self.allowed_mask_words(allowed_mask)
         if len(groups) < 2 or not (id_table(qids).distinct and id_table(table).distinct):
             sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
-            res, stats = self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=subset)
+            res, stats = self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=subset, _mask=mask)
             self._write_outputs(res, stats)
             return res
         os.makedirs(self.out_dir, exist_ok=True)
@@ -892,7 +912,7 @@ class SparseRetrieval:
                 q = QueryCSR(*sparse_reps_to_csr(reps, self.query_max_terms))
                 del reps
                 nnz += int(q.cols.numel())
-                scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=subset)
+                scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=subset, mask=mask)
                 piece = (to_host(scores), to_host(ids), to_host(counts))
                 pieces.append(piece)
                 writer.add(group_qids[gi], piece[0], piece[1], table, piece[2], last=gi + 1 == len(groups))
@@ -950,11 +970,14 @@ class ShardedSparseRetrieval(SparseRetrieval):
         raise NotImplementedError("ShardedSparseRetrieval.range_search: a range search is not offered on a doc-sharded index; "
                                   "search one merged index with SparseRetrieval instead")
 
-    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None):
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when
         `q_loader.replicated` is set."""
         if allowed_ids is not None:
             raise NotImplementedError("ShardedSparseRetrieval.retrieve: an allow-list (allowed_ids) is not supported on a doc-sharded "
+                                      "index; search one merged index with SparseRetrieval instead")
+        if allowed_mask is not None:
+            raise NotImplementedError("ShardedSparseRetrieval.retrieve: a document bitmap (allowed_mask) is not supported on a doc-sharded "
                                       "index; search one merged index with SparseRetrieval instead")
         from .distributed import all_gather_query_csr
         import torch.distributed as dist

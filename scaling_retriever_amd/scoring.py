@@ -594,10 +594,34 @@ class SparseIndexHIP:
         keys = ("dense_columns_loaded", "dense_column_applications", "light_postings", "grouped_postings", "plan_entries", "workgroup_tiles")
         return {k_: int(v) for k_, v in zip(keys, out)}
 
-    def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, id_base=0, id_stride=1, subset=None):
+    def _mask_argument(self, mask):
+        """The checks of `search(mask=)` that need no device: (packed, mask as tensor / array), the word count of a packed mask verified."""
+        if not torch.is_tensor(mask) and not isinstance(mask, np.ndarray):
+            mask = np.asarray(mask)
+        packed = (isinstance(mask, np.ndarray) and mask.dtype in (np.uint32, np.int32)) or \
+            (torch.is_tensor(mask) and mask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
+        if not packed:
+            is_bool = (isinstance(mask, np.ndarray) and mask.dtype == np.bool_) or (torch.is_tensor(mask) and mask.dtype == torch.bool)
+            if not is_bool:
+                raise ValueError("mask must be a bool tensor / array over the documents, or packed int32 / uint32 words (pack_doc_mask), got "
+                                 f"{getattr(mask, 'dtype', type(mask).__name__)}")
+        if (mask.dim() if torch.is_tensor(mask) else mask.ndim) != 1:
+            raise ValueError(f"expected a 1-D mask, got {tuple(mask.shape)}")
+        n = mask.numel() if torch.is_tensor(mask) else mask.size
+        if packed and n != (self.n_docs + 31) // 32:
+            raise ValueError(f"a packed mask of this index holds {(self.n_docs + 31) // 32} words (n_docs = {self.n_docs}), got {n}")
+        return packed, mask
+
+    def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, id_base=0, id_stride=1, subset=None, mask=None):
         """Queries as CSR tensors. Returns (scores [nq,k], ids [nq,k], counts [nq]) cuda tensors.  subset (None: every document):
         strictly ascending int64 document positions in [0, n_docs), one allow-list for all queries (include/sr_hip.h
-        sr_sparse_search_subset); a position outside the index or out of order: ValueError naming it."""
+        sr_sparse_search_subset); a position outside the index or out of order: ValueError naming it.  mask: the same filter as a
+        bitmap over [0, n_docs) - a bool tensor / array of length n_docs (packed on the device), or int32 / uint32 words already
+        packed (pack_doc_mask) - with exactly the result of `subset` = the set positions (sr_sparse_search_masked).  Not both."""
+        if subset is not None and mask is not None:
+            raise ValueError("search: pass subset or mask, not both")
+        packed, mask = self._mask_argument(mask) if mask is not None else (False, None)
+
         def to_dev(x, dt):
             if isinstance(x, np.ndarray):
                 x = torch.from_numpy(np.ascontiguousarray(x))
@@ -612,6 +636,22 @@ class SparseIndexHIP:
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         counts = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        if mask is not None:
+            if packed:
+                n_bits = self.n_docs
+                words = _mask_words(mask, self.device)
+            else:
+                flags = _to_dev(mask, torch.bool, self.device)
+                n_bits = flags.numel()            # the library compares it with n_docs
+                words = pack_doc_mask(flags)
+            if words.numel() == 0:
+                words = torch.zeros(1, dtype=torch.int32, device=self.device)      # keep a valid pointer
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_sparse_search_masked(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, int(k),
+                                                            float(threshold), _ptr(words), n_bits, int(id_base), int(id_stride),
+                                                            _ptr(scores), _ptr(ids), _ptr(counts), _lib.stream_ptr()),
+                           "sr_sparse_search_masked")
+            return scores, ids, counts
         if subset is not None:
             subset, m = _subset(subset, self.device)
             with torch.cuda.device(self.device):

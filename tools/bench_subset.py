@@ -184,6 +184,87 @@ def sparse_leg(a, dev):
     return out
 
 
+def timed_once(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return out, a.elapsed_time(b)
+
+
+def sparse_routes_leg(a, dev):
+    """The three routes of the sparse subset search, each forced (SR_SUBSET_SPARSE_ROUTE=pairs|array|mask), the rule's own choice and the
+    unrestricted sr_sparse_search of the same index in the same process (which launches the unmasked instantiation of the scorer's
+    kernel), for nq in --sparse-route-nqs and m in --sparse-route-ms, then half the collection and all of it.  The filter is given as a
+    packed bitmap (sr_sparse_search_masked), so a list route's time includes the bitmap -> list expansion.  Per m the legs ALTERNATE:
+    one run of each per round, --reps rounds after one warm-up run each; a leg whose warm-up run takes longer than --slow-ms is timed
+    with --slow-reps runs instead.  The three forced routes must return equal ids and score bits on every cell (asserted)."""
+    from scaling_retriever_amd.scoring import SparseIndexHIP, pack_doc_mask
+    os.environ["SR_DEV_SWITCHES"] = "1"
+    N = max(8 * (a.k + 1024), int(a.n_docs * a.scale))
+    indptr, doc_ids, vals, _ = build_index(a.vocab, N, a.l0_d, dev, 3)
+    idx = SparseIndexHIP(indptr, doc_ids, vals, N, device=dev)
+    legs = ("pairs", "array", "mask", "rule", "unrestricted_search")
+    rows = []
+    for nq in a.sparse_route_nqs:
+        q_indptr, q_cols, q_vals = build_queries(a.vocab, nq, a.l0_q, dev, 4)
+        for m in [x for x in a.sparse_route_ms if x < N // 2] + [N // 2, N]:
+            flags = torch.zeros(N, dtype=torch.bool, device=dev)
+            flags[draw_subset(N, m, dev, m + 1)] = True
+            words = pack_doc_mask(flags)
+
+            def run(leg):
+                if leg in ("pairs", "array", "mask"):
+                    os.environ["SR_SUBSET_SPARSE_ROUTE"] = leg
+                else:
+                    os.environ.pop("SR_SUBSET_SPARSE_ROUTE", None)
+                if leg == "unrestricted_search":
+                    return idx.search(q_indptr, q_cols, q_vals, a.k)
+                return idx.search(q_indptr, q_cols, q_vals, a.k, mask=words)
+            outs, ms, slow = {}, {leg: [] for leg in legs}, {}
+            before = idx.cert_stats()
+            for leg in legs:                                  # warm-up, and which legs are slow
+                outs[leg], first_ms = timed_once(lambda: run(leg))
+                slow[leg] = first_ms > a.slow_ms
+                after = idx.cert_stats()
+                if leg == "mask":
+                    handed_back = after["redone_exact"] - before["redone_exact"]
+                    through_the_scorer = after["queries"] - before["queries"]
+                if leg == "rule":                             # the scorer saw the queries: the rule chose the mask route
+                    rule_chose = "mask" if after["queries"] > before["queries"] else ("array" if m * 16 >= N else "pairs")
+                before = after
+            for r in range(a.reps):
+                for leg in legs:
+                    if not slow[leg] or r < a.slow_reps:
+                        ms[leg].append(timed_once(lambda: run(leg))[1])
+            os.environ.pop("SR_SUBSET_SPARSE_ROUTE", None)
+            row = {"m": m, "nq": nq, "k": a.k}
+            for leg in legs:
+                row[leg] = {"median_ms": round(statistics.median(ms[leg]), 3), "min_ms": round(min(ms[leg]), 3), "max_ms": round(max(ms[leg]), 3),
+                            "runs": len(ms[leg])}
+            row["mask"]["queries_through_the_scorer"] = through_the_scorer
+            row["mask"]["share_handed_back"] = round(handed_back / through_the_scorer, 4) if through_the_scorer else None
+            row["rule_chooses"] = rule_chose
+            for other in ("array", "mask"):
+                assert torch.equal(outs["pairs"][1], outs[other][1]) and torch.equal(outs["pairs"][2], outs[other][2]) and \
+                    torch.equal(outs["pairs"][0].view(torch.int32), outs[other][0].view(torch.int32)), f"routes pairs and {other} differ at nq={nq} m={m}"
+            row["routes_equal_bit_for_bit"] = True
+            fastest = min(row[r_]["median_ms"] for r_ in ("pairs", "array", "mask"))
+            row["rule_over_fastest_forced"] = round(row["rule"]["median_ms"] / fastest, 4)
+            row["mask_over_unrestricted"] = round(row["mask"]["median_ms"] / row["unrestricted_search"]["median_ms"], 4)
+            rows.append(row)
+            print("[sparse routes]", json.dumps(row), file=sys.stderr, flush=True)
+            del flags, words, outs
+    out = {"n_docs": N, "vocab": a.vocab, "postings": int(doc_ids.numel()), "L0_d": a.l0_d, "L0_q": a.l0_q,
+           "kernel": "cert_score_kernel<KS, true> (mask) / sparse_subset_array_kernel (array) / sparse_subset_pairs_kernel (pairs)",
+           "certified_scorer": idx.cert_stats()["present"] == 1, "rows": rows}
+    idx.close()
+    del indptr, doc_ids, vals, idx
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the 8 841 823 documents (both indexes)")
@@ -197,10 +278,12 @@ def main():
     ap.add_argument("--k", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=7, help="timed runs per figure after one warm-up run (median reported)")
     ap.add_argument("--pairs-limit", type=int, default=500_000_000, help="largest nq x m the pair-scorer baseline is run for (12 bytes each)")
-    ap.add_argument("--legs", type=str, default="dense,sparse", help="dense, sparse, dense_routes (both routes of the dense search forced)")
+    ap.add_argument("--legs", type=str, default="dense,sparse", help="dense, sparse, dense_routes (both routes of the dense search forced), sparse_routes (the three routes of the sparse search forced)")
     ap.add_argument("--route-nqs", type=str, default="64,6980")
     ap.add_argument("--route-ms", type=str, default="100000,1000000", help="dense_routes: these, then half the collection and all of it")
-    ap.add_argument("--slow-ms", type=float, default=1000.0, help="dense_routes: a search slower than this is timed with --slow-reps runs")
+    ap.add_argument("--sparse-route-nqs", type=str, default="6980,64")
+    ap.add_argument("--sparse-route-ms", type=str, default="1000,10000,100000,1000000", help="sparse_routes: these, then half the collection and all of it")
+    ap.add_argument("--slow-ms", type=float, default=1000.0, help="dense_routes / sparse_routes: a search slower than this is timed with --slow-reps runs")
     ap.add_argument("--slow-reps", type=int, default=1)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "subset_search.json"))
     a = ap.parse_args()
@@ -208,6 +291,8 @@ def main():
     a.ms = [int(x) for x in a.ms.split(",")]
     a.route_nqs = [int(x) for x in a.route_nqs.split(",")]
     a.route_ms = [int(x) for x in a.route_ms.split(",")]
+    a.sparse_route_nqs = [int(x) for x in a.sparse_route_nqs.split(",")]
+    a.sparse_route_ms = [int(x) for x in a.sparse_route_ms.split(",")]
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     t0 = time.time()
@@ -218,7 +303,7 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             earlier = json.load(f)
-    for leg, fn in (("dense", dense_leg), ("sparse", sparse_leg), ("dense_routes", dense_routes_leg)):
+    for leg, fn in (("dense", dense_leg), ("sparse", sparse_leg), ("dense_routes", dense_routes_leg), ("sparse_routes", sparse_routes_leg)):
         if leg in a.legs.split(","):
             res[leg] = fn(a, dev)
         elif isinstance(earlier.get(leg), dict) and earlier.get("scale") == a.scale:
