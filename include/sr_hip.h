@@ -657,6 +657,37 @@ int sr_attention_varlen(const void* d_qkv, void* d_out, const int32_t* d_cu_seql
 int sr_attention_varlen_f32(const float* d_qkv, float* d_out_f32, void* d_out_planes, int32_t fp32_planes,
                             const int32_t* d_cu_seqlens, const uint8_t* d_key_valid, int32_t B, int32_t num_heads,
                             int32_t num_kv_heads, int32_t head_dim, int32_t max_seqlen, sr_stream stream);
+/* Test-only hooks: what the bf16 regime (fp32_planes = 0) and the two heads launch besides the GEMMs and the attention, each with
+ * the arguments the encoder fills (per-kernel tables and bounds: tests/test_bf16_regime_gpu.py, tests/bf16_regime_cases.py).  Every
+ * call validates its arguments before it touches a device (SR_ERR_INVALID).
+ * sr_rmsnorm_bf16: one launch of the RMSNorm kernel on d_x fp32 [T, H] (H % 4 == 0; H = 256 / 512 / 1024 / 2048 / 3072 / 4096 run
+ *   the register kernels).  d_embed + d_tok_id [T] (both or neither): row t is gathered from d_embed[d_tok_id[t]] first.  d_delta bf16
+ *   [T, H] (or NULL): the pending residual, x = fl(x + delta).  With either, the new row is written back to d_x.  d_norm_w [H]:
+ *   y = (x rsqrt(mean(x^2) + eps)) w goes to d_xn (bf16 [T, H], round to nearest even) and / or d_xn_f32 (fp32 [T, H]); NULL = only
+ *   the residual is added and both outputs must be NULL.
+ * sr_dense_head_pool: the dense head's two launches.  Per token rs = rsqrt(mean(x^2) + eps), inv = 1 / max(|x rs w|, 1e-12)
+ *   (d_stats: [T] pairs of fp32, scratch); d_out fp32 [B, H] = mean over the tokens t of [cu[b], cu[b + 1]) with
+ *   d_pos[t] >= d_pool_start[b] of ((x rs) w) inv, summed in token order; a sequence without such a token gives zeros, T = 0 zeros
+ *   everywhere.
+ * sr_sparse_finish: d_out[i] = log(max(bf16(d_out[i]) scale, 0) + 1) in place over n elements, product and sum in fp32, the
+ *   logarithm in double and rounded once; round_bf16 = 0 leaves out the bf16 rounding of the input (the fp32 regime).
+ * sr_encode_plan: the packing plan of a [B, L] batch, as every sr_encode_* call computes it first.  mode 0 (dense) / 2 (both):
+ *   row b keeps the positions [min(first key, L - len), L), pool_start = L - len; mode 1 (sparse): [first key, last key]; a row
+ *   without a key keeps nothing.  d_row_shift [B] (or NULL, sr_encode_rows): positions and pool_start are counted that many
+ *   columns further left (never below 0).  Written: d_span_start, d_span_len, d_pool_start, d_row_len [B], d_cu_seqlens [B + 1],
+ *   *n_tokens (host), and for the n_tokens packed tokens d_tok_id (clamped into [0, vocab)), d_pos, d_key_valid (uint8) and
+ *   d_seq_of (row index; -2 for a masked position inside the span unless mode 0).  capacity = elements of the four token arrays:
+ *   a batch that packs to more is SR_ERR_INVALID (the [B] arrays and *n_tokens are written, the token arrays are not touched). */
+int sr_rmsnorm_bf16(float* d_x, const float* d_embed, const int32_t* d_tok_id, const void* d_delta, const float* d_norm_w,
+                    void* d_xn, float* d_xn_f32, float eps, int32_t T, int32_t H, sr_stream stream);
+int sr_dense_head_pool(const float* d_x, const float* d_norm_w, const int32_t* d_cu_seqlens, const int32_t* d_pos,
+                       const int32_t* d_pool_start, float eps, int32_t B, int32_t T, int32_t H, void* d_stats, float* d_out,
+                       sr_stream stream);
+int sr_sparse_finish(float* d_out, int64_t n, float scale, int32_t round_bf16, sr_stream stream);
+int sr_encode_plan(const int64_t* d_input_ids, const int64_t* d_attention_mask, int32_t B, int32_t L, int32_t mode, int32_t vocab,
+                   const int32_t* d_row_shift, int32_t* d_span_start, int32_t* d_span_len, int32_t* d_pool_start,
+                   int32_t* d_row_len, int32_t* d_cu_seqlens, int32_t* d_tok_id, int32_t* d_pos, uint8_t* d_key_valid,
+                   int32_t* d_seq_of, int64_t capacity, int64_t* n_tokens, sr_stream stream);
 
 #ifdef __cplusplus
 }

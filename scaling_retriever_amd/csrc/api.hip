@@ -171,3 +171,63 @@ extern "C" int sr_gemm_f16_planes(const void* d_A, const void* d_W, int32_t M, i
     if (epilogue == EPI_SWIGLU_SPLIT_H) { g.out_scale = d_out_scale; g.out_nseg = out_nseg; }
     return launch_gemm_bf16((GemmEpilogue)epilogue, g, (hipStream_t)stream);
 }
+
+// What the bf16 regime (fp32_planes = 0) and the two heads launch besides the GEMMs and the attention, exported for
+// tests/test_bf16_regime_gpu.py: thin calls into the launch functions of encoder.hip with the arguments the encoder fills.
+// Everything is validated before a device is touched.
+extern "C" int sr_rmsnorm_bf16(float* d_x, const float* d_embed, const int32_t* d_tok_id, const void* d_delta, const float* d_norm_w,
+                               void* d_xn, float* d_xn_f32, float eps, int32_t T, int32_t H, sr_stream stream) {
+    SR_REQUIRE(d_x, "sr_rmsnorm_bf16: null pointer");
+    SR_REQUIRE((d_embed == nullptr) == (d_tok_id == nullptr), "sr_rmsnorm_bf16: pass both d_embed and d_tok_id or neither");
+    SR_REQUIRE(d_norm_w || (!d_xn && !d_xn_f32), "sr_rmsnorm_bf16: an output needs d_norm_w (without it the call only adds the residual)");
+    SR_REQUIRE(T >= 0 && H > 0 && H % 4 == 0, "sr_rmsnorm_bf16: bad sizes T=%d H=%d (H must be a multiple of 4)", T, H);
+    SR_REQUIRE((uintptr_t)d_x % 16 == 0 && (uintptr_t)d_embed % 16 == 0 && (uintptr_t)d_norm_w % 16 == 0 && (uintptr_t)d_xn_f32 % 16 == 0 &&
+                   (uintptr_t)d_delta % 8 == 0 && (uintptr_t)d_xn % 8 == 0,
+               "sr_rmsnorm_bf16: d_x, d_embed, d_norm_w and d_xn_f32 must be 16-byte aligned, d_delta and d_xn 8-byte aligned");
+    return launch_rmsnorm(d_x, d_embed, d_tok_id, (const bf16_t*)d_delta, d_norm_w, (bf16_t*)d_xn, d_xn_f32, T, H, eps, (hipStream_t)stream);
+}
+
+extern "C" int sr_dense_head_pool(const float* d_x, const float* d_norm_w, const int32_t* d_cu_seqlens, const int32_t* d_pos,
+                                  const int32_t* d_pool_start, float eps, int32_t B, int32_t T, int32_t H, void* d_stats, float* d_out,
+                                  sr_stream stream) {
+    SR_REQUIRE(d_x && d_norm_w && d_cu_seqlens && d_pos && d_pool_start && d_stats && d_out, "sr_dense_head_pool: null pointer");
+    SR_REQUIRE(B >= 0 && T >= 0 && H > 0 && H % 4 == 0, "sr_dense_head_pool: bad sizes B=%d T=%d H=%d (H must be a multiple of 4)", B, T, H);
+    SR_REQUIRE((uintptr_t)d_x % 16 == 0 && (uintptr_t)d_norm_w % 16 == 0 && (uintptr_t)d_stats % 8 == 0,
+               "sr_dense_head_pool: d_x and d_norm_w must be 16-byte aligned, d_stats 8-byte aligned");
+    if (B == 0) return SR_OK;
+    if (T == 0) {                      // as sr_encode_dense: a batch that packs to no token gives zero vectors
+        SR_CHECK_HIP(hipMemsetAsync(d_out, 0, (size_t)B * H * 4, (hipStream_t)stream));
+        return SR_OK;
+    }
+    return launch_dense_head(d_x, d_norm_w, (float2*)d_stats, d_cu_seqlens, d_pos, d_pool_start, d_out, B, T, H, eps, (hipStream_t)stream);
+}
+
+extern "C" int sr_sparse_finish(float* d_out, int64_t n, float scale, int32_t round_bf16, sr_stream stream) {
+    SR_REQUIRE(d_out, "sr_sparse_finish: null pointer");
+    SR_REQUIRE(n >= 0 && n < ((int64_t)1 << 39), "sr_sparse_finish: bad size n=%lld", (long long)n);
+    SR_REQUIRE(round_bf16 == 0 || round_bf16 == 1, "sr_sparse_finish: round_bf16 must be 0 or 1");
+    if (n == 0) return SR_OK;
+    return launch_sparse_finish(d_out, n, scale, round_bf16, (hipStream_t)stream);
+}
+
+extern "C" int sr_encode_plan(const int64_t* d_input_ids, const int64_t* d_attention_mask, int32_t B, int32_t L, int32_t mode, int32_t vocab,
+                              const int32_t* d_row_shift, int32_t* d_span_start, int32_t* d_span_len, int32_t* d_pool_start,
+                              int32_t* d_row_len, int32_t* d_cu_seqlens, int32_t* d_tok_id, int32_t* d_pos, uint8_t* d_key_valid,
+                              int32_t* d_seq_of, int64_t capacity, int64_t* n_tokens, sr_stream stream) {
+    SR_REQUIRE(d_input_ids && d_attention_mask && d_span_start && d_span_len && d_pool_start && d_row_len && d_cu_seqlens && n_tokens,
+               "sr_encode_plan: null pointer");
+    SR_REQUIRE(capacity >= 0 && (capacity == 0 || (d_tok_id && d_pos && d_key_valid && d_seq_of)), "sr_encode_plan: null token array");
+    SR_REQUIRE(mode >= 0 && mode <= 2, "sr_encode_plan: mode %d (0 dense, 1 sparse, 2 both)", mode);
+    SR_REQUIRE(B >= 1 && B <= 65536 && L >= 1 && vocab >= 1 && (int64_t)B * L < ((int64_t)1 << 31),
+               "sr_encode_plan: bad sizes B=%d L=%d vocab=%d", B, L, vocab);
+    hipStream_t s = (hipStream_t)stream;
+    SR_TRY(launch_plan_rows(d_attention_mask, B, L, mode, d_span_start, d_span_len, d_pool_start, d_row_len, d_row_shift, d_cu_seqlens, s));
+    int T = 0;
+    SR_CHECK_HIP(hipMemcpyAsync(&T, d_cu_seqlens + B, 4, hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    *n_tokens = T;
+    SR_REQUIRE(T <= capacity, "sr_encode_plan: the batch packs to %d tokens, the token arrays hold %lld", T, (long long)capacity);
+    if (T == 0) return SR_OK;
+    return launch_plan_tokens(d_input_ids, d_attention_mask, B, L, d_span_start, d_cu_seqlens, d_tok_id, d_pos, d_key_valid, d_seq_of, vocab,
+                              mode, d_row_shift, s);
+}

@@ -89,6 +89,19 @@ int launch_rows_split_f16(float* x, const float* embed, const int* tok, const fl
                           int nseg, const float* gu_cmax, float* act_sc, float* act_inv, hipStream_t s);
 int launch_gu_cmax(const bf16_t* wgu_s, const float* wgu_i, int I, int K, int nseg, float* cmax, hipStream_t s);
 
+// bf16 regime and heads, for the test hooks of api.hip (the encoder calls the same functions, encoder.hip): RMSNorm with its optional
+// embedding gather / pending bf16 residual / "residual add only" exit, the plan's launches (spans + cu_seqlens, then the per-token
+// arrays), the dense head's two launches (stats: [T] float2 scratch) and the sparse head's finish
+int launch_rmsnorm(float* x, const float* embed, const int* tok_id, const bf16_t* delta, const float* w, bf16_t* xn, float* xn_f32, int T,
+                   int H, float eps, hipStream_t s);
+int launch_plan_rows(const int64_t* mask, int B, int L, int mode, int* span_start, int* span_len, int* pool_start, int* row_len,
+                     const int* row_shift, int* cu, hipStream_t s);
+int launch_plan_tokens(const int64_t* ids, const int64_t* mask, int B, int L, const int* span_start, const int* cu, int* tok_id, int* pos,
+                       unsigned char* key_valid, int* seq_of, int vocab, int mode, const int* row_shift, hipStream_t s);
+int launch_dense_head(const float* x, const float* w, float2* stats, const int* cu, const int* pos, const int* pool_start, float* out,
+                      int B, int T, int H, float eps, hipStream_t s);
+int launch_sparse_finish(float* out, int64_t n, float scale, int round_bf16, hipStream_t s);
+
 struct AttnArgs {
     const bf16_t* qkv;      // [T, (nh + 2*nkv) * hd] packed tokens, q heads then k heads then v heads
     bf16_t* out;            // [T, nh * hd]

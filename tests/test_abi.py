@@ -109,6 +109,61 @@ def test_fp16_plane_hooks_validate_before_they_launch():
     assert rc == _lib.SR_ERR_INVALID and b"null argument" in lib.sr_last_error()
 
 
+def test_bf16_regime_hooks_validate_before_they_launch():
+    """sr_rmsnorm_bf16, sr_dense_head_pool, sr_sparse_finish and sr_encode_plan reject what they cannot run with SR_ERR_INVALID before
+    anything touches a device: the pointers below are never dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    p, odd8, odd16 = ctypes.c_void_p(4096), ctypes.c_void_p(4100), ctypes.c_void_p(4104)
+
+    def norm(**kw):
+        a = dict(dict(x=p, embed=None, tok=None, delta=None, w=p, xn=p, f32=None, eps=1e-5, T=4, H=64), **kw)
+        return lib.sr_rmsnorm_bf16(a["x"], a["embed"], a["tok"], a["delta"], a["w"], a["xn"], a["f32"], a["eps"], a["T"], a["H"], None)
+    for change, text in [(dict(x=None), b"null pointer"), (dict(embed=p), b"both d_embed and d_tok_id"), (dict(tok=p), b"both d_embed and d_tok_id"),
+                         (dict(w=None), b"needs d_norm_w"), (dict(w=None, xn=None, f32=p), b"needs d_norm_w"),
+                         (dict(H=66), b"multiple of 4"), (dict(H=0), b"bad sizes"), (dict(T=-1), b"bad sizes"),
+                         (dict(x=odd16), b"aligned"), (dict(w=odd16), b"aligned"), (dict(f32=odd16), b"aligned"),
+                         (dict(embed=odd16, tok=p), b"aligned"), (dict(delta=odd8), b"aligned"), (dict(xn=odd8), b"aligned")]:
+        rc = norm(**change)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
+    assert norm(T=0) == _lib.SR_OK and norm(T=0, w=None, xn=None, delta=p) == _lib.SR_OK
+
+    def pool(**kw):
+        a = dict(dict(x=p, w=p, cu=p, pos=p, ps=p, eps=1e-5, B=2, T=4, H=64, stats=p, out=p), **kw)
+        return lib.sr_dense_head_pool(a["x"], a["w"], a["cu"], a["pos"], a["ps"], a["eps"], a["B"], a["T"], a["H"], a["stats"], a["out"], None)
+    for change, text in [(dict(x=None), b"null pointer"), (dict(w=None), b"null pointer"), (dict(cu=None), b"null pointer"),
+                         (dict(pos=None), b"null pointer"), (dict(ps=None), b"null pointer"), (dict(stats=None), b"null pointer"),
+                         (dict(out=None), b"null pointer"), (dict(B=-1), b"bad sizes"), (dict(T=-1), b"bad sizes"), (dict(H=0), b"bad sizes"),
+                         (dict(H=130), b"multiple of 4"), (dict(x=odd16), b"aligned"), (dict(w=odd16), b"aligned"), (dict(stats=odd8), b"aligned")]:
+        rc = pool(**change)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
+    assert pool(B=0) == _lib.SR_OK
+
+    for args, text in [((None, 8, 1.0, 1), b"null pointer"), ((p, -1, 1.0, 1), b"bad size"), ((p, 1 << 39, 1.0, 0), b"bad size"),
+                       ((p, 8, 1.0, 2), b"round_bf16"), ((p, 8, 1.0, -1), b"round_bf16")]:
+        rc = lib.sr_sparse_finish(*args, None)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (args, rc, lib.sr_last_error())
+    assert lib.sr_sparse_finish(p, 0, 1.0, 1, None) == _lib.SR_OK
+
+    n = ctypes.c_int64(-1)
+
+    def plan(**kw):
+        a = dict(dict(ids=p, mask=p, B=2, L=8, mode=0, vocab=100, shift=None, st=p, ln=p, ps=p, rl=p, cu=p, tok=p, pos=p, kv=p, sq=p,
+                      cap=16, n=ctypes.byref(n)), **kw)
+        return lib.sr_encode_plan(a["ids"], a["mask"], a["B"], a["L"], a["mode"], a["vocab"], a["shift"], a["st"], a["ln"], a["ps"], a["rl"],
+                                  a["cu"], a["tok"], a["pos"], a["kv"], a["sq"], a["cap"], a["n"], None)
+    for change, text in [(dict(ids=None), b"null pointer"), (dict(mask=None), b"null pointer"), (dict(st=None), b"null pointer"),
+                         (dict(ln=None), b"null pointer"), (dict(ps=None), b"null pointer"), (dict(rl=None), b"null pointer"),
+                         (dict(cu=None), b"null pointer"), (dict(n=None), b"null pointer"),
+                         (dict(tok=None), b"null token array"), (dict(pos=None), b"null token array"), (dict(kv=None), b"null token array"),
+                         (dict(sq=None), b"null token array"), (dict(cap=-1), b"null token array"),
+                         (dict(mode=3), b"mode 3"), (dict(mode=-1), b"mode -1"), (dict(B=0), b"bad sizes"), (dict(L=0), b"bad sizes"),
+                         (dict(vocab=0), b"bad sizes"), (dict(B=65537), b"bad sizes"), (dict(B=65536, L=32768), b"bad sizes")]:
+        rc = plan(**change)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
+    assert n.value == -1
+
+
 def test_attention_bf16_hook_empty_batch_and_head_geometry():
     """sr_attention_varlen: B = 0 is SR_OK, and num_heads that is no multiple of num_kv_heads is SR_ERR_INVALID - both before
     anything touches a device: the pointers below are never dereferenced."""
