@@ -95,14 +95,22 @@ int sr_dense_search(sr_dense_index* idx, const float* d_queries, int64_t nq, int
 /* Arithmetic of the score kernel for query batches > 64:
  *   SR_PRECISION_FP32   (default) exact fp32 MFMA, bit-for-bit a k-ordered fmaf chain;
  *   SR_PRECISION_BF16X3 fp32 operands split into bf16 hi + lo, q.d ~= qh.dh + qh.dl + ql.dh on the
- *                       bf16 MFMA pipe with fp32 accumulation: ~1e-7 relative to the fp32 result
- *                       (the size of an fp32 summation-order change), ~3x faster.  Keeps a
+ *                       bf16 MFMA pipe with fp32 accumulation, ~3x faster.  Per pair, with S = sum_i |q_i d_i|
+ *                       (<= |q||d|): |score - q.d| <= (2 + 2^-6) 2^-16 S from the dropped terms (reached to 3 % by
+ *                       data whose roundings all point one way) + 3.1 dim 2^-24 S from the accumulation of 3 dim
+ *                       exact products: about 2^-15 S, NOT the size of an fp32 summation-order change.  Typical
+ *                       (Gaussian) data shows ~1e-6 |q||d| at dim 256, where the roundings cancel.  Keeps a
  *                       library-owned bf16 copy of every segment (same bytes as the fp32 rows). */
 #define SR_PRECISION_FP32 0
 #define SR_PRECISION_BF16X3 1
 /*   SR_PRECISION_BF16X6 three bf16 planes per operand (the full 24-bit significand), six products:
- *                       the error class of an fp32 dot product (measured vs float64 like the exact
- *                       path), ~1.7x faster than fp32 MFMA; keeps three bf16 planes per segment.  */
+ *                       |score - q.d| <= (1 + 2^-6) 2^-24 S + 6.2 dim 2^-24 S per pair - the error class of an fp32
+ *                       dot product (typical data: ~1e-7 |q||d|); ~1.7x faster than fp32 MFMA; keeps three bf16
+ *                       planes per segment.
+ *   Both: the bounds are derived in tests/dense_split_cases.py and held for every pair by tests/test_dense_split_gpu.py;
+ *   add 2^-134 sum_i (|q_i| + |d_i|) where operands are so small that planes fall under bf16's smallest subnormal.
+ *   A finite operand has finite planes (the first plane saturates at the largest finite bf16 number instead of
+ *   rounding to infinity).  Scores of operands that hold inf or NaN are unspecified in these two modes.          */
 #define SR_PRECISION_BF16X6 2
 /*   SR_PRECISION_FP32_FILTERED  the SAME results as SR_PRECISION_FP32, bit for bit, several times faster for batches
  *                       > 64 queries: one fp16 plane product (fp16 rounding of the query x fp16 rounding of the document,
@@ -462,7 +470,8 @@ typedef struct {
     int32_t fp32_planes;              /* fp32 regime (sr_encode_*_fp32): 0 = not available; 16 = every weight also kept as two
                                          fp16 planes of power-of-two scaled rows (22 significand bits, 3 plane products
                                          per GEMM: truncation below the fp32 accumulation's own rounding); 3 = three bf16
-                                         planes (24 bits, 6 products); 2 = two bf16 planes (3 products, ~2^-17)        */
+                                         planes (24 bits, 6 products); 2 = two bf16 planes (3 products: dropped terms up
+                                         to 2^-15 of sum |a w| per output, see SR_PRECISION_BF16X3)                */
     int32_t attention_bias;           /* 1: q_proj / k_proj / v_proj carry a bias, added before the rotation (Qwen2:
                                          modeling/bidrectional_qwen2.py:68-101, llm_encoder.py:204-209,528-533); the model then
                                          needs model.layers.N.self_attn.{q,k,v}_proj.bias.  0 (Llama): those names are unknown */
@@ -688,6 +697,16 @@ int sr_encode_plan(const int64_t* d_input_ids, const int64_t* d_attention_mask, 
                    const int32_t* d_row_shift, int32_t* d_span_start, int32_t* d_span_len, int32_t* d_pool_start,
                    int32_t* d_row_len, int32_t* d_cu_seqlens, int32_t* d_tok_id, int32_t* d_pos, uint8_t* d_key_valid,
                    int32_t* d_seq_of, int64_t capacity, int64_t* n_tokens, sr_stream stream);
+/* Test-only hook: the plane split of SR_PRECISION_BF16X3 / _BF16X6 on its own (split_bf16_kernel, csrc/dense_split.hip), as
+ * sr_dense_index_set_precision runs it over a segment and every split-mode search over its queries (tests/test_dense_split_gpu.py,
+ * tests/dense_split_cases.py).  d_src fp32 [n], 16-byte aligned, n % 4 == 0; d_p0 and the nullable d_p1, d_p2: bf16 words [n], 8-byte
+ * aligned.  p0 = bf16(v), p1 = bf16(v - p0), p2 = bf16(v - p0 - p1), every rounding to nearest even, both subtractions exact in
+ * fp32; a finite v whose bf16 rounding would be infinite (|v| >= 0x7F7F8000, the top 2^-8 of the top binade) takes the largest
+ * finite bf16 number of its sign as p0, so that the planes of a finite value are finite and p0 + p1 + p2 = v exactly for every
+ * |v| >= 2^-110 (below that the planes lose what lies under bf16's smallest subnormal 2^-133).  Non-finite input is outside the
+ * contract of the split modes.  A null d_src / d_p0, n < 0, n % 4 != 0 or a misaligned pointer is SR_ERR_INVALID before anything
+ * launches; n = 0 is SR_OK.                                                                                                     */
+int sr_split_bf16(const float* d_src, int64_t n, void* d_p0, void* d_p1, void* d_p2, sr_stream stream);
 
 #ifdef __cplusplus
 }

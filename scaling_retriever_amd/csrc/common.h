@@ -123,9 +123,20 @@ __device__ inline unsigned short f32_to_bf16(float f) {
     return __builtin_bit_cast(unsigned short, b);
 }
 
-// fp32 -> three bf16 planes, x = p0 + p1 + p2 up to 2^-27 |x| (each residual subtraction is exact in fp32)
+// The first plane of a split: bf16(f), except that a FINITE f whose rounding is infinite (|f| >= 0x7F7F8000, the top 2^-8 of the top
+// binade) takes the largest finite bf16 number of its sign - else the residual f - inf = -inf makes every product of the row NaN.
+// inf and NaN stay what the cast makes of them.
+__device__ inline unsigned short f32_to_bf16_sat(float f) {
+    const unsigned short h = f32_to_bf16(f);
+    const bool over = (h & 0x7fffu) == 0x7f80u && __builtin_fabsf(f) < __builtin_inff();
+    return over ? (unsigned short)(h - 1) : h;
+}
+
+// fp32 -> three bf16 planes, x = p0 + p1 + p2 exactly for every finite |x| >= 2^-110 (each residual subtraction is exact in fp32, the
+// saturated first residual is below 2^120; below 2^-110 the planes lose what lies under bf16's smallest subnormal 2^-133) - the
+// arithmetic of split_bf16_kernel (dense_split.hip), derivation in tests/dense_split_cases.py
 __device__ inline void split_bf16x3(float v, unsigned short& p0, unsigned short& p1, unsigned short& p2) {
-    p0 = f32_to_bf16(v);
+    p0 = f32_to_bf16_sat(v);
     const float r1 = v - bf16_to_f32(p0);
     p1 = f32_to_bf16(r1);
     const float r2 = r1 - bf16_to_f32(p1);

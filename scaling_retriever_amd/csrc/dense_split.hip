@@ -1,10 +1,17 @@
-// Dense scoring in split-bf16 arithmetic: fp32-class inner products on the bf16 MFMA pipe.
+// Dense scoring in split-bf16 arithmetic: inner products of fp32 operands on the bf16 MFMA pipe.
 //
 // Every fp32 operand is split into bf16 planes, x = p0 + p1 (+ p2), each plane the bf16 rounding of what
-// the previous ones left over (the subtractions are exact in fp32):
-//   bf16x3:  q . d ~= q0.d0 + q0.d1 + q1.d0                        (dropped terms O(2^-17 |q||d|))
-//   bf16x6:  q . d ~= q0.d0 + q0.d1 + q1.d0 + q1.d1 + q0.d2 + q2.d0  (dropped terms O(2^-25): three planes carry
-//            the full 24-bit fp32 significand, so the result is in the error class of an fp32 dot product)
+// the previous ones left over (the subtractions are exact in fp32; a finite x keeps finite planes: p0 saturates
+// instead of rounding to inf; three planes reproduce every |x| >= 2^-110 exactly):
+//   bf16x3:  q . d ~= q0.d0 + q0.d1 + q1.d0
+//   bf16x6:  q . d ~= q0.d0 + q0.d1 + q1.d0 + q1.d1 + q0.d2 + q2.d0
+// Error per pair against the true inner product, derived in tests/dense_split_cases.py (S = sum_i |q_i d_i| <= |q||d|):
+//   bf16x3:  dropped terms <= (2 + 2^-6) 2^-16 S (|x - p0 - p1| <= 2^-17 |x|; reached to 3 %: 1.95 x 2^-16 S when every rounding
+//            points the same way), + the fp32 accumulation of 3 H exact products, <= 3.1 H 2^-24 S.  NOT the error class of an fp32
+//            dot product: 2^-15 S worst case.  Gaussian data shows ~1e-6 |q||d| at H = 256 (the errors cancel).
+//   bf16x6:  dropped terms <= (1 + 2^-6) 2^-24 S, + the accumulation of 6 H exact products, <= 6.2 H 2^-24 S: the error class of an
+//            fp32 dot product.
+//   (+ a floor of 2^-134 sum_i (|q_i| + |d_i|) where planes fall under bf16's smallest subnormal; inf / NaN inputs: unspecified.)
 // Products of bf16 pairs are exact in fp32 and v_mfma_f32_16x16x32_bf16 accumulates in fp32.  The plane pairs are
 // accumulated smallest first.  3 (6) bf16 MFMAs at the 2.5 PF bf16 rate replace one fp32 MFMA at 157 TF.
 //
@@ -24,7 +31,7 @@ __global__ void split_bf16_kernel(const float* __restrict__ src, unsigned short*
         bf16x4 a, b, c;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const unsigned short h = f32_to_bf16(v[e]);
+            const unsigned short h = f32_to_bf16_sat(v[e]);  // a finite value keeps finite planes (common.h)
             const float r1 = v[e] - bf16_to_f32(h);          // exact
             const unsigned short m = f32_to_bf16(r1);
             const float r2 = r1 - bf16_to_f32(m);            // exact
@@ -46,6 +53,16 @@ int launch_split_bf16(const float* src, unsigned short* p0, unsigned short* p1, 
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, p0, p1, p2, n4);
     SR_CHECK_LAUNCH();
     return SR_OK;
+}
+
+// The plane split on its own, exported for tests/test_dense_split_gpu.py: a thin call into launch_split_bf16 with the arguments
+// split_segment / dense_search_pass (dense_score.hip) fill.  Everything is validated before a device is touched.
+extern "C" int sr_split_bf16(const float* d_src, int64_t n, void* d_p0, void* d_p1, void* d_p2, sr_stream stream) {
+    SR_REQUIRE(d_src && d_p0, "sr_split_bf16: null pointer");
+    SR_REQUIRE(n >= 0 && n % 4 == 0, "sr_split_bf16: bad size n=%lld (n must be a multiple of 4)", (long long)n);
+    SR_REQUIRE((uintptr_t)d_src % 16 == 0 && (uintptr_t)d_p0 % 8 == 0 && (uintptr_t)d_p1 % 8 == 0 && (uintptr_t)d_p2 % 8 == 0,
+               "sr_split_bf16: d_src must be 16-byte aligned, the planes 8-byte aligned");
+    return launch_split_bf16(d_src, (unsigned short*)d_p0, (unsigned short*)d_p1, (unsigned short*)d_p2, n, (hipStream_t)stream);
 }
 
 // Tile slot -> (doc tile, query tile).  Workgroups are dealt to the 8 XCDs round-robin by their linear id, every XCD has its

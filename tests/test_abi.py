@@ -164,6 +164,21 @@ def test_bf16_regime_hooks_validate_before_they_launch():
     assert n.value == -1
 
 
+def test_split_bf16_hook_validates_before_it_launches():
+    """sr_split_bf16 rejects what it cannot run with SR_ERR_INVALID before anything touches a device: the pointers below are never
+    dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    p, odd8, odd4 = ctypes.c_void_p(4096), ctypes.c_void_p(4104), ctypes.c_void_p(4100)
+    for args, text in [((None, 8, p, p, p), b"null pointer"), ((p, 8, None, p, p), b"null pointer"), ((p, 8, None, None, None), b"null pointer"),
+                       ((p, 6, p, p, p), b"multiple of 4"), ((p, 1, p, None, None), b"multiple of 4"), ((p, -4, p, p, p), b"bad size"),
+                       ((odd8, 8, p, p, p), b"aligned"), ((p, 8, odd4, p, p), b"aligned"), ((p, 8, p, odd4, p), b"aligned"),
+                       ((p, 8, p, p, odd4), b"aligned")]:
+        rc = lib.sr_split_bf16(*args, None)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (args, rc, lib.sr_last_error())
+    assert lib.sr_split_bf16(p, 0, p, None, None, None) == _lib.SR_OK and lib.sr_split_bf16(p, 0, p, p, p, None) == _lib.SR_OK
+
+
 def test_attention_bf16_hook_empty_batch_and_head_geometry():
     """sr_attention_varlen: B = 0 is SR_OK, and num_heads that is no multiple of num_kv_heads is SR_ERR_INVALID - both before
     anything touches a device: the pointers below are never dereferenced."""
