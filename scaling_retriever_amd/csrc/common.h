@@ -213,6 +213,28 @@ int topk_large_compact(TopkWS& ws, int64_t nq, int k, int64_t select_over, hipSt
 int topk_large_finalize(TopkWS& ws, int64_t nq, int k, float pad_score, float* d_out_scores, int64_t* d_out_ids,
                         int32_t* d_out_counts, hipStream_t s);
 
+// ---- a device buffer a handle owns and reuses: it only ever grows ----
+template <typename T>
+struct DeviceBuf {
+    T* p = nullptr;
+    int64_t cap = 0;      // elements
+    // room for n elements (contents are not kept).  SR_ERR_NOMEM leaves the buffer empty; the message names `who`, or is left to
+    // the caller (who = nullptr: a site with a message of its own, or one that falls back instead of failing)
+    int reserve(int64_t n, const char* who) {
+        if (cap >= n) return SR_OK;
+        release();                                        // hipFree waits for the calls that read it
+        if (hipMalloc((void**)&p, (size_t)n * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            if (who) sr_set_error("%s: out of device memory for %lld bytes", who, (long long)(n * (int64_t)sizeof(T)));
+            return SR_ERR_NOMEM;
+        }
+        cap = n;
+        return SR_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
 // ---- per-launch HIP event log (measurement hook of the search handles) ----
 #include <vector>
 // A search handle owns ONE top-k workspace.  The handle's mutex serialises the host side of concurrent calls; this

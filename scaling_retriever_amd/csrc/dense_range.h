@@ -24,7 +24,7 @@ struct DenseRangeArgs {
     int64_t* out_ids;
     int64_t capacity;
 };
-// query tile: 256 wide for nq > 128, 128 wide below (as dense_search_pass picks its pipelined kernels)
+// query tile: 256 wide for nq > 128, 128 wide below (as launch_dense_exact picks its pipelined kernels)
 static inline int dense_range_query_tile(int64_t nq) { return nq > 128 ? 256 : 128; }
 int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
 int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);

@@ -20,6 +20,7 @@
 //
 // No global atomics anywhere: the result does not depend on the order workgroups run in, two calls give the same bytes.
 #include "dense_range.h"
+#include "dense_index.h"
 
 template <bool FILL, int WN, typename T>
 __device__ __forceinline__ void dense_range_body(const DenseRangeArgs& a) {
@@ -343,5 +344,131 @@ int launch_range_scan(uint32_t* table, int n_chunks, int64_t nq, int64_t* d_lims
     SR_CHECK_LAUNCH();
     hipLaunchKernelGGL(dense_range_lims_kernel, dim3(1), dim3(1024), 0, s, d_lims, nq);
     SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+// ---- host side: count + scan, then fill ---------------------------------------------------------------------------------------
+// Chunk rows of a range search: a multiple of 256 such that the chunks of all segments number at most max_chunks.  *n_chunks = 0: no
+// chunk size gives that few (more segments than max_chunks).
+static int64_t dense_range_chunking(const sr_dense_index* idx, int64_t max_chunks, int64_t want_chunks, int* n_chunks) {
+    int64_t tiles = 0;
+    for (const DenseSegment& seg : idx->segs) tiles += ceil_div64(seg.n, 256);
+    if (want_chunks > max_chunks) want_chunks = max_chunks;
+    if (want_chunks < 1) want_chunks = 1;
+    int64_t chunk_tiles = ceil_div64(tiles, want_chunks);
+    *n_chunks = 0;
+    if ((int64_t)idx->segs.size() > max_chunks) return 0;
+    for (;; ++chunk_tiles) {          // the segments' last chunks are partial: at most segs.size() chunks over the target, a few steps
+        int64_t n = 0;
+        for (const DenseSegment& seg : idx->segs) n += ceil_div64(seg.n, chunk_tiles * 256);
+        if (n <= max_chunks) { *n_chunks = (int)n; return chunk_tiles * 256; }
+    }
+}
+
+static void dense_range_args(const sr_dense_index* idx, const DenseSegment& seg, const float* d_queries, int64_t nq, const float* d_thr,
+                             int chunk_base, DenseRangeArgs& a) {
+    a = DenseRangeArgs{};
+    a.D = seg.rows; a.Q = d_queries; a.thr = d_thr; a.seg_rows = seg.n; a.chunk_rows = idx->range_chunk_rows; a.chunk_base = chunk_base;
+    a.H = idx->dim; a.nq = (int)nq; a.dtype = idx->row_dtype; a.id_base = seg.id_base; a.id_stride = seg.id_stride;
+    a.table = idx->range_tab.p;
+}
+
+extern "C" int sr_dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, int64_t* d_lims,
+                                    int64_t* total, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_count: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_range_count: bad nq=%lld", (long long)nq);
+    SR_REQUIRE(d_lims && total, "sr_dense_range_count: null d_lims or total");
+    SR_REQUIRE(nq == 0 || (d_queries && d_thresholds), "sr_dense_range_count: null queries or thresholds");
+    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_range_count: queries must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->range_nq = -1;
+    *total = 0;
+    if (nq == 0 || idx->ntotal == 0) {
+        SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
+        SR_CHECK_HIP(hipStreamSynchronize(s));
+        idx->range_nq = nq; idx->range_total = 0; idx->range_chunk_rows = 0;
+        idx->range_segs = idx->segs.size(); idx->range_ntotal = idx->ntotal;
+        return SR_OK;
+    }
+    if (idx->ntotal >= (1ll << 32)) {
+        sr_set_error("sr_dense_range_count: %lld documents; the per-chunk counts are 32-bit", (long long)idx->ntotal);
+        return SR_ERR_UNSUPPORTED;
+    }
+    // chunks x query tiles ~ the 2 048 workgroups of a launch of the exact search (dense_search.hip), rounded DOWN: one workgroup per CU and
+    // every workgroup equally long, so 2 048 are 8 full rounds on 256 CUs and a few more would be a ninth, nearly empty one.  The table
+    // (4 bytes per chunk and query) stays within the limit
+    const int64_t qtiles = ceil_div64(nq, dense_range_query_tile(nq));
+    int64_t max_chunks = idx->ws_limit / (4 * nq);
+    if (max_chunks > SR_RANGE_MAX_CHUNKS) max_chunks = SR_RANGE_MAX_CHUNKS;
+    int n_chunks = 0;
+    int64_t chunk_rows = dense_range_chunking(idx, max_chunks, 2048 / qtiles, &n_chunks);
+    if (const char* e = sr_dev_getenv("SR_RANGE_CHUNK_ROWS")) {       // dev switch, read per call: forces the chunk size
+        const int64_t forced = atoll(e);
+        SR_REQUIRE(forced >= 256 && forced % 256 == 0, "SR_RANGE_CHUNK_ROWS=%s must be a positive multiple of 256", e);
+        chunk_rows = forced;
+        int64_t n = 0;
+        for (const DenseSegment& seg : idx->segs) n += ceil_div64(seg.n, forced);
+        n_chunks = n <= max_chunks ? (int)n : 0;
+    }
+    if (n_chunks == 0) {
+        sr_set_error("sr_dense_range_count: the chunk table needs at least %lld bytes of workspace for %lld queries and %zu segments "
+                     "(limit %lld bytes, at most %d chunks)", (long long)(4 * nq * (int64_t)idx->segs.size()), (long long)nq, idx->segs.size(),
+                     (long long)idx->ws_limit, SR_RANGE_MAX_CHUNKS);
+        return SR_ERR_NOMEM;
+    }
+    const int64_t entries = (int64_t)n_chunks * nq;
+    if (idx->range_tab.reserve(entries, nullptr) != SR_OK) {
+        sr_set_error("sr_dense_range_count: out of device memory for the chunk table of %lld bytes", (long long)(entries * 4));
+        return SR_ERR_NOMEM;
+    }
+    StreamOrder::Scope in_order(idx->order, s);
+    idx->range_chunk_rows = chunk_rows;
+    int chunk_base = 0;
+    for (const DenseSegment& seg : idx->segs) {
+        const int n_seg = (int)ceil_div64(seg.n, chunk_rows);
+        DenseRangeArgs a;
+        dense_range_args(idx, seg, d_queries, nq, d_thresholds, chunk_base, a);
+        idx->prof.begin(s);
+        SR_TRY(launch_dense_range_count(a, n_seg, s));
+        idx->prof.end(s, 2.0 * (double)nq * (double)seg.n * idx->dim, (double)seg.n * idx->dim * (double)sr_dtype_size(idx->row_dtype));
+        chunk_base += n_seg;
+    }
+    SR_TRY(launch_range_scan(idx->range_tab.p, n_chunks, nq, d_lims, s));
+    int64_t h_total = 0;
+    SR_CHECK_HIP(hipMemcpyAsync(&h_total, d_lims + nq, 8, hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    *total = h_total;
+    idx->range_nq = nq; idx->range_total = h_total;
+    idx->range_segs = idx->segs.size(); idx->range_ntotal = idx->ntotal;
+    return SR_OK;
+}
+
+extern "C" int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, const int64_t* d_lims,
+                                   float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_fill: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30) && capacity >= 0, "sr_dense_range_fill: bad nq=%lld or capacity=%lld", (long long)nq, (long long)capacity);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SR_REQUIRE(idx->range_nq >= 0, "sr_dense_range_fill: no sr_dense_range_count precedes it on this handle");
+    SR_REQUIRE(idx->range_nq == nq, "sr_dense_range_fill: nq=%lld, the preceding count had %lld", (long long)nq, (long long)idx->range_nq);
+    SR_REQUIRE(idx->range_segs == idx->segs.size() && idx->range_ntotal == idx->ntotal, "sr_dense_range_fill: the index changed since the count");
+    SR_REQUIRE(capacity >= idx->range_total, "sr_dense_range_fill: capacity=%lld is below the count's total of %lld", (long long)capacity,
+               (long long)idx->range_total);
+    if (idx->range_total == 0) return SR_OK;          // nothing to write (also nq = 0, empty index)
+    SR_REQUIRE(d_queries && d_thresholds && d_lims && d_out_scores && d_out_ids, "sr_dense_range_fill: null pointer");
+    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_range_fill: queries must be 16-byte aligned");
+    StreamOrder::Scope in_order(idx->order, s);
+    int chunk_base = 0;
+    for (const DenseSegment& seg : idx->segs) {
+        const int n_seg = (int)ceil_div64(seg.n, idx->range_chunk_rows);
+        DenseRangeArgs a;
+        dense_range_args(idx, seg, d_queries, nq, d_thresholds, chunk_base, a);
+        a.lims = d_lims; a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.capacity = capacity;
+        idx->prof.begin(s);
+        SR_TRY(launch_dense_range_fill(a, n_seg, s));
+        idx->prof.end(s, 2.0 * (double)nq * (double)seg.n * idx->dim, (double)seg.n * idx->dim * (double)sr_dtype_size(idx->row_dtype));
+        chunk_base += n_seg;
+    }
     return SR_OK;
 }

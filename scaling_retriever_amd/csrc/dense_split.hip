@@ -56,7 +56,7 @@ int launch_split_bf16(const float* src, unsigned short* p0, unsigned short* p1, 
 }
 
 // The plane split on its own, exported for tests/test_dense_split_gpu.py: a thin call into launch_split_bf16 with the arguments
-// split_segment / dense_search_pass (dense_score.hip) fill.  Everything is validated before a device is touched.
+// split_segment (dense_index.hip) / dense_pass_16bit (dense_search.hip) fill.  Everything is validated before a device is touched.
 extern "C" int sr_split_bf16(const float* d_src, int64_t n, void* d_p0, void* d_p1, void* d_p2, sr_stream stream) {
     SR_REQUIRE(d_src && d_p0, "sr_split_bf16: null pointer");
     SR_REQUIRE(n >= 0 && n % 4 == 0, "sr_split_bf16: bad size n=%lld (n must be a multiple of 4)", (long long)n);

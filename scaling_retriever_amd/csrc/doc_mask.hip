@@ -1,6 +1,6 @@
 // Document bitmaps (gfx950): list -> bitmap by an atomic-or scatter, bitmap -> ascending list by popcount per word, a scan and an
 // ordered expand.  The reference has no counterpart (DenseFlatIndexer.search_knn, scaling_retriever/indexer.py:191-217, always ranks
-// the whole index); the bitmap is the form faiss offers as IDSelectorBitmap.  sr_dense_search_masked / _subset (dense_score.hip) hold
+// the whole index); the bitmap is the form faiss offers as IDSelectorBitmap.  sr_dense_search_masked / _subset (dense_restrict.hip) hold
 // both forms of a filter: the bitmap feeds the certified filter's masked pass (dense_split_kernel.h), the list the gather kernel.
 #include "doc_mask.h"
 

@@ -377,7 +377,7 @@ bool subset_sparse_use_array(int64_t m, int64_t n_docs) {
     }
     return m * 16 >= n_docs;
 }
-// Where the mask route takes over, as a product bound on nq x m like the dense one (dense_score.hip).  Measured on one MI355X at the config-3
+// Where the mask route takes over, as a product bound on nq x m like the dense one (dense_restrict.hip).  Measured on one MI355X at the config-3
 // shape, 8.84 M documents, k = 1 000 (profiles/subset_search.json, key sparse_routes.rows): the smallest measured m at which the forced
 // mask route beats both list routes, and does so at every larger measured m, is m = 10 000 for nq = 6 980 (mask 43.3 ms, pairs 55.6 ms;
 // at m = 1 000 pairs wins with 7.06 against 41.5 ms) and m = 1 000 000 for nq = 64 (mask 7.72 ms, array 15.7 ms; at m = 100 000 pairs wins

@@ -31,7 +31,7 @@ bf16 number P = (2 - 2^-7) 2^127 of v's sign (saturation; without it r1 = -inf a
   Non-finite v is outside the contract of the split modes.
 
 Tier A, the kernel (bound (G) of bf16_regime_cases.py, reused through its _products).  A mode forms the plane products
-(document plane, query plane) listed in dense_search_pass (csrc/dense_score.hip), in this order:
+(document plane, query plane) listed in dense_pass_16bit (csrc/dense_search.hip), in this order:
 
     bf16x3: (d1,q0) (d0,q1) (d0,q0)              bf16x6: (d2,q0) (d0,q2) (d1,q1) (d1,q0) (d0,q1) (d0,q0)
 
@@ -85,7 +85,7 @@ F32 = np.float32
 F134 = 2.0 ** -134
 MODES = ("bf16x3", "bf16x6")
 N_PLANES = {"bf16x3": 2, "bf16x6": 3}
-# (document plane, query plane) of every product, in the order dense_search_pass accumulates them
+# (document plane, query plane) of every product, in the order dense_pass_16bit accumulates them
 PAIRS = {"bf16x3": ((1, 0), (0, 1), (0, 0)), "bf16x6": ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0))}
 CB = {"bf16x3": (2 + 2.0 ** -6) * 2.0 ** -16, "bf16x6": (1 + 2.0 ** -6) * 2.0 ** -24}
 FITTED_TOL = {"bf16x3": 2.5e-6, "bf16x6": 4e-7}          # x |q| max_j |d_j|: what tests/test_dense_bf16x3_gpu.py asserts on Gaussian data

@@ -64,8 +64,8 @@ def test_python_front_end_rejects_unknown_row_dtype_before_the_gpu():
 
 def test_fp16_dense_kernels_use_no_scratch(tmp_path):
     """The fp16 instantiations hold the same operands as their fp32 twins (narrower loads, widened in registers): none may spill.
-    Checked for every instantiation the default dispatch reaches; dense_score_kernel<2, 2, 4, 4> (a development-switch variant whose
-    fp32 instantiation already keeps one register in scratch) is not one of them."""
+    Checked for every instantiation the default dispatch reaches (the two plain double-buffered tilings behind SR_DENSE_VARIANT=1 are
+    the bit-parity reference of the pipelined kernel, not a product path); no kernel of dense_score.o keeps a register in scratch."""
     csrc = os.path.join(ROOT, "scaling_retriever_amd", "csrc")
     want = {"dense_stream.o": [("dense_stream_kernelILi%dEDF16_" % n, 1) for n in (1, 2, 3, 4)],
             "dense_score.o": [("dense_score_pipe_kernelILi1EDF16_", 1), ("dense_score_pipe_kernelILi2EDF16_", 1),
