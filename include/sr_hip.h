@@ -445,6 +445,55 @@ int sr_sparse_csr_build(const int32_t* d_rows, const int32_t* d_cols, const floa
 int sr_topk_merge(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t nq, int k,
                   float pad_score, float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
 
+/* ---------------------------------------------------------- hybrid fusion ---
+ * The two device steps of the exact hybrid search (scaling_retriever_amd/hybrid.py) around the pair scorers.  No
+ * reference counterpart: its HybridRetriever (scaling_retriever/indexer.py:859-1019) dumps the two heads' runs and fuses nothing.
+ * The two indexes number documents independently: d_d2s int64 [n_d2s] maps a dense position to its sparse position (-1: the document
+ * has no posting), d_s2d int64 [n_s2d] back (-1: no such document).  n_s2d + n_d2s < 2^32 (the tie below is 32 bits of a key).
+ *
+ * sr_hybrid_union: per query the set union of two lists of dense positions as an ascending, duplicate-free CSR.
+ *   list A  d_a_indptr == NULL: d_a_ids int64 [nq, kd], any order, negative entries are padding (a dense top-k), kd <= sr_max_topk()
+ *           - sorted in LDS; else d_a_ids is a CSR over d_a_indptr int64 [nq + 1] of STRICTLY ASCENDING positions of any length
+ *           (range hits; kd is ignored) - only read, never staged: the union is placed by ranks, every A entry binary-searches the
+ *           LDS-resident B and every B entry binary-searches A.
+ *   list B  d_b_spos int64 [nq, ks] SPARSE positions with d_b_counts int32 [nq] valid entries per row (sr_sparse_search's outputs),
+ *           ks <= sr_max_topk(), mapped through d_s2d inside the kernel and sorted in LDS.
+ *   Outputs: d_out_indptr int64 [nq + 1]; d_out_dpos / d_out_spos / d_out_tie int64 [capacity]: the union's dense positions, their
+ *   sparse positions d2s[dpos] and tie = spos where spos >= 0, else n_s2d + dpos (retrieve_fused's tie rule); *total (host) =
+ *   indptr[nq].  Count, device scan, fill: no size is read back before the launches; the call waits for the stream once more at its
+ *   end to read the status and the total (and frees its nq * 8 scratch bytes).  total > capacity: SR_ERR_INVALID, indptr is complete
+ *   and no entry at or beyond capacity was written (nq * (kd + ks), or A's total + nq * ks, always suffices).  A sparse position of B
+ *   that maps to no dense document (outside [0, n_s2d) or s2d = -1), or a position of A at or beyond n_d2s (CSR: or negative):
+ *   SR_ERR_INVALID, found on the device, sr_last_error() names the first offender; the outputs are then not to be used and the
+ *   library stays usable.  An A that is not ascending gives a meaningless union, but no store leaves the query's segment.  nq = 0 is
+ *   legal (indptr[0] = 0).                                                                                                      */
+int sr_hybrid_union(const int64_t* d_a_ids, const int64_t* d_a_indptr, int64_t kd, const int64_t* d_b_spos,
+                    const int32_t* d_b_counts, int64_t ks, const int64_t* d_s2d, int64_t n_s2d, const int64_t* d_d2s,
+                    int64_t n_d2s, int64_t nq, int64_t* d_out_indptr, int64_t* d_out_dpos, int64_t* d_out_spos,
+                    int64_t* d_out_tie, int64_t capacity, int64_t* total, sr_stream stream);
+/* sr_hybrid_rank: per query the top-k of a ragged candidate list of ANY length by (fused descending, tie ascending), where
+ *   fused(p) = f32( f32(w_d * dense[p]) + f32(w_s * sparse'[p]) ),  sparse'[p] = sparse[p] where spos[p] >= 0, else 0.0f
+ * - two rounded products and one rounded sum (compiled with contraction off: the device compiler would turn a*b + c*d into an fma),
+ * the bits of rerank.fused_scores.  Candidates as CSR d_cand_indptr int64 [nq + 1] over d_dpos / d_spos / d_tie int64 and d_dense_scores /
+ * d_sparse_scores fp32 (sr_hybrid_union's outputs and the two pair scorers' over them); ties must be distinct inside a list and lie in
+ * [0, n_s2d + id_end), n_s2d + id_end < 2^32 (checked: SR_ERR_INVALID naming the first offender, found on the device).  The k best by
+ * the 64-bit key (order-preserving fused bits, then the complement of tie) are found by a radix select and sorted in LDS: 1 <= k <=
+ * sr_max_topk(), a larger k is SR_ERR_UNSUPPORTED.  w_d, w_s finite and >= 0.  Outputs d_out_scores fp32 / d_out_ids int64 [nq, k]
+ * (fused scores, dense positions; padding -FLT_MAX, -1) and d_out_counts int32 [nq].
+ * The certificate: with d_D / d_S fp32 [nq] the k'-th scores of the two searches whose lists made the candidates (S = 0.0f for a sparse
+ * list shorter than k') and d_complete uint8 [nq] "the dense list held every document", every document outside both lists has fused <=
+ * B = fused(D, S) (multiplying by a non-negative weight and adding are monotone under round-to-nearest), so d_out_certified int32 [nq] =
+ * complete, or the list holds k candidates and its k-th fused score F_k > B - strictly: at F_k == B an outside document with a smaller
+ * tie could win.  d_out_threshold fp32 [nq] = pred(d*), d* the smallest float with g(d*) = fused(d*, S) >= F_k, found by bisection
+ * over the ordered image of the floats with the same three roundings; -inf where g(-FLT_MAX) >= F_k or the list holds fewer than k
+ * candidates, +inf where not even g(+inf) reaches F_k.  Every document outside the sparse list with fused >= F_k has dense > that
+ * threshold: what sr_dense_range_count / _fill take.  nq = 0 is legal.  Waits for the stream once, to read the status.           */
+int sr_hybrid_rank(const int64_t* d_cand_indptr, const int64_t* d_dpos, const int64_t* d_spos, const int64_t* d_tie,
+                   const float* d_dense_scores, const float* d_sparse_scores, int64_t nq, float w_d, float w_s, int k,
+                   const float* d_D, const float* d_S, const uint8_t* d_complete, int64_t n_s2d, int64_t id_end,
+                   float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, int32_t* d_out_certified,
+                   float* d_out_threshold, sr_stream stream);
+
 /* ---------------------------------------------------------------- encoder ---
  * Replaces LlamaBiDense / LlamaBiSparse .encode / .query_encode / .doc_encode
  * (scaling_retriever/modeling/llm_encoder.py:66-70,186-196,424-443) and the

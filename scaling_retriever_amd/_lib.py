@@ -89,6 +89,10 @@ SIGNATURES = {
     "sr_sparse_csr_build": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
     "sr_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "sr_hybrid_union": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "sr_hybrid_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p,
+                               c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_model_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(SrModelConfig)]),
     "sr_model_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "sr_model_finalize": (c_int, [c_void_p]),

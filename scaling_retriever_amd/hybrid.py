@@ -1,0 +1,212 @@
+"""Exact hybrid search: the certified top-k of the fused dense + sparse score over EVERY document of the dense index.
+
+    fused(p) = f32( f32(w_d * dense(p)) + f32(w_s * sparse(p)) )        (rerank.fused_scores: two roundings, one add)
+
+dense(p) are the bits of DenseIndexHIP.score_pairs, sparse(p) those of SparseIndexHIP.score_pairs at d2s[p] (0.0 for a document without
+a posting); order: fused descending, then tie ascending (tie = sparse position, or len(s2d) + dense position without one) - the rule of
+HybridRetriever.retrieve_fused.  The reference's HybridRetriever (scaling_retriever/indexer.py:859-1019) dumps the two heads' runs and
+fuses nothing; retrieve_fused ranks the union of the two top-k lists, which is not the top-k of the fused score.  This module returns
+that top-k exactly, for every query, by three routes (the argument is in DESIGN.md 4.17):
+
+  first depth    both heads are searched at depths[0] >= k, the union of the two lists (sr_hybrid_union) is re-scored by both pair
+                 scorers and ranked (sr_hybrid_rank).  Every document outside both lists has dense <= D and sparse <= S (the last scores
+                 of the two lists), hence fused <= B = fused(D, S): the union holds the true top-k when its k-th fused score F_k > B.
+  deepening      queries without that certificate are searched again, those alone, at depths[1], depths[2], ...
+  range          queries still open after the last depth: the dense range search above pred(d*), d* the smallest dense score that can
+                 reach F_k next to the sparse bound S, returns every outside document that could enter; those and the sparse list are
+                 re-scored and ranked.  Always terminates; runs in query sub-batches under a byte budget.
+
+All arithmetic is in the HIP kernels; the host only moves rows between rounds.  Not offered: doc-sharded indexes, allow-lists / masks,
+k > sr_max_topk()."""
+import contextlib
+
+import numpy as np
+import torch
+
+from . import _lib
+
+FLT_MAX = float(np.finfo(np.float32).max)
+# device bytes the range route holds per candidate entry of a sub-batch: the hit (score 4 + id 8), the union's three int64 columns, the
+# clamped sparse positions, the two pair scores - rounded up
+CANDIDATE_BYTES = 64
+
+
+def check_arguments(topk, weights):
+    """(k, (w_d, w_s)) of a fused search, or ValueError: topk an integer >= 1, weights two finite numbers >= 0 (as fp32 too).  Touches no
+    device and does not load the library."""
+    try:
+        k = int(topk)
+        if k != topk:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"topk must be an integer >= 1, got {topk!r}") from None
+    if k < 1:
+        raise ValueError(f"topk must be an integer >= 1, got {topk!r}")
+    try:
+        with np.errstate(over="ignore"):                       # a weight beyond float32 becomes inf and is refused below
+            w = tuple(float(np.float32(float(x))) for x in weights)
+    except (TypeError, ValueError):
+        raise ValueError(f"weights must be two numbers, got {weights!r}") from None
+    if len(w) != 2 or not all(np.isfinite(x) and x >= 0.0 for x in w):
+        raise ValueError(f"weights must be two finite numbers >= 0 (in float32), got {weights!r}")
+    return k, w
+
+
+def default_depths(k, max_topk):
+    """4k, 16k, ... while <= max_topk; (k,) when even 4k is beyond it."""
+    out, d = [], 4 * k
+    while d <= max_topk:
+        out.append(d)
+        d *= 4
+    return tuple(out) if out else (k,)
+
+
+def _check_depths(depths, k, max_topk):
+    try:
+        depths = tuple(int(d) for d in depths)
+    except (TypeError, ValueError):
+        raise ValueError(f"depths must be a sequence of integers, got {depths!r}") from None
+    if not depths or any(d < k or d > max_topk for d in depths):
+        raise ValueError(f"every depth must lie in [topk, sr_max_topk()] = [{k}, {max_topk}] (the union is sorted in LDS), got {depths!r}")
+    return depths
+
+
+@contextlib.contextmanager
+def _pair_order(dense, nq):
+    """A dense search whose scores are pair-score bits (include/sr_hip.h sr_dense_score_pairs): batches of <= 64 queries with dim % 256
+    == 0 accumulate in the pair scorer's order only under set_batch_invariant(True), switched on here and put back afterwards."""
+    if nq <= 64 and dense.dim % 256 == 0 and not dense.batch_invariant:
+        dense.set_batch_invariant(True)
+        try:
+            yield
+        finally:
+            dense.set_batch_invariant(False)
+    else:
+        yield
+
+
+def _csr_rows(row_ptr, cols, vals, rows):
+    """The CSR of the given rows (an int64 device tensor), in that order."""
+    starts, lens = row_ptr[rows], row_ptr[rows + 1] - row_ptr[rows]
+    out_ptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=row_ptr.device)
+    out_ptr[1:] = torch.cumsum(lens, 0)
+    total = int(out_ptr[-1])
+    take = torch.repeat_interleave(starts - out_ptr[:-1], lens, output_size=total) + torch.arange(total, device=row_ptr.device)
+    return out_ptr, cols[take], vals[take]
+
+
+def _rescore_and_rank(dense, sparse, q, csr, indptr, dpos, spos, tie, w, k, D, S, complete, n_s2d):
+    dense_s = dense.score_pairs(q, indptr, dpos)
+    if sparse.n_docs > 0:
+        sparse_s = sparse.score_pairs(csr[0], csr[1], csr[2], indptr, torch.clamp(spos, min=0))
+    else:
+        sparse_s = torch.zeros_like(dense_s)
+    from .scoring import hybrid_rank
+    return hybrid_rank(indptr, dpos, spos, tie, dense_s, sparse_s, w, k, D, S, complete, n_s2d, dense.id_end)
+
+
+def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_vals, topk, weights=(1.0, 1.0), depths=None,
+                 fallback_bytes=1 << 30):
+    """dense: DenseIndexHIP in precision "fp32" or "fp32_filtered" (ValueError otherwise: the k'-th dense score must be comparable with
+    pair scores); sparse: SparseIndexHIP; d2s int64 [dense.id_end] / s2d int64 the two position maps on the device (-1: none); queries
+    fp32 [nq, dim] and a CSR over the vocabulary, on the device.  depths (default 4k, 16k, ... <= sr_max_topk()): the search depths of
+    the rounds, each in [topk, sr_max_topk()]; fallback_bytes: the device bytes a sub-batch of the range route may hold (a single query
+    whose candidates alone exceed it: MemoryError naming it).  Returns (scores fp32 [nq, k] padded with -FLT_MAX, dense positions int64
+    [nq, k] padded with -1, counts int32 [nq]) as numpy arrays and stats = {"depth": int64 [nq] the index into depths at which the
+    query was certified, -1 = range route; "union": int64 [nq] candidates ranked for it; "range_hits": int64 [nq]; "depths": the
+    schedule} - the exact top-k of the fused score for every query, whatever route served it."""
+    k, w = check_arguments(topk, weights)
+    if dense.precision not in ("fp32", "fp32_filtered"):
+        raise ValueError(f"search_fused needs a dense index whose search returns the exact kernel's bits (precision 'fp32' or 'fp32_filtered'), "
+                         f"this one is in {dense.precision!r}")
+    max_topk = int(_lib.load().sr_max_topk())
+    if k > max_topk:
+        raise ValueError(f"search_fused: topk = {k} is beyond sr_max_topk() = {max_topk}")
+    depths = default_depths(k, max_topk) if depths is None else _check_depths(depths, k, max_topk)
+    from .scoring import hybrid_union
+    dev = dense.device
+    q = dense_queries.to(device=dev, dtype=torch.float32).contiguous()
+    row_ptr, cols, vals = (q_row_ptr.to(device=dev, dtype=torch.int64), q_cols.to(device=dev, dtype=torch.int32),
+                           q_vals.to(device=dev, dtype=torch.float32))
+    nq, N = q.shape[0], dense.ntotal
+    if row_ptr.numel() != nq + 1:
+        raise ValueError(f"{nq} dense queries, {row_ptr.numel() - 1} sparse queries")
+    d2s, s2d = d2s.to(device=dev, dtype=torch.int64).contiguous(), s2d.to(device=dev, dtype=torch.int64).contiguous()
+    if d2s.numel() != dense.id_end:
+        raise ValueError(f"d2s holds {d2s.numel()} entries, the dense index numbers its documents in [0, {dense.id_end})")
+    n_s2d = s2d.numel()
+    scores = torch.full((nq, k), -FLT_MAX, dtype=torch.float32, device=dev)
+    ids = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+    counts = torch.zeros((nq,), dtype=torch.int32, device=dev)
+    stats = {"depth": np.full(nq, -1, np.int64), "union": np.zeros(nq, np.int64), "range_hits": np.zeros(nq, np.int64), "depths": depths}
+
+    def result():
+        return scores.cpu().numpy(), ids.cpu().numpy(), counts.cpu().numpy(), stats
+    if nq == 0 or N == 0:
+        stats["depth"][:] = 0
+        return result()
+
+    def store(rows, keep, out):
+        scores[rows], ids[rows], counts[rows] = out[0][keep], out[1][keep], out[2][keep]
+
+    pending = torch.arange(nq, device=dev)
+    open_lists = None
+    for depth_i, depth in enumerate(depths):
+        n = pending.numel()
+        if n == 0:
+            break
+        qs, csr = q[pending].contiguous(), _csr_rows(row_ptr, cols, vals, pending)
+        kd, ks = min(depth, N), min(depth, max(1, sparse.n_docs))
+        with _pair_order(dense, n):
+            ds, di = dense.search(qs, kd)
+        ss, si, sc = sparse.search(csr[0], csr[1], csr[2], ks, threshold=0.0)
+        D = ds[:, kd - 1].contiguous()
+        S = torch.where(sc == ks, ss[:, ks - 1], torch.zeros_like(D))      # a shorter list: every document outside it scores <= 0
+        complete = torch.full((n,), kd >= N, dtype=torch.bool, device=dev)
+        indptr, dpos, spos, tie = hybrid_union(di, si, sc, s2d, d2s)
+        out = _rescore_and_rank(dense, sparse, qs, csr, indptr, dpos, spos, tie, w, k, D, S, complete, n_s2d)
+        certified = out[3] != 0
+        rows = pending[certified]
+        store(rows, certified, out)
+        rows_h, lens = rows.cpu().numpy(), (indptr[1:] - indptr[:-1])[certified].cpu().numpy()
+        stats["depth"][rows_h], stats["union"][rows_h] = depth_i, lens
+        still = ~certified
+        open_lists = (out[4][still].contiguous(), si[still].contiguous(), sc[still].contiguous())
+        pending = pending[still]
+
+    if pending.numel():
+        # the range route.  Uncertified means g(D) >= F_k, so d* <= D: the dense list of the last depth lies inside the hits.
+        thr, si, sc = open_lists
+        qs = q[pending].contiguous()
+        qs, thr, lims, total = dense.range_count(qs, thr)
+        lens = (lims[1:] - lims[:-1]).cpu().numpy()
+        pend_h = pending.cpu().numpy()
+        need = (lens + si.shape[1]) * CANDIDATE_BYTES
+        groups, g0, held = [], 0, 0
+        for i in range(len(need)):
+            if need[i] > fallback_bytes:
+                raise MemoryError(f"search_fused: query {int(pend_h[i])} alone needs {int(need[i])} bytes on the range route ({int(lens[i])} dense "
+                                  f"range hits), fallback_bytes is {int(fallback_bytes)}")
+            if held + need[i] > fallback_bytes:
+                groups.append((g0, i))
+                g0, held = i, 0
+            held += need[i]
+        groups.append((g0, len(need)))
+        for g0, g1 in groups:
+            if len(groups) == 1:
+                gq, glims = qs, lims
+                _, hit_ids = dense.range_fill(qs, thr, lims, total)
+            else:
+                gq, gthr, glims, gtotal = dense.range_count(qs[g0:g1], thr[g0:g1])
+                _, hit_ids = dense.range_fill(gq, gthr, glims, gtotal)
+            rows = pending[g0:g1]
+            csr = _csr_rows(row_ptr, cols, vals, rows)
+            indptr, dpos, spos, tie = hybrid_union(hit_ids, si[g0:g1], sc[g0:g1], s2d, d2s, a_indptr=glims)
+            n = g1 - g0
+            zero = torch.zeros((n,), dtype=torch.float32, device=dev)
+            out = _rescore_and_rank(dense, sparse, gq, csr, indptr, dpos, spos, tie, w, k, zero, zero,
+                                    torch.ones((n,), dtype=torch.bool, device=dev), n_s2d)      # no certificate is needed here
+            store(rows, slice(None), out)
+            stats["union"][pend_h[g0:g1]] = (indptr[1:] - indptr[:-1]).cpu().numpy()
+            stats["range_hits"][pend_h[g0:g1]] = lens[g0:g1]
+    return result()

@@ -970,6 +970,10 @@ class ShardedSparseRetrieval(SparseRetrieval):
         raise NotImplementedError("ShardedSparseRetrieval.range_search: a range search is not offered on a doc-sharded index; "
                                   "search one merged index with SparseRetrieval instead")
 
+    def search_fused(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetrieval.search_fused: the exact fused search is not offered on a doc-sharded index; "
+                                  "use HybridRetriever over one merged index")
+
     def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when
         `q_loader.replicated` is set."""
@@ -1190,3 +1194,44 @@ class HybridRetriever(SparseRetrieval):
         tie = torch.where(spos_t >= 0, spos_t, int(s2d.numel()) + dpos_t)
         return ranked_run(qids, fused_scores(dense_s, sparse_s, weights), dpos_t, tie, torch.from_numpy(indptr).to(self._dev),
                           self.dense_index.run_table())
+
+    def search_fused(self, sparse_query_vecs, dense_query_vecs, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, qids=None,
+                     allowed_ids=None):
+        """The EXACT top-k of the fused score of retrieve_fused over every document of the dense index (hybrid.search_fused: the
+        union of the two heads' lists at depth depths[0] >= topk where a certificate proves it holds the true top-k, deeper lists
+        for the queries it does not, a dense range search for what is left; the same result whatever route served a query).
+        Returns (RunResult, stats): rows of (fused score, document) by fused descending, ties by sparse-index position ascending
+        (documents without a posting after the indexed ones); stats = {"depth": per query the index into `depths` at which it was
+        certified, -1 = range route; "union": candidates ranked; "range_hits"; "depths"}.  qids (None: 0 .. nq - 1) name the rows.
+        topk >= 1 and two finite weights >= 0, else ValueError before any device work; the dense index must be in precision fp32 /
+        fp32_filtered (ValueError).  Not supported (NotImplementedError): allowed_ids, and the doc-sharded classes."""
+        from . import hybrid
+        hybrid.check_arguments(topk, weights)
+        if allowed_ids is not None:
+            raise NotImplementedError("HybridRetriever.search_fused: an allow-list (allowed_ids) is not supported by the exact fused search; "
+                                      "retrieve_fused(allowed_ids=...) ranks the union of the two restricted lists")
+        q = _as_query_csr(sparse_query_vecs, self._dev)
+        d2s, s2d = self._position_maps()
+        if isinstance(dense_query_vecs, torch.Tensor):
+            dq = dense_query_vecs.to(device=self._dev, dtype=torch.float32)
+        else:
+            dq = torch.from_numpy(np.ascontiguousarray(dense_query_vecs, dtype=np.float32)).to(self._dev)
+        scores, positions, counts, stats = hybrid.search_fused(self.dense_index.index, self.hip_index, d2s, s2d, dq, q.row_ptr, q.cols, q.vals,
+                                                               topk, weights=weights, depths=depths, fallback_bytes=fallback_bytes)
+        qids = list(range(dq.shape[0])) if qids is None else qids
+        return RunResult(qids, scores, positions, self.dense_index.run_table(), counts), stats
+
+    def retrieve_fused_exact(self, q_loader, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, allowed_ids=None):
+        """Encodes the queries once (both heads) and writes {out_dir}/fused_exact/run.json, next to the two heads' runs: the exact
+        fused top-k of search_fused.  Returns (RunResult, stats).  The files of retrieve / retrieve_fused are not touched."""
+        from . import hybrid
+        hybrid.check_arguments(topk, weights)
+        if allowed_ids is not None:
+            raise NotImplementedError("HybridRetriever.retrieve_fused_exact: an allow-list (allowed_ids) is not supported")
+        sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
+        res, stats = self.search_fused(sparse_query_vecs, dense_query_vecs, topk, weights=weights, depths=depths,
+                                       fallback_bytes=fallback_bytes, qids=qids)
+        out_dir = os.path.join(os.path.dirname(self.sparse_out_dir), "fused_exact")
+        os.makedirs(out_dir, exist_ok=True)
+        res.dump(os.path.join(out_dir, "run.json"))
+        return res, stats

@@ -182,6 +182,8 @@ class DenseIndexHIP:
         self._h = ctypes.c_void_p()
         _lib.check(self.lib.sr_dense_index_create(ctypes.byref(self._h), self.dim), "sr_dense_index_create")
         self._segments = []  # keeps the device tensors alive (the C side holds non-owning views)
+        self.precision = "fp32"          # what set_precision / set_batch_invariant last set (the C ABI has no getters)
+        self.batch_invariant = False
 
     @staticmethod
     def _round_to_f16(rows, row0=0):
@@ -357,6 +359,7 @@ class DenseIndexHIP:
         """One k order for every batch size: a query's results are the same bits alone and inside any batch (batches of <= 64
         queries then run the tiled kernels instead of the streaming one, ~4.4 instead of ~5.9 TB/s).  Off by default."""
         _lib.check(self.lib.sr_dense_index_set_batch_invariant(self._h, 1 if on else 0))
+        self.batch_invariant = bool(on)
 
     def set_precision(self, mode):
         """"fp32" (default: the exact kernel), "fp32_filtered" (the same results bit for bit through a certified fp16 filter +
@@ -365,6 +368,7 @@ class DenseIndexHIP:
         code = {"fp32": 0, "bf16x3": 1, "bf16x6": 2, "fp32_filtered": 3}[mode]
         with torch.cuda.device(self.device):
             _lib.check(self.lib.sr_dense_index_set_precision(self._h, code), "sr_dense_index_set_precision")
+        self.precision = mode
 
     def filter_stats(self):
         """(searches answered by the certified filter alone, searches where some or all queries were re-done by the exact kernel)."""
@@ -434,6 +438,15 @@ class DenseIndexHIP:
         scores fp32 [total], ids int64 [total]) as cuda tensors: the documents of query q with score > thresholds[q] are entries
         lims[q]:lims[q + 1], in (segment, row) order - ascending id for segments added in id order.  Scores are the exact chain of
         `score_pairs` for every nq.  sort=True: each list by score descending, ties by ascending id (range_sort)."""
+        queries, thr, lims, n = self.range_count(queries, thresholds)
+        scores, ids = self.range_fill(queries, thr, lims, n)
+        if sort:
+            scores, ids = range_sort(lims, scores, ids)
+        return lims, scores, ids
+
+    def range_count(self, queries, thresholds):
+        """The first half of range_search (sr_dense_range_count): returns (queries, thresholds [nq], lims int64 [nq + 1], total) - the
+        contiguous tensors range_fill takes, and the sizes of the lists before anything of their size is allocated."""
         if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
         if not queries.is_cuda or queries.device != self.device:
@@ -451,15 +464,16 @@ class DenseIndexHIP:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.sr_dense_range_count(self._h, _ptr(queries), nq, _ptr(thr), _ptr(lims), ctypes.byref(total),
                                                      _lib.stream_ptr()), "sr_dense_range_count")
-            n = total.value
-            scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
-            ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
-            _lib.check(self.lib.sr_dense_range_fill(self._h, _ptr(queries), nq, _ptr(thr), _ptr(lims), _ptr(scores), _ptr(ids), n,
+        return queries, thr, lims, total.value
+
+    def range_fill(self, queries, thr, lims, n):
+        """The second half (sr_dense_range_fill) for what the preceding range_count on this index returned: (scores fp32 [n], ids int64 [n])."""
+        scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
+        ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sr_dense_range_fill(self._h, _ptr(queries), queries.shape[0], _ptr(thr), _ptr(lims), _ptr(scores), _ptr(ids), n,
                                                     _lib.stream_ptr()), "sr_dense_range_fill")
-        scores, ids = scores[:n], ids[:n]
-        if sort:
-            scores, ids = range_sort(lims, scores, ids)
-        return lims, scores, ids
+        return scores[:n], ids[:n]
 
     def score_pairs(self, queries, cand_indptr, cand_ids):
         """Exact scores of given (query, document) pairs: queries fp32 cuda [nq, dim]; the candidates of query q are
@@ -780,3 +794,77 @@ def topk_merge(scores, ids, pad_score=-3.402823466e38):
     _lib.check(lib.sr_topk_merge(_ptr(scores), _ptr(ids), W, nq, k, float(pad_score), _ptr(out_s), _ptr(out_i),
                                  _lib.stream_ptr()), "sr_topk_merge")
     return out_s, out_i
+
+
+def hybrid_union(a_ids, b_spos, b_counts, s2d, d2s, a_indptr=None):
+    """Per query the set union of two lists of dense positions (sr_hybrid_union, csrc/hybrid_fuse.hip), all cuda tensors: a_ids int64
+    [nq, kd] with negative padding in any order (a dense top-k, kd <= sr_max_topk()) - or, with a_indptr int64 [nq + 1], a CSR of
+    strictly ascending positions of any length (range hits); b_spos int64 [nq, ks] SPARSE positions with b_counts int32 [nq] valid
+    entries per row (ks <= sr_max_topk()), mapped through s2d on the device; d2s / s2d the two position maps (int64, -1 = none).
+    Returns (indptr int64 [nq + 1], dpos, spos, tie int64 [total]): each query's union ascending and duplicate-free, spos = d2s[dpos],
+    tie = spos where spos >= 0 else len(s2d) + dpos.  A sparse position without a dense document: ValueError naming it."""
+    _lib.require_gpu()
+    dev = b_spos.device
+    b_spos = b_spos.to(torch.int64).contiguous()
+    b_counts = b_counts.to(device=dev, dtype=torch.int32).contiguous()
+    s2d, d2s = s2d.to(device=dev, dtype=torch.int64).contiguous(), d2s.to(device=dev, dtype=torch.int64).contiguous()
+    if b_spos.dim() != 2 or b_counts.dim() != 1 or b_counts.numel() != b_spos.shape[0]:
+        raise ValueError(f"expected b_spos [nq, ks] and b_counts [nq], got {tuple(b_spos.shape)} and {tuple(b_counts.shape)}")
+    nq, ks = b_spos.shape
+    a_ids = a_ids.to(device=dev, dtype=torch.int64).contiguous()
+    if a_indptr is None:
+        if a_ids.dim() != 2 or a_ids.shape[0] != nq:
+            raise ValueError(f"expected a_ids [{nq}, kd], got {tuple(a_ids.shape)}")
+        kd = a_ids.shape[1]
+        capacity = nq * (kd + ks)
+    else:
+        a_indptr = a_indptr.to(device=dev, dtype=torch.int64).contiguous()
+        if a_ids.dim() != 1 or a_indptr.dim() != 1 or a_indptr.numel() != nq + 1:
+            raise ValueError(f"expected a CSR over {nq} queries, got a_indptr {tuple(a_indptr.shape)} and a_ids {tuple(a_ids.shape)}")
+        if int(a_indptr[-1]) != a_ids.numel() or int(a_indptr[0]) != 0:      # the kernels trust a_indptr for the extent of a_ids
+            raise ValueError(f"a_indptr runs from {int(a_indptr[0])} to {int(a_indptr[-1])}, a_ids holds {a_ids.numel()} positions")
+        kd = 0
+        capacity = a_ids.numel() + nq * ks
+    indptr = torch.empty((nq + 1,), dtype=torch.int64, device=dev)
+    out = torch.empty((3, max(1, capacity)), dtype=torch.int64, device=dev)
+    keep = [t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev) for t in (a_ids, b_spos, b_counts, s2d, d2s)]      # valid pointers
+    p = [_ptr(t) for t in keep]
+    total = ctypes.c_int64(0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sr_hybrid_union(p[0], _ptr(a_indptr), kd, p[1], p[2], ks, p[3], s2d.numel(), p[4], d2s.numel(), nq,
+                                               _ptr(indptr), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), capacity, ctypes.byref(total),
+                                               _lib.stream_ptr()), "sr_hybrid_union")
+    n = total.value
+    return indptr, out[0, :n], out[1, :n], out[2, :n]
+
+
+def hybrid_rank(cand_indptr, dpos, spos, tie, dense_scores, sparse_scores, weights, k, D, S, complete, n_s2d, id_end):
+    """Top-k of ragged candidate lists by (fused descending, tie ascending), the certificate and the range threshold (sr_hybrid_rank,
+    csrc/hybrid_fuse.hip): cuda tensors as hybrid_union and the two score_pairs return them; weights (w_d, w_s); D, S fp32 [nq] the
+    k'-th scores of the two searches, complete bool [nq] = the dense list held every document.  Returns (scores fp32 [nq, k] padded
+    with -FLT_MAX, dense positions int64 [nq, k] padded with -1, counts int32 [nq], certified int32 [nq], threshold fp32 [nq])."""
+    _lib.require_gpu()
+    dev = cand_indptr.device
+    nq = cand_indptr.numel() - 1
+    i64 = [t.to(device=dev, dtype=torch.int64).contiguous() for t in (cand_indptr, dpos, spos, tie)]
+    f32 = [t.to(device=dev, dtype=torch.float32).contiguous() for t in (dense_scores, sparse_scores, D, S)]
+    complete = complete.to(device=dev, dtype=torch.uint8).contiguous()
+    total = i64[1].numel()
+    if any(t.numel() != total for t in (i64[2], i64[3], f32[0], f32[1])) or any(t.numel() != nq for t in (f32[2], f32[3], complete)):
+        raise ValueError("hybrid_rank: the candidate arrays must share one length, and D, S, complete hold one entry per query")
+    if nq < 0 or (nq > 0 and int(i64[0][-1]) != total):      # the kernel trusts cand_indptr for the extent of the candidate arrays
+        raise ValueError(f"hybrid_rank: cand_indptr must hold nq + 1 >= 1 offsets ending at the {total} candidates")
+    k = int(k)
+    out_s = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+    out_i = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+    counts = torch.empty((nq,), dtype=torch.int32, device=dev)
+    cert = torch.empty((nq,), dtype=torch.int32, device=dev)
+    thr = torch.empty((nq,), dtype=torch.float32, device=dev)
+    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)      # noqa: E731  (valid pointers)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sr_hybrid_rank(_ptr(i64[0]), _ptr(one(i64[1])), _ptr(one(i64[2])), _ptr(one(i64[3])), _ptr(one(f32[0])),
+                                              _ptr(one(f32[1])), nq, float(weights[0]), float(weights[1]), k, _ptr(one(f32[2])),
+                                              _ptr(one(f32[3])), _ptr(one(complete)), int(n_s2d), int(id_end), _ptr(one(out_s)),
+                                              _ptr(one(out_i)), _ptr(one(counts)), _ptr(one(cert)), _ptr(one(thr)), _lib.stream_ptr()),
+                   "sr_hybrid_rank")
+    return out_s, out_i, counts, cert, thr
