@@ -387,8 +387,8 @@ int sr_sparse_index_profile_read(sr_sparse_index* idx, int64_t* n_launches, doub
 int sr_sparse_index_block_stats(sr_sparse_index* idx, int64_t* n_dense_terms, int64_t* n_block_calls,
                                 int64_t* n_fallback_calls);
 
-/* The certified two-stage scorer (csrc/sparse_cert.hip).  For an index without negative values sr_sparse_index_create also
- * builds: fp16 MFMA tiles of the heaviest terms, 4-byte packed postings, a per-term table of doc-tile boundaries and a
+/* The certified two-stage scorer (csrc/sparse_cert.hip; its index-side structures: csrc/sparse_cert_build.hip).  For an
+ * index without negative values sr_sparse_index_create also builds: fp16 MFMA tiles of the heaviest terms, 4-byte packed postings, a per-term table of doc-tile boundaries and a
  * doc-major forward index.  sr_sparse_search then scores every (query, doc) approximately with a proven error bound (matrix
  * pipe for the heavy terms, 16-bit fixed-point LDS atomics for the others), keeps the k + 1024 best keys, certifies that the
  * true top-k lies among them, re-scores those candidates with the reference's exact fp32 chain

@@ -217,19 +217,12 @@ __global__ void sparse_pairs_query_kernel(const int64_t* __restrict__ q_indptr, 
 // idx->pair_qflags[q] for the nq queries of a call (grown on demand): may the forward route serve query q
 int sparse_pair_query_flags(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, int64_t nq, const char* who,
                             hipStream_t s) {
-    if (idx->pair_qflags_cap < nq) {
-        if (idx->pair_qflags) (void)hipFree(idx->pair_qflags);
-        idx->pair_qflags = nullptr; idx->pair_qflags_cap = 0;
-        if (hipMalloc((void**)&idx->pair_qflags, (size_t)nq) != hipSuccess) {
-            (void)hipGetLastError();
-            idx->pair_qflags = nullptr;
-            sr_set_error("%s: out of device memory for %lld query flags", who, (long long)nq);
-            return SR_ERR_NOMEM;
-        }
-        idx->pair_qflags_cap = nq;
+    if (idx->pair_qflags.reserve(nq, nullptr) != SR_OK) {
+        sr_set_error("%s: out of device memory for %lld query flags", who, (long long)nq);
+        return SR_ERR_NOMEM;
     }
     hipLaunchKernelGGL(sparse_pairs_query_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, s, d_q_indptr, d_q_cols, nq,
-                       idx->n_terms, idx->pair_qflags);
+                       idx->n_terms, idx->pair_qflags.p);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }
@@ -279,7 +272,7 @@ extern "C" int sr_sparse_score_pairs(sr_sparse_index* idx, const int64_t* d_q_in
     a.q_ascending = nullptr;
     if (a.fwd_indptr) {
         SR_TRY(sparse_pair_query_flags(idx, d_q_indptr, d_q_cols, nq, "sr_sparse_score_pairs", s));
-        a.q_ascending = idx->pair_qflags;
+        a.q_ascending = idx->pair_qflags.p;
     }
     a.q_indptr = d_q_indptr; a.q_cols = d_q_cols; a.q_vals = d_q_vals; a.nq = nq;
     a.cand_indptr = d_cand_indptr; a.cand_ids = d_cand_ids; a.out = d_out_scores; a.st = idx->pair_status;

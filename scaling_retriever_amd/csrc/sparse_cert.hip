@@ -28,14 +28,12 @@
 //    a doc-major forward index, and the exact top-k of those is the result - bit for bit what the exact kernels return.
 //    Anything else - a query outside the preconditions (negative / unordered / too many terms), a band that does not fit,
 //    fewer than k docs with a non-zero key, an overflowing candidate buffer - is flagged and served by the exact kernels.
-#include "sparse_index.h"
+#include "sparse_cert.h"
 #include <algorithm>
 #include <math.h>
 #include <vector>
 
-#define SC_DT 1024                    // docs per tile
 #define SC_QB 32                      // queries per workgroup (one MFMA N block)
-#define SC_MB (SC_DT / 32)            // 32-doc M blocks per tile
 #define SC_PITCH_W (SC_DT / 2 + 2)    // 32-bit words per query row of the LDS tile (two 16-bit slots per word; + 2: bank spread)
 #define SC_MAXR 64                    // rare terms per group: one lane of a scatter wave each
 #define SC_MAXG 4                     // groups per query: the first runs through the staged, flattened walk, the others (queries with more than 64
@@ -44,8 +42,6 @@
 #define SC_BAND 1024                  // keys kept beyond k
 #define SC_CAND_CAP 16384             // candidate slots per query and launch
 #define SC_MAXQT 256                  // terms of a fast-path query
-#define SC_TMAX 128                   // dense terms (MFMA K), at most: 8 k-steps of B fragments in registers, 8 KB of them in LDS
-#define SC_FWD_MAX 1024               // postings per doc the forward-index sort handles
 #ifndef SC_DIAG
 #define SC_DIAG 0                     // timing-only variants (tools/micro/cert_diag.sh, wrong results): 1 no posting work, 2 no MFMA work, 4 no table lookups, 8 no LDS adds, 16 plain LDS read-modify-write, 32 no MFMA (operand loads stay), 64 no operand loads (MFMAs stay)
 #endif
@@ -55,357 +51,6 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-
-struct SparseCert {
-    int T = 0, KS = 0;                // dense terms (multiple of 16) and MFMA k-steps
-    int n_tiles = 0;
-    float vscale = 1.f;               // power of two applied to the values before the fp16 rounding
-    int32_t* dslot = nullptr;         // [V] dense slot of a term, -1 = rare
-    float* vmax = nullptr;            // [V] largest value of a posting list
-    _Float16* d16 = nullptr;          // [n_tiles][SC_MB][KS][64][8]: MFMA A fragments (row = doc, k = dense slot); a matrix wave streams 4 KS KB per tile
-    uint32_t* P = nullptr;            // [nnz] packed postings: (doc % SC_DT / 2) * 4 | doc % 2  (byte offset of the doc's LDS word | its half) | fp16(v * vscale) << 16
-    uint32_t* S = nullptr;            // [V][n_tiles + 1]: first posting (absolute index) of term t with doc >= tile * SC_DT
-    uint32_t* E = nullptr;            // [V][e_stride]: the run of term t inside tile i in one word: 0 = empty, a packed posting | 2 = its only
-                                      // posting, 0xffff0000 | length = two or more postings (in P from the running start on)
-    int e_stride = 0;                 // n_tiles rounded up to 4, + 4: 16-byte rows, a 16-byte read never leaves its row
-    int64_t* fwd_indptr = nullptr;    // doc-major forward index, terms ascending inside a doc
-    uint64_t* fwd_tv = nullptr;       // [nnz] term << 32 | value bits: one 16-byte load per lane brings two postings of a row
-    // per-call plan (grown on demand)
-    int64_t nq_cap = 0;
-    _Float16* bfrag = nullptr;        // [nq_pad / 32][KS][64][8]: MFMA B fragments (k = dense slot, col = query)
-    int32_t* rare_term = nullptr;     // [nq_pad][SC_MAXRT], -1 = none
-    float* rare_w = nullptr;          // [nq_pad][SC_MAXRT]: q_t * s_q * 65535 / vscale
-    float* cq = nullptr;              // [nq_pad]: MFMA sum -> [0, 1]
-    float* sq = nullptr;              // [nq_pad]: score -> [0, 0.98]
-    int32_t* n_rare = nullptr;        // [nq_pad]
-    int32_t* n_qt = nullptr;          // [nq_pad]
-    int32_t* n_drop = nullptr;        // [nq_pad] rare terms left out of stage 1 (weight below fp16's normal range)
-    float* tau2 = nullptr;            // [nq_pad] k-th best key so far (topk_compact2), 0 until a select has run: the band below it is the filter threshold
-    uint8_t* elig = nullptr;          // [nq_pad]
-    uint8_t* overflow = nullptr;      // [nq_pad]
-    int32_t* m_count = nullptr;       // [nq_pad] candidates to re-score
-    int* d_n_uncert = nullptr;
-    uint8_t* d_uncert = nullptr;      // [uncert_cap] flags of a search's batch (kept: a hipMalloc / hipFree pair per search synchronises the device)
-    int64_t uncert_cap = 0;
-    int64_t ap_cap = 0;               // approximate top lists [nq][k_eff]
-    int64_t* ap_ids = nullptr;
-    TopkWS ws;
-    // statistics (sr_sparse_index_cert_stats)
-    int64_t n_calls = 0, n_queries = 0, n_uncert = 0, n_rescored = 0;
-    uint16_t* dump = nullptr;         // debug: [nq_pad][n_tiles * SC_DT] keys of the last search (sr_sparse_index_cert_debug)
-    int64_t dump_nq = 0;
-    bool want_dump = false;
-    unsigned long long* d_stamps = nullptr;   // dev switch SR_CERT_STAMPS
-    uint32_t* mask_pad = nullptr;     // [n_tiles * SC_MB] a search's document bitmap as the masked score kernel walks it (sparse_cert_mask_pad), allocated on first use
-};
-
-// ------------------------------------------------------------------------------------------------------- build ---
-// per term: largest value; flags |= 1 for a negative or non-finite value
-__global__ __launch_bounds__(256) void cert_term_stats_kernel(const int64_t* __restrict__ indptr, const float* __restrict__ vals,
-                                                              float* __restrict__ vmax, int* __restrict__ flags) {
-    __shared__ float red[4];
-    const int64_t t = blockIdx.x;
-    const int64_t b = indptr[t], e = indptr[t + 1];
-    float mx = 0.f;
-    int bad = 0;
-    for (int64_t p = b + threadIdx.x; p < e; p += 256) {
-        const float v = vals[p];
-        if (!(v >= 0.f) || !(v < 3.0e38f)) bad = 1;
-        mx = fmaxf(mx, v);
-    }
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    if (bad) atomicOr(flags, 1);
-    __syncthreads();
-    if (threadIdx.x == 0) vmax[t] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-__global__ void cert_fill_d16_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc_ids,
-                                     const float* __restrict__ vals, const int32_t* __restrict__ slot_term, int KS, float vscale,
-                                     _Float16* __restrict__ d16) {
-    const int sl = blockIdx.y;
-    const int64_t t = slot_term[sl];
-    const int64_t b = indptr[t], e = indptr[t + 1];
-    const int s = sl >> 4, kk = sl & 15;
-    for (int64_t p = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < e; p += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t doc = doc_ids[p];
-        const int64_t tile = doc / SC_DT;
-        const int dl = (int)(doc - tile * SC_DT);
-        const int mb = dl >> 5, r = dl & 31;
-        const int lane = r + 32 * (kk >> 3);
-        d16[((((tile * SC_MB + mb) * KS + s) * 64 + lane) << 3) + (kk & 7)] = (_Float16)(vals[p] * vscale);
-    }
-}
-
-__global__ void cert_pack_postings_kernel(const int32_t* __restrict__ doc_ids, const float* __restrict__ vals, int64_t nnz, float vscale,
-                                          uint32_t* __restrict__ P) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    const _Float16 h = (_Float16)(vals[p] * vscale);
-    const uint32_t dl = (uint32_t)doc_ids[p] & (SC_DT - 1);
-    P[p] = ((dl >> 1) << 2) | (dl & 1u) | ((uint32_t)__builtin_bit_cast(unsigned short, h) << 16);
-}
-
-// S[t][i] = indptr[t] + #{postings of t with doc < i * SC_DT}, i = 0 .. n_tiles.  The thread of posting p (doc d, predecessor d')
-// fills the tiles in (tile(d'), tile(d)]; the thread "behind the last posting" fills the rest.
-__global__ __launch_bounds__(256) void cert_s_table_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc_ids, int n_tiles,
-                                                           uint32_t* __restrict__ S) {
-    const int64_t t = blockIdx.x;
-    const int64_t b = indptr[t], e = indptr[t + 1];
-    uint32_t* row = S + t * (int64_t)(n_tiles + 1);
-    for (int64_t p = b + threadIdx.x; p <= e; p += 256) {
-        const int prev = p > b ? (int)(doc_ids[p - 1] / SC_DT) : -1;
-        const int cur = p < e ? (int)(doc_ids[p] / SC_DT) : n_tiles;
-        for (int i = prev + 1; i <= cur; ++i) row[i] = (uint32_t)p;
-    }
-}
-
-// E[t][i] from the table of starts and the packed postings (see SparseCert::E)
-__global__ __launch_bounds__(256) void cert_e_table_kernel(const uint32_t* __restrict__ S, const uint32_t* __restrict__ P, int n_tiles, int e_stride,
-                                                           uint32_t* __restrict__ E) {
-    const int64_t t = blockIdx.x;
-    const uint32_t* srow = S + t * (int64_t)(n_tiles + 1);
-    uint32_t* erow = E + t * (int64_t)e_stride;
-    for (int i = threadIdx.x; i < e_stride; i += 256) {
-        uint32_t e = 0u;
-        if (i < n_tiles) {
-            const uint32_t b = srow[i], n = srow[i + 1] - b;
-            if (n == 1u) e = P[b] | 2u;
-            else if (n >= 2u) e = 0xffff0000u | (n < 0xffffu ? n : 0xffffu);
-        }
-        erow[i] = e;
-    }
-}
-
-__global__ void cert_fwd_count_kernel(const int32_t* __restrict__ doc_ids, int64_t nnz, int32_t* __restrict__ cnt) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < nnz) atomicAdd(&cnt[doc_ids[p]], 1);
-}
-__global__ void cert_i32_to_i64_kernel(const int32_t* __restrict__ in, int64_t n, int64_t* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-__global__ __launch_bounds__(256) void cert_fwd_fill_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc_ids,
-                                                            const float* __restrict__ vals, const int64_t* __restrict__ fwd_indptr,
-                                                            int32_t* __restrict__ cursor, uint64_t* __restrict__ fwd_tv) {
-    const int64_t t = blockIdx.y;
-    const int64_t b = indptr[t], e = indptr[t + 1];
-    for (int64_t p = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < e; p += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t d = doc_ids[p];
-        const int64_t pos = fwd_indptr[d] + atomicAdd(&cursor[d], 1);
-        fwd_tv[pos] = ((uint64_t)(uint32_t)t << 32) | (uint64_t)__float_as_uint(vals[p]);
-    }
-}
-// one wave per doc: bitonic sort of its (term, value) pairs by term in LDS; flags |= 2 for a doc with more than SC_FWD_MAX postings
-__global__ __launch_bounds__(256) void cert_fwd_sort_kernel(const int64_t* __restrict__ fwd_indptr, int64_t n_docs, uint64_t* __restrict__ fwd_tv,
-                                                            int* __restrict__ flags) {
-    __shared__ uint64_t keys_all[4][SC_FWD_MAX];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t d = (int64_t)blockIdx.x * 4 + wave;
-    if (d >= n_docs) return;
-    const int64_t b = fwd_indptr[d];
-    const int n = (int)(fwd_indptr[d + 1] - b);
-    if (n <= 1) return;
-    if (n > SC_FWD_MAX) {
-        if (lane == 0) atomicOr(flags, 2);
-        return;
-    }
-    uint64_t* keys = keys_all[wave];
-    int P = 64;
-    while (P < n) P <<= 1;
-    for (int i = lane; i < P; i += 64)
-        keys[i] = i < n ? fwd_tv[b + i] : ~0ull;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    for (int size = 2; size <= P; size <<= 1)
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int i = lane; i < P; i += 64) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool up = (i & size) == 0;
-                    const uint64_t x = keys[i], y = keys[ixj];
-                    if (up ? (x > y) : (x < y)) { keys[i] = y; keys[ixj] = x; }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-    for (int i = lane; i < n; i += 64) fwd_tv[b + i] = keys[i];
-}
-
-bool sparse_cert_forward_index(const SparseCert* c, const int64_t** fwd_indptr, const uint64_t** fwd_tv) {
-    if (!c || !c->fwd_indptr || !c->fwd_tv) return false;
-    *fwd_indptr = c->fwd_indptr;
-    *fwd_tv = c->fwd_tv;
-    return true;
-}
-
-void sparse_cert_destroy(SparseCert* c) {
-    if (!c) return;
-    if (c->d_stamps) {          // diagnostic: mean cycles per tile step of the sampled waves
-        unsigned long long h[80] = {0};
-        if (hipMemcpy(h, c->d_stamps, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[0]) {
-            const double n = (double)h[0];
-            fprintf(stderr, "[cert stamps] %llu sampled tile steps of %.0f cycles: last matrix wave at the barrier after %.0f, last scatter wave after %.0f (scatter last in %.0f %% of the steps); first blocks of wave 1 with a candidate: %.0f %%\n",
-                    h[0], (double)h[1] / n, (double)h[2] / n, (double)h[3] / n, 100.0 * (double)h[4] / n, 100.0 * (double)h[5] / n);
-            fprintf(stderr, "[cert stamps]   matrix waves  : barrier arrival");
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", (double)h[16 + w] / n);
-            fprintf(stderr, " | end of the last MFMA chain");
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", (double)h[32 + w] / n);
-            fprintf(stderr, " | keys of the first block done");
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", (double)h[48 + w] / n);
-            fprintf(stderr, " | end of the first filter");
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", (double)h[64 + w] / n);
-            fprintf(stderr, "\n[cert stamps]   scatter waves : barrier arrival");
-            for (int w = 8; w < 16; ++w) fprintf(stderr, " %.0f", (double)h[16 + w] / n);
-            fprintf(stderr, " | end of the adds");
-            for (int w = 8; w < 16; ++w) fprintf(stderr, " %.0f", (double)h[32 + w] / n);
-            fprintf(stderr, "\n");
-        }
-        (void)hipFree(c->d_stamps);
-    }
-    void* ptrs[] = {c->dslot, c->vmax, c->d16, c->P, c->S, c->E, c->fwd_indptr, c->fwd_tv, c->bfrag, c->rare_term, c->rare_w,
-                    c->cq, c->sq, c->n_rare, c->n_qt, c->n_drop, c->tau2, c->elig, c->overflow, c->m_count, c->d_n_uncert, c->d_uncert, c->ap_ids, c->dump, c->mask_pad};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    c->ws.release();
-    delete c;
-}
-
-int sparse_cert_build(sr_sparse_index* idx, hipStream_t s) {
-    // dev switch SR_SPARSE_CERT: 0 = never, 1 = whenever the index qualifies structurally (tests on small indexes);
-    // default: collections of at least 64 tiles
-    int mode = -1;
-    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT")) mode = atoi(e);
-    // public switches (include/sr_hip.h): SR_SPARSE_SCORER=exact keeps the index without the scorer's side structures (they take up to half
-    // of the free device memory: ~22 bytes per posting + 8 bytes per (term, doc tile)); SR_LOG=1 says on stderr what was built or why not
-    const char* scorer = getenv("SR_SPARSE_SCORER");
-    const bool log = getenv("SR_LOG") && atoi(getenv("SR_LOG")) != 0;
-    if (scorer && strcmp(scorer, "exact") == 0) mode = 0;
-    if (mode == 0 || (mode < 0 && idx->n_docs < 64 * SC_DT)) {
-        if (log) fprintf(stderr, "[sr_hip] sparse index of %lld docs: exact kernels only (%s)\n", (long long)idx->n_docs,
-                         mode == 0 ? "certified scorer switched off" : "fewer than 65 536 docs");
-        return SR_OK;
-    }
-    std::vector<int64_t> h_indptr((size_t)idx->n_terms + 1);
-    SR_CHECK_HIP(hipMemcpyAsync(h_indptr.data(), idx->indptr, sizeof(int64_t) * h_indptr.size(), hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipStreamSynchronize(s));
-    const int64_t nnz = h_indptr.back() - h_indptr.front();
-    if (nnz <= 0 || nnz >= 0xffffffffll || h_indptr.front() != 0) return SR_OK;
-    const int64_t V = idx->n_terms, N = idx->n_docs;
-    SparseCert* c = new SparseCert();
-    c->n_tiles = (int)ceil_div64(N, SC_DT);
-    int* d_flags = nullptr;
-    int32_t *d_terms = nullptr, *d_cnt = nullptr;
-    int64_t* d_cnt64 = nullptr;
-    bool ok = false;        // false: the index does not qualify (or no memory): not an error
-    int rc = SR_OK;
-    do {
-        if (hipMalloc((void**)&c->vmax, sizeof(float) * (size_t)V) != hipSuccess || hipMalloc((void**)&d_flags, sizeof(int)) != hipSuccess) break;
-        if (hipMemsetAsync(d_flags, 0, sizeof(int), s) != hipSuccess) { rc = SR_ERR_HIP; break; }
-        hipLaunchKernelGGL(cert_term_stats_kernel, dim3((unsigned)V), dim3(256), 0, s, idx->indptr, idx->vals, c->vmax, d_flags);
-        std::vector<float> h_vmax((size_t)V);
-        int h_flags = 0;
-        if (hipMemcpyAsync(h_vmax.data(), c->vmax, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(&h_flags, d_flags, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-            rc = SR_ERR_HIP;
-            break;
-        }
-        if (h_flags & 1) break;                   // a negative / non-finite value: exact kernels only
-        float vmax_all = 0.f;
-        for (float v : h_vmax) vmax_all = std::max(vmax_all, v);
-        if (!(vmax_all > 0.f)) break;
-        {   // largest value lands in [2^13, 2^14): far from fp16's subnormals and from its maximum
-            int ex;
-            (void)frexpf(vmax_all, &ex);          // vmax_all = m * 2^ex, m in [0.5, 1)
-            c->vscale = ldexpf(1.0f, 14 - ex);
-        }
-        // dense terms: the longest lists, those present in at least 1 / 1024 of the docs, at most T_max, a multiple of 16
-        int t_max = 128;
-        if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_T")) t_max = atoi(e);
-        t_max = std::max(16, std::min(SC_TMAX, t_max / 16 * 16));
-        std::vector<std::pair<int64_t, int32_t>> heavy;
-        for (int64_t t = 0; t < V; ++t) {
-            const int64_t len = h_indptr[(size_t)t + 1] - h_indptr[(size_t)t];
-            if (len > 0 && len * 1024 >= N) heavy.emplace_back(-len, (int32_t)t);
-        }
-        std::sort(heavy.begin(), heavy.end());
-        int n_heavy = (int)std::min<size_t>(heavy.size(), (size_t)t_max);
-        c->T = std::max(16, (n_heavy + 15) / 16 * 16);
-        c->KS = c->T / 16;
-        if (c->KS == 3) { c->KS = 4; c->T = 64; }                         // instantiated k-step counts: 1, 2, 4 .. 8
-        std::vector<int32_t> h_slot((size_t)V, -1), h_terms((size_t)std::max(1, n_heavy));
-        for (int i = 0; i < n_heavy; ++i) {
-            h_slot[(size_t)heavy[(size_t)i].second] = i;
-            h_terms[(size_t)i] = heavy[(size_t)i].second;
-        }
-        const size_t d16_halves = (size_t)c->n_tiles * (size_t)c->T * SC_DT;
-        const size_t s_words = (size_t)V * (size_t)(c->n_tiles + 1);
-        c->e_stride = (c->n_tiles + 3) / 4 * 4 + 4;
-        const size_t e_words = (size_t)V * (size_t)c->e_stride;
-        if (e_words >= 0xffffffffull) break;      // the kernel addresses table E with 32-bit word offsets
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { rc = SR_ERR_HIP; break; }
-        const size_t need = d16_halves * 2 + (size_t)nnz * 12 + (s_words + e_words) * 4 + (size_t)N * 16 + (64u << 20);
-        if (need > free_b / 2) {                  // side structures may take at most half of what is free
-            if (log) fprintf(stderr, "[sr_hip] sparse index: the certified scorer needs %.2f GB, more than half of the %.2f GB free: exact kernels only\n",
-                             (double)need / 1e9, (double)free_b / 1e9);
-            break;
-        }
-        if (log) fprintf(stderr, "[sr_hip] sparse index of %lld docs, %lld postings: certified scorer with %d heavy terms, %.2f GB of side structures "
-                                 "(SR_SPARSE_SCORER=exact to do without)\n", (long long)N, (long long)nnz, c->T, (double)need / 1e9);
-        if (hipMalloc((void**)&c->dslot, sizeof(int32_t) * (size_t)V) != hipSuccess || hipMalloc((void**)&c->d16, d16_halves * 2) != hipSuccess ||
-            hipMalloc((void**)&c->P, sizeof(uint32_t) * ((size_t)nnz + 4)) != hipSuccess || hipMalloc((void**)&c->S, s_words * 4) != hipSuccess ||
-            hipMalloc((void**)&c->E, e_words * 4) != hipSuccess ||
-            hipMalloc((void**)&c->fwd_indptr, sizeof(int64_t) * (size_t)(N + 1)) != hipSuccess ||
-            hipMalloc((void**)&c->fwd_tv, sizeof(uint64_t) * ((size_t)nnz + 2)) != hipSuccess ||
-            hipMalloc((void**)&d_terms, sizeof(int32_t) * h_terms.size()) != hipSuccess ||
-            hipMalloc((void**)&d_cnt, sizeof(int32_t) * (size_t)N) != hipSuccess || hipMalloc((void**)&d_cnt64, sizeof(int64_t) * (size_t)N) != hipSuccess) {
-            (void)hipGetLastError();
-            break;
-        }
-        rc = SR_ERR_HIP;
-        if (hipMemcpyAsync(c->dslot, h_slot.data(), sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemcpyAsync(d_terms, h_terms.data(), sizeof(int32_t) * h_terms.size(), hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemsetAsync(c->d16, 0, d16_halves * 2, s) != hipSuccess) break;
-        if (hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)N, s) != hipSuccess) break;
-        if (n_heavy > 0)
-            hipLaunchKernelGGL(cert_fill_d16_kernel, dim3(256, (unsigned)n_heavy), dim3(256), 0, s, idx->indptr, idx->doc_ids, idx->vals, d_terms,
-                               c->KS, c->vscale, c->d16);
-        hipLaunchKernelGGL(cert_pack_postings_kernel, dim3((unsigned)ceil_div64(nnz, 256)), dim3(256), 0, s, idx->doc_ids, idx->vals, nnz,
-                           c->vscale, c->P);
-        hipLaunchKernelGGL(cert_s_table_kernel, dim3((unsigned)V), dim3(256), 0, s, idx->indptr, idx->doc_ids, c->n_tiles, c->S);
-        if (hipMemsetAsync(c->P + nnz, 0, 4 * sizeof(uint32_t), s) != hipSuccess) break;       // an 8-byte read of the last posting stays inside
-        hipLaunchKernelGGL(cert_e_table_kernel, dim3((unsigned)V), dim3(256), 0, s, c->S, c->P, c->n_tiles, c->e_stride, c->E);
-        hipLaunchKernelGGL(cert_fwd_count_kernel, dim3((unsigned)ceil_div64(nnz, 256)), dim3(256), 0, s, idx->doc_ids, nnz, d_cnt);
-        hipLaunchKernelGGL(cert_i32_to_i64_kernel, dim3((unsigned)ceil_div64(N, 256)), dim3(256), 0, s, d_cnt, N, d_cnt64);
-        if (hipGetLastError() != hipSuccess) break;
-        if (sr_device_exclusive_scan_i64(d_cnt64, c->fwd_indptr, N, s) != SR_OK) break;
-        if (hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)N, s) != hipSuccess) break;
-        hipLaunchKernelGGL(cert_fwd_fill_kernel, dim3(64, (unsigned)V), dim3(256), 0, s, idx->indptr, idx->doc_ids, idx->vals, c->fwd_indptr, d_cnt,
-                           c->fwd_tv);
-        hipLaunchKernelGGL(cert_fwd_sort_kernel, dim3((unsigned)ceil_div64(N, 4)), dim3(256), 0, s, c->fwd_indptr, N, c->fwd_tv, d_flags);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipMemcpyAsync(&h_flags, d_flags, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) break;
-        rc = SR_OK;
-        if (h_flags & 2) break;                   // a doc with more postings than the forward sort handles
-        ok = true;
-    } while (0);
-    if (d_flags) (void)hipFree(d_flags);
-    if (d_terms) (void)hipFree(d_terms);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (d_cnt64) (void)hipFree(d_cnt64);
-    if (rc != SR_OK) {
-        sr_set_error("sr_sparse_index_create: building the certified scorer's structures failed: %s", hipGetErrorString(hipGetLastError()));
-        sparse_cert_destroy(c);
-        return rc;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        sparse_cert_destroy(c);
-        return SR_OK;
-    }
-    idx->cert = c;
-    return SR_OK;
-}
 
 // -------------------------------------------------------------------------------------------------------- plan ---
 // One wave per query: preconditions, scale, MFMA B fragment entries of its dense terms, rare term list.
@@ -1402,58 +1047,20 @@ __global__ __launch_bounds__(256) void cert_rescore_kernel(CertRescoreArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------ driver ---
-template <typename T>
-static bool cert_realloc(T*& p, size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    if (hipMalloc((void**)&p, sizeof(T) * n) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        return false;
-    }
-    return true;
-}
-
 // the per-call buffers of a batch of nq_pad queries; false = out of device memory: everything per-call is released (the index-side
 // structures stay) and the caller serves the batch with the exact kernels
 static bool cert_ensure_call_buffers(SparseCert* c, int64_t nq_pad, int k_eff) {      // k_eff = 0: the plan's buffers only (the band is chosen after the plan)
-    bool ok = true;
-    if (nq_pad > c->nq_cap) {
-        c->nq_cap = 0;
-        ok = ok && cert_realloc(c->bfrag, (size_t)nq_pad * (size_t)c->T);
-        ok = ok && cert_realloc(c->rare_term, (size_t)nq_pad * SC_MAXRT);
-        ok = ok && cert_realloc(c->rare_w, (size_t)nq_pad * SC_MAXRT);
-        ok = ok && cert_realloc(c->cq, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->sq, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->n_rare, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->n_qt, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->n_drop, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->tau2, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->elig, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->overflow, (size_t)nq_pad);
-        ok = ok && cert_realloc(c->m_count, (size_t)nq_pad);
-        if (ok) c->nq_cap = nq_pad;
-    }
-    if (ok && k_eff > 0 && nq_pad * k_eff > c->ap_cap) {
-        c->ap_cap = 0;
-        ok = cert_realloc(c->ap_ids, (size_t)nq_pad * (size_t)(2 * k_eff));
-        if (ok) c->ap_cap = nq_pad * k_eff;
-    }
-    if (ok && !c->d_n_uncert && hipMalloc((void**)&c->d_n_uncert, 4 * sizeof(int)) != hipSuccess) {     // [0] uncertified queries, [1] candidates re-scored (in units of 16), [2] largest rare-term count
-        (void)hipGetLastError();
-        c->d_n_uncert = nullptr;
-        ok = false;
-    }
-    if (ok && k_eff > 0 && c->ws.ensure(nq_pad, k_eff, SC_CAND_CAP) != SR_OK) ok = false;      // releases itself on failure
+    const bool ok =
+        c->bfrag.reserve(nq_pad * c->T, nullptr) == SR_OK && c->rare_term.reserve(nq_pad * SC_MAXRT, nullptr) == SR_OK &&
+        c->rare_w.reserve(nq_pad * SC_MAXRT, nullptr) == SR_OK && c->cq.reserve(nq_pad, nullptr) == SR_OK && c->sq.reserve(nq_pad, nullptr) == SR_OK &&
+        c->n_rare.reserve(nq_pad, nullptr) == SR_OK && c->n_qt.reserve(nq_pad, nullptr) == SR_OK && c->n_drop.reserve(nq_pad, nullptr) == SR_OK &&
+        c->tau2.reserve(nq_pad, nullptr) == SR_OK && c->elig.reserve(nq_pad, nullptr) == SR_OK && c->overflow.reserve(nq_pad, nullptr) == SR_OK &&
+        c->m_count.reserve(nq_pad, nullptr) == SR_OK && c->d_n_uncert.reserve(4, nullptr) == SR_OK &&
+        (k_eff == 0 || (c->ap_ids.reserve(nq_pad * 2 * k_eff, nullptr) == SR_OK && c->ws.ensure(nq_pad, k_eff, SC_CAND_CAP) == SR_OK));
     if (!ok) {
-        void** ptrs[] = {(void**)&c->bfrag, (void**)&c->rare_term, (void**)&c->rare_w, (void**)&c->cq, (void**)&c->sq, (void**)&c->n_rare, (void**)&c->n_qt,
-                         (void**)&c->n_drop, (void**)&c->tau2, (void**)&c->elig, (void**)&c->overflow, (void**)&c->m_count, (void**)&c->ap_ids};
-        for (void** pp : ptrs) {
-            if (*pp) (void)hipFree(*pp);
-            *pp = nullptr;
-        }
-        c->nq_cap = 0;
-        c->ap_cap = 0;
+        c->bfrag.release(); c->rare_term.release(); c->rare_w.release(); c->cq.release(); c->sq.release(); c->n_rare.release();
+        c->n_qt.release(); c->n_drop.release(); c->tau2.release(); c->elig.release(); c->overflow.release(); c->m_count.release();
+        c->ap_ids.release();
         c->ws.release();
     }
     return ok;
@@ -1468,12 +1075,7 @@ void sparse_cert_count_retry(SparseCert* c, int64_t ns) {
 }
 
 uint8_t* sparse_cert_uncert_buffer(SparseCert* c, int64_t nq) {
-    if (nq > c->uncert_cap) {
-        c->uncert_cap = 0;
-        if (!cert_realloc(c->d_uncert, (size_t)nq)) return nullptr;
-        c->uncert_cap = nq;
-    }
-    return c->d_uncert;
+    return c->d_uncert.reserve(nq, nullptr) == SR_OK ? c->d_uncert.p : nullptr;
 }
 
 template <int KS, bool MASKED>
@@ -1511,48 +1113,40 @@ int sparse_cert_mask_pad(sr_sparse_index* idx, const uint32_t* d_words, const ui
     SparseCert* c = idx->cert;
     const int64_t n_pad = (int64_t)c->n_tiles * SC_MB;
     *d_mask_pad = nullptr;
-    if (!c->mask_pad && hipMalloc((void**)&c->mask_pad, sizeof(uint32_t) * (size_t)n_pad) != hipSuccess) {
-        (void)hipGetLastError();
-        c->mask_pad = nullptr;
-        return SR_OK;
-    }
+    if (c->mask_pad.reserve(n_pad, nullptr) != SR_OK) return SR_OK;
     hipLaunchKernelGGL(cert_mask_pad_kernel, dim3((unsigned)ceil_div64(n_pad, 256)), dim3(256), 0, s, d_words, ceil_div64(idx->n_docs, 32), idx->n_docs,
-                       c->mask_pad, n_pad);
+                       c->mask_pad.p, n_pad);
     SR_CHECK_LAUNCH();
-    *d_mask_pad = c->mask_pad;
+    *d_mask_pad = c->mask_pad.p;
     return SR_OK;
 }
 
-int sparse_cert_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
-                       int k, float threshold, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids,
-                       int32_t* d_out_counts, uint8_t* d_uncert, int64_t* n_uncert, bool* no_memory, int band_keys, int* band_used,
-                       const uint32_t* d_mask_pad, hipStream_t s) {
+int sparse_cert_search(sr_sparse_index* idx, const SparseCall& call, const SparseCertOptions& opt, SparseCertResult* res, hipStream_t s) {
     SparseCert* c = idx->cert;
+    const int64_t nq = call.nq;
+    const int k = call.k;
     const int64_t nq_pad = ceil_div64(nq, SC_QB) * SC_QB;
     const int n_qblocks = (int)(nq_pad / SC_QB);
-    *no_memory = false;
+    *res = SparseCertResult{};
     if (!cert_ensure_call_buffers(c, nq_pad, 0)) {
-        *no_memory = true;
+        res->no_memory = true;
         return SR_OK;
     }
     const int64_t dump_stride = (int64_t)c->n_tiles * SC_DT;
-    if (c->want_dump && c->dump_nq < nq_pad) {
-        c->dump_nq = 0;
-        if (!cert_realloc(c->dump, (size_t)nq_pad * (size_t)dump_stride)) {
-            sr_set_error("sparse_cert_search: no device memory for the debug key dump");
-            return SR_ERR_NOMEM;
-        }
-        c->dump_nq = nq_pad;
+    if (c->want_dump && c->dump.reserve(nq_pad * dump_stride, nullptr) != SR_OK) {
+        sr_set_error("sparse_cert_search: no device memory for the debug key dump");
+        return SR_ERR_NOMEM;
     }
 
     // plan
-    SR_CHECK_HIP(hipMemsetAsync(c->bfrag, 0, sizeof(_Float16) * (size_t)nq_pad * (size_t)c->T, s));
-    SR_CHECK_HIP(hipMemsetAsync(c->d_n_uncert, 0, 4 * sizeof(int), s));
+    SR_CHECK_HIP(hipMemsetAsync(c->bfrag.p, 0, sizeof(_Float16) * (size_t)nq_pad * (size_t)c->T, s));
+    SR_CHECK_HIP(hipMemsetAsync(c->d_n_uncert.p, 0, 4 * sizeof(int), s));
     CertPlanArgs pa;
-    pa.q_indptr = d_q_indptr; pa.q_cols = d_q_cols; pa.q_vals = d_q_vals; pa.nq = nq; pa.n_terms = idx->n_terms;
-    pa.indptr = idx->indptr; pa.dslot = c->dslot; pa.vmax = c->vmax; pa.KS = c->KS; pa.vscale = c->vscale;
-    pa.bfrag = c->bfrag; pa.rare_term = c->rare_term; pa.rare_w = c->rare_w; pa.cq = c->cq; pa.sq = c->sq; pa.n_rare = c->n_rare; pa.n_qt = c->n_qt; pa.n_drop = c->n_drop;
-    pa.elig = c->elig; pa.overflow = c->overflow; pa.max_rare = c->d_n_uncert + 2;
+    pa.q_indptr = call.q_indptr; pa.q_cols = call.q_cols; pa.q_vals = call.q_vals; pa.nq = nq; pa.n_terms = idx->n_terms;
+    pa.indptr = idx->indptr; pa.dslot = c->dslot.p; pa.vmax = c->vmax.p; pa.KS = c->KS; pa.vscale = c->vscale;
+    pa.bfrag = c->bfrag.p; pa.rare_term = c->rare_term.p; pa.rare_w = c->rare_w.p; pa.cq = c->cq.p; pa.sq = c->sq.p; pa.n_rare = c->n_rare.p;
+    pa.n_qt = c->n_qt.p; pa.n_drop = c->n_drop.p;
+    pa.elig = c->elig.p; pa.overflow = c->overflow.p; pa.max_rare = c->d_n_uncert.p + 2;
     hipLaunchKernelGGL(cert_plan_kernel, dim3((unsigned)ceil_div64(nq_pad, 4)), dim3(256), 0, s, pa);
     SR_CHECK_LAUNCH();
     // The band: how many keys beyond k the running set keeps.  The certificate needs every key that the 16-bit arithmetic cannot tell from
@@ -1560,15 +1154,15 @@ int sparse_cert_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const in
     // it up to ~100 rare terms (L0_q = 128 at the MSMARCO shape: all certified), beyond that the band grows - at 145 rare terms (L0_q = 256)
     // 2 048 keys certify 93 % of the queries and 3 072 all of them, at 12 100 instead of 4 900 queries/s through the exact kernels.  The
     // short queries of a default batch keep the band that is fastest for them (140 000 q/s at 1 024, 130 000 at 3 072).
-    int band = band_keys;
+    int band = opt.band_keys;
     int h_plan[2] = {0, 0};                                  // largest rare-term count, queries on the fast path
-    SR_CHECK_HIP(hipMemcpyAsync(h_plan, c->d_n_uncert + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipMemcpyAsync(h_plan, c->d_n_uncert.p + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));
     if (h_plan[1] == 0) {                                    // nothing for the scorer in this batch (negative / unordered / too long queries): no pass over the collection
-        SR_CHECK_HIP(hipMemsetAsync(d_uncert, 1, (size_t)nq, s));
+        SR_CHECK_HIP(hipMemsetAsync(opt.uncert, 1, (size_t)nq, s));
         SR_CHECK_HIP(hipStreamSynchronize(s));
-        if (band_used) *band_used = SR_MAX_TOPK;             // no retry either
-        *n_uncert = nq;
+        res->band_used = SR_MAX_TOPK;                        // no retry either
+        res->n_uncert = nq;
         ++c->n_calls;
         c->n_queries += nq;
         c->n_uncert += nq;
@@ -1581,48 +1175,42 @@ int sparse_cert_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const in
     if (band < 64) band = 64;
     if (k + band > SR_MAX_TOPK) band = SR_MAX_TOPK - k;
     const int k_eff = k + band;
-    if (band_used) *band_used = band;
+    res->band_used = band;
     if (const char* e = getenv("SR_LOG")) if (atoi(e) >= 2)
         fprintf(stderr, "[sr_hip] certified sparse search: %lld queries, %d on the fast path, largest rare-term count %d, band %d keys%s\n", (long long)nq, h_plan[1], h_plan[0],
-                band, band_keys > 0 ? " (second pass)" : "");
+                band, opt.band_keys > 0 ? " (second pass)" : "");
     if (!cert_ensure_call_buffers(c, nq_pad, k_eff)) {
-        *no_memory = true;
+        res->no_memory = true;
         return SR_OK;
     }
 
     // stage 1: doc tiles in launches that grow geometrically (the threshold tightens early), at most 512 tiles each
     SR_TRY(topk_reset(c->ws, nq_pad, s));
     CertArgs a;
-    a.d16 = reinterpret_cast<const f16x8*>(c->d16);
-    a.P = c->P; a.S = c->S; a.s_stride = c->n_tiles + 1; a.E = c->E; a.e_stride = c->e_stride;
-    a.bfrag = reinterpret_cast<const f16x8*>(c->bfrag);
-    a.rare_term = c->rare_term; a.rare_w = c->rare_w; a.cq = c->cq; a.tau = c->ws.tau; a.nq = nq;
-    a.tau2 = c->tau2; a.n_rare = c->n_rare; a.n_qt = c->n_qt; a.n_drop = c->n_drop; a.T = c->T;
-    SR_CHECK_HIP(hipMemsetAsync(c->tau2, 0, sizeof(float) * (size_t)nq_pad, s));
-    a.cand_keys = c->ws.cand_keys; a.cand_count = c->ws.cand_count; a.cand_cap = c->ws.cand_cap; a.overflow = c->overflow;
+    a.d16 = reinterpret_cast<const f16x8*>(c->d16.p);
+    a.P = c->P.p; a.S = c->S.p; a.s_stride = c->n_tiles + 1; a.E = c->E.p; a.e_stride = c->e_stride;
+    a.bfrag = reinterpret_cast<const f16x8*>(c->bfrag.p);
+    a.rare_term = c->rare_term.p; a.rare_w = c->rare_w.p; a.cq = c->cq.p; a.tau = c->ws.tau; a.nq = nq;
+    a.tau2 = c->tau2.p; a.n_rare = c->n_rare.p; a.n_qt = c->n_qt.p; a.n_drop = c->n_drop.p; a.T = c->T;
+    SR_CHECK_HIP(hipMemsetAsync(c->tau2.p, 0, sizeof(float) * (size_t)nq_pad, s));
+    a.cand_keys = c->ws.cand_keys; a.cand_count = c->ws.cand_count; a.cand_cap = c->ws.cand_cap; a.overflow = c->overflow.p;
     a.n_qblocks = n_qblocks;
-    a.dump = c->want_dump ? c->dump : nullptr;
-    if (SC_STAMPS && sr_dev_getenv("SR_CERT_STAMPS") && !c->d_stamps) {
-        SR_CHECK_HIP(hipMalloc((void**)&c->d_stamps, 80 * 8));
-        SR_CHECK_HIP(hipMemsetAsync(c->d_stamps, 0, 80 * 8, s));
+    a.dump = c->want_dump ? c->dump.p : nullptr;
+    if (SC_STAMPS && sr_dev_getenv("SR_CERT_STAMPS") && !c->d_stamps.p) {
+        SR_TRY(c->d_stamps.reserve(80, "sparse_cert_search (stamps)"));
+        SR_CHECK_HIP(hipMemsetAsync(c->d_stamps.p, 0, 80 * 8, s));
     }
-    a.stamps = c->d_stamps;
+    a.stamps = c->d_stamps.p;
     a.stamps_from = 0;
     if (SC_STAMPS) { if (const char* e = sr_dev_getenv("SR_CERT_STAMPS")) a.stamps_from = atoi(e); }
     a.dump_stride = dump_stride;
-    a.mask = d_mask_pad;
+    a.mask = opt.mask_pad;
     int64_t step = k_eff / SC_DT + 1;      // the first launch covers just over k + band docs (no threshold exists before that many keys are held), then doubling
-    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_STEP0")) step = std::max(1, atoi(e));
     bool band_filter = true;               // dev switch SR_SPARSE_CERT_BAND=0: filter with the (k + band)-th best key only
     if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_BAND")) band_filter = atoi(e) != 0;
     int sel_over = 2 * k_eff;
     if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_SELOVER")) sel_over = (int)(atof(e) * k_eff);
-    // while the launches still double, every compaction selects: a launch then appends k + band candidates per query whatever its size, and a
-    // threshold one launch old lets twice as many through (-0.9 ms per pass at the MSMARCO shape; dev switch SR_SPARSE_CERT_SELEARLY=0)
-    bool sel_early = true;
-    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_SELEARLY")) sel_early = atoi(e) != 0;
-    int64_t tpw_max = 32;                  // tiles a workgroup walks: amortises its prologue; the chunk's operand (256 KB per tile at T = 128) should stay in its XCD's L2
-    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_TPW")) tpw_max = std::max(1, atoi(e));
+    const int64_t tpw_max = 32;            // tiles a workgroup walks: amortises its prologue; the chunk's operand (256 KB per tile at T = 128) should stay in its XCD's L2
     for (int64_t t0 = 0; t0 < c->n_tiles;) {
         int64_t nt = step < 512 ? step : 512;
         if (t0 + nt > c->n_tiles) nt = c->n_tiles - t0;
@@ -1647,92 +1235,40 @@ int sparse_cert_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const in
         }
         idx->prof.end(s, 0, 0);
         SR_TRY(rc);
-        SR_TRY(topk_compact2(c->ws, nq_pad, k_eff, band_filter ? k : 0, c->tau2, (sel_early && nt < 512) ? k_eff : sel_over, s));
+        // while the launches still double, every compaction selects: a launch then appends k + band candidates per query whatever its size, and a
+        // threshold one launch old lets twice as many through (-0.9 ms per pass at the MSMARCO shape)
+        SR_TRY(topk_compact2(c->ws, nq_pad, k_eff, band_filter ? k : 0, c->tau2.p, nt < 512 ? k_eff : sel_over, s));
         t0 += nt;
         step *= 2;
     }
 
     // stage 2: certificate, exact re-score of the candidates, exact top-k of those
     CertSelectArgs sa;
-    sa.run_keys = c->ws.run_keys; sa.run_count = c->ws.run_count; sa.tau = c->ws.tau; sa.ap_ids = c->ap_ids;
+    sa.run_keys = c->ws.run_keys; sa.run_count = c->ws.run_count; sa.tau = c->ws.tau; sa.ap_ids = c->ap_ids.p;
     sa.nq = nq; sa.k = k; sa.k_eff = k_eff; sa.T = c->T;
-    sa.elig = c->elig; sa.overflow = c->overflow; sa.n_rare = c->n_rare; sa.n_qt = c->n_qt; sa.n_drop = c->n_drop; sa.m_count = c->m_count;
-    sa.uncert = d_uncert; sa.n_uncert = c->d_n_uncert;
+    sa.elig = c->elig.p; sa.overflow = c->overflow.p; sa.n_rare = c->n_rare.p; sa.n_qt = c->n_qt.p; sa.n_drop = c->n_drop.p; sa.m_count = c->m_count.p;
+    sa.uncert = opt.uncert; sa.n_uncert = c->d_n_uncert.p;
     hipLaunchKernelGGL(cert_select_kernel, dim3((unsigned)nq), dim3(256), 0, s, sa);
     SR_CHECK_LAUNCH();
     SR_TRY(topk_reset(c->ws, nq_pad, s));
     CertRescoreArgs ra;
-    ra.q_indptr = d_q_indptr; ra.q_cols = d_q_cols; ra.q_vals = d_q_vals;
-    ra.fwd_indptr = c->fwd_indptr; ra.fwd_tv = c->fwd_tv;
-    ra.ap_ids = c->ap_ids; ra.m_count = c->m_count; ra.ap_stride = 2 * k_eff; ra.threshold = threshold;
-    ra.id_base = (uint32_t)id_base; ra.id_stride = (uint32_t)id_stride;
+    ra.q_indptr = call.q_indptr; ra.q_cols = call.q_cols; ra.q_vals = call.q_vals;
+    ra.fwd_indptr = c->fwd_indptr.p; ra.fwd_tv = c->fwd_tv.p;
+    ra.ap_ids = c->ap_ids.p; ra.m_count = c->m_count.p; ra.ap_stride = 2 * k_eff; ra.threshold = call.threshold;
+    ra.id_base = (uint32_t)call.id_base; ra.id_stride = (uint32_t)call.id_stride;
     ra.cand_keys = c->ws.cand_keys; ra.cand_count = c->ws.cand_count; ra.cand_cap = c->ws.cand_cap;
     hipLaunchKernelGGL(cert_rescore_kernel, dim3((unsigned)nq), dim3(256), 0, s, ra);
     SR_CHECK_LAUNCH();
     SR_TRY(topk_compact(c->ws, nq, k, s));
-    SR_TRY(topk_finalize(c->ws, nq, k, 0.f, d_out_scores, d_out_ids, d_out_counts, s));
+    SR_TRY(topk_finalize(c->ws, nq, k, 0.f, call.out_scores, call.out_ids, call.out_counts, s));
     int h_un2[2] = {0, 0};
-    SR_CHECK_HIP(hipMemcpyAsync(h_un2, c->d_n_uncert, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipMemcpyAsync(h_un2, c->d_n_uncert.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));
     const int h_un = h_un2[0];
     c->n_rescored += 16ll * h_un2[1];
-    *n_uncert = h_un;
+    res->n_uncert = h_un;
     ++c->n_calls;
     c->n_queries += nq;
     c->n_uncert += h_un;
-    return SR_OK;
-}
-
-// Which path served the searches so far.  out[0] = 1 if the certified scorer exists for this index, [1] dense terms (MFMA K),
-// [2] searches it ran, [3] queries it was given, [4] queries it handed to the exact kernels (uncertified), [5] doc tiles, [6] candidates
-// re-scored, [7] query batches served by the exact kernels because the scorer's per-call buffers did not fit in device memory
-extern "C" int sr_sparse_index_cert_stats(sr_sparse_index* idx, int64_t* out8) {
-    SR_REQUIRE(idx && out8, "sr_sparse_index_cert_stats: null argument");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    for (int i = 0; i < 8; ++i) out8[i] = 0;
-    if (SparseCert* c = idx->cert) {
-        out8[0] = 1; out8[1] = c->T; out8[2] = c->n_calls; out8[3] = c->n_queries; out8[4] = c->n_uncert; out8[5] = c->n_tiles; out8[6] = c->n_rescored;
-    }
-    out8[7] = idx->n_cert_no_memory;
-    return SR_OK;
-}
-
-// Debug / test hook: after enable = 1 every search keeps the stage-1 keys of all (query, doc) pairs; enable = 2 copies the keys of
-// the last search to h_keys [nq_pad][n_tiles * 1024] (uint16) and returns the per-query constants the bound needs:
-// h_consts [nq_pad][5] = {cq (0: the query is outside the fast path), s_q, rare terms in stage 1, query terms, rare terms left out}.  *vscale / *T: the index-side constants.
-extern "C" int sr_sparse_index_cert_debug(sr_sparse_index* idx, int enable, uint16_t* h_keys, int64_t keys_capacity, float* h_consts,
-                                          int64_t nq_pad, float* vscale, int32_t* T) {
-    SR_REQUIRE(idx, "sr_sparse_index_cert_debug: null index");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    SparseCert* c = idx->cert;
-    SR_REQUIRE(c, "sr_sparse_index_cert_debug: this index has no certified scorer");
-    if (enable != 2) {
-        c->want_dump = enable != 0;
-        return SR_OK;
-    }
-    SR_REQUIRE(c->dump && h_keys && h_consts && nq_pad <= c->dump_nq, "sr_sparse_index_cert_debug: nothing recorded");
-    const int64_t stride = (int64_t)c->n_tiles * SC_DT;
-    SR_REQUIRE(keys_capacity >= nq_pad * stride, "sr_sparse_index_cert_debug: key buffer too small");
-    SR_CHECK_HIP(hipDeviceSynchronize());
-    SR_CHECK_HIP(hipMemcpy(h_keys, c->dump, sizeof(uint16_t) * (size_t)(nq_pad * stride), hipMemcpyDeviceToHost));
-    std::vector<float> cqv((size_t)nq_pad), sqv((size_t)nq_pad);
-    std::vector<int32_t> nr((size_t)nq_pad), nt((size_t)nq_pad), nd((size_t)nq_pad);
-    SR_CHECK_HIP(hipMemcpy(cqv.data(), c->cq, sizeof(float) * (size_t)nq_pad, hipMemcpyDeviceToHost));
-    SR_CHECK_HIP(hipMemcpy(sqv.data(), c->sq, sizeof(float) * (size_t)nq_pad, hipMemcpyDeviceToHost));
-    SR_CHECK_HIP(hipMemcpy(nr.data(), c->n_rare, sizeof(int32_t) * (size_t)nq_pad, hipMemcpyDeviceToHost));
-    SR_CHECK_HIP(hipMemcpy(nt.data(), c->n_qt, sizeof(int32_t) * (size_t)nq_pad, hipMemcpyDeviceToHost));
-    SR_CHECK_HIP(hipMemcpy(nd.data(), c->n_drop, sizeof(int32_t) * (size_t)nq_pad, hipMemcpyDeviceToHost));
-    std::vector<float> t2((size_t)nq_pad);
-    SR_CHECK_HIP(hipMemcpy(t2.data(), c->tau2, sizeof(float) * (size_t)nq_pad, hipMemcpyDeviceToHost));
-    for (int64_t q = 0; q < nq_pad; ++q) {
-        h_consts[6 * q] = cqv[(size_t)q];
-        h_consts[6 * q + 1] = sqv[(size_t)q];
-        h_consts[6 * q + 2] = (float)nr[(size_t)q];
-        h_consts[6 * q + 3] = (float)nt[(size_t)q];
-        h_consts[6 * q + 4] = (float)nd[(size_t)q];
-        h_consts[6 * q + 5] = t2[(size_t)q];
-    }
-    if (vscale) *vscale = c->vscale;
-    if (T) *T = c->T;
     return SR_OK;
 }

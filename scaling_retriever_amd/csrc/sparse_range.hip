@@ -261,10 +261,10 @@ __global__ __launch_bounds__(256) void sparse_range_fill_kernel(SparseRangeArgs 
 static void sparse_range_args(const sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                               int64_t nq, const float* d_thr, SparseRangeArgs& a) {
     a = SparseRangeArgs{};
-    a.indptr = idx->indptr; a.doc_ids = idx->doc_ids; a.vals = idx->vals; a.skip = idx->skip;
+    a.indptr = idx->indptr; a.doc_ids = idx->doc_ids; a.vals = idx->vals; a.skip = idx->skip.p;
     a.n_tiles = idx->n_tiles; a.n_docs = idx->n_docs; a.n_terms = idx->n_terms;
     a.q_indptr = d_q_indptr; a.q_cols = d_q_cols; a.q_vals = d_q_vals; a.thr = d_thr; a.nq = nq;
-    a.chunk_tiles = idx->range_chunk_tiles; a.table = idx->range_tab;
+    a.chunk_tiles = idx->range_chunk_tiles; a.table = idx->range_tab.p;
 }
 
 extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
@@ -303,16 +303,9 @@ extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_in
     }
     const int n_chunks = (int)ceil_div64(idx->n_tiles, chunk_tiles);
     const int64_t entries = (int64_t)n_chunks * nq;
-    if (idx->range_tab_cap < entries) {
-        if (idx->range_tab) (void)hipFree(idx->range_tab);
-        idx->range_tab = nullptr; idx->range_tab_cap = 0;
-        if (hipMalloc((void**)&idx->range_tab, (size_t)entries * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            idx->range_tab = nullptr;
-            sr_set_error("sr_sparse_range_count: out of device memory for the chunk table of %lld bytes", (long long)(entries * 4));
-            return SR_ERR_NOMEM;
-        }
-        idx->range_tab_cap = entries;
+    if (idx->range_tab.reserve(entries, nullptr) != SR_OK) {
+        sr_set_error("sr_sparse_range_count: out of device memory for the chunk table of %lld bytes", (long long)(entries * 4));
+        return SR_ERR_NOMEM;
     }
     StreamOrder::Scope in_order(idx->order, s);
     idx->range_chunk_tiles = (int)chunk_tiles;
@@ -324,7 +317,7 @@ extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_in
         hipLaunchKernelGGL(sparse_range_count_kernel, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
         SR_CHECK_LAUNCH();
     }
-    SR_TRY(launch_range_scan(reinterpret_cast<uint32_t*>(idx->range_tab), n_chunks, nq, d_lims, s));
+    SR_TRY(launch_range_scan(reinterpret_cast<uint32_t*>(idx->range_tab.p), n_chunks, nq, d_lims, s));
     int64_t h_total = 0;
     SR_CHECK_HIP(hipMemcpyAsync(&h_total, d_lims + nq, 8, hipMemcpyDeviceToHost, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));

@@ -12,11 +12,7 @@
 // posting.  Terms are applied in the query's term order with a barrier between
 // them and an unfused multiply-add, so every per-doc sum is bit-identical to the
 // reference's term-serial fp32 accumulation.
-#include "common.h"
-#include <algorithm>
-#include <mutex>
-#include <utility>
-#include <vector>
+#include "sparse_index.h"
 
 #define SP_TILE 8192
 #ifndef SPB_Q
@@ -34,6 +30,8 @@
 #ifndef SP_RING
 #define SP_RING 3     // register sets of the group walk: SP_RING - 1 groups of loads in flight per workgroup
 #endif
+static_assert(SP_TILE == SR_SPARSE_TILE_DOCS && SP_SUB == SR_SPARSE_SKIP_DOCS && SPB_Q == SR_SPARSE_BLOCK_QUERIES,
+              "sparse_index.h states the skip table's geometry and the plan's weights per entry");
 
 struct SparseArgs {
     const int64_t* indptr;
@@ -931,56 +929,6 @@ __global__ void sparse_block_plan_kernel(const int64_t* __restrict__ q_indptr, c
         if (q[i] >= 0) q_done[q[i]] = ok ? 1 : 0;
 }
 
-// dense column of a heavy term: column[slot][doc] = value (the buffer is zero-filled first)
-__global__ void sparse_dense_fill_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc_ids,
-                                         const float* __restrict__ vals, const int32_t* __restrict__ slot_term,
-                                         int64_t stride, float* __restrict__ dense) {
-    const int slot = blockIdx.y;
-    const int64_t t = slot_term[slot];
-    const int64_t b = indptr[t], e = indptr[t + 1];
-    float* col = dense + (int64_t)slot * stride;
-    for (int64_t pp = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pp < e; pp += (int64_t)gridDim.x * blockDim.x)
-        col[doc_ids[pp]] = vals[pp];
-}
-
-// ---- index build: skip table + validation -----------------------------------
-// skip[t][b] = number of postings of term t with doc id < b * SP_SUB  (lower bound); n_sub entries + 1 per term
-__global__ void sparse_skip_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc_ids,
-                                   int64_t n_terms, int n_sub, int32_t* __restrict__ skip) {
-    const int64_t t = blockIdx.x;
-    const int64_t b = indptr[t], e = indptr[t + 1];
-    const int64_t len = e - b;
-    const int n_tiles = n_sub;
-    for (int tile = threadIdx.x; tile <= n_tiles; tile += blockDim.x) {
-        const int64_t bound = (int64_t)tile * SP_SUB;
-        int64_t lo = 0, hi = len;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)doc_ids[b + mid] < bound) lo = mid + 1; else hi = mid;
-        }
-        skip[t * (n_tiles + 1) + tile] = (int32_t)lo;
-    }
-}
-
-// flags[0] |= 1 if a posting list is not strictly ascending, |= 2 if a doc id is out of range,
-// |= 4 if indptr is not monotone
-__global__ void sparse_validate_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc_ids,
-                                       int64_t n_terms, int64_t n_docs, int* __restrict__ flags) {
-    const int64_t t = blockIdx.x;
-    const int64_t b = indptr[t], e = indptr[t + 1];
-    if (e < b) { if (threadIdx.x == 0) atomicOr(flags, 4); return; }
-    int bad = 0;
-    for (int64_t p = b + threadIdx.x; p < e; p += blockDim.x) {
-        const int32_t d = doc_ids[p];
-        if (d < 0 || (int64_t)d >= n_docs) bad |= 2;
-        if (p > b && doc_ids[p - 1] >= d) bad |= 1;
-    }
-    if (bad) atomicOr(flags, bad);
-}
-
-#include "sparse_index.h"
-static_assert(SP_TILE == SR_SPARSE_TILE_DOCS && SP_SUB == SR_SPARSE_SKIP_DOCS, "sparse_index.h states the skip table's geometry");
-
 // postings of the batch's query terms inside tiles [tile_begin, tile_begin + n_t): one thread per query term
 __global__ void sparse_count_postings_kernel(const int32_t* __restrict__ skip, int n_tiles, int64_t n_terms,
                                              const int64_t* __restrict__ q_indptr,
@@ -996,245 +944,61 @@ __global__ void sparse_count_postings_kernel(const int32_t* __restrict__ skip, i
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(total, n);
 }
 
-static void sparse_free_device(sr_sparse_index* idx) {
-    void* ptrs[] = {idx->skip, idx->dense, idx->dense_slot, idx->plan_term, idx->plan_w, idx->plan_n, idx->plan_ok, idx->plan_bad,
-                    idx->plan_off, idx->plan_perm, idx->q_done, idx->range_tab};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    idx->range_tab = nullptr;
-    idx->range_tab_cap = 0;
-    idx->range_nq = -1;
-    idx->skip = nullptr;
-    idx->dense = nullptr;
-    idx->dense_slot = nullptr;
-    idx->plan_term = nullptr;
-    idx->plan_w = nullptr;
-    idx->plan_n = nullptr;
-    idx->plan_ok = nullptr;
-    idx->plan_bad = nullptr;
-    idx->plan_off = nullptr;
-    idx->plan_perm = nullptr;
-    idx->q_done = nullptr;
-}
-
-// Terms present in at least 1 / SP_DENSE_DIV of the docs get a dense column: the longest lists first, at most SP_DENSE_MAX of
-// them and never more than a quarter of the free device memory (a column costs 4 B per doc, the list it shadows 8 B per
-// posting; measured at MSMARCO shape, thresholds of 1/3 .. 1/8 of the docs are within 2 % of each other, 1/2 is 5 % slower).
-// No such term: the query-block kernel is not used.
-#define SP_DENSE_DIV 4
-#define SP_DENSE_MAX 64
-static int sparse_build_dense(sr_sparse_index* idx, hipStream_t s) {
-    int div = SP_DENSE_DIV, max_slots = SP_DENSE_MAX;
-    if (const char* e = sr_dev_getenv("SR_SPARSE_DENSE_DIV")) div = atoi(e);
-    if (const char* e = sr_dev_getenv("SR_SPARSE_DENSE_MAX")) max_slots = atoi(e);
-    if (div <= 0 || max_slots <= 0) return SR_OK;
-    std::vector<int64_t> h_indptr((size_t)idx->n_terms + 1);
-    SR_CHECK_HIP(hipMemcpyAsync(h_indptr.data(), idx->indptr, sizeof(int64_t) * h_indptr.size(), hipMemcpyDeviceToHost, s));
+// Orders every batch's queries, cuts them into blocks of SPB_Q and plans the blocks, once per call.  *any_fallback: a query whose
+// terms do not ascend - its block goes through the per-query kernel.
+static int sparse_plan_blocks(sr_sparse_index* idx, const SparseCall& call, int64_t q_batch, bool* any_fallback, hipStream_t s) {
+    const int64_t nq = call.nq;
+    const int64_t n_batches = ceil_div64(nq, q_batch);
+    const int64_t blocks_per_batch = ceil_div64(q_batch, SPB_Q);
+    const int pad = (int)(blocks_per_batch * SPB_Q);
+    const int64_t n_blocks = n_batches * blocks_per_batch;
+    int64_t h[2];
+    SR_CHECK_HIP(hipMemcpyAsync(h, call.q_indptr, 8, hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipMemcpyAsync(h + 1, call.q_indptr + nq, 8, hipMemcpyDeviceToHost, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));
-    std::vector<std::pair<int64_t, int32_t>> heavy;   // (-length, term)
-    for (int64_t t = 0; t < idx->n_terms; ++t) {
-        const int64_t len = h_indptr[(size_t)t + 1] - h_indptr[(size_t)t];
-        if (len > 0 && len * div >= idx->n_docs) heavy.emplace_back(-len, (int32_t)t);
+    const int64_t nnz = h[1] - h[0];
+    SR_REQUIRE(nnz >= 0, "sr_sparse_search: query indptr not monotone");
+    const int64_t cap = nnz > 0 ? nnz : 1;
+    const char* who = "sr_sparse_search (query-block plan)";
+    SR_TRY(idx->plan_term.reserve(cap, who));
+    SR_TRY(idx->plan_w.reserve(cap * SPB_Q, who));
+    SR_TRY(idx->plan_n.reserve(n_blocks, who));
+    SR_TRY(idx->plan_ok.reserve(n_blocks, who));
+    SR_TRY(idx->plan_off.reserve(n_blocks, who));
+    SR_TRY(idx->plan_perm.reserve(n_blocks * SPB_Q, who));
+    SR_TRY(idx->q_done.reserve(nq, who));
+    SR_TRY(idx->plan_bad.reserve(1, who));
+    SR_CHECK_HIP(hipMemsetAsync(idx->plan_bad.p, 0, sizeof(int), s));
+    int do_sort = 1;
+    if (const char* e = sr_dev_getenv("SR_SPARSE_SORT")) do_sort = atoi(e);       // A/B switch: 0 = blocks of consecutive queries
+    hipLaunchKernelGGL(sparse_block_order_kernel, dim3((unsigned)n_batches), dim3(256), 0, s, call.q_indptr, call.q_cols, nq, q_batch, pad,
+                       idx->n_terms, idx->indptr, idx->dense_slot.p, idx->n_tiles * (SP_TILE / SP_SUB), do_sort, idx->plan_perm.p,
+                       idx->plan_off.p, blocks_per_batch);
+    SR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sparse_block_plan_kernel, dim3((unsigned)ceil_div64(n_blocks, 64)), dim3(64), 0, s, call.q_indptr, call.q_cols,
+                       call.q_vals, nq, idx->n_terms, q_batch, pad, blocks_per_batch, n_blocks, idx->plan_perm.p, idx->plan_off.p,
+                       idx->plan_term.p, idx->plan_w.p, idx->plan_n.p, idx->plan_ok.p, idx->q_done.p, idx->plan_bad.p);
+    SR_CHECK_LAUNCH();
+    int h_bad = 0;
+    SR_CHECK_HIP(hipMemcpyAsync(&h_bad, idx->plan_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    *any_fallback = h_bad != 0;
+    static DeviceOnce lds_set;
+    if (bool* slot = lds_set.pending()) {
+        SR_CHECK_HIP(hipFuncSetAttribute((const void*)sparse_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(sizeof(float) * SPB_Q * SPB_TSTRIDE)));
+        *slot = true;
     }
-    if (heavy.empty()) return SR_OK;
-    std::sort(heavy.begin(), heavy.end());
-    const int64_t stride = (int64_t)idx->n_tiles * SP_TILE;
-    size_t free_b = 0, total_b = 0;
-    SR_CHECK_HIP(hipMemGetInfo(&free_b, &total_b));
-    int64_t fit = (int64_t)(free_b / 4) / (stride * 4);       // at most a quarter of what is free
-    int n = (int)heavy.size();
-    if (n > max_slots) n = max_slots;
-    if (n > fit) n = (int)fit;
-    if (n <= 0) return SR_OK;
-    std::vector<int32_t> h_slot((size_t)idx->n_terms, -1), h_terms((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        h_slot[(size_t)heavy[(size_t)i].second] = i;
-        h_terms[(size_t)i] = heavy[(size_t)i].second;
-    }
-    int32_t* d_terms = nullptr;
-    if (hipMalloc(&idx->dense, sizeof(float) * (size_t)stride * (size_t)n) != hipSuccess ||
-        hipMalloc(&idx->dense_slot, sizeof(int32_t) * (size_t)idx->n_terms) != hipSuccess ||
-        hipMalloc(&d_terms, sizeof(int32_t) * (size_t)n) != hipSuccess) {
-        (void)hipGetLastError();      // columns are an optimisation: without them the per-query kernel serves every block
-        if (idx->dense) (void)hipFree(idx->dense);
-        if (idx->dense_slot) (void)hipFree(idx->dense_slot);
-        if (d_terms) (void)hipFree(d_terms);
-        idx->dense = nullptr;
-        idx->dense_slot = nullptr;
-        return SR_OK;
-    }
-    int rc = SR_OK;
-    if (hipMemsetAsync(idx->dense, 0, sizeof(float) * (size_t)stride * (size_t)n, s) != hipSuccess ||
-        hipMemcpyAsync(idx->dense_slot, h_slot.data(), sizeof(int32_t) * h_slot.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_terms, h_terms.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess) {
-        rc = SR_ERR_HIP;
-    } else {
-        hipLaunchKernelGGL(sparse_dense_fill_kernel, dim3(256, (unsigned)n), dim3(256), 0, s, idx->indptr, idx->doc_ids, idx->vals,
-                           d_terms, stride, idx->dense);
-        if (hipStreamSynchronize(s) != hipSuccess) rc = SR_ERR_HIP;
-    }
-    (void)hipFree(d_terms);
-    if (rc != SR_OK) {
-        sr_set_error("sr_sparse_index_create: building the dense columns failed: %s", hipGetErrorString(hipGetLastError()));
-        return rc;
-    }
-    idx->n_dense = n;
-    idx->dense_stride = stride;
+    ++idx->n_block_calls;
+    if (*any_fallback) ++idx->n_fallback_calls;
     return SR_OK;
 }
 
-extern "C" int sr_sparse_index_create(sr_sparse_index** out, const int64_t* d_indptr, const int32_t* d_doc_ids,
-                                      const float* d_vals, int64_t n_terms, int64_t n_docs, sr_stream stream) {
-    SR_REQUIRE(out, "sr_sparse_index_create: null out");
-    SR_REQUIRE(n_terms >= 1 && n_docs >= 1, "sr_sparse_index_create: need n_terms >= 1 and n_docs >= 1");
-    SR_REQUIRE(n_docs < 0xffffffffll, "sr_sparse_index_create: n_docs exceeds 32 bits");
-    SR_REQUIRE(d_indptr, "sr_sparse_index_create: null indptr");
-    hipStream_t s = (hipStream_t)stream;
-    sr_sparse_index* idx = new sr_sparse_index();
-    idx->indptr = d_indptr;
-    idx->doc_ids = d_doc_ids;
-    idx->vals = d_vals;
-    idx->n_terms = n_terms;
-    idx->n_docs = n_docs;
-    idx->n_tiles = (int)ceil_div64(n_docs, SP_TILE);
-    int* d_flags = nullptr;
-    int h_flags = 0;
-    int rc = SR_OK;
-    do {
-        const int n_sub = idx->n_tiles * (SP_TILE / SP_SUB);
-        if (hipMalloc(&idx->skip, sizeof(int32_t) * (size_t)n_terms * (size_t)(n_sub + 1)) != hipSuccess ||
-            hipMalloc(&d_flags, sizeof(int)) != hipSuccess) {
-            sr_set_error("sr_sparse_index_create: out of device memory for the skip table (%lld x %d)",
-                         (long long)n_terms, idx->n_tiles + 1);
-            rc = SR_ERR_NOMEM;
-            break;
-        }
-        if (hipMemsetAsync(d_flags, 0, sizeof(int), s) != hipSuccess) { rc = SR_ERR_HIP; break; }
-        hipLaunchKernelGGL(sparse_validate_kernel, dim3((unsigned)n_terms), dim3(256), 0, s, d_indptr, d_doc_ids,
-                           n_terms, n_docs, d_flags);
-        hipLaunchKernelGGL(sparse_skip_kernel, dim3((unsigned)n_terms), dim3(64), 0, s, d_indptr, d_doc_ids, n_terms,
-                           n_sub, idx->skip);
-        if (hipMemcpyAsync(&h_flags, d_flags, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            sr_set_error("sr_sparse_index_create: %s", hipGetErrorString(hipGetLastError()));
-            rc = SR_ERR_HIP;
-            break;
-        }
-        if (h_flags) {
-            sr_set_error("sr_sparse_index_create: invalid index (%s%s%s)",
-                         (h_flags & 1) ? "posting list not strictly ascending by doc id; " : "",
-                         (h_flags & 2) ? "doc id out of [0, n_docs); " : "", (h_flags & 4) ? "indptr not monotone" : "");
-            rc = SR_ERR_INVALID;
-        }
-    } while (0);
-    if (d_flags) (void)hipFree(d_flags);
-    if (rc == SR_OK) rc = sparse_build_dense(idx, s);
-    if (rc == SR_OK) rc = sparse_cert_build(idx, s);
-    if (rc != SR_OK) {
-        sparse_free_device(idx);
-        delete idx;
-        return rc;
-    }
-    *out = idx;
-    return SR_OK;
-}
-
-extern "C" int sr_sparse_index_set_workspace_limit(sr_sparse_index* idx, int64_t bytes) {
-    SR_REQUIRE(idx && bytes >= (1 << 20), "sr_sparse_index_set_workspace_limit: bad argument");
-    idx->ws_limit = bytes;
-    return SR_OK;
-}
-
-extern "C" int sr_sparse_index_destroy(sr_sparse_index* idx) {
-    if (!idx) return SR_OK;
-    if (idx->d_stamps) {       // diagnostic: mean microseconds per phase of a sampled wave
-        unsigned long long h[8] = {0};
-        if (hipMemcpy(h, idx->d_stamps, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[7])
-            fprintf(stderr, "[sparse stamps] waves %llu: fetch %.2f dense %.2f short %.2f long %.2f wait-for-slowest %.2f filter %.2f total %.2f us\n",
-                    h[7], h[0] * 0.01 / h[7], h[1] * 0.01 / h[7], h[2] * 0.01 / h[7], h[3] * 0.01 / h[7], h[6] * 0.01 / h[7], h[4] * 0.01 / h[7],
-                    h[5] * 0.01 / h[7]);
-        (void)hipFree(idx->d_stamps);
-    }
-    idx->ws.release();
-    idx->order.release();
-    sparse_cert_destroy(idx->cert);
-    idx->cert = nullptr;
-    sparse_free_device(idx);
-    if (idx->d_postings) (void)hipFree(idx->d_postings);
-    if (idx->d_counters) (void)hipFree(idx->d_counters);
-    if (idx->seg_cnt) (void)hipFree(idx->seg_cnt);
-    if (idx->pair_status) (void)hipFree(idx->pair_status);
-    if (idx->pair_qflags) (void)hipFree(idx->pair_qflags);
-    if (idx->filt_words) (void)hipFree(idx->filt_words);
-    if (idx->filt_blocks) (void)hipFree(idx->filt_blocks);
-    if (idx->filt_list) (void)hipFree(idx->filt_list);
-    delete idx;
-    return SR_OK;
-}
-
-extern "C" int sr_sparse_index_block_stats(sr_sparse_index* idx, int64_t* n_dense_terms, int64_t* n_block_calls,
-                                           int64_t* n_fallback_calls) {
-    SR_REQUIRE(idx && n_dense_terms && n_block_calls && n_fallback_calls, "sr_sparse_index_block_stats: null argument");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    *n_dense_terms = idx->n_dense;
-    *n_block_calls = idx->n_block_calls;
-    *n_fallback_calls = idx->n_fallback_calls;
-    return SR_OK;
-}
-
-// Work counters of the query-block kernel (measurement hook, like sr_sparse_index_profile): while enabled every workgroup adds
-// what it loads and applies to 6 device counters; the call returns them and resets them.  out[0] dense columns loaded (one =
-// 4096 floats), [1] (column, query) applications (one = 4096 unfused multiply-adds), [2] / [3] postings loaded by the one-step /
-// grouped scatter runs (8 bytes each, one LDS read-modify-write each), [4] plan entries fetched, [5] workgroup-tiles.
-extern "C" int sr_sparse_index_work_counters(sr_sparse_index* idx, int enable, uint64_t* out6) {
-    SR_REQUIRE(idx, "sr_sparse_index_work_counters: null index");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    if (!idx->d_counters) {
-        SR_CHECK_HIP(hipMalloc((void**)&idx->d_counters, 6 * 8));
-        SR_CHECK_HIP(hipMemset(idx->d_counters, 0, 6 * 8));
-    }
-    SR_CHECK_HIP(hipDeviceSynchronize());
-    if (out6) SR_CHECK_HIP(hipMemcpy(out6, idx->d_counters, 6 * 8, hipMemcpyDeviceToHost));
-    SR_CHECK_HIP(hipMemset(idx->d_counters, 0, 6 * 8));
-    idx->count_work = enable != 0;
-    return SR_OK;
-}
-
-extern "C" int sr_sparse_index_profile(sr_sparse_index* idx, int enable) {
-    SR_REQUIRE(idx, "sr_sparse_index_profile: null index");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    if (enable && !idx->d_postings) {
-        SR_CHECK_HIP(hipMalloc((void**)&idx->d_postings, 8));
-        SR_CHECK_HIP(hipMemset(idx->d_postings, 0, 8));
-    }
-    idx->prof.enabled = enable != 0;
-    return SR_OK;
-}
-
-extern "C" int sr_sparse_index_profile_read(sr_sparse_index* idx, int64_t* n_launches, double* total_ms,
-                                            double* total_posting_bytes) {
-    SR_REQUIRE(idx && n_launches && total_ms && total_posting_bytes, "sr_sparse_index_profile_read: null argument");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    *n_launches = idx->prof.read(total_ms);
-    unsigned long long n = 0;
-    if (idx->d_postings) {
-        SR_CHECK_HIP(hipMemcpy(&n, idx->d_postings, 8, hipMemcpyDeviceToHost));
-        SR_CHECK_HIP(hipMemset(idx->d_postings, 0, 8));
-    }
-    *total_posting_bytes = 8.0 * (double)n;
-    return SR_OK;
-}
-
-// The exact kernels over all docs for the queries of one CSR (the caller holds idx->mu and the stream order).
-static int sparse_exact_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
-                               const float* d_q_vals, int64_t nq, int k, float threshold, int64_t id_base,
-                               int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
-                               hipStream_t s) {
-
+int sparse_exact_search(sr_sparse_index* idx, const SparseCall& call, hipStream_t s) {
+    const int64_t nq = call.nq;
+    const int k = call.k;
     // query batches bound the candidate workspace: cap (slots per query) = docs per launch
-    int64_t q_batch_max = 1024;
-    if (const char* e = sr_dev_getenv("SR_SPARSE_QBATCH")) q_batch_max = atoll(e) >= 4 ? atoll(e) / 4 * 4 : 4;
-    int64_t q_batch = nq < q_batch_max ? nq : q_batch_max;
+    int64_t q_batch = nq < 1024 ? nq : 1024;
     // k > SR_MAX_TOPK: the running set and the select's buffers (topk_large.hip) count against the limit as well, next to at
     // least one tile of candidate slots per query; the batch shrinks to fit (the bits do not depend on it)
     const int64_t large_bytes = k > SR_MAX_TOPK ? topk_large_bytes_per_query(k) : 0;
@@ -1254,78 +1018,21 @@ static int sparse_exact_search(sr_sparse_index* idx, const int64_t* d_q_indptr, 
     if (max_tiles > idx->n_tiles) max_tiles = idx->n_tiles;
     SR_TRY(idx->ws.ensure(q_batch, k, max_tiles * SP_TILE));
     const int seg_cap = (int)(max_tiles * (SP_TILE / SPB_TILE) * 4);          // regions per query and launch (<= 512)
-    if (idx->seg_q_cap < q_batch || idx->seg_cap < seg_cap) {
-        if (idx->seg_cnt) (void)hipFree(idx->seg_cnt);
-        idx->seg_cnt = nullptr;
-        SR_CHECK_HIP(hipMalloc((void**)&idx->seg_cnt, sizeof(int) * (size_t)q_batch * (size_t)seg_cap));
-        SR_CHECK_HIP(hipMemsetAsync(idx->seg_cnt, 0, sizeof(int) * (size_t)q_batch * (size_t)seg_cap, s));
+    if (idx->seg_q_cap < q_batch || idx->seg_cap < seg_cap) {                 // a new shape [q_batch][seg_cap], zero between launches
+        idx->seg_q_cap = 0;
+        idx->seg_cap = 0;
+        SR_TRY(idx->seg_cnt.reserve(q_batch * seg_cap, "sr_sparse_search (candidate regions)"));
+        SR_CHECK_HIP(hipMemsetAsync(idx->seg_cnt.p, 0, sizeof(int) * (size_t)q_batch * (size_t)seg_cap, s));
         idx->seg_q_cap = q_batch;
         idx->seg_cap = seg_cap;
     }
 
-    // query-block path: order every batch's queries, cut them into blocks of SPB_Q and plan the blocks, once per call
-    bool use_blocks = idx->n_dense > 0;
-    if (const char* e = sr_dev_getenv("SR_SPARSE_BLOCKS")) use_blocks = use_blocks && atoi(e) != 0;
+    // query-block path where the index has dense columns
+    const bool use_blocks = idx->n_dense > 0;
     bool any_fallback = !use_blocks;
-    const int64_t n_batches = ceil_div64(nq, q_batch);
+    if (use_blocks) SR_TRY(sparse_plan_blocks(idx, call, q_batch, &any_fallback, s));
     const int64_t blocks_per_batch = ceil_div64(q_batch, SPB_Q);
     const int pad = (int)(blocks_per_batch * SPB_Q);
-    const int64_t n_blocks = n_batches * blocks_per_batch;
-    if (use_blocks) {
-        int64_t h[2];
-        SR_CHECK_HIP(hipMemcpyAsync(h, d_q_indptr, 8, hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipMemcpyAsync(h + 1, d_q_indptr + nq, 8, hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        const int64_t nnz = h[1] - h[0];
-        SR_REQUIRE(nnz >= 0, "sr_sparse_search: query indptr not monotone");
-        if (nnz > idx->plan_cap || n_blocks > idx->plan_blocks_cap || nq > idx->plan_q_cap) {
-            void* old[] = {idx->plan_term, idx->plan_w, idx->plan_n, idx->plan_ok, idx->plan_off, idx->plan_perm, idx->q_done};
-            for (void* p : old)
-                if (p) (void)hipFree(p);
-            idx->plan_term = nullptr; idx->plan_w = nullptr; idx->plan_n = nullptr; idx->plan_ok = nullptr;
-            idx->plan_off = nullptr; idx->plan_perm = nullptr; idx->q_done = nullptr;
-            idx->plan_cap = idx->plan_blocks_cap = idx->plan_q_cap = 0;
-            const int64_t cap = nnz > 0 ? nnz : 1;
-            SR_CHECK_HIP(hipMalloc(&idx->plan_term, sizeof(int32_t) * (size_t)cap));
-            SR_CHECK_HIP(hipMalloc(&idx->plan_w, sizeof(float) * SPB_Q * (size_t)cap));
-            SR_CHECK_HIP(hipMalloc(&idx->plan_n, sizeof(int32_t) * (size_t)n_blocks));
-            SR_CHECK_HIP(hipMalloc(&idx->plan_ok, (size_t)n_blocks));
-            SR_CHECK_HIP(hipMalloc(&idx->plan_off, sizeof(int64_t) * (size_t)n_blocks));
-            SR_CHECK_HIP(hipMalloc(&idx->plan_perm, sizeof(int32_t) * (size_t)n_blocks * SPB_Q));
-            SR_CHECK_HIP(hipMalloc(&idx->q_done, (size_t)nq));
-            idx->plan_cap = cap;
-            idx->plan_blocks_cap = n_blocks;
-            idx->plan_q_cap = nq;
-        }
-        if (!idx->plan_bad) SR_CHECK_HIP(hipMalloc(&idx->plan_bad, sizeof(int)));
-        SR_CHECK_HIP(hipMemsetAsync(idx->plan_bad, 0, sizeof(int), s));
-        int do_sort = 1;
-        if (const char* e = sr_dev_getenv("SR_SPARSE_SORT")) do_sort = atoi(e);       // A/B switch: 0 = blocks of consecutive queries
-        hipLaunchKernelGGL(sparse_block_order_kernel, dim3((unsigned)n_batches), dim3(256), 0, s, d_q_indptr, d_q_cols, nq, q_batch, pad,
-                           idx->n_terms, idx->indptr, idx->dense_slot, idx->n_tiles * (SP_TILE / SP_SUB), do_sort, idx->plan_perm,
-                           idx->plan_off, blocks_per_batch);
-        SR_CHECK_LAUNCH();
-        hipLaunchKernelGGL(sparse_block_plan_kernel, dim3((unsigned)ceil_div64(n_blocks, 64)), dim3(64), 0, s, d_q_indptr, d_q_cols,
-                           d_q_vals, nq, idx->n_terms, q_batch, pad, blocks_per_batch, n_blocks, idx->plan_perm, idx->plan_off,
-                           idx->plan_term, idx->plan_w, idx->plan_n, idx->plan_ok, idx->q_done, idx->plan_bad);
-        SR_CHECK_LAUNCH();
-        int h_bad = 0;
-        SR_CHECK_HIP(hipMemcpyAsync(&h_bad, idx->plan_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        any_fallback = h_bad != 0;        // a query whose terms do not ascend: its block goes through the per-query kernel
-        static DeviceOnce lds_set;
-        if (bool* slot = lds_set.pending()) {
-            SR_CHECK_HIP(hipFuncSetAttribute((const void*)sparse_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(sizeof(float) * SPB_Q * SPB_TSTRIDE)));
-            *slot = true;
-        }
-        if (sr_dev_getenv("SR_SPARSE_STAMPS") && !idx->d_stamps) {
-            SR_CHECK_HIP(hipMalloc((void**)&idx->d_stamps, 8 * 8));
-            SR_CHECK_HIP(hipMemsetAsync(idx->d_stamps, 0, 8 * 8, s));
-        }
-        ++idx->n_block_calls;
-        if (any_fallback) ++idx->n_fallback_calls;
-    }
 
     for (int64_t qb = 0; qb < nq; qb += q_batch) {
         const int64_t nqb = (nq - qb) < q_batch ? (nq - qb) : q_batch;
@@ -1338,46 +1045,45 @@ static int sparse_exact_search(sr_sparse_index* idx, const int64_t* d_q_indptr, 
             a.indptr = idx->indptr;
             a.doc_ids = idx->doc_ids;
             a.vals = idx->vals;
-            a.skip = idx->skip;
+            a.skip = idx->skip.p;
             a.n_tiles = idx->n_tiles;
             a.n_docs = idx->n_docs;
             a.n_terms = idx->n_terms;
-            a.q_indptr = d_q_indptr;
-            a.q_cols = d_q_cols;
-            a.q_vals = d_q_vals;
+            a.q_indptr = call.q_indptr;
+            a.q_cols = call.q_cols;
+            a.q_vals = call.q_vals;
             a.q_base = qb;
             a.tile_begin = (int)t0;
-            a.threshold = threshold;
+            a.threshold = call.threshold;
             a.tau = idx->ws.tau;
             a.cand_keys = idx->ws.cand_keys;
             a.cand_count = idx->ws.cand_count;
             a.cand_cap = idx->ws.cand_cap;
-            a.id_base = (uint32_t)id_base;
-            a.id_stride = (uint32_t)id_stride;
-            a.q_done = use_blocks ? idx->q_done : nullptr;
+            a.id_base = (uint32_t)call.id_base;
+            a.id_stride = (uint32_t)call.id_stride;
+            a.q_done = use_blocks ? idx->q_done.p : nullptr;
             // wave-owned regions only when every block runs the query-block kernel (the per-query kernel appends through the
-            // atomic counter into the same buffer); SR_SPARSE_SEG=0: atomic reservations (A/B)
-            bool use_seg = use_blocks && !any_fallback && SPB_Q == 4 && idx->seg_cap <= 512;
-            if (const char* e = sr_dev_getenv("SR_SPARSE_SEG")) use_seg = use_seg && atoi(e) != 0;
-            a.seg_cnt = use_seg ? idx->seg_cnt : nullptr;
+            // atomic counter into the same buffer)
+            const bool use_seg = use_blocks && !any_fallback && SPB_Q == 4 && idx->seg_cap <= 512;
+            a.seg_cnt = use_seg ? idx->seg_cnt.p : nullptr;
             a.seg_n = idx->seg_cap;
             idx->prof.begin(s);
             if (use_blocks) {
                 SparseBlockArgs b;
                 b.a = a;
-                b.dense = idx->dense;
-                b.dense_slot = idx->dense_slot;
+                b.dense = idx->dense.p;
+                b.dense_slot = idx->dense_slot.p;
                 b.dense_stride = idx->dense_stride;
-                b.plan_term = idx->plan_term;
-                b.plan_w = idx->plan_w;
-                b.plan_n = idx->plan_n;
-                b.plan_ok = idx->plan_ok;
-                b.plan_off = idx->plan_off;
-                b.blk_q = idx->plan_perm + (qb / q_batch) * pad;
+                b.plan_term = idx->plan_term.p;
+                b.plan_w = idx->plan_w.p;
+                b.plan_n = idx->plan_n.p;
+                b.plan_ok = idx->plan_ok.p;
+                b.plan_off = idx->plan_off.p;
+                b.blk_q = idx->plan_perm.p + (qb / q_batch) * pad;
                 b.blk_base = (qb / q_batch) * blocks_per_batch;
                 b.diag = 0;
-                b.stamps = idx->d_stamps;
-                b.counters = idx->count_work ? idx->d_counters : nullptr;
+                b.stamps = nullptr;           // the kernel's per-phase stamps: no switch allocates them
+                b.counters = idx->count_work ? idx->d_counters.p : nullptr;
 #ifdef SR_DIAG_BUILD        // wrong results by design: read only by a diagnostic build, never by the product .so
                 if (const char* e = sr_dev_getenv("SR_SPARSE_DIAG")) b.diag = atoi(e);
 #endif
@@ -1392,205 +1098,28 @@ static int sparse_exact_search(sr_sparse_index* idx, const int64_t* d_q_indptr, 
                 SR_CHECK_LAUNCH();
             }
             idx->prof.end(s, 0, 0);
-            if (idx->prof.enabled && idx->d_postings) {
+            if (idx->prof.enabled && idx->d_postings.p) {
                 int64_t h[2];
-                SR_CHECK_HIP(hipMemcpyAsync(h, d_q_indptr + qb, 8, hipMemcpyDeviceToHost, s));
-                SR_CHECK_HIP(hipMemcpyAsync(h + 1, d_q_indptr + qb + nqb, 8, hipMemcpyDeviceToHost, s));
+                SR_CHECK_HIP(hipMemcpyAsync(h, call.q_indptr + qb, 8, hipMemcpyDeviceToHost, s));
+                SR_CHECK_HIP(hipMemcpyAsync(h + 1, call.q_indptr + qb + nqb, 8, hipMemcpyDeviceToHost, s));
                 SR_CHECK_HIP(hipStreamSynchronize(s));
                 const int64_t nterms = h[1] - h[0];
                 if (nterms > 0)
                     hipLaunchKernelGGL(sparse_count_postings_kernel, dim3((unsigned)ceil_div64(nterms, 256)), dim3(256), 0, s,
-                                       idx->skip, idx->n_tiles, idx->n_terms, d_q_indptr, d_q_cols, qb, qb + nqb, (int)t0, (int)nt,
-                                       idx->d_postings);
+                                       idx->skip.p, idx->n_tiles, idx->n_terms, call.q_indptr, call.q_cols, qb, qb + nqb, (int)t0, (int)nt,
+                                       idx->d_postings.p);
             }
             if (a.seg_cnt) {
                 hipLaunchKernelGGL(sparse_gather_kernel, dim3((unsigned)nqb), dim3(256), 0, s, idx->ws.cand_keys, idx->ws.cand_count,
-                                   idx->ws.cand_cap, idx->seg_cnt, idx->seg_cap, SPB_TILE / 4);
+                                   idx->ws.cand_cap, idx->seg_cnt.p, idx->seg_cap, SPB_TILE / 4);
                 SR_CHECK_LAUNCH();
             }
             SR_TRY(topk_compact(idx->ws, nqb, k, s));
             t0 += nt;
             step *= 2;
         }
-        SR_TRY(topk_finalize(idx->ws, nqb, k, 0.f, d_out_scores + qb * k, d_out_ids + qb * k,
-                             d_out_counts ? d_out_counts + qb : nullptr, s));
+        const SparseCall part = call.rows(qb, nqb);
+        SR_TRY(topk_finalize(idx->ws, nqb, k, 0.f, part.out_scores, part.out_ids, part.out_counts, s));
     }
     return SR_OK;
-}
-
-// ---- queries the certified scorer hands back: their rows are gathered into a CSR of their own, scored by the exact kernels and
-// scattered into the result rows
-__global__ void sparse_sub_gather_kernel(const int64_t* __restrict__ q_indptr, const int32_t* __restrict__ q_cols, const float* __restrict__ q_vals,
-                                         const int64_t* __restrict__ sel, const int64_t* __restrict__ sub_indptr, int32_t* __restrict__ sub_cols,
-                                         float* __restrict__ sub_vals) {
-    const int64_t j = blockIdx.x;
-    const int64_t q = sel[j];
-    const int64_t b = q_indptr[q], n = q_indptr[q + 1] - b, o = sub_indptr[j];
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-        sub_cols[o + i] = q_cols[b + i];
-        sub_vals[o + i] = q_vals[b + i];
-    }
-}
-__global__ void sparse_sub_scatter_kernel(const int64_t* __restrict__ sel, int k, const float* __restrict__ s_in, const int64_t* __restrict__ i_in,
-                                          const int32_t* __restrict__ c_in, float* __restrict__ s_out, int64_t* __restrict__ i_out,
-                                          int32_t* __restrict__ c_out) {
-    const int64_t j = blockIdx.x;
-    const int64_t q = sel[j];
-    for (int i = threadIdx.x; i < k; i += blockDim.x) {
-        s_out[q * k + i] = s_in[j * k + i];
-        i_out[q * k + i] = i_in[j * k + i];
-    }
-    if (c_out && threadIdx.x == 0) c_out[q] = c_in[j];
-}
-
-// wide_band > 0 (and at least SR_CERT_RETRY_MIN queries handed back): the sub-batch first goes through the certified scorer once more with
-// that many keys beyond k - a certificate that failed for want of room is then usually given - and only what it hands back again reaches
-// the exact kernels.  filt (null: the whole collection): the search runs under a document filter - the second pass under its bitmap, and
-// the exact kernels are the list routes of sr_sparse_search_subset over its list, which rank the allowed documents only.
-#define SR_CERT_RETRY_MIN 256
-static int sparse_redo_exact(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
-                             int k, float threshold, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids,
-                             int32_t* d_out_counts, const uint8_t* d_uncert, hipStream_t s, int wide_band = 0, SparseDocFilter* filt = nullptr) {
-    std::vector<uint8_t> h_un((size_t)nq);
-    std::vector<int64_t> h_ip((size_t)nq + 1);
-    SR_CHECK_HIP(hipMemcpyAsync(h_un.data(), d_uncert, (size_t)nq, hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipMemcpyAsync(h_ip.data(), d_q_indptr, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipStreamSynchronize(s));
-    std::vector<int64_t> sel, sub_ip(1, 0);
-    for (int64_t q = 0; q < nq; ++q)
-        if (h_un[(size_t)q]) {
-            sel.push_back(q);
-            sub_ip.push_back(sub_ip.back() + (h_ip[(size_t)q + 1] - h_ip[(size_t)q]));
-        }
-    const int64_t ns = (int64_t)sel.size();
-    if (ns == 0) return SR_OK;
-    if (filt) SR_TRY(sparse_filter_need_list(idx, filt, s));
-    const int64_t nnz = sub_ip.back();
-    int64_t *d_sel = nullptr, *d_sip = nullptr, *d_ids = nullptr;
-    int32_t *d_cols = nullptr, *d_cnt = nullptr;
-    float *d_vals = nullptr, *d_sc = nullptr;
-    int rc = SR_OK;
-    if (hipMalloc((void**)&d_sel, 8 * (size_t)ns) != hipSuccess || hipMalloc((void**)&d_sip, 8 * ((size_t)ns + 1)) != hipSuccess ||
-        hipMalloc((void**)&d_cols, 4 * (size_t)(nnz > 0 ? nnz : 1)) != hipSuccess || hipMalloc((void**)&d_vals, 4 * (size_t)(nnz > 0 ? nnz : 1)) != hipSuccess ||
-        hipMalloc((void**)&d_sc, 4 * (size_t)ns * (size_t)k) != hipSuccess || hipMalloc((void**)&d_ids, 8 * (size_t)ns * (size_t)k) != hipSuccess ||
-        hipMalloc((void**)&d_cnt, 4 * (size_t)ns) != hipSuccess) {
-        sr_set_error("sr_sparse_search: out of device memory for %lld re-done queries", (long long)ns);
-        rc = SR_ERR_NOMEM;
-    }
-    if (rc == SR_OK && (hipMemcpyAsync(d_sel, sel.data(), 8 * (size_t)ns, hipMemcpyHostToDevice, s) != hipSuccess ||
-                        hipMemcpyAsync(d_sip, sub_ip.data(), 8 * ((size_t)ns + 1), hipMemcpyHostToDevice, s) != hipSuccess))
-        rc = SR_ERR_HIP;
-    if (rc == SR_OK) {
-        hipLaunchKernelGGL(sparse_sub_gather_kernel, dim3((unsigned)ns), dim3(64), 0, s, d_q_indptr, d_q_cols, d_q_vals, d_sel, d_sip, d_cols, d_vals);
-        bool done = false;
-        if (wide_band > 0 && ns >= SR_CERT_RETRY_MIN && idx->cert) {
-            uint8_t* d_un2 = nullptr;
-            if (hipMalloc((void**)&d_un2, (size_t)ns) == hipSuccess) {
-                int64_t n_un2 = 0;
-                bool no_memory = false;
-                int band_used = 0;
-                rc = sparse_cert_search(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, d_un2, &n_un2, &no_memory,
-                                        wide_band, &band_used, filt ? filt->mask_pad : nullptr, s);
-                if (rc == SR_OK && !no_memory) {
-                    ++idx->n_cert_retries;
-                    sparse_cert_count_retry(idx->cert, ns);
-                    if (n_un2 > 0)
-                        rc = sparse_redo_exact(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, d_un2, s, 0, filt);
-                    done = true;
-                }
-                if (hipStreamSynchronize(s) != hipSuccess && rc == SR_OK) rc = SR_ERR_HIP;
-                (void)hipFree(d_un2);
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        if (rc == SR_OK && !done)
-            rc = filt ? sparse_subset_lists(idx, d_sip, d_cols, d_vals, ns, k, threshold, filt->list, filt->m, subset_sparse_use_array(filt->m, idx->n_docs),
-                                            id_base, id_stride, d_sc, d_ids, d_cnt, s, filt->who)
-                      : sparse_exact_search(idx, d_sip, d_cols, d_vals, ns, k, threshold, id_base, id_stride, d_sc, d_ids, d_cnt, s);
-    }
-    if (rc == SR_OK) {
-        hipLaunchKernelGGL(sparse_sub_scatter_kernel, dim3((unsigned)ns), dim3(256), 0, s, d_sel, k, d_sc, d_ids, d_cnt, d_out_scores, d_out_ids,
-                           d_out_counts);
-        if (hipGetLastError() != hipSuccess) rc = SR_ERR_HIP;
-    }
-    if (hipStreamSynchronize(s) != hipSuccess && rc == SR_OK) rc = SR_ERR_HIP;      // the temporaries are freed below
-    if (rc == SR_ERR_HIP) sr_set_error("sr_sparse_search: re-doing uncertified queries failed: %s", hipGetErrorString(hipGetLastError()));
-    void* ptrs[] = {d_sel, d_sip, d_cols, d_vals, d_sc, d_ids, d_cnt};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    return rc;
-}
-
-// certified two-stage scorer (sparse_cert.hip) where the index has one and k leaves room for its band of extra keys.  Dev switch
-// SR_SPARSE_CERT_SEARCH=0: exact kernels only (A/B)
-bool sparse_cert_applies(const sr_sparse_index* idx, int k) {
-    bool use_cert = idx->cert != nullptr && k + 1024 <= SR_MAX_TOPK;
-    {
-        const char* forced = sr_dev_getenv("SR_SPARSE_CERT");        // 1: also on collections too small for it to pay (tests)
-        if (!(forced && atoi(forced) == 1)) use_cert = use_cert && idx->n_docs >= 8ll * (k + 1024);
-    }
-    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_SEARCH")) use_cert = use_cert && atoi(e) != 0;
-    return use_cert;
-}
-
-int sparse_certified_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq, int k,
-                            float threshold, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
-                            SparseDocFilter* filt, hipStream_t s) {
-    // The scorer's workspace is ~200 KB per query: the query set goes through in batches (a whole MSMARCO-Dev set is one batch), and
-    // a batch whose buffers do not fit in device memory is served by the exact kernels instead of failing the call; the queries it
-    // cannot certify are re-done by the exact kernels.
-    int64_t batch = SR_CERT_QUERY_BATCH;
-    if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_BATCH")) batch = std::max<int64_t>(32, atoll(e) / 32 * 32);   // tests: several batches on small inputs
-    uint8_t* d_uncert = sparse_cert_uncert_buffer(idx->cert, nq < batch ? nq : batch);
-    for (int64_t qb = 0; qb < nq; qb += batch) {
-        const int64_t nqb = nq - qb < batch ? nq - qb : batch;
-        float* o_s = d_out_scores + qb * k;
-        int64_t* o_i = d_out_ids + qb * k;
-        int32_t* o_c = d_out_counts ? d_out_counts + qb : nullptr;
-        int64_t n_un = 0;
-        bool no_memory = d_uncert == nullptr || (filt && filt->mask_pad == nullptr);
-        if (sr_dev_getenv("SR_SPARSE_CERT_FAKE_OOM")) no_memory = true;          // tests: the fallback below
-        int band_used = 0;
-        if (!no_memory)
-            SR_TRY(sparse_cert_search(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, d_uncert,
-                                      &n_un, &no_memory, 0, &band_used, filt ? filt->mask_pad : nullptr, s));
-        if (no_memory) {
-            ++idx->n_cert_no_memory;
-            if (filt) {
-                SR_TRY(sparse_filter_need_list(idx, filt, s));
-                SR_TRY(sparse_subset_lists(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, filt->list, filt->m,
-                                           subset_sparse_use_array(filt->m, idx->n_docs), id_base, id_stride, o_s, o_i, o_c, s, filt->who));
-            } else {
-                SR_TRY(sparse_exact_search(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, s));
-            }
-        } else if (n_un > 0) {
-            // many queries handed back under a band that could still grow: once more through the scorer with the widest band, then the exact kernels
-            const int widest = SR_MAX_TOPK - k;                // worth a second pass only if it at least doubles the band
-            SR_TRY(sparse_redo_exact(idx, d_q_indptr + qb, d_q_cols, d_q_vals, nqb, k, threshold, id_base, id_stride, o_s, o_i, o_c, d_uncert, s,
-                                     2 * band_used <= widest ? widest : 0, filt));
-        }
-    }
-    return SR_OK;
-}
-
-extern "C" int sr_sparse_search(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
-                                const float* d_q_vals, int64_t nq, int k, float threshold, int64_t id_base,
-                                int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
-                                sr_stream stream) {
-    SR_REQUIRE(idx, "sr_sparse_search: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search: bad nq");
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
-    SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
-               "sr_sparse_search: global doc index exceeds 32 bits");
-    if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids, "sr_sparse_search: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(idx->mu);
-    StreamOrder::Scope in_order(idx->order, s);
-    if (sparse_cert_applies(idx, k))
-        return sparse_certified_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids,
-                                       d_out_counts, nullptr, s);
-    return sparse_exact_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids,
-                               d_out_counts, s);
 }

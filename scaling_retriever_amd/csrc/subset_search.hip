@@ -395,33 +395,19 @@ static bool subset_sparse_use_mask(const sr_sparse_index* idx, int64_t nq, int k
     return wants && m > 0 && sparse_cert_applies(idx, k) && sparse_cert_mask_pad_bytes(idx->cert) <= idx->ws_limit;
 }
 
-template <typename T>
-static int sparse_filter_scratch(T** p, int64_t* cap, int64_t want, const char* who) {
-    if (*cap >= want) return SR_OK;
-    if (*p) (void)hipFree(*p);                            // waits for the calls that read it
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, (size_t)want * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        sr_set_error("%s: out of device memory for %lld bytes of filter scratch", who, (long long)(want * (int64_t)sizeof(T)));
-        return SR_ERR_NOMEM;
-    }
-    *cap = want;
-    return SR_OK;
-}
-
 int sparse_filter_need_list(sr_sparse_index* idx, SparseDocFilter* f, hipStream_t s) {
     if (f->list_ready) return SR_OK;
-    SR_TRY(sparse_filter_scratch(&idx->filt_list, &idx->filt_list_cap, f->m > 0 ? f->m : 1, f->who));
-    SR_TRY(launch_doc_mask_expand(f->words, idx->n_docs, idx->filt_blocks, idx->filt_list, f->m, s));
-    f->list = idx->filt_list;
+    SR_TRY(idx->filt_list.reserve(f->m > 0 ? f->m : 1, f->who));
+    SR_TRY(launch_doc_mask_expand(f->words, idx->n_docs, idx->filt_blocks.p, idx->filt_list.p, f->m, s));
+    f->list = idx->filt_list.p;
     f->list_ready = true;
     return SR_OK;
 }
 
-int sparse_subset_lists(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq, int k,
-                        float threshold, const int64_t* d_subset, int64_t m, bool array, int64_t id_base, int64_t id_stride, float* d_out_scores,
-                        int64_t* d_out_ids, int32_t* d_out_counts, hipStream_t s, const char* who) {
+int sparse_subset_lists(sr_sparse_index* idx, const SparseCall& call, const int64_t* d_subset, int64_t m, bool array, hipStream_t s,
+                        const char* who) {
+    const int64_t nq = call.nq;
+    const int k = call.k;
     int64_t nq_batch = 0, slab = 0;
     SR_TRY(subset_plan(idx->ws_limit, nq, k, m, array ? SS_TILE : 64, &nq_batch, &slab, who));
     SparseSubsetArgs a;
@@ -432,12 +418,12 @@ int sparse_subset_lists(sr_sparse_index* idx, const int64_t* d_q_indptr, const i
         // the pair route's own two ways to the postings, as in sr_sparse_score_pairs (dev switch SR_PAIR_SPARSE_ROUTE=postings)
         const char* route = sr_dev_getenv("SR_PAIR_SPARSE_ROUTE");
         if (!(route && strcmp(route, "postings") == 0)) sparse_cert_forward_index(idx->cert, &a.x.fwd_indptr, &a.x.fwd_tv);
-        if (a.x.fwd_indptr) SR_TRY(sparse_pair_query_flags(idx, d_q_indptr, d_q_cols, nq, who, s));
+        if (a.x.fwd_indptr) SR_TRY(sparse_pair_query_flags(idx, call.q_indptr, call.q_cols, nq, who, s));
     }
-    a.q_cols = d_q_cols; a.q_vals = d_q_vals;
-    a.skip = idx->skip; a.skip_n = idx->n_tiles * (SR_SPARSE_TILE_DOCS / SR_SPARSE_SKIP_DOCS);
-    a.threshold = threshold;
-    a.id_base = (uint32_t)id_base; a.id_stride = (uint32_t)id_stride;
+    a.q_cols = call.q_cols; a.q_vals = call.q_vals;
+    a.skip = idx->skip.p; a.skip_n = idx->n_tiles * (SR_SPARSE_TILE_DOCS / SR_SPARSE_SKIP_DOCS);
+    a.threshold = call.threshold;
+    a.id_base = (uint32_t)call.id_base; a.id_stride = (uint32_t)call.id_stride;
     a.st = idx->pair_status;
     const int n_tiles = idx->n_tiles;
     // a launch appends at most min(m, its docs) keys per query; slab < m only with slab >= SS_TILE (subset_plan: min_slab)
@@ -445,10 +431,11 @@ int sparse_subset_lists(sr_sparse_index* idx, const int64_t* d_q_indptr, const i
     if (tiles_per_launch > 65535) tiles_per_launch = 65535;                   // the grid's second dimension
     for (int64_t qb = 0; qb < nq; qb += nq_batch) {
         const int64_t nqb = nq - qb < nq_batch ? nq - qb : nq_batch;
+        const SparseCall part = call.rows(qb, nqb);
         SR_TRY(idx->ws.ensure(nqb, k, slab));
         SR_TRY(topk_reset(idx->ws, nqb, s));
-        a.q_indptr = d_q_indptr + qb;
-        a.q_ascending = a.x.fwd_indptr ? idx->pair_qflags + qb : nullptr;
+        a.q_indptr = part.q_indptr;
+        a.q_ascending = a.x.fwd_indptr ? idx->pair_qflags.p + qb : nullptr;
         a.nq = nqb;
         a.tau = idx->ws.tau; a.cand_keys = idx->ws.cand_keys; a.cand_count = idx->ws.cand_count; a.cand_cap = idx->ws.cand_cap;
         if (m > 0 && array) {
@@ -476,7 +463,7 @@ int sparse_subset_lists(sr_sparse_index* idx, const int64_t* d_q_indptr, const i
                 step *= 2;
             }
         }
-        SR_TRY(topk_finalize(idx->ws, nqb, k, 0.f, d_out_scores + qb * k, d_out_ids + qb * k, d_out_counts ? d_out_counts + qb : nullptr, s));
+        SR_TRY(topk_finalize(idx->ws, nqb, k, 0.f, part.out_scores, part.out_ids, part.out_counts, s));
     }
     return SR_OK;
 }
@@ -497,6 +484,7 @@ extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
+    const SparseCall call{d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts};
     const bool array = subset_sparse_use_array(m, idx->n_docs);
     {   // a call that cannot run fails before any launch, whichever route serves it
         int64_t nq_batch = 0, slab = 0;
@@ -512,16 +500,14 @@ extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_
     // list goes on to the list routes, which score nothing, write the padding rows and report it)
     if (subset_sparse_use_mask(idx, nq, k, m) && subset_status_end(idx->pair_status, d_subset, "sr_sparse_search_subset", "position", s) == SR_OK) {
         const int64_t n_words = doc_mask_words(idx->n_docs);
-        SR_TRY(sparse_filter_scratch(&idx->filt_words, &idx->filt_words_cap, n_words > 0 ? n_words : 1, "sr_sparse_search_subset"));
-        SR_TRY(launch_doc_mask_from_list(d_subset, m, idx->filt_words, idx->n_docs, idx->pair_status, nullptr, s));
+        SR_TRY(idx->filt_words.reserve(n_words > 0 ? n_words : 1, "sr_sparse_search_subset"));
+        SR_TRY(launch_doc_mask_from_list(d_subset, m, idx->filt_words.p, idx->n_docs, idx->pair_status, nullptr, s));
         SparseDocFilter f;
-        f.words = idx->filt_words; f.list = d_subset; f.m = m; f.list_ready = true; f.who = "sr_sparse_search_subset";
+        f.words = idx->filt_words.p; f.list = d_subset; f.m = m; f.list_ready = true; f.who = "sr_sparse_search_subset";
         SR_TRY(sparse_cert_mask_pad(idx, f.words, &f.mask_pad, s));
-        return sparse_certified_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts,
-                                       &f, s);
+        return sparse_certified_search(idx, call, &f, s);
     }
-    SR_TRY(sparse_subset_lists(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, d_subset, m, array, id_base, id_stride, d_out_scores, d_out_ids,
-                               d_out_counts, s, "sr_sparse_search_subset"));
+    SR_TRY(sparse_subset_lists(idx, call, d_subset, m, array, s, "sr_sparse_search_subset"));
     return subset_status_end(idx->pair_status, d_subset, "sr_sparse_search_subset", "position", s);
 }
 
@@ -543,10 +529,11 @@ extern "C" int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
+    const SparseCall call{d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts};
     const int64_t n_blocks = doc_mask_blocks(n_bits);
-    SR_TRY(sparse_filter_scratch(&idx->filt_blocks, &idx->filt_blocks_cap, n_blocks + 1, "sr_sparse_search_masked"));
-    int64_t* d_count = idx->filt_blocks + n_blocks;
-    SR_TRY(launch_doc_mask_count(d_mask_words, n_bits, idx->filt_blocks, d_count, s));
+    SR_TRY(idx->filt_blocks.reserve(n_blocks + 1, "sr_sparse_search_masked"));
+    int64_t* d_count = idx->filt_blocks.p + n_blocks;
+    SR_TRY(launch_doc_mask_count(d_mask_words, n_bits, idx->filt_blocks.p, d_count, s));
     SparseDocFilter f;
     f.words = d_mask_words;
     SR_CHECK_HIP(hipMemcpyAsync(&f.m, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -559,10 +546,8 @@ extern "C" int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_
     SR_TRY(subset_status_begin(&idx->pair_status, s));        // the list kernels read it; nothing here can raise it
     if (subset_sparse_use_mask(idx, nq, k, f.m)) {
         SR_TRY(sparse_cert_mask_pad(idx, f.words, &f.mask_pad, s));
-        return sparse_certified_search(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts,
-                                       &f, s);
+        return sparse_certified_search(idx, call, &f, s);
     }
     SR_TRY(sparse_filter_need_list(idx, &f, s));
-    return sparse_subset_lists(idx, d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, f.list, f.m, array, id_base, id_stride, d_out_scores, d_out_ids,
-                               d_out_counts, s, "sr_sparse_search_masked");
+    return sparse_subset_lists(idx, call, f.list, f.m, array, s, "sr_sparse_search_masked");
 }

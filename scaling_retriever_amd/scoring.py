@@ -1,7 +1,7 @@
 """Thin torch-tensor front ends over the scoring entry points of libsr_hip.so.
 
 These hold device memory (torch tensors) and call the C ABI; all arithmetic is in
-the HIP kernels (csrc/dense_score.hip, csrc/sparse_score.hip, csrc/topk.hip).
+the HIP kernels (csrc/dense_score.hip, csrc/sparse_cert.hip, csrc/sparse_score.hip, csrc/topk.hip).
 The reference-shaped classes in indexer.py are built on top of these.
 """
 import ctypes

@@ -48,7 +48,7 @@ def _queries(rng, V, nq, max_terms, always=(), order="asc"):
     return np.array(qi, np.int64), np.concatenate(qc), np.concatenate(qv)
 
 
-DENSE_DIV, DENSE_MAX = 4, 64      # csrc/sparse_score.hip SP_DENSE_DIV / SP_DENSE_MAX
+DENSE_DIV, DENSE_MAX = 4, 64      # csrc/sparse_index.hip SP_DENSE_DIV / SP_DENSE_MAX
 
 
 def _n_dense(indptr, N):
