@@ -119,7 +119,7 @@ extern "C" int sr_gemm_f16_scaled(const void* d_A, const void* d_W, int32_t M, i
     return launch_gemm_bf16(EPI_RESID_F32_H, g, (hipStream_t)stream);
 }
 
-// The other launches of the fp16-plane layer loop (model_forward, encoder.hip), exported for tests/test_fp32_planes_gpu.py: thin
+// The other launches of the fp16-plane layer loop (layer_f16_planes, encoder.hip), exported for tests/test_fp32_planes_gpu.py: thin
 // calls into the launch functions with the arguments the encoder fills.  Everything is validated before a device is touched.
 extern "C" int sr_rows_split_f16(float* d_src, const float* d_embed, const int32_t* d_tok_id, const float* d_norm_w, float eps,
                                  int32_t T, int32_t K, int32_t nseg, void* d_planes, float* d_a_inv, const float* d_gu_cmax,
@@ -173,7 +173,7 @@ extern "C" int sr_gemm_f16_planes(const void* d_A, const void* d_W, int32_t M, i
 }
 
 // What the bf16 regime (fp32_planes = 0) and the two heads launch besides the GEMMs and the attention, exported for
-// tests/test_bf16_regime_gpu.py: thin calls into the launch functions of encoder.hip with the arguments the encoder fills.
+// tests/test_bf16_regime_gpu.py: thin calls into the launch functions of encoder_kernels.hip with the arguments the encoder fills.
 // Everything is validated before a device is touched.
 extern "C" int sr_rmsnorm_bf16(float* d_x, const float* d_embed, const int32_t* d_tok_id, const void* d_delta, const float* d_norm_w,
                                void* d_xn, float* d_xn_f32, float eps, int32_t T, int32_t H, sr_stream stream) {

@@ -234,6 +234,13 @@ struct DeviceBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+// a device allocation that lives as long as one call: freed when the scope ends, not kept on a handle
+template <typename T>
+struct CallBuf : DeviceBuf<T> {
+    CallBuf() = default;
+    CallBuf(const CallBuf&) = delete;
+    ~CallBuf() { this->release(); }
+};
 
 // ---- per-launch HIP event log (measurement hook of the search handles) ----
 #include <vector>

@@ -82,16 +82,20 @@ struct GemmArgs {
 // A/W/C 16-byte aligned.
 int launch_gemm_bf16(GemmEpilogue epi, const GemmArgs& g, hipStream_t s);
 
-// fp16-plane regime, for the test hooks of api.hip (the encoder launches the same kernels, encoder.hip): norm + split of fp32 rows
-// [T, K] into [f1 | f0 | f0] / [f1 | f0] plane segments + inverse row scales, and the gate/up bound max_j |w_gate_j||w_up_j|
-// (cmax is zeroed first)
+// fp16-plane regime (encoder_f16_planes.hip), called by the layer loop of encoder.hip and by the test hooks of api.hip: norm + split of
+// fp32 rows [T, K] (T >= 1) into [f1 | f0 | f0] / [f1 | f0] plane segments + inverse row scales, and the gate/up bound
+// max_j |w_gate_j||w_up_j| (cmax is zeroed first); launch_gu_pair_samples: that product for ns evenly spaced single pairs (sr_model_finalize)
 int launch_rows_split_f16(float* x, const float* embed, const int* tok, const float* w, bf16_t* xs, float* inv, int T, int K, float eps,
                           int nseg, const float* gu_cmax, float* act_sc, float* act_inv, hipStream_t s);
 int launch_gu_cmax(const bf16_t* wgu_s, const float* wgu_i, int I, int K, int nseg, float* cmax, hipStream_t s);
+int launch_gu_pair_samples(const bf16_t* wgu_s, const float* wgu_i, int I, int K, int nseg, int ns, float* p, hipStream_t s);
 
-// bf16 regime and heads, for the test hooks of api.hip (the encoder calls the same functions, encoder.hip): RMSNorm with its optional
+// bf16 regime and heads (encoder_kernels.hip), called by encoder.hip and by the test hooks of api.hip: RMSNorm with its optional
 // embedding gather / pending bf16 residual / "residual add only" exit, the plan's launches (spans + cu_seqlens, then the per-token
-// arrays), the dense head's two launches (stats: [T] float2 scratch) and the sparse head's finish
+// arrays), the dense head's two launches (stats: [T] float2 scratch) and the sparse head's finish; launch_rmsnorm_split: the RMSNorm of
+// the bf16-plane fp32 regimes, output as plane segments [T, n_seg * H]
+int launch_rmsnorm_split(float* x, const float* embed, const int* tok_id, const float* w, bf16_t* xs, int T, int H, float eps,
+                         const SplitMap& map, hipStream_t s);
 int launch_rmsnorm(float* x, const float* embed, const int* tok_id, const bf16_t* delta, const float* w, bf16_t* xn, float* xn_f32, int T,
                    int H, float eps, hipStream_t s);
 int launch_plan_rows(const int64_t* mask, int B, int L, int mode, int* span_start, int* span_len, int* pool_start, int* row_len,

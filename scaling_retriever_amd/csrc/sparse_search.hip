@@ -30,14 +30,6 @@ __global__ void sparse_sub_scatter_kernel(const int64_t* __restrict__ sel, int k
     if (c_out && threadIdx.x == 0) c_out[q] = c_in[j];
 }
 
-// a device allocation that lives as long as one call of sparse_redo_exact: freed when it returns, not kept on the handle
-template <typename T>
-struct CallBuf : DeviceBuf<T> {
-    CallBuf() = default;
-    CallBuf(const CallBuf&) = delete;
-    ~CallBuf() { this->release(); }
-};
-
 // The queries of `call` that d_uncert flags, through the exact kernels.  wide_band > 0 (and at least SR_CERT_RETRY_MIN queries handed
 // back): the sub-batch first goes through the certified scorer once more with that many keys beyond k - a certificate that failed for
 // want of room is then usually given - and only what it hands back again reaches the exact kernels.  filt (null: the whole collection):

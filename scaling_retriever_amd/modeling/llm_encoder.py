@@ -6,7 +6,7 @@ DecoderOnlyBiSparse :175-196, DecoderOnlyBiDense :370-520, LlamaBiSparse :199-20
 LlamaBiDense :523-525, Qwen2BiSparse :204-209, Qwen2BiDense :528-533) for the inference path: load / load_from_lora / encode /
 query_encode / doc_encode, attributes vocab_size / hidden_size / T / base_model.config.
 
-All arithmetic runs in libsr_hip.so (csrc/encoder.hip, gemm_bf16.hip, attention.hip).
+All arithmetic runs in libsr_hip.so (csrc/encoder.hip, model_weights.hip, gemm_bf16.hip, attention.hip).
 torch is used for device memory and checkpoint I/O only; there is no eager fallback -
 without the HIP library or a ROCm device, encode() raises.
 Training-only methods of the reference (forward losses, build with LoRA adapters,
@@ -359,7 +359,7 @@ class HipLlamaBackbone(torch.nn.Module):
     def _call_ranges(self, mask, sparse):
         """Row ranges [b0, b1) per C call.  The workspace holds max_batch_tokens PACKED tokens (pads are not computed), so
         a batch whose padded size fits goes through in one call; otherwise the rows are cut by the tokens they really
-        pack to - the span plan_rows_kernel keeps per row (csrc/encoder.hip): for the dense head
+        pack to - the span plan_rows_kernel keeps per row (csrc/encoder_kernels.hip): for the dense head
         [min(first unmasked, L - len), L), for the sparse head [first unmasked, last unmasked]."""
         B, L = mask.shape
         if B <= self.max_batch_seqs and B * L <= self.max_batch_tokens:

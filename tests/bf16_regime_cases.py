@@ -1,5 +1,5 @@
 """CPU-only pieces shared by test_bf16_regime_host.py and test_bf16_regime_gpu.py: what the bf16 regime (fp32_planes = 0,
-model_forward in csrc/encoder.hip) and the two heads launch besides the attention - the RMSNorm with its gather and pending
+layer_bf16 in csrc/encoder.hip) and the two heads launch besides the attention - the RMSNorm with its gather and pending
 residual, the bf16 GEMM with each of its epilogues, the dense head's pool, the sparse head's finish and the packing plan - as
 seeded cases, numpy restatements of the format arithmetic, float64 references, and the element-wise error bound of every kernel.
 
@@ -71,7 +71,7 @@ the bound is the documented one and stays.)
     |out - log(1 + m)| <= 2 e log(1 + m) + e (1 + m / (1 + m))          m <= 0: exactly +0                                  (F)
 
 Plan.  Integers: every array is compared bit for bit with plan_reference(), a plain restatement of the comments above
-plan_rows_kernel / plan_tokens_kernel in csrc/encoder.hip."""
+plan_rows_kernel / plan_tokens_kernel in csrc/encoder_kernels.hip."""
 import functools
 
 import numpy as np
@@ -137,7 +137,7 @@ NORM_H = [64, 320, 256, 512, 1024, 2048, 3072, 4096]        # rmsnorm_kernel<0> 
 NORM_T = [1, 3, 4, 5, 9]                                     # a workgroup holds four rows
 NORM_NCH = {64: 0, 320: 0, 256: 1, 512: 2, 1024: 4, 2048: 8, 3072: 12, 4096: 16}
 VOCAB = 23
-# what the encoder launches (launch_rmsnorm's call sites in csrc/encoder.hip), + gather and residual together with both outputs
+# what the encoder launches (launch_rmsnorm's call sites in csrc/encoder.hip: layer_bf16, model_forward, head_sparse, sr_model_last_hidden), + gather and residual together with both outputs
 NORM_COMBOS = {
     "first_layer": dict(gather=True, delta=False, w=True, xn=True, f32=False),       # embedding gather + input_layernorm
     "layer": dict(gather=False, delta=True, w=True, xn=True, f32=False),             # pending residual + norm

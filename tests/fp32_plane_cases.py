@@ -1,5 +1,5 @@
 """CPU-only pieces shared by test_fp32_planes_host.py and test_fp32_planes_gpu.py: what the fp32 regime on fp16 planes
-(fp32_planes = 16, model_forward in csrc/encoder.hip) launches around the attention - the row split with its norm, the gate/up
+(fp32_planes = 16, layer_f16_planes in csrc/encoder.hip) launches around the attention - the row split with its norm, the gate/up
 bound, and the fp16-plane GEMM with each of its epilogues - as seeded cases, numpy restatements of the format arithmetic
 (row_scale_pow2, split_f16x2 of csrc/common.h), float64 references, and the element-wise error bound of every kernel.
 

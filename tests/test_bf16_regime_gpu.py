@@ -5,7 +5,7 @@ sr_rmsnorm_bf16, sr_dense_head_pool, sr_sparse_finish, sr_encode_plan (include/s
 sr_gemm_bf16 (epilogues 0 - 4) and sr_gemm_qkv_rope_bias (fp32_out 0 / 1) reach every bf16-operand epilogue.  No element and no case
 is exempt; every output buffer is pre-filled with NaN and carries guard rows behind it that must come back untouched.
 
-RMSNorm (launch_rmsnorm, csrc/encoder.hip):
+RMSNorm (launch_rmsnorm, csrc/encoder_kernels.hip):
 
   kernel               H       reached by
   rmsnorm_kernel<0>    64 320  test_rmsnorm[64] [320]: H % 256 != 0, second pass re-reads the row

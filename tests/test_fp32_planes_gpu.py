@@ -3,7 +3,7 @@ element against float64 with the derived bounds of tests/fp32_plane_cases.py (te
 ideally rounded arithmetic is inside every bound and that the defects these tests are there for are outside).  Test hooks:
 sr_rows_split_f16, sr_gu_cmax_f16, sr_gemm_f16_planes (include/sr_hip.h, "building blocks").
 
-Row split (launch_rows_split_h, csrc/encoder.hip):
+Row split (launch_rows_split_f16, csrc/encoder_f16_planes.hip):
 
   kernel                          K            reached by
   rows_split_h_kernel             64 192 320   test_row_split[64 / 192 / 320]: K % 256 != 0, the maximum in the last K tail
