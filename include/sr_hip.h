@@ -89,7 +89,10 @@ int64_t sr_dense_index_ntotal(const sr_dense_index* idx);
  * select's buffers (4 k bytes per query) count against the workspace limit next to the candidate buffer; a call that does not
  * fit runs in query sub-batches of more than 64 queries each (same bits as one batch).  If even the smallest such batch does
  * not fit, the call returns SR_ERR_NOMEM (the byte count in sr_last_error()) and writes nothing.  The certified filter of
- * SR_PRECISION_FP32_FILTERED needs k + 64 candidates in the in-LDS path: a larger k runs the exact kernel.               */
+ * SR_PRECISION_FP32_FILTERED needs k + 64 candidates in the in-LDS path: a larger k runs the exact kernel.
+ * Order of every top-k this library returns (dense, sparse, subset / masked, merge): score descending with the scores compared as
+ * float values, then doc index ascending.  -0.0 and +0.0 are one score: between them the doc index alone decides, and a returned
+ * score of -0.0 reads back as +0.0.                                                                                          */
 int sr_dense_search(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
                     float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
 /* Arithmetic of the score kernel for query batches > 64:
@@ -439,8 +442,9 @@ int sr_sparse_csr_build(const int32_t* d_rows, const int32_t* d_cols, const floa
 /* ------------------------------------------------------------ top-k merge ---
  * The one exchange step of doc-sharded retrieval: merge `n_lists` per-shard
  * top-k lists (after the RCCL gather) into the global top-k per query.
- * d_scores fp32 [n_lists, nq, k], d_ids int64 [n_lists, nq, k] (ids < 0 = pad).
- * Outputs as sr_dense_search (pad_score fills unused slots).  1 <= k <= 2^30 with n_lists * k < 2^31; the library's workspace
+ * d_scores fp32 [n_lists, nq, k], d_ids int64 [n_lists, nq, k] (ids < 0 = pad; every other id must be below 2^32 and unique
+ * within its query: the key holds 32 id bits and nothing on the device checks the range; no score may be NaN).
+ * Outputs as sr_dense_search, in its order (pad_score fills unused slots).  1 <= k <= 2^30 with n_lists * k < 2^31; the library's workspace
  * holds n_lists * k candidates and, for k > sr_max_topk(), 2k + k / 2 more 8-byte words per query.                        */
 int sr_topk_merge(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t nq, int k,
                   float pad_score, float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
@@ -756,6 +760,26 @@ int sr_encode_plan(const int64_t* d_input_ids, const int64_t* d_attention_mask, 
  * contract of the split modes.  A null d_src / d_p0, n < 0, n % 4 != 0 or a misaligned pointer is SR_ERR_INVALID before anything
  * launches; n = 0 is SR_OK.                                                                                                     */
 int sr_split_bf16(const float* d_src, int64_t n, void* d_p0, void* d_p1, void* d_p2, sr_stream stream);
+/* Test-only hook: the top-k protocol every search ends in (csrc/topk.hip, csrc/topk_large.hip), replayed on a caller-supplied stream of
+ * (score, id) entries with the thresholds and the running set read out after every compaction (tests/test_topk_replay_gpu.py,
+ * tests/topk_cases.py).  d_scores fp32 / d_ids int64 [nq, n_stream] on the device; an entry with id < 0 is no entry, every other id must
+ * be below 2^32 and unique within its query, no score may be NaN.  h_steps (host): n_steps + 1 ascending offsets into the stream, step i
+ * = entries [h_steps[i], h_steps[i + 1]), at most 2^22 of them.  Per step a producer appends the step's entries (filter = 1: only those
+ * with score >= tau[q], as every score kernel does; 0: all), then the library's compaction runs with k, k2 (0: no second rank) and
+ * select_over as the searches pass them (select_over is clamped into [k, 2k]); after the last step the final sort.  seg_n > 0: the
+ * producers use the segmented candidate slots of the split-bf16 kernels - producer p takes the step's entries [p seg_group,
+ * (p + 1) seg_group) and owns segment p; 1..4 survivors go to its segment, more (or p >= seg_n) behind one atomic reservation.
+ * Outputs: d_out_scores / d_out_ids [nq, k] and d_out_counts [nq] as sr_dense_search writes them (pad_score, id -1); per step
+ * d_trace_tau / d_trace_tau2 fp32 [n_steps, nq] (tau; the k2-th best score, tau2_init until a select has refreshed it) and
+ * d_trace_run int32 [n_steps, nq] (keys held) after the compaction, d_trace_cand int32 [n_steps, nq] the candidates it found, and, unless
+ * NULL, d_trace_keys uint64 [n_steps, nq, 2k]: the running set's keys (ordered score word << 32 | ~id), the first d_trace_run of each row.
+ * The workspace lives for the call, which waits for the stream before it returns.  SR_ERR_INVALID before anything touches a device: a
+ * null pointer (but d_trace_keys), sizes out of range, k outside [1, 2^20], k2 outside [0, k) or k2 > 0 / seg_n > 0 with k >
+ * sr_max_topk(), seg_n no multiple of 4, steps that do not ascend inside [0, n_stream] or are longer than 2^22.                       */
+int sr_topk_replay(const float* d_scores, const int64_t* d_ids, int64_t nq, int64_t n_stream, const int64_t* h_steps, int n_steps,
+                   int k, int k2, int64_t select_over, int filter, int seg_n, int seg_group, float tau2_init, float pad_score,
+                   float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, float* d_trace_tau, float* d_trace_tau2,
+                   int32_t* d_trace_cand, int32_t* d_trace_run, uint64_t* d_trace_keys, sr_stream stream);
 
 #ifdef __cplusplus
 }

@@ -99,9 +99,12 @@ __device__ inline f32x4 sr_load_row4(const T* p) { return SrRow<T>::widen(*reint
 static inline size_t sr_dtype_size(int dtype) { return dtype == SR_DTYPE_F16 ? 2 : 4; }
 
 // ---- order-preserving float <-> uint32 (larger float => larger uint) ----
+// -0.0 takes the word of +0.0: the two compare equal as floats, so a key's order between them is the doc index alone (the
+// bit patterns would put every -0.0 below every +0.0), and sr_ord2f gives +0.0 back for both
 __host__ __device__ inline uint32_t sr_f2ord(float f) {
     union { float f; uint32_t u; } c; c.f = f;
-    return (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
+    const uint32_t u = c.u == 0x80000000u ? 0u : c.u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __host__ __device__ inline float sr_ord2f(uint32_t o) {
     union { float f; uint32_t u; } c;

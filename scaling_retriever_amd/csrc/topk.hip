@@ -12,8 +12,13 @@
 // the end and emits the best k.
 //
 // Result = top-k by (score desc, doc index asc): deterministic, independent of
-// tile scheduling.  Stands in for faiss' heap top-k (indexer.py:211) and for
-// np.argpartition in select_topk (indexer.py:315-322).
+// tile scheduling.  Scores compare as float values: -0.0 and +0.0 are one score
+// (sr_f2ord in common.h gives both the word of +0.0, so the doc index decides
+// between them and -0.0 is returned as +0.0); NaN is never a key (no producer's
+// `score >= tau` lets one through).  Stands in for faiss' heap top-k
+// (indexer.py:211) and for np.argpartition in select_topk (indexer.py:315-322).
+// tests/topk_cases.py models this protocol; sr_topk_replay (topk_replay.hip)
+// runs it on a given key stream, path by path (tests/test_topk_replay_gpu.py).
 #include "common.h"
 #include <mutex>
 

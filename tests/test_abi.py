@@ -179,6 +179,41 @@ def test_split_bf16_hook_validates_before_it_launches():
     assert lib.sr_split_bf16(p, 0, p, None, None, None) == _lib.SR_OK and lib.sr_split_bf16(p, 0, p, p, p, None) == _lib.SR_OK
 
 
+def test_topk_replay_hook_validates_before_it_launches():
+    """sr_topk_replay rejects what it cannot run with SR_ERR_INVALID before anything touches a device: the device pointers below are
+    never dereferenced (h_steps is host memory and is read)."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(4096)
+    max_k = lib.sr_max_topk()
+
+    def replay(**kw):
+        a = dict(dict(sc=p, ids=p, nq=3, n=100, steps=[0, 40, 40, 100], k=10, k2=0, over=20, filter=1, seg_n=0, seg_group=1, out_s=p,
+                      out_i=p, out_c=p, t_tau=p, t_tau2=p, t_cand=p, t_run=p, t_keys=None), **kw)
+        steps = a["steps"]
+        h = None if steps is None else (ctypes.c_int64 * len(steps))(*steps)
+        n_steps = a.get("n_steps", 0 if steps is None else len(steps) - 1)
+        return lib.sr_topk_replay(a["sc"], a["ids"], a["nq"], a["n"], h, n_steps, a["k"], a["k2"], a["over"], a["filter"], a["seg_n"],
+                                  a["seg_group"], float("-inf"), -1.0, a["out_s"], a["out_i"], a["out_c"], a["t_tau"], a["t_tau2"],
+                                  a["t_cand"], a["t_run"], a["t_keys"], None)
+    for change, text in [(dict(sc=None), b"null pointer"), (dict(ids=None), b"null pointer"), (dict(steps=None, n_steps=1), b"null pointer"),
+                         (dict(out_s=None), b"null pointer"), (dict(out_i=None), b"null pointer"), (dict(out_c=None), b"null pointer"),
+                         (dict(t_tau=None), b"null pointer"), (dict(t_tau2=None), b"null pointer"), (dict(t_cand=None), b"null pointer"),
+                         (dict(t_run=None), b"null pointer"),
+                         (dict(nq=-1), b"bad sizes"), (dict(n=-1), b"bad sizes"), (dict(n_steps=-1), b"bad sizes"),
+                         (dict(k=0), b"k = 0"), (dict(k=(1 << 20) + 1), b"k = 1048577"),
+                         (dict(k2=-1), b"k2 = -1"), (dict(k2=10), b"k2 = 10"), (dict(k=max_k + 1, k2=1), b"k2 = 1"),
+                         (dict(filter=2), b"filter 2"),
+                         (dict(seg_n=6), b"seg_n = 6"), (dict(seg_n=-4), b"seg_n = -4"), (dict(k=max_k + 1, seg_n=8), b"seg_n = 8"),
+                         (dict(seg_n=8, seg_group=0), b"seg_group = 0"),
+                         (dict(steps=[0, 50, 40, 100]), b"steps must ascend"), (dict(steps=[-1, 40]), b"steps must ascend"),
+                         (dict(steps=[0, 40, 101]), b"steps must ascend"),
+                         (dict(n=1 << 23, steps=[0, (1 << 22) + 1]), b"more than 2^22")]:
+        rc = replay(**change)
+        assert rc == _lib.SR_ERR_INVALID and text in lib.sr_last_error(), (change, rc, lib.sr_last_error())
+    assert replay(nq=0) == _lib.SR_OK and replay(nq=0, k=max_k + 1, over=0, t_keys=p) == _lib.SR_OK
+
+
 def test_attention_bf16_hook_empty_batch_and_head_geometry():
     """sr_attention_varlen: B = 0 is SR_OK, and num_heads that is no multiple of num_kv_heads is SR_ERR_INVALID - both before
     anything touches a device: the pointers below are never dereferenced."""
