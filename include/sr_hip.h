@@ -215,6 +215,12 @@ int64_t sr_dense_index_id_end(const sr_dense_index* idx);
 int sr_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t* d_words, int64_t n_bits, sr_stream stream);
 int sr_doc_list_from_mask(const uint32_t* d_words, int64_t n_bits, int64_t* d_list, int64_t capacity,
                           int64_t* d_count, sr_stream stream);
+/* A bitmap carried over to another numbering: bit i of d_dst_words uint32 [ceil(n_dst_bits / 32)] := bit d_map[i] of d_src_words where
+ * 0 <= d_map[i] < n_src_bits (d_map int64 [n_dst_bits] on the device), else 0; the unused bits of the last word are 0.  Entries of
+ * d_map may repeat.  One thread per destination word, no atomics, queued on `stream`, no read-back.  The exact hybrid search turns a
+ * mask over dense positions into one over sparse positions with it (d_map = s2d).                                                  */
+int sr_doc_mask_remap(const uint32_t* d_src_words, int64_t n_src_bits, const int64_t* d_map, int64_t n_dst_bits,
+                      uint32_t* d_dst_words, sr_stream stream);
 /* sr_dense_search_subset with the allow-list given as a bitmap: d_mask_words uint32 [ceil(n_bits / 32)] on the device, n_bits ==
  * sr_dense_index_id_end(idx) (anything else: SR_ERR_INVALID before any device work).  Returns EXACTLY what sr_dense_search_subset
  * returns for the ascending list of the set bits - ids, score bits, tie order, padding, limits on k (with m = the number of set bits) -
@@ -246,12 +252,30 @@ int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t 
  * above -inf.  nq = 0 or an empty index: lims all zero, total 0.  Scores: the exact fp32 chain of sr_dense_score_pairs (per 8 columns
  * k = 8s + j, then 8s + 4 + j) for EVERY nq, 1 included, whatever sr_dense_index_set_precision says: a returned score equals
  * sr_dense_score_pairs of that pair bit for bit, and sr_dense_search's wherever that search accumulates in this order.  fp32 and fp16
- * rows alike (the twin contract of sr_dense_index_add_f16).  No atomics: two calls return the same bytes.  Not offered: a range
- * search under a subset or mask, doc-sharded, or on the certified filter's 16-bit pass.                           */
+ * rows alike (the twin contract of sr_dense_index_add_f16).  No atomics: two calls return the same bytes.  Under a document bitmap:
+ * sr_dense_range_count_masked / _fill_masked below.  Not offered: a range search under a per-query mask or a list (a caller with a
+ * short list has sr_dense_score_pairs), doc-sharded, or on the certified filter's 16-bit pass.                    */
 int sr_dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
                          int64_t* d_lims, int64_t* total, sr_stream stream);
 int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
                         const int64_t* d_lims, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream);
+/* The range search under a document bitmap: d_mask_words uint32 [ceil(n_bits / 32)] on the device, in the bit convention
+ * of sr_dense_search_masked, n_bits == sr_dense_index_id_end(idx) (anything else: SR_ERR_INVALID before any device work).  A hit is
+ * score > thr[q] AND the bit of the document's global index is set; everything else is the contract of sr_dense_range_count / _fill
+ * word for word: (segment, row) order, the score bits of sr_dense_score_pairs for every nq, fp32 and fp16 rows, no atomics, the
+ * guard p < min(lims[q + 1], capacity) on every store, and the pairing on the handle - a fill needs a preceding count of the same kind
+ * with the same nq (a masked fill after an unmasked count, or the reverse: SR_ERR_INVALID) and the count's bitmap.  Bits are
+ * consulted only at the indices of indexed documents: a set bit in a gap of a strided segment is ignored, not an error (unlike
+ * sr_dense_search_masked, which names it), bits of the last word at or beyond n_bits are ignored, and the library never reads past
+ * word ceil(n_bits / 32) - 1.  The bitmap is read in place by both passes: keep it unchanged between the count and its fill.  A
+ * 256-row tile whose bits are all clear is skipped whole (no loads, no MFMAs), so a clustered filter costs about its share of
+ * non-empty tiles; under a uniformly random filter nearly every tile holds an allowed row and the pass costs what the unrestricted
+ * one does.  Not offered: per-query masks, doc-sharded.                                                                            */
+int sr_dense_range_count_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                const uint32_t* d_mask_words, int64_t n_bits, int64_t* d_lims, int64_t* total, sr_stream stream);
+int sr_dense_range_fill_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                               const uint32_t* d_mask_words, int64_t n_bits, const int64_t* d_lims, float* d_out_scores,
+                               int64_t* d_out_ids, int64_t capacity, sr_stream stream);
 int sr_dense_index_destroy(sr_dense_index* idx);
 /* Measurement hook: while enabled, every launch of the score kernel is bracketed by HIP
  * events on the search stream.  _read synchronises those events and returns the number
@@ -334,7 +358,8 @@ int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, con
  * a copy of the bitmap in the length its kernel walks (n_docs / 8 bytes rounded up to whole 1 024-document tiles, counted against the
  * workspace limit).  sr_sparse_index_cert_stats counts a masked pass like any other.  The call waits for the stream once for the
  * count of set bits, then on the mask route as sr_sparse_search does (twice per batch of 8 192 queries, and once more per batch with
- * handed-back queries); on the list routes not again.  Not under a mask: doc-sharded search, per-query masks, range search.      */
+ * handed-back queries); on the list routes not again.  Not under a mask: doc-sharded search, per-query masks (the range search under
+ * a mask is sr_sparse_range_count_masked / _fill_masked).                                                                          */
 int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
                             const float* d_q_vals, int64_t nq, int k, float threshold,
                             const uint32_t* d_mask_words, int64_t n_bits, int64_t id_base, int64_t id_stride,
@@ -362,13 +387,29 @@ int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, con
  * every document with a score above -inf.  nq = 0 or n_docs = 0: lims all zero, total 0.  Scores: the term-serial chain
  * of sr_sparse_search / sr_sparse_score_pairs - an unfused fp32 multiply then add, in the query's term order, from +0.0f - so a returned
  * score equals sr_sparse_score_pairs of that pair bit for bit.  No global atomic takes part in placing a result: two calls return the
- * same bytes.  Not offered: a range search under a subset or mask, doc-sharded, or on the certified scorer's 16-bit stage
- * (DESIGN.md 4.15).                                                                                                                  */
+ * same bytes.  Under a document bitmap: sr_sparse_range_count_masked / _fill_masked below.  Not offered: a range search under a
+ * per-query mask or a list, doc-sharded, or on the certified scorer's 16-bit stage.                                 */
 int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                           int64_t nq, const float* d_thresholds, int64_t* d_lims, int64_t* total, sr_stream stream);
 int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                          int64_t nq, const float* d_thresholds, const int64_t* d_lims, int64_t id_base, int64_t id_stride,
                          float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream);
+/* The range search under a document bitmap: d_mask_words uint32 [ceil(n_bits / 32)] on the device, bit (i & 31) of word
+ * i >> 5 stands for document position i, n_bits == n_docs (anything else: SR_ERR_INVALID before any device work).  A hit is score >
+ * thr[q] AND the bit of the document position is set; a document without a common term (score +0.0f) under a negative threshold is a
+ * hit exactly when its bit is set.  Everything else is the contract of sr_sparse_range_count / _fill: document order, the score bits
+ * of sr_sparse_score_pairs, the table / chunk rules, the store guard, no global atomics, and the pairing on the handle - a fill needs
+ * a preceding count of the same kind with the same nq, and the count's bitmap.  Bits of the last word at or beyond n_bits are
+ * ignored and the library never reads past word ceil(n_bits / 32) - 1 (the kernels clamp their reads; no copy is kept).  The bitmap is
+ * read in place by both passes: keep it unchanged between the count and its fill.  An 8 192-document tile whose 256 words are all zero
+ * is skipped before a posting is touched.  Not offered: per-query masks, doc-sharded.                                              */
+int sr_sparse_range_count_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                 int64_t nq, const float* d_thresholds, const uint32_t* d_mask_words, int64_t n_bits,
+                                 int64_t* d_lims, int64_t* total, sr_stream stream);
+int sr_sparse_range_fill_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                int64_t nq, const float* d_thresholds, const uint32_t* d_mask_words, int64_t n_bits,
+                                const int64_t* d_lims, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids,
+                                int64_t capacity, sr_stream stream);
 int sr_sparse_index_destroy(sr_sparse_index* idx);
 /* Measurement hook as for the dense index; algorithmic bytes = 8 B per posting of the
  * query terms that falls in the launched doc tiles (computed on the device).       */

@@ -68,6 +68,7 @@ struct sr_dense_index {
     DeviceBuf<uint32_t> range_tab;                                   // [chunks of all segments, range_nq]
     int64_t range_nq = -1, range_total = 0, range_chunk_rows = 0;    // range_nq = -1: no count to fill from
     size_t range_segs = 0; int64_t range_ntotal = 0;                 // stamp of the segment list (segments are only ever added)
+    bool range_masked = false;                                       // the last count ran under a bitmap: its fill must too
 };
 
 // bf16 planes of every segment a score mode needs (the certified filter keeps its own fp16 plane, filter_prepare_segment)

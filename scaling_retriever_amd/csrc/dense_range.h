@@ -23,8 +23,14 @@ struct DenseRangeArgs {
     float* out_scores;
     int64_t* out_ids;
     int64_t capacity;
+    // masked kernels only
+    const uint32_t* mask;     // bitmap over global doc indices: bit (i & 31) of word i >> 5; read at id_base + row * id_stride of the segment's rows only
 };
 // query tile: 256 wide for nq > 128, 128 wide below (as launch_dense_exact picks its pipelined kernels)
 static inline int dense_range_query_tile(int64_t nq) { return nq > 128 ? 256 : 128; }
+// a.mask null: the unrestricted kernels; else their masked twins (a hit needs its document's bit, a 256-row tile without a set bit is skipped)
 int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
 int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
+// the masked instantiations (dense_range_masked.hip); called by the two above, after their checks of the chunking
+int launch_dense_range_count_masked(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
+int launch_dense_range_fill_masked(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);

@@ -19,254 +19,15 @@
 //     advances by the tile's popcount.
 //
 // No global atomics anywhere: the result does not depend on the order workgroups run in, two calls give the same bytes.
-#include "dense_range.h"
+//
+// Under a document bitmap (sr_dense_range_count_masked / _fill_masked; MASKED in dense_range_kernel.h, instantiated by
+// dense_range_masked.hip) a hit also needs the bit of its global index.  At the top of a tile every wave ballots the tile's 256 row
+// bits in four steps (lane l tests rows l, 64 + l, 128 + l, 192 + l; rows past the chunk read as clear): four wave-uniform 64-bit
+// words in scalar registers, the same in every wave, so nothing is added to the vector registers that live across the k-loop and no
+// LDS or barrier is needed.  A tile whose 256 bits are all clear runs no k-loop - no loads, no MFMAs, no barriers; the decision is
+// workgroup-uniform.  In the epilogue a block's 32 bits are ANDed into the hit word.
+#include "dense_range_kernel.h"
 #include "dense_index.h"
-
-template <bool FILL, int WN, typename T>
-__device__ __forceinline__ void dense_range_body(const DenseRangeArgs& a) {
-    typedef typename SrRow<T>::V RowV;
-    constexpr int WAVES_N = 4, WM = 4, BK = 16;
-    constexpr int NT = 512, TM = 256, TN = 32 * WN * WAVES_N, LDK = BK + 4, KC = BK / 4, NSTAGE = 3;
-    constexpr int PER_T = TM * KC / NT;                 // 16-B chunks per thread of the doc tile (= 2)
-    constexpr int PER_TB = TN * KC / NT;                // ... of the query tile (2 or 1)
-    constexpr int HALF_MFMAS = 4 * WM * WN;
-    constexpr int MPO = WN == 2 ? 2 : 1;
-    constexpr int BMP = TM / 32 + 1;                    // bitmap pitch in words: 9 is odd, the 32 query columns of a ds_write_b32 hit 32 banks
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                       // [NSTAGE][TM][LDK]
-    float* Bs = smem + NSTAGE * TM * LDK;   // [NSTAGE][TN][LDK]
-    uint32_t* aux = reinterpret_cast<uint32_t*>(smem + NSTAGE * (TM + TN) * LDK);   // count: [TN] sums; fill: [TN][BMP] hit bitmap
-    int64_t* posl = reinterpret_cast<int64_t*>(aux + TN * BMP);                       // fill: [TN] the running write position of each query
-
-    const int q0 = blockIdx.x * TN;
-    const int chunk = a.chunk_base + (int)blockIdx.y;
-    const int64_t r_begin = (int64_t)blockIdx.y * a.chunk_rows;
-    const int64_t r_end = r_begin + a.chunk_rows < a.seg_rows ? r_begin + a.chunk_rows : a.seg_rows;
-    const int H = a.H;
-    const int nk = H / BK;
-
-    // per-query state of the chunk lives in LDS, not in registers: nothing lane-derived is live across the 256-register k-loop
-    if (threadIdx.x < TN) {
-        const int q = q0 + (int)threadIdx.x;
-        if (FILL) posl[threadIdx.x] = q < a.nq ? a.lims[q] + (int64_t)a.table[(int64_t)chunk * a.nq + q] : 0;
-        else aux[threadIdx.x] = 0;
-    }   // made visible by the first tile's barriers
-
-    for (int64_t row0 = r_begin; row0 < r_end; row0 += TM) {
-        // hipcc would hoist every lane-derived value of a tile's set-up and epilogue out of this loop and spill it through the k-loop
-        // (dense_split_kernel.h): the thread index is made opaque once per tile and once per epilogue, recomputing costs a few VALU
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const int lane = tid & 63, wave = tid >> 6;
-        const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-        const T* asrc[PER_T];
-        const float* bsrc[PER_TB];
-        int soff[PER_T];
-#pragma unroll
-        for (int i = 0; i < PER_T; ++i) {
-            // chunk c -> (row r, k-chunk kc) as in dense_score_pipe_kernel: conflict-free stage writes, 64-byte row pieces
-            const int c = tid + i * NT, kc = c & 3, grp = c >> 3;
-            const int r = (grp >> 2) * 8 + (grp & 3) + 4 * ((c >> 2) & 1);
-            soff[i] = r * LDK + kc * 4;
-            int64_t row = row0 + r;
-            row = row < r_end ? row : r_end - 1;          // rows past the chunk are clamped, their scores never emitted
-            asrc[i] = static_cast<const T*>(a.D) + row * H + kc * 4;
-            if (i < PER_TB) {
-                int q = q0 + r;
-                q = q < a.nq ? q : a.nq - 1;
-                bsrc[i] = a.Q + (int64_t)q * H + kc * 4;
-            }
-        }
-        const int aoff = (wm * WM * 32 + (lane & 31)) * LDK + 4 * (lane >> 5);
-        const int boff = (wn * WN * 32 + (lane & 31)) * LDK + 4 * (lane >> 5);
-        RowV ra[PER_T];
-        f32x4 rb[PER_TB];
-        auto gload = [&](int k0) {
-#pragma unroll
-            for (int i = 0; i < PER_T; ++i) ra[i] = *reinterpret_cast<const RowV*>(asrc[i] + k0);
-#pragma unroll
-            for (int i = 0; i < PER_TB; ++i) rb[i] = *reinterpret_cast<const f32x4*>(bsrc[i] + k0);
-        };
-        auto sstore = [&](int st) {
-#pragma unroll
-            for (int i = 0; i < PER_T; ++i) *reinterpret_cast<f32x4*>(&As[st * TM * LDK + soff[i]]) = SrRow<T>::widen(ra[i]);
-#pragma unroll
-            for (int i = 0; i < PER_TB; ++i) *reinterpret_cast<f32x4*>(&Bs[st * TN * LDK + soff[i]]) = rb[i];
-        };
-        auto frag = [&](int st, int sub, f32x4 (&af)[WM], f32x4 (&bf)[WN]) {
-#pragma unroll
-            for (int m = 0; m < WM; ++m) af[m] = *reinterpret_cast<const f32x4*>(&As[st * TM * LDK + aoff + m * 32 * LDK + 8 * sub]);
-#pragma unroll
-            for (int n = 0; n < WN; ++n) bf[n] = *reinterpret_cast<const f32x4*>(&Bs[st * TN * LDK + boff + n * 32 * LDK + 8 * sub]);
-        };
-
-        f32x16 acc[WM][WN];
-#pragma unroll
-        for (int m = 0; m < WM; ++m)
-#pragma unroll
-            for (int n = 0; n < WN; ++n)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
-#define SR_RANGE_MFMAS(AF, BF)                                                                                   \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                \
-        _Pragma("unroll") for (int m = 0; m < WM; ++m)                                                           \
-            _Pragma("unroll") for (int n = 0; n < WN; ++n)                                                       \
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(AF[m][j], BF[n][j], acc[m][n], 0, 0, 0);
-
-        // The previous tile's k-loop ended on a barrier behind its last stage reads and writes, and its epilogue touches only
-        // `aux`: the stages are free here.
-        {   // prologue: three k-steps' loads in flight before the first stage is written
-            RowV pa[2][PER_T];
-            f32x4 pb[2][PER_TB];
-#pragma unroll
-            for (int st0 = 0; st0 < 2; ++st0) {
-                const int k0 = (st0 < nk ? st0 : 0) * BK;
-#pragma unroll
-                for (int i = 0; i < PER_T; ++i) pa[st0][i] = *reinterpret_cast<const RowV*>(asrc[i] + k0);
-#pragma unroll
-                for (int i = 0; i < PER_TB; ++i) pb[st0][i] = *reinterpret_cast<const f32x4*>(bsrc[i] + k0);
-            }
-            gload(nk > 2 ? 2 * BK : 0);
-#pragma unroll
-            for (int st0 = 0; st0 < 2; ++st0) {
-#pragma unroll
-                for (int i = 0; i < PER_T; ++i) *reinterpret_cast<f32x4*>(&As[st0 * TM * LDK + soff[i]]) = SrRow<T>::widen(pa[st0][i]);
-#pragma unroll
-                for (int i = 0; i < PER_TB; ++i) *reinterpret_cast<f32x4*>(&Bs[st0 * TN * LDK + soff[i]]) = pb[st0][i];
-            }
-        }
-        __syncthreads();
-        f32x4 a0[WM], b0[WN], a1[WM], b1[WN];
-        frag(0, 0, a0, b0);
-        int st = 0;
-        for (int kt = 0; kt < nk; ++kt) {     // the k-step of dense_score_pipe_kernel, issue order included
-            const int st1 = st == NSTAGE - 1 ? 0 : st + 1;
-            const int st2 = st1 == NSTAGE - 1 ? 0 : st1 + 1;
-            frag(st, 1, a1, b1);
-            sstore(st2);
-            gload(kt + 3 < nk ? (kt + 3) * BK : H - BK);
-            SR_RANGE_MFMAS(a0, b0)
-#pragma unroll
-            for (int i = 0; i < WM + WN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, MPO, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < PER_T + PER_TB; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, MPO, 0);
-                __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < PER_T + PER_TB; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, MPO, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, HALF_MFMAS - MPO * (WM + WN + 2 * (PER_T + PER_TB)), 0);
-            __builtin_amdgcn_sched_barrier(0);
-            frag(st1, 0, a0, b0);
-            SR_RANGE_MFMAS(a1, b1)
-#pragma unroll
-            for (int i = 0; i < WM + WN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, MPO, 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, HALF_MFMAS - MPO * (WM + WN), 1);
-            __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
-            st = st1;
-        }
-#undef SR_RANGE_MFMAS
-
-        // ---- epilogue.  Register r of block m is local row lr0 + 32 m + (r & 3) + 8 (r >> 2); the lane halves are 4 rows apart ----
-        int tid_e = threadIdx.x;
-        asm volatile("" : "+v"(tid_e));
-        const int lane_e = tid_e & 63, half = lane_e >> 5;
-        const int em = (tid_e >> 6) / WAVES_N, en = (tid_e >> 6) % WAVES_N;
-        const int64_t left = r_end - row0;
-        const int rows_valid = left < TM ? (int)left : TM;
-        const int lr0 = em * WM * 32 + 4 * half;
-        uint32_t word[WN][WM];
-#pragma unroll
-        for (int n = 0; n < WN; ++n) {
-            const int qcol = en * WN * 32 + n * 32 + (lane_e & 31);
-            const int q = q0 + qcol;
-            const float thr = q < a.nq ? a.thr[q] : __builtin_inff();      // a column past nq: never a hit
-            int cnt = 0;
-#pragma unroll
-            for (int m = 0; m < WM; ++m) {
-                uint32_t w = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int lr = lr0 + m * 32 + (r & 3) + 8 * (r >> 2);
-                    const bool hit = lr < rows_valid && acc[m][n][r] > thr;      // strict; false for a NaN on either side
-                    if (FILL) w |= (hit ? 1u : 0u) << ((r & 3) + 8 * (r >> 2));
-                    else cnt += hit ? 1 : 0;
-                }
-                if (FILL) {
-                    w <<= 4 * half;
-                    w |= (uint32_t)__shfl_xor((int)w, 32);          // both halves now hold the block's 32 rows
-                    word[n][m] = w;
-                    if (half == 0) aux[qcol * BMP + em * WM + m] = w;
-                }
-            }
-            if (!FILL && cnt) atomicAdd(&aux[qcol], (uint32_t)cnt);     // LDS add: the 4 lanes that share the query
-        }
-        if (FILL) {
-            __syncthreads();
-#pragma unroll
-            for (int n = 0; n < WN; ++n) {
-                const int qcol = en * WN * 32 + n * 32 + (lane_e & 31);
-                int below = 0, total = 0;                          // hits of the query in the tile, and in the blocks below this wave's
-#pragma unroll
-                for (int b = 0; b < TM / 32; ++b) {
-                    const int c = __popc(aux[qcol * BMP + b]);
-                    total += c;
-                    below += b < em * WM ? c : 0;
-                }
-                if (total == 0) continue;
-                const int q = q0 + qcol;                           // has hits: q < nq
-                int64_t p0 = posl[qcol] + below;
-                int64_t p_end = a.lims[q + 1];
-                p_end = p_end < a.capacity ? p_end : a.capacity;
-#pragma unroll
-                for (int m = 0; m < WM; ++m) {
-                    const uint32_t w = word[n][m];
-                    if (w & (0x0f0f0f0fu << (4 * half))) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int bit = (r & 3) + 8 * (r >> 2) + 4 * half;
-                            if ((w >> bit) & 1u) {
-                                const int64_t p = p0 + __popc(w & ((1u << bit) - 1u));
-                                if (p >= 0 && p < p_end) {         // never outside the query's segment, whatever the count saw
-                                    a.out_scores[p] = acc[m][n][r];
-                                    a.out_ids[p] = a.id_base + (row0 + em * WM * 32 + m * 32 + bit) * a.id_stride;
-                                }
-                            }
-                        }
-                    }
-                    p0 += __popc(w);
-                }
-            }
-            __syncthreads();                                       // every reader of the positions is through
-            if (tid_e < TN) {
-                int total = 0;
-#pragma unroll
-                for (int b = 0; b < TM / 32; ++b) total += __popc(aux[tid_e * BMP + b]);
-                posl[tid_e] += total;
-            }   // bitmap and positions are next touched behind the next tile's k-loop barriers
-        }
-    }
-
-    if (!FILL) {
-        __syncthreads();
-        if (threadIdx.x < TN && q0 + (int)threadIdx.x < a.nq) a.table[(int64_t)chunk * a.nq + q0 + threadIdx.x] = aux[threadIdx.x];
-    }
-}
-
-template <int WN, typename T>
-__global__ __launch_bounds__(512, 2) void dense_range_count_kernel(DenseRangeArgs a) { dense_range_body<false, WN, T>(a); }
-template <int WN, typename T>
-__global__ __launch_bounds__(512, 2) void dense_range_fill_kernel(DenseRangeArgs a) { dense_range_body<true, WN, T>(a); }
 
 // table[c][q]: counts -> exclusive prefixes over the chunks; lims[q + 1] := hits of query q (summed up by dense_range_lims_kernel)
 __global__ __launch_bounds__(256) void dense_range_scan_kernel(uint32_t* table, int n_chunks, int64_t nq, int64_t* lims) {
@@ -305,25 +66,6 @@ __global__ __launch_bounds__(1024) void dense_range_lims_kernel(int64_t* lims, i
     }
 }
 
-template <bool FILL, int WN, typename T>
-static int launch_dense_range_t(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) {
-    constexpr int TN = 128 * WN;
-    constexpr size_t lds = sizeof(float) * 3 * (256 + TN) * (16 + 4) + (FILL ? (4 * (256 / 32 + 1) + 8) * (size_t)TN : 4 * (size_t)TN);
-    static_assert(lds <= 160 * 1024, "one workgroup per CU");
-    const void* fn = FILL ? reinterpret_cast<const void*>(&dense_range_fill_kernel<WN, T>)
-                          : reinterpret_cast<const void*>(&dense_range_count_kernel<WN, T>);
-    static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
-    dim3 grid((unsigned)ceil_div64(a.nq, TN), (unsigned)n_chunks_seg);
-    if (FILL) hipLaunchKernelGGL((dense_range_fill_kernel<WN, T>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((dense_range_count_kernel<WN, T>), grid, dim3(512), lds, s, a);
-    SR_CHECK_LAUNCH();
-    return SR_OK;
-}
 template <bool FILL>
 static int launch_dense_range(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) {
     if (a.nq < 1 || n_chunks_seg < 1 || a.seg_rows < 1 || a.chunk_rows < 256 || a.chunk_rows % 256 != 0 ||
@@ -331,10 +73,8 @@ static int launch_dense_range(const DenseRangeArgs& a, int n_chunks_seg, hipStre
         sr_set_error("dense range launch: bad chunking (%lld rows, chunks of %lld, %d chunks)", (long long)a.seg_rows, (long long)a.chunk_rows, n_chunks_seg);
         return SR_ERR_INVALID;
     }
-    const bool wide = dense_range_query_tile(a.nq) == 256;
-    if (a.dtype == SR_DTYPE_F16)
-        return wide ? launch_dense_range_t<FILL, 2, _Float16>(a, n_chunks_seg, s) : launch_dense_range_t<FILL, 1, _Float16>(a, n_chunks_seg, s);
-    return wide ? launch_dense_range_t<FILL, 2, float>(a, n_chunks_seg, s) : launch_dense_range_t<FILL, 1, float>(a, n_chunks_seg, s);
+    if (a.mask) return FILL ? launch_dense_range_fill_masked(a, n_chunks_seg, s) : launch_dense_range_count_masked(a, n_chunks_seg, s);      // dense_range_masked.hip
+    return launch_dense_range_m<FILL, false>(a, n_chunks_seg, s);
 }
 int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) { return launch_dense_range<false>(a, n_chunks_seg, s); }
 int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) { return launch_dense_range<true>(a, n_chunks_seg, s); }
@@ -366,23 +106,24 @@ static int64_t dense_range_chunking(const sr_dense_index* idx, int64_t max_chunk
 }
 
 static void dense_range_args(const sr_dense_index* idx, const DenseSegment& seg, const float* d_queries, int64_t nq, const float* d_thr,
-                             int chunk_base, DenseRangeArgs& a) {
+                             const uint32_t* d_mask, int chunk_base, DenseRangeArgs& a) {
     a = DenseRangeArgs{};
     a.D = seg.rows; a.Q = d_queries; a.thr = d_thr; a.seg_rows = seg.n; a.chunk_rows = idx->range_chunk_rows; a.chunk_base = chunk_base;
     a.H = idx->dim; a.nq = (int)nq; a.dtype = idx->row_dtype; a.id_base = seg.id_base; a.id_stride = seg.id_stride;
-    a.table = idx->range_tab.p;
+    a.table = idx->range_tab.p; a.mask = d_mask;
 }
 
-extern "C" int sr_dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, int64_t* d_lims,
-                                    int64_t* total, sr_stream stream) {
+// d_mask null: the unrestricted search.  The caller holds idx->mu.
+static int dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                             const uint32_t* d_mask, int64_t* d_lims, int64_t* total, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_range_count: null index");
     SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_range_count: bad nq=%lld", (long long)nq);
     SR_REQUIRE(d_lims && total, "sr_dense_range_count: null d_lims or total");
     SR_REQUIRE(nq == 0 || (d_queries && d_thresholds), "sr_dense_range_count: null queries or thresholds");
     SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_range_count: queries must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(idx->mu);
     idx->range_nq = -1;
+    idx->range_masked = d_mask != nullptr;
     *total = 0;
     if (nq == 0 || idx->ntotal == 0) {
         SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
@@ -428,7 +169,7 @@ extern "C" int sr_dense_range_count(sr_dense_index* idx, const float* d_queries,
     for (const DenseSegment& seg : idx->segs) {
         const int n_seg = (int)ceil_div64(seg.n, chunk_rows);
         DenseRangeArgs a;
-        dense_range_args(idx, seg, d_queries, nq, d_thresholds, chunk_base, a);
+        dense_range_args(idx, seg, d_queries, nq, d_thresholds, d_mask, chunk_base, a);
         idx->prof.begin(s);
         SR_TRY(launch_dense_range_count(a, n_seg, s));
         idx->prof.end(s, 2.0 * (double)nq * (double)seg.n * idx->dim, (double)seg.n * idx->dim * (double)sr_dtype_size(idx->row_dtype));
@@ -444,13 +185,31 @@ extern "C" int sr_dense_range_count(sr_dense_index* idx, const float* d_queries,
     return SR_OK;
 }
 
-extern "C" int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, const int64_t* d_lims,
-                                   float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+extern "C" int sr_dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, int64_t* d_lims,
+                                    int64_t* total, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_count: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    return dense_range_count(idx, d_queries, nq, d_thresholds, nullptr, d_lims, total, stream);
+}
+
+extern "C" int sr_dense_range_count_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                           const uint32_t* d_mask_words, int64_t n_bits, int64_t* d_lims, int64_t* total, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_count_masked: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SR_REQUIRE(n_bits == dense_id_end(idx), "sr_dense_range_count_masked: n_bits=%lld, the index numbers its documents in [0, %lld)",
+               (long long)n_bits, (long long)dense_id_end(idx));
+    SR_REQUIRE(d_mask_words, "sr_dense_range_count_masked: null mask");
+    return dense_range_count(idx, d_queries, nq, d_thresholds, d_mask_words, d_lims, total, stream);
+}
+
+// d_mask: what the preceding count was given (null: none).  The caller holds idx->mu.
+static int dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, const uint32_t* d_mask,
+                            const int64_t* d_lims, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_range_fill: null index");
     SR_REQUIRE(nq >= 0 && nq < (1ll << 30) && capacity >= 0, "sr_dense_range_fill: bad nq=%lld or capacity=%lld", (long long)nq, (long long)capacity);
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(idx->mu);
     SR_REQUIRE(idx->range_nq >= 0, "sr_dense_range_fill: no sr_dense_range_count precedes it on this handle");
+    SR_REQUIRE(idx->range_masked == (d_mask != nullptr), "sr_dense_range_fill: the preceding count ran %s a mask", idx->range_masked ? "under" : "without");
     SR_REQUIRE(idx->range_nq == nq, "sr_dense_range_fill: nq=%lld, the preceding count had %lld", (long long)nq, (long long)idx->range_nq);
     SR_REQUIRE(idx->range_segs == idx->segs.size() && idx->range_ntotal == idx->ntotal, "sr_dense_range_fill: the index changed since the count");
     SR_REQUIRE(capacity >= idx->range_total, "sr_dense_range_fill: capacity=%lld is below the count's total of %lld", (long long)capacity,
@@ -463,7 +222,7 @@ extern "C" int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, 
     for (const DenseSegment& seg : idx->segs) {
         const int n_seg = (int)ceil_div64(seg.n, idx->range_chunk_rows);
         DenseRangeArgs a;
-        dense_range_args(idx, seg, d_queries, nq, d_thresholds, chunk_base, a);
+        dense_range_args(idx, seg, d_queries, nq, d_thresholds, d_mask, chunk_base, a);
         a.lims = d_lims; a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.capacity = capacity;
         idx->prof.begin(s);
         SR_TRY(launch_dense_range_fill(a, n_seg, s));
@@ -471,4 +230,22 @@ extern "C" int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, 
         chunk_base += n_seg;
     }
     return SR_OK;
+}
+
+extern "C" int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, const int64_t* d_lims,
+                                   float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_fill: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    return dense_range_fill(idx, d_queries, nq, d_thresholds, nullptr, d_lims, d_out_scores, d_out_ids, capacity, stream);
+}
+
+extern "C" int sr_dense_range_fill_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                          const uint32_t* d_mask_words, int64_t n_bits, const int64_t* d_lims, float* d_out_scores,
+                                          int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_fill_masked: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SR_REQUIRE(n_bits == dense_id_end(idx), "sr_dense_range_fill_masked: n_bits=%lld, the index numbers its documents in [0, %lld)",
+               (long long)n_bits, (long long)dense_id_end(idx));
+    SR_REQUIRE(d_mask_words, "sr_dense_range_fill_masked: null mask");
+    return dense_range_fill(idx, d_queries, nq, d_thresholds, d_mask_words, d_lims, d_out_scores, d_out_ids, capacity, stream);
 }

@@ -159,3 +159,32 @@ extern "C" int sr_doc_list_from_mask(const uint32_t* d_words, int64_t n_bits, in
     }
     return rc;
 }
+
+// one thread per destination word: bit i of dst = bit map[i] of src where map[i] names a source bit, else 0
+__global__ __launch_bounds__(DM_THREADS) void doc_mask_remap_kernel(const uint32_t* __restrict__ src, int64_t n_src_bits,
+                                                                     const int64_t* __restrict__ map, int64_t n_dst_bits,
+                                                                     uint32_t* __restrict__ dst) {
+    const int64_t w = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    if (w >= (n_dst_bits + 31) >> 5) return;
+    uint32_t v = 0;
+#pragma unroll 8
+    for (int b = 0; b < 32; ++b) {
+        const int64_t i = w * 32 + b;
+        if (i >= n_dst_bits) break;
+        const int64_t j = map[i];
+        if (j >= 0 && j < n_src_bits) v |= ((src[j >> 5] >> (unsigned)(j & 31)) & 1u) << b;
+    }
+    dst[w] = v;
+}
+
+extern "C" int sr_doc_mask_remap(const uint32_t* d_src_words, int64_t n_src_bits, const int64_t* d_map, int64_t n_dst_bits,
+                                 uint32_t* d_dst_words, sr_stream stream) {
+    SR_REQUIRE(n_src_bits >= 0 && n_src_bits <= (1ll << 32) && n_dst_bits >= 0 && n_dst_bits <= (1ll << 32),
+               "sr_doc_mask_remap: bad sizes n_src_bits=%lld n_dst_bits=%lld", (long long)n_src_bits, (long long)n_dst_bits);
+    SR_REQUIRE((d_src_words || n_src_bits == 0) && ((d_map && d_dst_words) || n_dst_bits == 0), "sr_doc_mask_remap: null pointer");
+    if (n_dst_bits == 0) return SR_OK;
+    hipLaunchKernelGGL(doc_mask_remap_kernel, dim3((unsigned)ceil_div64(doc_mask_words(n_dst_bits), DM_THREADS)), dim3(DM_THREADS), 0,
+                       (hipStream_t)stream, d_src_words, n_src_bits, d_map, n_dst_bits, d_dst_words);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}

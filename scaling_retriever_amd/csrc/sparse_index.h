@@ -65,6 +65,7 @@ struct sr_sparse_index {
     DeviceBuf<int32_t> range_tab;                                     // [range_chunks, range_nq]
     int64_t range_nq = -1, range_total = 0;                           // range_nq = -1: no count to fill from
     int range_chunk_tiles = 0, range_chunks = 0;
+    bool range_masked = false;                                       // the last count ran under a bitmap: its fill must too
     std::mutex mu;
 };
 

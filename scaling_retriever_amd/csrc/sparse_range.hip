@@ -15,6 +15,12 @@
 //     to lims[q] + prefix[chunk][q] + hits of the chunk's earlier tiles + hits of the tile's lower waves + its rank in the wave.
 //
 // No global atomics anywhere: the result does not depend on the order workgroups run in, two calls give the same bytes.
+//
+// Under a document bitmap (sr_sparse_range_count_masked / _fill_masked, MASKED below) a hit also needs the bit of its position.  Per
+// tile every wave loads the tile's 256 mask words, four per lane (reads beyond the bitmap's last word are clamped to 0, the last word's
+// bits at or beyond n_docs cleared): all clear - the same answer in every wave, no barrier - and the tile is skipped before a posting is
+// touched.  Otherwise lane l keeps word l of its wave's quarter, and the two words of a 64-document step come back with v_readlane and
+// are ANDed into the step's hit ballot (sparse_range_step_hits: the one predicate of the count and of the fill).
 #include "sparse_index.h"
 #include "range_scan.h"
 
@@ -51,6 +57,8 @@ struct SparseRangeArgs {
     float* out_scores;
     int64_t* out_ids;
     int64_t capacity;
+    // masked kernels only
+    const uint32_t* mask;     // bitmap over document positions: ceil(n_docs / 32) words, nothing beyond them is read
 };
 
 __device__ inline int64_t srr_readlane64(int64_t v, int j) {
@@ -170,19 +178,45 @@ __device__ __forceinline__ void sparse_range_accumulate(const SparseRangeArgs& a
     }
 }
 
+// The hits of step st of a wave's quarter (64 documents, lane l holds document d with score s) as a lane mask; *mine = this lane's bit.
+// Under a mask, mw is word l of the quarter's 64 mask words: the step's documents are the bits of words 2 st and 2 st + 1.
+template <bool MASKED>
+__device__ __forceinline__ uint64_t sparse_range_step_hits(float s, int d, int n_here, float thr, uint32_t mw, int st, int lane, bool* mine) {
+    bool hit = d < n_here && s > thr;                       // strict; false for a NaN on either side
+    uint64_t m = __ballot(hit);
+    if constexpr (MASKED) {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)mw, 2 * st), hi = (uint32_t)__builtin_amdgcn_readlane((int)mw, 2 * st + 1);
+        m &= ((uint64_t)hi << 32) | lo;
+        hit = (m >> lane) & 1ull;
+    }
+    *mine = hit;
+    return m;
+}
+
 // hits of this wave's quarter of the tile: lanes read consecutive LDS words, 64 documents per step
-__device__ __forceinline__ int sparse_range_wave_hits(const float* sc, int wave, int lane, int n_here, float thr) {
+template <bool MASKED>
+__device__ __forceinline__ int sparse_range_wave_hits(const float* sc, int wave, int lane, int n_here, float thr, uint32_t mw) {
     int cnt = 0;
 #pragma unroll 4
     for (int st = 0; st < SRR_QUARTER / 64; ++st) {
         const int d = wave * SRR_QUARTER + st * 64 + lane;
-        const bool hit = d < n_here && sc[d] > thr;          // strict; false for a NaN on either side
-        cnt += __popcll(__ballot(hit));
+        bool hit;
+        cnt += __popcll(sparse_range_step_hits<MASKED>(sc[d], d, n_here, thr, mw, st, lane, &hit));
     }
     return cnt;
 }
 
-template <bool FILL>
+// word wi of the bitmap over n_docs documents: 0 beyond the last word, the last word's bits at or beyond n_docs cleared
+__device__ __forceinline__ uint32_t sparse_range_mask_word(const uint32_t* __restrict__ words, int64_t wi, int64_t n_docs) {
+    const int64_t n_words = (n_docs + 31) >> 5;
+    if (wi >= n_words) return 0u;
+    uint32_t v = words[wi];
+    const unsigned tail = (unsigned)(n_docs & 31);
+    if (wi == n_words - 1 && tail != 0) v &= (1u << tail) - 1u;
+    return v;
+}
+
+template <bool FILL, bool MASKED>
 __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
     __shared__ float sc[SRR_TILE + 64];         // + one dummy slot per lane for the postings beyond a run's end
     __shared__ int wave_tot[4];
@@ -204,8 +238,19 @@ __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
     for (int tile = tile_first; tile < tile_end; ++tile) {
         const int64_t doc0 = (int64_t)tile * SRR_TILE;
         const int n_here = (int)((a.n_docs - doc0) < SRR_TILE ? (a.n_docs - doc0) : SRR_TILE);
+        uint32_t mw = 0;                 // MASKED: word `lane` of this wave's quarter of the tile's mask words
+        if constexpr (MASKED) {
+            uint32_t any = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t v = sparse_range_mask_word(a.mask, (int64_t)tile * (SRR_TILE / 32) + j * 64 + lane, a.n_docs);
+                any |= v;
+                mw = j == wave ? v : mw;
+            }
+            if (__ballot(any != 0) == 0) continue;      // no allowed document in the tile (every wave read the same 256 words): it contributes 0
+        }
         sparse_range_accumulate(a, sc, q, tile, tid);
-        const int mine = sparse_range_wave_hits(sc, wave, lane, n_here, thr);
+        const int mine = sparse_range_wave_hits<MASKED>(sc, wave, lane, n_here, thr, mw);
         if (!FILL) {
             wave_cnt += mine;
         } else {
@@ -223,8 +268,8 @@ __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
                 for (int st = 0; st < SRR_QUARTER / 64; ++st) {
                     const int d = wave * SRR_QUARTER + st * 64 + lane;
                     const float s = sc[d];
-                    const bool hit = d < n_here && s > thr;
-                    const uint64_t m = __ballot(hit);
+                    bool hit;
+                    const uint64_t m = sparse_range_step_hits<MASKED>(s, d, n_here, thr, mw, st, lane, &hit);
                     if (m == 0) continue;
                     const int64_t p = p0 + __popcll(m & ((1ull << lane) - 1ull));      // consecutive positions: the stores coalesce
                     if (hit && p >= 0 && p < p_end) {          // never outside the query's segment, whatever the count saw
@@ -245,37 +290,39 @@ __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void sparse_range_count_kernel(SparseRangeArgs a) { sparse_range_body<false>(a); }
+template <bool MASKED>
+__global__ __launch_bounds__(256) void sparse_range_count_kernel(SparseRangeArgs a) { sparse_range_body<false, MASKED>(a); }
 
 // The chunk's cell first: table holds exclusive prefixes, so the cell's own count is the next chunk's prefix minus its own (the query's
 // total minus its own for the last chunk).  0: the workgroup returns before it touches a posting.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void sparse_range_fill_kernel(SparseRangeArgs a, int n_chunks) {
     const int64_t q = blockIdx.x;
     const int chunk = a.chunk_begin + (int)blockIdx.y;
     const int64_t mine = (int64_t)(uint32_t)a.table[(int64_t)chunk * a.nq + q];
     const int64_t next = chunk + 1 < n_chunks ? (int64_t)(uint32_t)a.table[(int64_t)(chunk + 1) * a.nq + q] : a.lims[q + 1] - a.lims[q];
     if (next == mine) return;            // block-uniform
-    sparse_range_body<true>(a);
+    sparse_range_body<true, MASKED>(a);
 }
 
 static void sparse_range_args(const sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
-                              int64_t nq, const float* d_thr, SparseRangeArgs& a) {
+                              int64_t nq, const float* d_thr, const uint32_t* d_mask, SparseRangeArgs& a) {
     a = SparseRangeArgs{};
     a.indptr = idx->indptr; a.doc_ids = idx->doc_ids; a.vals = idx->vals; a.skip = idx->skip.p;
     a.n_tiles = idx->n_tiles; a.n_docs = idx->n_docs; a.n_terms = idx->n_terms;
     a.q_indptr = d_q_indptr; a.q_cols = d_q_cols; a.q_vals = d_q_vals; a.thr = d_thr; a.nq = nq;
-    a.chunk_tiles = idx->range_chunk_tiles; a.table = idx->range_tab.p;
+    a.chunk_tiles = idx->range_chunk_tiles; a.table = idx->range_tab.p; a.mask = d_mask;
 }
 
-extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
-                                     int64_t nq, const float* d_thresholds, int64_t* d_lims, int64_t* total, sr_stream stream) {
-    SR_REQUIRE(idx, "sr_sparse_range_count: null index");
+// d_mask null: the unrestricted search.  The caller holds idx->mu.
+static int sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
+                              const float* d_thresholds, const uint32_t* d_mask, int64_t* d_lims, int64_t* total, sr_stream stream) {
     SR_REQUIRE(nq >= 0 && nq < SRR_MAX_NQ, "sr_sparse_range_count: bad nq=%lld (0 <= nq < 2^24: one workgroup per query and chunk in one launch)", (long long)nq);
     SR_REQUIRE(d_lims && total, "sr_sparse_range_count: null d_lims or total");
     SR_REQUIRE(nq == 0 || (d_q_indptr && d_q_cols && d_q_vals && d_thresholds), "sr_sparse_range_count: null queries or thresholds");
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(idx->mu);
     idx->range_nq = -1;
+    idx->range_masked = d_mask != nullptr;
     if (nq == 0 || idx->n_docs == 0) {
         SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
         SR_CHECK_HIP(hipStreamSynchronize(s));
@@ -310,11 +357,12 @@ extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_in
     StreamOrder::Scope in_order(idx->order, s);
     idx->range_chunk_tiles = (int)chunk_tiles;
     SparseRangeArgs a;
-    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, a);
+    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask, a);
     for (int c0 = 0; c0 < n_chunks; c0 += SRR_MAX_GRID_Y) {
         const int nc = n_chunks - c0 < SRR_MAX_GRID_Y ? n_chunks - c0 : SRR_MAX_GRID_Y;
         a.chunk_begin = c0;
-        hipLaunchKernelGGL(sparse_range_count_kernel, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
+        if (d_mask) hipLaunchKernelGGL(sparse_range_count_kernel<true>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(sparse_range_count_kernel<false>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
         SR_CHECK_LAUNCH();
     }
     SR_TRY(launch_range_scan(reinterpret_cast<uint32_t*>(idx->range_tab.p), n_chunks, nq, d_lims, s));
@@ -326,16 +374,34 @@ extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_in
     return SR_OK;
 }
 
-extern "C" int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
-                                    int64_t nq, const float* d_thresholds, const int64_t* d_lims, int64_t id_base, int64_t id_stride,
-                                    float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
-    SR_REQUIRE(idx, "sr_sparse_range_fill: null index");
+extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                     int64_t nq, const float* d_thresholds, int64_t* d_lims, int64_t* total, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_range_count: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    return sparse_range_count(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, nullptr, d_lims, total, stream);
+}
+
+extern "C" int sr_sparse_range_count_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                            int64_t nq, const float* d_thresholds, const uint32_t* d_mask_words, int64_t n_bits,
+                                            int64_t* d_lims, int64_t* total, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_range_count_masked: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_range_count_masked: n_bits=%lld, the index holds %lld documents", (long long)n_bits,
+               (long long)idx->n_docs);
+    SR_REQUIRE(d_mask_words, "sr_sparse_range_count_masked: null mask");
+    return sparse_range_count(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask_words, d_lims, total, stream);
+}
+
+// d_mask: what the preceding count was given (null: none).  The caller holds idx->mu.
+static int sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
+                             const float* d_thresholds, const uint32_t* d_mask, const int64_t* d_lims, int64_t id_base, int64_t id_stride,
+                             float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(nq >= 0 && nq < SRR_MAX_NQ && capacity >= 0, "sr_sparse_range_fill: bad nq=%lld (0 <= nq < 2^24) or capacity=%lld", (long long)nq, (long long)capacity);
     SR_REQUIRE(id_base >= 0 && id_stride >= 1, "sr_sparse_range_fill: need id_base >= 0 and id_stride >= 1, got %lld and %lld", (long long)id_base,
                (long long)id_stride);
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(idx->mu);
     SR_REQUIRE(idx->range_nq >= 0, "sr_sparse_range_fill: no sr_sparse_range_count precedes it on this handle");
+    SR_REQUIRE(idx->range_masked == (d_mask != nullptr), "sr_sparse_range_fill: the preceding count ran %s a mask", idx->range_masked ? "under" : "without");
     SR_REQUIRE(idx->range_nq == nq, "sr_sparse_range_fill: nq=%lld, the preceding count had %lld", (long long)nq, (long long)idx->range_nq);
     SR_REQUIRE(capacity >= idx->range_total, "sr_sparse_range_fill: capacity=%lld is below the count's total of %lld", (long long)capacity,
                (long long)idx->range_total);
@@ -343,14 +409,37 @@ extern "C" int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_ind
     SR_REQUIRE(d_q_indptr && d_q_cols && d_q_vals && d_thresholds && d_lims && d_out_scores && d_out_ids, "sr_sparse_range_fill: null pointer");
     StreamOrder::Scope in_order(idx->order, s);
     SparseRangeArgs a;
-    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, a);
+    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask, a);
     a.lims = d_lims; a.id_base = id_base; a.id_stride = id_stride; a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.capacity = capacity;
     const int n_chunks = idx->range_chunks;
     for (int c0 = 0; c0 < n_chunks; c0 += SRR_MAX_GRID_Y) {
         const int nc = n_chunks - c0 < SRR_MAX_GRID_Y ? n_chunks - c0 : SRR_MAX_GRID_Y;
         a.chunk_begin = c0;
-        hipLaunchKernelGGL(sparse_range_fill_kernel, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a, n_chunks);
+        if (d_mask) hipLaunchKernelGGL(sparse_range_fill_kernel<true>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a, n_chunks);
+        else hipLaunchKernelGGL(sparse_range_fill_kernel<false>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a, n_chunks);
         SR_CHECK_LAUNCH();
     }
     return SR_OK;
+}
+
+extern "C" int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                    int64_t nq, const float* d_thresholds, const int64_t* d_lims, int64_t id_base, int64_t id_stride,
+                                    float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_range_fill: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, nullptr, d_lims, id_base, id_stride, d_out_scores,
+                             d_out_ids, capacity, stream);
+}
+
+extern "C" int sr_sparse_range_fill_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                           int64_t nq, const float* d_thresholds, const uint32_t* d_mask_words, int64_t n_bits,
+                                           const int64_t* d_lims, int64_t id_base, int64_t id_stride, float* d_out_scores,
+                                           int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_range_fill_masked: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_range_fill_masked: n_bits=%lld, the index holds %lld documents", (long long)n_bits,
+               (long long)idx->n_docs);
+    SR_REQUIRE(d_mask_words, "sr_sparse_range_fill_masked: null mask");
+    return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask_words, d_lims, id_base, id_stride, d_out_scores,
+                             d_out_ids, capacity, stream);
 }

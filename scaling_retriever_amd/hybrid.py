@@ -16,8 +16,13 @@ that top-k exactly, for every query, by three routes (the argument is in DESIGN.
                  reach F_k next to the sparse bound S, returns every outside document that could enter; those and the sparse list are
                  re-scored and ranked.  Always terminates; runs in query sub-batches under a byte budget.
 
-All arithmetic is in the HIP kernels; the host only moves rows between rounds.  Not offered: doc-sharded indexes, allow-lists / masks,
-k > sr_max_topk()."""
+Under a document bitmap (mask=, one for all queries) the same three routes run over the allowed documents alone: both heads search
+under the mask (the sparse head under the bitmap carried over to its own positions, sr_doc_mask_remap), the range route is the masked
+dense range search, and a dense list that holds every allowed document (depth >= their number m) is complete.  The argument holds for
+the allowed set word for word: every allowed document outside both lists has dense <= D and sparse <= S.
+
+All arithmetic is in the HIP kernels; the host only moves rows between rounds.  Not offered: doc-sharded indexes, per-query masks,
+allow-lists given as ids (build the bitmap: HybridRetriever.allowed_mask), k > sr_max_topk()."""
 import contextlib
 
 import numpy as np
@@ -106,12 +111,15 @@ def _rescore_and_rank(dense, sparse, q, csr, indptr, dpos, spos, tie, w, k, D, S
 
 
 def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_vals, topk, weights=(1.0, 1.0), depths=None,
-                 fallback_bytes=1 << 30):
+                 fallback_bytes=1 << 30, mask=None):
     """dense: DenseIndexHIP in precision "fp32" or "fp32_filtered" (ValueError otherwise: the k'-th dense score must be comparable with
     pair scores); sparse: SparseIndexHIP; d2s int64 [dense.id_end] / s2d int64 the two position maps on the device (-1: none); queries
     fp32 [nq, dim] and a CSR over the vocabulary, on the device.  depths (default 4k, 16k, ... <= sr_max_topk()): the search depths of
     the rounds, each in [topk, sr_max_topk()]; fallback_bytes: the device bytes a sub-batch of the range route may hold (a single query
-    whose candidates alone exceed it: MemoryError naming it).  Returns (scores fp32 [nq, k] padded with -FLT_MAX, dense positions int64
+    whose candidates alone exceed it: MemoryError naming it).  mask (None: every document): packed int32 / uint32 words over dense
+    positions [0, dense.id_end) (scoring.pack_doc_mask), one bitmap for all queries - only documents whose bit is set are ranked; a set
+    bit that names no document is a ValueError (DenseIndexHIP.search); with fewer than k allowed documents a row ends in padding and its
+    count says so.  Returns (scores fp32 [nq, k] padded with -FLT_MAX, dense positions int64
     [nq, k] padded with -1, counts int32 [nq]) as numpy arrays and stats = {"depth": int64 [nq] the index into depths at which the
     query was certified, -1 = range route; "union": int64 [nq] candidates ranked for it; "range_hits": int64 [nq]; "depths": the
     schedule} - the exact top-k of the fused score for every query, whatever route served it."""
@@ -123,8 +131,12 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
     if k > max_topk:
         raise ValueError(f"search_fused: topk = {k} is beyond sr_max_topk() = {max_topk}")
     depths = default_depths(k, max_topk) if depths is None else _check_depths(depths, k, max_topk)
-    from .scoring import hybrid_union
+    from .scoring import _mask_words, doc_list_from_mask, doc_mask_remap, hybrid_union
     dev = dense.device
+    if mask is not None:
+        mask = _mask_words(mask, dev)
+        if mask.numel() != (dense.id_end + 31) // 32:
+            raise ValueError(f"a packed mask of this index holds {(dense.id_end + 31) // 32} words (id_end = {dense.id_end}), got {mask.numel()}")
     q = dense_queries.to(device=dev, dtype=torch.float32).contiguous()
     row_ptr, cols, vals = (q_row_ptr.to(device=dev, dtype=torch.int64), q_cols.to(device=dev, dtype=torch.int32),
                            q_vals.to(device=dev, dtype=torch.float32))
@@ -145,6 +157,14 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
     if nq == 0 or N == 0:
         stats["depth"][:] = 0
         return result()
+    n_allowed, sparse_mask = N, None
+    if mask is not None:
+        n_allowed = doc_list_from_mask(mask, dense.id_end, capacity=0)[1]      # m: counted once per call
+        if n_allowed == 0:
+            stats["depth"][:] = 0
+            return result()
+        if sparse.n_docs > 0:                                                  # the same filter over sparse positions, built once per call
+            sparse_mask = doc_mask_remap(mask, dense.id_end, s2d[:sparse.n_docs], sparse.n_docs)      # an s2d shorter than n_docs: ValueError
 
     def store(rows, keep, out):
         scores[rows], ids[rows], counts[rows] = out[0][keep], out[1][keep], out[2][keep]
@@ -157,12 +177,15 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
             break
         qs, csr = q[pending].contiguous(), _csr_rows(row_ptr, cols, vals, pending)
         kd, ks = min(depth, N), min(depth, max(1, sparse.n_docs))
-        with _pair_order(dense, n):
-            ds, di = dense.search(qs, kd)
-        ss, si, sc = sparse.search(csr[0], csr[1], csr[2], ks, threshold=0.0)
+        if mask is None:
+            with _pair_order(dense, n):
+                ds, di = dense.search(qs, kd)
+        else:
+            ds, di = dense.search(qs, kd, mask=mask)                       # pair-score bits for every nq; padded (-FLT_MAX, -1) when m < kd
+        ss, si, sc = sparse.search(csr[0], csr[1], csr[2], ks, threshold=0.0, mask=sparse_mask)
         D = ds[:, kd - 1].contiguous()
         S = torch.where(sc == ks, ss[:, ks - 1], torch.zeros_like(D))      # a shorter list: every document outside it scores <= 0
-        complete = torch.full((n,), kd >= N, dtype=torch.bool, device=dev)
+        complete = torch.full((n,), kd >= n_allowed, dtype=torch.bool, device=dev)
         indptr, dpos, spos, tie = hybrid_union(di, si, sc, s2d, d2s)
         out = _rescore_and_rank(dense, sparse, qs, csr, indptr, dpos, spos, tie, w, k, D, S, complete, n_s2d)
         certified = out[3] != 0
@@ -178,7 +201,7 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
         # the range route.  Uncertified means g(D) >= F_k, so d* <= D: the dense list of the last depth lies inside the hits.
         thr, si, sc = open_lists
         qs = q[pending].contiguous()
-        qs, thr, lims, total = dense.range_count(qs, thr)
+        qs, thr, lims, total = dense.range_count(qs, thr, mask=mask)
         lens = (lims[1:] - lims[:-1]).cpu().numpy()
         pend_h = pending.cpu().numpy()
         need = (lens + si.shape[1]) * CANDIDATE_BYTES
@@ -195,10 +218,10 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
         for g0, g1 in groups:
             if len(groups) == 1:
                 gq, glims = qs, lims
-                _, hit_ids = dense.range_fill(qs, thr, lims, total)
+                _, hit_ids = dense.range_fill(qs, thr, lims, total, mask=mask)
             else:
-                gq, gthr, glims, gtotal = dense.range_count(qs[g0:g1], thr[g0:g1])
-                _, hit_ids = dense.range_fill(gq, gthr, glims, gtotal)
+                gq, gthr, glims, gtotal = dense.range_count(qs[g0:g1], thr[g0:g1], mask=mask)
+                _, hit_ids = dense.range_fill(gq, gthr, glims, gtotal, mask=mask)
             rows = pending[g0:g1]
             csr = _csr_rows(row_ptr, cols, vals, rows)
             indptr, dpos, spos, tie = hybrid_union(hit_ids, si[g0:g1], sc[g0:g1], s2d, d2s, a_indptr=glims)

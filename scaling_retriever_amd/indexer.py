@@ -269,17 +269,26 @@ class DenseFlatIndexer(DenseIndexer):
         positions = np.ascontiguousarray(positions, dtype=np.int64)
         return _host_lists.take_rows(table.ctypes.data, len(table) - 1, positions.ctypes.data, positions.shape[0], positions.shape[1])
 
-    def range_search(self, query_reps, thresholds, sort=True):
+    def range_search(self, query_reps, thresholds, sort=True, allowed_ids=None, allowed_mask=None):
         """Every document scoring above a threshold (faiss's IndexFlatIP.range_search; the dense counterpart of the threshold of
         numba_score_float, indexer.py:315-344): (list of db-id lists, list of fp32 score arrays), one pair per query, of the documents
         with score > thresholds (a float, or one value per query).  sort=True: best first, ties by index position, so a list is a
         prefix of what search_knn ranks; False: index order.  The ids go through id_table in one numpy take (the ragged counterpart
-        of id_lists)."""
+        of id_lists).  allowed_ids / allowed_mask (not both) as for search_knn: only these documents are returned - the lists are the
+        unrestricted ones with every other document removed (DenseIndexHIP.range_search, mask; faiss's range_search with an IDSelector)."""
+        if allowed_ids is not None and allowed_mask is not None:
+            raise ValueError("range_search: pass allowed_ids or allowed_mask, not both")
+        mask = None
+        if allowed_mask is not None:
+            mask = self.allowed_mask_words(allowed_mask)
+        elif allowed_ids is not None:
+            from .scoring import doc_mask_from_list
+            mask = doc_mask_from_list(self.allowed_subset(allowed_ids), self.index.id_end, device=self.index.device)
         if isinstance(query_reps, torch.Tensor):
             q = query_reps.to(device=self.index.device, dtype=torch.float32)
         else:
             q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
-        lims, scores, positions = self.index.range_search(q, thresholds, sort=sort)
+        lims, scores, positions = self.index.range_search(q, thresholds, sort=sort, mask=mask)
         lims, scores = lims.cpu().numpy(), scores.cpu().numpy()
         flat = self.id_table()[positions.cpu().numpy()]
         return ([flat[a:b].tolist() for a, b in zip(lims[:-1], lims[1:])],
@@ -814,7 +823,7 @@ class SparseRetrieval:
             self._doc_table = IdTable(_doc_id_table(self.doc_ids, self.sparse_index.nb_docs()))
         return self._doc_table
 
-    def range_search(self, sparse_query_vecs, thresholds=0., sort=True):
+    def range_search(self, sparse_query_vecs, thresholds=0., sort=True, allowed_ids=None, allowed_mask=None):
         """Every document scoring above a threshold - the full list of numba_score_float (indexer.py:324-344) for a whole query set,
         the counterpart of DenseFlatIndexer.range_search: (list of collection-id lists, list of fp32 score arrays), one pair per query,
         of the documents with score > thresholds (a float, or one value per query).  sparse_query_vecs as _generate_query_vecs returns
@@ -822,9 +831,19 @@ class SparseRetrieval:
         a prefix of what retrieve ranks; False: document order.  The ids go through doc_id_table in one numpy take.
         A document without any posting has no collection id (doc_ids.pkl does not list it; the reference's doc_ids[id_] raises
         KeyError for it).  It scores 0.0 and so passes a negative threshold: such documents are left out of the lists here, their
-        placeholders of doc_id_table never come back.  SparseIndexHIP.range_search returns them, by position."""
+        placeholders of doc_id_table never come back.  SparseIndexHIP.range_search returns them, by position.
+        allowed_ids / allowed_mask (not both) as for retrieve: only these documents are returned - the unrestricted lists with every
+        other document removed (SparseIndexHIP.range_search, mask)."""
+        if allowed_ids is not None and allowed_mask is not None:
+            raise ValueError("range_search: pass allowed_ids or allowed_mask, not both")
+        mask = None
+        if allowed_mask is not None:
+            mask = self.allowed_mask_words(allowed_mask)
+        elif allowed_ids is not None:
+            from .scoring import doc_mask_from_list
+            mask = doc_mask_from_list(self.allowed_subset(allowed_ids), self.hip_index.n_docs, device=self._dev)
         q = _as_query_csr(sparse_query_vecs, self._dev)
-        lims, scores, positions = self.hip_index.range_search(q.row_ptr, q.cols, q.vals, thresholds, sort=sort)
+        lims, scores, positions = self.hip_index.range_search(q.row_ptr, q.cols, q.vals, thresholds, sort=sort, mask=mask)
         lims, scores, positions = lims.cpu().numpy(), scores.cpu().numpy(), positions.cpu().numpy()
         table = self.doc_id_table()
         if len(self.doc_ids) < table.n:                      # some document has no id: drop its entries, list by list
@@ -966,7 +985,7 @@ class ShardedSparseRetrieval(SparseRetrieval):
                 ids.update(pickle.load(f))
         return ids
 
-    def range_search(self, sparse_query_vecs, thresholds=0., sort=True):
+    def range_search(self, sparse_query_vecs, thresholds=0., sort=True, allowed_ids=None, allowed_mask=None):
         raise NotImplementedError("ShardedSparseRetrieval.range_search: a range search is not offered on a doc-sharded index; "
                                   "search one merged index with SparseRetrieval instead")
 
@@ -1195,8 +1214,16 @@ class HybridRetriever(SparseRetrieval):
         return ranked_run(qids, fused_scores(dense_s, sparse_s, weights), dpos_t, tie, torch.from_numpy(indptr).to(self._dev),
                           self.dense_index.run_table())
 
+    def allowed_mask(self, allowed_ids):
+        """Database ids (any order, duplicates allowed) -> a boolean array over dense index positions, True at these documents: the
+        allowed_mask of search_fused / retrieve_fused_exact (and of the dense index's search_knn / range_search).  An unknown id:
+        ValueError naming it."""
+        flags = np.zeros(self.dense_index.index.id_end, dtype=bool)
+        flags[self.dense_index.allowed_subset(allowed_ids).cpu().numpy()] = True
+        return flags
+
     def search_fused(self, sparse_query_vecs, dense_query_vecs, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, qids=None,
-                     allowed_ids=None):
+                     allowed_ids=None, allowed_mask=None):
         """The EXACT top-k of the fused score of retrieve_fused over every document of the dense index (hybrid.search_fused: the
         union of the two heads' lists at depth depths[0] >= topk where a certificate proves it holds the true top-k, deeper lists
         for the queries it does not, a dense range search for what is left; the same result whatever route served a query).
@@ -1204,12 +1231,15 @@ class HybridRetriever(SparseRetrieval):
         (documents without a posting after the indexed ones); stats = {"depth": per query the index into `depths` at which it was
         certified, -1 = range route; "union": candidates ranked; "range_hits"; "depths"}.  qids (None: 0 .. nq - 1) name the rows.
         topk >= 1 and two finite weights >= 0, else ValueError before any device work; the dense index must be in precision fp32 /
-        fp32_filtered (ValueError).  Not supported (NotImplementedError): allowed_ids, and the doc-sharded classes."""
+        fp32_filtered (ValueError).  allowed_mask (None: every document): a boolean array over dense index positions, the allowed_mask
+        of search_knn - the exact top-k of the fused score over these documents alone (fewer than topk of them: shorter rows); build
+        it from database ids with allowed_mask(ids).  Not supported (NotImplementedError): allowed_ids, and the doc-sharded classes."""
         from . import hybrid
         hybrid.check_arguments(topk, weights)
         if allowed_ids is not None:
-            raise NotImplementedError("HybridRetriever.search_fused: an allow-list (allowed_ids) is not supported by the exact fused search; "
-                                      "retrieve_fused(allowed_ids=...) ranks the union of the two restricted lists")
+            raise NotImplementedError("HybridRetriever.search_fused: an allow-list of ids (allowed_ids) is not taken by the exact fused "
+                                      "search; pass the bitmap instead: allowed_mask=ret.allowed_mask(ids)")
+        mask = None if allowed_mask is None else self.dense_index.allowed_mask_words(allowed_mask)
         q = _as_query_csr(sparse_query_vecs, self._dev)
         d2s, s2d = self._position_maps()
         if isinstance(dense_query_vecs, torch.Tensor):
@@ -1217,20 +1247,23 @@ class HybridRetriever(SparseRetrieval):
         else:
             dq = torch.from_numpy(np.ascontiguousarray(dense_query_vecs, dtype=np.float32)).to(self._dev)
         scores, positions, counts, stats = hybrid.search_fused(self.dense_index.index, self.hip_index, d2s, s2d, dq, q.row_ptr, q.cols, q.vals,
-                                                               topk, weights=weights, depths=depths, fallback_bytes=fallback_bytes)
+                                                               topk, weights=weights, depths=depths, fallback_bytes=fallback_bytes, mask=mask)
         qids = list(range(dq.shape[0])) if qids is None else qids
         return RunResult(qids, scores, positions, self.dense_index.run_table(), counts), stats
 
-    def retrieve_fused_exact(self, q_loader, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, allowed_ids=None):
+    def retrieve_fused_exact(self, q_loader, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, allowed_ids=None,
+                             allowed_mask=None):
         """Encodes the queries once (both heads) and writes {out_dir}/fused_exact/run.json, next to the two heads' runs: the exact
-        fused top-k of search_fused.  Returns (RunResult, stats).  The files of retrieve / retrieve_fused are not touched."""
+        fused top-k of search_fused (allowed_mask as there).  Returns (RunResult, stats).  The files of retrieve / retrieve_fused are
+        not touched."""
         from . import hybrid
         hybrid.check_arguments(topk, weights)
         if allowed_ids is not None:
-            raise NotImplementedError("HybridRetriever.retrieve_fused_exact: an allow-list (allowed_ids) is not supported")
+            raise NotImplementedError("HybridRetriever.retrieve_fused_exact: an allow-list of ids (allowed_ids) is not taken; pass the "
+                                      "bitmap instead: allowed_mask=ret.allowed_mask(ids)")
         sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
         res, stats = self.search_fused(sparse_query_vecs, dense_query_vecs, topk, weights=weights, depths=depths,
-                                       fallback_bytes=fallback_bytes, qids=qids)
+                                       fallback_bytes=fallback_bytes, qids=qids, allowed_mask=allowed_mask)
         out_dir = os.path.join(os.path.dirname(self.sparse_out_dir), "fused_exact")
         os.makedirs(out_dir, exist_ok=True)
         res.dump(os.path.join(out_dir, "run.json"))

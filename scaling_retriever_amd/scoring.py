@@ -124,6 +124,64 @@ def _mask_words(words, device):
     return words.to(device).contiguous()
 
 
+def _mask_argument(mask, n_bits_of, what):
+    """The checks of a `mask=` argument that need no device: (packed, mask as tensor / array).  n_bits_of() - asked only for a packed
+    mask - is the number of bits the index expects (`what` names it in the message); the word count is verified against it."""
+    if not torch.is_tensor(mask) and not isinstance(mask, np.ndarray):
+        mask = np.asarray(mask)
+    packed = (isinstance(mask, np.ndarray) and mask.dtype in (np.uint32, np.int32)) or \
+        (torch.is_tensor(mask) and mask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
+    if not packed:
+        is_bool = (isinstance(mask, np.ndarray) and mask.dtype == np.bool_) or (torch.is_tensor(mask) and mask.dtype == torch.bool)
+        if not is_bool:
+            raise ValueError("mask must be a bool tensor / array over the documents, or packed int32 / uint32 words (pack_doc_mask), got "
+                             f"{getattr(mask, 'dtype', type(mask).__name__)}")
+    if (mask.dim() if torch.is_tensor(mask) else mask.ndim) != 1:
+        raise ValueError(f"expected a 1-D mask, got {tuple(mask.shape)}")
+    if packed:
+        n, n_bits = (mask.numel() if torch.is_tensor(mask) else mask.size), int(n_bits_of())
+        if n != (n_bits + 31) // 32:
+            raise ValueError(f"a packed mask of this index holds {(n_bits + 31) // 32} words ({what} = {n_bits}), got {n}")
+    return packed, mask
+
+
+def _mask_on_device(packed, mask, n_bits_of, device):
+    """(int32 words on the device, n_bits) of a mask that went through _mask_argument; a bool mask is packed on the device and its own
+    length is n_bits (the library compares it with the index)."""
+    if packed:
+        n_bits, words = int(n_bits_of()), _mask_words(mask, device)
+    else:
+        flags = _to_dev(mask, torch.bool, device)
+        n_bits, words = flags.numel(), pack_doc_mask(flags)
+    return words, n_bits
+
+
+def _valid(t):
+    """t, or one zero of its type where t is empty: a valid pointer for the C ABI."""
+    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+def doc_mask_remap(words, n_src_bits, map, n_dst_bits):
+    """A bitmap carried over to another numbering (sr_doc_mask_remap): bit i of the result = bit map[i] of `words` (packed int32 / uint32
+    words over n_src_bits bits) where 0 <= map[i] < n_src_bits, else 0; map int64 [n_dst_bits].  Returns int32 words
+    [ceil(n_dst_bits / 32)] on the device."""
+    _lib.require_gpu()
+    device = words.device if torch.is_tensor(words) and words.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    words = _mask_words(words, device)
+    n_src_bits, n_dst_bits = int(n_src_bits), int(n_dst_bits)
+    if words.numel() < (n_src_bits + 31) // 32:
+        raise ValueError(f"{n_src_bits} bits need {(n_src_bits + 31) // 32} words, got {words.numel()}")
+    map = _to_dev(map, torch.int64, device)
+    if map.dim() != 1 or map.numel() != n_dst_bits:
+        raise ValueError(f"expected a map of {n_dst_bits} entries, got {tuple(map.shape)}")
+    out = torch.empty((max(1, (n_dst_bits + 31) // 32),), dtype=torch.int32, device=device)
+    keep = [t if t.numel() else torch.zeros(1, dtype=t.dtype, device=device) for t in (words, map)]      # valid pointers
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().sr_doc_mask_remap(_ptr(keep[0]), n_src_bits, _ptr(keep[1]), n_dst_bits, _ptr(out), _lib.stream_ptr()),
+                   "sr_doc_mask_remap")
+    return out[:(n_dst_bits + 31) // 32]
+
+
 def allowed_positions(allowed_ids, position_of, what="document id"):
     """External document ids (any order, duplicates allowed) -> sorted unique positions, np.int64: the allow-list the subset searches take.
     position_of maps an id to its position (a dict's .get, or any callable that returns None for an unknown id); an unknown id raises
@@ -432,21 +490,35 @@ class DenseIndexHIP:
                                                 _lib.stream_ptr()), "sr_dense_search")
         return scores, ids
 
-    def range_search(self, queries, thresholds, sort=False):
+    def _range_mask(self, mask):
+        """(words, n_bits) on the device of a range search's mask=, checked as far as possible before anything is uploaded."""
+        packed, mask = _mask_argument(mask, lambda: self.id_end, "id_end")
+        return _mask_on_device(packed, mask, lambda: self.id_end, self.device)
+
+    def range_search(self, queries, thresholds, sort=False, mask=None):
         """Every document scoring above a threshold (faiss's IndexFlatIP.range_search; include/sr_hip.h sr_dense_range_count / _fill):
         queries fp32 cuda [nq, dim]; thresholds a float for all queries, or a tensor / array [nq].  Returns (lims int64 [nq + 1],
         scores fp32 [total], ids int64 [total]) as cuda tensors: the documents of query q with score > thresholds[q] are entries
         lims[q]:lims[q + 1], in (segment, row) order - ascending id for segments added in id order.  Scores are the exact chain of
-        `score_pairs` for every nq.  sort=True: each list by score descending, ties by ascending id (range_sort)."""
-        queries, thr, lims, n = self.range_count(queries, thresholds)
-        scores, ids = self.range_fill(queries, thr, lims, n)
+        `score_pairs` for every nq.  sort=True: each list by score descending, ties by ascending id (range_sort).  mask (None: every
+        document): a bitmap over [0, id_end) in the forms `search(mask=)` takes - only documents whose bit is set are returned
+        (sr_dense_range_count_masked / _fill_masked; a set bit that names no document is ignored); one mask for all queries."""
+        if mask is not None:
+            mask, n_bits = self._range_mask(mask)     # packed once, shared by the two halves
+            if n_bits != self.id_end:
+                raise ValueError(f"a mask of this index holds {self.id_end} flags (id_end), got {n_bits}")
+        queries, thr, lims, n = self.range_count(queries, thresholds, mask=mask)
+        scores, ids = self.range_fill(queries, thr, lims, n, mask=mask)
         if sort:
             scores, ids = range_sort(lims, scores, ids)
         return lims, scores, ids
 
-    def range_count(self, queries, thresholds):
-        """The first half of range_search (sr_dense_range_count): returns (queries, thresholds [nq], lims int64 [nq + 1], total) - the
-        contiguous tensors range_fill takes, and the sizes of the lists before anything of their size is allocated."""
+    def range_count(self, queries, thresholds, mask=None):
+        """The first half of range_search (sr_dense_range_count; under a mask sr_dense_range_count_masked): returns (queries, thresholds
+        [nq], lims int64 [nq + 1], total) - the contiguous tensors range_fill takes, and the sizes of the lists before anything of their
+        size is allocated."""
+        if mask is not None:
+            packed, mask = _mask_argument(mask, lambda: self.id_end, "id_end")
         if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
         if not queries.is_cuda or queries.device != self.device:
@@ -461,15 +533,30 @@ class DenseIndexHIP:
                 raise ValueError(f"expected {nq} thresholds, got {tuple(thr.shape)}")
         lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
+        if mask is not None:
+            words, n_bits = _mask_on_device(packed, mask, lambda: self.id_end, self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_dense_range_count_masked(self._h, _ptr(queries), nq, _ptr(thr), _ptr(_valid(words)), n_bits, _ptr(lims),
+                                                                ctypes.byref(total), _lib.stream_ptr()), "sr_dense_range_count_masked")
+            return queries, thr, lims, total.value
         with torch.cuda.device(self.device):
             _lib.check(self.lib.sr_dense_range_count(self._h, _ptr(queries), nq, _ptr(thr), _ptr(lims), ctypes.byref(total),
                                                      _lib.stream_ptr()), "sr_dense_range_count")
         return queries, thr, lims, total.value
 
-    def range_fill(self, queries, thr, lims, n):
-        """The second half (sr_dense_range_fill) for what the preceding range_count on this index returned: (scores fp32 [n], ids int64 [n])."""
+    def range_fill(self, queries, thr, lims, n, mask=None):
+        """The second half (sr_dense_range_fill; under a mask sr_dense_range_fill_masked) for what the preceding range_count on this index
+        returned, under the mask that count was given: (scores fp32 [n], ids int64 [n])."""
+        if mask is not None:
+            words, n_bits = self._range_mask(mask)
         scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
         ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
+        if mask is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_dense_range_fill_masked(self._h, _ptr(queries), queries.shape[0], _ptr(thr), _ptr(_valid(words)), n_bits,
+                                                               _ptr(lims), _ptr(scores), _ptr(ids), n, _lib.stream_ptr()),
+                           "sr_dense_range_fill_masked")
+            return scores[:n], ids[:n]
         with torch.cuda.device(self.device):
             _lib.check(self.lib.sr_dense_range_fill(self._h, _ptr(queries), queries.shape[0], _ptr(thr), _ptr(lims), _ptr(scores), _ptr(ids), n,
                                                     _lib.stream_ptr()), "sr_dense_range_fill")
@@ -610,21 +697,7 @@ class SparseIndexHIP:
 
     def _mask_argument(self, mask):
         """The checks of `search(mask=)` that need no device: (packed, mask as tensor / array), the word count of a packed mask verified."""
-        if not torch.is_tensor(mask) and not isinstance(mask, np.ndarray):
-            mask = np.asarray(mask)
-        packed = (isinstance(mask, np.ndarray) and mask.dtype in (np.uint32, np.int32)) or \
-            (torch.is_tensor(mask) and mask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
-        if not packed:
-            is_bool = (isinstance(mask, np.ndarray) and mask.dtype == np.bool_) or (torch.is_tensor(mask) and mask.dtype == torch.bool)
-            if not is_bool:
-                raise ValueError("mask must be a bool tensor / array over the documents, or packed int32 / uint32 words (pack_doc_mask), got "
-                                 f"{getattr(mask, 'dtype', type(mask).__name__)}")
-        if (mask.dim() if torch.is_tensor(mask) else mask.ndim) != 1:
-            raise ValueError(f"expected a 1-D mask, got {tuple(mask.shape)}")
-        n = mask.numel() if torch.is_tensor(mask) else mask.size
-        if packed and n != (self.n_docs + 31) // 32:
-            raise ValueError(f"a packed mask of this index holds {(self.n_docs + 31) // 32} words (n_docs = {self.n_docs}), got {n}")
-        return packed, mask
+        return _mask_argument(mask, lambda: self.n_docs, "n_docs")
 
     def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, id_base=0, id_stride=1, subset=None, mask=None):
         """Queries as CSR tensors. Returns (scores [nq,k], ids [nq,k], counts [nq]) cuda tensors.  subset (None: every document):
@@ -680,13 +753,16 @@ class SparseIndexHIP:
                                                  _ptr(counts), _lib.stream_ptr()), "sr_sparse_search")
         return scores, ids, counts
 
-    def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False):
+    def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False, mask=None):
         """Every document scoring above a threshold - the full list of numba_score_float (scaling_retriever/indexer.py:324-344;
         include/sr_hip.h sr_sparse_range_count / _fill): queries as CSR as for `search`; thresholds a float for all queries, or a
         tensor / array [nq].  Returns (lims int64 [nq + 1], scores fp32 [total], ids int64 [total]) as cuda tensors: the documents of
         query q with score > thresholds[q] are entries lims[q]:lims[q + 1], in ascending document position, ids = id_base + position *
         id_stride.  A document without a common term scores 0.0 and is returned exactly under a negative threshold.  Scores are the
-        chain of `score_pairs`.  sort=True: each list by score descending, ties by ascending id (range_sort)."""
+        chain of `score_pairs`.  sort=True: each list by score descending, ties by ascending id (range_sort).  mask (None: every
+        document): a bitmap over [0, n_docs) in the forms `search(mask=)` takes - only documents whose bit is set are returned
+        (sr_sparse_range_count_masked / _fill_masked), a document without a common term included when the threshold is negative."""
+        packed, mask = self._mask_argument(mask) if mask is not None else (False, None)
         q_indptr = _to_dev(q_indptr, torch.int64, self.device)
         q_cols = _to_dev(q_cols, torch.int32, self.device)
         q_vals = _to_dev(q_vals, torch.float32, self.device)
@@ -704,15 +780,29 @@ class SparseIndexHIP:
             raise ValueError("sort=True orders by the search's 64-bit key, which holds ids below 2^32; sort the lists of larger ids yourself")
         lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_range_count(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
-                                                      ctypes.byref(total), _lib.stream_ptr()), "sr_sparse_range_count")
-            n = total.value
-            scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
-            ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
-            _lib.check(self.lib.sr_sparse_range_fill(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
-                                                     int(id_base), int(id_stride), _ptr(scores), _ptr(ids), n, _lib.stream_ptr()),
-                       "sr_sparse_range_fill")
+        if mask is not None:
+            words, n_bits = _mask_on_device(packed, mask, lambda: self.n_docs, self.device)
+            words = _valid(words)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_sparse_range_count_masked(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(words),
+                                                                 n_bits, _ptr(lims), ctypes.byref(total), _lib.stream_ptr()),
+                           "sr_sparse_range_count_masked")
+                n = total.value
+                scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
+                ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
+                _lib.check(self.lib.sr_sparse_range_fill_masked(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(words),
+                                                                n_bits, _ptr(lims), int(id_base), int(id_stride), _ptr(scores), _ptr(ids), n,
+                                                                _lib.stream_ptr()), "sr_sparse_range_fill_masked")
+        else:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sr_sparse_range_count(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
+                                                          ctypes.byref(total), _lib.stream_ptr()), "sr_sparse_range_count")
+                n = total.value
+                scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
+                ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
+                _lib.check(self.lib.sr_sparse_range_fill(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
+                                                         int(id_base), int(id_stride), _ptr(scores), _ptr(ids), n, _lib.stream_ptr()),
+                           "sr_sparse_range_fill")
         scores, ids = scores[:n], ids[:n]
         if sort:
             scores, ids = range_sort(lims, scores, ids)
