@@ -201,7 +201,7 @@ int sr_dense_search_subset(sr_dense_index* idx, const float* d_queries, int64_t 
  * SR_SUBSET_DENSE_ROUTE=gather|mask forces one (read per call; `mask` where it does not apply is served by gather).  The mask route
  * reads the call's status once BEFORE its pass instead of at the end; a bad list is then handled by the gather route as above.  The
  * handle keeps the bitmap (id_end / 8 bytes), allocated on first use.  Not under a mask: the sparse head, doc-sharded search,
- * per-query masks, the streaming / bf16x3 / bf16x6 passes, batches of <= 64 queries (gather).                                    */
+ * the streaming / bf16x3 / bf16x6 passes, batches of <= 64 queries (gather).  A mask per query: sr_dense_search_grouped below.   */
 /* The largest document index of any segment, plus one (not ntotal: segments have id_base / id_stride); 0 for an empty index, -1 for a
  * null one.  The length in bits of a document bitmap of this index.                                                              */
 int64_t sr_dense_index_id_end(const sr_dense_index* idx);
@@ -232,6 +232,40 @@ int sr_doc_mask_remap(const uint32_t* d_src_words, int64_t n_src_bits, const int
 int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
                            const uint32_t* d_mask_words, int64_t n_bits,
                            float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
+/* Dense top-k under per-query document filters (filter groups).  d_group_words uint32 [n_groups, W] on the device, W =
+ * ceil(n_bits / 32): n_groups bitmaps in the bit convention of sr_dense_search_masked, stacked; n_bits == sr_dense_index_id_end(idx);
+ * d_query_group int32 [nq] on the device: query q searches under bitmap d_query_group[q].  One group is sr_dense_search_masked,
+ * n_groups == nq a filter of its own per query; a group without queries is allowed.
+ * Result: for every group g, the output rows of the queries with d_query_group[q] == g are EXACTLY what sr_dense_search_masked returns
+ * for those queries alone, in their order, under bitmap g - ids, score bits, tie order (ascending doc index) and padding (-FLT_MAX, -1:
+ * a group with fewer than k allowed documents, or none) - for every group size, 1 included, on fp32 and fp16 rows, contiguous and
+ * strided segments, whichever route served the call (the subset searches' scores do not depend on nq, so this is well defined).
+ * k: 1 <= k <= sr_max_topk(); a larger k is SR_ERR_INVALID.  Sizes: n_groups >= 1 and n_groups * W < 2^32.
+ * Errors, all SR_ERR_INVALID: n_bits != id_end, a bad k or n_groups, or a null pointer with nq > 0 - before any device work; an entry of
+ * d_query_group outside [0, n_groups) - sr_last_error() names the first such query; a set bit below n_bits that names no document (a
+ * gap of a strided segment) - sr_last_error() names the first such (group, bit).  In the last two cases nothing is scored, every
+ * output row is padding and the index stays usable.  The bitmaps are tested in one word-parallel pass against a bitmap of the indexed
+ * positions (id_end / 8 bytes on the handle, built from the segment table, rebuilt when a segment was added; not needed, not built, for
+ * stride-1 segments that cover [0, id_end)) - no group is expanded to a list to be validated.
+ * Routes, the same bits.  (1) The grouped pass: under the conditions of the masked search's mask route (SR_PRECISION_FP32_FILTERED,
+ * nq > 64, k <= 1 365, dim % 64 == 0, dim >= 128, every segment filterable) the certified filter's upper-bound pass with the bit test
+ * reading the query's own bitmap (4 nq bytes of word offsets on the handle); thresholds, certificate and re-score are per-query
+ * quantities over that query's allowed documents, so the filter's argument holds as for one mask.  Queries left without a certificate
+ * are re-done by the gather route under their own group's list, those alone, group by group.  (2) The group loop, everywhere else: per
+ * group with a query in it, its queries gathered, its bitmap expanded to the ascending list (8 m_g bytes on the handle, one group at a
+ * time), the gather route, the rows scattered back.  Rule: the pass where it applies and sum_g nq_g * m_g >= 6 980 * 130 000 - the
+ * constant of the subset searches, measured for ONE group; the loop's per-group overhead moves the real crossover down as groups
+ * multiply, and that has not been measured.  Dev switch SR_GROUPED_DENSE_ROUTE=pass|loop forces one (read per call; `pass` where it
+ * does not apply is served by the loop).
+ * Synchronisation: the call waits for the stream twice before any scoring - the group ids (4 nq bytes), then the per-group counts with
+ * the gap check's word (8 n_groups + 8 bytes); then the pass route once for the certificate's flags, as the masked search does, and
+ * once more only if queries were re-done; the loop route once at its end.
+ * sr_dense_index_filter_stats / _filter_query_stats count a call that ran the grouped pass like any filtered search (the loop: not at
+ * all).  Not offered under groups: the sparse head and the hybrid searches, range searches, k > sr_max_topk(), doc-sharded search.    */
+int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
+                            const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits,
+                            const int32_t* d_query_group,
+                            float* d_out_scores, int64_t* d_out_ids, sr_stream stream);
 /* Range search: EVERY document whose score exceeds a per-query threshold, as CSR - faiss's IndexFlatIP.range_search(x, thresh) ->
  * (lims, D, I) with one threshold per query, and on the dense head what the reference's sparse scorer does with its threshold
  * (numba_score_float, scaling_retriever/indexer.py:315-344: every document with score > threshold).  Two calls, because the size of

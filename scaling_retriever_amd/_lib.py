@@ -51,6 +51,8 @@ SIGNATURES = {
     "sr_doc_mask_from_list": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "sr_doc_list_from_mask": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "sr_dense_search_masked": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_dense_search_grouped": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
     "sr_dense_range_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     "sr_dense_range_fill": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sr_dense_range_count_masked": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, ctypes.POINTER(c_int64),

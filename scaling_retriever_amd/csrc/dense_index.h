@@ -1,6 +1,6 @@
 // The dense index handle and what its parts share (internal): dense_index.hip owns the handle and the segments' preparation,
-// dense_search.hip the search pass and the certified filter's orchestration, dense_restrict.hip pair scoring and the subset / masked
-// searches, dense_range.hip the range search.
+// dense_search.hip the search pass and the certified filter's orchestration, dense_restrict.hip pair scoring and the subset / masked /
+// grouped searches, dense_range.hip the range search.
 #pragma once
 #include "common.h"
 #include "pair_score.h"
@@ -64,6 +64,11 @@ struct sr_dense_index {
     DeviceBuf<uint32_t> mask_words;        // the bitmap of a list: id_end / 8 bytes
     DeviceBuf<int64_t> mask_list;          // the list of a bitmap: 8 m bytes
     DeviceBuf<int64_t> mask_blocks;        // per-workgroup counts of the bitmap -> list scan, + 1: the count
+    // sr_dense_search_grouped (dense_restrict.hip): allocated on first use, reused
+    DeviceBuf<uint32_t> grp_valid;         // bitmap of the positions below id_end that name a document (only for layouts with gaps)
+    size_t grp_valid_segs = 0;             // stamp of the segment list grp_valid was built from (segments are only ever added)
+    DeviceBuf<uint32_t> grp_qoff;          // [nq rounded up to 256] word offset of every query's bitmap: the grouped pass reads it
+    DeviceBuf<int64_t> grp_counts;         // [n_groups] set bits per group, + 1: the first (group, bit) that names no document
     // sr_dense_range_count / _fill (dense_range.hip): the (chunk, query) prefix table of the last count and what it was made for
     DeviceBuf<uint32_t> range_tab;                                   // [chunks of all segments, range_nq]
     int64_t range_nq = -1, range_total = 0, range_chunk_rows = 0;    // range_nq = -1: no count to fill from
@@ -88,6 +93,7 @@ struct DensePassOpts {
     bool tiled_only = false;                // the re-do of a few queries: the tiled kernels whatever the count (one k order), workspace ws3
     int k_inner = 0;                        // filter_upper_bound: the k of the search, where the pass's own k is the candidates per query
     const uint32_t* mask = nullptr;         // filter_upper_bound, nullable: the document bitmap of a masked search - only set bits become keys
+    const uint32_t* mask_qoff = nullptr;    // with mask, nullable: per query the word offset of its own bitmap inside mask (grouped search)
 };
 // top-k of every query over all segments (16-bit arithmetic serves batches of more than 64 queries, the exact kernels the others)
 int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, float* d_out_scores, int64_t* d_out_ids,
@@ -95,13 +101,19 @@ int dense_search_pass(sr_dense_index* idx, const float* d_queries, int64_t nq, i
 // whether the certified filter can serve this index and batch, and with how many candidates per query (*kp)
 int dense_filter_applies(sr_dense_index* idx, int64_t nq, int k, int* kp, bool* applies, bool full_kp = false);
 // The two halves of a filtered search.  First: the kp documents with the largest upper bounds per query (idx->a_scores / a_ids / qa), under
-// the document bitmap d_mask over [0, id_end) if one is given; *done = false: the filter does not apply.
+// the document bitmap d_mask over [0, id_end) if one is given - query q's own at d_mask + d_mask_qoff[q] words if offsets are given too;
+// *done = false: the filter does not apply.
 int dense_filtered_candidates(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, hipStream_t s, bool* done,
-                              const uint32_t* d_mask = nullptr);
+                              const uint32_t* d_mask = nullptr, const uint32_t* d_mask_qoff = nullptr);
 // Second: exact re-score, certificate, exact re-do of the queries without one.  d_thr (nullable, doc-sharded search): per query a value
-// proven not to exceed the GLOBAL k-th exact score.  d_list / m (masked search; d_list null otherwise): the allowed documents, ascending
+// proven not to exceed the GLOBAL k-th exact score.  d_list / m (masked search; d_list null otherwise): the allowed documents, ascending.
+// redo_out (grouped search; null otherwise): the queries without a certificate are counted and handed back, ascending, instead of re-done -
+// the caller re-does each under its own group's list.
 int dense_filtered_finish(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const float* d_thr, float* d_out_scores,
-                          int64_t* d_out_ids, hipStream_t s, const int64_t* d_list = nullptr, int64_t m = 0);
+                          int64_t* d_out_ids, hipStream_t s, const int64_t* d_list = nullptr, int64_t m = 0,
+                          std::vector<int64_t>* redo_out = nullptr);
+// room in idx->redo_q / redo_idx / redo_scores / redo_ids for nf queries taken out of a batch and their [nf, k] results
+int dense_redo_reserve(sr_dense_index* idx, int64_t nf, int k);
 
 // ---- dense_restrict.hip (idx->mu held): idx->pair_segs := the segments as a device table; top-k within an ascending list by the gather kernel ----
 int dense_pair_segs(sr_dense_index* idx, const char* who);

@@ -1,9 +1,12 @@
 // Dense scoring restricted to given documents: caller-supplied (query, document) pairs (pair_score.hip), and top-k within a subset
 // given as an ascending list or as a bitmap - by the gather kernel (subset_search.hip) or by the certified filter's pass under the
-// bitmap (dense_search.hip, doc_mask.hip).
+// bitmap (dense_search.hip, doc_mask.hip); and the same under a bitmap per query (filter groups, at the end of the file).
 #include "dense_index.h"
+#include "dense_filter.h"
 #include "subset_search.h"
 #include "doc_mask.h"
+#include <algorithm>
+#include <utility>
 
 int dense_pair_segs(sr_dense_index* idx, const char* who) {
     if (idx->pair_segs_n != idx->segs.size()) {           // segments are only ever added, all of one row type
@@ -213,4 +216,168 @@ extern "C" int sr_dense_search_masked(sr_dense_index* idx, const float* d_querie
         return SR_ERR_INVALID;
     }
     return SR_OK;
+}
+
+// ---- filter groups: a document bitmap per query (sr_dense_search_grouped) ------------------------------------------
+// Route rule.  The grouped pass is the mask route with the bit read from the query's own bitmap: cost ~ nq x ntotal whatever the groups
+// are.  The loop runs the gather route once per group: cost ~ sum_g nq_g x m_g pairs, plus a gather of the queries, a bitmap -> list
+// expansion and a scatter per group.  auto takes the pass where it applies and the pairs reach SR_SUBSET_DENSE_CROSSOVER - a constant
+// that was measured for ONE group (above).  The loop's per-group overhead moves the real crossover down as the groups multiply, and
+// nobody has measured where.  Dev switch SR_GROUPED_DENSE_ROUTE=pass|loop forces one, read per call; `pass` where the filter does not
+// apply is served by the loop.
+static bool grouped_dense_wants_pass(int64_t pairs) {
+    if (const char* route = sr_dev_getenv("SR_GROUPED_DENSE_ROUTE")) {
+        if (strcmp(route, "pass") == 0) return true;
+        if (strcmp(route, "loop") == 0) return false;
+    }
+    return pairs >= SR_SUBSET_DENSE_CROSSOVER;
+}
+
+// every output row of the call := padding, then the stream is waited for: what an error that scores nothing leaves behind
+static int grouped_pad_rows(float* d_out_scores, int64_t* d_out_ids, int64_t nq, int k, hipStream_t s) {
+    const int64_t n = nq * (int64_t)k;
+    const int64_t blocks = ceil_div64(n, 256) < 65536 ? ceil_div64(n, 256) : 65536;
+    hipLaunchKernelGGL(dense_pad_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_out_scores, d_out_ids, n);
+    SR_CHECK_LAUNCH();
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    return SR_OK;
+}
+
+// idx->grp_valid := the bitmap of the positions that name a document, or *d_valid = null where every position below id_end does (stride-1
+// segments that cover [0, id_end): nothing to test).  Built from the segment table and kept until a segment is added.
+static int grouped_valid_bitmap(sr_dense_index* idx, int64_t n_bits, const uint32_t** d_valid, hipStream_t s) {
+    *d_valid = nullptr;
+    std::vector<std::pair<int64_t, int64_t>> spans;       // (id_base, n) of the stride-1 segments
+    bool dense_layout = true;
+    for (const DenseSegment& seg : idx->segs) {
+        if (seg.n > 1 && seg.id_stride != 1) dense_layout = false;
+        spans.push_back({seg.id_base, seg.n});
+    }
+    if (dense_layout) {
+        std::sort(spans.begin(), spans.end());
+        int64_t end = 0;
+        for (const auto& sp : spans) {
+            if (sp.first > end) break;                    // a hole in front of this segment
+            if (sp.first + sp.second > end) end = sp.first + sp.second;
+        }
+        if (end >= n_bits) return SR_OK;
+    }
+    if (idx->grp_valid_segs != idx->segs.size() || !idx->grp_valid.p) {
+        idx->grp_valid_segs = 0;
+        SR_TRY(dense_mask_scratch(idx->grp_valid, doc_mask_words(n_bits), "sr_dense_search_grouped"));
+        SR_CHECK_HIP(hipMemsetAsync(idx->grp_valid.p, 0, (size_t)doc_mask_words(n_bits) * 4, s));
+        for (const DenseSegment& seg : idx->segs) SR_TRY(launch_doc_mask_add_segment(idx->grp_valid.p, n_bits, seg.n, seg.id_base, seg.id_stride, s));
+        idx->grp_valid_segs = idx->segs.size();
+    }
+    *d_valid = idx->grp_valid.p;
+    return SR_OK;
+}
+
+// The queries h_members[0 .. n) of the call (ascending) searched under one group's bitmap of m set bits, by the gather route, and their
+// rows written into the call's outputs.  h_members is the source of an asynchronous copy: it must outlive the caller's next wait.
+static int grouped_gather_group(sr_dense_index* idx, const float* d_queries, int k, const uint32_t* d_words, int64_t n_bits, int64_t m,
+                                const int64_t* h_members, int64_t n, float* d_out_scores, int64_t* d_out_ids, hipStream_t s) {
+    if (n == 0) return SR_OK;
+    SR_TRY(dense_redo_reserve(idx, n, k));
+    SR_CHECK_HIP(hipMemcpyAsync(idx->redo_idx.p, h_members, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    SR_TRY(launch_filter_gather_rows(d_queries, idx->redo_idx.p, n, idx->dim, idx->redo_q.p, false, s));
+    // the ascending list of the group's bits: the count is known, the scan only places the workgroups
+    const int64_t n_blocks = doc_mask_blocks(n_bits);
+    SR_TRY(dense_mask_scratch(idx->mask_blocks, n_blocks + 1, "sr_dense_search_grouped"));
+    SR_TRY(dense_mask_scratch(idx->mask_list, m > 0 ? m : 1, "sr_dense_search_grouped"));
+    SR_TRY(launch_doc_mask_count(d_words, n_bits, idx->mask_blocks.p, idx->mask_blocks.p + n_blocks, s));
+    SR_TRY(launch_doc_mask_expand(d_words, n_bits, idx->mask_blocks.p, idx->mask_list.p, m, s));
+    SR_TRY(dense_subset_gather(idx, idx->redo_q.p, n, k, idx->mask_list.p, m, idx->redo_scores.p, idx->redo_ids.p, s, "sr_dense_search_grouped"));
+    SR_TRY(launch_filter_gather_rows(idx->redo_scores.p, idx->redo_idx.p, n, k, d_out_scores, true, s));
+    return launch_filter_gather_rows(idx->redo_ids.p, idx->redo_idx.p, n, 2 * (int64_t)k, d_out_ids, true, s);
+}
+
+// Top-k of every query within its own group's documents.  Two routes, the same bits: the certified filter's pass with the bit test reading
+// the query's bitmap (dense_split_grouped.hip), its uncertified queries re-done by the gather route under their group's list; or the
+// gather route group by group.
+extern "C" int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const uint32_t* d_group_words,
+                                       int64_t n_groups, int64_t n_bits, const int32_t* d_query_group, float* d_out_scores,
+                                       int64_t* d_out_ids, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_search_grouped: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search_grouped: bad nq=%lld", (long long)nq);
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK, "sr_dense_search_grouped: k=%d outside [1, %d]", k, SR_MAX_TOPK);
+    SR_REQUIRE(n_groups >= 1, "sr_dense_search_grouped: n_groups=%lld, at least one group is needed", (long long)n_groups);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    const int64_t id_end = dense_id_end(idx);
+    SR_REQUIRE(n_bits == id_end, "sr_dense_search_grouped: the masks hold n_bits=%lld bits each, the index's document indices end at %lld",
+               (long long)n_bits, (long long)id_end);
+    const int64_t n_words = doc_mask_words(n_bits);
+    SR_REQUIRE(n_groups < (1ll << 32) && n_groups * n_words < (1ll << 32), "sr_dense_search_grouped: %lld groups of %lld words exceed 2^32 words",
+               (long long)n_groups, (long long)n_words);
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && d_query_group && (d_group_words || n_bits == 0), "sr_dense_search_grouped: null pointer");
+    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_grouped: queries must be 16-byte aligned");
+    StreamOrder::Scope in_order(idx->order, s);
+    // 1. the group ids: one read-back of 4 nq bytes
+    std::vector<int32_t> grp((size_t)nq);
+    SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    for (int64_t q = 0; q < nq; ++q)
+        if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
+            SR_TRY(grouped_pad_rows(d_out_scores, d_out_ids, nq, k, s));
+            sr_set_error("sr_dense_search_grouped: query %lld is in group %d, outside [0, %lld) (nothing was searched)", (long long)q,
+                         grp[(size_t)q], (long long)n_groups);
+            return SR_ERR_INVALID;
+        }
+    // 2. set bits per group, and the first set bit that names no document: one read-back of 8 (n_groups + 1) bytes
+    const uint32_t* d_valid = nullptr;
+    SR_TRY(grouped_valid_bitmap(idx, n_bits, &d_valid, s));
+    SR_TRY(dense_mask_scratch(idx->grp_counts, n_groups + 1, "sr_dense_search_grouped"));
+    SR_TRY(launch_doc_masks_check(d_group_words, n_groups, n_bits, d_valid, idx->grp_counts.p, s));
+    std::vector<int64_t> counts((size_t)n_groups + 1);
+    SR_CHECK_HIP(hipMemcpyAsync(counts.data(), idx->grp_counts.p, (size_t)(n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    if (counts[(size_t)n_groups] != -1) {
+        const uint64_t at = (uint64_t)counts[(size_t)n_groups];
+        const int64_t word = (int64_t)(at >> 5);
+        SR_TRY(grouped_pad_rows(d_out_scores, d_out_ids, nq, k, s));
+        sr_set_error("sr_dense_search_grouped: group %lld: mask bit %lld is set but names no document of the index (nothing was searched)",
+                     (long long)(word / n_words), (long long)((word % n_words) * 32 + (int64_t)(at & 31)));
+        return SR_ERR_INVALID;
+    }
+    // 3. the queries by group (a stable sort: ascending inside a group), the pairs a gather of everything would score
+    std::vector<int64_t> order((size_t)nq);
+    for (int64_t q = 0; q < nq; ++q) order[(size_t)q] = q;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return grp[(size_t)a] < grp[(size_t)b]; });
+    int64_t pairs = 0;
+    for (int64_t q = 0; q < nq; ++q) pairs += counts[(size_t)grp[(size_t)q]];
+    if (idx->ntotal > 0) SR_TRY(dense_pair_segs(idx, "sr_dense_search_grouped"));
+    SR_TRY(subset_status_begin(&idx->pair_status, s));    // the gather kernel reads it; the bitmaps have passed their own check
+    // runs of `sel` (positions of `order`, sorted by group) -> one gather search per group that has a query in it
+    auto gather_groups = [&](const std::vector<int64_t>& sel) -> int {
+        for (size_t i0 = 0; i0 < sel.size();) {
+            const int64_t g = grp[(size_t)sel[i0]];
+            size_t i1 = i0;
+            while (i1 < sel.size() && grp[(size_t)sel[i1]] == g) ++i1;
+            SR_TRY(grouped_gather_group(idx, d_queries, k, d_group_words + g * n_words, n_bits, counts[(size_t)g], sel.data() + i0, (int64_t)(i1 - i0),
+                                        d_out_scores, d_out_ids, s));
+            i0 = i1;
+        }
+        SR_CHECK_HIP(hipStreamSynchronize(s));            // `sel` (pageable host memory) is the source of asynchronous copies
+        return SR_OK;
+    };
+    int kp = 0;
+    bool pass_route = idx->precision == SR_PRECISION_FP32_FILTERED && grouped_dense_wants_pass(pairs);
+    if (pass_route) SR_TRY(dense_filter_applies(idx, nq, k, &kp, &pass_route, true));
+    if (pass_route) {
+        const int64_t nq_pad = ceil_div64(nq, 256) * 256;  // the pass's query tile: a lane beyond nq reads an offset of 0
+        SR_TRY(dense_mask_scratch(idx->grp_qoff, nq_pad, "sr_dense_search_grouped"));
+        SR_TRY(launch_doc_mask_query_offsets(d_query_group, nq, nq_pad, n_bits, idx->grp_qoff.p, s));
+        bool done = false;
+        SR_TRY(dense_filtered_candidates(idx, d_queries, nq, k, s, &done, d_group_words, idx->grp_qoff.p));
+        if (done) {
+            std::vector<int64_t> redo;                     // the queries without a certificate, ascending
+            SR_TRY(dense_filtered_finish(idx, d_queries, nq, k, nullptr, d_out_scores, d_out_ids, s, nullptr, 0, &redo));
+            if (redo.empty()) return SR_OK;
+            std::stable_sort(redo.begin(), redo.end(), [&](int64_t a, int64_t b) { return grp[(size_t)a] < grp[(size_t)b]; });
+            return gather_groups(redo);
+        }
+    }
+    return gather_groups(order);                          // the group loop (also: no room for the candidate lists)
 }

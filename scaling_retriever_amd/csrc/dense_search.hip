@@ -99,6 +99,7 @@ static int dense_pass_16bit(sr_dense_index* idx, const float* d_queries, int64_t
                 a.dxy = seg.fxy.p; a.qa = idx->qa.p; a.sd = seg.fsd; a.isd = seg.fisd;
                 a.dxy_gmax = seg.fxy.p + 2 * seg.n;
                 a.mask = opts.mask;
+                a.mask_qoff = opts.mask_qoff;
             } else {                  // (d plane, q plane), smallest products first: the last three are bf16x3's
                 a.n_pairs = np == 2 ? 3 : 6;
                 const int pd[6] = {2, 0, 1, 1, 0, 0}, pq[6] = {0, 2, 1, 0, 1, 0};
@@ -232,7 +233,7 @@ int dense_filter_applies(sr_dense_index* idx, int64_t nq, int k, int* kp_out, bo
 }
 
 int dense_filtered_candidates(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, hipStream_t s, bool* done,
-                              const uint32_t* d_mask) {
+                              const uint32_t* d_mask, const uint32_t* d_mask_qoff) {
     *done = false;
     int kp = 0;
     bool applies = false;
@@ -249,16 +250,32 @@ int dense_filtered_candidates(sr_dense_index* idx, const float* d_queries, int64
     }
     SR_CHECK_HIP(hipMemsetAsync(idx->flags.p, 0, (size_t)nq * 4, s));
     // 1. the kp documents with the largest upper bounds U (the query planes and constants are made by the pass)
-    const DensePassOpts opts{DenseArith::filter_upper_bound, /*tiled_only=*/false, /*k_inner=*/k, d_mask};
+    const DensePassOpts opts{DenseArith::filter_upper_bound, /*tiled_only=*/false, /*k_inner=*/k, d_mask, d_mask_qoff};
     SR_TRY(dense_search_pass(idx, d_queries, nq, kp, idx->a_scores.p, idx->a_ids.p, opts, s));
     *done = true;
     return SR_OK;
 }
 
+// the re-do buffers, sized for nf queries at this k (kept until a call needs more)
+int dense_redo_reserve(sr_dense_index* idx, int64_t nf, int k) {
+    if (idx->redo_cap >= nf && idx->redo_k == k) return SR_OK;
+    idx->redo_q.release(); idx->redo_idx.release(); idx->redo_scores.release(); idx->redo_ids.release();
+    idx->redo_cap = 0;
+    const int64_t cap = nf < 64 ? 64 : nf;
+    SR_TRY(idx->redo_q.reserve(cap * idx->dim, "dense search (re-do)"));
+    SR_TRY(idx->redo_idx.reserve(cap, "dense search (re-do)"));
+    SR_TRY(idx->redo_scores.reserve(cap * k, "dense search (re-do)"));
+    SR_TRY(idx->redo_ids.reserve(cap * k, "dense search (re-do)"));
+    idx->redo_cap = cap;
+    idx->redo_k = k;
+    return SR_OK;
+}
+
 // d_list: queries without a certificate are re-done by the gather kernel over that list, whose chains are the exact kernel's
-// (subset_search.hip): the same bits, no masked exact kernel.
+// (subset_search.hip): the same bits, no masked exact kernel.  redo_out: they are handed back instead (the grouped search re-does each
+// under its own group's list).
 int dense_filtered_finish(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const float* d_thr, float* d_out_scores,
-                          int64_t* d_out_ids, hipStream_t s, const int64_t* d_list, int64_t m) {
+                          int64_t* d_out_ids, hipStream_t s, const int64_t* d_list, int64_t m, std::vector<int64_t>* redo_out) {
     const int kp = idx->fkp;
     int* const flags = idx->flags.p;
     FilterSegs fs;
@@ -284,21 +301,12 @@ int dense_filtered_finish(sr_dense_index* idx, const float* d_queries, int64_t n
     idx->nq_redone += nf;
     if (nf == 0) { ++idx->n_filtered; return SR_OK; }
     ++idx->n_fallback;
+    if (redo_out) { redo_out->swap(redo); return SR_OK; }     // grouped search: every query is re-done under its own group's list
     if (nf * 2 > nq) {                                         // most of the batch: redo all of it in place
         if (d_list) return dense_subset_gather(idx, d_queries, nq, k, d_list, m, d_out_scores, d_out_ids, s, "dense search (masked)");
         return dense_search_pass(idx, d_queries, nq, k, d_out_scores, d_out_ids, DensePassOpts{}, s);
     }
-    if (idx->redo_cap < nf || idx->redo_k != k) {
-        idx->redo_q.release(); idx->redo_idx.release(); idx->redo_scores.release(); idx->redo_ids.release();
-        idx->redo_cap = 0;
-        const int64_t cap = nf < 64 ? 64 : nf;
-        SR_TRY(idx->redo_q.reserve(cap * idx->dim, "dense search (re-do)"));
-        SR_TRY(idx->redo_idx.reserve(cap, "dense search (re-do)"));
-        SR_TRY(idx->redo_scores.reserve(cap * k, "dense search (re-do)"));
-        SR_TRY(idx->redo_ids.reserve(cap * k, "dense search (re-do)"));
-        idx->redo_cap = cap;
-        idx->redo_k = k;
-    }
+    SR_TRY(dense_redo_reserve(idx, nf, k));
     SR_CHECK_HIP(hipMemcpyAsync(idx->redo_idx.p, redo.data(), (size_t)nf * 8, hipMemcpyHostToDevice, s));
     SR_TRY(launch_filter_gather_rows(d_queries, idx->redo_idx.p, nf, idx->dim, idx->redo_q.p, false, s));
     // the tiled kernels whatever the count: one k order for the whole batch (the streaming kernel accumulates in another)

@@ -33,9 +33,14 @@ struct DenseSplitArgs {
     // upper_bound only (sr_dense_search_masked / _subset, mask route): bit (g & 31) of word g >> 5 says whether the document with global
     // index g = id_base + row * id_stride may become a key; null = every document may (the unmasked instantiation)
     const uint32_t* mask;
+    // with mask (sr_dense_search_grouped): [nq rounded up to the query tile] the word offset of every query's own bitmap inside mask,
+    // group * ceil(id_end / 32), computed once per call; null = one bitmap for all queries
+    const uint32_t* mask_qoff;
 };
 // p1 and p2 may be null (fewer planes)
 int launch_split_bf16(const float* src, unsigned short* p0, unsigned short* p1, unsigned short* p2, int64_t n_elems, hipStream_t s);
 int launch_dense_split(const DenseSplitArgs& a, hipStream_t s);
 // dense_split_kernel<true, true> (dense_split_masked.hip); called by launch_dense_split with the grid fields filled in
 int launch_dense_split_masked(const DenseSplitArgs& a, unsigned grid, size_t lds, hipStream_t s);
+// dense_split_kernel<true, true, true> (dense_split_grouped.hip): the same under a bitmap per query (a.mask_qoff)
+int launch_dense_split_grouped(const DenseSplitArgs& a, unsigned grid, size_t lds, hipStream_t s);

@@ -90,6 +90,7 @@ int launch_dense_split(const DenseSplitArgs& a, hipStream_t s) {
     SR_REQUIRE(a.n_pairs >= 1 && a.n_pairs <= 6 && a.n_pairs * (a.H / 64) >= 2, "dense_split: bad plane-pair count %d", a.n_pairs);
     SR_REQUIRE(!a.upper_bound || (a.n_pairs == 1 && a.dxy && a.qa), "dense_split: the upper-bound pass is one plane product");
     SR_REQUIRE(!a.mask || a.upper_bound, "dense_split: a document mask goes with the upper-bound pass only");
+    SR_REQUIRE(!a.mask_qoff || a.mask, "dense_split: per-query mask offsets without a mask");
     constexpr size_t lds = 2 * (size_t)(SP_BN + SP_BM) * 128 + SP_BN * 2 * sizeof(float) + SP_BM * 4 * sizeof(float) + SP_BM * sizeof(float);
     static DeviceOnce attr_once;
     bool* attr_slot = attr_once.pending();
@@ -133,6 +134,7 @@ int launch_dense_split(const DenseSplitArgs& a, hipStream_t s) {
     if (wgs < 8) wgs = 8;
     if (const char* e = sr_dev_getenv("SR_SPLIT_PERSIST")) if (atoi(e) == 0) wgs = sg.total;
     const dim3 grid((unsigned)(sg.total < wgs ? sg.total : wgs));
+    if (a.mask_qoff) return launch_dense_split_grouped(b, grid.x, lds, s); // dense_split_grouped.hip: a bitmap per query
     if (a.mask) return launch_dense_split_masked(b, grid.x, lds, s);       // dense_split_masked.hip: the instantiation of an object of its own
     if (a.upper_bound) hipLaunchKernelGGL((dense_split_kernel<true, false>), grid, dim3(512), lds, s, b);
     else hipLaunchKernelGGL((dense_split_kernel<false, false>), grid, dim3(512), lds, s, b);

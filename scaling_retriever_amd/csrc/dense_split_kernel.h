@@ -1,5 +1,6 @@
 // The split-plane score kernel itself (dense_split.hip has the text): epilogue, tile mapping and the persistent k-loop, as a header so that
-// the certified filter's masked instantiation (dense_split_masked.hip) is built from the same source in an object of its own.
+// the certified filter's masked instantiations (dense_split_masked.hip: one bitmap; dense_split_grouped.hip: a bitmap per query) are built
+// from the same source in objects of their own.
 #pragma once
 #include "dense_split.h"
 
@@ -39,13 +40,20 @@ __device__ __forceinline__ f32x4 split_mma(const mfma_bf16x8& w, const mfma_bf16
 // predicate below, so the three agree.  The block test and the bounds are untouched: a masked-out document may pass the block test,
 // it just never becomes a key.  Soundness: every quantity the filter builds from keys (tau, the second threshold, the certificate)
 // is then a quantity over the allowed documents alone, and the argument of dense_filter.h holds for that set word for word.
-template <bool MASKED>
-__device__ __forceinline__ bool split_doc_allowed(const DenseSplitArgs& a, uint32_t gid) {
-    if constexpr (MASKED) return ((a.mask[gid >> 5] >> (gid & 31u)) & 1u) != 0;
+// GROUPED (MASKED only, sr_dense_search_grouped): the bit is read from the QUERY's own bitmap, a.mask + a.mask_qoff[q] words.  The offset is
+// loaded here, in the survivor branch, next to the word it leads to - carried across the epilogue it would be four more registers per
+// lane in a kernel that has none to spare (see split_epilogue on what hoisting does to it).  The lanes of a row group are 16 queries,
+// so the word is no longer shared among them; the branch stays as rare as it was.  Everything the filter builds from a query's keys is
+// a quantity over that query's allowed documents, which is all the argument of dense_filter.h asks for.  A lane with q >= nq has
+// tau = +inf and never gets here (the offsets are padded to the query tile all the same: dense_restrict.hip).
+template <bool MASKED, bool GROUPED>
+__device__ __forceinline__ bool split_doc_allowed(const DenseSplitArgs& a, uint32_t gid, int q) {
+    if constexpr (GROUPED) return ((a.mask[(size_t)a.mask_qoff[q] + (gid >> 5)] >> (gid & 31u)) & 1u) != 0;
+    else if constexpr (MASKED) return ((a.mask[gid >> 5] >> (gid & 31u)) & 1u) != 0;
     else return true;
 }
 
-template <bool UB, bool MASKED, int NB, int MB>
+template <bool UB, bool MASKED, bool GROUPED, int NB, int MB>
 __device__ __forceinline__ void split_epilogue(const DenseSplitArgs& a, f32x4 (&acc)[NB][MB], int64_t row0, int q0, int wn, int wm,
                                                int frow, int fg, const float* xy_s, const float* qa_s, const float* tau_s, float gx, float gy) {
 #pragma clang fp contract(off)
@@ -143,7 +151,7 @@ __device__ __forceinline__ void split_epilogue(const DenseSplitArgs& a, f32x4 (&
             for (int r = 0; r < 4; ++r) {
                 const float sc = acc[i][j][r];
                 if constexpr (MASKED) {
-                    if (lr0 + r < rows_valid && sc >= tq[j] && split_doc_allowed<true>(a, gid0 + (uint32_t)(lr0 + r) * a.id_stride)) {
+                    if (lr0 + r < rows_valid && sc >= tq[j] && split_doc_allowed<true, GROUPED>(a, gid0 + (uint32_t)(lr0 + r) * a.id_stride, q)) {
                         if (seg_ok && n < SR_SEG_P) seg_dst[n] = sr_make_key(sc * out_scale[j], gid0 + (uint32_t)(lr0 + r) * a.id_stride);
                         ++n;
                     }
@@ -173,7 +181,7 @@ __device__ __forceinline__ void split_epilogue(const DenseSplitArgs& a, f32x4 (&
                 for (int r = 0; r < 4; ++r) {
                     const int lr = wn * NB * 16 + i * 16 + fg * 4 + r;
                     if constexpr (MASKED)
-                        cnt += (lr < rows_valid && acc[i][j][r] >= tq[j] && split_doc_allowed<true>(a, gid0 + (uint32_t)lr * a.id_stride)) ? 1 : 0;
+                        cnt += (lr < rows_valid && acc[i][j][r] >= tq[j] && split_doc_allowed<true, GROUPED>(a, gid0 + (uint32_t)lr * a.id_stride, q)) ? 1 : 0;
                     else
                     cnt += (lr < rows_valid && acc[i][j][r] >= tq[j]) ? 1 : 0;
                 }
@@ -189,7 +197,7 @@ __device__ __forceinline__ void split_epilogue(const DenseSplitArgs& a, f32x4 (&
                 const int lr = wn * NB * 16 + i * 16 + fg * 4 + r;
                 const float sc = acc[i][j][r];
                 if constexpr (MASKED) {
-                    if (lr < rows_valid && sc >= tq[j] && split_doc_allowed<true>(a, gid0 + (uint32_t)lr * a.id_stride)) {
+                    if (lr < rows_valid && sc >= tq[j] && split_doc_allowed<true, GROUPED>(a, gid0 + (uint32_t)lr * a.id_stride, q)) {
                         if (p < limit) dst[p] = sr_make_key(sc * out_scale[j], gid0 + (uint32_t)lr * a.id_stride);
                         ++p;
                     }
@@ -220,9 +228,10 @@ __device__ __forceinline__ bool split_tile_of(const DenseSplitArgs& a, int lin, 
 // Persistent workgroups: the LDS-DMA of the NEXT tile's first two k-steps is issued during the last two k-steps of the
 // current one (the stages they free), so a tile's prologue latency and most of its epilogue hide behind the neighbour
 // tile's transfers; at K = 2048 a tile lives only 32 k-steps, and an exposed prologue + epilogue per tile was ~10 % of it.
-template <bool UB, bool MASKED>
+template <bool UB, bool MASKED, bool GROUPED = false>
 __global__ __launch_bounds__(512, 2) void dense_split_kernel(DenseSplitArgs a) {
     static_assert(UB || !MASKED, "a document mask goes with the upper-bound pass only");
+    static_assert(MASKED || !GROUPED, "per-query bitmaps are a kind of document mask");
     constexpr int NB = 8, MB = 4, WAVES_M = 4, HB = NB / 2;   // wave tile: 128 docs x 64 queries
     constexpr int W_BYTES = SP_BN * 128, STAGE_BYTES = (SP_BN + SP_BM) * 128;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -462,7 +471,7 @@ __global__ __launch_bounds__(512, 2) void dense_split_kernel(DenseSplitArgs a) {
             buf ^= 1;
         }
         const unsigned long long st1 = SR_SPLIT_STAMPS_PTR(a) ? __builtin_amdgcn_s_memrealtime() : 0;
-        split_epilogue<UB, MASKED, NB, MB>(a, acc, row0, q0, wn, wm, frow, fg, xy_s, qa_s, tau_s, gx, gy);
+        split_epilogue<UB, MASKED, GROUPED, NB, MB>(a, acc, row0, q0, wn, wm, frow, fg, xy_s, qa_s, tau_s, gx, gy);
         if (SR_SPLIT_STAMPS_PTR(a)) {          // dev switch SR_SPLIT_STAMPS: 10 ns ticks per tile of wave 0: k-loop, epilogue issue, wait at the next tile's top
             const unsigned long long st2 = __builtin_amdgcn_s_memrealtime();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -20,3 +20,14 @@ int launch_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t* d_word
 // Bits of the last word at or beyond n_bits are ignored.
 int launch_doc_mask_count(const uint32_t* d_words, int64_t n_bits, int64_t* d_blocks, int64_t* d_count, hipStream_t s);
 int launch_doc_mask_expand(const uint32_t* d_words, int64_t n_bits, const int64_t* d_blocks, int64_t* d_list, int64_t capacity, hipStream_t s);
+
+// ---- filter groups (sr_dense_search_grouped): n_groups bitmaps stacked as [n_groups, W], W = doc_mask_words(n_bits) ----
+// d_valid [W] |= the positions id_base + r * id_stride, r < n, of one segment (those below n_bits; the caller has zeroed the words)
+int launch_doc_mask_add_segment(uint32_t* d_valid, int64_t n_bits, int64_t n, int64_t id_base, int64_t id_stride, hipStream_t s);
+// One word-parallel pass over all groups: d_counts[g] := the set bits of group g below n_bits; d_counts[n_groups] := the smallest
+// (g * W + word) * 32 + bit over the set bits below n_bits that are not set in d_valid, ~0 if there is none (d_valid null: every
+// position names a document, nothing is tested).  n_groups * W < 2^32.
+int launch_doc_masks_check(const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits, const uint32_t* d_valid, int64_t* d_counts,
+                           hipStream_t s);
+// d_qoff[q] := d_query_group[q] * W for q < nq (group ids already checked), 0 for nq <= q < nq_pad
+int launch_doc_mask_query_offsets(const int32_t* d_query_group, int64_t nq, int64_t nq_pad, int64_t n_bits, uint32_t* d_qoff, hipStream_t s);

@@ -2,6 +2,7 @@
 // ordered expand.  The reference has no counterpart (DenseFlatIndexer.search_knn, scaling_retriever/indexer.py:191-217, always ranks
 // the whole index); the bitmap is the form faiss offers as IDSelectorBitmap.  sr_dense_search_masked / _subset (dense_restrict.hip) hold
 // both forms of a filter: the bitmap feeds the certified filter's masked pass (dense_split_kernel.h), the list the gather kernel.
+// At the end of the file: the kernels of the grouped search (sr_dense_search_grouped) - stacked bitmaps checked and counted in one pass.
 #include "doc_mask.h"
 
 #define DM_THREADS 256
@@ -185,6 +186,71 @@ extern "C" int sr_doc_mask_remap(const uint32_t* d_src_words, int64_t n_src_bits
     if (n_dst_bits == 0) return SR_OK;
     hipLaunchKernelGGL(doc_mask_remap_kernel, dim3((unsigned)ceil_div64(doc_mask_words(n_dst_bits), DM_THREADS)), dim3(DM_THREADS), 0,
                        (hipStream_t)stream, d_src_words, n_src_bits, d_map, n_dst_bits, d_dst_words);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+// ---- filter groups (sr_dense_search_grouped) ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DM_THREADS) void doc_mask_add_segment_kernel(uint32_t* __restrict__ valid, int64_t n_bits, int64_t n, int64_t id_base,
+                                                                           int64_t id_stride) {
+    for (int64_t r = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x; r < n; r += (int64_t)gridDim.x * DM_THREADS) {
+        const int64_t id = id_base + r * id_stride;
+        if (id >= 0 && id < n_bits) atomicOr(&valid[id >> 5], 1u << (unsigned)(id & 31));     // never a write outside the words
+    }
+}
+
+int launch_doc_mask_add_segment(uint32_t* d_valid, int64_t n_bits, int64_t n, int64_t id_base, int64_t id_stride, hipStream_t s) {
+    if (n <= 0 || n_bits <= 0) return SR_OK;
+    int64_t blocks = ceil_div64(n, DM_THREADS);
+    if (blocks > (1 << 20)) blocks = 1 << 20;             // the rest by the grid stride
+    hipLaunchKernelGGL(doc_mask_add_segment_kernel, dim3((unsigned)blocks), dim3(DM_THREADS), 0, s, d_valid, n_bits, n, id_base, id_stride);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+// blockIdx.x: 256 words of a bitmap; blockIdx.y, strided: the groups.  counts[g] += the workgroup's set bits; counts[n_groups] = the
+// smallest (g * n_words + w) * 32 + bit among the set bits that `valid` does not have
+__global__ __launch_bounds__(DM_THREADS) void doc_masks_check_kernel(const uint32_t* __restrict__ words, int64_t n_groups, int64_t n_words,
+                                                                      int64_t n_bits, const uint32_t* __restrict__ valid,
+                                                                      unsigned long long* __restrict__ counts) {
+    __shared__ int wave_tot[DM_THREADS / 64];
+    const int64_t w = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    const uint32_t ok = (valid && w < n_words) ? valid[w] : ~0u;
+    for (int64_t g = blockIdx.y; g < n_groups; g += gridDim.y) {
+        const uint32_t v = doc_mask_word(words + g * n_words, w, n_words, n_bits);
+        int total;
+        (void)doc_mask_block_scan(__popc(v), wave_tot, &total);
+        if (threadIdx.x == 0 && total) atomicAdd(&counts[g], (unsigned long long)total);
+        const uint32_t off = v & ~ok;
+        if (off) atomicMin(&counts[n_groups], ((unsigned long long)(g * n_words + w) << 5) + (unsigned)(__ffs((int)off) - 1));
+    }
+}
+
+int launch_doc_masks_check(const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits, const uint32_t* d_valid, int64_t* d_counts,
+                           hipStream_t s) {
+    SR_CHECK_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_groups * 8, s));
+    SR_CHECK_HIP(hipMemsetAsync(d_counts + n_groups, 0xff, 8, s));
+    if (n_bits == 0) return SR_OK;
+    const int64_t n_words = doc_mask_words(n_bits), gx = ceil_div64(n_words, DM_THREADS);
+    int64_t gy = n_groups < 65535 ? n_groups : 65535;     // a launch carries fewer than 2^31 threads; the other groups by the stride
+    if (gy > (1ll << 31) / (gx * DM_THREADS)) gy = (1ll << 31) / (gx * DM_THREADS);
+    if (gy < 1) gy = 1;
+    hipLaunchKernelGGL(doc_masks_check_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(DM_THREADS), 0, s, d_group_words, n_groups, n_words, n_bits,
+                       d_valid, reinterpret_cast<unsigned long long*>(d_counts));
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+__global__ void doc_mask_query_offsets_kernel(const int32_t* __restrict__ query_group, int64_t nq, int64_t nq_pad, uint32_t n_words,
+                                              uint32_t* __restrict__ qoff) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nq_pad) qoff[q] = q < nq ? (uint32_t)query_group[q] * n_words : 0u;
+}
+
+int launch_doc_mask_query_offsets(const int32_t* d_query_group, int64_t nq, int64_t nq_pad, int64_t n_bits, uint32_t* d_qoff, hipStream_t s) {
+    if (nq_pad == 0) return SR_OK;
+    hipLaunchKernelGGL(doc_mask_query_offsets_kernel, dim3((unsigned)ceil_div64(nq_pad, DM_THREADS)), dim3(DM_THREADS), 0, s, d_query_group, nq,
+                       nq_pad, (uint32_t)doc_mask_words(n_bits), d_qoff);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }

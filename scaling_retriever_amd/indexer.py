@@ -312,26 +312,53 @@ class DenseFlatIndexer(DenseIndexer):
             raise ValueError(f"allowed_mask must hold one flag per index position ({self.index.id_end}), got {tuple(flags.shape)}")
         return pack_doc_mask(flags.to(device=self.index.device, dtype=torch.bool))
 
-    def search_knn(self, query_reps, top_docs: int, allowed_ids=None, allowed_mask=None):
+    def allowed_group_words(self, allowed_masks, query_group):
+        """allowed_masks bool [G, index positions] and query_group int [nq] (both or neither) -> (packed bitmaps int32 [G, W] on the
+        index's device, group ids int64 on the device), packed once per call (scoring.pack_doc_masks)."""
+        from .scoring import pack_doc_masks
+        flags = allowed_masks if isinstance(allowed_masks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allowed_masks, dtype=bool))
+        if flags.dim() != 2 or flags.shape[0] < 1 or flags.shape[1] != self.index.id_end:
+            raise ValueError(f"allowed_masks must hold one row of flags per group, one flag per index position ({self.index.id_end}), got "
+                             f"{tuple(flags.shape)}")
+        groups = query_group if isinstance(query_group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(query_group))
+        if groups.dim() != 1 or groups.dtype.is_floating_point or groups.dtype == torch.bool:
+            raise ValueError(f"query_group must hold one integer group id per query, got {groups.dtype} {tuple(groups.shape)}")
+        return pack_doc_masks(flags.to(torch.bool), self.index.device), groups.to(device=self.index.device, dtype=torch.int64)
+
+    @staticmethod
+    def _check_filters(who, allowed_ids, allowed_mask, allowed_masks, query_group):
+        """The argument rules of the filtered searches, checked before anything is uploaded."""
+        if allowed_ids is not None and allowed_mask is not None:
+            raise ValueError(f"{who}: pass allowed_ids or allowed_mask, not both")
+        if (allowed_masks is not None or query_group is not None) and (allowed_ids is not None or allowed_mask is not None):
+            raise ValueError(f"{who}: pass allowed_masks / query_group or one filter for all queries (allowed_ids, allowed_mask), not both")
+        if (allowed_masks is None) != (query_group is None):
+            raise ValueError(f"{who}: allowed_masks and query_group go together (one bitmap per group, one group id per query)")
+
+    def search_knn(self, query_reps, top_docs: int, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
         """indexer.py:210-214: (list of db-id lists, fp32 scores [nq, k]); label -1 (fewer than k vectors) -> None.  allowed_ids (None:
         the whole index): database ids, any order, duplicates allowed - only these documents are ranked (DenseIndexHIP.search, subset).
         allowed_mask: the same filter as a boolean array over index positions (DenseIndexHIP.search, mask); not both.
+        allowed_masks bool [G, index positions] with query_group int [nq]: a filter per query - query q is ranked within the documents of
+        allowed_masks[query_group[q]] (DenseIndexHIP.search_grouped); not together with a filter for all queries.
         The lists come
         from id_lists (csrc/host_lists.c).  A large query set is searched in KNN_CHUNKS pieces, the GPU working on piece c + 1 (in a
         worker thread: the C call releases the GIL) while this thread builds the lists of piece c - the exact results do not depend
         on how the queries are batched (pieces stay above 64 queries: one kernel family, one k order)."""
+        self._check_filters("search_knn", allowed_ids, allowed_mask, allowed_masks, query_group)
         if isinstance(query_reps, torch.Tensor):
             q = query_reps.to(device=self.index.device, dtype=torch.float32)
         else:
             q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
         nq = q.shape[0]
-        if allowed_ids is not None and allowed_mask is not None:
-            raise ValueError("search_knn: pass allowed_ids or allowed_mask, not both")
         subset = None if allowed_ids is None else self.allowed_subset(allowed_ids)
         mask = None if allowed_mask is None else self.allowed_mask_words(allowed_mask)
+        groups = None if allowed_masks is None else self.allowed_group_words(allowed_masks, query_group)
+        if groups is not None and groups[1].numel() != nq:
+            raise ValueError(f"search_knn: query_group must hold one group id per query ({nq}), got {groups[1].numel()}")
         n_chunks = self.KNN_CHUNKS if nq >= 1024 else 1
         if n_chunks == 1:
-            scores, indexes = self.search_arrays(q, top_docs, _subset=subset, _mask=mask)
+            scores, indexes = self.search_arrays(q, top_docs, _subset=subset, _mask=mask, _groups=groups)
             return self.id_lists(indexes), scores
         from concurrent.futures import ThreadPoolExecutor
         per = (nq + n_chunks - 1) // n_chunks
@@ -343,7 +370,8 @@ class DenseFlatIndexer(DenseIndexer):
         def gpu(c):
             with torch.cuda.device(dev):
                 torch.cuda.current_stream(dev).wait_event(ready)          # the worker thread's current stream is the default one
-                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs, _subset=subset, _mask=mask)
+                part = None if groups is None else (groups[0], groups[1][bounds[c][0]:bounds[c][1]])
+                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs, _subset=subset, _mask=mask, _groups=part)
         top_doc_ids, score_parts = [], []
         with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(gpu, 0)
@@ -355,20 +383,26 @@ class DenseFlatIndexer(DenseIndexer):
                 score_parts.append(scores)
         return top_doc_ids, np.concatenate(score_parts)
 
-    def search_arrays(self, query_reps, top_docs: int, allowed_ids=None, _subset=None, allowed_mask=None, _mask=None):
+    def search_arrays(self, query_reps, top_docs: int, allowed_ids=None, _subset=None, allowed_mask=None, _mask=None, allowed_masks=None,
+                      query_group=None, _groups=None):
         """(scores fp32 [nq, k], index positions int64 [nq, k]; -1 = fewer than k vectors) as host arrays: what search_knn maps
-        to db ids, and what the run.json writer takes as they are (utils/run_file.py).  allowed_ids / allowed_mask as for search_knn
-        (_subset: the positions, already on the device; _mask: the packed bitmap, already on the device)."""
-        if allowed_ids is not None and allowed_mask is not None:
-            raise ValueError("search_arrays: pass allowed_ids or allowed_mask, not both")
+        to db ids, and what the run.json writer takes as they are (utils/run_file.py).  allowed_ids / allowed_mask / allowed_masks with
+        query_group as for search_knn (_subset: the positions, already on the device; _mask: the packed bitmap, already on the device;
+        _groups: the packed bitmaps and the group ids, already on the device)."""
+        self._check_filters("search_arrays", allowed_ids, allowed_mask, allowed_masks, query_group)
         if allowed_ids is not None:
             _subset = self.allowed_subset(allowed_ids)
         if allowed_mask is not None:
             _mask = self.allowed_mask_words(allowed_mask)
+        if allowed_masks is not None:
+            _groups = self.allowed_group_words(allowed_masks, query_group)
         if isinstance(query_reps, torch.Tensor):
             q = query_reps.to(device=self.index.device, dtype=torch.float32)
         else:
             q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
+        if _groups is not None:
+            scores, indexes = self.index.search_grouped(q, top_docs, _groups[0], _groups[1])
+            return to_host(scores), to_host(indexes)
         scores, indexes = self.index.search(q, top_docs, subset=_subset, mask=_mask)
         return to_host(scores), to_host(indexes)
 

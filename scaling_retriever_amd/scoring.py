@@ -77,6 +77,68 @@ def pack_doc_mask(allowed):
     return raw.view("<u4").astype(np.uint32)                              # little-endian words: bit i & 31 of word i >> 5
 
 
+def pack_doc_masks(flags, device=None):
+    """A bool [G, n_bits] tensor or array -> the stacked bitmaps the grouped search takes (include/sr_hip.h sr_dense_search_grouped): int32
+    [G, ceil(n_bits / 32)], row g = pack_doc_mask(flags[g]).  Packed on `device` (None: where a tensor lives; an array on the host), a
+    few rows at a time, so the unpacked intermediate stays at 256 MB however many groups there are."""
+    if not torch.is_tensor(flags):
+        flags = torch.from_numpy(np.ascontiguousarray(np.asarray(flags), dtype=bool))
+    if flags.dim() != 2:
+        raise ValueError(f"expected a 2-D boolean [groups, n_bits] mask, got {tuple(flags.shape)}")
+    if flags.dtype != torch.bool:
+        raise ValueError(f"expected a boolean [groups, n_bits] mask, got {flags.dtype}")
+    device = flags.device if device is None else torch.device(device)
+    n_groups, n = flags.shape
+    n_words = (n + 31) // 32
+    out = torch.empty((n_groups, n_words), dtype=torch.int32, device=device)
+    if n_words == 0:
+        return out
+    weights = torch.ones(32, dtype=torch.int64, device=device) << torch.arange(32, dtype=torch.int64, device=device)
+    rows = max(1, (1 << 25) // (32 * n_words))
+    for g0 in range(0, n_groups, rows):
+        part = flags[g0:g0 + rows].to(device)
+        bits = torch.zeros((part.shape[0], 32 * n_words), dtype=torch.int64, device=device)
+        bits[:, :n] = part
+        out[g0:g0 + rows] = (bits.view(part.shape[0], n_words, 32) * weights).sum(dim=2).to(torch.int32)   # keeps the low 32 bits
+    return out
+
+
+def _group_masks_argument(masks, n_bits_of, what):
+    """The checks of a grouped search's `masks` that need no device: (packed, masks as tensor / array, G).  Packed words are verified
+    against the word count of n_bits_of() (`what` names it in the message)."""
+    if not torch.is_tensor(masks) and not isinstance(masks, np.ndarray):
+        masks = np.asarray(masks)
+    packed = (isinstance(masks, np.ndarray) and masks.dtype in (np.uint32, np.int32)) or \
+        (torch.is_tensor(masks) and masks.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
+    if not packed:
+        is_bool = (isinstance(masks, np.ndarray) and masks.dtype == np.bool_) or (torch.is_tensor(masks) and masks.dtype == torch.bool)
+        if not is_bool:
+            raise ValueError("masks must be a bool [groups, n_bits] tensor / array, or packed int32 / uint32 words [groups, words] "
+                             f"(pack_doc_masks), got {getattr(masks, 'dtype', type(masks).__name__)}")
+    if (masks.dim() if torch.is_tensor(masks) else masks.ndim) != 2:
+        raise ValueError(f"expected 2-D masks [groups, ...], got {tuple(masks.shape)}")
+    if masks.shape[0] < 1:
+        raise ValueError("masks must hold at least one group")
+    if packed:
+        n_bits = int(n_bits_of())
+        if masks.shape[1] != (n_bits + 31) // 32:
+            raise ValueError(f"a packed mask of this index holds {(n_bits + 31) // 32} words ({what} = {n_bits}), got {masks.shape[1]}")
+    return packed, masks, int(masks.shape[0])
+
+
+def _query_group_argument(query_group, nq, n_groups):
+    """query_group as given -> an int array / tensor of nq entries, checked without a device (the library checks the range)."""
+    if not torch.is_tensor(query_group) and not isinstance(query_group, np.ndarray):
+        query_group = np.asarray(query_group)
+    is_int = (not query_group.dtype.is_floating_point and not query_group.dtype.is_complex and query_group.dtype != torch.bool) \
+        if torch.is_tensor(query_group) else query_group.dtype.kind in "iu"
+    if not is_int:
+        raise ValueError(f"query_group must hold integer group ids, got {query_group.dtype}")
+    if (query_group.dim() if torch.is_tensor(query_group) else query_group.ndim) != 1 or query_group.shape[0] != nq:
+        raise ValueError(f"query_group must hold one group id per query ({nq}), got {tuple(query_group.shape)}")
+    return query_group
+
+
 def doc_mask_from_list(ids, n_bits, device=None):
     """Document indices (int64, any order, repeats allowed; tensor / array / list) -> the bitmap over [0, n_bits) as int32 words on the
     device (sr_doc_mask_from_list).  An entry outside [0, n_bits): ValueError."""
@@ -488,6 +550,43 @@ class DenseIndexHIP:
         with torch.cuda.device(self.device):      # the library allocates its workspace on the current device
             _lib.check(self.lib.sr_dense_search(self._h, _ptr(queries), nq, int(k), _ptr(scores), _ptr(ids),
                                                 _lib.stream_ptr()), "sr_dense_search")
+        return scores, ids
+
+    def search_grouped(self, queries, k, masks, query_group):
+        """Top-k of every query within its own group's documents (include/sr_hip.h sr_dense_search_grouped).  masks: one bitmap per group
+        over [0, id_end) - bool [G, id_end] (tensor / array, packed on the device) or int32 / uint32 words [G, ceil(id_end / 32)] already
+        packed (pack_doc_masks); query_group: int array / tensor [nq], query q searches under masks[query_group[q]].  The rows of a
+        group's queries are exactly what search(those queries, k, mask=masks[g]) returns.  1 <= k <= sr_max_topk().  Wrong shapes, a wrong
+        word count, a length mismatch or non-integer groups: ValueError before anything is uploaded; a group id outside [0, G) or a set
+        bit that names no document: ValueError naming the query / the (group, bit), every row of the result is then padding."""
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
+        nq = queries.shape[0]
+        packed, masks, n_groups = _group_masks_argument(masks, lambda: self.id_end, "id_end")
+        query_group = _query_group_argument(query_group, nq, n_groups)
+        if not queries.is_cuda:
+            raise ValueError("queries must be a cuda tensor")
+        if queries.device != self.device:
+            raise ValueError(f"queries live on {queries.device}, the index on {self.device}")
+        queries = queries.contiguous()
+        if packed:
+            n_bits = self.id_end
+            if isinstance(masks, np.ndarray):
+                masks = torch.from_numpy(np.ascontiguousarray(masks).view(np.int32))
+            elif masks.dtype != torch.int32:
+                masks = masks.view(torch.int32)
+            words = masks.to(self.device).contiguous()
+        else:
+            n_bits = int(masks.shape[1])              # the library compares it with id_end
+            words = pack_doc_masks(masks, self.device)
+        # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
+        groups = _to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sr_dense_search_grouped(self._h, _ptr(queries), nq, int(k), _ptr(_valid(words)), n_groups, n_bits,
+                                                        _ptr(_valid(groups)), _ptr(scores), _ptr(ids), _lib.stream_ptr()),
+                       "sr_dense_search_grouped")
         return scores, ids
 
     def _range_mask(self, mask):
