@@ -494,6 +494,24 @@ int sr_sparse_index_cert_stats(sr_sparse_index* idx, int64_t* out8);
  * true_fix (1 - dd) - 1.2 - 2.03 * left out <= key <= true_fix (1 + dd) + 1.2 + 1.01 * rare terms.                          */
 int sr_sparse_index_cert_debug(sr_sparse_index* idx, int enable, uint16_t* h_keys, int64_t keys_capacity,
                                float* h_consts, int64_t nq_pad, float* vscale, int32_t* T);
+/* Test-only hook: one of the certified scorer's buffers copied to the host as it stands (tests/test_sparse_cert_kernels_gpu.py,
+ * tests/sparse_cert_cases.py hold the numpy models they are compared with).  It launches no kernel and changes none: one
+ * hipDeviceSynchronize and one device-to-host copy per call, nothing when it is not called.  *n_bytes = the buffer's size; h_dst NULL:
+ * the size only, otherwise capacity_bytes must hold it.  what:
+ *   0  int64 [12] = {T, k-steps KS, doc tiles, e_stride, terms V, docs N, postings nnz, queries / padded queries (to 32) / k / k + band
+ *      of the last search (k + band = 0: its plan found no query for the fast path), the bits of fp32 vscale}
+ *   index side, built once:  1 dslot int32 [V] (dense slot, -1 = rare)   2 vmax fp32 [V]   3 d16 fp16 [tiles][32][KS][64][8] (MFMA A
+ *      fragments)   4 P uint32 [nnz + 4] (packed postings, four zero words behind them)   5 S uint32 [V][tiles + 1]
+ *      6 E uint32 [V][e_stride]   7 fwd_indptr int64 [N + 1]   8 fwd_tv uint64 [nnz] (term << 32 | value bits, terms ascending per doc)
+ *   the last search's plan, [nq_pad] rows:  9 bfrag fp16 [nq_pad / 32][KS][64][8]   10 rare_term int32 [nq_pad][256] (-1 = none)
+ *      11 rare_w fp32 [nq_pad][256]   12 elig uint8   13 c_q fp32   14 s_q fp32   15 rare terms in stage 1 int32   16 query terms int32
+ *      17 rare terms left out int32
+ *   the last search's certificate:  18 m_count int32 [nq_pad] (candidates re-scored, 0 = not certified)   19 ap_ids int64
+ *      [nq_pad][2 (k + band)] (their doc indices, the first m_count of a row, in no order)   20 uint8 [nq] the flags of the queries the
+ *      pass handed to the exact kernels (kept only while sr_sparse_index_cert_debug's recording is on)
+ * A search larger than one scorer batch (8 192 queries) or one that retried a sub-batch leaves the LAST pass's plan and certificate.
+ * SR_ERR_INVALID: no scorer on this index, an unknown `what`, a plan / certificate buffer before any search, a buffer too small.      */
+int sr_sparse_index_cert_readout(sr_sparse_index* idx, int what, void* h_dst, int64_t capacity_bytes, int64_t* n_bytes);
 
 /* On-device index build: doc-major postings -> CSR by term.  Replaces the per-posting Python append of
  * IndexDictOfArray.add_batch_document (scaling_retriever/utils/inverted_index.py:67-76) and the per-term concatenation of

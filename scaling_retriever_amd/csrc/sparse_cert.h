@@ -2,6 +2,7 @@
 // sparse_cert.hip grows on demand.  The calls other files use are declared in sparse_index.h.
 #pragma once
 #include "sparse_index.h"
+#include <vector>
 
 #define SC_DT 1024                    // docs per tile
 #define SC_MB (SC_DT / 32)            // 32-doc M blocks per tile
@@ -43,6 +44,10 @@ struct SparseCert {
     int64_t n_calls = 0, n_queries = 0, n_uncert = 0, n_rescored = 0;
     DeviceBuf<uint16_t> dump;         // debug: [nq_pad][n_tiles * SC_DT] keys of the last search (sr_sparse_index_cert_debug)
     bool want_dump = false;
+    // what sr_sparse_index_cert_readout needs beyond the buffers themselves: the index's posting count and the shape of the last search
+    int64_t nnz = 0, last_nq = 0, last_nq_pad = 0;
+    int last_k = 0, last_k_eff = 0;
+    std::vector<uint8_t> h_uncert;    // the last search's uncertified flags, kept on the host while the key recording is on
     DeviceBuf<unsigned long long> d_stamps;   // [80] dev switch SR_CERT_STAMPS of a -DSC_STAMPS=1 build
     DeviceBuf<uint32_t> mask_pad;     // [n_tiles * SC_MB] a search's document bitmap as the masked score kernel walks it (sparse_cert_mask_pad), allocated on first use
 };

@@ -1128,6 +1128,8 @@ int sparse_cert_search(sr_sparse_index* idx, const SparseCall& call, const Spars
     const int64_t nq_pad = ceil_div64(nq, SC_QB) * SC_QB;
     const int n_qblocks = (int)(nq_pad / SC_QB);
     *res = SparseCertResult{};
+    c->last_nq = nq; c->last_nq_pad = nq_pad; c->last_k = k; c->last_k_eff = 0;
+    c->h_uncert.clear();
     if (!cert_ensure_call_buffers(c, nq_pad, 0)) {
         res->no_memory = true;
         return SR_OK;
@@ -1176,6 +1178,7 @@ int sparse_cert_search(sr_sparse_index* idx, const SparseCall& call, const Spars
     if (k + band > SR_MAX_TOPK) band = SR_MAX_TOPK - k;
     const int k_eff = k + band;
     res->band_used = band;
+    c->last_k_eff = k_eff;
     if (const char* e = getenv("SR_LOG")) if (atoi(e) >= 2)
         fprintf(stderr, "[sr_hip] certified sparse search: %lld queries, %d on the fast path, largest rare-term count %d, band %d keys%s\n", (long long)nq, h_plan[1], h_plan[0],
                 band, opt.band_keys > 0 ? " (second pass)" : "");
@@ -1265,6 +1268,10 @@ int sparse_cert_search(sr_sparse_index* idx, const SparseCall& call, const Spars
     SR_CHECK_HIP(hipMemcpyAsync(h_un2, c->d_n_uncert.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));
     const int h_un = h_un2[0];
+    if (c->want_dump) {                                      // test read-out (sr_sparse_index_cert_readout): the flags of THIS pass
+        c->h_uncert.resize((size_t)nq);
+        SR_CHECK_HIP(hipMemcpy(c->h_uncert.data(), opt.uncert, (size_t)nq, hipMemcpyDeviceToHost));
+    }
     c->n_rescored += 16ll * h_un2[1];
     res->n_uncert = h_un;
     ++c->n_calls;

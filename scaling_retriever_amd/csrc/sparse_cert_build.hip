@@ -318,6 +318,7 @@ int sparse_cert_build(sr_sparse_index* idx, hipStream_t s) {
     const int64_t nnz = h_indptr.back() - h_indptr.front();
     if (nnz <= 0 || nnz >= 0xffffffffll || h_indptr.front() != 0) return SR_OK;
     SparseCert* c = new SparseCert();
+    c->nnz = nnz;
     c->n_tiles = (int)ceil_div64(idx->n_docs, SC_DT);
     CertBuildScratch scratch;
     bool ok = false;
@@ -389,5 +390,59 @@ extern "C" int sr_sparse_index_cert_debug(sr_sparse_index* idx, int enable, uint
     }
     if (vscale) *vscale = c->vscale;
     if (T) *T = c->T;
+    return SR_OK;
+}
+
+// Test-only read-out of the scorer's buffers (include/sr_hip.h): no kernel, one device-to-host copy per call.
+extern "C" int sr_sparse_index_cert_readout(sr_sparse_index* idx, int what, void* h_dst, int64_t capacity_bytes, int64_t* n_bytes) {
+    SR_REQUIRE(idx && n_bytes, "sr_sparse_index_cert_readout: null argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SparseCert* c = idx->cert;
+    SR_REQUIRE(c, "sr_sparse_index_cert_readout: this index has no certified scorer");
+    const int64_t V = idx->n_terms, N = idx->n_docs, nqp = c->last_nq_pad;
+    const void* src = nullptr;
+    int64_t bytes = 0;
+    bool host = false;
+    int64_t info[12];
+    uint32_t vs_bits;
+    memcpy(&vs_bits, &c->vscale, 4);
+    auto plan_ok = [&](const void* p) { return p != nullptr && nqp > 0; };
+    switch (what) {
+        case 0:
+            info[0] = c->T; info[1] = c->KS; info[2] = c->n_tiles; info[3] = c->e_stride; info[4] = V; info[5] = N; info[6] = c->nnz;
+            info[7] = c->last_nq; info[8] = nqp; info[9] = c->last_k; info[10] = c->last_k_eff; info[11] = (int64_t)vs_bits;
+            src = info; bytes = (int64_t)sizeof(info); host = true; break;
+        case 1: src = c->dslot.p; bytes = 4 * V; break;
+        case 2: src = c->vmax.p; bytes = 4 * V; break;
+        case 3: src = c->d16.p; bytes = 2 * (int64_t)c->n_tiles * c->T * SC_DT; break;
+        case 4: src = c->P.p; bytes = 4 * (c->nnz + 4); break;
+        case 5: src = c->S.p; bytes = 4 * V * (int64_t)(c->n_tiles + 1); break;
+        case 6: src = c->E.p; bytes = 4 * V * (int64_t)c->e_stride; break;
+        case 7: src = c->fwd_indptr.p; bytes = 8 * (N + 1); break;
+        case 8: src = c->fwd_tv.p; bytes = 8 * c->nnz; break;
+        case 9: src = c->bfrag.p; bytes = 2 * nqp * c->T; break;
+        case 10: src = c->rare_term.p; bytes = 4 * nqp * 256; break;
+        case 11: src = c->rare_w.p; bytes = 4 * nqp * 256; break;
+        case 12: src = c->elig.p; bytes = nqp; break;
+        case 13: src = c->cq.p; bytes = 4 * nqp; break;
+        case 14: src = c->sq.p; bytes = 4 * nqp; break;
+        case 15: src = c->n_rare.p; bytes = 4 * nqp; break;
+        case 16: src = c->n_qt.p; bytes = 4 * nqp; break;
+        case 17: src = c->n_drop.p; bytes = 4 * nqp; break;
+        case 18: src = c->m_count.p; bytes = 4 * nqp; break;
+        case 19: src = c->ap_ids.p; bytes = 8 * nqp * 2 * (int64_t)c->last_k_eff; break;
+        case 20: src = c->h_uncert.data(); bytes = (int64_t)c->h_uncert.size(); host = true; break;
+        default: sr_set_error("sr_sparse_index_cert_readout: unknown buffer %d", what); return SR_ERR_INVALID;
+    }
+    if (what >= 9 && what <= 19) SR_REQUIRE(plan_ok(src), "sr_sparse_index_cert_readout: no search has run");
+    if (what == 19) SR_REQUIRE(c->last_k_eff > 0, "sr_sparse_index_cert_readout: the last search ran no certificate");
+    if (what == 20) SR_REQUIRE(!c->h_uncert.empty(), "sr_sparse_index_cert_readout: no flags recorded (enable sr_sparse_index_cert_debug first)");
+    *n_bytes = bytes;
+    if (!h_dst) return SR_OK;                                // size query
+    SR_REQUIRE(capacity_bytes >= bytes, "sr_sparse_index_cert_readout: buffer too small");
+    if (bytes == 0) return SR_OK;
+    if (host) { memcpy(h_dst, src, (size_t)bytes); return SR_OK; }
+    SR_CHECK_HIP(hipDeviceSynchronize());
+    SR_CHECK_HIP(hipMemcpy(h_dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
     return SR_OK;
 }

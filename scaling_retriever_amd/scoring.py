@@ -785,6 +785,29 @@ class SparseIndexHIP:
                        "sr_sparse_index_cert_debug")
         return keys, consts, vs.value, T.value
 
+    _CERT_BUFFERS = {"dslot": (1, np.int32), "vmax": (2, np.float32), "d16": (3, np.float16), "P": (4, np.uint32), "S": (5, np.uint32),
+                     "E": (6, np.uint32), "fwd_indptr": (7, np.int64), "fwd_tv": (8, np.uint64), "bfrag": (9, np.float16),
+                     "rare_term": (10, np.int32), "rare_w": (11, np.float32), "elig": (12, np.uint8), "cq": (13, np.float32),
+                     "sq": (14, np.float32), "n_rare": (15, np.int32), "n_qt": (16, np.int32), "n_drop": (17, np.int32),
+                     "m_count": (18, np.int32), "ap_ids": (19, np.int64), "uncert": (20, np.uint8)}
+
+    def cert_readout(self, name):
+        """Test hook (include/sr_hip.h sr_sparse_index_cert_readout): "info" -> {"T", "KS", "n_tiles", "e_stride", "V", "N", "nnz", "nq",
+        "nq_pad", "k", "k_eff", "vscale"}; any other name of _CERT_BUFFERS -> that buffer as a flat numpy array of its element type."""
+        what, dt = (0, np.int64) if name == "info" else self._CERT_BUFFERS[name]
+        n = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sr_sparse_index_cert_readout(self._h, what, None, 0, ctypes.byref(n)), "sr_sparse_index_cert_readout")
+            out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
+            _lib.check(self.lib.sr_sparse_index_cert_readout(self._h, what, out.ctypes.data_as(ctypes.c_void_p), out.nbytes, ctypes.byref(n)),
+                       "sr_sparse_index_cert_readout")
+        if name != "info":
+            return out
+        keys = ("T", "KS", "n_tiles", "e_stride", "V", "N", "nnz", "nq", "nq_pad", "k", "k_eff")
+        info = {k_: int(v) for k_, v in zip(keys, out)}
+        info["vscale"] = float(np.array([out[11]], np.int64).astype(np.uint32).view(np.float32)[0])
+        return info
+
     def work_counters(self, enable):
         """Switch the query-block kernel's work counters on / off; returns what was counted since the last call:
         {"dense_columns_loaded", "dense_column_applications", "light_postings", "grouped_postings", "plan_entries", "workgroup_tiles"}."""

@@ -321,3 +321,14 @@ def test_index_build_kernels_fit_two_workgroups_per_cu(tmp_path):
     for name, m in meta.items():
         if "radix_" in name:
             assert m[".private_segment_fixed_size:"] == 0, (name, m)
+
+
+def test_sparse_cert_readout_hook_validates_before_it_touches_a_device():
+    """sr_sparse_index_cert_readout without an index (or without a size pointer) is SR_ERR_INVALID; nothing is dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    n = ctypes.c_int64(-1)
+    for idx, np_ in [(None, ctypes.byref(n)), (ctypes.c_void_p(4096), None)]:
+        rc = lib.sr_sparse_index_cert_readout(idx, 0, None, 0, np_)
+        assert rc == _lib.SR_ERR_INVALID and b"null argument" in lib.sr_last_error()
+    assert n.value == -1

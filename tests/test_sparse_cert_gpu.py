@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import sparse_cert_cases as C
 from oracle import scoring as O
 
 pytestmark = pytest.mark.gpu
@@ -88,7 +89,6 @@ def test_stage1_keys_obey_the_bound_for_every_query_doc_pair(forced):
     D = sp.csr_matrix((vals.astype(np.float64), (ids, term_of)), shape=(N, V))
     Q = sp.csr_matrix((qv.astype(np.float64), qc, qi), shape=(nq, V))
     true = np.asarray((Q @ D.T).todense())                                   # real-arithmetic scores, [nq, N]
-    dd = 2.0 * 2.0 ** -11 + 2.4e-7 + T * 2.4e-7 + 1.0e-5
     checked = 0
     for q in range(nq):
         cq, sq, n_rare, n_qt, n_drop = consts[q, :5]
@@ -96,9 +96,10 @@ def test_stage1_keys_obey_the_bound_for_every_query_doc_pair(forced):
             continue
         tf = 65535.0 * float(sq) * true[q]
         kq = keys[q, :N].astype(np.float64)
-        assert (kq >= tf * (1 - dd) - 1.2 - 2.03 * n_drop).all(), (q, float((tf * (1 - dd) - 1.2 - kq).max()))
-        assert (kq <= tf * (1 + dd) + 1.2 + 1.01 * n_rare).all(), (q, float((kq - tf * (1 + dd) - 1.2 - 1.01 * n_rare).max()))
-        assert kq.max() <= 65535 * 0.99                                      # no key near its half word's limit
+        lo, hi = C.bound(tf, T, float(n_rare), float(n_drop))                # the documented bound, derived in sparse_cert_cases.py
+        assert (kq >= lo).all(), (q, float((lo - kq).max()))
+        assert (kq <= hi).all(), (q, float((kq - hi).max()))
+        assert kq.max() <= min(65535 * 0.99, C.saturation_limit(T, float(n_rare)))       # no key near its half word's limit
         assert (keys[q, N:] == 0).all()                                      # docs beyond the collection
         checked += 1
     assert checked >= nq - 2
@@ -412,11 +413,10 @@ def test_up_to_256_rare_terms_stay_on_the_fast_path(forced):
         for t, w in zip(cols, v):
             true[ids[indptr[t]:indptr[t + 1]]] += float(w) * vals[indptr[t]:indptr[t + 1]].astype(np.float64)
         tf = true * sq * 65535.0
-        dd = 2.0 * 2.0 ** -11 + 2.4e-7 + T * 2.4e-7 + 1.0e-5               # as in test_stage1_keys_obey_the_bound_for_every_query_doc_pair
+        lo, hi = C.bound(tf, T, n_r, n_drop)                               # as in test_stage1_keys_obey_the_bound_for_every_query_doc_pair
         kq = keys[q, :N].astype(np.float64)
-        assert (kq >= tf * (1 - dd) - 1.2 - 2.03 * n_drop).all(), q
-        assert (kq <= tf * (1 + dd) + 1.2 + 1.01 * n_r).all(), q
-        assert kq.max() <= 65535 * 0.99
+        assert (kq >= lo).all() and (kq <= hi).all(), q
+        assert kq.max() <= min(65535 * 0.99, C.saturation_limit(T, n_r))
 
 
 def test_band_grows_with_the_rare_terms_and_a_failed_batch_is_retried_wider(forced, monkeypatch):
