@@ -131,12 +131,15 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
     if k > max_topk:
         raise ValueError(f"search_fused: topk = {k} is beyond sr_max_topk() = {max_topk}")
     depths = default_depths(k, max_topk) if depths is None else _check_depths(depths, k, max_topk)
-    from .scoring import _mask_words, doc_list_from_mask, doc_mask_remap, hybrid_union
+    from .doc_filter import mask_argument, mask_on_device
+    from .scoring import doc_list_from_mask, doc_mask_remap, hybrid_union
     dev = dense.device
     if mask is not None:
-        mask = _mask_words(mask, dev)
-        if mask.numel() != (dense.id_end + 31) // 32:
-            raise ValueError(f"a packed mask of this index holds {(dense.id_end + 31) // 32} words (id_end = {dense.id_end}), got {mask.numel()}")
+        mask, n_bits = mask_argument(mask, lambda: dense.id_end, "id_end")
+        if n_bits is None:
+            raise ValueError("search_fused takes its mask as packed int32 / uint32 words (scoring.pack_doc_mask), not as flags")
+        # the words themselves on the device: the searches below resolve them again, without a copy
+        mask = mask_on_device(mask, n_bits, dev)[0][:(n_bits + 31) // 32]
     q = dense_queries.to(device=dev, dtype=torch.float32).contiguous()
     row_ptr, cols, vals = (q_row_ptr.to(device=dev, dtype=torch.int64), q_cols.to(device=dev, dtype=torch.int32),
                            q_vals.to(device=dev, dtype=torch.float32))

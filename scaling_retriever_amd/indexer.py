@@ -25,6 +25,7 @@ import torch
 from tqdm import tqdm
 
 from . import _lib
+from .doc_filter import Filter, allowed_positions_on, doc_mask_from_list, flags_to_words, one_filter
 from .scoring import DenseIndexHIP, SparseIndexHIP, sparse_csr_build, sparse_csr_expand_terms
 from .utils.inverted_index import IndexDictOfArray
 from .utils.run_file import IdTable, PiecewiseRunWriter, RunResult, id_table, to_host, write_run_json
@@ -35,6 +36,18 @@ logger = logging.getLogger()
 
 def _unwrap(model):
     return model.module if hasattr(model, "module") else model
+
+
+def _dense_queries(query_reps, device):
+    """Query vectors as given (a tensor on any device, or an array) -> fp32 on the index's device."""
+    if isinstance(query_reps, torch.Tensor):
+        return query_reps.to(device=device, dtype=torch.float32)
+    return torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(device)
+
+
+def _search_filter(filt):
+    """The subset= / mask= keyword of the index classes' `search` for a resolved doc_filter.Filter (None: none)."""
+    return {} if filt is None else {filt.kind: filt.data}
 
 
 def batch_groups(loader, max_rows=16384):
@@ -274,20 +287,14 @@ class DenseFlatIndexer(DenseIndexer):
         numba_score_float, indexer.py:315-344): (list of db-id lists, list of fp32 score arrays), one pair per query, of the documents
         with score > thresholds (a float, or one value per query).  sort=True: best first, ties by index position, so a list is a
         prefix of what search_knn ranks; False: index order.  The ids go through id_table in one numpy take (the ragged counterpart
-        of id_lists).  allowed_ids / allowed_mask (not both) as for search_knn: only these documents are returned - the lists are the
-        unrestricted ones with every other document removed (DenseIndexHIP.range_search, mask; faiss's range_search with an IDSelector)."""
-        if allowed_ids is not None and allowed_mask is not None:
-            raise ValueError("range_search: pass allowed_ids or allowed_mask, not both")
-        mask = None
-        if allowed_mask is not None:
-            mask = self.allowed_mask_words(allowed_mask)
-        elif allowed_ids is not None:
-            from .scoring import doc_mask_from_list
-            mask = doc_mask_from_list(self.allowed_subset(allowed_ids), self.index.id_end, device=self.index.device)
-        if isinstance(query_reps, torch.Tensor):
-            q = query_reps.to(device=self.index.device, dtype=torch.float32)
-        else:
-            q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
+        of id_lists).  allowed_ids / allowed_mask (one of them at most) as for search_knn: only these documents are returned - the
+        lists are the unrestricted ones with every other document removed (DenseIndexHIP.range_search, mask; faiss's range_search with
+        an IDSelector)."""
+        filt = self._resolve("range_search", allowed_ids, allowed_mask)
+        mask = None if filt is None else filt.data
+        if filt is not None and filt.kind == "subset":
+            mask = doc_mask_from_list(filt.data, self.index.id_end, device=self.index.device)
+        q = _dense_queries(query_reps, self.index.device)
         lims, scores, positions = self.index.range_search(q, thresholds, sort=sort, mask=mask)
         lims, scores = lims.cpu().numpy(), scores.cpu().numpy()
         flat = self.id_table()[positions.cpu().numpy()]
@@ -299,66 +306,52 @@ class DenseFlatIndexer(DenseIndexer):
     def allowed_subset(self, allowed_ids):
         """External database ids (any order, duplicates allowed) -> the sorted unique index positions as an int64 tensor on the index's
         device: the allow-list of search_knn / search_arrays, uploaded once per call.  An unknown id: ValueError naming it."""
-        from .scoring import allowed_positions
-        inv = self.inverse_id_map()
-        return torch.from_numpy(allowed_positions(allowed_ids, lambda d: inv.pos.get(str(d)))).to(self.index.device)
+        return allowed_positions_on(allowed_ids, self.inverse_id_map(), self.index.device)
 
     def allowed_mask_words(self, allowed_mask):
         """A boolean array / tensor over index positions (length = the number of indexed vectors) -> the packed bitmap on the index's
-        device, uploaded and packed once per call (scoring.pack_doc_mask)."""
-        from .scoring import pack_doc_mask
-        flags = allowed_mask if isinstance(allowed_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allowed_mask, dtype=bool))
-        if flags.dim() != 1 or flags.numel() != self.index.id_end:
-            raise ValueError(f"allowed_mask must hold one flag per index position ({self.index.id_end}), got {tuple(flags.shape)}")
-        return pack_doc_mask(flags.to(device=self.index.device, dtype=torch.bool))
+        device, uploaded and packed once per call (doc_filter.flags_to_words)."""
+        return flags_to_words(allowed_mask, self.index.id_end, "index position", self.index.device)
 
     def allowed_group_words(self, allowed_masks, query_group):
         """allowed_masks bool [G, index positions] and query_group int [nq] (both or neither) -> (packed bitmaps int32 [G, W] on the
-        index's device, group ids int64 on the device), packed once per call (scoring.pack_doc_masks)."""
-        from .scoring import pack_doc_masks
-        flags = allowed_masks if isinstance(allowed_masks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allowed_masks, dtype=bool))
-        if flags.dim() != 2 or flags.shape[0] < 1 or flags.shape[1] != self.index.id_end:
-            raise ValueError(f"allowed_masks must hold one row of flags per group, one flag per index position ({self.index.id_end}), got "
-                             f"{tuple(flags.shape)}")
+        index's device, group ids int64 on the device), packed once per call (doc_filter.flags_to_words)."""
+        words = flags_to_words(allowed_masks, (None, self.index.id_end), "index position", self.index.device)
         groups = query_group if isinstance(query_group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(query_group))
         if groups.dim() != 1 or groups.dtype.is_floating_point or groups.dtype == torch.bool:
             raise ValueError(f"query_group must hold one integer group id per query, got {groups.dtype} {tuple(groups.shape)}")
-        return pack_doc_masks(flags.to(torch.bool), self.index.device), groups.to(device=self.index.device, dtype=torch.int64)
+        return words, groups.to(device=self.index.device, dtype=torch.int64)
 
-    @staticmethod
-    def _check_filters(who, allowed_ids, allowed_mask, allowed_masks, query_group):
-        """The argument rules of the filtered searches, checked before anything is uploaded."""
-        if allowed_ids is not None and allowed_mask is not None:
-            raise ValueError(f"{who}: pass allowed_ids or allowed_mask, not both")
-        if (allowed_masks is not None or query_group is not None) and (allowed_ids is not None or allowed_mask is not None):
-            raise ValueError(f"{who}: pass allowed_masks / query_group or one filter for all queries (allowed_ids, allowed_mask), not both")
-        if (allowed_masks is None) != (query_group is None):
-            raise ValueError(f"{who}: allowed_masks and query_group go together (one bitmap per group, one group id per query)")
+    def _resolve(self, who, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
+        """The filter keywords of a search -> a doc_filter.Filter on the index's device (None: no filter), resolved and uploaded once per
+        call; the argument rules (doc_filter.one_filter) come before anything is uploaded."""
+        one_filter(who, allowed_masks, query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        if allowed_ids is not None:
+            return Filter("subset", self.allowed_subset(allowed_ids))
+        if allowed_mask is not None:
+            return Filter("mask", self.allowed_mask_words(allowed_mask))
+        if allowed_masks is not None:
+            return Filter("groups", *self.allowed_group_words(allowed_masks, query_group))
+        return None
 
     def search_knn(self, query_reps, top_docs: int, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
         """indexer.py:210-214: (list of db-id lists, fp32 scores [nq, k]); label -1 (fewer than k vectors) -> None.  allowed_ids (None:
         the whole index): database ids, any order, duplicates allowed - only these documents are ranked (DenseIndexHIP.search, subset).
-        allowed_mask: the same filter as a boolean array over index positions (DenseIndexHIP.search, mask); not both.
+        allowed_mask: the same filter as a boolean array over index positions (DenseIndexHIP.search, mask); one of the two at most.
         allowed_masks bool [G, index positions] with query_group int [nq]: a filter per query - query q is ranked within the documents of
         allowed_masks[query_group[q]] (DenseIndexHIP.search_grouped); not together with a filter for all queries.
         The lists come
         from id_lists (csrc/host_lists.c).  A large query set is searched in KNN_CHUNKS pieces, the GPU working on piece c + 1 (in a
         worker thread: the C call releases the GIL) while this thread builds the lists of piece c - the exact results do not depend
         on how the queries are batched (pieces stay above 64 queries: one kernel family, one k order)."""
-        self._check_filters("search_knn", allowed_ids, allowed_mask, allowed_masks, query_group)
-        if isinstance(query_reps, torch.Tensor):
-            q = query_reps.to(device=self.index.device, dtype=torch.float32)
-        else:
-            q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
+        filt = self._resolve("search_knn", allowed_ids, allowed_mask, allowed_masks, query_group)
+        q = _dense_queries(query_reps, self.index.device)
         nq = q.shape[0]
-        subset = None if allowed_ids is None else self.allowed_subset(allowed_ids)
-        mask = None if allowed_mask is None else self.allowed_mask_words(allowed_mask)
-        groups = None if allowed_masks is None else self.allowed_group_words(allowed_masks, query_group)
-        if groups is not None and groups[1].numel() != nq:
-            raise ValueError(f"search_knn: query_group must hold one group id per query ({nq}), got {groups[1].numel()}")
+        if filt is not None and filt.kind == "groups" and filt.groups.numel() != nq:
+            raise ValueError(f"search_knn: query_group must hold one group id per query ({nq}), got {filt.groups.numel()}")
         n_chunks = self.KNN_CHUNKS if nq >= 1024 else 1
         if n_chunks == 1:
-            scores, indexes = self.search_arrays(q, top_docs, _subset=subset, _mask=mask, _groups=groups)
+            scores, indexes = self.search_arrays(q, top_docs, _filter=filt)
             return self.id_lists(indexes), scores
         from concurrent.futures import ThreadPoolExecutor
         per = (nq + n_chunks - 1) // n_chunks
@@ -366,12 +359,13 @@ class DenseFlatIndexer(DenseIndexer):
         dev = self.index.device
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(dev))          # q may come from a side stream of the caller
+        grouped = filt is not None and filt.kind == "groups"
 
         def gpu(c):
             with torch.cuda.device(dev):
                 torch.cuda.current_stream(dev).wait_event(ready)          # the worker thread's current stream is the default one
-                part = None if groups is None else (groups[0], groups[1][bounds[c][0]:bounds[c][1]])
-                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs, _subset=subset, _mask=mask, _groups=part)
+                part = filt._replace(groups=filt.groups[bounds[c][0]:bounds[c][1]]) if grouped else filt
+                return self.search_arrays(q[bounds[c][0]:bounds[c][1]], top_docs, _filter=part)
         top_doc_ids, score_parts = [], []
         with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(gpu, 0)
@@ -383,27 +377,16 @@ class DenseFlatIndexer(DenseIndexer):
                 score_parts.append(scores)
         return top_doc_ids, np.concatenate(score_parts)
 
-    def search_arrays(self, query_reps, top_docs: int, allowed_ids=None, _subset=None, allowed_mask=None, _mask=None, allowed_masks=None,
-                      query_group=None, _groups=None):
+    def search_arrays(self, query_reps, top_docs: int, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, _filter=None):
         """(scores fp32 [nq, k], index positions int64 [nq, k]; -1 = fewer than k vectors) as host arrays: what search_knn maps
         to db ids, and what the run.json writer takes as they are (utils/run_file.py).  allowed_ids / allowed_mask / allowed_masks with
-        query_group as for search_knn (_subset: the positions, already on the device; _mask: the packed bitmap, already on the device;
-        _groups: the packed bitmaps and the group ids, already on the device)."""
-        self._check_filters("search_arrays", allowed_ids, allowed_mask, allowed_masks, query_group)
-        if allowed_ids is not None:
-            _subset = self.allowed_subset(allowed_ids)
-        if allowed_mask is not None:
-            _mask = self.allowed_mask_words(allowed_mask)
-        if allowed_masks is not None:
-            _groups = self.allowed_group_words(allowed_masks, query_group)
-        if isinstance(query_reps, torch.Tensor):
-            q = query_reps.to(device=self.index.device, dtype=torch.float32)
+        query_group as for search_knn (_filter: such a filter already resolved and on the device, doc_filter.Filter)."""
+        filt = self._resolve("search_arrays", allowed_ids, allowed_mask, allowed_masks, query_group) or _filter
+        q = _dense_queries(query_reps, self.index.device)
+        if filt is not None and filt.kind == "groups":
+            scores, indexes = self.index.search_grouped(q, top_docs, filt.data, filt.groups)
         else:
-            q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
-        if _groups is not None:
-            scores, indexes = self.index.search_grouped(q, top_docs, _groups[0], _groups[1])
-            return to_host(scores), to_host(indexes)
-        scores, indexes = self.index.search(q, top_docs, subset=_subset, mask=_mask)
+            scores, indexes = self.index.search(q, top_docs, **_search_filter(filt))
         return to_host(scores), to_host(indexes)
 
     def inverse_id_map(self):
@@ -421,10 +404,7 @@ class DenseFlatIndexer(DenseIndexer):
         Returns a RunResult (rows sorted by score descending, ties by index position ascending; `.dump(path)` writes run.json).
         The scores are DenseIndexHIP.score_pairs's: the bits a search of more than 64 queries returns for the pair."""
         from .rerank import ranked_run
-        if isinstance(query_reps, torch.Tensor):
-            q = query_reps.to(device=self.index.device, dtype=torch.float32)
-        else:
-            q = torch.from_numpy(np.ascontiguousarray(query_reps, dtype=np.float32)).to(self.index.device)
+        q = _dense_queries(query_reps, self.index.device)
         assert len(doc_id_lists) == q.shape[0], (len(doc_id_lists), q.shape[0])
         indptr, positions = self.inverse_id_map().positions(doc_id_lists)
         pos_t = torch.from_numpy(positions).to(self.index.device)
@@ -866,16 +846,12 @@ class SparseRetrieval:
         A document without any posting has no collection id (doc_ids.pkl does not list it; the reference's doc_ids[id_] raises
         KeyError for it).  It scores 0.0 and so passes a negative threshold: such documents are left out of the lists here, their
         placeholders of doc_id_table never come back.  SparseIndexHIP.range_search returns them, by position.
-        allowed_ids / allowed_mask (not both) as for retrieve: only these documents are returned - the unrestricted lists with every
-        other document removed (SparseIndexHIP.range_search, mask)."""
-        if allowed_ids is not None and allowed_mask is not None:
-            raise ValueError("range_search: pass allowed_ids or allowed_mask, not both")
-        mask = None
-        if allowed_mask is not None:
-            mask = self.allowed_mask_words(allowed_mask)
-        elif allowed_ids is not None:
-            from .scoring import doc_mask_from_list
-            mask = doc_mask_from_list(self.allowed_subset(allowed_ids), self.hip_index.n_docs, device=self._dev)
+        allowed_ids / allowed_mask (one of them at most) as for retrieve: only these documents are returned - the unrestricted lists
+        with every other document removed (SparseIndexHIP.range_search, mask)."""
+        filt = self._resolve("range_search", allowed_ids, allowed_mask)
+        mask = None if filt is None else filt.data
+        if filt is not None and filt.kind == "subset":
+            mask = doc_mask_from_list(filt.data, self.hip_index.n_docs, device=self._dev)
         q = _as_query_csr(sparse_query_vecs, self._dev)
         lims, scores, positions = self.hip_index.range_search(q.row_ptr, q.cols, q.vals, thresholds, sort=sort, mask=mask)
         lims, scores, positions = lims.cpu().numpy(), scores.cpu().numpy(), positions.cpu().numpy()
@@ -893,35 +869,31 @@ class SparseRetrieval:
     def allowed_subset(self, allowed_ids):
         """Collection ids (any order, duplicates allowed) -> the sorted unique document positions of the inverted index as an int64
         tensor on its device: the allow-list of retrieve, uploaded once per call.  An unknown id: ValueError naming it."""
-        from .scoring import allowed_positions
-        inv = self.inverse_id_map()
-        return torch.from_numpy(allowed_positions(allowed_ids, lambda d: inv.pos.get(str(d)))).to(self._dev)
+        return allowed_positions_on(allowed_ids, self.inverse_id_map(), self._dev)
 
     def allowed_mask_words(self, allowed_mask):
         """A boolean array / tensor over the document positions of the inverted index (one flag per document) -> the packed bitmap on
-        its device, uploaded and packed once per call (scoring.pack_doc_mask)."""
-        from .scoring import pack_doc_mask
-        flags = allowed_mask if isinstance(allowed_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allowed_mask, dtype=bool))
-        n_docs = self.hip_index.n_docs
-        if flags.dim() != 1 or flags.numel() != n_docs:
-            raise ValueError(f"allowed_mask must hold one flag per document position ({n_docs}), got {tuple(flags.shape)}")
-        return pack_doc_mask(flags.to(device=self._dev, dtype=torch.bool))
+        its device, uploaded and packed once per call (doc_filter.flags_to_words)."""
+        return flags_to_words(allowed_mask, self.hip_index.n_docs, "document position", self._dev)
 
-    def _sparse_retrieve_multithreaded(self, sparse_query_vecs, qids, threshold=0., topk=1000, allowed_ids=None, _subset=None,
-                                       allowed_mask=None, _mask=None):
-        """allowed_ids (None: every document): collection ids - only these documents are ranked (_subset: their positions, already on
-        the device).  allowed_mask: the same filter as a boolean array over document positions (_mask: its packed bitmap, already on
-        the device); not both.  indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
+    def _resolve(self, who, allowed_ids=None, allowed_mask=None):
+        """allowed_ids / allowed_mask of a search -> a doc_filter.Filter on the index's device (None: no filter), resolved and uploaded
+        once per call; the argument rule (doc_filter.one_filter) comes before anything is uploaded."""
+        one_filter(who, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        if allowed_ids is not None:
+            return Filter("subset", self.allowed_subset(allowed_ids))
+        return None if allowed_mask is None else Filter("mask", self.allowed_mask_words(allowed_mask))
+
+    def _sparse_retrieve_multithreaded(self, sparse_query_vecs, qids, threshold=0., topk=1000, allowed_ids=None, allowed_mask=None,
+                                       _filter=None):
+        """allowed_ids (None: every document): collection ids - only these documents are ranked.  allowed_mask: the same filter as a
+        boolean array over document positions; one of the two at most (_filter: such a filter already resolved and on the device,
+        doc_filter.Filter).  indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
         whole query set is one batched HIP search (the doc space is tiled across workgroups instead) and `res` is a RunResult
         over the result arrays: the same mapping, without 7 M dict insertions."""
-        if allowed_ids is not None and allowed_mask is not None:
-            raise ValueError("_sparse_retrieve_multithreaded: pass allowed_ids or allowed_mask, not both")
+        filt = self._resolve("_sparse_retrieve_multithreaded", allowed_ids, allowed_mask) or _filter
         q = _as_query_csr(sparse_query_vecs, self._dev)
-        if allowed_ids is not None:
-            _subset = self.allowed_subset(allowed_ids)
-        if allowed_mask is not None:
-            _mask = self.allowed_mask_words(allowed_mask)
-        scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=_subset, mask=_mask)
+        scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, **_search_filter(filt))
         res = RunResult(qids, to_host(scores), to_host(ids), self.doc_id_table(), to_host(counts))
         stats = defaultdict(float)
         stats["L0_q"] = q.mean_l0()
@@ -937,22 +909,19 @@ class SparseRetrieval:
     def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None):
         """allowed_ids (None: every document): collection ids, any order, duplicates allowed - only these documents are ranked; an unknown
         id raises ValueError before anything is encoded.  allowed_mask: the same filter as a boolean array over the document positions
-        of the inverted index (SparseIndexHIP.search, mask); not both.  run.json and q_stats.json keep their format.
+        of the inverted index (SparseIndexHIP.search, mask); one of the two at most.  run.json and q_stats.json keep their format.
         indexer.py:530-540.  Query groups of QUERY_GROUP_ROWS rows go through encode -> search one after the other while a worker
         thread writes the previous group's piece of run.json (sr_write_run_json_part): formatting and the page-cache copy of a Dev-sized
         file take as long as the encode, and nothing in them needs the GPU.  A query's rows do not depend on the batch it is searched in
         (certified or exact: the same bits), and the file is the one-call file byte for byte (tests/test_boundary_gpu.py)."""
-        if allowed_ids is not None and allowed_mask is not None:
-            raise ValueError("retrieve: pass allowed_ids or allowed_mask, not both")
+        filt = self._resolve("retrieve", allowed_ids, allowed_mask)
         groups = list(batch_groups(q_loader, self.QUERY_GROUP_ROWS))
         group_qids = [[x for batch in g for x in (batch["ids"] if isinstance(batch["ids"], list) else to_list(batch["ids"]))] for g in groups]
         qids = [x for g in group_qids for x in g]
         table = self.doc_id_table()
-        subset = None if allowed_ids is None else self.allowed_subset(allowed_ids)
-        mask = None if allowed_mask is None else self.allowed_mask_words(allowed_mask)
         if len(groups) < 2 or not (id_table(qids).distinct and id_table(table).distinct):
             sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
-            res, stats = self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=subset, _mask=mask)
+            res, stats = self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _filter=filt)
             self._write_outputs(res, stats)
             return res
         os.makedirs(self.out_dir, exist_ok=True)
@@ -965,7 +934,7 @@ class SparseRetrieval:
                 q = QueryCSR(*sparse_reps_to_csr(reps, self.query_max_terms))
                 del reps
                 nnz += int(q.cols.numel())
-                scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, subset=subset, mask=mask)
+                scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, **_search_filter(filt))
                 piece = (to_host(scores), to_host(ids), to_host(counts))
                 pieces.append(piece)
                 writer.add(group_qids[gi], piece[0], piece[1], table, piece[2], last=gi + 1 == len(groups))
@@ -1142,31 +1111,27 @@ class HybridRetriever(SparseRetrieval):
         assert len(sparse_query_vecs) == len(dense_query_vecs) == len(qids)
         return sparse_query_vecs, dense_query_vecs, qids
 
-    def _dense_retrieve(self, query_reps, qids, topk=1000, _subset=None):
+    def _dense_retrieve(self, query_reps, qids, topk=1000, _filter=None):
         """indexer.py:973-982, as a RunResult over the result arrays (label -1 rows = fewer than k vectors are skipped)."""
-        scores, positions = self.dense_index.search_arrays(query_reps, topk, _subset=_subset)
+        scores, positions = self.dense_index.search_arrays(query_reps, topk, _filter=_filter)
         return RunResult(qids, scores, positions, self.dense_index.run_table())
 
-    def _sparse_retrieve(self, sparse_query_vecs, qids, threshold=0., topk=1000, _subset=None):
-        return self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=_subset)
+    def _sparse_retrieve(self, sparse_query_vecs, qids, threshold=0., topk=1000, _filter=None):
+        return self._sparse_retrieve_multithreaded(sparse_query_vecs, qids, threshold=threshold, topk=topk, _filter=_filter)
 
     def allowed_subsets(self, allowed_ids):
         """(dense positions, sparse positions) of an allow-list of database ids, each sorted, unique and on the device.  The two indexes
         number documents independently.  Every id must be in the dense index (ValueError naming it otherwise); one without a posting is
         unknown to the inverted index and is simply not in its list (it shares no term with any query)."""
-        from .scoring import allowed_positions
-        dense = self.dense_index.allowed_subset(allowed_ids)
-        inv = self.inverse_id_map()
-        known = [d for d in allowed_ids if inv.pos.get(str(d)) is not None]
-        sparse = torch.from_numpy(allowed_positions(known, lambda d: inv.pos.get(str(d)))).to(self._dev)
-        return dense, sparse
+        sparse = allowed_positions_on(allowed_ids, self.inverse_id_map(), self._dev, skip_unknown=True)
+        return self.dense_index.allowed_subset(allowed_ids), sparse
 
     def _retrieve_both(self, q_loader, topk, threshold, allowed_ids=None):
         """The two searches and their files (sparse/run.json + q_stats.json, dense/run.json): shared by retrieve and retrieve_fused."""
-        d_subset, s_subset = (None, None) if allowed_ids is None else self.allowed_subsets(allowed_ids)
+        d_subset, s_subset = (None, None) if allowed_ids is None else (Filter("subset", t) for t in self.allowed_subsets(allowed_ids))
         sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
-        sparse_res, sparse_stats = self._sparse_retrieve(sparse_query_vecs, qids, threshold=threshold, topk=topk, _subset=s_subset)
-        dense_res = self._dense_retrieve(dense_query_vecs, qids, topk=topk, _subset=d_subset)
+        sparse_res, sparse_stats = self._sparse_retrieve(sparse_query_vecs, qids, threshold=threshold, topk=topk, _filter=s_subset)
+        dense_res = self._dense_retrieve(dense_query_vecs, qids, topk=topk, _filter=d_subset)
         with open(os.path.join(self.sparse_out_dir, "q_stats.json"), "w") as handler:
             json.dump(sparse_stats, handler)
         sparse_res.dump(os.path.join(self.sparse_out_dir, "run.json"))
@@ -1276,10 +1241,7 @@ class HybridRetriever(SparseRetrieval):
         mask = None if allowed_mask is None else self.dense_index.allowed_mask_words(allowed_mask)
         q = _as_query_csr(sparse_query_vecs, self._dev)
         d2s, s2d = self._position_maps()
-        if isinstance(dense_query_vecs, torch.Tensor):
-            dq = dense_query_vecs.to(device=self._dev, dtype=torch.float32)
-        else:
-            dq = torch.from_numpy(np.ascontiguousarray(dense_query_vecs, dtype=np.float32)).to(self._dev)
+        dq = _dense_queries(dense_query_vecs, self._dev)
         scores, positions, counts, stats = hybrid.search_fused(self.dense_index.index, self.hip_index, d2s, s2d, dq, q.row_ptr, q.cols, q.vals,
                                                                topk, weights=weights, depths=depths, fallback_bytes=fallback_bytes, mask=mask)
         qids = list(range(dq.shape[0])) if qids is None else qids

@@ -3,6 +3,15 @@
 These hold device memory (torch tensors) and call the C ABI; all arithmetic is in
 the HIP kernels (csrc/dense_score.hip, csrc/sparse_cert.hip, csrc/sparse_score.hip, csrc/topk.hip).
 The reference-shaped classes in indexer.py are built on top of these.
+
+What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, topk_merge, hybrid_union,
+hybrid_rank).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
+the status checked under that name); a filtered variant of an entry is the same call with "_subset" / "_masked" appended to the name
+and the filter's two arguments spliced in where the header puts them (_filter_args).  Each class checks its queries in one place
+(DenseIndexHIP._queries, SparseIndexHIP._query_csr), the range searches share _thresholds, and add_host_rows / add_npy_file share
+one pinned staging ring (DenseIndexHIP._add_staged).  Everything about document filters - packing, the resolver of a mask= argument,
+the "only one filter" rule, the order of checks - lives in doc_filter.py; its public names are re-exported here, the module
+everything imports from.
 """
 import ctypes
 
@@ -10,18 +19,25 @@ import numpy as np
 import torch
 
 from . import _lib
+from .doc_filter import (_call, _mask_words, _ptr, _subset, _to_dev, _valid, allowed_positions, doc_list_from_mask,  # noqa: F401  (re-exported)
+                         doc_mask_from_list, doc_mask_remap, mask_argument, mask_on_device, one_filter, pack_doc_mask, pack_doc_masks,
+                         query_group_argument, read_allowed_ids_file)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+def _thresholds(thresholds, nq, device):
+    """The thresholds of a range search as fp32 [nq] on the device: one Python / numpy scalar for all queries, or a tensor / array [nq]."""
+    if isinstance(thresholds, (int, float, np.floating, np.integer)):
+        return torch.full((nq,), float(thresholds), dtype=torch.float32, device=device)
+    thr = _to_dev(thresholds, torch.float32, device)
+    if thr.dim() != 1 or thr.numel() != nq:
+        raise ValueError(f"expected {nq} thresholds, got {tuple(thr.shape)}")
+    return thr
 
 
-def _to_dev(x, dt, device):
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    elif not torch.is_tensor(x):
-        x = torch.as_tensor(x)
-    return x.to(device=device, dtype=dt).contiguous()
+def _filter_args(filt):
+    """(suffix of the entry's name, the arguments spliced in where the header puts them) of a resolved filter: None, ("_subset", list,
+    m) or ("_masked", words, n_bits).  The caller keeps `filt`, and with it the tensor, until the call has been made."""
+    return ("", ()) if filt is None else (filt[0], (_ptr(filt[1]), filt[2]))
 
 
 def _candidates(cand_indptr, cand_ids, nq, device):
@@ -37,230 +53,7 @@ def _candidates(cand_indptr, cand_ids, nq, device):
     # the kernels trust cand_indptr[nq] for the size of cand_ids and of the output: the one thing checked here
     if int(cand_indptr[-1]) != total:
         raise ValueError(f"cand_indptr ends at {int(cand_indptr[-1])}, cand_ids holds {total} ids")
-    if total == 0:
-        cand_ids = torch.zeros(1, dtype=torch.int64, device=device)      # keep a valid pointer
-    return cand_indptr, cand_ids, total
-
-
-def _subset(subset, device):
-    """(int64 device tensor with a valid pointer, m) of an allow-list for the *_search_subset entry points; its order and content are
-    checked by the kernels."""
-    subset = _to_dev(subset, torch.int64, device)
-    if subset.dim() != 1:
-        raise ValueError(f"expected a 1-D subset, got {tuple(subset.shape)}")
-    m = subset.numel()
-    if m == 0:
-        subset = torch.zeros(1, dtype=torch.int64, device=device)        # keep a valid pointer
-    return subset, m
-
-
-def pack_doc_mask(allowed):
-    """A boolean array over document indices -> the bitmap the masked search takes: bit (i & 31) of word i >> 5 is allowed[i], the unused
-    bits of the last word are 0 (include/sr_hip.h sr_dense_search_masked).  A numpy array is packed on the host and comes back as
-    np.uint32 [ceil(n / 32)]; a torch tensor is packed on its own device and comes back as int32 words (torch has no arithmetic on
-    uint32; the bits are the same)."""
-    if torch.is_tensor(allowed):
-        if allowed.dim() != 1:
-            raise ValueError(f"expected a 1-D boolean mask, got {tuple(allowed.shape)}")
-        n = allowed.numel()
-        bits = torch.zeros(((n + 31) // 32) * 32, dtype=torch.int64, device=allowed.device)
-        bits[:n] = allowed.to(torch.bool)
-        weights = torch.ones(32, dtype=torch.int64, device=allowed.device) << torch.arange(32, dtype=torch.int64, device=allowed.device)
-        return (bits.view(-1, 32) * weights).sum(dim=1).to(torch.int32)      # int64 -> int32 keeps the low 32 bits
-    allowed = np.asarray(allowed)
-    if allowed.ndim != 1:
-        raise ValueError(f"expected a 1-D boolean mask, got {allowed.shape}")
-    n_words = (allowed.size + 31) // 32
-    raw = np.zeros(4 * n_words, dtype=np.uint8)
-    packed = np.packbits(allowed.astype(bool), bitorder="little")         # bit i & 7 of byte i >> 3
-    raw[:packed.size] = packed
-    return raw.view("<u4").astype(np.uint32)                              # little-endian words: bit i & 31 of word i >> 5
-
-
-def pack_doc_masks(flags, device=None):
-    """A bool [G, n_bits] tensor or array -> the stacked bitmaps the grouped search takes (include/sr_hip.h sr_dense_search_grouped): int32
-    [G, ceil(n_bits / 32)], row g = pack_doc_mask(flags[g]).  Packed on `device` (None: where a tensor lives; an array on the host), a
-    few rows at a time, so the unpacked intermediate stays at 256 MB however many groups there are."""
-    if not torch.is_tensor(flags):
-        flags = torch.from_numpy(np.ascontiguousarray(np.asarray(flags), dtype=bool))
-    if flags.dim() != 2:
-        raise ValueError(f"expected a 2-D boolean [groups, n_bits] mask, got {tuple(flags.shape)}")
-    if flags.dtype != torch.bool:
-        raise ValueError(f"expected a boolean [groups, n_bits] mask, got {flags.dtype}")
-    device = flags.device if device is None else torch.device(device)
-    n_groups, n = flags.shape
-    n_words = (n + 31) // 32
-    out = torch.empty((n_groups, n_words), dtype=torch.int32, device=device)
-    if n_words == 0:
-        return out
-    weights = torch.ones(32, dtype=torch.int64, device=device) << torch.arange(32, dtype=torch.int64, device=device)
-    rows = max(1, (1 << 25) // (32 * n_words))
-    for g0 in range(0, n_groups, rows):
-        part = flags[g0:g0 + rows].to(device)
-        bits = torch.zeros((part.shape[0], 32 * n_words), dtype=torch.int64, device=device)
-        bits[:, :n] = part
-        out[g0:g0 + rows] = (bits.view(part.shape[0], n_words, 32) * weights).sum(dim=2).to(torch.int32)   # keeps the low 32 bits
-    return out
-
-
-def _group_masks_argument(masks, n_bits_of, what):
-    """The checks of a grouped search's `masks` that need no device: (packed, masks as tensor / array, G).  Packed words are verified
-    against the word count of n_bits_of() (`what` names it in the message)."""
-    if not torch.is_tensor(masks) and not isinstance(masks, np.ndarray):
-        masks = np.asarray(masks)
-    packed = (isinstance(masks, np.ndarray) and masks.dtype in (np.uint32, np.int32)) or \
-        (torch.is_tensor(masks) and masks.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
-    if not packed:
-        is_bool = (isinstance(masks, np.ndarray) and masks.dtype == np.bool_) or (torch.is_tensor(masks) and masks.dtype == torch.bool)
-        if not is_bool:
-            raise ValueError("masks must be a bool [groups, n_bits] tensor / array, or packed int32 / uint32 words [groups, words] "
-                             f"(pack_doc_masks), got {getattr(masks, 'dtype', type(masks).__name__)}")
-    if (masks.dim() if torch.is_tensor(masks) else masks.ndim) != 2:
-        raise ValueError(f"expected 2-D masks [groups, ...], got {tuple(masks.shape)}")
-    if masks.shape[0] < 1:
-        raise ValueError("masks must hold at least one group")
-    if packed:
-        n_bits = int(n_bits_of())
-        if masks.shape[1] != (n_bits + 31) // 32:
-            raise ValueError(f"a packed mask of this index holds {(n_bits + 31) // 32} words ({what} = {n_bits}), got {masks.shape[1]}")
-    return packed, masks, int(masks.shape[0])
-
-
-def _query_group_argument(query_group, nq, n_groups):
-    """query_group as given -> an int array / tensor of nq entries, checked without a device (the library checks the range)."""
-    if not torch.is_tensor(query_group) and not isinstance(query_group, np.ndarray):
-        query_group = np.asarray(query_group)
-    is_int = (not query_group.dtype.is_floating_point and not query_group.dtype.is_complex and query_group.dtype != torch.bool) \
-        if torch.is_tensor(query_group) else query_group.dtype.kind in "iu"
-    if not is_int:
-        raise ValueError(f"query_group must hold integer group ids, got {query_group.dtype}")
-    if (query_group.dim() if torch.is_tensor(query_group) else query_group.ndim) != 1 or query_group.shape[0] != nq:
-        raise ValueError(f"query_group must hold one group id per query ({nq}), got {tuple(query_group.shape)}")
-    return query_group
-
-
-def doc_mask_from_list(ids, n_bits, device=None):
-    """Document indices (int64, any order, repeats allowed; tensor / array / list) -> the bitmap over [0, n_bits) as int32 words on the
-    device (sr_doc_mask_from_list).  An entry outside [0, n_bits): ValueError."""
-    _lib.require_gpu()
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    ids, m = _subset(ids, device)
-    words = torch.empty((max(1, (int(n_bits) + 31) // 32),), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.load().sr_doc_mask_from_list(_ptr(ids), m, _ptr(words), int(n_bits), _lib.stream_ptr()), "sr_doc_mask_from_list")
-    return words[:(int(n_bits) + 31) // 32]
-
-
-def doc_list_from_mask(words, n_bits, capacity=None):
-    """The set bits below n_bits of a packed bitmap (int32 / uint32 words, tensor or array) as an ascending int64 tensor on the device
-    (sr_doc_list_from_mask).  capacity (None: room for every bit): at most that many entries are written; returns (list, count) with
-    count = the number of set bits whatever the capacity."""
-    _lib.require_gpu()
-    words = _mask_words(words, torch.device("cuda", torch.cuda.current_device()) if not (torch.is_tensor(words) and words.is_cuda) else words.device)
-    n_bits = int(n_bits)
-    if words.numel() < (n_bits + 31) // 32:
-        raise ValueError(f"{n_bits} bits need {(n_bits + 31) // 32} words, got {words.numel()}")
-    cap = n_bits if capacity is None else int(capacity)
-    out = torch.empty((max(1, cap),), dtype=torch.int64, device=words.device)
-    count = torch.zeros(1, dtype=torch.int64, device=words.device)
-    if words.numel() == 0:
-        words = torch.zeros(1, dtype=torch.int32, device=words.device)
-    with torch.cuda.device(words.device):
-        _lib.check(_lib.load().sr_doc_list_from_mask(_ptr(words), n_bits, _ptr(out), cap, _ptr(count), _lib.stream_ptr()), "sr_doc_list_from_mask")
-    c = int(count.item())
-    return out[:min(c, cap)], c
-
-
-def _mask_words(words, device):
-    """Packed bitmap words (np.uint32 / np.int32 array, or an int32 / uint32 tensor) -> a contiguous int32 tensor on the device."""
-    if isinstance(words, np.ndarray):
-        if words.dtype not in (np.uint32, np.int32):
-            raise ValueError(f"packed mask words must be uint32 or int32, got {words.dtype}")
-        words = torch.from_numpy(np.ascontiguousarray(words).view(np.int32))
-    elif words.dtype == getattr(torch, "uint32", None):
-        words = words.view(torch.int32)
-    elif words.dtype != torch.int32:
-        raise ValueError(f"packed mask words must be uint32 or int32, got {words.dtype}")
-    if words.dim() != 1:
-        raise ValueError(f"expected 1-D mask words, got {tuple(words.shape)}")
-    return words.to(device).contiguous()
-
-
-def _mask_argument(mask, n_bits_of, what):
-    """The checks of a `mask=` argument that need no device: (packed, mask as tensor / array).  n_bits_of() - asked only for a packed
-    mask - is the number of bits the index expects (`what` names it in the message); the word count is verified against it."""
-    if not torch.is_tensor(mask) and not isinstance(mask, np.ndarray):
-        mask = np.asarray(mask)
-    packed = (isinstance(mask, np.ndarray) and mask.dtype in (np.uint32, np.int32)) or \
-        (torch.is_tensor(mask) and mask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
-    if not packed:
-        is_bool = (isinstance(mask, np.ndarray) and mask.dtype == np.bool_) or (torch.is_tensor(mask) and mask.dtype == torch.bool)
-        if not is_bool:
-            raise ValueError("mask must be a bool tensor / array over the documents, or packed int32 / uint32 words (pack_doc_mask), got "
-                             f"{getattr(mask, 'dtype', type(mask).__name__)}")
-    if (mask.dim() if torch.is_tensor(mask) else mask.ndim) != 1:
-        raise ValueError(f"expected a 1-D mask, got {tuple(mask.shape)}")
-    if packed:
-        n, n_bits = (mask.numel() if torch.is_tensor(mask) else mask.size), int(n_bits_of())
-        if n != (n_bits + 31) // 32:
-            raise ValueError(f"a packed mask of this index holds {(n_bits + 31) // 32} words ({what} = {n_bits}), got {n}")
-    return packed, mask
-
-
-def _mask_on_device(packed, mask, n_bits_of, device):
-    """(int32 words on the device, n_bits) of a mask that went through _mask_argument; a bool mask is packed on the device and its own
-    length is n_bits (the library compares it with the index)."""
-    if packed:
-        n_bits, words = int(n_bits_of()), _mask_words(mask, device)
-    else:
-        flags = _to_dev(mask, torch.bool, device)
-        n_bits, words = flags.numel(), pack_doc_mask(flags)
-    return words, n_bits
-
-
-def _valid(t):
-    """t, or one zero of its type where t is empty: a valid pointer for the C ABI."""
-    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
-
-
-def doc_mask_remap(words, n_src_bits, map, n_dst_bits):
-    """A bitmap carried over to another numbering (sr_doc_mask_remap): bit i of the result = bit map[i] of `words` (packed int32 / uint32
-    words over n_src_bits bits) where 0 <= map[i] < n_src_bits, else 0; map int64 [n_dst_bits].  Returns int32 words
-    [ceil(n_dst_bits / 32)] on the device."""
-    _lib.require_gpu()
-    device = words.device if torch.is_tensor(words) and words.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    words = _mask_words(words, device)
-    n_src_bits, n_dst_bits = int(n_src_bits), int(n_dst_bits)
-    if words.numel() < (n_src_bits + 31) // 32:
-        raise ValueError(f"{n_src_bits} bits need {(n_src_bits + 31) // 32} words, got {words.numel()}")
-    map = _to_dev(map, torch.int64, device)
-    if map.dim() != 1 or map.numel() != n_dst_bits:
-        raise ValueError(f"expected a map of {n_dst_bits} entries, got {tuple(map.shape)}")
-    out = torch.empty((max(1, (n_dst_bits + 31) // 32),), dtype=torch.int32, device=device)
-    keep = [t if t.numel() else torch.zeros(1, dtype=t.dtype, device=device) for t in (words, map)]      # valid pointers
-    with torch.cuda.device(device):
-        _lib.check(_lib.load().sr_doc_mask_remap(_ptr(keep[0]), n_src_bits, _ptr(keep[1]), n_dst_bits, _ptr(out), _lib.stream_ptr()),
-                   "sr_doc_mask_remap")
-    return out[:(n_dst_bits + 31) // 32]
-
-
-def allowed_positions(allowed_ids, position_of, what="document id"):
-    """External document ids (any order, duplicates allowed) -> sorted unique positions, np.int64: the allow-list the subset searches take.
-    position_of maps an id to its position (a dict's .get, or any callable that returns None for an unknown id); an unknown id raises
-    ValueError naming it."""
-    out = set()
-    for d in allowed_ids:
-        p = position_of(d)
-        if p is None:
-            raise ValueError(f"allowed_ids: unknown {what} {d!r}")
-        out.add(int(p))
-    return np.fromiter(sorted(out), dtype=np.int64, count=len(out))
-
-
-def read_allowed_ids_file(path):
-    """One document id per line (surrounding white space and empty lines ignored) -> list of str, in file order."""
-    with open(path) as f:
-        return [line.strip() for line in f if line.strip()]
+    return cand_indptr, _valid(cand_ids), total
 
 
 def range_sort(lims, scores, ids):
@@ -305,6 +98,29 @@ class DenseIndexHIP:
         self.precision = "fp32"          # what set_precision / set_batch_invariant last set (the C ABI has no getters)
         self.batch_invariant = False
 
+    def _call(self, name, *args, stream=True):
+        """The C-ABI entry `name` on this index, on its device (doc_filter._call)."""
+        _call(self.device, name, self._h, *args, stream=stream, lib=self.lib)
+
+    def _check_queries(self, queries):
+        """dtype and shape of a query tensor; returns nq."""
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
+        return queries.shape[0]
+
+    def _queries(self, queries):
+        """The one check of a query tensor: dtype and shape, then cuda, then the index's device; returns it contiguous."""
+        self._check_queries(queries)
+        if not queries.is_cuda:
+            raise ValueError("queries must be a cuda tensor")
+        if queries.device != self.device:
+            raise ValueError(f"queries live on {queries.device}, the index on {self.device}")
+        return queries.contiguous()
+
+    def _mask(self, mask, ndim=1):
+        """The host step of a mask= / masks= argument of this index (doc_filter.mask_argument)."""
+        return mask_argument(mask, lambda: self.id_end, "id_end", ndim)
+
     @staticmethod
     def _round_to_f16(rows, row0=0):
         """fp32 cuda rows -> float16 (round to nearest even, on the device); ValueError naming the first row in which a finite
@@ -331,13 +147,8 @@ class DenseIndexHIP:
         rows = rows.contiguous()
         if id_base is None:
             id_base = self.ntotal
-        with torch.cuda.device(self.device):
-            if rows.dtype == torch.float16:
-                _lib.check(self.lib.sr_dense_index_add_f16(self._h, _ptr(rows), rows.shape[0], int(id_base), int(id_stride)),
-                           "sr_dense_index_add_f16")
-            else:
-                _lib.check(self.lib.sr_dense_index_add(self._h, _ptr(rows), rows.shape[0], int(id_base), int(id_stride)),
-                           "sr_dense_index_add")
+        self._call("sr_dense_index_add_f16" if rows.dtype == torch.float16 else "sr_dense_index_add", _ptr(rows), rows.shape[0], int(id_base),
+                   int(id_stride), stream=False)
         self._segments.append(rows)
 
     def stored_dtype(self):
@@ -368,22 +179,14 @@ class DenseIndexHIP:
         tmp = pinned.to(self.device, non_blocking=True)
         dev[r0:r1].copy_(self._round_to_f16(tmp, r0))
 
-    def add_host_rows(self, rows, buffer_size=50000, id_base=None, id_stride=1, piece_bytes=64 << 20, n_buffers=8, n_threads=8):
-        """rows: np.float32 [n, dim] - an in-memory array or an np.load(..., mmap_mode="r") view of a shard file.
-        Streamed into ONE HBM segment through a ring of pinned staging buffers: worker threads copy pieces of the
-        source into pinned memory (numpy releases the GIL for the copy, a memory-mapped source is read from the page
-        cache / the file right there) and queue the H2D copy of each piece on a side stream, so file reads, host
-        copies and PCIe transfers overlap and no second host copy of the matrix ever exists (the reference
-        concatenates every shard on the host, eval_dense.py:113-121, then faiss copies it again, indexer.py:203).
-        `buffer_size` (rows per add, indexer.py:198-208) is accepted for signature compatibility."""
+    def _add_staged(self, src_dtype, n, fill, id_base, id_stride, piece_bytes, n_buffers, n_threads):
+        """n host rows of `src_dtype` -> ONE HBM segment through a ring of pinned staging buffers: worker threads have
+        fill(pinned_view, r0, r1) put rows [r0, r1) of the source into a buffer (a numpy view of its first r1 - r0 rows; the GIL is
+        released inside) and queue the H2D copy of each piece on a side stream, so reads, host copies and PCIe transfers overlap and
+        no second host copy of the matrix ever exists."""
         import threading
         from concurrent.futures import ThreadPoolExecutor
-        if rows.dtype not in (np.float32, np.float16) or rows.ndim != 2 or rows.shape[1] != self.dim:
-            if rows.ndim != 2 or rows.shape[1] != self.dim:
-                raise ValueError(f"expected [n, {self.dim}] rows, got {rows.shape}")
-            rows = np.asarray(rows, dtype=np.float32)
-        n = rows.shape[0]
-        stage_dt, dev, convert = self._staging(rows.dtype, n)
+        stage_dt, dev, convert = self._staging(src_dtype, n)
         if n == 0:
             self.add_device_rows(dev, id_base=id_base, id_stride=id_stride)
             return
@@ -403,7 +206,7 @@ class DenseIndexHIP:
                 b = i % n_buffers
                 with locks[b]:                          # pieces i, i + n_buffers, ... share buffer b, in order
                     free[b].synchronize()               # its previous H2D copy has left the buffer
-                    np.copyto(bufs[b].numpy()[:r1 - r0], rows[r0:r1])
+                    fill(bufs[b].numpy()[:r1 - r0], r0, r1)
                     with torch.cuda.device(self.device), torch.cuda.stream(side):
                         self._h2d_piece(dev, r0, r1, bufs[b][:r1 - r0], convert)
                         free[b].record(side)
@@ -412,56 +215,43 @@ class DenseIndexHIP:
             side.synchronize()
         self.add_device_rows(dev, id_base=id_base, id_stride=id_stride)
 
+    def add_host_rows(self, rows, buffer_size=50000, id_base=None, id_stride=1, piece_bytes=64 << 20, n_buffers=8, n_threads=8):
+        """rows: np.float32 [n, dim] - an in-memory array or an np.load(..., mmap_mode="r") view of a shard file.
+        Streamed into ONE HBM segment through the pinned ring (_add_staged): numpy releases the GIL for the copy of a piece, a
+        memory-mapped source is read from the page cache / the file right there (the reference concatenates every shard on the
+        host, eval_dense.py:113-121, then faiss copies it again, indexer.py:203).
+        `buffer_size` (rows per add, indexer.py:198-208) is accepted for signature compatibility."""
+        if rows.dtype not in (np.float32, np.float16) or rows.ndim != 2 or rows.shape[1] != self.dim:
+            if rows.ndim != 2 or rows.shape[1] != self.dim:
+                raise ValueError(f"expected [n, {self.dim}] rows, got {rows.shape}")
+            rows = np.asarray(rows, dtype=np.float32)
+        self._add_staged(rows.dtype, rows.shape[0], lambda view, r0, r1: np.copyto(view, rows[r0:r1]), id_base, id_stride, piece_bytes,
+                         n_buffers, n_threads)
+
     def add_npy_file(self, path, id_base=None, id_stride=1, piece_bytes=64 << 20, n_buffers=8, n_threads=8):
-        """One embs_{rank}_{chunk}.npy shard file -> one HBM segment, never loaded whole on the host: worker threads
-        `preadv` pieces of the file straight into a ring of pinned staging buffers (one kernel copy out of the page cache,
-        no per-page mapping faults as a memory-mapped source costs, GIL released) and queue each piece's H2D copy on a side
-        stream."""
+        """One embs_{rank}_{chunk}.npy shard file -> one HBM segment, never loaded whole on the host: the ring's worker threads
+        `preadv` pieces of the file straight into the pinned staging buffers (one kernel copy out of the page cache, no per-page
+        mapping faults as a memory-mapped source costs, GIL released); a float16 shard moves half the bytes, file to HBM."""
         import os
-        import threading
-        from concurrent.futures import ThreadPoolExecutor
         arr = np.load(path, mmap_mode="r")              # header only: shape, dtype, data offset
         if arr.dtype not in (np.float32, np.float16) or arr.ndim != 2 or arr.shape[1] != self.dim or not arr.flags["C_CONTIGUOUS"]:
             return self.add_host_rows(np.ascontiguousarray(arr, dtype=np.float32), id_base=id_base, id_stride=id_stride)
-        n, offset0 = arr.shape[0], arr.offset
-        stage_dt, dev, convert = self._staging(arr.dtype, n)        # a float16 shard moves half the bytes, file to HBM
+        src_dtype, n, offset0, row_bytes = arr.dtype, arr.shape[0], arr.offset, arr.dtype.itemsize * self.dim
         del arr
-        if n == 0:
-            return self.add_device_rows(dev, id_base=id_base, id_stride=id_stride)
-        row_bytes = (2 if stage_dt == torch.float16 else 4) * self.dim
-        piece_rows = max(1, int(piece_bytes) // row_bytes)
-        pieces = [(r0, min(n, r0 + piece_rows)) for r0 in range(0, n, piece_rows)]
-        n_buffers = max(1, min(n_buffers, len(pieces)))
         fd = os.open(path, os.O_RDONLY)
-        try:
-            with torch.cuda.device(self.device):
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream(self.device))      # see add_host_rows
-                bufs = [torch.empty((piece_rows, self.dim), dtype=stage_dt, pin_memory=True) for _ in range(n_buffers)]
-                free = [torch.cuda.Event() for _ in range(n_buffers)]
-                locks = [threading.Lock() for _ in range(n_buffers)]
 
-                def move(i):
-                    r0, r1 = pieces[i]
-                    b = i % n_buffers
-                    with locks[b]:
-                        free[b].synchronize()
-                        view = memoryview(bufs[b].numpy()[:r1 - r0]).cast("B")
-                        got, want = 0, (r1 - r0) * row_bytes
-                        while got < want:
-                            k = os.preadv(fd, [view[got:want]], offset0 + r0 * row_bytes + got)
-                            if k <= 0:
-                                raise IOError(f"{path}: short read at row {r0}")
-                            got += k
-                        with torch.cuda.device(self.device), torch.cuda.stream(side):
-                            self._h2d_piece(dev, r0, r1, bufs[b][:r1 - r0], convert)
-                            free[b].record(side)
-                with ThreadPoolExecutor(max_workers=max(1, min(n_threads, n_buffers))) as pool:
-                    list(pool.map(move, range(len(pieces))))
-                side.synchronize()
+        def fill(view, r0, r1):
+            view = memoryview(view).cast("B")
+            got, want = 0, (r1 - r0) * row_bytes
+            while got < want:
+                k = os.preadv(fd, [view[got:want]], offset0 + r0 * row_bytes + got)
+                if k <= 0:
+                    raise IOError(f"{path}: short read at row {r0}")
+                got += k
+        try:
+            self._add_staged(src_dtype, n, fill, id_base, id_stride, piece_bytes, n_buffers, n_threads)
         finally:
             os.close(fd)
-        self.add_device_rows(dev, id_base=id_base, id_stride=id_stride)
 
     @property
     def ntotal(self):
@@ -486,8 +276,7 @@ class DenseIndexHIP:
         exact re-score, ~7x faster for batches > 64 queries, one fp16 plane of the corpus in HBM), "bf16x3" / "bf16x6"
         (split-bf16 scores, not bit-identical; not available on an index of fp16 rows: SrHipError)."""
         code = {"fp32": 0, "bf16x3": 1, "bf16x6": 2, "fp32_filtered": 3}[mode]
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_index_set_precision(self._h, code), "sr_dense_index_set_precision")
+        self._call("sr_dense_index_set_precision", code, stream=False)
         self.precision = mode
 
     def filter_stats(self):
@@ -508,48 +297,22 @@ class DenseIndexHIP:
         ranking with every other document removed, cut to k (include/sr_hip.h sr_dense_search_subset); an id outside the index or
         out of order: ValueError naming its position.  mask: the same filter as a bitmap over [0, id_end) - a bool tensor / array
         of length id_end (packed on the device), or int32 / uint32 words already packed (pack_doc_mask) - with exactly the result
-        of `subset` = the set positions (sr_dense_search_masked); a set bit that names no document: ValueError naming it.  Not both."""
-        if subset is not None and mask is not None:
-            raise ValueError("search: pass subset or mask, not both")
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
-        if not queries.is_cuda:
-            raise ValueError("queries must be a cuda tensor")
-        queries = queries.contiguous()
-        nq = queries.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-        if queries.device != self.device:
-            raise ValueError(f"queries live on {queries.device}, the index on {self.device}")
-        if subset is not None:
-            subset, m = _subset(subset, self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_dense_search_subset(self._h, _ptr(queries), nq, int(k), _ptr(subset), m, _ptr(scores), _ptr(ids),
-                                                           _lib.stream_ptr()), "sr_dense_search_subset")
-            return scores, ids
+        of `subset` = the set positions (sr_dense_search_masked); a set bit that names no document: ValueError naming it.  One of
+        the two at most."""
+        one_filter("search", subset=subset, mask=mask)
         if mask is not None:
-            packed = (isinstance(mask, np.ndarray) and mask.dtype in (np.uint32, np.int32)) or \
-                (torch.is_tensor(mask) and mask.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)))
-            if packed:
-                n_bits = self.id_end
-                words = _mask_words(mask, self.device)
-                if words.numel() != (n_bits + 31) // 32:
-                    raise ValueError(f"a packed mask of this index holds {(n_bits + 31) // 32} words (id_end = {n_bits}), got {words.numel()}")
-            else:
-                flags = _to_dev(mask, torch.bool, self.device)
-                if flags.dim() != 1:
-                    raise ValueError(f"expected a 1-D mask, got {tuple(flags.shape)}")
-                n_bits = flags.numel()            # the library compares it with id_end
-                words = pack_doc_mask(flags)
-            if words.numel() == 0:
-                words = torch.zeros(1, dtype=torch.int32, device=self.device)      # keep a valid pointer
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_dense_search_masked(self._h, _ptr(queries), nq, int(k), _ptr(words), n_bits, _ptr(scores), _ptr(ids),
-                                                           _lib.stream_ptr()), "sr_dense_search_masked")
-            return scores, ids
-        with torch.cuda.device(self.device):      # the library allocates its workspace on the current device
-            _lib.check(self.lib.sr_dense_search(self._h, _ptr(queries), nq, int(k), _ptr(scores), _ptr(ids),
-                                                _lib.stream_ptr()), "sr_dense_search")
+            mask = self._mask(mask)
+        queries = self._queries(queries)
+        nq = queries.shape[0]
+        filt = None
+        if subset is not None:
+            filt = ("_subset",) + _subset(subset, self.device)
+        elif mask is not None:
+            filt = ("_masked",) + mask_on_device(*mask, self.device)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        suffix, spliced = _filter_args(filt)
+        self._call("sr_dense_search" + suffix, _ptr(queries), nq, int(k), *spliced, _ptr(scores), _ptr(ids))
         return scores, ids
 
     def search_grouped(self, queries, k, masks, query_group):
@@ -559,40 +322,18 @@ class DenseIndexHIP:
         group's queries are exactly what search(those queries, k, mask=masks[g]) returns.  1 <= k <= sr_max_topk().  Wrong shapes, a wrong
         word count, a length mismatch or non-integer groups: ValueError before anything is uploaded; a group id outside [0, G) or a set
         bit that names no document: ValueError naming the query / the (group, bit), every row of the result is then padding."""
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
-        nq = queries.shape[0]
-        packed, masks, n_groups = _group_masks_argument(masks, lambda: self.id_end, "id_end")
-        query_group = _query_group_argument(query_group, nq, n_groups)
-        if not queries.is_cuda:
-            raise ValueError("queries must be a cuda tensor")
-        if queries.device != self.device:
-            raise ValueError(f"queries live on {queries.device}, the index on {self.device}")
-        queries = queries.contiguous()
-        if packed:
-            n_bits = self.id_end
-            if isinstance(masks, np.ndarray):
-                masks = torch.from_numpy(np.ascontiguousarray(masks).view(np.int32))
-            elif masks.dtype != torch.int32:
-                masks = masks.view(torch.int32)
-            words = masks.to(self.device).contiguous()
-        else:
-            n_bits = int(masks.shape[1])              # the library compares it with id_end
-            words = pack_doc_masks(masks, self.device)
+        masks = self._mask(masks, ndim=2)
+        nq = self._check_queries(queries)
+        query_group = query_group_argument(query_group, nq)
+        queries = self._queries(queries)
+        words, n_bits = mask_on_device(*masks, self.device)
         # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
-        groups = _to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        groups = _valid(_to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32))
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_search_grouped(self._h, _ptr(queries), nq, int(k), _ptr(_valid(words)), n_groups, n_bits,
-                                                        _ptr(_valid(groups)), _ptr(scores), _ptr(ids), _lib.stream_ptr()),
-                       "sr_dense_search_grouped")
+        self._call("sr_dense_search_grouped", _ptr(queries), nq, int(k), _ptr(words), int(masks[0].shape[0]), n_bits, _ptr(groups),
+                   _ptr(scores), _ptr(ids))
         return scores, ids
-
-    def _range_mask(self, mask):
-        """(words, n_bits) on the device of a range search's mask=, checked as far as possible before anything is uploaded."""
-        packed, mask = _mask_argument(mask, lambda: self.id_end, "id_end")
-        return _mask_on_device(packed, mask, lambda: self.id_end, self.device)
 
     def range_search(self, queries, thresholds, sort=False, mask=None):
         """Every document scoring above a threshold (faiss's IndexFlatIP.range_search; include/sr_hip.h sr_dense_range_count / _fill):
@@ -603,9 +344,10 @@ class DenseIndexHIP:
         document): a bitmap over [0, id_end) in the forms `search(mask=)` takes - only documents whose bit is set are returned
         (sr_dense_range_count_masked / _fill_masked; a set bit that names no document is ignored); one mask for all queries."""
         if mask is not None:
-            mask, n_bits = self._range_mask(mask)     # packed once, shared by the two halves
+            words, n_bits = mask_on_device(*self._mask(mask), self.device)     # packed once, shared by the two halves
             if n_bits != self.id_end:
                 raise ValueError(f"a mask of this index holds {self.id_end} flags (id_end), got {n_bits}")
+            mask = words[:(n_bits + 31) // 32]        # the packed words themselves (an empty bitmap: no words)
         queries, thr, lims, n = self.range_count(queries, thresholds, mask=mask)
         scores, ids = self.range_fill(queries, thr, lims, n, mask=mask)
         if sort:
@@ -617,48 +359,25 @@ class DenseIndexHIP:
         [nq], lims int64 [nq + 1], total) - the contiguous tensors range_fill takes, and the sizes of the lists before anything of their
         size is allocated."""
         if mask is not None:
-            packed, mask = _mask_argument(mask, lambda: self.id_end, "id_end")
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
-        if not queries.is_cuda or queries.device != self.device:
-            raise ValueError(f"queries must live on {self.device}")
-        queries = queries.contiguous()
+            mask = self._mask(mask)
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        if isinstance(thresholds, (int, float)):
-            thr = torch.full((nq,), float(thresholds), dtype=torch.float32, device=self.device)
-        else:
-            thr = _to_dev(thresholds, torch.float32, self.device)
-            if thr.dim() != 1 or thr.numel() != nq:
-                raise ValueError(f"expected {nq} thresholds, got {tuple(thr.shape)}")
+        thr = _thresholds(thresholds, nq, self.device)
         lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
-        if mask is not None:
-            words, n_bits = _mask_on_device(packed, mask, lambda: self.id_end, self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_dense_range_count_masked(self._h, _ptr(queries), nq, _ptr(thr), _ptr(_valid(words)), n_bits, _ptr(lims),
-                                                                ctypes.byref(total), _lib.stream_ptr()), "sr_dense_range_count_masked")
-            return queries, thr, lims, total.value
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_range_count(self._h, _ptr(queries), nq, _ptr(thr), _ptr(lims), ctypes.byref(total),
-                                                     _lib.stream_ptr()), "sr_dense_range_count")
+        filt = None if mask is None else ("_masked",) + mask_on_device(*mask, self.device)
+        suffix, spliced = _filter_args(filt)
+        self._call("sr_dense_range_count" + suffix, _ptr(queries), nq, _ptr(thr), *spliced, _ptr(lims), ctypes.byref(total))
         return queries, thr, lims, total.value
 
     def range_fill(self, queries, thr, lims, n, mask=None):
         """The second half (sr_dense_range_fill; under a mask sr_dense_range_fill_masked) for what the preceding range_count on this index
         returned, under the mask that count was given: (scores fp32 [n], ids int64 [n])."""
-        if mask is not None:
-            words, n_bits = self._range_mask(mask)
+        filt = None if mask is None else ("_masked",) + mask_on_device(*self._mask(mask), self.device)
+        suffix, spliced = _filter_args(filt)
         scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
         ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
-        if mask is not None:
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_dense_range_fill_masked(self._h, _ptr(queries), queries.shape[0], _ptr(thr), _ptr(_valid(words)), n_bits,
-                                                               _ptr(lims), _ptr(scores), _ptr(ids), n, _lib.stream_ptr()),
-                           "sr_dense_range_fill_masked")
-            return scores[:n], ids[:n]
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_range_fill(self._h, _ptr(queries), queries.shape[0], _ptr(thr), _ptr(lims), _ptr(scores), _ptr(ids), n,
-                                                    _lib.stream_ptr()), "sr_dense_range_fill")
+        self._call("sr_dense_range_fill" + suffix, _ptr(queries), queries.shape[0], _ptr(thr), *spliced, _ptr(lims), _ptr(scores), _ptr(ids), n)
         return scores[:n], ids[:n]
 
     def score_pairs(self, queries, cand_indptr, cand_ids):
@@ -666,29 +385,21 @@ class DenseIndexHIP:
         cand_ids[cand_indptr[q]:cand_indptr[q + 1]] (int64, the ids `search` returns; ragged, empty lists and repeats allowed, any
         length).  Returns fp32 cuda [total] - for every nq the fmaf chain of the exact score kernel, i.e. what `search` returns for
         that pair with more than 64 queries (include/sr_hip.h sr_dense_score_pairs).  An id outside the index: ValueError."""
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"expected float32 [nq, {self.dim}] queries, got {queries.dtype} {tuple(queries.shape)}")
-        if not queries.is_cuda or queries.device != self.device:
-            raise ValueError(f"queries must live on {self.device}")
-        queries = queries.contiguous()
+        queries = self._queries(queries)
         nq = queries.shape[0]
         cand_indptr, cand_ids, total = _candidates(cand_indptr, cand_ids, nq, self.device)
         out = torch.empty((max(1, total),), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_score_pairs(self._h, _ptr(queries), nq, _ptr(cand_indptr), _ptr(cand_ids), _ptr(out),
-                                                     _lib.stream_ptr()), "sr_dense_score_pairs")
+        self._call("sr_dense_score_pairs", _ptr(queries), nq, _ptr(cand_indptr), _ptr(cand_ids), _ptr(out))
         return out[:total]
 
     def search_begin(self, queries, k, share):
         """First half of a doc-sharded search (include/sr_hip.h sr_dense_search_begin): returns lower [nq] fp32 (cuda) - per
         query a value at least ceil(k / share) documents of this index reach exactly (-inf where the filter does not apply).
         `queries` must be the same contiguous tensor that is passed to search_finish."""
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim or not queries.is_cuda or not queries.is_contiguous():
+        if self._queries(queries) is not queries:
             raise ValueError(f"expected a contiguous float32 cuda tensor [nq, {self.dim}], got {queries.dtype} {tuple(queries.shape)}")
         lower = torch.empty((queries.shape[0],), dtype=torch.float32, device=queries.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_search_begin(self._h, _ptr(queries), queries.shape[0], int(k), int(share), _ptr(lower),
-                                                      _lib.stream_ptr()), "sr_dense_search_begin")
+        self._call("sr_dense_search_begin", _ptr(queries), queries.shape[0], int(k), int(share), _ptr(lower))
         return lower
 
     def search_finish(self, queries, k, threshold=None):
@@ -699,9 +410,7 @@ class DenseIndexHIP:
         ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
         if threshold is not None:
             threshold = threshold.to(device=queries.device, dtype=torch.float32).contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_dense_search_finish(self._h, _ptr(queries), nq, int(k), _ptr(threshold), _ptr(scores), _ptr(ids),
-                                                       _lib.stream_ptr()), "sr_dense_search_finish")
+        self._call("sr_dense_search_finish", _ptr(queries), nq, int(k), _ptr(threshold), _ptr(scores), _ptr(ids))
         return scores, ids
 
     def close(self):
@@ -728,24 +437,25 @@ class SparseIndexHIP:
         _lib.require_gpu()
         self.lib = _lib.load()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-
-        def to_dev(x, dt):
-            if isinstance(x, np.ndarray):
-                x = torch.from_numpy(np.ascontiguousarray(x))
-            return x.to(device=self.device, dtype=dt).contiguous()
-        self.indptr = to_dev(indptr, torch.int64)
-        self.doc_ids = to_dev(doc_ids, torch.int32)
-        self.vals = to_dev(vals, torch.float32)
-        if self.doc_ids.numel() == 0:  # keep valid pointers
-            self.doc_ids = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.vals = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.indptr = _to_dev(indptr, torch.int64, self.device)
+        self.doc_ids = _valid(_to_dev(doc_ids, torch.int32, self.device))
+        self.vals = _valid(_to_dev(vals, torch.float32, self.device))
         self.n_terms = self.indptr.numel() - 1
         self.n_docs = int(n_docs)
         self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_index_create(ctypes.byref(self._h), _ptr(self.indptr), _ptr(self.doc_ids),
-                                                       _ptr(self.vals), self.n_terms, self.n_docs, _lib.stream_ptr()),
-                       "sr_sparse_index_create")
+        _call(self.device, "sr_sparse_index_create", ctypes.byref(self._h), _ptr(self.indptr), _ptr(self.doc_ids), _ptr(self.vals), self.n_terms,
+              self.n_docs, lib=self.lib)
+
+    def _call(self, name, *args, stream=True):
+        """The C-ABI entry `name` on this index, on its device (doc_filter._call)."""
+        _call(self.device, name, self._h, *args, stream=stream, lib=self.lib)
+
+    def _query_csr(self, q_indptr, q_cols, q_vals):
+        """Queries as CSR (tensors / arrays, any device) -> ((indptr int64 [nq + 1], cols int32, vals fp32) on the device, cols and
+        vals with valid pointers, nq)."""
+        q_indptr = _to_dev(q_indptr, torch.int64, self.device)
+        q = (q_indptr, _valid(_to_dev(q_cols, torch.int32, self.device)), _valid(_to_dev(q_vals, torch.float32, self.device)))
+        return q, q_indptr.numel() - 1
 
     def set_workspace_limit(self, nbytes):
         _lib.check(self.lib.sr_sparse_index_set_workspace_limit(self._h, int(nbytes)))
@@ -767,9 +477,7 @@ class SparseIndexHIP:
 
     def cert_record_keys(self, enable):
         """Test hook: keep the stage-1 keys of every (query, doc) pair of the following searches."""
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_index_cert_debug(self._h, 1 if enable else 0, None, 0, None, 0, None, None),
-                       "sr_sparse_index_cert_debug")
+        self._call("sr_sparse_index_cert_debug", 1 if enable else 0, None, 0, None, 0, None, None, stream=False)
 
     def cert_recorded_keys(self, nq):
         """(keys uint16 [nq_pad, n_tiles * 1024], consts fp32 [nq_pad, 6] = (c_q, s_q, rare terms, query terms, rare terms left out, the k-th best
@@ -779,10 +487,8 @@ class SparseIndexHIP:
         keys = np.empty((nq_pad, stride), dtype=np.uint16)
         consts = np.empty((nq_pad, 6), dtype=np.float32)
         vs, T = ctypes.c_float(0), ctypes.c_int32(0)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_index_cert_debug(self._h, 2, keys.ctypes.data_as(ctypes.c_void_p), keys.size,
-                                                           consts.ctypes.data_as(ctypes.c_void_p), nq_pad, ctypes.byref(vs), ctypes.byref(T)),
-                       "sr_sparse_index_cert_debug")
+        self._call("sr_sparse_index_cert_debug", 2, keys.ctypes.data_as(ctypes.c_void_p), keys.size, consts.ctypes.data_as(ctypes.c_void_p),
+                   nq_pad, ctypes.byref(vs), ctypes.byref(T), stream=False)
         return keys, consts, vs.value, T.value
 
     _CERT_BUFFERS = {"dslot": (1, np.int32), "vmax": (2, np.float32), "d16": (3, np.float16), "P": (4, np.uint32), "S": (5, np.uint32),
@@ -796,11 +502,9 @@ class SparseIndexHIP:
         "nq_pad", "k", "k_eff", "vscale"}; any other name of _CERT_BUFFERS -> that buffer as a flat numpy array of its element type."""
         what, dt = (0, np.int64) if name == "info" else self._CERT_BUFFERS[name]
         n = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_index_cert_readout(self._h, what, None, 0, ctypes.byref(n)), "sr_sparse_index_cert_readout")
-            out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
-            _lib.check(self.lib.sr_sparse_index_cert_readout(self._h, what, out.ctypes.data_as(ctypes.c_void_p), out.nbytes, ctypes.byref(n)),
-                       "sr_sparse_index_cert_readout")
+        self._call("sr_sparse_index_cert_readout", what, None, 0, ctypes.byref(n), stream=False)
+        out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
+        self._call("sr_sparse_index_cert_readout", what, out.ctypes.data_as(ctypes.c_void_p), out.nbytes, ctypes.byref(n), stream=False)
         if name != "info":
             return out
         keys = ("T", "KS", "n_tiles", "e_stride", "V", "N", "nnz", "nq", "nq_pad", "k", "k_eff")
@@ -812,67 +516,36 @@ class SparseIndexHIP:
         """Switch the query-block kernel's work counters on / off; returns what was counted since the last call:
         {"dense_columns_loaded", "dense_column_applications", "light_postings", "grouped_postings", "plan_entries", "workgroup_tiles"}."""
         out = (ctypes.c_uint64 * 6)()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_index_work_counters(self._h, 1 if enable else 0, out), "sr_sparse_index_work_counters")
+        self._call("sr_sparse_index_work_counters", 1 if enable else 0, out, stream=False)
         keys = ("dense_columns_loaded", "dense_column_applications", "light_postings", "grouped_postings", "plan_entries", "workgroup_tiles")
         return {k_: int(v) for k_, v in zip(keys, out)}
 
-    def _mask_argument(self, mask):
-        """The checks of `search(mask=)` that need no device: (packed, mask as tensor / array), the word count of a packed mask verified."""
-        return _mask_argument(mask, lambda: self.n_docs, "n_docs")
+    def _mask(self, mask):
+        """The host step of a mask= argument of this index (doc_filter.mask_argument)."""
+        return mask_argument(mask, lambda: self.n_docs, "n_docs")
 
     def search(self, q_indptr, q_cols, q_vals, k, threshold=0.0, id_base=0, id_stride=1, subset=None, mask=None):
         """Queries as CSR tensors. Returns (scores [nq,k], ids [nq,k], counts [nq]) cuda tensors.  subset (None: every document):
         strictly ascending int64 document positions in [0, n_docs), one allow-list for all queries (include/sr_hip.h
         sr_sparse_search_subset); a position outside the index or out of order: ValueError naming it.  mask: the same filter as a
         bitmap over [0, n_docs) - a bool tensor / array of length n_docs (packed on the device), or int32 / uint32 words already
-        packed (pack_doc_mask) - with exactly the result of `subset` = the set positions (sr_sparse_search_masked).  Not both."""
-        if subset is not None and mask is not None:
-            raise ValueError("search: pass subset or mask, not both")
-        packed, mask = self._mask_argument(mask) if mask is not None else (False, None)
-
-        def to_dev(x, dt):
-            if isinstance(x, np.ndarray):
-                x = torch.from_numpy(np.ascontiguousarray(x))
-            return x.to(device=self.device, dtype=dt).contiguous()
-        q_indptr = to_dev(q_indptr, torch.int64)
-        q_cols = to_dev(q_cols, torch.int32)
-        q_vals = to_dev(q_vals, torch.float32)
-        nq = q_indptr.numel() - 1
-        if q_cols.numel() == 0:
-            q_cols = torch.zeros(1, dtype=torch.int32, device=self.device)
-            q_vals = torch.zeros(1, dtype=torch.float32, device=self.device)
+        packed (pack_doc_mask) - with exactly the result of `subset` = the set positions (sr_sparse_search_masked).  One of the two
+        at most."""
+        one_filter("search", subset=subset, mask=mask)
+        if mask is not None:
+            mask = self._mask(mask)
+        q, nq = self._query_csr(q_indptr, q_cols, q_vals)
+        filt = None
+        if mask is not None:
+            filt = ("_masked",) + mask_on_device(*mask, self.device)
+        elif subset is not None:
+            filt = ("_subset",) + _subset(subset, self.device)
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         counts = torch.empty((nq,), dtype=torch.int32, device=self.device)
-        if mask is not None:
-            if packed:
-                n_bits = self.n_docs
-                words = _mask_words(mask, self.device)
-            else:
-                flags = _to_dev(mask, torch.bool, self.device)
-                n_bits = flags.numel()            # the library compares it with n_docs
-                words = pack_doc_mask(flags)
-            if words.numel() == 0:
-                words = torch.zeros(1, dtype=torch.int32, device=self.device)      # keep a valid pointer
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_sparse_search_masked(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, int(k),
-                                                            float(threshold), _ptr(words), n_bits, int(id_base), int(id_stride),
-                                                            _ptr(scores), _ptr(ids), _ptr(counts), _lib.stream_ptr()),
-                           "sr_sparse_search_masked")
-            return scores, ids, counts
-        if subset is not None:
-            subset, m = _subset(subset, self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_sparse_search_subset(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, int(k),
-                                                            float(threshold), _ptr(subset), m, int(id_base), int(id_stride),
-                                                            _ptr(scores), _ptr(ids), _ptr(counts), _lib.stream_ptr()),
-                           "sr_sparse_search_subset")
-            return scores, ids, counts
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_search(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, int(k),
-                                                 float(threshold), int(id_base), int(id_stride), _ptr(scores), _ptr(ids),
-                                                 _ptr(counts), _lib.stream_ptr()), "sr_sparse_search")
+        suffix, spliced = _filter_args(filt)
+        self._call("sr_sparse_search" + suffix, *map(_ptr, q), nq, int(k), float(threshold), *spliced, int(id_base), int(id_stride),
+                   _ptr(scores), _ptr(ids), _ptr(counts))
         return scores, ids, counts
 
     def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False, mask=None):
@@ -884,47 +557,22 @@ class SparseIndexHIP:
         chain of `score_pairs`.  sort=True: each list by score descending, ties by ascending id (range_sort).  mask (None: every
         document): a bitmap over [0, n_docs) in the forms `search(mask=)` takes - only documents whose bit is set are returned
         (sr_sparse_range_count_masked / _fill_masked), a document without a common term included when the threshold is negative."""
-        packed, mask = self._mask_argument(mask) if mask is not None else (False, None)
-        q_indptr = _to_dev(q_indptr, torch.int64, self.device)
-        q_cols = _to_dev(q_cols, torch.int32, self.device)
-        q_vals = _to_dev(q_vals, torch.float32, self.device)
-        nq = q_indptr.numel() - 1
-        if q_cols.numel() == 0:
-            q_cols = torch.zeros(1, dtype=torch.int32, device=self.device)
-            q_vals = torch.zeros(1, dtype=torch.float32, device=self.device)
-        if isinstance(thresholds, (int, float, np.floating, np.integer)):
-            thr = torch.full((max(1, nq),), float(thresholds), dtype=torch.float32, device=self.device)
-        else:
-            thr = _to_dev(thresholds, torch.float32, self.device)
-            if thr.dim() != 1 or thr.numel() != nq:
-                raise ValueError(f"expected {nq} thresholds, got {tuple(thr.shape)}")
+        if mask is not None:
+            mask = self._mask(mask)
+        q, nq = self._query_csr(q_indptr, q_cols, q_vals)
+        thr = _valid(_thresholds(thresholds, nq, self.device))
         if sort and int(id_base) + (self.n_docs - 1) * int(id_stride) >= 1 << 32:
             raise ValueError("sort=True orders by the search's 64-bit key, which holds ids below 2^32; sort the lists of larger ids yourself")
         lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
-        if mask is not None:
-            words, n_bits = _mask_on_device(packed, mask, lambda: self.n_docs, self.device)
-            words = _valid(words)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_sparse_range_count_masked(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(words),
-                                                                 n_bits, _ptr(lims), ctypes.byref(total), _lib.stream_ptr()),
-                           "sr_sparse_range_count_masked")
-                n = total.value
-                scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
-                ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
-                _lib.check(self.lib.sr_sparse_range_fill_masked(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(words),
-                                                                n_bits, _ptr(lims), int(id_base), int(id_stride), _ptr(scores), _ptr(ids), n,
-                                                                _lib.stream_ptr()), "sr_sparse_range_fill_masked")
-        else:
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.sr_sparse_range_count(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
-                                                          ctypes.byref(total), _lib.stream_ptr()), "sr_sparse_range_count")
-                n = total.value
-                scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
-                ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
-                _lib.check(self.lib.sr_sparse_range_fill(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(thr), _ptr(lims),
-                                                         int(id_base), int(id_stride), _ptr(scores), _ptr(ids), n, _lib.stream_ptr()),
-                           "sr_sparse_range_fill")
+        filt = None if mask is None else ("_masked",) + mask_on_device(*mask, self.device)
+        suffix, spliced = _filter_args(filt)
+        head = (*map(_ptr, q), nq, _ptr(thr), *spliced, _ptr(lims))
+        self._call("sr_sparse_range_count" + suffix, *head, ctypes.byref(total))
+        n = total.value
+        scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
+        ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
+        self._call("sr_sparse_range_fill" + suffix, *head, int(id_base), int(id_stride), _ptr(scores), _ptr(ids), n)
         scores, ids = scores[:n], ids[:n]
         if sort:
             scores, ids = range_sort(lims, scores, ids)
@@ -934,18 +582,10 @@ class SparseIndexHIP:
         """Exact scores of given (query, document) pairs: queries as for `search`, candidates as for DenseIndexHIP.score_pairs (ids =
         document positions).  Returns fp32 cuda [total]: the reference's term-serial chain, no threshold, 0.0 where nothing matches
         (include/sr_hip.h sr_sparse_score_pairs).  An id outside [0, n_docs): ValueError."""
-        q_indptr = _to_dev(q_indptr, torch.int64, self.device)
-        q_cols = _to_dev(q_cols, torch.int32, self.device)
-        q_vals = _to_dev(q_vals, torch.float32, self.device)
-        nq = q_indptr.numel() - 1
-        if q_cols.numel() == 0:
-            q_cols = torch.zeros(1, dtype=torch.int32, device=self.device)
-            q_vals = torch.zeros(1, dtype=torch.float32, device=self.device)
+        q, nq = self._query_csr(q_indptr, q_cols, q_vals)
         cand_indptr, cand_ids, total = _candidates(cand_indptr, cand_ids, nq, self.device)
         out = torch.empty((max(1, total),), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.sr_sparse_score_pairs(self._h, _ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(cand_indptr),
-                                                      _ptr(cand_ids), _ptr(out), _lib.stream_ptr()), "sr_sparse_score_pairs")
+        self._call("sr_sparse_score_pairs", *map(_ptr, q), nq, _ptr(cand_indptr), _ptr(cand_ids), _ptr(out))
         return out[:total]
 
     def close(self):
@@ -965,7 +605,6 @@ def sparse_csr_build(rows, cols, vals, n_terms, n_docs=0, sort_docs=False):
     (indptr int64 [n_terms + 1], doc_ids int32, vals fp32) with sr_sparse_csr_build: this library's stable radix sort on the device.
     Replaces the per-posting append of IndexDictOfArray.add_batch_document (inverted_index.py:67-76)."""
     _lib.require_gpu()
-    lib = _lib.load()
     rows = rows.to(torch.int32).contiguous()
     cols = cols.to(torch.int32).contiguous()
     vals = vals.to(torch.float32).contiguous()
@@ -974,21 +613,17 @@ def sparse_csr_build(rows, cols, vals, n_terms, n_docs=0, sort_docs=False):
     indptr = torch.empty(int(n_terms) + 1, dtype=torch.int64, device=dev)
     out_rows = torch.empty(max(1, nnz), dtype=torch.int32, device=dev)
     out_vals = torch.empty(max(1, nnz), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_sparse_csr_build(_ptr(rows), _ptr(cols), _ptr(vals), nnz, int(n_terms), int(n_docs), 1 if sort_docs else 0,
-                                           _ptr(indptr), _ptr(out_rows), _ptr(out_vals), _lib.stream_ptr()), "sr_sparse_csr_build")
+    _call(dev, "sr_sparse_csr_build", _ptr(rows), _ptr(cols), _ptr(vals), nnz, int(n_terms), int(n_docs), 1 if sort_docs else 0, _ptr(indptr),
+          _ptr(out_rows), _ptr(out_vals))
     return indptr, out_rows[:nnz], out_vals[:nnz]
 
 
 def sparse_csr_expand_terms(indptr, nnz):
     """Term of every posting of a CSR-by-term index (indptr int64 [V + 1] on the device) -> int32 [nnz]: sr_sparse_csr_expand_terms."""
     _lib.require_gpu()
-    lib = _lib.load()
     indptr = indptr.to(torch.int64).contiguous()
     out = torch.empty(max(1, int(nnz)), dtype=torch.int32, device=indptr.device)
-    with torch.cuda.device(indptr.device):
-        _lib.check(lib.sr_sparse_csr_expand_terms(_ptr(indptr), indptr.numel() - 1, int(nnz), _ptr(out), _lib.stream_ptr()),
-                   "sr_sparse_csr_expand_terms")
+    _call(indptr.device, "sr_sparse_csr_expand_terms", _ptr(indptr), indptr.numel() - 1, int(nnz), _ptr(out))
     return out[:int(nnz)]
 
 
@@ -1039,13 +674,11 @@ def hybrid_union(a_ids, b_spos, b_counts, s2d, d2s, a_indptr=None):
         capacity = a_ids.numel() + nq * ks
     indptr = torch.empty((nq + 1,), dtype=torch.int64, device=dev)
     out = torch.empty((3, max(1, capacity)), dtype=torch.int64, device=dev)
-    keep = [t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev) for t in (a_ids, b_spos, b_counts, s2d, d2s)]      # valid pointers
+    keep = [_valid(t) for t in (a_ids, b_spos, b_counts, s2d, d2s)]
     p = [_ptr(t) for t in keep]
     total = ctypes.c_int64(0)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().sr_hybrid_union(p[0], _ptr(a_indptr), kd, p[1], p[2], ks, p[3], s2d.numel(), p[4], d2s.numel(), nq,
-                                               _ptr(indptr), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), capacity, ctypes.byref(total),
-                                               _lib.stream_ptr()), "sr_hybrid_union")
+    _call(dev, "sr_hybrid_union", p[0], _ptr(a_indptr), kd, p[1], p[2], ks, p[3], s2d.numel(), p[4], d2s.numel(), nq, _ptr(indptr), _ptr(out[0]),
+          _ptr(out[1]), _ptr(out[2]), capacity, ctypes.byref(total))
     n = total.value
     return indptr, out[0, :n], out[1, :n], out[2, :n]
 
@@ -1072,11 +705,7 @@ def hybrid_rank(cand_indptr, dpos, spos, tie, dense_scores, sparse_scores, weigh
     counts = torch.empty((nq,), dtype=torch.int32, device=dev)
     cert = torch.empty((nq,), dtype=torch.int32, device=dev)
     thr = torch.empty((nq,), dtype=torch.float32, device=dev)
-    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)      # noqa: E731  (valid pointers)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().sr_hybrid_rank(_ptr(i64[0]), _ptr(one(i64[1])), _ptr(one(i64[2])), _ptr(one(i64[3])), _ptr(one(f32[0])),
-                                              _ptr(one(f32[1])), nq, float(weights[0]), float(weights[1]), k, _ptr(one(f32[2])),
-                                              _ptr(one(f32[3])), _ptr(one(complete)), int(n_s2d), int(id_end), _ptr(one(out_s)),
-                                              _ptr(one(out_i)), _ptr(one(counts)), _ptr(one(cert)), _ptr(one(thr)), _lib.stream_ptr()),
-                   "sr_hybrid_rank")
+    keep = [_valid(t) for t in (*i64[1:], f32[0], f32[1], f32[2], f32[3], complete, out_s, out_i, counts, cert, thr)]
+    p = [_ptr(t) for t in keep]
+    _call(dev, "sr_hybrid_rank", _ptr(i64[0]), *p[:5], nq, float(weights[0]), float(weights[1]), k, *p[5:8], int(n_s2d), int(id_end), *p[8:])
     return out_s, out_i, counts, cert, thr

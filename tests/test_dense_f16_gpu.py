@@ -256,6 +256,56 @@ def test_rounding_at_ingest(tmp_path):
         DenseIndexHIP(H, row_dtype="fp16").add_host_rows(bad.cpu().numpy())
 
 
+def test_staging_ring_is_one_for_both_entry_points(tmp_path):
+    """add_host_rows (array, memory-mapped view) and add_npy_file share one pinned ring: 1 000 rows in pieces of 96 make 11 pieces with a
+    ragged last one, through 3 buffers and 2 threads, so every buffer is used again.  Each way produces, bit for bit, the segment
+    add_device_rows makes of the same data, in all three staging modes."""
+    from scaling_retriever_amd.scoring import DenseIndexHIP
+    N, H = 1000, 64
+    g = torch.Generator(device="cpu").manual_seed(7)
+    rows32 = torch.randn((N, H), generator=g).numpy()
+    rows16 = rows32.astype(np.float16)
+    ring = dict(n_buffers=3, n_threads=2)
+
+    def segments(src, row_dtype):
+        """The segment each of the three ways makes of `src`, and the one add_device_rows makes."""
+        path = str(tmp_path / f"rows_{src.dtype}_{len(src)}.npy")
+        np.save(path, src)
+        piece = 96 * H * src.dtype.itemsize
+        made = []
+        for add in (lambda i: i.add_host_rows(src, piece_bytes=piece, **ring),
+                    lambda i: i.add_host_rows(np.load(path, mmap_mode="r"), piece_bytes=piece, **ring),
+                    lambda i: i.add_npy_file(path, piece_bytes=piece, **ring),
+                    lambda i: i.add_device_rows(torch.from_numpy(src).cuda())):
+            idx = DenseIndexHIP(H, row_dtype=row_dtype)
+            add(idx)
+            assert len(idx._segments) == 1 and idx.ntotal == len(src)
+            made.append(idx._segments[0])
+        return made[:3], made[3]
+
+    for src, row_dtype, want in ((rows32, "fp32", torch.from_numpy(rows32)),                 # fp32 source into an fp32 index
+                                 (rows16, "fp32", torch.from_numpy(rows16)),                 # fp16 source: stored as it is, either index
+                                 (rows16, "fp16", torch.from_numpy(rows16)),
+                                 (rows32, "fp16", torch.from_numpy(rows32).half())):         # fp32 source, rounded on the device
+        staged, direct = segments(src, row_dtype)
+        assert direct.dtype == want.dtype and torch.equal(direct.cpu(), want)
+        for seg in staged:
+            assert seg.dtype == direct.dtype and seg.shape == direct.shape and seg.device == direct.device
+            assert torch.equal(seg.view(torch.int16 if seg.dtype == torch.float16 else torch.int32),
+                               direct.view(torch.int16 if seg.dtype == torch.float16 else torch.int32))
+    # a value float16 cannot hold, in the tenth piece: both entry points name the row
+    bad = rows32.copy()
+    bad[917, 5] = 70000.0
+    np.save(tmp_path / "bad.npy", bad)
+    with pytest.raises(ValueError, match="row 917"):
+        DenseIndexHIP(H, row_dtype="fp16").add_host_rows(bad, piece_bytes=96 * H * 4, **ring)
+    with pytest.raises(ValueError, match="row 917"):
+        DenseIndexHIP(H, row_dtype="fp16").add_npy_file(str(tmp_path / "bad.npy"), piece_bytes=96 * H * 4, **ring)
+    # no rows: an empty segment
+    staged, direct = segments(rows32[:0], "fp32")
+    assert all(seg.shape == (0, H) and seg.dtype == torch.float32 for seg in staged + [direct])
+
+
 def test_errors():
     from scaling_retriever_amd import _lib
     lib = _lib.load()
