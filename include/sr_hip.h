@@ -261,7 +261,8 @@ int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t 
  * the gap check's word (8 n_groups + 8 bytes); then the pass route once for the certificate's flags, as the masked search does, and
  * once more only if queries were re-done; the loop route once at its end.
  * sr_dense_index_filter_stats / _filter_query_stats count a call that ran the grouped pass like any filtered search (the loop: not at
- * all).  Not offered under groups: the sparse head and the hybrid searches, range searches, k > sr_max_topk(), doc-sharded search.    */
+ * all).  Not offered under groups: range searches and the exact hybrid search, k > sr_max_topk(), doc-sharded search.  The sparse
+ * head under groups is sr_sparse_search_grouped.                                                                                    */
 int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
                             const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits,
                             const int32_t* d_query_group,
@@ -392,12 +393,50 @@ int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_indptr, con
  * a copy of the bitmap in the length its kernel walks (n_docs / 8 bytes rounded up to whole 1 024-document tiles, counted against the
  * workspace limit).  sr_sparse_index_cert_stats counts a masked pass like any other.  The call waits for the stream once for the
  * count of set bits, then on the mask route as sr_sparse_search does (twice per batch of 8 192 queries, and once more per batch with
- * handed-back queries); on the list routes not again.  Not under a mask: doc-sharded search, per-query masks (the range search under
- * a mask is sr_sparse_range_count_masked / _fill_masked).                                                                          */
+ * handed-back queries); on the list routes not again.  Not under a mask: doc-sharded search (a mask per query is
+ * sr_sparse_search_grouped below; the range search under a mask is sr_sparse_range_count_masked / _fill_masked).                   */
 int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
                             const float* d_q_vals, int64_t nq, int k, float threshold,
                             const uint32_t* d_mask_words, int64_t n_bits, int64_t id_base, int64_t id_stride,
                             float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream);
+/* Filter groups for the sparse head: every query searches within its OWN set of allowed documents, in one call (the counterpart of
+ * sr_dense_search_grouped).  d_group_words uint32 [n_groups, W], W = ceil(n_bits / 32): one bitmap per group in the bit convention of
+ * sr_sparse_search_masked, n_bits == n_docs; bits of a row's last word at or beyond n_bits are ignored and the library never reads past
+ * a row.  d_query_group int32 [nq]: query q searches under bitmap d_query_group[q].  All on the device.
+ * Contract: for every group g the output rows of the queries with d_query_group[q] == g are EXACTLY what sr_sparse_search_masked returns
+ * for those queries alone, in their order, under bitmap g - counts, ids, score bits, tie order, padding (0, -1), threshold semantics,
+ * id_base / id_stride - whichever route served the call.  n_groups == nq, a group without queries and an all-zero bitmap are all valid.
+ * 1 <= k <= 2^30, as for the masked search.
+ * Errors, all SR_ERR_INVALID.  Before any device work: n_bits != n_docs, n_groups < 1, (n_groups + 1) * n_tiles * 32 >= 2^32 (n_tiles =
+ * ceil(n_docs / 1 024)), a bad k, or a null pointer with nq > 0.  An entry of d_query_group outside [0, n_groups): sr_last_error()
+ * names the first such query, nothing is scored, every output row is padding with count 0, and the index stays usable.  Every sparse
+ * position names a document, so a set bit is never invalid.
+ * Routes, the same bits.  (1) The grouped pass, where sr_sparse_search_masked's mask route is eligible (the index has the certified
+ * scorer, k + 1 024 <= sr_max_topk(), n_docs >= 8 (k + 1 024)), at least one group with a query has a set bit, and the scorer's copy of
+ * the bitmaps - every group in the length its kernel walks plus their union, (n_groups + 1) * n_tiles * 128 bytes on the handle,
+ * allocated on first use and grown on demand - fits the workspace limit: ONE pass of the certified scorer in which the bit test reads
+ * the query's own bitmap (4 bytes of word offset per query on the handle) and the block skip reads the union.  Thresholds, band cut and
+ * certificate are per-query quantities over that query's allowed documents, so the scorer's argument holds as for one mask.  Queries it
+ * hands back (not eligible, band does not fit, fewer than k allowed documents with a non-zero key - the queries of an all-zero group
+ * among them, which are then not scored at all -, candidate overflow, no memory for the batch) are re-done by the list routes (pairs /
+ * array) under their own group's list, those alone, group by group, the list expanded one group at a time (8 m_g bytes on the handle);
+ * there is no second, wider-band pass under groups.  (2) The group loop, everywhere else: per group with a query in it, its queries
+ * gathered into a CSR of their own, the body of sr_sparse_search_masked under that group's bitmap (which picks pairs / array / mask by
+ * its own rule and dev switch, and serves any k), the rows scattered back.  Rule: the pass where it is eligible and
+ * sum_g nq_g * m_g >= 64 * 1 000 000 - the constant of the masked search, measured for ONE group; the loop's per-group overhead moves
+ * the real crossing down as groups multiply.  Dev switch SR_GROUPED_SPARSE_ROUTE=pass|loop forces one (read per call;
+ * `pass` where it is not eligible is served by the loop).
+ * Synchronisation: the call waits for the stream twice before any scoring - the group ids (4 nq bytes), then the per-group counts of
+ * set bits (8 n_groups bytes, one word-parallel pass over all bitmaps).  Then the pass waits as sr_sparse_search does (twice per batch
+ * of 8 192 queries) and, for a batch with handed-back queries, once for their flags, once for the query offsets (8 (nq + 1) bytes) and
+ * once at the end of the re-do; the loop waits once for the query offsets, per group as sr_sparse_search_masked does, and once at its
+ * end.  sr_sparse_index_cert_stats counts a grouped pass like any other search; the loop's masked bodies count as they do on their own.
+ * Not offered under groups: range searches, the exact hybrid search, doc-sharded search.                                            */
+int sr_sparse_search_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
+                             const float* d_q_vals, int64_t nq, int k, float threshold,
+                             const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits,
+                             const int32_t* d_query_group, int64_t id_base, int64_t id_stride,
+                             float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream);
 /* Range search: EVERY document whose score exceeds a per-query threshold, as CSR.  This is what the reference's scorer computes before
  * select_topk cuts it (numba_score_float, scaling_retriever/indexer.py:324-344: the score array starts at zero, every query term is
  * scatter-added in term order, then every document with score > threshold is returned in document order), with one threshold per query;

@@ -83,6 +83,8 @@ SIGNATURES = {
                                         c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_sparse_search_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int64, c_int64,
                                         c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_sparse_search_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int64, c_int64,
+                                         c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_sparse_range_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     "sr_sparse_range_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                      c_void_p, c_int64, c_void_p]),

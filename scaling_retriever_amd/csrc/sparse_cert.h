@@ -50,4 +50,7 @@ struct SparseCert {
     std::vector<uint8_t> h_uncert;    // the last search's uncertified flags, kept on the host while the key recording is on
     DeviceBuf<unsigned long long> d_stamps;   // [80] dev switch SR_CERT_STAMPS of a -DSC_STAMPS=1 build
     DeviceBuf<uint32_t> mask_pad;     // [n_tiles * SC_MB] a search's document bitmap as the masked score kernel walks it (sparse_cert_mask_pad), allocated on first use
+    // a grouped search's bitmaps (sparse_cert_group_pad), allocated on first use and grown on demand
+    DeviceBuf<uint32_t> group_pad;    // [n_groups + 1][n_tiles * SC_MB]: every group's bitmap in the kernel's length, then their union
+    DeviceBuf<uint32_t> group_qoff;   // [nq rounded up to 32]: word offset of the query's group in group_pad, 0 behind the last query
 };

@@ -211,6 +211,10 @@ struct CertArgs {
     unsigned long long* stamps;   // dev switch SR_CERT_STAMPS: [8] cycle sums per phase of sampled waves
     int64_t dump_stride;
     const uint32_t* mask;    // MASKED launches: [n_tiles * SC_MB] words, bit b of word tile * SC_MB + block = may doc tile * SC_DT + block * 32 + b become a key; null otherwise
+    // GROUPED launches (a bitmap per query, sr_sparse_search_grouped): `mask` is the UNION of the groups' bitmaps; gmask holds the groups'
+    // own, [n_groups][n_tiles * SC_MB] words, and qoff[q] the 32-bit word offset of query q's row in it, [nq_pad].  Null otherwise
+    const uint32_t* gmask;
+    const uint32_t* qoff;
 };
 
 // low half of a packed posting: byte offset of the doc's word inside a query row of the LDS tile | doc parity (SC_POST_LO)
@@ -396,8 +400,17 @@ constexpr int sc_ring_depth(int nl) {
 // time, so one mask word covers the block at a wave-uniform address; a doc whose bit is clear never becomes a candidate, and everything
 // downstream (tau, tau2, the band cut, the certificate) is a quantity over the allowed docs alone.  MASKED = false compiles to the kernel
 // without any of it.
-template <int KS, bool MASKED>
+// GROUPED (with MASKED): every query has its own bitmap.  In the matrix waves lane = query, so the word a lane tests is its own query's:
+// one vector load per lane and block, gmask[qoff[q] + the block's word].  The block's 32 offsets wait in LDS (nothing is carried across
+// the tile loop: the kernel has no register to spare), and the load is issued behind the block's MFMA chain, in front of the key
+// arithmetic, so the candidate branch finds the word there.  Measured at G = 1 against the masked twin: both loads
+// inside the branch, the offset from global memory, 1.16 - 1.19; the offset from LDS 1.09 - 1.10; the word asked for ahead of the
+// keys 1.04 - 1.05.  The wave-uniform skip in front of the branch keeps its scalar read and is fed from the union of all groups'
+// bitmaps: a block no group allows costs what it costs the masked twin.  tau, tau2, the band cut and the certificate are
+// per-query quantities over the docs that became keys FOR THAT QUERY; nothing relates two queries.
+template <int KS, bool MASKED, bool GROUPED>
 __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
+    static_assert(MASKED || !GROUPED, "the grouped twin is a masked one");
     extern __shared__ uint32_t slots[];                          // 2 x [SC_QB][SC_PITCH_W] | B fragments | mark buffers
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // workgroups of one doc chunk share blockIdx.x % 8, i.e. one XCD under round-robin placement: the chunk's tiles, postings
@@ -419,6 +432,10 @@ __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
     // 32-bit write each); matrix wave 0 adds them up in global memory after the step's barrier - nothing is carried in registers across the loop
     const bool st_wg = SC_STAMPS && a.stamps != nullptr && (blockIdx.x & 63) == 0 && a.tile_begin >= a.stamps_from;
     volatile uint32_t* const t_ph = reinterpret_cast<volatile uint32_t*>(reinterpret_cast<char*>(bl) + SC_BREGION + SC_TAIL_LDS);   // [4 phases][16 waves]
+    // GROUPED: the block's 32 word offsets wait in LDS behind the stamps' words - a block pays one LDS read and ONE global round trip
+    // for the lane's word instead of two dependent ones, and nothing is held across the tile loop
+    uint32_t* const qo = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(bl) + SC_BREGION + SC_TAIL_LDS + 256);
+    if constexpr (GROUPED) { if (tid < SC_QB) qo[tid] = a.qoff[(int64_t)qb * SC_QB + tid]; }
     __syncthreads();
     // The two roles work on DIFFERENT tiles: in step t the scatter waves add the rare postings of tile t into LDS tile t & 1 while
     // the matrix waves multiply tile t - 1, add LDS tile (t - 1) & 1 to it, filter and clear it.  One barrier per step.
@@ -487,6 +504,8 @@ __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
                 if (mbi == 3) SC_STAMP(1);                       // end of the step's last MFMA chain
                 // accumulators -> 16-bit fixed point, two docs per word: register pair (2 g, 2 g + 1) = rows 8 (g / 2) + 4 h + 2 (g % 2) + {0, 1};
                 // + the LDS tile's fixed-point sums of the rare terms
+                uint32_t lword = 0u;                             // GROUPED: the lane's own query's word of this block, asked for ahead of the keys
+                if constexpr (GROUPED) lword = a.gmask[qo[qn] + (uint32_t)(tile * SC_MB + wave * 4 + mb)];
                 uint2 sv[4];
 #pragma unroll
                 for (int G = 0; G < 4; ++G) {
@@ -523,7 +542,8 @@ __global__ __launch_bounds__(1024) void cert_score_kernel(CertArgs a) {
                 if constexpr (MASKED) { if (mword == 0u) any = 0; }      // wave-uniform: a block without an allowed doc has no candidate
                 if (any != 0) {                                  // one block in two at the MSMARCO shape once the threshold has risen (46 % in the launches from tile 2 000 on)
                     // the bit of the doc at offset o = 8 (g / 2) + 4 h + 2 (g % 2) (+ 1: the high half) of the block, behind the score test
-                    const uint32_t mh = MASKED ? mword >> (4 * h) : 0u;
+                    uint32_t mh = MASKED ? mword >> (4 * h) : 0u;
+                    if constexpr (GROUPED) mh = lword >> (4 * h);     // the lane's own query's word
                     auto allowed = [&](int g, int half) -> bool { return !MASKED || ((mh >> (8 * (g >> 1) + 2 * (g & 1) + half)) & 1u) != 0u; };
                     int cnt = 0;
 #pragma unroll
@@ -1078,22 +1098,25 @@ uint8_t* sparse_cert_uncert_buffer(SparseCert* c, int64_t nq) {
     return c->d_uncert.reserve(nq, nullptr) == SR_OK ? c->d_uncert.p : nullptr;
 }
 
-template <int KS, bool MASKED>
+template <int KS, bool MASKED, bool GROUPED>
 static int cert_launch_score_as(const CertArgs& a, unsigned grid, hipStream_t s) {
-    static DeviceOnce lds_set;                               // one per (KS, MASKED) instantiation
+    static DeviceOnce lds_set;                               // one per (KS, MASKED, GROUPED) instantiation
     static_assert(1024 * KS <= SC_BREGION, "B fragments");
-    const int lds = (int)(sizeof(uint32_t) * 2 * SC_SLOT_WORDS + SC_BREGION + SC_TAIL_LDS + (a.stamps ? 256 : 0));
+    // GROUPED: the stamps' 256 bytes (used or not) and the block's 32 word offsets behind them
+    const int lds = (int)(sizeof(uint32_t) * 2 * SC_SLOT_WORDS + SC_BREGION + SC_TAIL_LDS + (GROUPED ? 256 + 4 * SC_QB : (a.stamps ? 256 : 0)));
+    static_assert(sizeof(uint32_t) * 2 * SC_SLOT_WORDS + SC_BREGION + SC_TAIL_LDS + 256 + 4 * SC_QB <= 160 * 1024, "LDS of a workgroup");
     if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)cert_score_kernel<KS, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        SR_CHECK_HIP(hipFuncSetAttribute((const void*)cert_score_kernel<KS, MASKED, GROUPED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         *slot = true;
     }
-    hipLaunchKernelGGL((cert_score_kernel<KS, MASKED>), dim3(grid), dim3(1024), lds, s, a);
+    hipLaunchKernelGGL((cert_score_kernel<KS, MASKED, GROUPED>), dim3(grid), dim3(1024), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }
 template <int KS>
 static int cert_launch_score(const CertArgs& a, unsigned grid, hipStream_t s) {
-    return a.mask != nullptr ? cert_launch_score_as<KS, true>(a, grid, s) : cert_launch_score_as<KS, false>(a, grid, s);
+    if (a.qoff != nullptr) return cert_launch_score_as<KS, true, true>(a, grid, s);
+    return a.mask != nullptr ? cert_launch_score_as<KS, true, false>(a, grid, s) : cert_launch_score_as<KS, false, false>(a, grid, s);
 }
 
 // The bitmap of a masked search as the score kernel walks it: n_tiles * SC_MB words.  A caller's bitmap holds ceil(n_docs / 32) words and
@@ -1118,6 +1141,52 @@ int sparse_cert_mask_pad(sr_sparse_index* idx, const uint32_t* d_words, const ui
                        c->mask_pad.p, n_pad);
     SR_CHECK_LAUNCH();
     *d_mask_pad = c->mask_pad.p;
+    return SR_OK;
+}
+
+// The bitmaps of a grouped search as the score kernel walks them: row g < n_groups = group g's words padded and trimmed as
+// cert_mask_pad_kernel does, row n_groups = the OR of all of them (the wave-uniform skip reads it).  One thread per word position.
+__global__ void cert_group_pad_kernel(const uint32_t* __restrict__ words, int64_t n_groups, int64_t n_words, int64_t n_docs, uint32_t* __restrict__ pad,
+                                      int64_t n_pad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    const unsigned tail = (unsigned)(n_docs & 31);
+    const uint32_t keep = (i == n_words - 1 && tail != 0) ? (1u << tail) - 1u : 0xffffffffu;
+    uint32_t u = 0u;
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const uint32_t v = i < n_words ? words[g * n_words + i] & keep : 0u;
+        pad[g * n_pad + i] = v;
+        u |= v;
+    }
+    pad[n_groups * n_pad + i] = u;
+}
+// qoff[q] := query_group[q] * n_pad (group ids already checked, the product below 2^32), 0 for nq <= q < nq_pad
+__global__ void cert_group_qoff_kernel(const int32_t* __restrict__ query_group, int64_t nq, int64_t nq_pad, uint32_t n_pad, uint32_t* __restrict__ qoff) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nq_pad) qoff[q] = q < nq ? (uint32_t)query_group[q] * n_pad : 0u;
+}
+
+int64_t sparse_cert_group_pad_bytes(const SparseCert* c, int64_t n_groups) {
+    return (n_groups + 1) * (int64_t)c->n_tiles * SC_MB * (int64_t)sizeof(uint32_t);
+}
+
+int sparse_cert_group_pad(sr_sparse_index* idx, const uint32_t* d_group_words, int64_t n_groups, const int32_t* d_query_group, int64_t nq,
+                          const uint32_t** d_group_pad, const uint32_t** d_union_pad, const uint32_t** d_qoff, hipStream_t s) {
+    SparseCert* c = idx->cert;
+    const int64_t n_pad = (int64_t)c->n_tiles * SC_MB;
+    const int64_t nq_pad = ceil_div64(nq, SC_QB) * SC_QB;
+    *d_group_pad = nullptr; *d_union_pad = nullptr; *d_qoff = nullptr;
+    SR_REQUIRE((n_groups + 1) * n_pad < (1ll << 32), "sparse_cert_group_pad: %lld groups of %lld words exceed 2^32 words", (long long)n_groups, (long long)n_pad);
+    if (c->group_pad.reserve((n_groups + 1) * n_pad, nullptr) != SR_OK || c->group_qoff.reserve(nq_pad, nullptr) != SR_OK) return SR_OK;
+    hipLaunchKernelGGL(cert_group_pad_kernel, dim3((unsigned)ceil_div64(n_pad, 256)), dim3(256), 0, s, d_group_words, n_groups, ceil_div64(idx->n_docs, 32),
+                       idx->n_docs, c->group_pad.p, n_pad);
+    SR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(cert_group_qoff_kernel, dim3((unsigned)ceil_div64(nq_pad, 256)), dim3(256), 0, s, d_query_group, nq, nq_pad, (uint32_t)n_pad,
+                       c->group_qoff.p);
+    SR_CHECK_LAUNCH();
+    *d_group_pad = c->group_pad.p;
+    *d_union_pad = c->group_pad.p + n_groups * n_pad;
+    *d_qoff = c->group_qoff.p;
     return SR_OK;
 }
 
@@ -1208,6 +1277,8 @@ int sparse_cert_search(sr_sparse_index* idx, const SparseCall& call, const Spars
     if (SC_STAMPS) { if (const char* e = sr_dev_getenv("SR_CERT_STAMPS")) a.stamps_from = atoi(e); }
     a.dump_stride = dump_stride;
     a.mask = opt.mask_pad;
+    a.gmask = opt.group_pad; a.qoff = opt.group_pad ? opt.qoff : nullptr;
+    if (a.qoff != nullptr && a.mask == nullptr) { sr_set_error("sparse_cert_search: per-query bitmaps without their union"); return SR_ERR_INVALID; }
     int64_t step = k_eff / SC_DT + 1;      // the first launch covers just over k + band docs (no threshold exists before that many keys are held), then doubling
     bool band_filter = true;               // dev switch SR_SPARSE_CERT_BAND=0: filter with the (k + band)-th best key only
     if (const char* e = sr_dev_getenv("SR_SPARSE_CERT_BAND")) band_filter = atoi(e) != 0;

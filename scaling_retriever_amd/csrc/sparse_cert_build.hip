@@ -197,6 +197,8 @@ void sparse_cert_destroy(SparseCert* c) {
     c->d_uncert.release();
     c->dump.release();
     c->mask_pad.release();
+    c->group_pad.release();
+    c->group_qoff.release();
     c->ws.release();
     delete c;
 }

@@ -7,6 +7,7 @@
 
 struct SparseCert;      // sparse_cert.h
 struct PairStatus;      // pair_score.h
+struct SparseGroups;    // below
 
 // Geometry of sr_sparse_index::skip (built by sparse_index.hip; sparse_score.hip checks these against its own tile constants): the
 // exact scorer's doc tiles hold SR_SPARSE_TILE_DOCS documents (n_tiles of them), and skip[t * (n_sub + 1) + b] = number of postings of
@@ -60,6 +61,7 @@ struct sr_sparse_index {
     DeviceBuf<uint32_t> filt_words;
     DeviceBuf<int64_t> filt_blocks;
     DeviceBuf<int64_t> filt_list;
+    DeviceBuf<int64_t> grp_counts;       // sr_sparse_search_grouped: [n_groups + 1] set bits per group (+ the unused word of launch_doc_masks_check)
     // sr_sparse_range_count / _fill (sparse_range.hip): the (chunk, query) table of the last count - hits per cell, turned into exclusive
     // prefixes over the chunks by the scan - and what it was made for.  A chunk is range_chunk_tiles consecutive doc tiles
     DeviceBuf<int32_t> range_tab;                                     // [range_chunks, range_nq]
@@ -114,6 +116,10 @@ struct SparseCertOptions {
     // null: every document; else the bitmap of sparse_cert_mask_pad: a document whose bit is clear never becomes a stage-1 key, so the
     // result is the top-k among the allowed documents and "fewer than k docs with a non-zero key" counts allowed documents only
     const uint32_t* mask_pad = nullptr;
+    // a bitmap per query (sparse_cert_group_pad): group_pad = the groups' padded bitmaps, qoff [nq rounded up to 32] = the word offset of
+    // each query's row in it, mask_pad = their union.  Null: one bitmap for all queries, or none
+    const uint32_t* group_pad = nullptr;
+    const uint32_t* qoff = nullptr;
 };
 struct SparseCertResult {
     int64_t n_uncert = 0;                // queries flagged in SparseCertOptions::uncert
@@ -131,6 +137,13 @@ int sparse_cert_search(sr_sparse_index* idx, const SparseCall& call, const Spars
 // SR_OK): no device memory for it.  _bytes: its size.
 int sparse_cert_mask_pad(sr_sparse_index* idx, const uint32_t* d_words, const uint32_t** d_mask_pad, hipStream_t s);
 int64_t sparse_cert_mask_pad_bytes(const SparseCert* c);
+// The same for a grouped search: d_group_words uint32 [n_groups, ceil(n_docs / 32)] -> [n_groups + 1][n_tiles * 32] words on the handle, row
+// n_groups = the union of the groups, and the queries' word offsets d_query_group[q] * n_tiles * 32, zero-padded to a multiple of 32
+// queries.  (n_groups + 1) * n_tiles * 32 < 2^32 (SR_ERR_INVALID otherwise).  Pointers null (with SR_OK): no device memory.  _bytes: the
+// size of the bitmaps.
+int sparse_cert_group_pad(sr_sparse_index* idx, const uint32_t* d_group_words, int64_t n_groups, const int32_t* d_query_group, int64_t nq,
+                          const uint32_t** d_group_pad, const uint32_t** d_union_pad, const uint32_t** d_qoff, hipStream_t s);
+int64_t sparse_cert_group_pad_bytes(const SparseCert* c, int64_t n_groups);
 void sparse_cert_count_retry(SparseCert* c, int64_t ns);
 // [nq] flag bytes kept with the scorer (grown on demand); nullptr = out of device memory
 uint8_t* sparse_cert_uncert_buffer(SparseCert* c, int64_t nq);
@@ -161,8 +174,34 @@ int sparse_subset_lists(sr_sparse_index* idx, const SparseCall& call, const int6
 bool sparse_cert_applies(const sr_sparse_index* idx, int k);
 // The certified search of sr_sparse_search in query batches, with the exact re-do of what the scorer hands back.  filt (null: the whole
 // collection): the pass runs under filt->mask_pad and handed-back queries, or a batch whose buffers do not fit, are served by
-// sparse_subset_lists over the filter's list.  idx->mu held.
-int sparse_certified_search(sr_sparse_index* idx, const SparseCall& call, SparseDocFilter* filt, hipStream_t s);
+// sparse_subset_lists over the filter's list.  groups (with filt null): a bitmap per query - the pass runs the grouped twin of the score
+// kernel, every batch with its slice of groups->qoff, and what a batch hands back is re-done by sparse_grouped_each under each query's
+// own group's list (no second, wider-band pass).  idx->mu held.
+int sparse_certified_search(sr_sparse_index* idx, const SparseCall& call, SparseDocFilter* filt, hipStream_t s, const SparseGroups* groups = nullptr);
+
+// ---- search under a bitmap per query (sr_sparse_search_grouped: subset_search.hip, sparse_search.hip) ----
+// What the drivers know of a grouped call.  The host arrays describe ALL queries of the entry's call; q0 = the first of them that the
+// SparseCall handed along with this struct holds (a batch, a sub-call).
+struct SparseGroups {
+    const uint32_t* words = nullptr;     // the caller's bitmaps, uint32 [n_groups, n_words]
+    int64_t n_groups = 0, n_words = 0;
+    const int32_t* h_group = nullptr;    // host: group of every query, range-checked
+    const int64_t* h_count = nullptr;    // host: set bits of every group
+    int64_t q0 = 0;
+    // sparse_cert_group_pad (all null: no device memory for them)
+    const uint32_t* group_pad = nullptr;
+    const uint32_t* union_pad = nullptr;
+    const uint32_t* qoff = nullptr;      // of query 0 of the entry's call
+    const char* who = "sr_sparse_search_grouped";
+};
+// The body of sr_sparse_search_masked behind its argument checks: count of the set bits (one read-back), workspace check, route rule, search.
+int sparse_masked_body(sr_sparse_index* idx, const SparseCall& call, const uint32_t* d_mask_words, hipStream_t s, const char* who);
+// The list routes (pairs / array by the rule) for one call under a bitmap of m set bits: the bitmap expanded into the handle's list
+int sparse_masked_lists(sr_sparse_index* idx, const SparseCall& call, const uint32_t* d_mask_words, int64_t m, hipStream_t s, const char* who);
+// The queries of `call` (h_flags null: all; else those with a non-zero flag, h_flags [call.nq] on the host) searched group by group, only
+// groups that hold such a query: the group's queries gathered into a CSR of their own, searched under the group's bitmap - lists_only:
+// by sparse_masked_lists, else by sparse_masked_body - and their rows scattered back.  Waits for the stream.
+int sparse_grouped_each(sr_sparse_index* idx, const SparseCall& call, const SparseGroups& groups, const uint8_t* h_flags, bool lists_only, hipStream_t s);
 
 // ---- device-wide exclusive scan of int64 counts (sparse_build.hip): out[i] = sum_{j < i} in[j], out[n] = total; in == out allowed
 int sr_device_exclusive_scan_i64(const int64_t* d_in, int64_t* d_out, int64_t n, hipStream_t s);

@@ -200,6 +200,7 @@ extern "C" int sr_sparse_index_destroy(sr_sparse_index* idx) {
     idx->filt_words.release();
     idx->filt_blocks.release();
     idx->filt_list.release();
+    idx->grp_counts.release();
     idx->range_tab.release();
     delete idx;
     return SR_OK;

@@ -115,7 +115,63 @@ bool sparse_cert_applies(const sr_sparse_index* idx, int k) {
     return use_cert;
 }
 
-int sparse_certified_search(sr_sparse_index* idx, const SparseCall& call, SparseDocFilter* filt, hipStream_t s) {
+// ---- a bitmap per query (sr_sparse_search_grouped): the queries of a call group by group, each group under its own bitmap
+int sparse_grouped_each(sr_sparse_index* idx, const SparseCall& call, const SparseGroups& groups, const uint8_t* h_flags, bool lists_only, hipStream_t s) {
+    const int64_t nq = call.nq;
+    const int32_t* grp = groups.h_group + groups.q0;
+    std::vector<int64_t> sel;                                // the chosen queries by group (a stable sort: ascending inside a group)
+    for (int64_t q = 0; q < nq; ++q)
+        if (!h_flags || h_flags[q]) sel.push_back(q);
+    if (sel.empty()) return SR_OK;
+    std::stable_sort(sel.begin(), sel.end(), [&](int64_t a, int64_t b) { return grp[a] < grp[b]; });
+    std::vector<int64_t> h_ip((size_t)nq + 1);
+    SR_CHECK_HIP(hipMemcpyAsync(h_ip.data(), call.q_indptr, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    const int64_t ns_all = (int64_t)sel.size();
+    std::vector<int64_t> sub_ip((size_t)ns_all + 1, 0);      // one CSR over all chosen queries in `sel` order; a group is a run of its rows
+    for (int64_t j = 0; j < ns_all; ++j) sub_ip[(size_t)j + 1] = sub_ip[(size_t)j] + (h_ip[(size_t)sel[(size_t)j] + 1] - h_ip[(size_t)sel[(size_t)j]]);
+    const int64_t nnz = sub_ip.back() > 0 ? sub_ip.back() : 1;
+    CallBuf<int64_t> d_sel, d_sip, d_ids;
+    CallBuf<int32_t> d_cols, d_cnt;
+    CallBuf<float> d_vals, d_sc;
+    if (d_sel.reserve(ns_all, nullptr) != SR_OK || d_sip.reserve(ns_all + 1, nullptr) != SR_OK || d_cols.reserve(nnz, nullptr) != SR_OK ||
+        d_vals.reserve(nnz, nullptr) != SR_OK || d_sc.reserve(ns_all * call.k, nullptr) != SR_OK || d_ids.reserve(ns_all * call.k, nullptr) != SR_OK ||
+        d_cnt.reserve(ns_all, nullptr) != SR_OK) {
+        sr_set_error("%s: out of device memory for %lld queries searched group by group", groups.who, (long long)ns_all);
+        return SR_ERR_NOMEM;
+    }
+    int rc = SR_OK;
+    if (hipMemcpyAsync(d_sel.p, sel.data(), 8 * (size_t)ns_all, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_sip.p, sub_ip.data(), 8 * ((size_t)ns_all + 1), hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = SR_ERR_HIP;
+    if (rc == SR_OK) {
+        hipLaunchKernelGGL(sparse_sub_gather_kernel, dim3((unsigned)ns_all), dim3(64), 0, s, call.q_indptr, call.q_cols, call.q_vals, d_sel.p, d_sip.p,
+                           d_cols.p, d_vals.p);
+        if (hipGetLastError() != hipSuccess) rc = SR_ERR_HIP;
+    }
+    for (int64_t j0 = 0; rc == SR_OK && j0 < ns_all;) {
+        const int64_t g = grp[sel[(size_t)j0]];
+        int64_t j1 = j0;
+        while (j1 < ns_all && grp[sel[(size_t)j1]] == g) ++j1;
+        // rows [j0, j1) of the gathered CSR as a call of their own (SparseCall::rows: q_indptr moves, cols / vals stay)
+        SparseCall sub = call;
+        sub.q_indptr = d_sip.p + j0; sub.q_cols = d_cols.p; sub.q_vals = d_vals.p; sub.nq = j1 - j0;
+        sub.out_scores = d_sc.p + j0 * call.k; sub.out_ids = d_ids.p + j0 * call.k; sub.out_counts = d_cnt.p + j0;
+        const uint32_t* words = groups.words + g * groups.n_words;
+        rc = lists_only ? sparse_masked_lists(idx, sub, words, groups.h_count[g], s, groups.who) : sparse_masked_body(idx, sub, words, s, groups.who);
+        j0 = j1;
+    }
+    if (rc == SR_OK) {
+        hipLaunchKernelGGL(sparse_sub_scatter_kernel, dim3((unsigned)ns_all), dim3(256), 0, s, d_sel.p, call.k, d_sc.p, d_ids.p, d_cnt.p, call.out_scores,
+                           call.out_ids, call.out_counts);
+        if (hipGetLastError() != hipSuccess) rc = SR_ERR_HIP;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && rc == SR_OK) rc = SR_ERR_HIP;      // the temporaries (and `sel`, a copy's source) go when this returns
+    if (rc == SR_ERR_HIP) sr_set_error("%s: searching group by group failed: %s", groups.who, hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+int sparse_certified_search(sr_sparse_index* idx, const SparseCall& call, SparseDocFilter* filt, hipStream_t s, const SparseGroups* groups) {
     // The scorer's workspace is ~200 KB per query: the query set goes through in batches (a whole MSMARCO-Dev set is one batch), and
     // a batch whose buffers do not fit in device memory is served by the exact kernels instead of failing the call; the queries it
     // cannot certify are re-done by the exact kernels.
@@ -124,10 +180,31 @@ int sparse_certified_search(sr_sparse_index* idx, const SparseCall& call, Sparse
     SparseCertOptions opt;
     opt.uncert = sparse_cert_uncert_buffer(idx->cert, call.nq < batch ? call.nq : batch);
     opt.mask_pad = filt ? filt->mask_pad : nullptr;
+    if (groups) { opt.mask_pad = groups->union_pad; opt.group_pad = groups->group_pad; }
     for (int64_t qb = 0; qb < call.nq; qb += batch) {
         const SparseCall part = call.rows(qb, call.nq - qb < batch ? call.nq - qb : batch);
         SparseCertResult res;
-        res.no_memory = opt.uncert == nullptr || (filt && filt->mask_pad == nullptr);
+        res.no_memory = opt.uncert == nullptr || (filt && filt->mask_pad == nullptr) || (groups && groups->group_pad == nullptr);
+        if (groups) {
+            // a batch (a multiple of 32 queries) walks its own slice of the word offsets.  What it hands back - or all of it, if its buffers
+            // do not fit - is re-done under each query's OWN group's list, group by group, and goes straight there: a second, wider-band pass
+            // would need the gathered queries' offsets and a scorer call per retry, for the few queries a grouped pass hands back
+            SparseGroups part_groups = *groups;
+            part_groups.q0 = groups->q0 + qb;
+            opt.qoff = groups->qoff ? groups->qoff + qb : nullptr;
+            if (sr_dev_getenv("SR_SPARSE_CERT_FAKE_OOM")) res.no_memory = true;
+            if (!res.no_memory) SR_TRY(sparse_cert_search(idx, part, opt, &res, s));
+            if (res.no_memory) {
+                ++idx->n_cert_no_memory;
+                SR_TRY(sparse_grouped_each(idx, part, part_groups, nullptr, true, s));
+            } else if (res.n_uncert > 0) {
+                std::vector<uint8_t> h_un((size_t)part.nq);
+                SR_CHECK_HIP(hipMemcpyAsync(h_un.data(), opt.uncert, (size_t)part.nq, hipMemcpyDeviceToHost, s));
+                SR_CHECK_HIP(hipStreamSynchronize(s));
+                SR_TRY(sparse_grouped_each(idx, part, part_groups, h_un.data(), true, s));
+            }
+            continue;
+        }
         if (sr_dev_getenv("SR_SPARSE_CERT_FAKE_OOM")) res.no_memory = true;          // tests: the fallback below
         if (!res.no_memory) SR_TRY(sparse_cert_search(idx, part, opt, &res, s));
         if (res.no_memory) {

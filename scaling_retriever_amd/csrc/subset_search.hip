@@ -22,12 +22,16 @@
 //   mask   the certified scorer's pass over the whole collection under the filter's bitmap (sparse_cert.hip): a document whose bit is
 //          clear never becomes a stage-1 key; the re-score from the forward index returns the same chain.
 // pairs and array keep score > threshold and score >= tau[query] and feed the same top-k.
+//
+// A bitmap per query (sr_sparse_search_grouped, at the end of this file): one pass of the certified scorer for all groups
+// (cert_score_kernel<KS, true, true>), or the body of the masked search group by group.
 #include "subset_search.h"
 #include "doc_mask.h"
 #include "sparse_index.h"
 #include "sparse_pair_chain.h"
 #include <math.h>
 #include <mutex>
+#include <vector>
 
 // ---------------------------------------------------------------------------------------------------- status ---
 int subset_status_begin(PairStatus** d_status, hipStream_t s) {
@@ -383,6 +387,9 @@ bool subset_sparse_use_array(int64_t m, int64_t n_docs) {
 // at m = 1 000 pairs wins with 7.06 against 41.5 ms) and m = 1 000 000 for nq = 64 (mask 7.72 ms, array 15.7 ms; at m = 100 000 pairs wins
 // with 6.15 against 7.41 ms).  Both crossings lie at nq x m of 6.4e7 - 7.0e7; the constant is the smaller of the two products, so that the
 // rule sends each measured nq to the mask route from its own crossing on.  One box, one collection size.
+// sr_sparse_search_grouped compares sum_g nq_g * m_g with the same constant.  It was measured for ONE group: the group loop pays its
+// per-group overhead once per group, so the real crossing moves down as groups multiply (64 queries in 8 groups of 10 %: the pass 8.5
+// ms, the loop 45.0 ms at a product of 5.7e7, below the constant).  The constant stays where it is.
 #define SR_SUBSET_SPARSE_MASK_CROSSOVER (64ll * 1000000ll)
 // The one rule of sr_sparse_search_subset and sr_sparse_search_masked: does a call with nq queries, this k and m allowed documents take the mask route
 static bool subset_sparse_use_mask(const sr_sparse_index* idx, int64_t nq, int k, int64_t m) {
@@ -530,18 +537,25 @@ extern "C" int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
     const SparseCall call{d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts};
+    return sparse_masked_body(idx, call, d_mask_words, s, "sr_sparse_search_masked");
+}
+
+int sparse_masked_body(sr_sparse_index* idx, const SparseCall& call, const uint32_t* d_mask_words, hipStream_t s, const char* who) {
+    const int64_t nq = call.nq, n_bits = idx->n_docs;
+    const int k = call.k;
     const int64_t n_blocks = doc_mask_blocks(n_bits);
-    SR_TRY(idx->filt_blocks.reserve(n_blocks + 1, "sr_sparse_search_masked"));
+    SR_TRY(idx->filt_blocks.reserve(n_blocks + 1, who));
     int64_t* d_count = idx->filt_blocks.p + n_blocks;
     SR_TRY(launch_doc_mask_count(d_mask_words, n_bits, idx->filt_blocks.p, d_count, s));
     SparseDocFilter f;
     f.words = d_mask_words;
+    f.who = who;
     SR_CHECK_HIP(hipMemcpyAsync(&f.m, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     SR_CHECK_HIP(hipStreamSynchronize(s));
     const bool array = subset_sparse_use_array(f.m, idx->n_docs);
     {   // the workspace errors of sr_sparse_search_subset for a list of this length, before any scoring
         int64_t nq_batch = 0, slab = 0;
-        SR_TRY(subset_plan(idx->ws_limit, nq, k, f.m, array ? SS_TILE : 64, &nq_batch, &slab, "sr_sparse_search_masked"));
+        SR_TRY(subset_plan(idx->ws_limit, nq, k, f.m, array ? SS_TILE : 64, &nq_batch, &slab, who));
     }
     SR_TRY(subset_status_begin(&idx->pair_status, s));        // the list kernels read it; nothing here can raise it
     if (subset_sparse_use_mask(idx, nq, k, f.m)) {
@@ -549,5 +563,101 @@ extern "C" int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_
         return sparse_certified_search(idx, call, &f, s);
     }
     SR_TRY(sparse_filter_need_list(idx, &f, s));
-    return sparse_subset_lists(idx, call, f.list, f.m, array, s, "sr_sparse_search_masked");
+    return sparse_subset_lists(idx, call, f.list, f.m, array, s, who);
+}
+
+int sparse_masked_lists(sr_sparse_index* idx, const SparseCall& call, const uint32_t* d_mask_words, int64_t m, hipStream_t s, const char* who) {
+    const int64_t n_blocks = doc_mask_blocks(idx->n_docs);
+    SR_TRY(idx->filt_blocks.reserve(n_blocks + 1, who));
+    // the count is known; the launch is there for the per-workgroup offsets the expansion starts from
+    SR_TRY(launch_doc_mask_count(d_mask_words, idx->n_docs, idx->filt_blocks.p, idx->filt_blocks.p + n_blocks, s));
+    SparseDocFilter f;
+    f.words = d_mask_words; f.m = m; f.who = who;
+    SR_TRY(sparse_filter_need_list(idx, &f, s));
+    SR_TRY(subset_status_begin(&idx->pair_status, s));
+    return sparse_subset_lists(idx, call, f.list, f.m, subset_sparse_use_array(f.m, idx->n_docs), s, who);
+}
+
+// ---- filter groups: a document bitmap per query (sr_sparse_search_grouped) --------------------------------------------
+// Route rule.  The grouped pass is the mask route with the bit read from the query's own bitmap: one pass of the certified scorer whatever
+// the groups are.  The loop runs the body of sr_sparse_search_masked once per group that holds a query.  auto takes the pass where it
+// applies and sum_g nq_g * m_g reaches SR_SUBSET_SPARSE_MASK_CROSSOVER - a constant that was measured for ONE group (above).  The loop's
+// per-group overhead (a gather of the queries, the count's read-back, and for a group on the mask route a whole pass of its own) moves
+// the real crossing down as the groups multiply; the constant is left where it is (DESIGN.md 4.20 has the measurements).  Dev switch
+// SR_GROUPED_SPARSE_ROUTE=pass|loop forces one, read per call; `pass` where the pass does not apply is served by the loop.
+static bool grouped_sparse_wants_pass(int64_t pairs) {
+    if (const char* route = sr_dev_getenv("SR_GROUPED_SPARSE_ROUTE")) {
+        if (strcmp(route, "pass") == 0) return true;
+        if (strcmp(route, "loop") == 0) return false;
+    }
+    return pairs >= SR_SUBSET_SPARSE_MASK_CROSSOVER;
+}
+
+// every output row of the call := padding (0, -1), every count 0
+__global__ void sparse_pad_rows_kernel(float* __restrict__ scores, int64_t* __restrict__ ids, int32_t* __restrict__ counts, int64_t nq, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        scores[i] = 0.f;
+        ids[i] = -1;
+        if (counts && i < nq) counts[i] = 0;
+    }
+}
+
+extern "C" int sr_sparse_search_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                        int64_t nq, int k, float threshold, const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits,
+                                        const int32_t* d_query_group, int64_t id_base, int64_t id_stride, float* d_out_scores,
+                                        int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_search_grouped: null index");
+    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_grouped: bad nq");
+    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_grouped: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_search_grouped: the masks hold n_bits=%lld bits each, the index %lld documents", (long long)n_bits,
+               (long long)idx->n_docs);
+    SR_REQUIRE(n_groups >= 1, "sr_sparse_search_grouped: n_groups=%lld, at least one group is needed", (long long)n_groups);
+    const int64_t n_pad = ceil_div64(n_bits, 1024) * 32;      // words of a bitmap in the score kernel's length: whole tiles of 1 024 documents
+    SR_REQUIRE(n_groups < (1ll << 32) && (n_groups + 1) * n_pad < (1ll << 32), "sr_sparse_search_grouped: %lld groups (and their union) of %lld words exceed 2^32 words",
+               (long long)n_groups, (long long)n_pad);
+    SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
+               "sr_sparse_search_grouped: global doc index exceeds 32 bits");
+    if (nq == 0) return SR_OK;
+    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && d_query_group && (d_group_words || n_bits == 0), "sr_sparse_search_grouped: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    StreamOrder::Scope in_order(idx->order, s);
+    const SparseCall call{d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts};
+    // 1. the group ids: one read-back of 4 nq bytes
+    std::vector<int32_t> grp((size_t)nq);
+    SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    for (int64_t q = 0; q < nq; ++q)
+        if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
+            const int64_t n = nq * (int64_t)k;
+            const int64_t blocks = ceil_div64(n > nq ? n : nq, 256) < 65536 ? ceil_div64(n > nq ? n : nq, 256) : 65536;
+            hipLaunchKernelGGL(sparse_pad_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_out_scores, d_out_ids, d_out_counts, nq, n);
+            SR_CHECK_LAUNCH();
+            SR_CHECK_HIP(hipStreamSynchronize(s));
+            sr_set_error("sr_sparse_search_grouped: query %lld is in group %d, outside [0, %lld) (nothing was searched)", (long long)q,
+                         grp[(size_t)q], (long long)n_groups);
+            return SR_ERR_INVALID;
+        }
+    // 2. set bits per group, one word-parallel pass over all bitmaps: one read-back of 8 n_groups bytes
+    const int64_t n_words = doc_mask_words(n_bits);
+    SR_TRY(idx->grp_counts.reserve(n_groups + 1, "sr_sparse_search_grouped"));
+    SR_TRY(launch_doc_masks_check(d_group_words, n_groups, n_bits, nullptr, idx->grp_counts.p, s));
+    std::vector<int64_t> counts((size_t)n_groups);
+    SR_CHECK_HIP(hipMemcpyAsync(counts.data(), idx->grp_counts.p, (size_t)n_groups * 8, hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    int64_t pairs = 0;
+    bool any_bit = false;                                  // does a group with a query allow a document at all
+    for (int64_t q = 0; q < nq; ++q) {
+        pairs += counts[(size_t)grp[(size_t)q]];
+        any_bit = any_bit || counts[(size_t)grp[(size_t)q]] > 0;
+    }
+    SparseGroups groups;
+    groups.words = d_group_words; groups.n_groups = n_groups; groups.n_words = n_words;
+    groups.h_group = grp.data(); groups.h_count = counts.data();
+    // 3. the pass where the masked search's mask route would apply and the padded bitmaps fit the workspace limit; else the group loop
+    if (grouped_sparse_wants_pass(pairs) && any_bit && sparse_cert_applies(idx, k) && sparse_cert_group_pad_bytes(idx->cert, n_groups) <= idx->ws_limit) {
+        SR_TRY(sparse_cert_group_pad(idx, d_group_words, n_groups, d_query_group, nq, &groups.group_pad, &groups.union_pad, &groups.qoff, s));
+        if (groups.group_pad) return sparse_certified_search(idx, call, nullptr, s, &groups);
+    }
+    return sparse_grouped_each(idx, call, groups, nullptr, false, s);
 }

@@ -25,7 +25,7 @@ import torch
 from tqdm import tqdm
 
 from . import _lib
-from .doc_filter import Filter, allowed_positions_on, doc_mask_from_list, flags_to_words, one_filter
+from .doc_filter import Filter, allowed_positions_on, doc_mask_from_list, doc_mask_remap, flags_to_words, one_filter
 from .scoring import DenseIndexHIP, SparseIndexHIP, sparse_csr_build, sparse_csr_expand_terms
 from .utils.inverted_index import IndexDictOfArray
 from .utils.run_file import IdTable, PiecewiseRunWriter, RunResult, id_table, to_host, write_run_json
@@ -876,24 +876,50 @@ class SparseRetrieval:
         its device, uploaded and packed once per call (doc_filter.flags_to_words)."""
         return flags_to_words(allowed_mask, self.hip_index.n_docs, "document position", self._dev)
 
-    def _resolve(self, who, allowed_ids=None, allowed_mask=None):
-        """allowed_ids / allowed_mask of a search -> a doc_filter.Filter on the index's device (None: no filter), resolved and uploaded
-        once per call; the argument rule (doc_filter.one_filter) comes before anything is uploaded."""
-        one_filter(who, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+    def allowed_group_words(self, allowed_masks, query_group):
+        """allowed_masks bool [G, document positions] and query_group int [number of queries] -> (packed bitmaps int32 [G, W] on the
+        index's device, group ids int64 on the device), packed once per call (doc_filter.flags_to_words)."""
+        words = flags_to_words(allowed_masks, (None, self.hip_index.n_docs), "document position", self._dev)
+        groups = query_group if isinstance(query_group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(query_group))
+        if groups.dim() != 1 or groups.dtype.is_floating_point or groups.dtype == torch.bool:
+            raise ValueError(f"query_group must hold one integer group id per query, got {groups.dtype} {tuple(groups.shape)}")
+        return words, groups.to(device=self._dev, dtype=torch.int64)
+
+    def _resolve(self, who, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
+        """The filter keywords of a search -> a doc_filter.Filter on the index's device (None: no filter), resolved and uploaded once per
+        call; the argument rules (doc_filter.one_filter) come before anything is uploaded."""
+        one_filter(who, allowed_masks, query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
         if allowed_ids is not None:
             return Filter("subset", self.allowed_subset(allowed_ids))
-        return None if allowed_mask is None else Filter("mask", self.allowed_mask_words(allowed_mask))
+        if allowed_mask is not None:
+            return Filter("mask", self.allowed_mask_words(allowed_mask))
+        if allowed_masks is not None:
+            return Filter("groups", *self.allowed_group_words(allowed_masks, query_group))
+        return None
+
+    def _search(self, q, topk, threshold, filt, row0=0):
+        """One search of the query CSR `q` under a resolved filter (None: none).  Under groups the queries are rows row0 .. of the query
+        set the filter's group ids were given for (SparseIndexHIP.search_grouped)."""
+        if filt is not None and filt.kind == "groups":
+            if row0 + len(q) > filt.groups.numel():
+                raise ValueError(f"query_group must hold one group id per query, got {filt.groups.numel()} for at least {row0 + len(q)} queries")
+            return self.hip_index.search_grouped(q.row_ptr, q.cols, q.vals, topk, filt.data, filt.groups[row0:row0 + len(q)], threshold=threshold)
+        return self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, **_search_filter(filt))
 
     def _sparse_retrieve_multithreaded(self, sparse_query_vecs, qids, threshold=0., topk=1000, allowed_ids=None, allowed_mask=None,
-                                       _filter=None):
+                                       allowed_masks=None, query_group=None, _filter=None):
         """allowed_ids (None: every document): collection ids - only these documents are ranked.  allowed_mask: the same filter as a
-        boolean array over document positions; one of the two at most (_filter: such a filter already resolved and on the device,
-        doc_filter.Filter).  indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
+        boolean array over document positions; one of the two at most.  allowed_masks bool [G, document positions] with query_group int
+        [number of queries]: a filter per query - query q is ranked within the documents of allowed_masks[query_group[q]]
+        (SparseIndexHIP.search_grouped); not together with a filter for all queries (_filter: such a filter already resolved and on the
+        device, doc_filter.Filter).  indexer.py:405-474 runs 4 Python threads x numba and fills res[str(qid)][str(doc_ids[id_])] hit by hit; here the
         whole query set is one batched HIP search (the doc space is tiled across workgroups instead) and `res` is a RunResult
         over the result arrays: the same mapping, without 7 M dict insertions."""
-        filt = self._resolve("_sparse_retrieve_multithreaded", allowed_ids, allowed_mask) or _filter
+        filt = self._resolve("_sparse_retrieve_multithreaded", allowed_ids, allowed_mask, allowed_masks, query_group) or _filter
         q = _as_query_csr(sparse_query_vecs, self._dev)
-        scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, **_search_filter(filt))
+        if filt is not None and filt.kind == "groups" and filt.groups.numel() != len(q):
+            raise ValueError(f"query_group must hold one group id per query ({len(q)}), got {filt.groups.numel()}")
+        scores, ids, counts = self._search(q, topk, threshold, filt)
         res = RunResult(qids, to_host(scores), to_host(ids), self.doc_id_table(), to_host(counts))
         stats = defaultdict(float)
         stats["L0_q"] = q.mean_l0()
@@ -906,18 +932,23 @@ class SparseRetrieval:
                 json.dump(stats, handler)
         res.dump(os.path.join(self.out_dir, "run.json"))        # sr_write_run_json: the bytes json.dump(res) writes
 
-    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None):
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
         """allowed_ids (None: every document): collection ids, any order, duplicates allowed - only these documents are ranked; an unknown
         id raises ValueError before anything is encoded.  allowed_mask: the same filter as a boolean array over the document positions
-        of the inverted index (SparseIndexHIP.search, mask); one of the two at most.  run.json and q_stats.json keep their format.
+        of the inverted index (SparseIndexHIP.search, mask); one of the two at most.  allowed_masks bool [G, document positions] with
+        query_group int [number of queries, in loader order]: a filter per query (SparseIndexHIP.search_grouped), not together with a
+        filter for all queries; the query set is searched in pieces and every piece takes its own slice of query_group.  run.json and
+        q_stats.json keep their format.
         indexer.py:530-540.  Query groups of QUERY_GROUP_ROWS rows go through encode -> search one after the other while a worker
         thread writes the previous group's piece of run.json (sr_write_run_json_part): formatting and the page-cache copy of a Dev-sized
         file take as long as the encode, and nothing in them needs the GPU.  A query's rows do not depend on the batch it is searched in
         (certified or exact: the same bits), and the file is the one-call file byte for byte (tests/test_boundary_gpu.py)."""
-        filt = self._resolve("retrieve", allowed_ids, allowed_mask)
+        filt = self._resolve("retrieve", allowed_ids, allowed_mask, allowed_masks, query_group)
         groups = list(batch_groups(q_loader, self.QUERY_GROUP_ROWS))
         group_qids = [[x for batch in g for x in (batch["ids"] if isinstance(batch["ids"], list) else to_list(batch["ids"]))] for g in groups]
         qids = [x for g in group_qids for x in g]
+        if filt is not None and filt.kind == "groups" and filt.groups.numel() != len(qids):
+            raise ValueError(f"retrieve: query_group must hold one group id per query ({len(qids)}), got {filt.groups.numel()}")
         table = self.doc_id_table()
         if len(groups) < 2 or not (id_table(qids).distinct and id_table(table).distinct):
             sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
@@ -926,7 +957,7 @@ class SparseRetrieval:
             return res
         os.makedirs(self.out_dir, exist_ok=True)
         path = os.path.join(self.out_dir, "run.json")
-        pieces, nnz = [], 0
+        pieces, nnz, row0 = [], 0, 0
         with PiecewiseRunWriter(path) as writer:                       # run.json appears only when its last piece is written
             for gi, group in enumerate(groups):
                 with torch.inference_mode(), torch.autocast("cuda", dtype=torch.bfloat16):  # indexer.py:390-391
@@ -934,7 +965,8 @@ class SparseRetrieval:
                 q = QueryCSR(*sparse_reps_to_csr(reps, self.query_max_terms))
                 del reps
                 nnz += int(q.cols.numel())
-                scores, ids, counts = self.hip_index.search(q.row_ptr, q.cols, q.vals, topk, threshold=threshold, **_search_filter(filt))
+                scores, ids, counts = self._search(q, topk, threshold, filt, row0)
+                row0 += len(q)
                 piece = (to_host(scores), to_host(ids), to_host(counts))
                 pieces.append(piece)
                 writer.add(group_qids[gi], piece[0], piece[1], table, piece[2], last=gi + 1 == len(groups))
@@ -996,9 +1028,12 @@ class ShardedSparseRetrieval(SparseRetrieval):
         raise NotImplementedError("ShardedSparseRetrieval.search_fused: the exact fused search is not offered on a doc-sharded index; "
                                   "use HybridRetriever over one merged index")
 
-    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None):
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when
         `q_loader.replicated` is set."""
+        if allowed_masks is not None or query_group is not None:
+            raise NotImplementedError("ShardedSparseRetrieval.retrieve: filter groups (allowed_masks / query_group) are not supported on a "
+                                      "doc-sharded index; search one merged index with SparseRetrieval instead")
         if allowed_ids is not None:
             raise NotImplementedError("ShardedSparseRetrieval.retrieve: an allow-list (allowed_ids) is not supported on a doc-sharded "
                                       "index; search one merged index with SparseRetrieval instead")
@@ -1126,10 +1161,28 @@ class HybridRetriever(SparseRetrieval):
         sparse = allowed_positions_on(allowed_ids, self.inverse_id_map(), self._dev, skip_unknown=True)
         return self.dense_index.allowed_subset(allowed_ids), sparse
 
-    def _retrieve_both(self, q_loader, topk, threshold, allowed_ids=None):
+    def allowed_group_filters(self, allowed_masks, query_group):
+        """allowed_masks bool [G, dense index positions] (the numbering of allowed_mask) and query_group int [number of queries] -> the
+        two heads' doc_filter.Filter("groups", ...): the dense head takes the rows as they are; for the sparse head every row is carried
+        over to the inverted index's numbering (doc_mask_remap with the _position_maps table), one row at a time, stacked on the device.
+        A document without a posting has no sparse position and simply drops out of the sparse row."""
+        d_filt = Filter("groups", *self.dense_index.allowed_group_words(allowed_masks, query_group))
+        _, s2d = self._position_maps()
+        n_dense, n_sparse = self.dense_index.index.id_end, self.hip_index.n_docs
+        s2d = s2d[:n_sparse] if s2d.numel() >= n_sparse else torch.cat([s2d, s2d.new_full((n_sparse - s2d.numel(),), -1)])
+        s_words = torch.stack([doc_mask_remap(row, n_dense, s2d, n_sparse) for row in d_filt.data]) if n_sparse else \
+            torch.zeros((d_filt.data.shape[0], 0), dtype=torch.int32, device=self._dev)
+        return d_filt, Filter("groups", s_words, d_filt.groups)
+
+    def _retrieve_both(self, q_loader, topk, threshold, allowed_ids=None, allowed_masks=None, query_group=None):
         """The two searches and their files (sparse/run.json + q_stats.json, dense/run.json): shared by retrieve and retrieve_fused."""
+        one_filter("HybridRetriever.retrieve", allowed_masks, query_group, allowed_ids=allowed_ids)
         d_subset, s_subset = (None, None) if allowed_ids is None else (Filter("subset", t) for t in self.allowed_subsets(allowed_ids))
+        if allowed_masks is not None:
+            d_subset, s_subset = self.allowed_group_filters(allowed_masks, query_group)
         sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
+        if allowed_masks is not None and d_subset.groups.numel() != len(qids):
+            raise ValueError(f"HybridRetriever.retrieve: query_group must hold one group id per query ({len(qids)}), got {d_subset.groups.numel()}")
         sparse_res, sparse_stats = self._sparse_retrieve(sparse_query_vecs, qids, threshold=threshold, topk=topk, _filter=s_subset)
         dense_res = self._dense_retrieve(dense_query_vecs, qids, topk=topk, _filter=d_subset)
         with open(os.path.join(self.sparse_out_dir, "q_stats.json"), "w") as handler:
@@ -1138,9 +1191,11 @@ class HybridRetriever(SparseRetrieval):
         dense_res.dump(os.path.join(self.dense_out_dir, "run.json"))
         return sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res
 
-    def retrieve(self, q_loader, topk, id_dict=False, threshold=0., allowed_ids=None):
-        """allowed_ids (None: every document): database ids - both heads rank only these documents (allowed_subsets)."""
-        return self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids)[3:]
+    def retrieve(self, q_loader, topk, id_dict=False, threshold=0., allowed_ids=None, allowed_masks=None, query_group=None):
+        """allowed_ids (None: every document): database ids - both heads rank only these documents (allowed_subsets).  allowed_masks bool
+        [G, dense index positions] (the numbering of allowed_mask()) with query_group int [number of queries]: a filter per query for
+        both heads (allowed_group_filters); not together with allowed_ids."""
+        return self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids, allowed_masks=allowed_masks, query_group=query_group)[3:]
 
     def _position_maps(self):
         """The two indexes number documents independently: (dense position -> sparse position, -1 where the inverted index has no
@@ -1155,15 +1210,17 @@ class HybridRetriever(SparseRetrieval):
             self._s2d = torch.from_numpy(s2d).to(self._dev)
         return self._d2s, self._s2d
 
-    def retrieve_fused(self, q_loader, topk, weights=(1.0, 1.0), threshold=0., allowed_ids=None):
+    def retrieve_fused(self, q_loader, topk, weights=(1.0, 1.0), threshold=0., allowed_ids=None, allowed_masks=None, query_group=None):
         """`retrieve` (the same two runs, the same bytes) plus {out_dir}/fused/run.json: per query the UNION of the two top-k lists,
         taken over database ids, is scored by BOTH heads with the pair kernels (a document only one search found gets its other
         score exactly, not a zero) and ranked by fused = float32(w_d * dense) + float32(w_s * sparse), top-k by (fused descending,
         sparse-index position ascending; a document without a posting has sparse score 0.0 and sorts after every indexed one).
         Every document of the inverted index must be in the dense index.  allowed_ids (None: every document): database ids - both
-        heads, and with them the union that is fused, are restricted to these documents.  Returns (sparse_res, dense_res, fused_res)."""
+        heads, and with them the union that is fused, are restricted to these documents; allowed_masks / query_group as for retrieve: a
+        filter per query, the union of the two restricted lists is fused.  Returns (sparse_res, dense_res, fused_res)."""
         from .rerank import fused_scores, ranked_run
-        sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res = self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids)
+        sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res = self._retrieve_both(
+            q_loader, topk, threshold, allowed_ids=allowed_ids, allowed_masks=allowed_masks, query_group=query_group)
         dev, nq = self._dev, len(qids)
         d2s, s2d = self._position_maps()
         n_dense = int(d2s.numel())

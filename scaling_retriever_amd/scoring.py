@@ -548,6 +548,27 @@ class SparseIndexHIP:
                    _ptr(scores), _ptr(ids), _ptr(counts))
         return scores, ids, counts
 
+    def search_grouped(self, q_indptr, q_cols, q_vals, k, masks, query_group, threshold=0.0, id_base=0, id_stride=1):
+        """Top-k of every query within its own group's documents (include/sr_hip.h sr_sparse_search_grouped).  masks: one bitmap per group
+        over [0, n_docs) - bool [G, n_docs] (tensor / array, packed on the device) or int32 / uint32 words [G, ceil(n_docs / 32)] already
+        packed (pack_doc_masks); query_group: int array / tensor [nq], query q searches under masks[query_group[q]].  The rows of a
+        group's queries are exactly what search(those queries, k, mask=masks[g]) returns.  Returns (scores [nq,k], ids [nq,k], counts
+        [nq]).  Wrong shapes, a wrong word count, a length mismatch or non-integer groups: ValueError before anything is uploaded; a group
+        id outside [0, G): ValueError naming the query, every row of the result is then padding."""
+        masks = mask_argument(masks, lambda: self.n_docs, "n_docs", ndim=2)
+        nq = len(q_indptr) - 1
+        query_group = query_group_argument(query_group, nq)
+        q, nq = self._query_csr(q_indptr, q_cols, q_vals)
+        words, n_bits = mask_on_device(*masks, self.device)
+        # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
+        groups = _valid(_to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32))
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        counts = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        self._call("sr_sparse_search_grouped", *map(_ptr, q), nq, int(k), float(threshold), _ptr(words), int(masks[0].shape[0]), n_bits,
+                   _ptr(groups), int(id_base), int(id_stride), _ptr(scores), _ptr(ids), _ptr(counts))
+        return scores, ids, counts
+
     def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False, mask=None):
         """Every document scoring above a threshold - the full list of numba_score_float (scaling_retriever/indexer.py:324-344;
         include/sr_hip.h sr_sparse_range_count / _fill): queries as CSR as for `search`; thresholds a float for all queries, or a
