@@ -261,7 +261,8 @@ int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t 
  * the gap check's word (8 n_groups + 8 bytes); then the pass route once for the certificate's flags, as the masked search does, and
  * once more only if queries were re-done; the loop route once at its end.
  * sr_dense_index_filter_stats / _filter_query_stats count a call that ran the grouped pass like any filtered search (the loop: not at
- * all).  Not offered under groups: range searches and the exact hybrid search, k > sr_max_topk(), doc-sharded search.  The sparse
+ * all).  Also under groups: the range search (sr_dense_range_count_grouped / _fill_grouped below) and, in Python, the exact hybrid
+ * search (hybrid.search_fused(masks=, query_group=)).  Not offered under groups: k > sr_max_topk(), doc-sharded search.  The sparse
  * head under groups is sr_sparse_search_grouped.                                                                                    */
 int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, int k,
                             const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits,
@@ -288,8 +289,9 @@ int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queries, int64_t
  * k = 8s + j, then 8s + 4 + j) for EVERY nq, 1 included, whatever sr_dense_index_set_precision says: a returned score equals
  * sr_dense_score_pairs of that pair bit for bit, and sr_dense_search's wherever that search accumulates in this order.  fp32 and fp16
  * rows alike (the twin contract of sr_dense_index_add_f16).  No atomics: two calls return the same bytes.  Under a document bitmap:
- * sr_dense_range_count_masked / _fill_masked below.  Not offered: a range search under a per-query mask or a list (a caller with a
- * short list has sr_dense_score_pairs), doc-sharded, or on the certified filter's 16-bit pass.                    */
+ * sr_dense_range_count_masked / _fill_masked below; under a bitmap per query: sr_dense_range_count_grouped / _fill_grouped.  Not
+ * offered: a range search under a list (a caller with a short list has sr_dense_score_pairs), doc-sharded, or on the certified
+ * filter's 16-bit pass.                                                                                           */
 int sr_dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
                          int64_t* d_lims, int64_t* total, sr_stream stream);
 int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
@@ -305,12 +307,37 @@ int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq,
  * word ceil(n_bits / 32) - 1.  The bitmap is read in place by both passes: keep it unchanged between the count and its fill.  A
  * 256-row tile whose bits are all clear is skipped whole (no loads, no MFMAs), so a clustered filter costs about its share of
  * non-empty tiles; under a uniformly random filter nearly every tile holds an allowed row and the pass costs what the unrestricted
- * one does.  Not offered: per-query masks, doc-sharded.                                                                            */
+ * one does.  Per-query masks: sr_dense_range_count_grouped / _fill_grouped below.  Not offered: doc-sharded.                       */
 int sr_dense_range_count_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
                                 const uint32_t* d_mask_words, int64_t n_bits, int64_t* d_lims, int64_t* total, sr_stream stream);
 int sr_dense_range_fill_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
                                const uint32_t* d_mask_words, int64_t n_bits, const int64_t* d_lims, float* d_out_scores,
                                int64_t* d_out_ids, int64_t capacity, sr_stream stream);
+/* The range search under a document bitmap PER QUERY (filter groups): d_group_words uint32 [n_groups, W], W =
+ * ceil(n_bits / 32), one bitmap per group in the convention above, n_bits == sr_dense_index_id_end(idx); d_query_group int32 [nq]: query
+ * q searches under bitmap d_query_group[q].  All on the device.
+ * Contract: for every group g the lists of the queries with d_query_group[q] == g are EXACTLY what sr_dense_range_count_masked /
+ * _fill_masked return for those queries under bitmap g - lengths, ids, score bits (the chain of sr_dense_score_pairs) and (segment, row)
+ * order - on fp32 and fp16 rows, contiguous and strided segments, for every nq, 1 included.  One group is the masked call byte for byte;
+ * n_groups == nq, a group without a query and an all-clear bitmap are all valid.  The guard p < min(lims[q + 1], capacity) is on every
+ * store; no atomics: two calls return the same bytes.  Bits are consulted only at the indices of indexed documents (a set bit in a gap
+ * of a strided segment is ignored) and nothing past word W - 1 of a group's bitmap is read.
+ * A 256-row tile is skipped when the UNION of the bitmaps of the groups that have a query is clear there; the count builds that union
+ * (W words) and the queries' word offsets (4 bytes per query, rounded up to 256 queries) on the handle, counted against the workspace
+ * limit (SR_ERR_NOMEM with the byte count where they do not fit), and the fill reuses both: the fill does not read d_query_group again,
+ * which - like the bitmaps - must be what the count was given.  The hit test reads the query's own bitmap behind the product of a tile.
+ * Errors, all SR_ERR_INVALID.  Before any device work: n_bits != id_end, n_groups < 1, n_groups * W >= 2^32, a null pointer with nq > 0.
+ * An entry of d_query_group outside [0, n_groups): found before any scoring (the count waits for the stream once to read the 4 nq
+ * bytes), sr_last_error() names the first such query, d_lims is written as zeros and *total as 0, and no fill can follow.  Pairing on
+ * the handle: three kinds - unrestricted, masked, grouped; a fill needs a preceding count of its own kind with the same nq (and, grouped,
+ * the same n_groups); any mix is SR_ERR_INVALID and nothing is written.
+ * Not offered under groups: doc-sharded indexes.                                                                                   */
+int sr_dense_range_count_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                 const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits, const int32_t* d_query_group,
+                                 int64_t* d_lims, int64_t* total, sr_stream stream);
+int sr_dense_range_fill_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits, const int32_t* d_query_group,
+                                const int64_t* d_lims, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream);
 int sr_dense_index_destroy(sr_dense_index* idx);
 /* Measurement hook: while enabled, every launch of the score kernel is bracketed by HIP
  * events on the search stream.  _read synchronises those events and returns the number
@@ -431,7 +458,8 @@ int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, con
  * of 8 192 queries) and, for a batch with handed-back queries, once for their flags, once for the query offsets (8 (nq + 1) bytes) and
  * once at the end of the re-do; the loop waits once for the query offsets, per group as sr_sparse_search_masked does, and once at its
  * end.  sr_sparse_index_cert_stats counts a grouped pass like any other search; the loop's masked bodies count as they do on their own.
- * Not offered under groups: range searches, the exact hybrid search, doc-sharded search.                                            */
+ * Also under groups: the range search (sr_sparse_range_count_grouped / _fill_grouped below) and, in Python, the exact hybrid search.
+ * Not offered under groups: doc-sharded search.                                                                                    */
 int sr_sparse_search_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols,
                              const float* d_q_vals, int64_t nq, int k, float threshold,
                              const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits,
@@ -460,8 +488,9 @@ int sr_sparse_search_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, co
  * every document with a score above -inf.  nq = 0 or n_docs = 0: lims all zero, total 0.  Scores: the term-serial chain
  * of sr_sparse_search / sr_sparse_score_pairs - an unfused fp32 multiply then add, in the query's term order, from +0.0f - so a returned
  * score equals sr_sparse_score_pairs of that pair bit for bit.  No global atomic takes part in placing a result: two calls return the
- * same bytes.  Under a document bitmap: sr_sparse_range_count_masked / _fill_masked below.  Not offered: a range search under a
- * per-query mask or a list, doc-sharded, or on the certified scorer's 16-bit stage.                                 */
+ * same bytes.  Under a document bitmap: sr_sparse_range_count_masked / _fill_masked below; under a bitmap per query:
+ * sr_sparse_range_count_grouped / _fill_grouped.  Not offered: a range search under a list, doc-sharded, or on the certified scorer's
+ * 16-bit stage.                                                                                                     */
 int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                           int64_t nq, const float* d_thresholds, int64_t* d_lims, int64_t* total, sr_stream stream);
 int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
@@ -475,7 +504,8 @@ int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const 
  * a preceding count of the same kind with the same nq, and the count's bitmap.  Bits of the last word at or beyond n_bits are
  * ignored and the library never reads past word ceil(n_bits / 32) - 1 (the kernels clamp their reads; no copy is kept).  The bitmap is
  * read in place by both passes: keep it unchanged between the count and its fill.  An 8 192-document tile whose 256 words are all zero
- * is skipped before a posting is touched.  Not offered: per-query masks, doc-sharded.                                              */
+ * is skipped before a posting is touched.  Per-query masks: sr_sparse_range_count_grouped / _fill_grouped below.  Not offered:
+ * doc-sharded.                                                                                                                       */
 int sr_sparse_range_count_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                                  int64_t nq, const float* d_thresholds, const uint32_t* d_mask_words, int64_t n_bits,
                                  int64_t* d_lims, int64_t* total, sr_stream stream);
@@ -483,6 +513,26 @@ int sr_sparse_range_fill_masked(sr_sparse_index* idx, const int64_t* d_q_indptr,
                                 int64_t nq, const float* d_thresholds, const uint32_t* d_mask_words, int64_t n_bits,
                                 const int64_t* d_lims, int64_t id_base, int64_t id_stride, float* d_out_scores, int64_t* d_out_ids,
                                 int64_t capacity, sr_stream stream);
+/* The range search under a document bitmap PER QUERY (filter groups): d_group_words uint32 [n_groups, W], W =
+ * ceil(n_bits / 32), one bitmap per group over document positions, n_bits == n_docs; d_query_group int32 [nq]: query q searches under
+ * bitmap d_query_group[q].  All on the device.  Contract: for every group g the lists of the queries with d_query_group[q] == g are
+ * EXACTLY what sr_sparse_range_count_masked / _fill_masked return for those queries under bitmap g - counts, ids, score bits, document
+ * order, id_base / id_stride, and the zero-score documents of the allowed set under a negative threshold.  One group is the masked call
+ * byte for byte; n_groups == nq, a group without a query and an all-clear bitmap are valid.  A workgroup serves one (query, chunk), so
+ * the query's group only selects the bitmap its tile skip and hit test read; nothing past word W - 1 of a group's bitmap is read.
+ * Errors, all SR_ERR_INVALID.  Before any device work: n_bits != n_docs, n_groups < 1, n_groups * W >= 2^32, a null pointer with nq > 0.
+ * An entry of d_query_group outside [0, n_groups): found before any scoring (the count waits for the stream once to read the 4 nq
+ * bytes), sr_last_error() names the first such query, d_lims is written as zeros and *total as 0, and no fill can follow.  The count
+ * keeps the checked group ids on the handle (4 nq bytes) and its fill reads those, not d_query_group.  Pairing on the handle: three
+ * kinds - unrestricted, masked, grouped; a fill needs a preceding count of its own kind with the same nq (and, grouped, the same
+ * n_groups); any mix is SR_ERR_INVALID and nothing is written.  Not offered under groups: doc-sharded indexes.                      */
+int sr_sparse_range_count_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                  int64_t nq, const float* d_thresholds, const uint32_t* d_group_words, int64_t n_groups,
+                                  int64_t n_bits, const int32_t* d_query_group, int64_t* d_lims, int64_t* total, sr_stream stream);
+int sr_sparse_range_fill_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                 int64_t nq, const float* d_thresholds, const uint32_t* d_group_words, int64_t n_groups,
+                                 int64_t n_bits, const int32_t* d_query_group, const int64_t* d_lims, int64_t id_base,
+                                 int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream);
 int sr_sparse_index_destroy(sr_sparse_index* idx);
 /* Measurement hook as for the dense index; algorithmic bytes = 8 B per posting of the
  * query terms that falls in the launched doc tiles (computed on the device).       */

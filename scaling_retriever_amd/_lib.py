@@ -59,6 +59,10 @@ SIGNATURES = {
                                             c_void_p]),
     "sr_dense_range_fill_masked": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                            c_void_p]),
+    "sr_dense_range_count_grouped": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                             ctypes.POINTER(c_int64), c_void_p]),
+    "sr_dense_range_fill_grouped": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int64, c_void_p]),
     "sr_doc_mask_remap": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "sr_dense_index_set_precision": (c_int, [c_void_p, c_int]),
     "sr_dense_search_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
@@ -92,6 +96,10 @@ SIGNATURES = {
                                              ctypes.POINTER(c_int64), c_void_p]),
     "sr_sparse_range_fill_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                             c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sr_sparse_range_count_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                              c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    "sr_sparse_range_fill_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                             c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "sr_sparse_index_block_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
                                             ctypes.POINTER(c_int64)]),
     "sr_sparse_index_destroy": (c_int, [c_void_p]),

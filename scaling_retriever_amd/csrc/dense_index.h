@@ -73,8 +73,18 @@ struct sr_dense_index {
     DeviceBuf<uint32_t> range_tab;                                   // [chunks of all segments, range_nq]
     int64_t range_nq = -1, range_total = 0, range_chunk_rows = 0;    // range_nq = -1: no count to fill from
     size_t range_segs = 0; int64_t range_ntotal = 0;                 // stamp of the segment list (segments are only ever added)
-    bool range_masked = false;                                       // the last count ran under a bitmap: its fill must too
+    int range_kind = 0;                                              // what the last count ran under (SR_RANGE_KIND_*): its fill must too
+    // sr_dense_range_count_grouped: written by the count, read by its fill (buffers of their own: a grouped search in between leaves them)
+    DeviceBuf<uint32_t> range_qoff;        // [range_nq rounded up to 256] word offset of every query's bitmap
+    DeviceBuf<uint32_t> range_union;       // [W] the OR of the bitmaps of the groups that have a query: the tile skip reads it
+    DeviceBuf<int32_t> range_used;         // the ids of those groups, ascending
+    int64_t range_groups = 0;              // n_groups of the last grouped count
 };
+// the three kinds of a range search on a handle: a fill needs a preceding count of its own kind
+enum { SR_RANGE_KIND_ALL = 0, SR_RANGE_KIND_MASKED = 1, SR_RANGE_KIND_GROUPED = 2 };
+static inline const char* sr_range_kind_text(int kind) {
+    return kind == SR_RANGE_KIND_GROUPED ? "under filter groups" : kind == SR_RANGE_KIND_MASKED ? "under a mask" : "without a mask";
+}
 
 // bf16 planes of every segment a score mode needs (the certified filter keeps its own fp16 plane, filter_prepare_segment)
 static inline int planes_of(int precision) {

@@ -161,7 +161,7 @@ extern "C" int sr_dense_index_destroy(sr_dense_index* idx) {
     if (idx->pair_status) (void)hipFree(idx->pair_status);      // allocated by pair_status_begin / subset_status_begin
     idx->mask_words.release(); idx->mask_list.release(); idx->mask_blocks.release();
     idx->grp_valid.release(); idx->grp_qoff.release(); idx->grp_counts.release();
-    idx->range_tab.release();
+    idx->range_tab.release(); idx->range_qoff.release(); idx->range_union.release(); idx->range_used.release();
     delete idx;
     return SR_OK;
 }

@@ -25,12 +25,20 @@ struct DenseRangeArgs {
     int64_t capacity;
     // masked kernels only
     const uint32_t* mask;     // bitmap over global doc indices: bit (i & 31) of word i >> 5; read at id_base + row * id_stride of the segment's rows only
+    // grouped kernels only: `mask` holds the groups' bitmaps stacked, mask_words words each
+    const uint32_t* mask_qoff;    // [nq rounded up to 256] word offset of every query's own bitmap inside mask (0 past nq)
+    const uint32_t* mask_union;   // [mask_words] the OR of the bitmaps of the groups that have a query: decides which tiles are skipped
+    int64_t mask_words;           // words of one bitmap: nothing at or beyond them is read
 };
 // query tile: 256 wide for nq > 128, 128 wide below (as launch_dense_exact picks its pipelined kernels)
 static inline int dense_range_query_tile(int64_t nq) { return nq > 128 ? 256 : 128; }
-// a.mask null: the unrestricted kernels; else their masked twins (a hit needs its document's bit, a 256-row tile without a set bit is skipped)
+// a.mask null: the unrestricted kernels; else their masked twins (a hit needs its document's bit, a 256-row tile without a set bit is
+// skipped); with a.mask_qoff too: the grouped twins (the bit of the query's own bitmap, a tile without a bit in the union is skipped)
 int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
 int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
 // the masked instantiations (dense_range_masked.hip); called by the two above, after their checks of the chunking
 int launch_dense_range_count_masked(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
 int launch_dense_range_fill_masked(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
+// the grouped instantiations (dense_range_grouped.hip), likewise
+int launch_dense_range_count_grouped(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);
+int launch_dense_range_fill_grouped(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s);

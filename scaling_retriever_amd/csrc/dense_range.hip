@@ -26,8 +26,15 @@
 // words in scalar registers, the same in every wave, so nothing is added to the vector registers that live across the k-loop and no
 // LDS or barrier is needed.  A tile whose 256 bits are all clear runs no k-loop - no loads, no MFMAs, no barriers; the decision is
 // workgroup-uniform.  In the epilogue a block's 32 bits are ANDed into the hit word.
+//
+// Under a bitmap per query (sr_dense_range_count_grouped / _fill_grouped; GROUPED, instantiated by dense_range_grouped.hip) the ballot
+// reads the UNION of the bitmaps of the groups that have a query - built once per count by launch_doc_masks_union and kept on the handle
+// for the fill - and in the epilogue every lane tests its own query column's bitmap, found through the per-query word offsets the count
+// put on the handle (launch_doc_mask_query_offsets, as the grouped search does).  Nothing of that is live across the k-loop.
 #include "dense_range_kernel.h"
 #include "dense_index.h"
+#include "doc_mask.h"
+#include <algorithm>
 
 // table[c][q]: counts -> exclusive prefixes over the chunks; lims[q + 1] := hits of query q (summed up by dense_range_lims_kernel)
 __global__ __launch_bounds__(256) void dense_range_scan_kernel(uint32_t* table, int n_chunks, int64_t nq, int64_t* lims) {
@@ -73,8 +80,9 @@ static int launch_dense_range(const DenseRangeArgs& a, int n_chunks_seg, hipStre
         sr_set_error("dense range launch: bad chunking (%lld rows, chunks of %lld, %d chunks)", (long long)a.seg_rows, (long long)a.chunk_rows, n_chunks_seg);
         return SR_ERR_INVALID;
     }
+    if (a.mask_qoff) return FILL ? launch_dense_range_fill_grouped(a, n_chunks_seg, s) : launch_dense_range_count_grouped(a, n_chunks_seg, s);    // dense_range_grouped.hip
     if (a.mask) return FILL ? launch_dense_range_fill_masked(a, n_chunks_seg, s) : launch_dense_range_count_masked(a, n_chunks_seg, s);      // dense_range_masked.hip
-    return launch_dense_range_m<FILL, false>(a, n_chunks_seg, s);
+    return launch_dense_range_m<FILL, RangeFilter::all>(a, n_chunks_seg, s);
 }
 int launch_dense_range_count(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) { return launch_dense_range<false>(a, n_chunks_seg, s); }
 int launch_dense_range_fill(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) { return launch_dense_range<true>(a, n_chunks_seg, s); }
@@ -105,25 +113,41 @@ static int64_t dense_range_chunking(const sr_dense_index* idx, int64_t max_chunk
     }
 }
 
+// What a range search runs under: kind SR_RANGE_KIND_*; mask = the bitmap (masked) or the groups' stacked bitmaps (grouped); the last
+// three for the grouped kind only.
+struct DenseRangeFilter {
+    int kind = SR_RANGE_KIND_ALL;
+    const uint32_t* mask = nullptr;
+    const uint32_t* qoff = nullptr;
+    const uint32_t* mask_union = nullptr;
+    int64_t words = 0;
+};
+
 static void dense_range_args(const sr_dense_index* idx, const DenseSegment& seg, const float* d_queries, int64_t nq, const float* d_thr,
-                             const uint32_t* d_mask, int chunk_base, DenseRangeArgs& a) {
+                             const DenseRangeFilter& f, int chunk_base, DenseRangeArgs& a) {
     a = DenseRangeArgs{};
     a.D = seg.rows; a.Q = d_queries; a.thr = d_thr; a.seg_rows = seg.n; a.chunk_rows = idx->range_chunk_rows; a.chunk_base = chunk_base;
     a.H = idx->dim; a.nq = (int)nq; a.dtype = idx->row_dtype; a.id_base = seg.id_base; a.id_stride = seg.id_stride;
-    a.table = idx->range_tab.p; a.mask = d_mask;
+    a.table = idx->range_tab.p; a.mask = f.mask; a.mask_qoff = f.qoff; a.mask_union = f.mask_union; a.mask_words = f.words;
 }
 
-// d_mask null: the unrestricted search.  The caller holds idx->mu.
-static int dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
-                             const uint32_t* d_mask, int64_t* d_lims, int64_t* total, sr_stream stream) {
+// the argument checks of every count, before any device work
+static int dense_range_count_checks(const sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                    const int64_t* d_lims, const int64_t* total) {
     SR_REQUIRE(idx, "sr_dense_range_count: null index");
     SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_range_count: bad nq=%lld", (long long)nq);
     SR_REQUIRE(d_lims && total, "sr_dense_range_count: null d_lims or total");
     SR_REQUIRE(nq == 0 || (d_queries && d_thresholds), "sr_dense_range_count: null queries or thresholds");
     SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_range_count: queries must be 16-byte aligned");
+    return SR_OK;
+}
+
+// f.kind SR_RANGE_KIND_ALL: the unrestricted search.  The caller holds idx->mu and has run dense_range_count_checks.
+static int dense_range_count_run(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                 const DenseRangeFilter& f, int64_t* d_lims, int64_t* total, sr_stream stream) {
     hipStream_t s = (hipStream_t)stream;
     idx->range_nq = -1;
-    idx->range_masked = d_mask != nullptr;
+    idx->range_kind = f.kind;
     *total = 0;
     if (nq == 0 || idx->ntotal == 0) {
         SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
@@ -169,7 +193,7 @@ static int dense_range_count(sr_dense_index* idx, const float* d_queries, int64_
     for (const DenseSegment& seg : idx->segs) {
         const int n_seg = (int)ceil_div64(seg.n, chunk_rows);
         DenseRangeArgs a;
-        dense_range_args(idx, seg, d_queries, nq, d_thresholds, d_mask, chunk_base, a);
+        dense_range_args(idx, seg, d_queries, nq, d_thresholds, f, chunk_base, a);
         idx->prof.begin(s);
         SR_TRY(launch_dense_range_count(a, n_seg, s));
         idx->prof.end(s, 2.0 * (double)nq * (double)seg.n * idx->dim, (double)seg.n * idx->dim * (double)sr_dtype_size(idx->row_dtype));
@@ -185,11 +209,19 @@ static int dense_range_count(sr_dense_index* idx, const float* d_queries, int64_
     return SR_OK;
 }
 
+static DenseRangeFilter dense_range_one_mask(const uint32_t* d_mask) {
+    DenseRangeFilter f;
+    f.kind = d_mask ? SR_RANGE_KIND_MASKED : SR_RANGE_KIND_ALL;
+    f.mask = d_mask;
+    return f;
+}
+
 extern "C" int sr_dense_range_count(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, int64_t* d_lims,
                                     int64_t* total, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_range_count: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    return dense_range_count(idx, d_queries, nq, d_thresholds, nullptr, d_lims, total, stream);
+    SR_TRY(dense_range_count_checks(idx, d_queries, nq, d_thresholds, d_lims, total));
+    return dense_range_count_run(idx, d_queries, nq, d_thresholds, dense_range_one_mask(nullptr), d_lims, total, stream);
 }
 
 extern "C" int sr_dense_range_count_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
@@ -199,17 +231,88 @@ extern "C" int sr_dense_range_count_masked(sr_dense_index* idx, const float* d_q
     SR_REQUIRE(n_bits == dense_id_end(idx), "sr_dense_range_count_masked: n_bits=%lld, the index numbers its documents in [0, %lld)",
                (long long)n_bits, (long long)dense_id_end(idx));
     SR_REQUIRE(d_mask_words, "sr_dense_range_count_masked: null mask");
-    return dense_range_count(idx, d_queries, nq, d_thresholds, d_mask_words, d_lims, total, stream);
+    SR_TRY(dense_range_count_checks(idx, d_queries, nq, d_thresholds, d_lims, total));
+    return dense_range_count_run(idx, d_queries, nq, d_thresholds, dense_range_one_mask(d_mask_words), d_lims, total, stream);
 }
 
-// d_mask: what the preceding count was given (null: none).  The caller holds idx->mu.
-static int dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, const uint32_t* d_mask,
+// the checks the two grouped halves share, before any device work; *n_words = the words of one bitmap
+static int dense_range_group_checks(const sr_dense_index* idx, const char* who, int64_t nq, const uint32_t* d_group_words, int64_t n_groups,
+                                    int64_t n_bits, const int32_t* d_query_group, int64_t* n_words) {
+    SR_REQUIRE(n_groups >= 1, "%s: n_groups=%lld, at least one group is needed", who, (long long)n_groups);
+    SR_REQUIRE(n_bits == dense_id_end(idx), "%s: n_bits=%lld, the index numbers its documents in [0, %lld)", who, (long long)n_bits,
+               (long long)dense_id_end(idx));
+    *n_words = doc_mask_words(n_bits);
+    SR_REQUIRE(n_groups < (1ll << 32) && n_groups * *n_words < (1ll << 32), "%s: %lld groups of %lld words exceed 2^32 words", who,
+               (long long)n_groups, (long long)*n_words);
+    SR_REQUIRE(nq <= 0 || (d_query_group && (d_group_words || n_bits == 0)), "%s: null masks or query groups", who);
+    return SR_OK;
+}
+
+// Range count under a bitmap per query.  Before any scoring: the group ids are read back and checked (one wait for 4 nq bytes), the
+// queries' word offsets and the union of the used groups' bitmaps go onto the handle (a second wait: the list of used groups is host
+// memory).  Then the count of the other kinds with the grouped kernels.
+extern "C" int sr_dense_range_count_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                            const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits, const int32_t* d_query_group,
+                                            int64_t* d_lims, int64_t* total, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_count_grouped: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    int64_t n_words = 0;
+    SR_TRY(dense_range_group_checks(idx, "sr_dense_range_count_grouped", nq, d_group_words, n_groups, n_bits, d_query_group, &n_words));
+    SR_TRY(dense_range_count_checks(idx, d_queries, nq, d_thresholds, d_lims, total));
+    hipStream_t s = (hipStream_t)stream;
+    idx->range_nq = -1;                               // whatever happens below, no earlier count can be filled from
+    DenseRangeFilter f;
+    f.kind = SR_RANGE_KIND_GROUPED;
+    f.mask = d_group_words; f.words = n_words;
+    std::vector<int32_t> grp((size_t)nq), used;
+    if (nq > 0) {
+        StreamOrder::Scope in_order(idx->order, s);
+        SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        SR_CHECK_HIP(hipStreamSynchronize(s));
+        for (int64_t q = 0; q < nq; ++q)
+            if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
+                SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
+                SR_CHECK_HIP(hipStreamSynchronize(s));
+                *total = 0;
+                sr_set_error("sr_dense_range_count_grouped: query %lld is in group %d, outside [0, %lld) (nothing was scored)", (long long)q,
+                             grp[(size_t)q], (long long)n_groups);
+                return SR_ERR_INVALID;
+            }
+        if (idx->ntotal > 0) {
+            used = grp;
+            std::sort(used.begin(), used.end());
+            used.erase(std::unique(used.begin(), used.end()), used.end());
+            const int64_t nq_pad = ceil_div64(nq, 256) * 256;     // the widest query tile: a lane beyond nq reads an offset of 0
+            const int64_t scratch = 4 * (nq_pad + n_words + (int64_t)used.size());
+            if (scratch > idx->ws_limit) {
+                sr_set_error("sr_dense_range_count_grouped: the queries' word offsets and the union bitmap need %lld bytes of workspace (limit %lld bytes)",
+                             (long long)scratch, (long long)idx->ws_limit);
+                return SR_ERR_NOMEM;
+            }
+            SR_TRY(idx->range_qoff.reserve(nq_pad, "sr_dense_range_count_grouped"));
+            SR_TRY(idx->range_union.reserve(n_words > 0 ? n_words : 1, "sr_dense_range_count_grouped"));
+            SR_TRY(idx->range_used.reserve((int64_t)used.size(), "sr_dense_range_count_grouped"));
+            SR_CHECK_HIP(hipMemcpyAsync(idx->range_used.p, used.data(), used.size() * 4, hipMemcpyHostToDevice, s));
+            SR_TRY(launch_doc_masks_union(d_group_words, idx->range_used.p, (int64_t)used.size(), n_bits, idx->range_union.p, s));
+            SR_TRY(launch_doc_mask_query_offsets(d_query_group, nq, nq_pad, n_bits, idx->range_qoff.p, s));
+            SR_CHECK_HIP(hipStreamSynchronize(s));            // `used` (pageable host memory) was the source of an asynchronous copy
+            f.qoff = idx->range_qoff.p; f.mask_union = idx->range_union.p;
+        }
+    }
+    SR_TRY(dense_range_count_run(idx, d_queries, nq, d_thresholds, f, d_lims, total, stream));
+    idx->range_groups = n_groups;
+    return SR_OK;
+}
+
+// f: what the preceding count was given.  The caller holds idx->mu.
+static int dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds, const DenseRangeFilter& f,
                             const int64_t* d_lims, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_range_fill: null index");
     SR_REQUIRE(nq >= 0 && nq < (1ll << 30) && capacity >= 0, "sr_dense_range_fill: bad nq=%lld or capacity=%lld", (long long)nq, (long long)capacity);
     hipStream_t s = (hipStream_t)stream;
     SR_REQUIRE(idx->range_nq >= 0, "sr_dense_range_fill: no sr_dense_range_count precedes it on this handle");
-    SR_REQUIRE(idx->range_masked == (d_mask != nullptr), "sr_dense_range_fill: the preceding count ran %s a mask", idx->range_masked ? "under" : "without");
+    SR_REQUIRE(idx->range_kind == f.kind, "sr_dense_range_fill: the preceding count ran %s, this fill runs %s", sr_range_kind_text(idx->range_kind),
+               sr_range_kind_text(f.kind));
     SR_REQUIRE(idx->range_nq == nq, "sr_dense_range_fill: nq=%lld, the preceding count had %lld", (long long)nq, (long long)idx->range_nq);
     SR_REQUIRE(idx->range_segs == idx->segs.size() && idx->range_ntotal == idx->ntotal, "sr_dense_range_fill: the index changed since the count");
     SR_REQUIRE(capacity >= idx->range_total, "sr_dense_range_fill: capacity=%lld is below the count's total of %lld", (long long)capacity,
@@ -222,7 +325,7 @@ static int dense_range_fill(sr_dense_index* idx, const float* d_queries, int64_t
     for (const DenseSegment& seg : idx->segs) {
         const int n_seg = (int)ceil_div64(seg.n, idx->range_chunk_rows);
         DenseRangeArgs a;
-        dense_range_args(idx, seg, d_queries, nq, d_thresholds, d_mask, chunk_base, a);
+        dense_range_args(idx, seg, d_queries, nq, d_thresholds, f, chunk_base, a);
         a.lims = d_lims; a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.capacity = capacity;
         idx->prof.begin(s);
         SR_TRY(launch_dense_range_fill(a, n_seg, s));
@@ -236,7 +339,7 @@ extern "C" int sr_dense_range_fill(sr_dense_index* idx, const float* d_queries, 
                                    float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_range_fill: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    return dense_range_fill(idx, d_queries, nq, d_thresholds, nullptr, d_lims, d_out_scores, d_out_ids, capacity, stream);
+    return dense_range_fill(idx, d_queries, nq, d_thresholds, dense_range_one_mask(nullptr), d_lims, d_out_scores, d_out_ids, capacity, stream);
 }
 
 extern "C" int sr_dense_range_fill_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
@@ -247,5 +350,22 @@ extern "C" int sr_dense_range_fill_masked(sr_dense_index* idx, const float* d_qu
     SR_REQUIRE(n_bits == dense_id_end(idx), "sr_dense_range_fill_masked: n_bits=%lld, the index numbers its documents in [0, %lld)",
                (long long)n_bits, (long long)dense_id_end(idx));
     SR_REQUIRE(d_mask_words, "sr_dense_range_fill_masked: null mask");
-    return dense_range_fill(idx, d_queries, nq, d_thresholds, d_mask_words, d_lims, d_out_scores, d_out_ids, capacity, stream);
+    return dense_range_fill(idx, d_queries, nq, d_thresholds, dense_range_one_mask(d_mask_words), d_lims, d_out_scores, d_out_ids, capacity, stream);
+}
+
+// The grouped fill reads the word offsets and the union its count left on the handle: the group ids were checked there, and
+// d_query_group is not read again (it must be the count's, as the bitmaps must).
+extern "C" int sr_dense_range_fill_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, const float* d_thresholds,
+                                           const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits, const int32_t* d_query_group,
+                                           const int64_t* d_lims, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_dense_range_fill_grouped: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    int64_t n_words = 0;
+    SR_TRY(dense_range_group_checks(idx, "sr_dense_range_fill_grouped", nq, d_group_words, n_groups, n_bits, d_query_group, &n_words));
+    DenseRangeFilter f;
+    f.kind = SR_RANGE_KIND_GROUPED;
+    f.mask = d_group_words; f.words = n_words; f.qoff = idx->range_qoff.p; f.mask_union = idx->range_union.p;
+    SR_REQUIRE(idx->range_nq < 0 || idx->range_kind != SR_RANGE_KIND_GROUPED || idx->range_groups == n_groups,
+               "sr_dense_range_fill_grouped: n_groups=%lld, the preceding count had %lld", (long long)n_groups, (long long)idx->range_groups);
+    return dense_range_fill(idx, d_queries, nq, d_thresholds, f, d_lims, d_out_scores, d_out_ids, capacity, stream);
 }

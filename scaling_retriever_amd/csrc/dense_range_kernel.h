@@ -1,10 +1,28 @@
 // The dense range search's tile kernel (see dense_range.hip) and its launcher, as templates: dense_range.hip instantiates the unrestricted
-// kernels, dense_range_masked.hip their twins under a document bitmap - an object of its own, as dense_split_masked.hip is.
+// kernels, dense_range_masked.hip their twins under a document bitmap - an object of its own, as dense_split_masked.hip is - and
+// dense_range_grouped.hip those under a bitmap per query.
 #pragma once
 #include "dense_range.h"
 
-template <bool FILL, int WN, typename T, bool MASKED>
+// Which documents a range search may return.  all: every indexed one.  masked: those whose bit is set in a.mask.  grouped: query q's own
+// bitmap a.mask + a.mask_qoff[q] words decides its hits, and a.mask_union - the OR of the bitmaps of the groups that have a query - the
+// tiles that are skipped.
+enum class RangeFilter { all, masked, grouped };
+
+// GROUPED epilogue: the mask bits of the 32 rows row_b .. row_b + 31 of the segment for one query (bitmap `words`, n_words long), bit =
+// row within the block.  Stride 1: the block is 32 consecutive bits from id_base + row_b, two words joined by a funnel shift; a word at or
+// beyond n_words reads as 0 (only a block that ends past the segment's rows reaches there, and those rows are never hits).
+__device__ __forceinline__ uint32_t dense_range_block_bits(const uint32_t* __restrict__ words, int64_t n_words, int64_t bit0) {
+    const int64_t w = bit0 >> 5;
+    const unsigned sh = (unsigned)(bit0 & 31);
+    const uint32_t lo = w < n_words ? words[w] : 0u;
+    const uint32_t hi = (sh != 0 && w + 1 < n_words) ? words[w + 1] : 0u;
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+}
+
+template <bool FILL, int WN, typename T, RangeFilter FILTER>
 __device__ __forceinline__ void dense_range_body(const DenseRangeArgs& a) {
+    constexpr bool MASKED = FILTER == RangeFilter::masked, GROUPED = FILTER == RangeFilter::grouped;
     typedef typename SrRow<T>::V RowV;
     constexpr int WAVES_N = 4, WM = 4, BK = 16;
     constexpr int NT = 512, TM = 256, TN = 32 * WN * WAVES_N, LDK = BK + 4, KC = BK / 4, NSTAGE = 3;
@@ -39,15 +57,16 @@ __device__ __forceinline__ void dense_range_body(const DenseRangeArgs& a) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = tid >> 6;
-        uint64_t mbits[4] = {0, 0, 0, 0};     // MASKED: the mask bits of the tile's rows 64 j .. 64 j + 63, wave-uniform
-        if constexpr (MASKED) {
+        uint64_t mbits[4] = {0, 0, 0, 0};     // MASKED: the mask bits of the tile's rows 64 j .. 64 j + 63, wave-uniform (GROUPED: the union's)
+        if constexpr (MASKED || GROUPED) {
+            const uint32_t* __restrict__ tile_mask = GROUPED ? a.mask_union : a.mask;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t row = row0 + 64 * j + lane;
                 bool allowed = false;
                 if (row < r_end) {                // an indexed document: its index is below id_end = the mask's n_bits
                     const int64_t bit = a.id_base + row * a.id_stride;
-                    allowed = (a.mask[bit >> 5] >> (unsigned)(bit & 31)) & 1u;
+                    allowed = (tile_mask[bit >> 5] >> (unsigned)(bit & 31)) & 1u;
                 }
                 mbits[j] = __ballot(allowed);
             }
@@ -195,6 +214,18 @@ __device__ __forceinline__ void dense_range_body(const DenseRangeArgs& a) {
             const int qcol = en * WN * 32 + n * 32 + (lane_e & 31);
             const int q = q0 + qcol;
             const float thr = q < a.nq ? a.thr[q] : __builtin_inff();      // a column past nq: never a hit
+            // GROUPED: the column's own bitmap, loaded here, behind the k-loop (a.mask_qoff is padded to the query tile: 0 past nq)
+            const uint32_t* qmask = nullptr;
+            uint32_t mq[WM] = {0, 0, 0, 0};                              // GROUPED, stride 1: the column's bits of the wave's four 32-row blocks
+            if constexpr (GROUPED) {
+                __builtin_amdgcn_sched_barrier(0);                       // one column's eight words in flight at a time, not both columns'
+                qmask = a.mask + a.mask_qoff[q];
+                if (a.id_stride == 1) {
+#pragma unroll
+                    for (int m = 0; m < WM; ++m) mq[m] = dense_range_block_bits(qmask, a.mask_words, a.id_base + row0 + em * WM * 32 + m * 32);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
             int cnt = 0;
 #pragma unroll
             for (int m = 0; m < WM; ++m) {
@@ -206,8 +237,20 @@ __device__ __forceinline__ void dense_range_body(const DenseRangeArgs& a) {
                     const int lr = lr0 + m * 32 + (r & 3) + 8 * (r >> 2);
                     bool hit = lr < rows_valid && acc[m][n][r] > thr;      // strict; false for a NaN on either side
                     if constexpr (MASKED && !FILL) hit = hit && ((mh >> ((r & 3) + 8 * (r >> 2))) & 1u);
-                    if (FILL) w |= (hit ? 1u : 0u) << ((r & 3) + 8 * (r >> 2));
+                    if (FILL || GROUPED) w |= (hit ? 1u : 0u) << ((r & 3) + 8 * (r >> 2));
                     else cnt += hit ? 1 : 0;
+                }
+                if constexpr (GROUPED) {      // w: this lane's 16 rows above the threshold; the column's own bitmap decides among them
+                    if (a.id_stride == 1) {
+                        w &= mq[m] >> (4 * half);
+                    } else {                  // other strides: the bit of each such row, gathered (an indexed row: its bit lies below n_bits)
+                        for (uint32_t t = w; t; t &= t - 1u) {
+                            const int b = __ffs((int)t) - 1;
+                            const int64_t bit = a.id_base + (row0 + lr0 + m * 32 + b) * a.id_stride;
+                            if (!((qmask[bit >> 5] >> (unsigned)(bit & 31)) & 1u)) w &= ~(1u << b);
+                        }
+                    }
+                    if (!FILL) cnt += __popc(w);
                 }
                 if (FILL) {
                     w <<= 4 * half;
@@ -271,18 +314,18 @@ __device__ __forceinline__ void dense_range_body(const DenseRangeArgs& a) {
     }
 }
 
-template <int WN, typename T, bool MASKED>
-__global__ __launch_bounds__(512, 2) void dense_range_count_kernel(DenseRangeArgs a) { dense_range_body<false, WN, T, MASKED>(a); }
-template <int WN, typename T, bool MASKED>
-__global__ __launch_bounds__(512, 2) void dense_range_fill_kernel(DenseRangeArgs a) { dense_range_body<true, WN, T, MASKED>(a); }
+template <int WN, typename T, RangeFilter FILTER>
+__global__ __launch_bounds__(512, 2) void dense_range_count_kernel(DenseRangeArgs a) { dense_range_body<false, WN, T, FILTER>(a); }
+template <int WN, typename T, RangeFilter FILTER>
+__global__ __launch_bounds__(512, 2) void dense_range_fill_kernel(DenseRangeArgs a) { dense_range_body<true, WN, T, FILTER>(a); }
 
-template <bool FILL, int WN, typename T, bool MASKED>
+template <bool FILL, int WN, typename T, RangeFilter FILTER>
 static int launch_dense_range_t(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) {
     constexpr int TN = 128 * WN;
     constexpr size_t lds = sizeof(float) * 3 * (256 + TN) * (16 + 4) + (FILL ? (4 * (256 / 32 + 1) + 8) * (size_t)TN : 4 * (size_t)TN);
     static_assert(lds <= 160 * 1024, "one workgroup per CU");
-    const void* fn = FILL ? reinterpret_cast<const void*>(&dense_range_fill_kernel<WN, T, MASKED>)
-                          : reinterpret_cast<const void*>(&dense_range_count_kernel<WN, T, MASKED>);
+    const void* fn = FILL ? reinterpret_cast<const void*>(&dense_range_fill_kernel<WN, T, FILTER>)
+                          : reinterpret_cast<const void*>(&dense_range_count_kernel<WN, T, FILTER>);
     static DeviceOnce attr_once;
     bool* attr_slot = attr_once.pending();
     if (attr_slot) {
@@ -290,15 +333,15 @@ static int launch_dense_range_t(const DenseRangeArgs& a, int n_chunks_seg, hipSt
         *attr_slot = true;
     }
     dim3 grid((unsigned)ceil_div64(a.nq, TN), (unsigned)n_chunks_seg);
-    if (FILL) hipLaunchKernelGGL((dense_range_fill_kernel<WN, T, MASKED>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((dense_range_count_kernel<WN, T, MASKED>), grid, dim3(512), lds, s, a);
+    if (FILL) hipLaunchKernelGGL((dense_range_fill_kernel<WN, T, FILTER>), grid, dim3(512), lds, s, a);
+    else hipLaunchKernelGGL((dense_range_count_kernel<WN, T, FILTER>), grid, dim3(512), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }
-template <bool FILL, bool MASKED>
+template <bool FILL, RangeFilter FILTER>
 static int launch_dense_range_m(const DenseRangeArgs& a, int n_chunks_seg, hipStream_t s) {
     const bool wide = dense_range_query_tile(a.nq) == 256;
     if (a.dtype == SR_DTYPE_F16)
-        return wide ? launch_dense_range_t<FILL, 2, _Float16, MASKED>(a, n_chunks_seg, s) : launch_dense_range_t<FILL, 1, _Float16, MASKED>(a, n_chunks_seg, s);
-    return wide ? launch_dense_range_t<FILL, 2, float, MASKED>(a, n_chunks_seg, s) : launch_dense_range_t<FILL, 1, float, MASKED>(a, n_chunks_seg, s);
+        return wide ? launch_dense_range_t<FILL, 2, _Float16, FILTER>(a, n_chunks_seg, s) : launch_dense_range_t<FILL, 1, _Float16, FILTER>(a, n_chunks_seg, s);
+    return wide ? launch_dense_range_t<FILL, 2, float, FILTER>(a, n_chunks_seg, s) : launch_dense_range_t<FILL, 1, float, FILTER>(a, n_chunks_seg, s);
 }

@@ -29,5 +29,9 @@ int launch_doc_mask_add_segment(uint32_t* d_valid, int64_t n_bits, int64_t n, in
 // position names a document, nothing is tested).  n_groups * W < 2^32.
 int launch_doc_masks_check(const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits, const uint32_t* d_valid, int64_t* d_counts,
                            hipStream_t s);
+// d_union [W] := the OR of the bitmaps of the groups d_used[0 .. n_used) (int32, each in [0, n_groups)); all zero for n_used = 0.  The
+// grouped range search skips the tiles where it is clear.
+int launch_doc_masks_union(const uint32_t* d_group_words, const int32_t* d_used, int64_t n_used, int64_t n_bits, uint32_t* d_union,
+                           hipStream_t s);
 // d_qoff[q] := d_query_group[q] * W for q < nq (group ids already checked), 0 for nq <= q < nq_pad
 int launch_doc_mask_query_offsets(const int32_t* d_query_group, int64_t nq, int64_t nq_pad, int64_t n_bits, uint32_t* d_qoff, hipStream_t s);

@@ -2,7 +2,8 @@
 // ordered expand.  The reference has no counterpart (DenseFlatIndexer.search_knn, scaling_retriever/indexer.py:191-217, always ranks
 // the whole index); the bitmap is the form faiss offers as IDSelectorBitmap.  sr_dense_search_masked / _subset (dense_restrict.hip) hold
 // both forms of a filter: the bitmap feeds the certified filter's masked pass (dense_split_kernel.h), the list the gather kernel.
-// At the end of the file: the kernels of the grouped search (sr_dense_search_grouped) - stacked bitmaps checked and counted in one pass.
+// At the end of the file: the kernels of the grouped search (sr_dense_search_grouped) - stacked bitmaps checked and counted in one pass -
+// and the union of the present groups' bitmaps that the grouped range search skips tiles by (sr_dense_range_count_grouped).
 #include "doc_mask.h"
 
 #define DM_THREADS 256
@@ -237,6 +238,26 @@ int launch_doc_masks_check(const uint32_t* d_group_words, int64_t n_groups, int6
     if (gy < 1) gy = 1;
     hipLaunchKernelGGL(doc_masks_check_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(DM_THREADS), 0, s, d_group_words, n_groups, n_words, n_bits,
                        d_valid, reinterpret_cast<unsigned long long*>(d_counts));
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
+// one thread per word: the OR of that word over the bitmaps of the listed groups
+__global__ __launch_bounds__(DM_THREADS) void doc_masks_union_kernel(const uint32_t* __restrict__ words, const int32_t* __restrict__ used,
+                                                                      int64_t n_used, int64_t n_words, uint32_t* __restrict__ out) {
+    const int64_t w = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    if (w >= n_words) return;
+    uint32_t v = 0;
+    for (int64_t j = 0; j < n_used; ++j) v |= words[(int64_t)used[j] * n_words + w];
+    out[w] = v;
+}
+
+int launch_doc_masks_union(const uint32_t* d_group_words, const int32_t* d_used, int64_t n_used, int64_t n_bits, uint32_t* d_union,
+                           hipStream_t s) {
+    const int64_t n_words = doc_mask_words(n_bits);
+    if (n_words == 0) return SR_OK;
+    hipLaunchKernelGGL(doc_masks_union_kernel, dim3((unsigned)ceil_div64(n_words, DM_THREADS)), dim3(DM_THREADS), 0, s, d_group_words, d_used,
+                       n_used, n_words, d_union);
     SR_CHECK_LAUNCH();
     return SR_OK;
 }

@@ -67,7 +67,9 @@ struct sr_sparse_index {
     DeviceBuf<int32_t> range_tab;                                     // [range_chunks, range_nq]
     int64_t range_nq = -1, range_total = 0;                           // range_nq = -1: no count to fill from
     int range_chunk_tiles = 0, range_chunks = 0;
-    bool range_masked = false;                                       // the last count ran under a bitmap: its fill must too
+    int range_kind = 0;                                              // what the last count ran under (0 none, 1 a bitmap, 2 filter groups): its fill must too
+    DeviceBuf<int32_t> range_qgroup;                                  // grouped count: [range_nq] the checked group of every query, read by its fill
+    int64_t range_groups = 0;                                         // n_groups of the last grouped count
     std::mutex mu;
 };
 

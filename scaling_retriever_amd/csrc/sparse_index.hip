@@ -202,6 +202,7 @@ extern "C" int sr_sparse_index_destroy(sr_sparse_index* idx) {
     idx->filt_list.release();
     idx->grp_counts.release();
     idx->range_tab.release();
+    idx->range_qgroup.release();
     delete idx;
     return SR_OK;
 }

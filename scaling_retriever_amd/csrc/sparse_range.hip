@@ -23,6 +23,7 @@
 // are ANDed into the step's hit ballot (sparse_range_step_hits: the one predicate of the count and of the fill).
 #include "sparse_index.h"
 #include "range_scan.h"
+#include <vector>
 
 #define SRR_TILE SR_SPARSE_TILE_DOCS
 #define SRR_SUBS (SR_SPARSE_TILE_DOCS / SR_SPARSE_SKIP_DOCS)      // skip-table entries per tile
@@ -59,6 +60,8 @@ struct SparseRangeArgs {
     int64_t capacity;
     // masked kernels only
     const uint32_t* mask;     // bitmap over document positions: ceil(n_docs / 32) words, nothing beyond them is read
+    // grouped kernels only: `mask` holds the groups' bitmaps stacked, ceil(n_docs / 32) words each
+    const int32_t* qgroup;    // [nq] the group of every query, each in [0, n_groups): checked by the count before any launch
 };
 
 __device__ inline int64_t srr_readlane64(int64_t v, int j) {
@@ -216,7 +219,7 @@ __device__ __forceinline__ uint32_t sparse_range_mask_word(const uint32_t* __res
     return v;
 }
 
-template <bool FILL, bool MASKED>
+template <bool FILL, bool MASKED, bool GROUPED = false>
 __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
     __shared__ float sc[SRR_TILE + 64];         // + one dummy slot per lane for the postings beyond a run's end
     __shared__ int wave_tot[4];
@@ -227,6 +230,9 @@ __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
     const int tile_first = chunk * a.chunk_tiles;
     const int tile_end = tile_first + a.chunk_tiles < a.n_tiles ? tile_first + a.chunk_tiles : a.n_tiles;
     const float thr = a.thr[q];
+    // GROUPED (with MASKED): the query's own bitmap - one workgroup serves one query, so the choice is workgroup-uniform
+    const uint32_t* mask = a.mask;
+    if constexpr (GROUPED) mask += (int64_t)a.qgroup[q] * ((a.n_docs + 31) >> 5);
 
     int64_t pos = 0, p_end = 0;          // fill: the write position of the chunk's next hit, and the end of the query's segment
     if (FILL) {
@@ -243,7 +249,7 @@ __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
             uint32_t any = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const uint32_t v = sparse_range_mask_word(a.mask, (int64_t)tile * (SRR_TILE / 32) + j * 64 + lane, a.n_docs);
+                const uint32_t v = sparse_range_mask_word(mask, (int64_t)tile * (SRR_TILE / 32) + j * 64 + lane, a.n_docs);
                 any |= v;
                 mw = j == wave ? v : mw;
             }
@@ -290,39 +296,55 @@ __device__ __forceinline__ void sparse_range_body(const SparseRangeArgs& a) {
     }
 }
 
-template <bool MASKED>
-__global__ __launch_bounds__(256) void sparse_range_count_kernel(SparseRangeArgs a) { sparse_range_body<false, MASKED>(a); }
+template <bool MASKED, bool GROUPED = false>
+__global__ __launch_bounds__(256) void sparse_range_count_kernel(SparseRangeArgs a) { sparse_range_body<false, MASKED, GROUPED>(a); }
 
 // The chunk's cell first: table holds exclusive prefixes, so the cell's own count is the next chunk's prefix minus its own (the query's
 // total minus its own for the last chunk).  0: the workgroup returns before it touches a posting.
-template <bool MASKED>
+template <bool MASKED, bool GROUPED = false>
 __global__ __launch_bounds__(256) void sparse_range_fill_kernel(SparseRangeArgs a, int n_chunks) {
     const int64_t q = blockIdx.x;
     const int chunk = a.chunk_begin + (int)blockIdx.y;
     const int64_t mine = (int64_t)(uint32_t)a.table[(int64_t)chunk * a.nq + q];
     const int64_t next = chunk + 1 < n_chunks ? (int64_t)(uint32_t)a.table[(int64_t)(chunk + 1) * a.nq + q] : a.lims[q + 1] - a.lims[q];
     if (next == mine) return;            // block-uniform
-    sparse_range_body<true, MASKED>(a);
+    sparse_range_body<true, MASKED, GROUPED>(a);
 }
 
 static void sparse_range_args(const sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
-                              int64_t nq, const float* d_thr, const uint32_t* d_mask, SparseRangeArgs& a) {
+                              int64_t nq, const float* d_thr, const uint32_t* d_mask, const int32_t* d_qgroup, SparseRangeArgs& a) {
     a = SparseRangeArgs{};
     a.indptr = idx->indptr; a.doc_ids = idx->doc_ids; a.vals = idx->vals; a.skip = idx->skip.p;
     a.n_tiles = idx->n_tiles; a.n_docs = idx->n_docs; a.n_terms = idx->n_terms;
     a.q_indptr = d_q_indptr; a.q_cols = d_q_cols; a.q_vals = d_q_vals; a.thr = d_thr; a.nq = nq;
-    a.chunk_tiles = idx->range_chunk_tiles; a.table = idx->range_tab.p; a.mask = d_mask;
+    a.chunk_tiles = idx->range_chunk_tiles; a.table = idx->range_tab.p; a.mask = d_mask; a.qgroup = d_qgroup;
 }
 
-// d_mask null: the unrestricted search.  The caller holds idx->mu.
-static int sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
-                              const float* d_thresholds, const uint32_t* d_mask, int64_t* d_lims, int64_t* total, sr_stream stream) {
+// the three kinds of a range search on a handle: a fill needs a preceding count of its own kind
+enum { SRR_KIND_ALL = 0, SRR_KIND_MASKED = 1, SRR_KIND_GROUPED = 2 };
+static const char* srr_kind_text(int kind) {
+    return kind == SRR_KIND_GROUPED ? "under filter groups" : kind == SRR_KIND_MASKED ? "under a mask" : "without a mask";
+}
+
+// the argument checks of every count, before any device work
+static int sparse_range_count_checks(int64_t nq, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                     const float* d_thresholds, const int64_t* d_lims, const int64_t* total) {
     SR_REQUIRE(nq >= 0 && nq < SRR_MAX_NQ, "sr_sparse_range_count: bad nq=%lld (0 <= nq < 2^24: one workgroup per query and chunk in one launch)", (long long)nq);
     SR_REQUIRE(d_lims && total, "sr_sparse_range_count: null d_lims or total");
     SR_REQUIRE(nq == 0 || (d_q_indptr && d_q_cols && d_q_vals && d_thresholds), "sr_sparse_range_count: null queries or thresholds");
+    return SR_OK;
+}
+
+// d_mask null: the unrestricted search; with d_qgroup: d_mask holds a bitmap per group, d_qgroup the checked group of every query.  The
+// caller holds idx->mu.
+static int sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
+                              const float* d_thresholds, const uint32_t* d_mask, const int32_t* d_qgroup, int64_t* d_lims, int64_t* total,
+                              sr_stream stream) {
+    SR_TRY(sparse_range_count_checks(nq, d_q_indptr, d_q_cols, d_q_vals, d_thresholds, d_lims, total));
+    const int kind = d_qgroup ? SRR_KIND_GROUPED : d_mask ? SRR_KIND_MASKED : SRR_KIND_ALL;
     hipStream_t s = (hipStream_t)stream;
     idx->range_nq = -1;
-    idx->range_masked = d_mask != nullptr;
+    idx->range_kind = kind;
     if (nq == 0 || idx->n_docs == 0) {
         SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
         SR_CHECK_HIP(hipStreamSynchronize(s));
@@ -357,11 +379,12 @@ static int sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, c
     StreamOrder::Scope in_order(idx->order, s);
     idx->range_chunk_tiles = (int)chunk_tiles;
     SparseRangeArgs a;
-    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask, a);
+    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask, d_qgroup, a);
     for (int c0 = 0; c0 < n_chunks; c0 += SRR_MAX_GRID_Y) {
         const int nc = n_chunks - c0 < SRR_MAX_GRID_Y ? n_chunks - c0 : SRR_MAX_GRID_Y;
         a.chunk_begin = c0;
-        if (d_mask) hipLaunchKernelGGL(sparse_range_count_kernel<true>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
+        if (d_qgroup) hipLaunchKernelGGL((sparse_range_count_kernel<true, true>), dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
+        else if (d_mask) hipLaunchKernelGGL(sparse_range_count_kernel<true>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(sparse_range_count_kernel<false>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a);
         SR_CHECK_LAUNCH();
     }
@@ -378,7 +401,7 @@ extern "C" int sr_sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_in
                                      int64_t nq, const float* d_thresholds, int64_t* d_lims, int64_t* total, sr_stream stream) {
     SR_REQUIRE(idx, "sr_sparse_range_count: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    return sparse_range_count(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, nullptr, d_lims, total, stream);
+    return sparse_range_count(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, nullptr, nullptr, d_lims, total, stream);
 }
 
 extern "C" int sr_sparse_range_count_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
@@ -389,19 +412,20 @@ extern "C" int sr_sparse_range_count_masked(sr_sparse_index* idx, const int64_t*
     SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_range_count_masked: n_bits=%lld, the index holds %lld documents", (long long)n_bits,
                (long long)idx->n_docs);
     SR_REQUIRE(d_mask_words, "sr_sparse_range_count_masked: null mask");
-    return sparse_range_count(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask_words, d_lims, total, stream);
+    return sparse_range_count(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask_words, nullptr, d_lims, total, stream);
 }
 
 // d_mask: what the preceding count was given (null: none).  The caller holds idx->mu.
 static int sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
-                             const float* d_thresholds, const uint32_t* d_mask, const int64_t* d_lims, int64_t id_base, int64_t id_stride,
-                             float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+                             const float* d_thresholds, int kind, const uint32_t* d_mask, const int32_t* d_qgroup, const int64_t* d_lims, int64_t id_base,
+                             int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(nq >= 0 && nq < SRR_MAX_NQ && capacity >= 0, "sr_sparse_range_fill: bad nq=%lld (0 <= nq < 2^24) or capacity=%lld", (long long)nq, (long long)capacity);
     SR_REQUIRE(id_base >= 0 && id_stride >= 1, "sr_sparse_range_fill: need id_base >= 0 and id_stride >= 1, got %lld and %lld", (long long)id_base,
                (long long)id_stride);
     hipStream_t s = (hipStream_t)stream;
     SR_REQUIRE(idx->range_nq >= 0, "sr_sparse_range_fill: no sr_sparse_range_count precedes it on this handle");
-    SR_REQUIRE(idx->range_masked == (d_mask != nullptr), "sr_sparse_range_fill: the preceding count ran %s a mask", idx->range_masked ? "under" : "without");
+    SR_REQUIRE(idx->range_kind == kind, "sr_sparse_range_fill: the preceding count ran %s, this fill runs %s", srr_kind_text(idx->range_kind),
+               srr_kind_text(kind));
     SR_REQUIRE(idx->range_nq == nq, "sr_sparse_range_fill: nq=%lld, the preceding count had %lld", (long long)nq, (long long)idx->range_nq);
     SR_REQUIRE(capacity >= idx->range_total, "sr_sparse_range_fill: capacity=%lld is below the count's total of %lld", (long long)capacity,
                (long long)idx->range_total);
@@ -409,13 +433,14 @@ static int sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_indptr, co
     SR_REQUIRE(d_q_indptr && d_q_cols && d_q_vals && d_thresholds && d_lims && d_out_scores && d_out_ids, "sr_sparse_range_fill: null pointer");
     StreamOrder::Scope in_order(idx->order, s);
     SparseRangeArgs a;
-    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask, a);
+    sparse_range_args(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask, d_qgroup, a);
     a.lims = d_lims; a.id_base = id_base; a.id_stride = id_stride; a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.capacity = capacity;
     const int n_chunks = idx->range_chunks;
     for (int c0 = 0; c0 < n_chunks; c0 += SRR_MAX_GRID_Y) {
         const int nc = n_chunks - c0 < SRR_MAX_GRID_Y ? n_chunks - c0 : SRR_MAX_GRID_Y;
         a.chunk_begin = c0;
-        if (d_mask) hipLaunchKernelGGL(sparse_range_fill_kernel<true>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a, n_chunks);
+        if (d_qgroup) hipLaunchKernelGGL((sparse_range_fill_kernel<true, true>), dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a, n_chunks);
+        else if (d_mask) hipLaunchKernelGGL(sparse_range_fill_kernel<true>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a, n_chunks);
         else hipLaunchKernelGGL(sparse_range_fill_kernel<false>, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, a, n_chunks);
         SR_CHECK_LAUNCH();
     }
@@ -427,7 +452,7 @@ extern "C" int sr_sparse_range_fill(sr_sparse_index* idx, const int64_t* d_q_ind
                                     float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(idx, "sr_sparse_range_fill: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, nullptr, d_lims, id_base, id_stride, d_out_scores,
+    return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, SRR_KIND_ALL, nullptr, nullptr, d_lims, id_base, id_stride, d_out_scores,
                              d_out_ids, capacity, stream);
 }
 
@@ -440,6 +465,67 @@ extern "C" int sr_sparse_range_fill_masked(sr_sparse_index* idx, const int64_t* 
     SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_range_fill_masked: n_bits=%lld, the index holds %lld documents", (long long)n_bits,
                (long long)idx->n_docs);
     SR_REQUIRE(d_mask_words, "sr_sparse_range_fill_masked: null mask");
-    return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_mask_words, d_lims, id_base, id_stride, d_out_scores,
+    return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, SRR_KIND_MASKED, d_mask_words, nullptr, d_lims, id_base, id_stride, d_out_scores,
+                             d_out_ids, capacity, stream);
+}
+
+// ---- under a bitmap per query (filter groups) ------------------------------------------------------------------------------------
+// the checks the two grouped halves share, before any device work
+static int sparse_range_group_checks(const sr_sparse_index* idx, const char* who, int64_t nq, const uint32_t* d_group_words, int64_t n_groups,
+                                     int64_t n_bits, const int32_t* d_query_group) {
+    SR_REQUIRE(n_groups >= 1, "%s: n_groups=%lld, at least one group is needed", who, (long long)n_groups);
+    SR_REQUIRE(n_bits == idx->n_docs, "%s: n_bits=%lld, the index holds %lld documents", who, (long long)n_bits, (long long)idx->n_docs);
+    const int64_t n_words = (n_bits + 31) >> 5;
+    SR_REQUIRE(n_groups < (1ll << 32) && n_groups * n_words < (1ll << 32), "%s: %lld groups of %lld words exceed 2^32 words", who,
+               (long long)n_groups, (long long)n_words);
+    SR_REQUIRE(nq <= 0 || (d_query_group && (d_group_words || n_bits == 0)), "%s: null masks or query groups", who);
+    return SR_OK;
+}
+
+// One workgroup serves one (query, chunk), so the query's group only moves the base of the mask words (sparse_range_body<.., GROUPED>);
+// the count reads the group ids back once (4 nq bytes) and checks them before anything is launched, and keeps a copy on the handle that
+// its fill reads - the fill does not look at d_query_group again.
+extern "C" int sr_sparse_range_count_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                             int64_t nq, const float* d_thresholds, const uint32_t* d_group_words, int64_t n_groups,
+                                             int64_t n_bits, const int32_t* d_query_group, int64_t* d_lims, int64_t* total, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_range_count_grouped: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SR_TRY(sparse_range_group_checks(idx, "sr_sparse_range_count_grouped", nq, d_group_words, n_groups, n_bits, d_query_group));
+    SR_TRY(sparse_range_count_checks(nq, d_q_indptr, d_q_cols, d_q_vals, d_thresholds, d_lims, total));
+    hipStream_t s = (hipStream_t)stream;
+    idx->range_nq = -1;                               // whatever happens below, no earlier count can be filled from
+    *total = 0;
+    if (nq > 0) {
+        std::vector<int32_t> grp((size_t)nq);
+        SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        SR_CHECK_HIP(hipStreamSynchronize(s));
+        for (int64_t q = 0; q < nq; ++q)
+            if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
+                SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
+                SR_CHECK_HIP(hipStreamSynchronize(s));
+                sr_set_error("sr_sparse_range_count_grouped: query %lld is in group %d, outside [0, %lld) (nothing was scored)", (long long)q,
+                             grp[(size_t)q], (long long)n_groups);
+                return SR_ERR_INVALID;
+            }
+    }
+    SR_TRY(idx->range_qgroup.reserve(nq > 0 ? nq : 1, "sr_sparse_range_count_grouped"));      // never null: it names the kind below
+    if (nq > 0) {
+        SR_CHECK_HIP(hipMemcpyAsync(idx->range_qgroup.p, d_query_group, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
+    }
+    SR_TRY(sparse_range_count(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, d_group_words, idx->range_qgroup.p, d_lims, total, stream));
+    idx->range_groups = n_groups;
+    return SR_OK;
+}
+
+extern "C" int sr_sparse_range_fill_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
+                                            int64_t nq, const float* d_thresholds, const uint32_t* d_group_words, int64_t n_groups,
+                                            int64_t n_bits, const int32_t* d_query_group, const int64_t* d_lims, int64_t id_base,
+                                            int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
+    SR_REQUIRE(idx, "sr_sparse_range_fill_grouped: null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    SR_TRY(sparse_range_group_checks(idx, "sr_sparse_range_fill_grouped", nq, d_group_words, n_groups, n_bits, d_query_group));
+    SR_REQUIRE(idx->range_nq < 0 || idx->range_kind != SRR_KIND_GROUPED || idx->range_groups == n_groups,
+               "sr_sparse_range_fill_grouped: n_groups=%lld, the preceding count had %lld", (long long)n_groups, (long long)idx->range_groups);
+    return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, SRR_KIND_GROUPED, d_group_words, idx->range_qgroup.p, d_lims, id_base, id_stride, d_out_scores,
                              d_out_ids, capacity, stream);
 }

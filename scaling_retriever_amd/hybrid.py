@@ -21,8 +21,15 @@ under the mask (the sparse head under the bitmap carried over to its own positio
 dense range search, and a dense list that holds every allowed document (depth >= their number m) is complete.  The argument holds for
 the allowed set word for word: every allowed document outside both lists has dense <= D and sparse <= S.
 
-All arithmetic is in the HIP kernels; the host only moves rows between rounds.  Not offered: doc-sharded indexes, per-query masks,
-allow-lists given as ids (build the bitmap: HybridRetriever.allowed_mask), k > sr_max_topk()."""
+Under per-query masks (masks= + query_group=: a bitmap per filter group and a group id per query) every query runs the
+three routes over ITS group's allowed documents: both heads search under groups (search_grouped; the stacked bitmaps are carried over to
+sparse positions once per call), the allowed documents are counted per group once per call and a dense list is complete when its depth
+reaches the count of the query's own group, later rounds carry the pending queries' group ids, and the range route is the grouped dense
+range search.  The argument holds per query: every allowed document of that query outside both of its lists has dense <= D and sparse
+<= S.  For every group the rows, counts and stats are those of search_fused(mask=masks[g]) for its queries alone.
+
+All arithmetic is in the HIP kernels; the host only moves rows between rounds.  Not offered: doc-sharded indexes, allow-lists given as
+ids (build the bitmap: HybridRetriever.allowed_mask), k > sr_max_topk()."""
 import contextlib
 
 import numpy as np
@@ -111,7 +118,7 @@ def _rescore_and_rank(dense, sparse, q, csr, indptr, dpos, spos, tie, w, k, D, S
 
 
 def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_vals, topk, weights=(1.0, 1.0), depths=None,
-                 fallback_bytes=1 << 30, mask=None):
+                 fallback_bytes=1 << 30, mask=None, masks=None, query_group=None):
     """dense: DenseIndexHIP in precision "fp32" or "fp32_filtered" (ValueError otherwise: the k'-th dense score must be comparable with
     pair scores); sparse: SparseIndexHIP; d2s int64 [dense.id_end] / s2d int64 the two position maps on the device (-1: none); queries
     fp32 [nq, dim] and a CSR over the vocabulary, on the device.  depths (default 4k, 16k, ... <= sr_max_topk()): the search depths of
@@ -119,7 +126,10 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
     whose candidates alone exceed it: MemoryError naming it).  mask (None: every document): packed int32 / uint32 words over dense
     positions [0, dense.id_end) (scoring.pack_doc_mask), one bitmap for all queries - only documents whose bit is set are ranked; a set
     bit that names no document is a ValueError (DenseIndexHIP.search); with fewer than k allowed documents a row ends in padding and its
-    count says so.  Returns (scores fp32 [nq, k] padded with -FLT_MAX, dense positions int64
+    count says so.  masks + query_group (not together with mask): packed words [G, W] over dense positions (scoring.pack_doc_masks), one
+    bitmap per filter group, and one group id per query - query q is ranked over the documents of masks[query_group[q]] alone; a group
+    without an allowed document gives padding rows with count 0 at depth 0; a group id outside [0, G) is a ValueError naming the query.
+    Returns (scores fp32 [nq, k] padded with -FLT_MAX, dense positions int64
     [nq, k] padded with -1, counts int32 [nq]) as numpy arrays and stats = {"depth": int64 [nq] the index into depths at which the
     query was certified, -1 = range route; "union": int64 [nq] candidates ranked for it; "range_hits": int64 [nq]; "depths": the
     schedule} - the exact top-k of the fused score for every query, whatever route served it."""
@@ -131,9 +141,19 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
     if k > max_topk:
         raise ValueError(f"search_fused: topk = {k} is beyond sr_max_topk() = {max_topk}")
     depths = default_depths(k, max_topk) if depths is None else _check_depths(depths, k, max_topk)
-    from .doc_filter import mask_argument, mask_on_device
+    from .doc_filter import mask_argument, mask_on_device, one_filter, query_group_argument
     from .scoring import doc_list_from_mask, doc_mask_remap, hybrid_union
     dev = dense.device
+    one_filter("search_fused", masks, query_group, mask=mask)
+    if masks is not None:
+        masks, n_bits = mask_argument(masks, lambda: dense.id_end, "id_end", ndim=2)
+        if n_bits is None:
+            raise ValueError("search_fused takes its masks as packed int32 / uint32 words (scoring.pack_doc_masks), not as flags")
+        query_group = query_group_argument(query_group, dense_queries.shape[0])
+        n_groups = int(masks.shape[0])
+        n_words = (n_bits + 31) // 32
+        masks = mask_on_device(masks, n_bits, dev)[0].reshape(-1)[:n_groups * n_words].reshape(n_groups, n_words)      # on the device, uploaded once
+        groups = (query_group if torch.is_tensor(query_group) else torch.from_numpy(np.ascontiguousarray(query_group))).to(device=dev, dtype=torch.int64)
     if mask is not None:
         mask, n_bits = mask_argument(mask, lambda: dense.id_end, "id_end")
         if n_bits is None:
@@ -161,6 +181,14 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
         stats["depth"][:] = 0
         return result()
     n_allowed, sparse_mask = N, None
+    if masks is not None:
+        bad = torch.nonzero((groups < 0) | (groups >= n_groups))
+        if bad.numel():
+            raise ValueError(f"search_fused: query {int(bad[0])} is in group {int(groups[int(bad[0])])}, outside [0, {n_groups})")
+        # m_g: counted once per call; the same filters over sparse positions, built once per call
+        n_allowed = torch.tensor([doc_list_from_mask(masks[g], dense.id_end, capacity=0)[1] for g in range(n_groups)], dtype=torch.int64, device=dev)
+        if sparse.n_docs > 0:
+            sparse_mask = torch.stack([doc_mask_remap(masks[g], dense.id_end, s2d[:sparse.n_docs], sparse.n_docs) for g in range(n_groups)])
     if mask is not None:
         n_allowed = doc_list_from_mask(mask, dense.id_end, capacity=0)[1]      # m: counted once per call
         if n_allowed == 0:
@@ -173,6 +201,10 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
         scores[rows], ids[rows], counts[rows] = out[0][keep], out[1][keep], out[2][keep]
 
     pending = torch.arange(nq, device=dev)
+    if masks is not None:                       # a group without an allowed document: padding rows, count 0, depth 0 - nothing to search
+        empty = n_allowed[groups] == 0
+        stats["depth"][empty.cpu().numpy()] = 0
+        pending = pending[~empty]
     open_lists = None
     for depth_i, depth in enumerate(depths):
         n = pending.numel()
@@ -180,15 +212,24 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
             break
         qs, csr = q[pending].contiguous(), _csr_rows(row_ptr, cols, vals, pending)
         kd, ks = min(depth, N), min(depth, max(1, sparse.n_docs))
-        if mask is None:
-            with _pair_order(dense, n):
-                ds, di = dense.search(qs, kd)
+        if masks is not None:
+            pg = groups[pending]                                           # later rounds carry the pending queries' groups, no mask is re-uploaded
+            ds, di = dense.search_grouped(qs, kd, masks, pg)               # each group's rows are those of search(mask=masks[g])
+            if sparse_mask is not None:
+                ss, si, sc = sparse.search_grouped(csr[0], csr[1], csr[2], ks, sparse_mask, pg, threshold=0.0)
+            else:
+                ss, si, sc = sparse.search(csr[0], csr[1], csr[2], ks, threshold=0.0)
+            complete = kd >= n_allowed[pg]
         else:
-            ds, di = dense.search(qs, kd, mask=mask)                       # pair-score bits for every nq; padded (-FLT_MAX, -1) when m < kd
-        ss, si, sc = sparse.search(csr[0], csr[1], csr[2], ks, threshold=0.0, mask=sparse_mask)
+            if mask is None:
+                with _pair_order(dense, n):
+                    ds, di = dense.search(qs, kd)
+            else:
+                ds, di = dense.search(qs, kd, mask=mask)                   # pair-score bits for every nq; padded (-FLT_MAX, -1) when m < kd
+            ss, si, sc = sparse.search(csr[0], csr[1], csr[2], ks, threshold=0.0, mask=sparse_mask)
+            complete = torch.full((n,), kd >= n_allowed, dtype=torch.bool, device=dev)
         D = ds[:, kd - 1].contiguous()
         S = torch.where(sc == ks, ss[:, ks - 1], torch.zeros_like(D))      # a shorter list: every document outside it scores <= 0
-        complete = torch.full((n,), kd >= n_allowed, dtype=torch.bool, device=dev)
         indptr, dpos, spos, tie = hybrid_union(di, si, sc, s2d, d2s)
         out = _rescore_and_rank(dense, sparse, qs, csr, indptr, dpos, spos, tie, w, k, D, S, complete, n_s2d)
         certified = out[3] != 0
@@ -204,7 +245,9 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
         # the range route.  Uncertified means g(D) >= F_k, so d* <= D: the dense list of the last depth lies inside the hits.
         thr, si, sc = open_lists
         qs = q[pending].contiguous()
-        qs, thr, lims, total = dense.range_count(qs, thr, mask=mask)
+        pg = groups[pending] if masks is not None else None
+        how = (lambda a, b: dict(masks=masks, query_group=pg[a:b])) if masks is not None else (lambda a, b: dict(mask=mask))
+        qs, thr, lims, total = dense.range_count(qs, thr, **how(0, pending.numel()))
         lens = (lims[1:] - lims[:-1]).cpu().numpy()
         pend_h = pending.cpu().numpy()
         need = (lens + si.shape[1]) * CANDIDATE_BYTES
@@ -221,10 +264,10 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
         for g0, g1 in groups:
             if len(groups) == 1:
                 gq, glims = qs, lims
-                _, hit_ids = dense.range_fill(qs, thr, lims, total, mask=mask)
+                _, hit_ids = dense.range_fill(qs, thr, lims, total, **how(0, pending.numel()))
             else:
-                gq, gthr, glims, gtotal = dense.range_count(qs[g0:g1], thr[g0:g1], mask=mask)
-                _, hit_ids = dense.range_fill(gq, gthr, glims, gtotal, mask=mask)
+                gq, gthr, glims, gtotal = dense.range_count(qs[g0:g1], thr[g0:g1], **how(g0, g1))
+                _, hit_ids = dense.range_fill(gq, gthr, glims, gtotal, **how(g0, g1))
             rows = pending[g0:g1]
             csr = _csr_rows(row_ptr, cols, vals, rows)
             indptr, dpos, spos, tie = hybrid_union(hit_ids, si[g0:g1], sc[g0:g1], s2d, d2s, a_indptr=glims)

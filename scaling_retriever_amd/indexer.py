@@ -282,20 +282,28 @@ class DenseFlatIndexer(DenseIndexer):
         positions = np.ascontiguousarray(positions, dtype=np.int64)
         return _host_lists.take_rows(table.ctypes.data, len(table) - 1, positions.ctypes.data, positions.shape[0], positions.shape[1])
 
-    def range_search(self, query_reps, thresholds, sort=True, allowed_ids=None, allowed_mask=None):
+    def range_search(self, query_reps, thresholds, sort=True, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
         """Every document scoring above a threshold (faiss's IndexFlatIP.range_search; the dense counterpart of the threshold of
         numba_score_float, indexer.py:315-344): (list of db-id lists, list of fp32 score arrays), one pair per query, of the documents
         with score > thresholds (a float, or one value per query).  sort=True: best first, ties by index position, so a list is a
         prefix of what search_knn ranks; False: index order.  The ids go through id_table in one numpy take (the ragged counterpart
         of id_lists).  allowed_ids / allowed_mask (one of them at most) as for search_knn: only these documents are returned - the
         lists are the unrestricted ones with every other document removed (DenseIndexHIP.range_search, mask; faiss's range_search with
-        an IDSelector)."""
-        filt = self._resolve("range_search", allowed_ids, allowed_mask)
-        mask = None if filt is None else filt.data
-        if filt is not None and filt.kind == "subset":
-            mask = doc_mask_from_list(filt.data, self.index.id_end, device=self.index.device)
+        an IDSelector).  allowed_masks bool [G, index positions] with query_group int [nq], as for search_knn: a filter per query - the
+        lists of query q hold documents of allowed_masks[query_group[q]] only (DenseIndexHIP.range_search, masks / query_group); not
+        together with a filter for all queries."""
+        filt = self._resolve("range_search", allowed_ids, allowed_mask, allowed_masks, query_group)
         q = _dense_queries(query_reps, self.index.device)
-        lims, scores, positions = self.index.range_search(q, thresholds, sort=sort, mask=mask)
+        if filt is not None and filt.kind == "groups":
+            if filt.groups.numel() != q.shape[0]:
+                raise ValueError(f"range_search: query_group must hold one group id per query ({q.shape[0]}), got {filt.groups.numel()}")
+            how = dict(masks=filt.data, query_group=filt.groups)
+        else:
+            mask = None if filt is None else filt.data
+            if filt is not None and filt.kind == "subset":
+                mask = doc_mask_from_list(filt.data, self.index.id_end, device=self.index.device)
+            how = dict(mask=mask)
+        lims, scores, positions = self.index.range_search(q, thresholds, sort=sort, **how)
         lims, scores = lims.cpu().numpy(), scores.cpu().numpy()
         flat = self.id_table()[positions.cpu().numpy()]
         return ([flat[a:b].tolist() for a, b in zip(lims[:-1], lims[1:])],
@@ -837,7 +845,8 @@ class SparseRetrieval:
             self._doc_table = IdTable(_doc_id_table(self.doc_ids, self.sparse_index.nb_docs()))
         return self._doc_table
 
-    def range_search(self, sparse_query_vecs, thresholds=0., sort=True, allowed_ids=None, allowed_mask=None):
+    def range_search(self, sparse_query_vecs, thresholds=0., sort=True, allowed_ids=None, allowed_mask=None, allowed_masks=None,
+                     query_group=None, _filter=None):
         """Every document scoring above a threshold - the full list of numba_score_float (indexer.py:324-344) for a whole query set,
         the counterpart of DenseFlatIndexer.range_search: (list of collection-id lists, list of fp32 score arrays), one pair per query,
         of the documents with score > thresholds (a float, or one value per query).  sparse_query_vecs as _generate_query_vecs returns
@@ -847,13 +856,22 @@ class SparseRetrieval:
         KeyError for it).  It scores 0.0 and so passes a negative threshold: such documents are left out of the lists here, their
         placeholders of doc_id_table never come back.  SparseIndexHIP.range_search returns them, by position.
         allowed_ids / allowed_mask (one of them at most) as for retrieve: only these documents are returned - the unrestricted lists
-        with every other document removed (SparseIndexHIP.range_search, mask)."""
-        filt = self._resolve("range_search", allowed_ids, allowed_mask)
-        mask = None if filt is None else filt.data
-        if filt is not None and filt.kind == "subset":
-            mask = doc_mask_from_list(filt.data, self.hip_index.n_docs, device=self._dev)
+        with every other document removed (SparseIndexHIP.range_search, mask).  allowed_masks bool [G, document positions] with
+        query_group int [number of queries], as for retrieve: a filter per query - the lists of query q hold documents of
+        allowed_masks[query_group[q]] only (SparseIndexHIP.range_search, masks / query_group); not together with a filter for all queries
+        (_filter: such a filter already resolved and on the device, doc_filter.Filter)."""
+        filt = self._resolve("range_search", allowed_ids, allowed_mask, allowed_masks, query_group) or _filter
         q = _as_query_csr(sparse_query_vecs, self._dev)
-        lims, scores, positions = self.hip_index.range_search(q.row_ptr, q.cols, q.vals, thresholds, sort=sort, mask=mask)
+        if filt is not None and filt.kind == "groups":
+            if filt.groups.numel() != len(q):
+                raise ValueError(f"range_search: query_group must hold one group id per query ({len(q)}), got {filt.groups.numel()}")
+            how = dict(masks=filt.data, query_group=filt.groups)
+        else:
+            mask = None if filt is None else filt.data
+            if filt is not None and filt.kind == "subset":
+                mask = doc_mask_from_list(filt.data, self.hip_index.n_docs, device=self._dev)
+            how = dict(mask=mask)
+        lims, scores, positions = self.hip_index.range_search(q.row_ptr, q.cols, q.vals, thresholds, sort=sort, **how)
         lims, scores, positions = lims.cpu().numpy(), scores.cpu().numpy(), positions.cpu().numpy()
         table = self.doc_id_table()
         if len(self.doc_ids) < table.n:                      # some document has no id: drop its entries, list by list
@@ -1020,11 +1038,18 @@ class ShardedSparseRetrieval(SparseRetrieval):
                 ids.update(pickle.load(f))
         return ids
 
-    def range_search(self, sparse_query_vecs, thresholds=0., sort=True, allowed_ids=None, allowed_mask=None):
+    def range_search(self, sparse_query_vecs, thresholds=0., sort=True, allowed_ids=None, allowed_mask=None, allowed_masks=None,
+                     query_group=None):
+        if allowed_masks is not None or query_group is not None:
+            raise NotImplementedError("ShardedSparseRetrieval.range_search: filter groups (allowed_masks / query_group) are not supported on "
+                                      "a doc-sharded index, and neither is a range search; search one merged index with SparseRetrieval instead")
         raise NotImplementedError("ShardedSparseRetrieval.range_search: a range search is not offered on a doc-sharded index; "
                                   "search one merged index with SparseRetrieval instead")
 
     def search_fused(self, *args, **kwargs):
+        if kwargs.get("allowed_masks") is not None or kwargs.get("query_group") is not None:
+            raise NotImplementedError("ShardedSparseRetrieval.search_fused: filter groups (allowed_masks / query_group) are not supported on "
+                                      "a doc-sharded index, and neither is the exact fused search; use HybridRetriever over one merged index")
         raise NotImplementedError("ShardedSparseRetrieval.search_fused: the exact fused search is not offered on a doc-sharded index; "
                                   "use HybridRetriever over one merged index")
 
@@ -1278,8 +1303,19 @@ class HybridRetriever(SparseRetrieval):
         flags[self.dense_index.allowed_subset(allowed_ids).cpu().numpy()] = True
         return flags
 
+    def range_search(self, sparse_query_vecs, thresholds=0., sort=True, allowed_ids=None, allowed_mask=None, allowed_masks=None,
+                     query_group=None):
+        """SparseRetrieval.range_search on the inverted index.  allowed_ids / allowed_mask as there (allowed_mask over the document
+        positions of the inverted index).  allowed_masks / query_group as for retrieve: bool [G, DENSE index positions] (the numbering
+        of allowed_mask()), carried over to the inverted index's numbering once per call (allowed_group_filters) - a document without a
+        posting has no sparse position and is in no list."""
+        one_filter("range_search", allowed_masks, query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        if allowed_masks is None:
+            return super().range_search(sparse_query_vecs, thresholds, sort=sort, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        return super().range_search(sparse_query_vecs, thresholds, sort=sort, _filter=self.allowed_group_filters(allowed_masks, query_group)[1])
+
     def search_fused(self, sparse_query_vecs, dense_query_vecs, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, qids=None,
-                     allowed_ids=None, allowed_mask=None):
+                     allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
         """The EXACT top-k of the fused score of retrieve_fused over every document of the dense index (hybrid.search_fused: the
         union of the two heads' lists at depth depths[0] >= topk where a certificate proves it holds the true top-k, deeper lists
         for the queries it does not, a dense range search for what is left; the same result whatever route served a query).
@@ -1289,34 +1325,45 @@ class HybridRetriever(SparseRetrieval):
         topk >= 1 and two finite weights >= 0, else ValueError before any device work; the dense index must be in precision fp32 /
         fp32_filtered (ValueError).  allowed_mask (None: every document): a boolean array over dense index positions, the allowed_mask
         of search_knn - the exact top-k of the fused score over these documents alone (fewer than topk of them: shorter rows); build
-        it from database ids with allowed_mask(ids).  Not supported (NotImplementedError): allowed_ids, and the doc-sharded classes."""
+        it from database ids with allowed_mask(ids).  allowed_masks bool [G, dense index positions] with query_group int [nq] (not
+        together with allowed_mask): a filter per query - the exact top-k of the fused score over the documents of
+        allowed_masks[query_group[q]] alone, for every group what allowed_mask=allowed_masks[g] returns for its queries.  Not supported
+        (NotImplementedError): allowed_ids, and the doc-sharded classes."""
         from . import hybrid
         hybrid.check_arguments(topk, weights)
         if allowed_ids is not None:
             raise NotImplementedError("HybridRetriever.search_fused: an allow-list of ids (allowed_ids) is not taken by the exact fused "
                                       "search; pass the bitmap instead: allowed_mask=ret.allowed_mask(ids)")
-        mask = None if allowed_mask is None else self.dense_index.allowed_mask_words(allowed_mask)
+        one_filter("HybridRetriever.search_fused", allowed_masks, query_group, allowed_mask=allowed_mask)
+        how = {}
+        if allowed_mask is not None:
+            how = dict(mask=self.dense_index.allowed_mask_words(allowed_mask))
+        elif allowed_masks is not None:
+            words, groups = self.dense_index.allowed_group_words(allowed_masks, query_group)
+            how = dict(masks=words, query_group=groups)
         q = _as_query_csr(sparse_query_vecs, self._dev)
         d2s, s2d = self._position_maps()
         dq = _dense_queries(dense_query_vecs, self._dev)
         scores, positions, counts, stats = hybrid.search_fused(self.dense_index.index, self.hip_index, d2s, s2d, dq, q.row_ptr, q.cols, q.vals,
-                                                               topk, weights=weights, depths=depths, fallback_bytes=fallback_bytes, mask=mask)
+                                                               topk, weights=weights, depths=depths, fallback_bytes=fallback_bytes, **how)
         qids = list(range(dq.shape[0])) if qids is None else qids
         return RunResult(qids, scores, positions, self.dense_index.run_table(), counts), stats
 
     def retrieve_fused_exact(self, q_loader, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, allowed_ids=None,
-                             allowed_mask=None):
+                             allowed_mask=None, allowed_masks=None, query_group=None):
         """Encodes the queries once (both heads) and writes {out_dir}/fused_exact/run.json, next to the two heads' runs: the exact
-        fused top-k of search_fused (allowed_mask as there).  Returns (RunResult, stats).  The files of retrieve / retrieve_fused are
+        fused top-k of search_fused (allowed_mask, or allowed_masks with query_group in loader order, as there).  Returns (RunResult, stats).  The files of retrieve / retrieve_fused are
         not touched."""
         from . import hybrid
         hybrid.check_arguments(topk, weights)
         if allowed_ids is not None:
             raise NotImplementedError("HybridRetriever.retrieve_fused_exact: an allow-list of ids (allowed_ids) is not taken; pass the "
                                       "bitmap instead: allowed_mask=ret.allowed_mask(ids)")
+        one_filter("HybridRetriever.retrieve_fused_exact", allowed_masks, query_group, allowed_mask=allowed_mask)
         sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
         res, stats = self.search_fused(sparse_query_vecs, dense_query_vecs, topk, weights=weights, depths=depths,
-                                       fallback_bytes=fallback_bytes, qids=qids, allowed_mask=allowed_mask)
+                                       fallback_bytes=fallback_bytes, qids=qids, allowed_mask=allowed_mask, allowed_masks=allowed_masks,
+                                       query_group=query_group)
         out_dir = os.path.join(os.path.dirname(self.sparse_out_dir), "fused_exact")
         os.makedirs(out_dir, exist_ok=True)
         res.dump(os.path.join(out_dir, "run.json"))

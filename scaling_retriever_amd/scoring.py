@@ -36,8 +36,13 @@ def _thresholds(thresholds, nq, device):
 
 def _filter_args(filt):
     """(suffix of the entry's name, the arguments spliced in where the header puts them) of a resolved filter: None, ("_subset", list,
-    m) or ("_masked", words, n_bits).  The caller keeps `filt`, and with it the tensor, until the call has been made."""
-    return ("", ()) if filt is None else (filt[0], (_ptr(filt[1]), filt[2]))
+    m), ("_masked", words, n_bits) or ("_grouped", words, n_groups, n_bits, group ids).  The caller keeps `filt`, and with it the
+    tensors, until the call has been made."""
+    if filt is None:
+        return "", ()
+    if filt[0] == "_grouped":
+        return filt[0], (_ptr(filt[1]), filt[2], filt[3], _ptr(filt[4]))
+    return filt[0], (_ptr(filt[1]), filt[2])
 
 
 def _candidates(cand_indptr, cand_ids, nq, device):
@@ -322,6 +327,17 @@ class DenseIndexHIP:
         group's queries are exactly what search(those queries, k, mask=masks[g]) returns.  1 <= k <= sr_max_topk().  Wrong shapes, a wrong
         word count, a length mismatch or non-integer groups: ValueError before anything is uploaded; a group id outside [0, G) or a set
         bit that names no document: ValueError naming the query / the (group, bit), every row of the result is then padding."""
+        queries, filt = self._groups(masks, query_group, queries)
+        nq = queries.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        suffix, spliced = _filter_args(filt)
+        self._call("sr_dense_search" + suffix, _ptr(queries), nq, int(k), *spliced, _ptr(scores), _ptr(ids))
+        return scores, ids
+
+    def _groups(self, masks, query_group, queries):
+        """The checks of a masks= / query_group= pair in the order doc_filter.py lists, then its device step: (queries contiguous,
+        ("_grouped", words int32 [G, W] on the device, G, n_bits, group ids int32 [nq] on the device))."""
         masks = self._mask(masks, ndim=2)
         nq = self._check_queries(queries)
         query_group = query_group_argument(query_group, nq)
@@ -329,51 +345,62 @@ class DenseIndexHIP:
         words, n_bits = mask_on_device(*masks, self.device)
         # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
         groups = _valid(_to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32))
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        self._call("sr_dense_search_grouped", _ptr(queries), nq, int(k), _ptr(words), int(masks[0].shape[0]), n_bits, _ptr(groups),
-                   _ptr(scores), _ptr(ids))
-        return scores, ids
+        return queries, ("_grouped", words, int(masks[0].shape[0]), n_bits, groups)
 
-    def range_search(self, queries, thresholds, sort=False, mask=None):
+    def _range_filter(self, who, queries, mask, masks, query_group):
+        """(queries contiguous, the resolved filter of a range call: None, ("_masked", words, n_bits) or the tuple of _groups)."""
+        one_filter(who, masks, query_group, mask=mask)
+        if masks is not None:
+            return self._groups(masks, query_group, queries)
+        if mask is not None:
+            mask = self._mask(mask)
+        queries = self._queries(queries)
+        return queries, (None if mask is None else ("_masked",) + mask_on_device(*mask, self.device))
+
+    def range_search(self, queries, thresholds, sort=False, mask=None, masks=None, query_group=None):
         """Every document scoring above a threshold (faiss's IndexFlatIP.range_search; include/sr_hip.h sr_dense_range_count / _fill):
         queries fp32 cuda [nq, dim]; thresholds a float for all queries, or a tensor / array [nq].  Returns (lims int64 [nq + 1],
         scores fp32 [total], ids int64 [total]) as cuda tensors: the documents of query q with score > thresholds[q] are entries
         lims[q]:lims[q + 1], in (segment, row) order - ascending id for segments added in id order.  Scores are the exact chain of
         `score_pairs` for every nq.  sort=True: each list by score descending, ties by ascending id (range_sort).  mask (None: every
         document): a bitmap over [0, id_end) in the forms `search(mask=)` takes - only documents whose bit is set are returned
-        (sr_dense_range_count_masked / _fill_masked; a set bit that names no document is ignored); one mask for all queries."""
-        if mask is not None:
-            words, n_bits = mask_on_device(*self._mask(mask), self.device)     # packed once, shared by the two halves
-            if n_bits != self.id_end:
-                raise ValueError(f"a mask of this index holds {self.id_end} flags (id_end), got {n_bits}")
-            mask = words[:(n_bits + 31) // 32]        # the packed words themselves (an empty bitmap: no words)
-        queries, thr, lims, n = self.range_count(queries, thresholds, mask=mask)
-        scores, ids = self.range_fill(queries, thr, lims, n, mask=mask)
+        (sr_dense_range_count_masked / _fill_masked; a set bit that names no document is ignored); one mask for all queries.
+        masks + query_group (not together with mask): a bitmap per group and a group id per query in the forms `search_grouped` takes -
+        query q gets the documents of masks[query_group[q]] (sr_dense_range_count_grouped / _fill_grouped): for every group exactly the
+        lists of range_search(those queries, mask=masks[g]).  A group id outside [0, G): ValueError naming the query."""
+        queries, filt = self._range_filter("range_search", queries, mask, masks, query_group)      # resolved once, shared by the two halves
+        if filt is not None and filt[0] == "_masked" and filt[2] != self.id_end:
+            raise ValueError(f"a mask of this index holds {self.id_end} flags (id_end), got {filt[2]}")
+        queries, thr, lims, n = self._range_count(queries, thresholds, filt)
+        scores, ids = self._range_fill(queries, thr, lims, n, filt)
         if sort:
             scores, ids = range_sort(lims, scores, ids)
         return lims, scores, ids
 
-    def range_count(self, queries, thresholds, mask=None):
-        """The first half of range_search (sr_dense_range_count; under a mask sr_dense_range_count_masked): returns (queries, thresholds
-        [nq], lims int64 [nq + 1], total) - the contiguous tensors range_fill takes, and the sizes of the lists before anything of their
-        size is allocated."""
-        if mask is not None:
-            mask = self._mask(mask)
-        queries = self._queries(queries)
+    def range_count(self, queries, thresholds, mask=None, masks=None, query_group=None):
+        """The first half of range_search (sr_dense_range_count; under a mask sr_dense_range_count_masked, under masks + query_group
+        sr_dense_range_count_grouped): returns (queries, thresholds [nq], lims int64 [nq + 1], total) - the contiguous tensors range_fill
+        takes, and the sizes of the lists before anything of their size is allocated."""
+        queries, filt = self._range_filter("range_count", queries, mask, masks, query_group)
+        return self._range_count(queries, thresholds, filt)
+
+    def _range_count(self, queries, thresholds, filt):
         nq = queries.shape[0]
         thr = _thresholds(thresholds, nq, self.device)
         lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
-        filt = None if mask is None else ("_masked",) + mask_on_device(*mask, self.device)
         suffix, spliced = _filter_args(filt)
         self._call("sr_dense_range_count" + suffix, _ptr(queries), nq, _ptr(thr), *spliced, _ptr(lims), ctypes.byref(total))
         return queries, thr, lims, total.value
 
-    def range_fill(self, queries, thr, lims, n, mask=None):
-        """The second half (sr_dense_range_fill; under a mask sr_dense_range_fill_masked) for what the preceding range_count on this index
-        returned, under the mask that count was given: (scores fp32 [n], ids int64 [n])."""
-        filt = None if mask is None else ("_masked",) + mask_on_device(*self._mask(mask), self.device)
+    def range_fill(self, queries, thr, lims, n, mask=None, masks=None, query_group=None):
+        """The second half (sr_dense_range_fill; under a mask sr_dense_range_fill_masked, under masks + query_group
+        sr_dense_range_fill_grouped) for what the preceding range_count on this index returned, under the filter that count was given:
+        (scores fp32 [n], ids int64 [n])."""
+        queries, filt = self._range_filter("range_fill", queries, mask, masks, query_group)
+        return self._range_fill(queries, thr, lims, n, filt)
+
+    def _range_fill(self, queries, thr, lims, n, filt):
         suffix, spliced = _filter_args(filt)
         scores = torch.empty((max(1, n),), dtype=torch.float32, device=self.device)
         ids = torch.empty((max(1, n),), dtype=torch.int64, device=self.device)
@@ -569,7 +596,7 @@ class SparseIndexHIP:
                    _ptr(groups), int(id_base), int(id_stride), _ptr(scores), _ptr(ids), _ptr(counts))
         return scores, ids, counts
 
-    def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False, mask=None):
+    def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False, mask=None, masks=None, query_group=None):
         """Every document scoring above a threshold - the full list of numba_score_float (scaling_retriever/indexer.py:324-344;
         include/sr_hip.h sr_sparse_range_count / _fill): queries as CSR as for `search`; thresholds a float for all queries, or a
         tensor / array [nq].  Returns (lims int64 [nq + 1], scores fp32 [total], ids int64 [total]) as cuda tensors: the documents of
@@ -577,9 +604,16 @@ class SparseIndexHIP:
         id_stride.  A document without a common term scores 0.0 and is returned exactly under a negative threshold.  Scores are the
         chain of `score_pairs`.  sort=True: each list by score descending, ties by ascending id (range_sort).  mask (None: every
         document): a bitmap over [0, n_docs) in the forms `search(mask=)` takes - only documents whose bit is set are returned
-        (sr_sparse_range_count_masked / _fill_masked), a document without a common term included when the threshold is negative."""
+        (sr_sparse_range_count_masked / _fill_masked), a document without a common term included when the threshold is negative.
+        masks + query_group (not together with mask): a bitmap per group and a group id per query in the forms `search_grouped` takes -
+        query q gets the documents of masks[query_group[q]] (sr_sparse_range_count_grouped / _fill_grouped): for every group exactly the
+        lists of range_search(those queries, mask=masks[g]).  A group id outside [0, G): ValueError naming the query."""
+        one_filter("range_search", masks, query_group, mask=mask)
         if mask is not None:
             mask = self._mask(mask)
+        if masks is not None:
+            masks = mask_argument(masks, lambda: self.n_docs, "n_docs", ndim=2)
+            query_group = query_group_argument(query_group, len(q_indptr) - 1)
         q, nq = self._query_csr(q_indptr, q_cols, q_vals)
         thr = _valid(_thresholds(thresholds, nq, self.device))
         if sort and int(id_base) + (self.n_docs - 1) * int(id_stride) >= 1 << 32:
@@ -587,6 +621,11 @@ class SparseIndexHIP:
         lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
         filt = None if mask is None else ("_masked",) + mask_on_device(*mask, self.device)
+        if masks is not None:
+            words, n_bits = mask_on_device(*masks, self.device)
+            # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
+            groups = _valid(_to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32))
+            filt = ("_grouped", words, int(masks[0].shape[0]), n_bits, groups)
         suffix, spliced = _filter_args(filt)
         head = (*map(_ptr, q), nq, _ptr(thr), *spliced, _ptr(lims))
         self._call("sr_sparse_range_count" + suffix, *head, ctypes.byref(total))
