@@ -49,6 +49,9 @@ def parse_args(argv=None):
     ap.add_argument("--tokenize_workers", type=int, default=4)
     ap.add_argument("--allowed_ids_file", type=str, default=None,
                     help="retrieval task: rank only the documents whose ids this file lists, one id per line (any order, repeats allowed)")
+    ap.add_argument("--collapse_file", type=str, default=None,
+                    help="retrieval task: a TSV of passage_id<TAB>group_id - rank the top_k best GROUPS, each scored by its best passage "
+                         "(MaxP); run.json is then keyed by group id")
     ap.add_argument("--index_dtype", choices=["fp32", "fp16"], default="fp32",
                     help="retrieval: how the flat index keeps its rows. fp16 rounds the (fp32) shard files once, at ingest, and "
                          "holds half the bytes; the shard files themselves are not changed")
@@ -243,6 +246,9 @@ def retrieval(args):
     if args.allowed_ids_file and args.world_size > 1:           # before the model and the index shards are loaded
         raise NotImplementedError("--allowed_ids_file is not supported by the doc-sharded retrieval (world_size > 1): "
                                   "run the retrieval task on one process")
+    if args.collapse_file and args.world_size > 1:
+        raise NotImplementedError("--collapse_file is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaDenseCollectionCollator
     from scaling_retriever_amd.dataset.dataset import MSMARCOQueryDataset
     from scaling_retriever_amd.distributed import gather_topk, sharded_dense_search
@@ -278,6 +284,15 @@ def retrieval(args):
         index.add_npy_file(vec_files[fi], id_base=int(offsets[fi]))        # mmap -> pinned ring -> async H2D
     subset = allowed_subset_positions(args.allowed_ids_file, id_files, world) if args.allowed_ids_file else None
     q_reps, qids = generate_query_vecs(model, q_loader, device)
+    if args.collapse_file:
+        # the top_k best groups, each scored by its best passage: run.json keyed by group id (collapse.py)
+        from scaling_retriever_amd.collapse import key_table, read_collapse_file
+        from scaling_retriever_amd.utils.run_file import to_host, write_run_json
+        group_of = read_collapse_file(args.collapse_file)
+        keys, table = key_table(lambda d: group_of[str(d)], np.concatenate([np.load(f) for f in id_files]).tolist())
+        scores, _, gkeys, counts, _ = index.search_collapsed(q_reps.contiguous(), args.top_k, keys, subset=subset)
+        write_run_json(os.path.join(args.out_dir, "run.json"), qids, to_host(scores), to_host(gkeys.to(torch.int64)), table, to_host(counts))
+        return
     if subset is not None:
         scores, idx = index.search(q_reps.contiguous(), args.top_k, subset=subset)      # positions = the files' rows in plan order
     else:

@@ -43,6 +43,9 @@ def parse_args(argv=None):
     # term budgets (no counterpart in the reference's SparseArguments): keep only the largest terms of a row, 0 = all of them
     ap.add_argument("--allowed_ids_file", type=str, default=None,
                     help="retrieval task: rank only the documents whose ids this file lists, one id per line (any order, repeats allowed)")
+    ap.add_argument("--collapse_file", type=str, default=None,
+                    help="retrieval task: a TSV of passage_id<TAB>group_id - rank the top_k best GROUPS, each scored by its best passage "
+                         "(MaxP); run.json is then keyed by group id")
     ap.add_argument("--doc_max_terms", type=int, default=0, help="indexing task: terms indexed per document (index size)")
     ap.add_argument("--query_max_terms", type=int, default=0, help="retrieval task: terms searched per query (latency)")
     args = ap.parse_args(argv)
@@ -127,6 +130,9 @@ def sparse_retrieval(args):
     if args.allowed_ids_file and args.world_size > 1:           # before the model and the index shards are loaded
         raise NotImplementedError("--allowed_ids_file is not supported by the doc-sharded retrieval (world_size > 1): "
                                   "run the retrieval task on one process")
+    if args.collapse_file and args.world_size > 1:
+        raise NotImplementedError("--collapse_file is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaSparseCollectionCollator
     from scaling_retriever_amd.indexer import SparseRetrieval
     from scaling_retriever_amd.modeling.llm_encoder import retriever_class
@@ -157,7 +163,12 @@ def sparse_retrieval(args):
     q_loader = DataLoader(queries, batch_size=args.eval_batch_size, shuffle=False, num_workers=0, collate_fn=collate)
     retriever = SparseRetrieval(config=config, model=model, compute_stats=True, dim_voc=model.vocab_size, device=args.local_rank,
                                 query_max_terms=args.query_max_terms)
-    return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids)
+    collapse = None
+    if args.collapse_file:
+        from scaling_retriever_amd.collapse import read_collapse_file
+        group_of = read_collapse_file(args.collapse_file)
+        collapse = lambda d: group_of[str(d)]      # noqa: E731  (collection ids may be ints, the file's are text)
+    return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids, collapse=collapse)
 
 
 def evaluate_msmarco(args):

@@ -963,6 +963,32 @@ int sr_topk_replay(const float* d_scores, const int64_t* d_ids, int64_t nq, int6
                    float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, float* d_trace_tau, float* d_trace_tau2,
                    int32_t* d_trace_cand, int32_t* d_trace_run, uint64_t* d_trace_keys, sr_stream stream);
 
+/* ------------------------------------------------------------------------------------------------------- collapsed search ---
+ * sr_topk_collapse: the device step of the collapsed search (top-k distinct groups, each scored by its best passage: "MaxP", field
+ * collapsing; scaling_retriever_amd/collapse.py).  No reference counterpart.  Turns every ranked row into its
+ * first-occurrence-per-group row and says whether that row is provably complete.
+ *   Inputs: d_scores fp32 / d_ids int64 [nq, row_len], rows as the searches return them (score descending, ties by ascending id).  The
+ *   valid prefix of row q is d_counts[q] entries (int32, clamped to [0, row_len]: sr_sparse_search's counts), or with d_counts == NULL
+ *   everything before the first negative id (the dense searches' padding).  row_len is any value in [0, 2^31): a row is streamed in
+ *   chunks of 1024 ranks, never staged whole.  d_keys int32 [n_keys] maps an id to its group key >= 0.
+ *   Outputs: d_out_scores fp32 / d_out_ids int64 / d_out_keys int32 [nq, k]: the first k entries of the valid prefix whose key did not
+ *   occur earlier in the row, in row order, the rest padding (-FLT_MAX, -1, -1); d_out_counts int32 [nq] = min(k, distinct keys of the
+ *   prefix); d_out_complete int32 [nq] = 1 iff out_counts[q] == k, or the valid prefix is shorter than row_len (the search had nothing
+ *   more to return), or exhaustive != 0 (the caller states that the rows are whole rankings), else 0.  When complete, the row is the
+ *   top-k groups of the full ranking: the order on (score, id) is total, so every passage outside the prefix ranks behind everything
+ *   inside it and cannot change the first k first occurrences.
+ *   1 <= k <= sr_max_topk() (the keys met so far sit in an LDS hash table of 1.5 (k + 1024) slots); a larger k: SR_ERR_UNSUPPORTED.
+ *   Null pointers (d_counts may be NULL), nq < 0, row_len outside [0, 2^31), n_keys < 0, k < 1: SR_ERR_INVALID before anything touches
+ *   a device.  nq == 0 and row_len == 0 are legal (row_len == 0: every row is padding with count 0, complete only when exhaustive).
+ *   An id outside [0, n_keys) inside a valid prefix, or a negative key: SR_ERR_INVALID, found on the device, sr_last_error() names the
+ *   first (query, position); the outputs are then not to be used and the library stays usable.  A workgroup stops reading its row
+ *   behind the chunk of 1024 ranks in which it found its k-th group: entries of later chunks are NOT checked (those of that chunk are).
+ *   One workgroup per query, no global atomics, the same bytes on every run; the call waits for the stream once, at its end, to read
+ *   the status (and frees its nq * 4 scratch bytes).                                                                             */
+int sr_topk_collapse(const float* d_scores, const int64_t* d_ids, const int32_t* d_counts, int64_t nq, int64_t row_len, int exhaustive,
+                     const int32_t* d_keys, int64_t n_keys, int k, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_keys,
+                     int32_t* d_out_counts, int32_t* d_out_complete, sr_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,28 +11,6 @@
 #include <float.h>
 #include <math.h>
 
-// exclusive prefix of v over the 256 threads of the workgroup (lw: 4 LDS words); total = the sum.  Two barriers.
-__device__ inline int hf_block_scan(int v, int* lw, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) lw[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wave) base += lw[w];
-        total += lw[w];
-    }
-    __syncthreads();
-    return base + incl - v;
-}
-
 // bitonic sort, ascending, of a[0, P) in LDS (P a power of two); the caller has a barrier behind its stores
 __device__ inline void hf_sort_asc(uint32_t* a, int P) {
     for (int size = 2; size <= P; size <<= 1)

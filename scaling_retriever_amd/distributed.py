@@ -253,6 +253,10 @@ class ShardedSparseRetriever:
         ms, mi = topk_merge(gs, gi, pad_score=0.0)
         return ms, mi, (mi >= 0).sum(1).to(torch.int32)
 
+    def search_collapsed(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetriever.search_collapsed: the collapsed search (collapse.py) is not offered on a "
+                                  "doc-sharded index; search one merged index with SparseIndexHIP.search_collapsed")
+
     def search_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedSparseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "
                                   "doc-sharded index")
@@ -286,6 +290,10 @@ class ShardedDenseRetriever:
         if gs.shape[0] == 1:
             return gs[0], gi[0]
         return topk_merge(gs, gi)
+
+    def search_collapsed(self, *args, **kwargs):
+        raise NotImplementedError("ShardedDenseRetriever.search_collapsed: the collapsed search (collapse.py) is not offered on a doc-sharded "
+                                  "index; search one index that holds every document with DenseIndexHIP.search_collapsed")
 
     def search_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedDenseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "

@@ -50,6 +50,13 @@ def _search_filter(filt):
     return {} if filt is None else {filt.kind: filt.data}
 
 
+def _collapse_filter(filt):
+    """The filter keywords of the index classes' `search_collapsed` for a resolved doc_filter.Filter (None: none)."""
+    if filt is not None and filt.kind == "groups":
+        return dict(masks=filt.data, query_group=filt.groups)
+    return _search_filter(filt)
+
+
 def batch_groups(loader, max_rows=16384):
     """Consecutive collator batches of `loader`, grouped until `max_rows` rows: one LlamaBi*.encode_batches call per group.
     The reference's query loaders yield eval_batch_size (128) rows at a time (eval_dense.py:219-220, eval_sparse.py:125-127);
@@ -396,6 +403,28 @@ class DenseFlatIndexer(DenseIndexer):
         else:
             scores, indexes = self.index.search(q, top_docs, **_search_filter(filt))
         return to_host(scores), to_host(indexes)
+
+    def collapse_keys(self, group_of):
+        """(keys np.int32 [index positions], table of group labels) of a `group_of` - a dict on the database id, a callable on it, or a
+        sequence aligned with index order (collapse.key_table: built once, on the host)."""
+        from .collapse import key_table
+        return key_table(group_of, self.index_id_to_db_id)
+
+    def search_collapsed(self, query_reps, top_docs: int, group_of, depths=None, fallback_bytes=1 << 30, allowed_ids=None, allowed_mask=None,
+                         allowed_masks=None, query_group=None, return_stats=False):
+        """The top_docs best GROUPS of every query, each represented and scored by its best passage (MaxP; DenseIndexHIP.search_collapsed,
+        collapse.py): group_of gives each passage's group label - a dict on the database id, a callable on it, or a sequence aligned with
+        index order.  Returns one (group_labels, scores fp32, passage_db_ids) triple per query, best group first (fewer than top_docs
+        groups: shorter lists); return_stats=True: also the route statistics of the driver.  Filters as for search_knn."""
+        filt = self._resolve("search_collapsed", allowed_ids, allowed_mask, allowed_masks, query_group)
+        keys, table = self.collapse_keys(group_of)
+        q = _dense_queries(query_reps, self.index.device)
+        scores, positions, gkeys, counts, stats = self.index.search_collapsed(q, top_docs, keys, depths=depths, fallback_bytes=fallback_bytes,
+                                                                              **_collapse_filter(filt))
+        scores, positions, gkeys, counts = to_host(scores), to_host(positions), to_host(gkeys), to_host(counts)
+        ids = self.id_lists(positions)
+        out = [([table[g] for g in gkeys[i, :c].tolist()], scores[i, :c].copy(), ids[i][:c]) for i, c in enumerate(counts.tolist())]
+        return (out, stats) if return_stats else out
 
     def inverse_id_map(self):
         """str(db id) -> index position, cached with the id table (rebuilt when the list grew)."""
@@ -943,6 +972,29 @@ class SparseRetrieval:
         stats["L0_q"] = q.mean_l0()
         return res, stats
 
+    def collapse_keys(self, group_of):
+        """(keys np.int32 [document positions], table of group labels) of a `group_of` - a dict on the collection id, a callable on it,
+        or a sequence aligned with document positions (collapse.key_table); a document without a posting has no collection id and gets a
+        group of its own."""
+        from .collapse import key_table
+        return key_table(group_of, [self.doc_ids.get(p) for p in range(self.hip_index.n_docs)])
+
+    def _retrieve_collapsed(self, sparse_query_vecs, qids, group_of, threshold, topk, filt, depths=None, fallback_bytes=1 << 30):
+        """One collapsed search of the whole query set (SparseIndexHIP.search_collapsed): a RunResult keyed by group label - its
+        "positions" are the group keys, its id table the labels - and the stats of q_stats.json with the route statistics."""
+        from .collapse import route_stats
+        q = _as_query_csr(sparse_query_vecs, self._dev)
+        if filt is not None and filt.kind == "groups" and filt.groups.numel() != len(q):
+            raise ValueError(f"query_group must hold one group id per query ({len(q)}), got {filt.groups.numel()}")
+        keys, table = self.collapse_keys(group_of)
+        scores, _, gkeys, counts, route = self.hip_index.search_collapsed(q.row_ptr, q.cols, q.vals, topk, keys, threshold=threshold, depths=depths,
+                                                                          fallback_bytes=fallback_bytes, **_collapse_filter(filt))
+        res = RunResult(qids, to_host(scores), to_host(gkeys.to(torch.int64)), IdTable(table), to_host(counts))
+        stats = defaultdict(float)
+        stats["L0_q"] = q.mean_l0()
+        stats["collapse"] = route_stats(route)
+        return res, stats
+
     def _write_outputs(self, res, stats):
         os.makedirs(self.out_dir, exist_ok=True)
         if self.compute_stats:
@@ -950,8 +1002,12 @@ class SparseRetrieval:
                 json.dump(stats, handler)
         res.dump(os.path.join(self.out_dir, "run.json"))        # sr_write_run_json: the bytes json.dump(res) writes
 
-    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
-        """allowed_ids (None: every document): collection ids, any order, duplicates allowed - only these documents are ranked; an unknown
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
+        """collapse (None: rank passages): a `group_of` - dict on the collection id, callable on it, or a sequence aligned with document
+        positions - makes this the collapsed search: the topk best GROUPS per query, each scored by its best passage
+        (SparseIndexHIP.search_collapsed); run.json is then keyed by group label instead of passage id, and q_stats.json gains the route
+        statistics ("collapse").  The query set is searched in one call.
+        allowed_ids (None: every document): collection ids, any order, duplicates allowed - only these documents are ranked; an unknown
         id raises ValueError before anything is encoded.  allowed_mask: the same filter as a boolean array over the document positions
         of the inverted index (SparseIndexHIP.search, mask); one of the two at most.  allowed_masks bool [G, document positions] with
         query_group int [number of queries, in loader order]: a filter per query (SparseIndexHIP.search_grouped), not together with a
@@ -967,6 +1023,11 @@ class SparseRetrieval:
         qids = [x for g in group_qids for x in g]
         if filt is not None and filt.kind == "groups" and filt.groups.numel() != len(qids):
             raise ValueError(f"retrieve: query_group must hold one group id per query ({len(qids)}), got {filt.groups.numel()}")
+        if collapse is not None:
+            sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
+            res, stats = self._retrieve_collapsed(sparse_query_vecs, qids, collapse, threshold, topk, filt)
+            self._write_outputs(res, stats)
+            return res
         table = self.doc_id_table()
         if len(groups) < 2 or not (id_table(qids).distinct and id_table(table).distinct):
             sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
@@ -1053,9 +1114,12 @@ class ShardedSparseRetrieval(SparseRetrieval):
         raise NotImplementedError("ShardedSparseRetrieval.search_fused: the exact fused search is not offered on a doc-sharded index; "
                                   "use HybridRetriever over one merged index")
 
-    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when
         `q_loader.replicated` is set."""
+        if collapse is not None:
+            raise NotImplementedError("ShardedSparseRetrieval.retrieve: the collapsed search (collapse=) is not supported on a doc-sharded "
+                                      "index; search one merged index with SparseRetrieval instead")
         if allowed_masks is not None or query_group is not None:
             raise NotImplementedError("ShardedSparseRetrieval.retrieve: filter groups (allowed_masks / query_group) are not supported on a "
                                       "doc-sharded index; search one merged index with SparseRetrieval instead")
@@ -1216,11 +1280,41 @@ class HybridRetriever(SparseRetrieval):
         dense_res.dump(os.path.join(self.dense_out_dir, "run.json"))
         return sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res
 
-    def retrieve(self, q_loader, topk, id_dict=False, threshold=0., allowed_ids=None, allowed_masks=None, query_group=None):
+    def retrieve(self, q_loader, topk, id_dict=False, threshold=0., allowed_ids=None, allowed_masks=None, query_group=None, collapse=None):
         """allowed_ids (None: every document): database ids - both heads rank only these documents (allowed_subsets).  allowed_masks bool
         [G, dense index positions] (the numbering of allowed_mask()) with query_group int [number of queries]: a filter per query for
-        both heads (allowed_group_filters); not together with allowed_ids."""
+        both heads (allowed_group_filters); not together with allowed_ids.  collapse (None: rank passages): a `group_of` - dict on the
+        database id, callable on it, or a sequence aligned with the DENSE index's order - makes both searches collapsed searches: both
+        run.json files are keyed by group label (the topk best groups, each scored by its best passage under that head) and
+        sparse/q_stats.json gains the route statistics of both heads ("collapse", "collapse_dense")."""
+        if collapse is not None:
+            return self._retrieve_both_collapsed(q_loader, topk, threshold, collapse, allowed_ids, allowed_masks, query_group)
         return self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids, allowed_masks=allowed_masks, query_group=query_group)[3:]
+
+    def _retrieve_both_collapsed(self, q_loader, topk, threshold, group_of, allowed_ids=None, allowed_masks=None, query_group=None):
+        from .collapse import route_stats
+        one_filter("HybridRetriever.retrieve", allowed_masks, query_group, allowed_ids=allowed_ids)
+        d_filt, s_filt = (None, None) if allowed_ids is None else (Filter("subset", t) for t in self.allowed_subsets(allowed_ids))
+        if allowed_masks is not None:
+            d_filt, s_filt = self.allowed_group_filters(allowed_masks, query_group)
+        if not isinstance(group_of, dict) and not callable(group_of):       # a sequence: aligned with the dense index, the sparse head by id
+            db_ids = self.dense_index.index_id_to_db_id
+            labels = list(group_of)
+            if len(labels) != len(db_ids):
+                raise ValueError(f"collapse: a sequence of group labels is aligned with the dense index ({len(db_ids)} documents), got {len(labels)}")
+            group_of = dict(zip(db_ids, labels))
+        sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
+        sparse_res, sparse_stats = self._retrieve_collapsed(sparse_query_vecs, qids, group_of, threshold, topk, s_filt)
+        keys, table = self.dense_index.collapse_keys(group_of)
+        q = _dense_queries(dense_query_vecs, self._dev)
+        scores, _, gkeys, counts, route = self.dense_index.index.search_collapsed(q, topk, keys, **_collapse_filter(d_filt))
+        dense_res = RunResult(qids, to_host(scores), to_host(gkeys.to(torch.int64)), IdTable(table), to_host(counts))
+        sparse_stats["collapse_dense"] = route_stats(route)
+        with open(os.path.join(self.sparse_out_dir, "q_stats.json"), "w") as handler:
+            json.dump(sparse_stats, handler)
+        sparse_res.dump(os.path.join(self.sparse_out_dir, "run.json"))
+        dense_res.dump(os.path.join(self.dense_out_dir, "run.json"))
+        return sparse_res, dense_res
 
     def _position_maps(self):
         """The two indexes number documents independently: (dense position -> sparse position, -1 where the inverted index has no
@@ -1235,7 +1329,7 @@ class HybridRetriever(SparseRetrieval):
             self._s2d = torch.from_numpy(s2d).to(self._dev)
         return self._d2s, self._s2d
 
-    def retrieve_fused(self, q_loader, topk, weights=(1.0, 1.0), threshold=0., allowed_ids=None, allowed_masks=None, query_group=None):
+    def retrieve_fused(self, q_loader, topk, weights=(1.0, 1.0), threshold=0., allowed_ids=None, allowed_masks=None, query_group=None, collapse=None):
         """`retrieve` (the same two runs, the same bytes) plus {out_dir}/fused/run.json: per query the UNION of the two top-k lists,
         taken over database ids, is scored by BOTH heads with the pair kernels (a document only one search found gets its other
         score exactly, not a zero) and ranked by fused = float32(w_d * dense) + float32(w_s * sparse), top-k by (fused descending,
@@ -1243,6 +1337,8 @@ class HybridRetriever(SparseRetrieval):
         Every document of the inverted index must be in the dense index.  allowed_ids (None: every document): database ids - both
         heads, and with them the union that is fused, are restricted to these documents; allowed_masks / query_group as for retrieve: a
         filter per query, the union of the two restricted lists is fused.  Returns (sparse_res, dense_res, fused_res)."""
+        from .collapse import not_under_collapse
+        not_under_collapse("HybridRetriever.retrieve_fused", collapse)
         from .rerank import fused_scores, ranked_run
         sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res = self._retrieve_both(
             q_loader, topk, threshold, allowed_ids=allowed_ids, allowed_masks=allowed_masks, query_group=query_group)
@@ -1315,7 +1411,7 @@ class HybridRetriever(SparseRetrieval):
         return super().range_search(sparse_query_vecs, thresholds, sort=sort, _filter=self.allowed_group_filters(allowed_masks, query_group)[1])
 
     def search_fused(self, sparse_query_vecs, dense_query_vecs, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, qids=None,
-                     allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
+                     allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
         """The EXACT top-k of the fused score of retrieve_fused over every document of the dense index (hybrid.search_fused: the
         union of the two heads' lists at depth depths[0] >= topk where a certificate proves it holds the true top-k, deeper lists
         for the queries it does not, a dense range search for what is left; the same result whatever route served a query).
@@ -1329,6 +1425,8 @@ class HybridRetriever(SparseRetrieval):
         together with allowed_mask): a filter per query - the exact top-k of the fused score over the documents of
         allowed_masks[query_group[q]] alone, for every group what allowed_mask=allowed_masks[g] returns for its queries.  Not supported
         (NotImplementedError): allowed_ids, and the doc-sharded classes."""
+        from .collapse import not_under_collapse
+        not_under_collapse("HybridRetriever.search_fused", collapse)
         from . import hybrid
         hybrid.check_arguments(topk, weights)
         if allowed_ids is not None:
@@ -1350,10 +1448,12 @@ class HybridRetriever(SparseRetrieval):
         return RunResult(qids, scores, positions, self.dense_index.run_table(), counts), stats
 
     def retrieve_fused_exact(self, q_loader, topk, weights=(1.0, 1.0), depths=None, fallback_bytes=1 << 30, allowed_ids=None,
-                             allowed_mask=None, allowed_masks=None, query_group=None):
+                             allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
         """Encodes the queries once (both heads) and writes {out_dir}/fused_exact/run.json, next to the two heads' runs: the exact
         fused top-k of search_fused (allowed_mask, or allowed_masks with query_group in loader order, as there).  Returns (RunResult, stats).  The files of retrieve / retrieve_fused are
         not touched."""
+        from .collapse import not_under_collapse
+        not_under_collapse("HybridRetriever.retrieve_fused_exact", collapse)
         from . import hybrid
         hybrid.check_arguments(topk, weights)
         if allowed_ids is not None:

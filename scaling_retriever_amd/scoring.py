@@ -5,7 +5,7 @@ the HIP kernels (csrc/dense_score.hip, csrc/sparse_cert.hip, csrc/sparse_score.h
 The reference-shaped classes in indexer.py are built on top of these.
 
 What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, topk_merge, hybrid_union,
-hybrid_rank).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
+hybrid_rank, topk_collapse).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
 the status checked under that name); a filtered variant of an entry is the same call with "_subset" / "_masked" appended to the name
 and the filter's two arguments spliced in where the header puts them (_filter_args).  Each class checks its queries in one place
 (DenseIndexHIP._queries, SparseIndexHIP._query_csr), the range searches share _thresholds, and add_host_rows / add_npy_file share
@@ -407,6 +407,26 @@ class DenseIndexHIP:
         self._call("sr_dense_range_fill" + suffix, _ptr(queries), queries.shape[0], _ptr(thr), *spliced, _ptr(lims), _ptr(scores), _ptr(ids), n)
         return scores[:n], ids[:n]
 
+    def search_collapsed(self, queries, k, keys, depths=None, fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None):
+        """The top-k distinct groups of every query, each represented and scored by its best passage (MaxP / field collapsing;
+        collapse.py).  keys: int32 [id_end] tensor / array, the group key >= 0 of every document index.  Returns
+        (scores fp32 [nq, k], ids int64 [nq, k] the best passages, keys int32 [nq, k], counts int32 [nq]) as cuda tensors, padded with
+        (-FLT_MAX, -1, -1), and stats = {"depth": int64 [nq] the index into depths at which the query was proven complete, -1 = the
+        full-ranking route; "groups_seen": int64 [nq]; "depths": the schedule} - exactly the first-occurrence-per-group row of the full
+        ranking cut to k, whatever route served the query.  depths (default 4k, 16k, ... <= sr_max_topk()): the search depths of the
+        rounds, each >= k, beyond sr_max_topk() allowed, clipped to the number of (allowed) documents; queries still open after the
+        last depth are searched with k = that number, in sub-batches of fallback_bytes (a single query that does not fit: MemoryError
+        naming it).  1 <= k <= sr_max_topk().  subset / mask / masks + query_group: the filters of `search` / `search_grouped`, one at
+        most, resolved once per call; under masks the depths are clipped to sr_max_topk() (the grouped search's limit) and the
+        full-ranking route runs group by group with mask=.  Precision other than "fp32" / "fp32_filtered": ValueError.
+        Scores: every returned score is bit for bit score_pairs of (query, returned passage) and the ranking is by those scores.  Later
+        rounds run on small sub-batches, and a batch of <= 64 queries otherwise accumulates in another order; the driver therefore
+        switches set_batch_invariant(True) on for the duration of the call - every search of every round then accumulates in the
+        pair scorer's order - and puts the caller's setting back afterwards."""
+        from .collapse import dense_search_collapsed
+        return dense_search_collapsed(self, queries, k, keys, depths=depths, fallback_bytes=fallback_bytes, subset=subset, mask=mask,
+                                      masks=masks, query_group=query_group)
+
     def score_pairs(self, queries, cand_indptr, cand_ids):
         """Exact scores of given (query, document) pairs: queries fp32 cuda [nq, dim]; the candidates of query q are
         cand_ids[cand_indptr[q]:cand_indptr[q + 1]] (int64, the ids `search` returns; ragged, empty lists and repeats allowed, any
@@ -638,6 +658,18 @@ class SparseIndexHIP:
             scores, ids = range_sort(lims, scores, ids)
         return lims, scores, ids
 
+    def search_collapsed(self, q_indptr, q_cols, q_vals, k, keys, threshold=0.0, id_base=0, id_stride=1, depths=None, fallback_bytes=1 << 30,
+                         subset=None, mask=None, masks=None, query_group=None):
+        """The top-k distinct groups of every query, each represented and scored by its best passage (collapse.py):
+        DenseIndexHIP.search_collapsed on this head.  Queries, threshold, id_base / id_stride as for `search` - only documents with
+        score > threshold are ranked; keys int32 is indexed by the ids the search returns (id_base + position * id_stride), so it holds
+        id_base + (n_docs - 1) * id_stride + 1 entries; the search's counts are handed to the device step.  Filters as for `search` /
+        `search_grouped`, one at most.  Returns (scores, ids, keys, counts, stats) as there."""
+        from .collapse import sparse_search_collapsed
+        return sparse_search_collapsed(self, q_indptr, q_cols, q_vals, k, keys, threshold=threshold, id_base=id_base, id_stride=id_stride,
+                                       depths=depths, fallback_bytes=fallback_bytes, subset=subset, mask=mask, masks=masks,
+                                       query_group=query_group)
+
     def score_pairs(self, q_indptr, q_cols, q_vals, cand_indptr, cand_ids):
         """Exact scores of given (query, document) pairs: queries as for `search`, candidates as for DenseIndexHIP.score_pairs (ids =
         document positions).  Returns fp32 cuda [total]: the reference's term-serial chain, no threshold, 0.0 where nothing matches
@@ -769,3 +801,46 @@ def hybrid_rank(cand_indptr, dpos, spos, tie, dense_scores, sparse_scores, weigh
     p = [_ptr(t) for t in keep]
     _call(dev, "sr_hybrid_rank", _ptr(i64[0]), *p[:5], nq, float(weights[0]), float(weights[1]), k, *p[5:8], int(n_s2d), int(id_end), *p[8:])
     return out_s, out_i, counts, cert, thr
+
+
+def collapse_keys_argument(keys):
+    """The host check of a group-key table (collapse.py): a 1-D int32 tensor / array, as given.  Touches no device."""
+    if not torch.is_tensor(keys) and not isinstance(keys, np.ndarray):
+        raise ValueError(f"keys must be an int32 tensor / array that maps a document index to its group key, got {type(keys).__name__}")
+    if keys.dtype not in (np.int32, torch.int32):
+        raise ValueError(f"keys must be int32 (one group key >= 0 per document index), got {keys.dtype}")
+    if len(keys.shape) != 1:
+        raise ValueError(f"expected 1-D keys, got {tuple(keys.shape)}")
+    return keys
+
+
+def topk_collapse(scores, ids, keys, k, counts=None, exhaustive=False):
+    """Every ranked row -> its first k first-occurrence-per-group entries (sr_topk_collapse, csrc/topk_collapse.hip): scores fp32 / ids
+    int64 [nq, row_len] cuda tensors as a search returns them (row_len of any size), keys int32 [n_keys] the group key >= 0 of every id,
+    counts int32 [nq] the valid prefix of each row (the sparse search's; None: a row ends at its first negative id), exhaustive: the
+    rows are whole rankings.  Returns (scores fp32 [nq, k], ids int64 [nq, k], keys int32 [nq, k], counts int32 [nq], complete int32
+    [nq]) on the device, padded with (-FLT_MAX, -1, -1); complete[q] = 1: the row is the top-k groups of the full ranking.  1 <= k <=
+    sr_max_topk().  An id outside [0, n_keys) or a negative key inside a row: ValueError naming the (query, position)."""
+    keys = collapse_keys_argument(keys)
+    if scores.dim() != 2 or ids.shape != scores.shape:
+        raise ValueError(f"expected scores and ids of one shape [nq, row_len], got {tuple(scores.shape)} and {tuple(ids.shape)}")
+    _lib.require_gpu()
+    dev = scores.device
+    scores, ids = scores.to(torch.float32).contiguous(), ids.to(device=dev, dtype=torch.int64).contiguous()
+    keys = _to_dev(keys, torch.int32, dev)
+    nq, row_len = scores.shape
+    if counts is not None:
+        counts = _to_dev(counts, torch.int32, dev)
+        if counts.dim() != 1 or counts.numel() != nq:
+            raise ValueError(f"expected {nq} counts, got {tuple(counts.shape)}")
+        counts = _valid(counts)
+    k = int(k)
+    out_s = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+    out_i = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+    out_k = torch.empty((nq, max(k, 0)), dtype=torch.int32, device=dev)
+    out_c = torch.empty((nq,), dtype=torch.int32, device=dev)
+    done = torch.empty((nq,), dtype=torch.int32, device=dev)
+    keep = [_valid(t) for t in (scores, ids, keys, out_s, out_i, out_k, out_c, done)]
+    p = [_ptr(t) for t in keep]
+    _call(dev, "sr_topk_collapse", p[0], p[1], _ptr(counts), nq, row_len, 1 if exhaustive else 0, p[2], keys.numel(), k, *p[3:])
+    return out_s, out_i, out_k, out_c, done
