@@ -52,10 +52,17 @@ def parse_args(argv=None):
     ap.add_argument("--collapse_file", type=str, default=None,
                     help="retrieval task: a TSV of passage_id<TAB>group_id - rank the top_k best GROUPS, each scored by its best passage "
                          "(MaxP); run.json is then keyed by group id")
+    ap.add_argument("--collapse_hits", type=int, default=0,
+                    help="with --collapse_file: also the up to M best passages inside every returned group, written as a passage-level run "
+                         "to hits/run.json (0: off; at most 64)")
     ap.add_argument("--index_dtype", choices=["fp32", "fp16"], default="fp32",
                     help="retrieval: how the flat index keeps its rows. fp16 rounds the (fp32) shard files once, at ingest, and "
                          "holds half the bytes; the shard files themselves are not changed")
     args = ap.parse_args(argv)
+    if args.collapse_hits and not args.collapse_file:
+        ap.error("--collapse_hits needs --collapse_file (hits are the passages inside the groups of a collapsed search)")
+    if not 0 <= args.collapse_hits <= 64:
+        ap.error(f"--collapse_hits must be in [0, 64], got {args.collapse_hits}")
     if args.eval_metric:
         args.eval_metric = ast.literal_eval(args.eval_metric)     # the reference uses eval() (eval_dense.py:70)
     return args
@@ -289,9 +296,17 @@ def retrieval(args):
         from scaling_retriever_amd.collapse import key_table, read_collapse_file
         from scaling_retriever_amd.utils.run_file import to_host, write_run_json
         group_of = read_collapse_file(args.collapse_file)
-        keys, table = key_table(lambda d: group_of[str(d)], np.concatenate([np.load(f) for f in id_files]).tolist())
-        scores, _, gkeys, counts, _ = index.search_collapsed(q_reps.contiguous(), args.top_k, keys, subset=subset)
+        db_ids = np.concatenate([np.load(f) for f in id_files]).tolist()
+        keys, table = key_table(lambda d: group_of[str(d)], db_ids)
+        found = index.search_collapsed(q_reps.contiguous(), args.top_k, keys, subset=subset, hits=args.collapse_hits or None)
+        scores, _, gkeys, counts = found[:4]
         write_run_json(os.path.join(args.out_dir, "run.json"), qids, to_host(scores), to_host(gkeys.to(torch.int64)), table, to_host(counts))
+        if args.collapse_hits:
+            # the passages inside the groups, a passage-level run: per query its groups' hits by (group rank, hit rank)
+            from scaling_retriever_amd.collapse import pack_hits
+            h_scores, h_ids, h_counts = pack_hits(*found[5])
+            os.makedirs(os.path.join(args.out_dir, "hits"), exist_ok=True)
+            write_run_json(os.path.join(args.out_dir, "hits", "run.json"), qids, to_host(h_scores), to_host(h_ids), db_ids, to_host(h_counts))
         return
     if subset is not None:
         scores, idx = index.search(q_reps.contiguous(), args.top_k, subset=subset)      # positions = the files' rows in plan order

@@ -46,9 +46,16 @@ def parse_args(argv=None):
     ap.add_argument("--collapse_file", type=str, default=None,
                     help="retrieval task: a TSV of passage_id<TAB>group_id - rank the top_k best GROUPS, each scored by its best passage "
                          "(MaxP); run.json is then keyed by group id")
+    ap.add_argument("--collapse_hits", type=int, default=0,
+                    help="with --collapse_file: also the up to M best passages inside every returned group, written as a passage-level run "
+                         "to hits/run.json (0: off; at most 64)")
     ap.add_argument("--doc_max_terms", type=int, default=0, help="indexing task: terms indexed per document (index size)")
     ap.add_argument("--query_max_terms", type=int, default=0, help="retrieval task: terms searched per query (latency)")
     args = ap.parse_args(argv)
+    if args.collapse_hits and not args.collapse_file:
+        ap.error("--collapse_hits needs --collapse_file (hits are the passages inside the groups of a collapsed search)")
+    if not 0 <= args.collapse_hits <= 64:
+        ap.error(f"--collapse_hits must be in [0, 64], got {args.collapse_hits}")
     if args.eval_metric:
         args.eval_metric = ast.literal_eval(args.eval_metric)
     return args
@@ -168,7 +175,8 @@ def sparse_retrieval(args):
         from scaling_retriever_amd.collapse import read_collapse_file
         group_of = read_collapse_file(args.collapse_file)
         collapse = lambda d: group_of[str(d)]      # noqa: E731  (collection ids may be ints, the file's are text)
-    return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids, collapse=collapse)
+    return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids, collapse=collapse,
+                              hits=args.collapse_hits or None)
 
 
 def evaluate_msmarco(args):

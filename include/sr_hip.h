@@ -989,6 +989,53 @@ int sr_topk_collapse(const float* d_scores, const int64_t* d_ids, const int32_t*
                      const int32_t* d_keys, int64_t n_keys, int k, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_keys,
                      int32_t* d_out_counts, int32_t* d_out_complete, sr_stream stream);
 
+/* ------------------------------------------------------------------------------------- hits inside a collapsed search's groups ---
+ * The two device steps of collapse.group_hits (csrc/group_hits.hip): the top-m passages of every group a collapsed
+ * search returned ("inner hits").  Between them run the pair scorers above, unchanged, so a hit's score is sr_dense_score_pairs /
+ * sr_sparse_score_pairs of that pair bit for bit.  No reference counterpart.
+ *
+ * The member table (built once per key table, collapse.member_table): d_uniq_keys int32 [n_groups] STRICTLY ASCENDING group keys;
+ * d_member_indptr int64 [n_groups + 1]; d_member_ids int64 [n_members], the documents of group g at indptr[g] .. indptr[g + 1], ascending.
+ * Keys are arbitrary non-negative int32: a slot's key is looked up by binary search, never used as an array index.
+ *
+ * sr_group_members_count / _fill: which members of every (query, slot) the query's filter allows, as CSR over the nq * kg slots.
+ *   d_slot_keys int32 [nq, kg]: the keys a collapsed search returned; a negative key is padding and has no members.
+ *   Filter: n_masks == 0: none (d_mask_words / d_query_group unused).  Otherwise d_mask_words uint32 [n_masks, W], W = ceil(n_bits / 32),
+ *   stacked bitmaps in the convention of sr_dense_search_grouped, and d_query_group int32 [nq]: query q's members are tested against
+ *   bitmap d_query_group[q]; n_masks == 1 with d_query_group == NULL: the one bitmap for every query.
+ *   count  writes d_out_indptr int64 [nq * kg + 1], the exclusive scan in slot order of the number of allowed members of every slot, and
+ *          *total (host) = its last entry.
+ *   fill   the same inputs and that d_out_indptr: d_out_ids int64 [capacity] holds at indptr[s] .. indptr[s + 1] the allowed members of
+ *          slot s in ascending order; nothing is written at or beyond `capacity`.
+ *   Eight lanes per slot, a ballot per eight members; no global atomics, the same bytes on every run.  Each call waits for the stream
+ *   once, to read the status (and count's total), and frees its scratch (count: 4 bytes per slot).
+ *   SR_ERR_INVALID before any device work: null pointers (the mask pointers only where n_masks asks for them), nq < 0, kg < 0,
+ *   nq * kg >= 2^38, negative sizes, n_members >= 2^31.  SR_ERR_INVALID found on the device, the outputs then not to be used and the
+ *   library usable as before - sr_last_error() names the first offender in slot order: a d_query_group entry outside [0, n_masks) ("query
+ *   Q is in group G"), a non-negative slot key absent from the table ("query Q, slot J: key K"), under a mask a member id outside
+ *   [0, n_bits) ("query Q, slot J: member id I"; without a mask the ids are copied unread).  nq * kg == 0: indptr[0] = 0, total 0.
+ *
+ * sr_segment_topm: the m best entries of every segment of a scored CSR.  d_scores fp32 / d_ids int64 [d_seg_indptr[n_segs]], segment s
+ *   at d_seg_indptr[s] .. [s + 1] (int64 [n_segs + 1], starting at 0, never decreasing), of any length, ids in any order (below
+ *   INT64_MAX).  With use_threshold != 0 only entries with score > threshold take part.  Order: score descending compared as floats
+ *   (-0.0 and +0.0 are one score and read back as +0.0), then id ascending - the order of the searches.  d_out_scores fp32 / d_out_ids
+ *   int64 [n_segs, m]: the best min(m, count) entries, then (pad_score, -1); d_out_counts int32 [n_segs] = the number of entries that
+ *   took part (NOT cut to m).  One wave per segment over tiles of 64 entries, the running best one per lane, in-wave bitonic sort and
+ *   merge through cross-lane exchanges; no atomics, the same bytes on every run.  1 <= m <= 64.  m outside that, null pointers, n_segs
+ *   < 0: SR_ERR_INVALID before any device work; a d_seg_indptr that does not start at 0 or decreases: SR_ERR_INVALID found on the device
+ *   (reads stay inside [0, d_seg_indptr[n_segs])), naming the place.  The call waits for the stream once.                            */
+int sr_group_members_count(const int32_t* d_slot_keys, int64_t nq, int64_t kg, const int32_t* d_uniq_keys, int64_t n_groups,
+                           const int64_t* d_member_indptr, const int64_t* d_member_ids, int64_t n_members,
+                           const uint32_t* d_mask_words, int64_t n_masks, int64_t n_bits, const int32_t* d_query_group,
+                           int64_t* d_out_indptr, int64_t* total, sr_stream stream);
+int sr_group_members_fill(const int32_t* d_slot_keys, int64_t nq, int64_t kg, const int32_t* d_uniq_keys, int64_t n_groups,
+                          const int64_t* d_member_indptr, const int64_t* d_member_ids, int64_t n_members,
+                          const uint32_t* d_mask_words, int64_t n_masks, int64_t n_bits, const int32_t* d_query_group,
+                          const int64_t* d_out_indptr, int64_t* d_out_ids, int64_t capacity, sr_stream stream);
+int sr_segment_topm(const float* d_scores, const int64_t* d_ids, const int64_t* d_seg_indptr, int64_t n_segs, int m,
+                    int use_threshold, float threshold, float pad_score, float* d_out_scores, int64_t* d_out_ids,
+                    int32_t* d_out_counts, sr_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,12 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_topk_collapse": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    "sr_group_members_count": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                       c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    "sr_group_members_fill": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                      c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sr_segment_topm": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
     "sr_model_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(SrModelConfig)]),
     "sr_model_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "sr_model_finalize": (c_int, [c_void_p]),

@@ -20,7 +20,14 @@ hybrid.search_fused:
 
 Collapsing post-processes rows the existing searches return, so it composes with every filter (subset=, mask=, masks= + query_group=).
 All arithmetic is in the HIP kernels; the host only moves rows between rounds.  Not offered: the fused hybrid searches and the range
-searches under collapse, doc-sharded indexes, k > sr_max_topk()."""
+searches under collapse, doc-sharded indexes, k > sr_max_topk().
+
+Hits inside the groups (hits=m of the two drivers): for every returned group its up to m best passages - the members
+of the group that the call's filter allows for the query, on the sparse head with score > threshold, in the same (score, id) order,
+scored by the head's pair scorer.  member_table inverts `keys` once (torch's stable sort on the device); group_hits runs
+sr_group_members_count -> _fill -> score_pairs -> sr_segment_topm (csrc/group_hits.hip) in query sub-batches sized from fallback_bytes
+by the count pass's totals (PAIR_BYTES per pair); pack_hits turns the ragged [k, m] block into the left-aligned rows the run writer
+takes.  Without hits= nothing here runs and every call returns what it returned before."""
 import numpy as np
 import torch
 
@@ -185,14 +192,142 @@ def collapse_rounds(who, nq, k, keys, depths, device, search, full_parts, fallba
     return scores, ids, gkeys, counts, stats
 
 
-def dense_search_collapsed(dense, queries, k, keys, depths=None, fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None):
+def member_table(keys, device=None):
+    """The inverse of a key table, the input of group_hits: (uniq_keys int32 [G] strictly ascending, member_indptr int64 [G + 1],
+    member_ids int64 [n]) on `device` (None: where keys live) - the documents of group uniq_keys[g] are member_ids[member_indptr[g] :
+    member_indptr[g + 1]], ascending.  keys (int32 tensor / array) is indexed in the numbering the head's bitmaps and pair scorer use:
+    the dense head's global document index (what its search returns), the sparse head's document POSITION (for a sparse search with
+    id_base / id_stride: keys[id_base + id_stride * arange(n_docs)]).  A negative key is an index without a document and belongs to
+    no group.  Built with torch's stable sort where the keys are - plumbing, no arithmetic; build it once per key table and pass it as
+    members= when many calls share it."""
+    from .scoring import collapse_keys_argument
+    keys = collapse_keys_argument(keys)
+    keys = keys if torch.is_tensor(keys) else torch.from_numpy(np.ascontiguousarray(keys))
+    if device is not None:
+        keys = keys.to(device)
+    ids = torch.nonzero(keys >= 0).reshape(-1)                      # ascending
+    by_key, order = torch.sort(keys[ids], stable=True)              # stable: ids stay ascending inside a group
+    uniq, sizes = torch.unique_consecutive(by_key, return_counts=True)
+    indptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=keys.device)
+    indptr[1:] = torch.cumsum(sizes, 0)
+    return uniq.to(torch.int32).contiguous(), indptr, ids[order].contiguous()
+
+
+# device bytes group_hits holds per (query, member) pair of a sub-batch: the member's id in the head's numbering (8) and its score (4) -
+# the materialised pair list - and the id in the caller's numbering where a strided sparse search renames it (8); rounded up for the
+# per-slot offsets (8 per slot) and the [slots, m] result, which do not grow with the group sizes
+PAIR_BYTES = 24
+
+
+def hits_stats(stats, hit_counts, gkeys, m):
+    """stats of a collapsed search + "mean_hits": the mean number of hits RETURNED (at most m) per returned group."""
+    valid = gkeys >= 0
+    n = int(valid.sum())
+    stats["mean_hits"] = float(hit_counts.clamp(max=m)[valid].sum()) / n if n else 0.0
+    return stats
+
+
+def group_hits(head, queries, slot_keys, members, m, filt=None, threshold=None, id_base=0, id_stride=1, fallback_bytes=1 << 30,
+               who="group_hits"):
+    """The top-m passages inside every group of a collapsed result ("inner hits") - the driver both heads share.
+    head: a DenseIndexHIP (queries: its contiguous fp32 cuda [nq, dim] tensor) or a SparseIndexHIP (queries: the (indptr, cols, vals) CSR
+    on its device); slot_keys int32 cuda [nq, kg], the keys search_collapsed returned (-1: padding); members: member_table(...) in the
+    head's numbering; filt: None, (words int32 [W], n_bits) or (words int32 [G, W], n_bits, query_group [nq]) - the call's filter as
+    bitmaps in that numbering.
+
+    The hits of (q, slot j) are the members of the slot's group that the filter allows for q - on the sparse head (threshold given) only
+    those with score > threshold - ordered by (score descending as floats, id ascending) and cut to m.  Returns (hit_scores fp32
+    [nq, kg, m], hit_ids int64 [nq, kg, m], hit_counts int32 [nq, kg]): min(hit_counts, m) entries of a list are hits, the rest the
+    head's padding (dense (-FLT_MAX, -1), sparse (0, -1)); hit_counts is the number of hits before the cut, 0 for a padding slot.
+    Every score is the head's score_pairs of that pair, bit for bit.
+
+    Steps, all on the device: sr_group_members_count over all queries; then per sub-batch of queries sr_group_members_fill, the head's
+    score_pairs, sr_segment_topm.  A sub-batch is as many consecutive queries as have at most fallback_bytes / PAIR_BYTES pairs by the
+    count's totals; a list is selected whole inside its sub-batch, so the bytes do not depend on the cut.  A query whose pairs alone do not
+    fit: MemoryError naming it."""
+    from .hybrid import _csr_rows
+    from .scoring import SparseIndexHIP, group_members_count, group_members_fill, hits_argument, segment_topm
+    m = hits_argument(who, m)
+    sparse = isinstance(head, SparseIndexHIP)
+    dev = slot_keys.device
+    nq, kg = slot_keys.shape
+    pad = 0.0 if sparse else -FLT_MAX
+    out_s = torch.full((nq, kg, m), pad, dtype=torch.float32, device=dev)
+    out_i = torch.full((nq, kg, m), -1, dtype=torch.int64, device=dev)
+    out_c = torch.zeros((nq, kg), dtype=torch.int32, device=dev)
+    if nq * kg == 0:
+        return out_s, out_i, out_c
+    slot_keys = slot_keys.contiguous()
+    indptr, _ = group_members_count(slot_keys, members, filt)
+    per_query = (indptr[kg::kg] - indptr[:-1:kg]).cpu().numpy()             # pairs of every query: nq words to the host
+    budget = int(fallback_bytes) // PAIR_BYTES
+    q0 = 0
+    while q0 < nq:
+        if per_query[q0] > budget:
+            raise MemoryError(f"{who}: query {q0} alone needs {int(per_query[q0]) * PAIR_BYTES} bytes for its {int(per_query[q0])} (query, "
+                              f"group member) pairs, fallback_bytes is {int(fallback_bytes)}")
+        q1, pairs = q0, 0
+        while q1 < nq and pairs + per_query[q1] <= budget:
+            pairs += int(per_query[q1])
+            q1 += 1
+        sub_ptr = indptr[q0 * kg:q1 * kg + 1] - indptr[q0 * kg]
+        sub_filt = filt if filt is None or len(filt) < 3 or filt[2] is None else (filt[0], filt[1], filt[2][q0:q1])
+        ids = group_members_fill(slot_keys[q0:q1], members, sub_ptr, pairs, sub_filt)
+        cand_ptr = sub_ptr[::kg].contiguous()
+        if sparse:
+            csr = _csr_rows(*queries, torch.arange(q0, q1, device=dev))
+            scores = head.score_pairs(csr[0], csr[1], csr[2], cand_ptr, ids)
+        else:
+            scores = head.score_pairs(queries[q0:q1], cand_ptr, ids)
+        s, i, c = segment_topm(scores, ids, sub_ptr, m, threshold=threshold, pad_score=pad)
+        out_s[q0:q1], out_i[q0:q1], out_c[q0:q1] = s.view(-1, kg, m), i.view(-1, kg, m), c.view(-1, kg)
+        q0 = q1
+    if sparse and (int(id_base) != 0 or int(id_stride) != 1):
+        out_i = torch.where(out_i >= 0, int(id_base) + out_i * int(id_stride), out_i)
+    return out_s, out_i, out_c
+
+
+def pack_hits(hit_scores, hit_ids, hit_counts):
+    """The ragged [nq, k, m] block of a hits result as left-aligned rows, on the device: (scores fp32 [nq, k * m], ids int64 [nq, k * m],
+    counts int32 [nq]) - per query the hits of its groups in (group rank, hit rank) order, counts[q] of them, the rest (0, -1).  What the
+    run writer takes for the passage-level run of a collapsed retrieval."""
+    nq, k, m = hit_scores.shape
+    dev = hit_scores.device
+    valid = (torch.arange(m, device=dev)[None, None, :] < hit_counts.clamp(max=m)[:, :, None]).reshape(nq, k * m)
+    order = torch.argsort((~valid).to(torch.int8), dim=1, stable=True)          # the hits first, in their order
+    scores = torch.gather(hit_scores.reshape(nq, k * m), 1, order)
+    ids = torch.gather(hit_ids.reshape(nq, k * m), 1, order)
+    counts = valid.sum(1).to(torch.int32)
+    rest = torch.arange(k * m, device=dev)[None, :] >= counts[:, None]
+    return scores.masked_fill(rest, 0.0), ids.masked_fill(rest, -1), counts
+
+
+def hits_of_no_collapse(who, hits, collapse):
+    """hits= asks for the passages inside the groups of a collapsed search: without collapse= there are none."""
+    if hits is not None and collapse is None:
+        raise ValueError(f"{who}: hits= are the passages inside the groups of a collapsed search; pass collapse= as well")
+
+
+def _with_hits(out, hits):
+    """(scores, ids, keys, counts, stats) of a collapsed search + the hits tuple and its statistic."""
+    hits_stats(out[4], hits[2], out[2], hits[0].shape[2])
+    return (*out, hits)
+
+
+def dense_search_collapsed(dense, queries, k, keys, depths=None, fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None,
+                           hits=None, members=None):
     """DenseIndexHIP.search_collapsed (see there)."""
-    from .doc_filter import _subset, doc_list_from_mask, mask_on_device, one_filter, query_group_argument
+    from .doc_filter import _subset, doc_list_from_mask, doc_mask_from_list, mask_on_device, one_filter, query_group_argument
+    from .scoring import hits_argument, member_table_argument
     who = "search_collapsed"
     if dense.precision not in ("fp32", "fp32_filtered"):
         raise ValueError(f"{who} needs a dense index whose search returns the exact kernel's bits (precision 'fp32' or 'fp32_filtered'), "
                          f"this one is in {dense.precision!r}")
     one_filter(who, masks, query_group, subset=subset, mask=mask)
+    if hits is not None:
+        hits = hits_argument(who, hits)
+    if members is not None:
+        members = member_table_argument(members)
     grouped = masks is not None
     k, depths = check_arguments(who, k, keys, depths, lambda: dense.id_end, clip=int(_lib.load().sr_max_topk()) if grouped else None)
     if mask is not None:
@@ -245,27 +380,46 @@ def dense_search_collapsed(dense, queries, k, keys, depths=None, fallback_bytes=
             parts.append((rows[pg == g], m, lambda sub, g=g, m=m: (*dense.search(q[sub].contiguous(), max(1, m), mask=words[g]), None)))
         return parts
 
+    def with_hits(out):
+        """The hits of the groups just returned, under the call's filter as a bitmap over [0, id_end)."""
+        if hits is None:
+            return out
+        filt = None
+        if subset is not None:
+            filt = (doc_mask_from_list(subset, dense.id_end, dev), dense.id_end)
+        elif mask is not None:
+            filt = (words, n_bits)
+        elif grouped:
+            filt = (words, n_bits, groups)
+        table = member_table(keys) if members is None else members
+        return _with_hits(out, group_hits(dense, q, out[2], table, hits, filt=filt, fallback_bytes=fallback_bytes, who=who))
+
     if N == 0:                                  # nothing to rank: padding rows, count 0, depth 0
         out = collapse_rounds(who, nq, k, keys, (), dev, search, lambda rows: [], fallback_bytes)
         out[4]["depth"][:], out[4]["depths"] = 0, depths
-        return out
+        return with_hits(out)
     was_invariant = dense.batch_invariant
     if not was_invariant:
         dense.set_batch_invariant(True)
     try:
-        return collapse_rounds(who, nq, k, keys, depths, dev, search, full_parts, fallback_bytes)
+        return with_hits(collapse_rounds(who, nq, k, keys, depths, dev, search, full_parts, fallback_bytes))
     finally:
         if not was_invariant:
             dense.set_batch_invariant(False)
 
 
 def sparse_search_collapsed(sparse, q_indptr, q_cols, q_vals, k, keys, threshold=0.0, id_base=0, id_stride=1, depths=None,
-                            fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None):
+                            fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None, hits=None, members=None):
     """SparseIndexHIP.search_collapsed (see there)."""
-    from .doc_filter import _subset, mask_argument, mask_on_device, one_filter, query_group_argument
+    from .doc_filter import _subset, doc_mask_from_list, mask_argument, mask_on_device, one_filter, query_group_argument
     from .hybrid import _csr_rows
+    from .scoring import hits_argument, member_table_argument
     who = "search_collapsed"
     one_filter(who, masks, query_group, subset=subset, mask=mask)
+    if hits is not None:
+        hits = hits_argument(who, hits)
+    if members is not None:
+        members = member_table_argument(members)
     grouped = masks is not None
     N = sparse.n_docs
     id_base, id_stride = int(id_base), int(id_stride)
@@ -310,4 +464,19 @@ def sparse_search_collapsed(sparse, q_indptr, q_cols, q_vals, k, keys, threshold
     def full_parts(rows):
         return [(rows, N, lambda sub: run(sub, max(1, N)))]
 
-    return collapse_rounds(who, nq, k, keys, depths, dev, search, full_parts, fallback_bytes)
+    out = collapse_rounds(who, nq, k, keys, depths, dev, search, full_parts, fallback_bytes)
+    if hits is None:
+        return out
+    # the hits of the groups just returned: members, bitmaps and the pair scorer number documents by POSITION; ids go out renamed
+    filt = None
+    if subset is not None:
+        filt = (doc_mask_from_list(how["subset"], N, dev), N)
+    elif mask is not None:
+        filt = (how["mask"], N)
+    elif grouped:
+        filt = (words, N, groups)
+    table = members
+    if table is None:
+        table = member_table(keys[id_base + id_stride * torch.arange(N, device=dev)] if (id_base, id_stride) != (0, 1) else keys)
+    return _with_hits(out, group_hits(sparse, (row_ptr, cols, vals), out[2], table, hits, filt=filt, threshold=float(threshold), id_base=id_base,
+                                      id_stride=id_stride, fallback_bytes=fallback_bytes, who=who))

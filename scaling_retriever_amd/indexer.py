@@ -57,6 +57,29 @@ def _collapse_filter(filt):
     return _search_filter(filt)
 
 
+def _collapse_stats(route):
+    """collapse.route_stats plus, where the search computed hits, their mean number per returned group (q_stats.json)."""
+    from .collapse import route_stats
+    out = route_stats(route)
+    if "mean_hits" in route:
+        out["mean_hits"] = float(route["mean_hits"])
+    return out
+
+
+def _hits_run(qids, hits, table):
+    """The passage-level run of a collapsed search's hits (scores [nq, k, m], ids [nq, k, m], counts [nq, k] on the device): packed to
+    left-aligned rows there (collapse.pack_hits), a RunResult over the id table of the head."""
+    from .collapse import pack_hits
+    scores, ids, counts = pack_hits(*hits)
+    return RunResult(qids, to_host(scores), to_host(ids), table, to_host(counts))
+
+
+def _dump_hits_run(hits_res, out_dir):
+    """{out_dir}/hits/run.json through the run writer."""
+    os.makedirs(os.path.join(out_dir, "hits"), exist_ok=True)
+    hits_res.dump(os.path.join(out_dir, "hits", "run.json"))
+
+
 def batch_groups(loader, max_rows=16384):
     """Consecutive collator batches of `loader`, grouped until `max_rows` rows: one LlamaBi*.encode_batches call per group.
     The reference's query loaders yield eval_batch_size (128) rows at a time (eval_dense.py:219-220, eval_sparse.py:125-127);
@@ -411,19 +434,28 @@ class DenseFlatIndexer(DenseIndexer):
         return key_table(group_of, self.index_id_to_db_id)
 
     def search_collapsed(self, query_reps, top_docs: int, group_of, depths=None, fallback_bytes=1 << 30, allowed_ids=None, allowed_mask=None,
-                         allowed_masks=None, query_group=None, return_stats=False):
+                         allowed_masks=None, query_group=None, return_stats=False, hits=None):
         """The top_docs best GROUPS of every query, each represented and scored by its best passage (MaxP; DenseIndexHIP.search_collapsed,
         collapse.py): group_of gives each passage's group label - a dict on the database id, a callable on it, or a sequence aligned with
         index order.  Returns one (group_labels, scores fp32, passage_db_ids) triple per query, best group first (fewer than top_docs
-        groups: shorter lists); return_stats=True: also the route statistics of the driver.  Filters as for search_knn."""
+        groups: shorter lists); return_stats=True: also the route statistics of the driver.  Filters as for search_knn.
+        hits=m (1 <= m <= 64; None: off): every triple gains a fourth element, per group its (passage_db_ids, scores fp32) - the up to m
+        best passages of the group that the filter allows, best first (collapse.group_hits); the first is the group's passage above."""
         filt = self._resolve("search_collapsed", allowed_ids, allowed_mask, allowed_masks, query_group)
         keys, table = self.collapse_keys(group_of)
         q = _dense_queries(query_reps, self.index.device)
-        scores, positions, gkeys, counts, stats = self.index.search_collapsed(q, top_docs, keys, depths=depths, fallback_bytes=fallback_bytes,
-                                                                              **_collapse_filter(filt))
-        scores, positions, gkeys, counts = to_host(scores), to_host(positions), to_host(gkeys), to_host(counts)
+        found = self.index.search_collapsed(q, top_docs, keys, depths=depths, fallback_bytes=fallback_bytes, hits=hits, **_collapse_filter(filt))
+        scores, positions, gkeys, counts = (to_host(t) for t in found[:4])
+        stats = found[4]
         ids = self.id_lists(positions)
         out = [([table[g] for g in gkeys[i, :c].tolist()], scores[i, :c].copy(), ids[i][:c]) for i, c in enumerate(counts.tolist())]
+        if hits is not None:
+            h_scores, h_pos, h_counts = (to_host(t) for t in found[5])
+            m = h_scores.shape[2]
+            h_ids = self.id_lists(h_pos.reshape(h_pos.shape[0], -1))
+            h_n = np.minimum(h_counts, m)
+            out = [row + ([(h_ids[i][j * m:j * m + n], h_scores[i, j, :n].copy()) for j, n in enumerate(h_n[i, :len(row[0])].tolist())],)
+                   for i, row in enumerate(out)]
         return (out, stats) if return_stats else out
 
     def inverse_id_map(self):
@@ -979,34 +1011,44 @@ class SparseRetrieval:
         from .collapse import key_table
         return key_table(group_of, [self.doc_ids.get(p) for p in range(self.hip_index.n_docs)])
 
-    def _retrieve_collapsed(self, sparse_query_vecs, qids, group_of, threshold, topk, filt, depths=None, fallback_bytes=1 << 30):
+    def _retrieve_collapsed(self, sparse_query_vecs, qids, group_of, threshold, topk, filt, depths=None, fallback_bytes=1 << 30, hits=None):
         """One collapsed search of the whole query set (SparseIndexHIP.search_collapsed): a RunResult keyed by group label - its
-        "positions" are the group keys, its id table the labels - and the stats of q_stats.json with the route statistics."""
-        from .collapse import route_stats
-        q = _as_query_csr(sparse_query_vecs, self._dev)
+        "positions" are the group keys, its id table the labels - and the stats of q_stats.json with the route statistics.  hits=m: a
+        third value, the passage-level RunResult of the groups' hits (collapse.pack_hits), and "mean_hits" in the statistics."""
+        q =_as_query_csr(sparse_query_vecs, self._dev)
         if filt is not None and filt.kind == "groups" and filt.groups.numel() != len(q):
             raise ValueError(f"query_group must hold one group id per query ({len(q)}), got {filt.groups.numel()}")
         keys, table = self.collapse_keys(group_of)
-        scores, _, gkeys, counts, route = self.hip_index.search_collapsed(q.row_ptr, q.cols, q.vals, topk, keys, threshold=threshold, depths=depths,
-                                                                          fallback_bytes=fallback_bytes, **_collapse_filter(filt))
+        found = self.hip_index.search_collapsed(q.row_ptr, q.cols, q.vals, topk, keys, threshold=threshold, depths=depths,
+                                                fallback_bytes=fallback_bytes, hits=hits, **_collapse_filter(filt))
+        scores, _, gkeys, counts, route = found[:5]
         res = RunResult(qids, to_host(scores), to_host(gkeys.to(torch.int64)), IdTable(table), to_host(counts))
         stats = defaultdict(float)
         stats["L0_q"] = q.mean_l0()
-        stats["collapse"] = route_stats(route)
-        return res, stats
+        stats["collapse"] = _collapse_stats(route)
+        if hits is None:
+            return res, stats
+        return res, stats, _hits_run(qids, found[5], self.doc_id_table())
 
-    def _write_outputs(self, res, stats):
+    def _write_outputs(self, res, stats, hits_res=None):
         os.makedirs(self.out_dir, exist_ok=True)
         if self.compute_stats:
             with open(os.path.join(self.out_dir, "q_stats.json"), "w") as handler:
                 json.dump(stats, handler)
         res.dump(os.path.join(self.out_dir, "run.json"))        # sr_write_run_json: the bytes json.dump(res) writes
+        if hits_res is not None:
+            _dump_hits_run(hits_res, self.out_dir)
 
-    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
+    def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None,
+                 hits=None):
         """collapse (None: rank passages): a `group_of` - dict on the collection id, callable on it, or a sequence aligned with document
         positions - makes this the collapsed search: the topk best GROUPS per query, each scored by its best passage
         (SparseIndexHIP.search_collapsed); run.json is then keyed by group label instead of passage id, and q_stats.json gains the route
         statistics ("collapse").  The query set is searched in one call.
+        hits=m (with collapse only, else ValueError; 1 <= m <= 64): also the up to m best passages inside every returned group
+        (collapse.group_hits).  run.json stays the group-keyed file, byte for byte; a second, passage-level run goes to hits/run.json -
+        qid -> {passage id: score}, per query the hits of its topk groups ordered by group rank, then hit rank - through the same run
+        writer; q_stats.json's "collapse" gains "mean_hits"; the return value becomes (group run, hits run).
         allowed_ids (None: every document): collection ids, any order, duplicates allowed - only these documents are ranked; an unknown
         id raises ValueError before anything is encoded.  allowed_mask: the same filter as a boolean array over the document positions
         of the inverted index (SparseIndexHIP.search, mask); one of the two at most.  allowed_masks bool [G, document positions] with
@@ -1017,6 +1059,8 @@ class SparseRetrieval:
         thread writes the previous group's piece of run.json (sr_write_run_json_part): formatting and the page-cache copy of a Dev-sized
         file take as long as the encode, and nothing in them needs the GPU.  A query's rows do not depend on the batch it is searched in
         (certified or exact: the same bits), and the file is the one-call file byte for byte (tests/test_boundary_gpu.py)."""
+        from .collapse import hits_of_no_collapse
+        hits_of_no_collapse("retrieve", hits, collapse)
         filt = self._resolve("retrieve", allowed_ids, allowed_mask, allowed_masks, query_group)
         groups = list(batch_groups(q_loader, self.QUERY_GROUP_ROWS))
         group_qids = [[x for batch in g for x in (batch["ids"] if isinstance(batch["ids"], list) else to_list(batch["ids"]))] for g in groups]
@@ -1025,9 +1069,9 @@ class SparseRetrieval:
             raise ValueError(f"retrieve: query_group must hold one group id per query ({len(qids)}), got {filt.groups.numel()}")
         if collapse is not None:
             sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
-            res, stats = self._retrieve_collapsed(sparse_query_vecs, qids, collapse, threshold, topk, filt)
-            self._write_outputs(res, stats)
-            return res
+            res, stats, *hits_res = self._retrieve_collapsed(sparse_query_vecs, qids, collapse, threshold, topk, filt, hits=hits)
+            self._write_outputs(res, stats, *hits_res)
+            return (res, hits_res[0]) if hits_res else res
         table = self.doc_id_table()
         if len(groups) < 2 or not (id_table(qids).distinct and id_table(table).distinct):
             sparse_query_vecs, qids = self._generate_query_vecs([batch for g in groups for batch in g])
@@ -1280,19 +1324,24 @@ class HybridRetriever(SparseRetrieval):
         dense_res.dump(os.path.join(self.dense_out_dir, "run.json"))
         return sparse_query_vecs, dense_query_vecs, qids, sparse_res, dense_res
 
-    def retrieve(self, q_loader, topk, id_dict=False, threshold=0., allowed_ids=None, allowed_masks=None, query_group=None, collapse=None):
+    def retrieve(self, q_loader, topk, id_dict=False, threshold=0., allowed_ids=None, allowed_masks=None, query_group=None, collapse=None,
+                 hits=None):
         """allowed_ids (None: every document): database ids - both heads rank only these documents (allowed_subsets).  allowed_masks bool
         [G, dense index positions] (the numbering of allowed_mask()) with query_group int [number of queries]: a filter per query for
         both heads (allowed_group_filters); not together with allowed_ids.  collapse (None: rank passages): a `group_of` - dict on the
         database id, callable on it, or a sequence aligned with the DENSE index's order - makes both searches collapsed searches: both
         run.json files are keyed by group label (the topk best groups, each scored by its best passage under that head) and
-        sparse/q_stats.json gains the route statistics of both heads ("collapse", "collapse_dense")."""
+        sparse/q_stats.json gains the route statistics of both heads ("collapse", "collapse_dense").  hits=m (with collapse only, else
+        ValueError): both heads also return the up to m best passages inside every group (collapse.group_hits) - the two run.json files
+        stay as they are, passage-level runs go to sparse/hits/run.json and dense/hits/run.json (SparseRetrieval.retrieve), both
+        statistics gain "mean_hits", and the return value becomes (sparse run, dense run, sparse hits run, dense hits run)."""
+        from .collapse import hits_of_no_collapse
+        hits_of_no_collapse("HybridRetriever.retrieve", hits, collapse)
         if collapse is not None:
-            return self._retrieve_both_collapsed(q_loader, topk, threshold, collapse, allowed_ids, allowed_masks, query_group)
+            return self._retrieve_both_collapsed(q_loader, topk, threshold, collapse, allowed_ids, allowed_masks, query_group, hits=hits)
         return self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids, allowed_masks=allowed_masks, query_group=query_group)[3:]
 
-    def _retrieve_both_collapsed(self, q_loader, topk, threshold, group_of, allowed_ids=None, allowed_masks=None, query_group=None):
-        from .collapse import route_stats
+    def _retrieve_both_collapsed(self, q_loader, topk, threshold, group_of, allowed_ids=None, allowed_masks=None, query_group=None, hits=None):
         one_filter("HybridRetriever.retrieve", allowed_masks, query_group, allowed_ids=allowed_ids)
         d_filt, s_filt = (None, None) if allowed_ids is None else (Filter("subset", t) for t in self.allowed_subsets(allowed_ids))
         if allowed_masks is not None:
@@ -1304,17 +1353,23 @@ class HybridRetriever(SparseRetrieval):
                 raise ValueError(f"collapse: a sequence of group labels is aligned with the dense index ({len(db_ids)} documents), got {len(labels)}")
             group_of = dict(zip(db_ids, labels))
         sparse_query_vecs, dense_query_vecs, qids = self._generate_query_vecs(q_loader)
-        sparse_res, sparse_stats = self._retrieve_collapsed(sparse_query_vecs, qids, group_of, threshold, topk, s_filt)
+        sparse_res, sparse_stats, *sparse_hits = self._retrieve_collapsed(sparse_query_vecs, qids, group_of, threshold, topk, s_filt, hits=hits)
         keys, table = self.dense_index.collapse_keys(group_of)
         q = _dense_queries(dense_query_vecs, self._dev)
-        scores, _, gkeys, counts, route = self.dense_index.index.search_collapsed(q, topk, keys, **_collapse_filter(d_filt))
+        found = self.dense_index.index.search_collapsed(q, topk, keys, hits=hits, **_collapse_filter(d_filt))
+        scores, _, gkeys, counts, route = found[:5]
         dense_res = RunResult(qids, to_host(scores), to_host(gkeys.to(torch.int64)), IdTable(table), to_host(counts))
-        sparse_stats["collapse_dense"] = route_stats(route)
+        sparse_stats["collapse_dense"] = _collapse_stats(route)
         with open(os.path.join(self.sparse_out_dir, "q_stats.json"), "w") as handler:
             json.dump(sparse_stats, handler)
         sparse_res.dump(os.path.join(self.sparse_out_dir, "run.json"))
         dense_res.dump(os.path.join(self.dense_out_dir, "run.json"))
-        return sparse_res, dense_res
+        if hits is None:
+            return sparse_res, dense_res
+        dense_hits = _hits_run(qids, found[5], self.dense_index.run_table())
+        _dump_hits_run(sparse_hits[0], self.sparse_out_dir)
+        _dump_hits_run(dense_hits, self.dense_out_dir)
+        return sparse_res, dense_res, sparse_hits[0], dense_hits
 
     def _position_maps(self):
         """The two indexes number documents independently: (dense position -> sparse position, -1 where the inverted index has no

@@ -5,7 +5,7 @@ the HIP kernels (csrc/dense_score.hip, csrc/sparse_cert.hip, csrc/sparse_score.h
 The reference-shaped classes in indexer.py are built on top of these.
 
 What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, topk_merge, hybrid_union,
-hybrid_rank, topk_collapse).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
+hybrid_rank, topk_collapse, group_members, segment_topm).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
 the status checked under that name); a filtered variant of an entry is the same call with "_subset" / "_masked" appended to the name
 and the filter's two arguments spliced in where the header puts them (_filter_args).  Each class checks its queries in one place
 (DenseIndexHIP._queries, SparseIndexHIP._query_csr), the range searches share _thresholds, and add_host_rows / add_npy_file share
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .doc_filter import (_call, _mask_words, _ptr, _subset, _to_dev, _valid, allowed_positions, doc_list_from_mask,  # noqa: F401  (re-exported)
+from .doc_filter import (_call, _cuda_device, _mask_words, _ptr, _subset, _to_dev, _valid, allowed_positions, doc_list_from_mask,  # noqa: F401  (re-exported)
                          doc_mask_from_list, doc_mask_remap, mask_argument, mask_on_device, one_filter, pack_doc_mask, pack_doc_masks,
                          query_group_argument, read_allowed_ids_file)
 
@@ -407,7 +407,8 @@ class DenseIndexHIP:
         self._call("sr_dense_range_fill" + suffix, _ptr(queries), queries.shape[0], _ptr(thr), *spliced, _ptr(lims), _ptr(scores), _ptr(ids), n)
         return scores[:n], ids[:n]
 
-    def search_collapsed(self, queries, k, keys, depths=None, fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None):
+    def search_collapsed(self, queries, k, keys, depths=None, fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None,
+                         hits=None, members=None):
         """The top-k distinct groups of every query, each represented and scored by its best passage (MaxP / field collapsing;
         collapse.py).  keys: int32 [id_end] tensor / array, the group key >= 0 of every document index.  Returns
         (scores fp32 [nq, k], ids int64 [nq, k] the best passages, keys int32 [nq, k], counts int32 [nq]) as cuda tensors, padded with
@@ -422,10 +423,17 @@ class DenseIndexHIP:
         Scores: every returned score is bit for bit score_pairs of (query, returned passage) and the ranking is by those scores.  Later
         rounds run on small sub-batches, and a batch of <= 64 queries otherwise accumulates in another order; the driver therefore
         switches set_batch_invariant(True) on for the duration of the call - every search of every round then accumulates in the
-        pair scorer's order - and puts the caller's setting back afterwards."""
+        pair scorer's order - and puts the caller's setting back afterwards.
+        hits=m (1 <= m <= 64; None: off, the 5-tuple above unchanged): the tuple gains a sixth element (hit_scores fp32 [nq, k, m],
+        hit_ids int64 [nq, k, m], hit_counts int32 [nq, k]) - for every returned group its passages that the call's filter allows for
+        the query, by (score descending, id ascending), cut to m, padded with (-FLT_MAX, -1); hit_counts is the number of such
+        passages before the cut (0 for a padding slot), min(hit_counts, m) entries of a list are hits, and hits[.., 0] is the group's
+        representative, id and score bits.  Scores are score_pairs', computed inside the same batch-invariant scope; sub-batches
+        are sized from fallback_bytes (collapse.group_hits).  members (None: built from keys per call): collapse.member_table(keys),
+        prepared once.  stats gains "mean_hits", the mean number of hits returned per returned group."""
         from .collapse import dense_search_collapsed
         return dense_search_collapsed(self, queries, k, keys, depths=depths, fallback_bytes=fallback_bytes, subset=subset, mask=mask,
-                                      masks=masks, query_group=query_group)
+                                      masks=masks, query_group=query_group, hits=hits, members=members)
 
     def score_pairs(self, queries, cand_indptr, cand_ids):
         """Exact scores of given (query, document) pairs: queries fp32 cuda [nq, dim]; the candidates of query q are
@@ -659,16 +667,19 @@ class SparseIndexHIP:
         return lims, scores, ids
 
     def search_collapsed(self, q_indptr, q_cols, q_vals, k, keys, threshold=0.0, id_base=0, id_stride=1, depths=None, fallback_bytes=1 << 30,
-                         subset=None, mask=None, masks=None, query_group=None):
+                         subset=None, mask=None, masks=None, query_group=None, hits=None, members=None):
         """The top-k distinct groups of every query, each represented and scored by its best passage (collapse.py):
         DenseIndexHIP.search_collapsed on this head.  Queries, threshold, id_base / id_stride as for `search` - only documents with
         score > threshold are ranked; keys int32 is indexed by the ids the search returns (id_base + position * id_stride), so it holds
         id_base + (n_docs - 1) * id_stride + 1 entries; the search's counts are handed to the device step.  Filters as for `search` /
-        `search_grouped`, one at most.  Returns (scores, ids, keys, counts, stats) as there."""
+        `search_grouped`, one at most.  Returns (scores, ids, keys, counts, stats) as there.  hits=m: the sixth element (hit_scores,
+        hit_ids, hit_counts) as there - a hit must also score > threshold, the padding is (0, -1), ids are id_base + position *
+        id_stride, scores sr_sparse_score_pairs'.  members (None: built per call): collapse.member_table of the keys BY DOCUMENT
+        POSITION (keys[id_base + id_stride * arange(n_docs)]), the numbering of this head's bitmaps and pair scorer."""
         from .collapse import sparse_search_collapsed
         return sparse_search_collapsed(self, q_indptr, q_cols, q_vals, k, keys, threshold=threshold, id_base=id_base, id_stride=id_stride,
                                        depths=depths, fallback_bytes=fallback_bytes, subset=subset, mask=mask, masks=masks,
-                                       query_group=query_group)
+                                       query_group=query_group, hits=hits, members=members)
 
     def score_pairs(self, q_indptr, q_cols, q_vals, cand_indptr, cand_ids):
         """Exact scores of given (query, document) pairs: queries as for `search`, candidates as for DenseIndexHIP.score_pairs (ids =
@@ -844,3 +855,150 @@ def topk_collapse(scores, ids, keys, k, counts=None, exhaustive=False):
     p = [_ptr(t) for t in keep]
     _call(dev, "sr_topk_collapse", p[0], p[1], _ptr(counts), nq, row_len, 1 if exhaustive else 0, p[2], keys.numel(), k, *p[3:])
     return out_s, out_i, out_k, out_c, done
+
+
+def member_table_argument(members):
+    """The host check of a member table (collapse.member_table): (uniq_keys int32 [G], member_indptr int64 [G + 1], member_ids int64 [n])
+    as tensors, as given.  Touches no device."""
+    if not isinstance(members, (tuple, list)) or len(members) != 3 or not all(torch.is_tensor(t) for t in members):
+        raise ValueError("members must be the (uniq_keys, member_indptr, member_ids) tensors collapse.member_table returns")
+    uniq, indptr, ids = members
+    if uniq.dtype != torch.int32 or indptr.dtype != torch.int64 or ids.dtype != torch.int64 or uniq.dim() != 1 or indptr.dim() != 1 or ids.dim() != 1:
+        raise ValueError(f"members must be 1-D (int32, int64, int64) tensors, got {uniq.dtype} {tuple(uniq.shape)}, {indptr.dtype} "
+                         f"{tuple(indptr.shape)}, {ids.dtype} {tuple(ids.shape)}")
+    if indptr.numel() != uniq.numel() + 1:
+        raise ValueError(f"member_indptr must hold one offset more than there are keys ({uniq.numel()} + 1), got {indptr.numel()}")
+    return uniq, indptr, ids
+
+
+def _members_call(name, slot_keys, members, filt, tail):
+    """One of the sr_group_members pair: slot_keys int32 [nq, kg] and the member table on one device; filt None, (words int32 [W], n_bits)
+    or (words int32 [G, W], n_bits, group ids int32 [nq] or None); tail: the entry's own last arguments."""
+    uniq, indptr, ids = members
+    dev = slot_keys.device
+    nq, kg = slot_keys.shape
+    n_masks, n_bits, words, groups = 0, 0, None, None
+    if filt is not None:
+        words, n_bits = filt[0], int(filt[1])
+        groups = filt[2] if len(filt) > 2 else None
+        n_masks = 1 if words.dim() == 1 else int(words.shape[0])
+        if words.shape[-1] != (n_bits + 31) // 32:
+            raise ValueError(f"{n_bits} bits take {(n_bits + 31) // 32} words per mask, got {words.shape[-1]}")
+        if groups is not None and (groups.dim() != 1 or groups.numel() != nq):
+            raise ValueError(f"query_group must hold one group id per query ({nq}), got {tuple(groups.shape)}")
+        if groups is None and n_masks != 1:
+            raise ValueError(f"{n_masks} masks need a query_group")
+    keep = [_valid(t) for t in (slot_keys, uniq, indptr, ids)] + [None if t is None else _valid(t) for t in (words, groups)]
+    p = [_ptr(t) for t in keep]
+    _call(dev, name, p[0], nq, kg, p[1], uniq.numel(), p[2], p[3], ids.numel(), p[4], n_masks, n_bits, p[5], *tail)
+
+
+def _members_arguments(slot_keys, members, filt):
+    """The checks of group_members_count / _fill that need no device, then everything on slot_keys' device."""
+    uniq, indptr, ids = member_table_argument(members)
+    if not torch.is_tensor(slot_keys) or slot_keys.dtype != torch.int32 or slot_keys.dim() != 2:
+        raise ValueError("slot_keys must be an int32 [nq, kg] tensor (the keys a collapsed search returns)")
+    _lib.require_gpu()
+    if not slot_keys.is_cuda:
+        raise ValueError("slot_keys must be a cuda tensor")
+    dev = slot_keys.device
+    members = tuple(t.to(dev).contiguous() for t in (uniq, indptr, ids))
+    if filt is not None:
+        words = filt[0].to(dev).contiguous()
+        words = words if words.dtype == torch.int32 else words.view(torch.int32)
+        groups = filt[2] if len(filt) > 2 else None
+        if groups is not None:                      # an id that does not fit int32 must not wrap into range
+            groups = _to_dev(groups, torch.int64, dev).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        filt = (words, int(filt[1]), groups)
+    return slot_keys.contiguous(), members, filt
+
+
+def group_members_count(slot_keys, members, filt=None):
+    """The allowed members of every (query, slot) of a collapsed result, first half (sr_group_members_count, csrc/group_hits.hip):
+    slot_keys int32 cuda [nq, kg] (negative: padding); members = collapse.member_table(...); filt None (no filter), (words int32 [W],
+    n_bits) one bitmap for all queries, or (words int32 [G, W], n_bits, query_group [nq]) one per filter group.  Returns (indptr int64
+    [nq * kg + 1] on the device, total): the exclusive scan in slot order of the slots' allowed members.  A key absent from the table,
+    a group id outside [0, G), a member id outside the mask: ValueError naming the first."""
+    slot_keys, members, filt = _members_arguments(slot_keys, members, filt)
+    indptr = torch.empty((slot_keys.numel() + 1,), dtype=torch.int64, device=slot_keys.device)
+    total = ctypes.c_int64(0)
+    _members_call("sr_group_members_count", slot_keys, members, filt, (_ptr(indptr), ctypes.byref(total)))
+    return indptr, total.value
+
+
+def group_members_fill(slot_keys, members, indptr, total, filt=None):
+    """Second half (sr_group_members_fill) for the inputs and the indptr of a preceding group_members_count: ids int64 [total], the allowed
+    members of slot s at indptr[s] .. indptr[s + 1], ascending."""
+    slot_keys, members, filt = _members_arguments(slot_keys, members, filt)
+    indptr = _to_dev(indptr, torch.int64, slot_keys.device)
+    if indptr.dim() != 1 or indptr.numel() != slot_keys.numel() + 1:
+        raise ValueError(f"expected an indptr of {slot_keys.numel() + 1} entries, got {tuple(indptr.shape)}")
+    total = int(total)
+    out = torch.empty((max(1, total),), dtype=torch.int64, device=slot_keys.device)
+    _members_call("sr_group_members_fill", slot_keys, members, filt, (_ptr(indptr), _ptr(out), total))
+    return out[:total]
+
+
+def group_members(slot_keys, members, filt=None):
+    """group_members_count, then group_members_fill: (indptr int64 [nq * kg + 1], ids int64 [total])."""
+    indptr, total = group_members_count(slot_keys, members, filt)
+    return indptr, group_members_fill(slot_keys, members, indptr, total, filt)
+
+
+MAX_HITS = 64               # sr_segment_topm keeps the running best one per lane of a wave
+
+
+def hits_argument(who, m):
+    """m of a top-m selection as an int in [1, MAX_HITS], or ValueError.  Touches no device."""
+    try:
+        mm = int(m)
+        if mm != m or isinstance(m, bool):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: the number of hits must be an integer in [1, {MAX_HITS}], got {m!r}") from None
+    if not 1 <= mm <= MAX_HITS:
+        raise ValueError(f"{who}: the number of hits must be an integer in [1, {MAX_HITS}], got {m!r}")
+    return mm
+
+
+def segment_topm(scores, ids, seg_indptr, m, threshold=None, pad_score=-3.402823466e38):
+    """The m best entries of every segment of a scored CSR (sr_segment_topm, csrc/group_hits.hip): scores fp32 / ids int64 [total],
+    segment s at seg_indptr[s] .. [s + 1] (int64 [n_segs + 1], from 0, never decreasing, ending at total), any length, ids in any order.
+    Order: score descending (-0.0 = +0.0, read back as +0.0), then id ascending; threshold (None: off): only entries with score >
+    threshold.  Returns (scores fp32 [n_segs, m], ids int64 [n_segs, m], counts int32 [n_segs]) on the device: the best min(m, count)
+    entries, then (pad_score, -1); counts = the entries that took part, not cut to m.  1 <= m <= 64.  m, the shapes and - where
+    seg_indptr is given on the host - its content are checked before anything touches a device; a seg_indptr on the device is checked
+    there: ValueError either way."""
+    m = hits_argument("segment_topm", m)
+    if not torch.is_tensor(seg_indptr):
+        seg_indptr = np.asarray(seg_indptr)
+    host_indptr = None if torch.is_tensor(seg_indptr) and seg_indptr.is_cuda else np.asarray(seg_indptr)      # None: checked on the device
+    if len(seg_indptr.shape) != 1 or seg_indptr.shape[0] < 1:
+        raise ValueError("segment_topm: seg_indptr must be 1-D with n_segs + 1 >= 1 offsets")
+    if len(scores.shape) != 1 or tuple(ids.shape) != tuple(scores.shape):
+        raise ValueError(f"segment_topm: expected 1-D scores and ids of one length, got {tuple(scores.shape)} and {tuple(ids.shape)}")
+    if host_indptr is not None:
+        if host_indptr.dtype.kind not in "iu":
+            raise ValueError(f"segment_topm: seg_indptr must hold integers, got {host_indptr.dtype}")
+        if int(host_indptr[0]) != 0:
+            raise ValueError(f"segment_topm: seg_indptr must start at 0, got {int(host_indptr[0])}")
+        down = np.flatnonzero(np.diff(host_indptr.astype(np.int64)) < 0)
+        if down.size:
+            raise ValueError(f"segment_topm: seg_indptr decreases behind segment {int(down[0])}")
+        if int(host_indptr[-1]) != scores.shape[0]:
+            raise ValueError(f"segment_topm: seg_indptr ends at {int(host_indptr[-1])}, scores holds {scores.shape[0]} entries")
+    _lib.require_gpu()
+    dev = scores.device if torch.is_tensor(scores) and scores.is_cuda else _cuda_device()
+    scores, ids = _to_dev(scores, torch.float32, dev), _to_dev(ids, torch.int64, dev)
+    seg_indptr = _to_dev(seg_indptr, torch.int64, dev)
+    n_segs = seg_indptr.numel() - 1
+    if host_indptr is None and int(seg_indptr[-1]) != scores.numel():       # the kernel trusts seg_indptr[n_segs] for the arrays' extent
+        raise ValueError(f"segment_topm: seg_indptr ends at {int(seg_indptr[-1])}, scores holds {scores.numel()} entries")
+    out_s = torch.empty((n_segs, m), dtype=torch.float32, device=dev)
+    out_i = torch.empty((n_segs, m), dtype=torch.int64, device=dev)
+    out_c = torch.empty((n_segs,), dtype=torch.int32, device=dev)
+    keep = [_valid(t) for t in (scores, ids, seg_indptr, out_s, out_i, out_c)]
+    p = [_ptr(t) for t in keep]
+    _call(dev, "sr_segment_topm", p[0], p[1], p[2], n_segs, m, 0 if threshold is None else 1, 0.0 if threshold is None else float(threshold),
+          float(pad_score), p[3], p[4], p[5])
+    return out_s, out_i, out_c
