@@ -680,6 +680,32 @@ int sr_hybrid_rank(const int64_t* d_cand_indptr, const int64_t* d_dpos, const in
                    float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, int32_t* d_out_certified,
                    float* d_out_threshold, sr_stream stream);
 
+/* -------------------------------------------------------------- rank fusion ---
+ * sr_rank_fuse (csrc/rank_fuse.hip): per query the k best distinct documents of n_lists ranked lists by a fused score
+ * that is defined on the lists alone, so the result is exact by definition (no certificate, no pair scorer).  No reference counterpart.
+ * d_ids int64 [n_lists, nq, depth] (id < 0 = padding), d_counts int32 [n_lists, nq] the valid prefix of each row (NULL: depth), d_scores
+ * fp32 [n_lists, nq, depth], read only by SR_FUSE_MINMAX (else may be NULL).  Entry (l, q, r) is valid iff r < counts[l, q] and
+ * ids[l, q, r] >= 0; its rank is r + 1, the slot's place in the row.
+ *   SR_FUSE_RRF     contrib = f32( w_l / f32( c + f32(r + 1) ) ): one rounded add, one correctly rounded division.
+ *   SR_FUSE_MINMAX  over the valid entries of (l, q): mn, mx the smallest and largest score, span = f32(mx - mn);
+ *                   norm = f32( f32(s - mn) / span ) where span > 0, else 1.0f; contrib = f32(w_l * norm).  Scores are finite (not checked).
+ * The fused score of a document starts from +0.0f and adds the contributions of the lists that hold it in ascending l, one rounded fp32
+ * add each (compiled with contraction off).  A document only in lists of weight 0 is still a candidate, with fused 0.0.  Result: the k
+ * best distinct documents by (fused descending, id ascending) in d_out_scores fp32 / d_out_ids int64 [nq, k] (padding -FLT_MAX, -1),
+ * d_out_counts int32 [nq] = min(k, distinct documents), and, unless NULL, d_out_ranks int32 [nq, k, n_lists]: the 1-based rank of the hit
+ * in each list, 0 = absent (and in padding).  No atomic decides an output byte: two calls return the same bytes.
+ * h_weights is a HOST array [n_lists], finite and >= 0; c (RRF only) finite and > -1.  1 <= n_lists <= 8, 1 <= depth <= sr_max_topk(),
+ * n_lists * depth <= 2 * sr_max_topk(), 1 <= k <= sr_max_topk(): anything beyond is SR_ERR_UNSUPPORTED.  A null pointer, a bad nq, weight,
+ * c or method, or SR_FUSE_MINMAX without scores: SR_ERR_INVALID before any device work.  nq = 0 is legal.  Found on the device
+ * (SR_ERR_INVALID, sr_last_error() names the first offender as id, list, query, entry; the outputs are then not to be used and the
+ * library stays usable): a valid id >= 2^32 (the keys hold 32 id bits), and an id that occurs twice among the valid entries of one
+ * (l, q) row.  Waits for the stream once, to read the status.                                                                    */
+#define SR_FUSE_RRF 0
+#define SR_FUSE_MINMAX 1
+int sr_rank_fuse(const int64_t* d_ids, const int32_t* d_counts, const float* d_scores, int n_lists, int64_t nq, int64_t depth,
+                 int method, const float* h_weights, float c, int k, float* d_out_scores, int64_t* d_out_ids,
+                 int32_t* d_out_counts, int32_t* d_out_ranks, sr_stream stream);
+
 /* ---------------------------------------------------------------- encoder ---
  * Replaces LlamaBiDense / LlamaBiSparse .encode / .query_encode / .doc_encode
  * (scaling_retriever/modeling/llm_encoder.py:66-70,186-196,424-443) and the

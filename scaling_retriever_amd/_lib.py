@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("SR_HIP_LIB") or os.path.join(_HERE, "libsr_hip.so")  
 
 SR_OK, SR_ERR_INVALID, SR_ERR_HIP, SR_ERR_NOMEM, SR_ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 SR_DTYPE_F32, SR_DTYPE_BF16, SR_DTYPE_F16 = 0, 1, 2
+SR_FUSE_RRF, SR_FUSE_MINMAX = 0, 1              # sr_rank_fuse's methods
 
 c_void_p, c_int, c_int32, c_int64, c_float, c_char_p = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
                                                          ctypes.c_int64, ctypes.c_float, ctypes.c_char_p)
@@ -117,6 +118,8 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
     "sr_hybrid_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p,
                                c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_rank_fuse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, ctypes.POINTER(c_float), c_float, c_int, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_topk_collapse": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     "sr_group_members_count": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,

@@ -261,6 +261,10 @@ class ShardedSparseRetriever:
         raise NotImplementedError("ShardedSparseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "
                                   "doc-sharded index")
 
+    def retrieve_rank_fused(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetriever.retrieve_rank_fused: rank fusion of the two heads' lists is not offered on a "
+                                  "doc-sharded index (scoring.rank_fuse takes any merged lists)")
+
 
 class ShardedDenseRetriever:
     """Each rank holds rows rank, rank+W, ... of the corpus in its own HBM (DenseIndexHIP with
@@ -298,3 +302,7 @@ class ShardedDenseRetriever:
     def search_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedDenseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "
                                   "doc-sharded index")
+
+    def retrieve_rank_fused(self, *args, **kwargs):
+        raise NotImplementedError("ShardedDenseRetriever.retrieve_rank_fused: rank fusion of the two heads' lists is not offered on a "
+                                  "doc-sharded index (scoring.rank_fuse takes any merged lists)")

@@ -1158,6 +1158,10 @@ class ShardedSparseRetrieval(SparseRetrieval):
         raise NotImplementedError("ShardedSparseRetrieval.search_fused: the exact fused search is not offered on a doc-sharded index; "
                                   "use HybridRetriever over one merged index")
 
+    def retrieve_rank_fused(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetrieval.retrieve_rank_fused: rank fusion of the two heads' lists is not offered on a "
+                                  "doc-sharded index; use HybridRetriever over one merged index, or eval_fuse.py on the run files")
+
     def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when
         `q_loader.replicated` is set."""
@@ -1421,6 +1425,33 @@ class HybridRetriever(SparseRetrieval):
         tie = torch.where(spos >= 0, spos, int(s2d.numel()) + dpos)
         fused_res = ranked_run(qids, fused_scores(dense_s, sparse_s, weights), dpos, tie, indptr, self.dense_index.run_table(), topk=topk)
         fused_dir = os.path.join(os.path.dirname(self.sparse_out_dir), "fused")
+        os.makedirs(fused_dir, exist_ok=True)
+        fused_res.dump(os.path.join(fused_dir, "run.json"))
+        return sparse_res, dense_res, fused_res
+
+    def retrieve_rank_fused(self, q_loader, topk, method="rrf", c=60.0, weights=(1.0, 1.0), fused_topk=None, threshold=0., allowed_ids=None,
+                            allowed_masks=None, query_group=None, collapse=None):
+        """`retrieve` (the same two runs, the same bytes) plus {out_dir}/rank_fused/run.json: the two top-`topk` lists fused on the
+        lists alone (fusion.fuse_hybrid_lists over scoring.rank_fuse; no pair is scored again and no weight needs tuning to the heads'
+        score scales).  method "rrf": weights[l] / (c + rank) summed over the lists that hold the document; "minmax": weights[l] * the
+        score normalised to [0, 1] over its list.  weights = (w_dense, w_sparse), finite and >= 0.  The fused run holds the fused_topk
+        (default topk; at most sr_max_topk(), as is topk) best documents by (fused descending, retrieve_fused's tie: sparse-index
+        position ascending, documents without a posting last).  Filters as for retrieve: the two restricted lists are fused.  Every
+        document of the inverted index must be in the dense index (KeyError).  Returns (sparse_res, dense_res, fused_res)."""
+        from .collapse import not_under_collapse
+        not_under_collapse("HybridRetriever.retrieve_rank_fused", collapse)
+        from . import fusion, hybrid, scoring
+        hybrid.check_arguments(topk, weights)
+        k, _, weights, c = scoring.rank_fuse_arguments(2, topk if fused_topk is None else fused_topk, method, weights, c)
+        _, _, qids, sparse_res, dense_res = self._retrieve_both(q_loader, topk, threshold, allowed_ids=allowed_ids, allowed_masks=allowed_masks,
+                                                                query_group=query_group)
+        d2s, s2d = self._position_maps()
+        dp, sp, ds, ss = (torch.from_numpy(x).to(self._dev) for x in (dense_res.positions, sparse_res.positions, dense_res.scores, sparse_res.scores))
+        sc = None if sparse_res.counts is None else torch.from_numpy(sparse_res.counts).to(self._dev)
+        scores, dpos, counts = fusion.fuse_hybrid_lists(dp, sp, sc, d2s, s2d, k, method=method, weights=weights, c=c, dense_scores=ds,
+                                                        sparse_scores=ss)
+        fused_res = RunResult(qids, to_host(scores), to_host(dpos), self.dense_index.run_table(), to_host(counts))
+        fused_dir = os.path.join(os.path.dirname(self.sparse_out_dir), "rank_fused")
         os.makedirs(fused_dir, exist_ok=True)
         fused_res.dump(os.path.join(fused_dir, "run.json"))
         return sparse_res, dense_res, fused_res

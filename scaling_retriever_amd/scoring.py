@@ -814,6 +814,83 @@ def hybrid_rank(cand_indptr, dpos, spos, tie, dense_scores, sparse_scores, weigh
     return out_s, out_i, counts, cert, thr
 
 
+FUSE_METHODS = {"rrf": _lib.SR_FUSE_RRF, "minmax": _lib.SR_FUSE_MINMAX}
+FUSE_MAX_LISTS = 8
+
+
+def rank_fuse_arguments(n_lists, k, method, weights, c):
+    """The host checks of rank_fuse (touch no device) -> (k, method constant, weights as floats, c).  ValueError otherwise."""
+    if method not in FUSE_METHODS:
+        raise ValueError(f"rank_fuse: method must be one of {sorted(FUSE_METHODS)}, got {method!r}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"rank_fuse: k must be an integer >= 1, got {k!r}")
+    if not 1 <= n_lists <= FUSE_MAX_LISTS:
+        raise ValueError(f"rank_fuse: 1 to {FUSE_MAX_LISTS} lists are fused, got {n_lists}")
+    weights = [1.0] * n_lists if weights is None else weights
+    try:
+        with np.errstate(over="ignore"):                        # a value beyond float32 becomes inf and is refused below
+            w = [float(np.float32(float(x))) for x in weights]
+            c = float(np.float32(float(c)))
+    except (TypeError, ValueError):
+        raise ValueError(f"rank_fuse: weights and c must be numbers, got {weights!r} and {c!r}") from None
+    if len(w) != n_lists:
+        raise ValueError(f"rank_fuse: one weight per list ({n_lists}), got {len(w)}")
+    if not all(np.isfinite(x) and x >= 0 for x in w):
+        raise ValueError(f"rank_fuse: the weights must be finite (as float32) and >= 0, got {weights!r}")
+    if method == "rrf" and not (np.isfinite(c) and c > -1):
+        raise ValueError(f"rank_fuse: c must be finite and > -1, got {c!r}")
+    return int(k), FUSE_METHODS[method], w, c
+
+
+def rank_fuse(ids, k, counts=None, scores=None, method="rrf", weights=None, c=60.0, return_ranks=False):
+    """Rank fusion of L ranked lists per query on the device (sr_rank_fuse, csrc/rank_fuse.hip): ids int64 [L, nq, depth] cuda (or a list
+    / tuple of L tensors [nq, depth] of one shape; id < 0 = padding), counts int32 [L, nq] the valid prefix of each row (None: depth),
+    scores fp32 like ids (read by method="minmax" only).  method "rrf": sum_l weights[l] / (c + rank_l); "minmax": sum_l weights[l] *
+    (s - min_l) / (max_l - min_l) over each list's valid entries (1.0 where max_l == min_l); the sum runs in list order, one rounded fp32
+    add each.  weights (None: all ones) finite and >= 0.  Returns (scores fp32 [nq, k] padded with -FLT_MAX, ids int64 [nq, k] padded with
+    -1, counts int32 [nq]) by (fused descending, id ascending), and with return_ranks=True also ranks int32 [nq, k, L]: the 1-based rank
+    of the hit in each list, 0 = absent.  L <= 8, depth and k <= sr_max_topk(), L * depth <= 2 * sr_max_topk().  Argument errors are
+    ValueErrors before the library is asked for a device; an id >= 2^32 or twice in one row: ValueError naming list, query, entry, id."""
+    def stacked(x, what):
+        if isinstance(x, (list, tuple)):
+            if not x or not all(torch.is_tensor(t) for t in x) or any(t.shape != x[0].shape for t in x):
+                raise ValueError(f"rank_fuse: {what} must be tensors of one shape [nq, depth]")
+            x = torch.stack(list(x))
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise ValueError(f"rank_fuse: expected {what} [n_lists, nq, depth], got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        return x
+    ids = stacked(ids, "ids")
+    L, nq, depth = ids.shape
+    k, method_id, w, c = rank_fuse_arguments(L, k, method, weights, c)
+    if scores is not None:
+        scores = stacked(scores, "scores")
+        if scores.shape != ids.shape:
+            raise ValueError(f"rank_fuse: scores {tuple(scores.shape)} and ids {tuple(ids.shape)} must share one shape")
+    elif method == "minmax":
+        raise ValueError("rank_fuse: method 'minmax' needs the scores of the lists")
+    if counts is not None:
+        if isinstance(counts, (list, tuple)):
+            counts = torch.stack([torch.as_tensor(t) for t in counts])
+        if not torch.is_tensor(counts) or tuple(counts.shape) != (L, nq):
+            raise ValueError(f"rank_fuse: expected counts [{L}, {nq}], got {tuple(counts.shape) if torch.is_tensor(counts) else type(counts).__name__}")
+    if depth < 1:
+        raise ValueError("rank_fuse: the lists hold no entry (depth = 0)")
+    _lib.require_gpu()
+    dev = _cuda_device(ids)
+    ids = ids.to(device=dev, dtype=torch.int64).contiguous()
+    scores = None if scores is None else _valid(scores.to(device=dev, dtype=torch.float32).contiguous())
+    counts = None if counts is None else _valid(counts.to(device=dev, dtype=torch.int32).contiguous())
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_c = torch.empty((nq,), dtype=torch.int32, device=dev)
+    ranks = torch.empty((nq, k, L), dtype=torch.int32, device=dev) if return_ranks else None
+    keep = [_valid(t) for t in (ids, out_s, out_i, out_c)]
+    keep_r = None if ranks is None else _valid(ranks)
+    _call(dev, "sr_rank_fuse", _ptr(keep[0]), _ptr(counts), _ptr(scores), L, nq, depth, method_id, (ctypes.c_float * L)(*w), c, k,
+          _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(keep_r))
+    return (out_s, out_i, out_c, ranks) if return_ranks else (out_s, out_i, out_c)
+
+
 def collapse_keys_argument(keys):
     """The host check of a group-key table (collapse.py): a 1-D int32 tensor / array, as given.  Touches no device."""
     if not torch.is_tensor(keys) and not isinstance(keys, np.ndarray):
