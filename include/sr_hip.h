@@ -800,7 +800,8 @@ int sr_model_last_hidden(sr_model* m, float* d_out, int64_t capacity_rows, int64
 int sr_model_destroy(sr_model* m);
 
 /* peft merge_and_unload for one Linear (llm_encoder.py:116-122,502-508):
- * W[out,in] += scale * B[out,r] @ A[r,in], fp32 in place, scale = alpha / r. */
+ * W[out,in] += scale * B[out,r] @ A[r,in], fp32 in place, scale = alpha / r.  One grid row per output feature:
+ * out_features beyond the device's maxGridSize[1] is SR_ERR_INVALID, found by the argument check ("grid limit").  */
 int sr_lora_merge(float* d_W, const float* d_A, const float* d_B, int64_t out_features,
                   int64_t in_features, int32_t r, float scale, sr_stream stream);
 
@@ -875,6 +876,42 @@ int sr_gemm_bf16(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t
  * scaled by powers of two, d_a_scale [M] / d_w_scale [N] the inverse scales; C fp32 [M, N] += (A W^T) a_scale[m] w_scale[n]. */
 int sr_gemm_f16_scaled(const void* d_A, const void* d_W, int32_t M, int32_t N, int32_t K, const float* d_a_scale,
                        const float* d_w_scale, float* d_C, sr_stream stream);
+/* Test-only hook: one of the buffers that loading (sr_model_set_weight, sr_model_finalize) and sr_model_create's RoPE tables left
+ * on the device, copied to the host as it stands, in the INTERNAL row order (tests/model_load_cases.py restates the row maps and the
+ * conversions; tests/test_model_load_gpu.py compares).  It launches no kernel and changes nothing: the model's mutex, one
+ * hipDeviceSynchronize and one device-to-host copy per call; the product path never calls it.  Works before and after
+ * sr_model_finalize; after it an fp16-plane matrix reports the 2 or 3 segments finalize left.
+ * layer = -1: the model-level buffers; 0 .. num_layers - 1: that layer's.  buffer / kind:
+ *   SR_READOUT_EMBED     F32 [vocab, hidden]                      SR_READOUT_NORM  F32 [hidden, 1]
+ *   SR_READOUT_ROPE_COS, SR_READOUT_ROPE_SIN   F32 [8192, head_dim / 2]
+ *   SR_READOUT_LM_HEAD [vocab, hidden], SR_READOUT_QKV [(nh + 2 nkv) hd, hidden], SR_READOUT_O [hidden, nh hd],
+ *   SR_READOUT_GATE_UP [2 intermediate, hidden] (gate / up interleaved in 16-row blocks), SR_READOUT_DOWN [hidden, intermediate]:
+ *       BF16 uint16 [rows, K];  PLANES uint16 [rows, n_seg K] (fp32_planes 2 / 3: 3 / 6 bf16 segments; 16: 3 or 2 fp16 segments);
+ *       W_INV F32 [rows, 1] (fp32_planes 16 only)
+ *   SR_READOUT_LN1, SR_READOUT_LN2   F32 [hidden, 1]
+ *   SR_READOUT_BIAS (attention_bias = 1)   F32 [(nh + 2 nkv) hd, 1] the values, BF16_AS_F32 their bf16 roundings held as fp32
+ * *n_bytes, *n_rows, *row_elems = the buffer's size, rows and elements per row.  h_dst NULL or capacity_bytes 0: the size only,
+ * otherwise capacity_bytes must hold it.  SR_ERR_INVALID: a null model or size pointer, a layer out of range, a buffer / kind this
+ * model does not hold (an lm_head on a dense model, planes with fp32_planes = 0, ...), a buffer too small.                        */
+#define SR_READOUT_EMBED 0
+#define SR_READOUT_LM_HEAD 1
+#define SR_READOUT_NORM 2
+#define SR_READOUT_ROPE_COS 3
+#define SR_READOUT_ROPE_SIN 4
+#define SR_READOUT_QKV 5
+#define SR_READOUT_O 6
+#define SR_READOUT_GATE_UP 7
+#define SR_READOUT_DOWN 8
+#define SR_READOUT_LN1 9
+#define SR_READOUT_LN2 10
+#define SR_READOUT_BIAS 11
+#define SR_READOUT_F32 0
+#define SR_READOUT_BF16 1
+#define SR_READOUT_PLANES 2
+#define SR_READOUT_W_INV 3
+#define SR_READOUT_BF16_AS_F32 4
+int sr_model_readout(sr_model* m, int32_t layer, int32_t buffer, int32_t kind, void* h_dst, int64_t capacity_bytes,
+                     int64_t* n_bytes, int64_t* n_rows, int64_t* row_elems);
 /* Test-only hooks: the other launches of the fp16-plane layer loop, each with the arguments the encoder fills.  Every call
  * validates its arguments before it touches a device (SR_ERR_INVALID).
  * sr_rows_split_f16: rows of d_src fp32 [T, K] -> d_planes fp16 [T, nseg K] = [f1 | f0 | f0] (nseg = 3) or [f1 | f0] (2) of

@@ -131,6 +131,8 @@ SIGNATURES = {
     "sr_model_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(SrModelConfig)]),
     "sr_model_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "sr_model_finalize": (c_int, [c_void_p]),
+    "sr_model_readout": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
+                                 ctypes.POINTER(c_int64)]),
     "sr_model_weight_segments": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int64, ctypes.POINTER(c_int64)]),
     "sr_model_fused_act_layers": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int64, ctypes.POINTER(c_int64)]),
     "sr_encode_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),

@@ -367,8 +367,9 @@ extern "C" int sr_model_set_weight(sr_model* m, const char* name, const void* d_
     return SR_ERR_INVALID;
 }
 
-// fp16-plane regime: a matrix whose g1 plane is all zero (bf16-valued weights: 8 significand bits always fit the fp16 plane g0
-// of their power-of-two scaled row, unless they lie ~2^-31 below the row maximum) is re-packed from [N, 3K] = [g0 | g1 | g0] to
+// fp16-plane regime: a matrix whose g1 plane is all zero (bf16-valued weights, always: 8 significand bits fit the fp16 plane g0
+// of their power-of-two scaled row, and where an element lies so far below the row maximum that g0 is subnormal and drops bits,
+// what it drops is at most 2^-25, which rounds to a zero g1 - tests/model_load_cases.py) is re-packed from [N, 3K] = [g0 | g1 | g0] to
 // [N, 2K] = [g0 | g0], out of place.  The GEMM's middle product f0 . g1 only added exact zeros to the fp32 accumulators (an MFMA
 // does not flush its C input), so the 2-segment GEMM - same k order for what remains - gives the same bits with 2/3 of the work.
 static int pack_f16_weights(sr_model* m, bf16_t*& w, int& nseg, bool lo_nz, int64_t rows, int64_t K) {
@@ -477,10 +478,75 @@ extern "C" int sr_model_fused_act_layers(sr_model* m, int32_t* out, int64_t capa
     return SR_OK;
 }
 
+// Test-only read-out of what loading left on the device (include/sr_hip.h): no kernel, one device-to-host copy per call.
+extern "C" int sr_model_readout(sr_model* m, int32_t layer, int32_t buffer, int32_t kind, void* h_dst, int64_t capacity_bytes,
+                                int64_t* n_bytes, int64_t* n_rows, int64_t* row_elems) {
+    SR_REQUIRE(m && n_bytes && n_rows && row_elems, "sr_model_readout: null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const sr_model_config& c = m->cfg;
+    const int64_t H = m->d.H, I = m->d.I, V = m->d.V, nq = m->d.nq, n_qkv = m->d.n_qkv, half = c.head_dim / 2;
+    const bool f16p = c.fp32_planes == SR_FP32_PLANES_F16;
+    const int plain = c.fp32_planes ? split_map_w(c.fp32_planes).n_seg : 0;       // plane segments outside the fp16-plane regime
+    // a weight matrix [rows, K] in its three forms; seg = its plane segments as they stand (fp16 planes: 3, or 2 once finalize packed it)
+    struct Matrix { const bf16_t* w; const bf16_t* planes; const float* inv; int64_t rows, K; int seg; };
+    const void* src = nullptr;
+    int64_t rows = 0, elems = 0, esize = 4;
+    auto matrix = [&](const Matrix& x) {
+        if (kind == SR_READOUT_BF16) { src = x.w; rows = x.rows; elems = x.K; esize = 2; }
+        else if (kind == SR_READOUT_PLANES) { src = x.planes; rows = x.rows; elems = x.K * (f16p ? x.seg : plain); esize = 2; }
+        else if (kind == SR_READOUT_W_INV) { src = x.inv; rows = x.rows; elems = 1; }
+    };
+    auto vec_f32 = [&](const float* p, int64_t n_, int64_t per_row) {
+        if (kind == SR_READOUT_F32) { src = p; rows = n_; elems = per_row; }
+    };
+    if (layer == -1) {
+        switch (buffer) {
+            case SR_READOUT_EMBED: vec_f32(m->embed, V, H); break;
+            case SR_READOUT_LM_HEAD: matrix(Matrix{m->lm_head, m->lm_head_s, m->lm_head_i, V, H, m->lm_head_seg}); break;
+            case SR_READOUT_NORM: vec_f32(m->norm_w, H, 1); break;
+            case SR_READOUT_ROPE_COS: vec_f32(m->rope_cos, m->max_pos, half); break;
+            case SR_READOUT_ROPE_SIN: vec_f32(m->rope_sin, m->max_pos, half); break;
+            default: break;
+        }
+    } else {
+        SR_REQUIRE(layer >= 0 && layer < c.num_layers, "sr_model_readout: layer %d outside [-1, %d)", layer, c.num_layers);
+        const LayerW& l = m->layers[(size_t)layer];
+        switch (buffer) {
+            case SR_READOUT_QKV: matrix(Matrix{l.wqkv, l.wqkv_s, l.wqkv_i, n_qkv, H, l.qkv_seg}); break;
+            case SR_READOUT_O: matrix(Matrix{l.wo, l.wo_s, l.wo_i, H, nq, l.o_seg}); break;
+            case SR_READOUT_GATE_UP: matrix(Matrix{l.wgu, l.wgu_s, l.wgu_i, 2 * I, H, l.gu_seg}); break;
+            case SR_READOUT_DOWN: matrix(Matrix{l.wdown, l.wdown_s, l.wdown_i, H, I, l.down_seg}); break;
+            case SR_READOUT_LN1: vec_f32(l.ln1, H, 1); break;
+            case SR_READOUT_LN2: vec_f32(l.ln2, H, 1); break;
+            case SR_READOUT_BIAS:
+                if (kind == SR_READOUT_F32) { src = l.bqkv; rows = n_qkv; elems = 1; }
+                else if (kind == SR_READOUT_BF16_AS_F32) { src = l.bqkv_r; rows = n_qkv; elems = 1; }
+                break;
+            default: break;
+        }
+    }
+    SR_REQUIRE(src, "sr_model_readout: layer %d has no buffer %d of kind %d in this model", layer, buffer, kind);
+    const int64_t bytes = rows * elems * esize;
+    *n_bytes = bytes;
+    *n_rows = rows;
+    *row_elems = elems;
+    if (!h_dst || capacity_bytes == 0) return SR_OK;         // size query
+    SR_REQUIRE(capacity_bytes >= bytes, "sr_model_readout: buffer too small");
+    SR_CHECK_HIP(hipDeviceSynchronize());                    // sr_model_set_weight converted on the caller's streams
+    SR_CHECK_HIP(hipMemcpy(h_dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
 extern "C" int sr_lora_merge(float* d_W, const float* d_A, const float* d_B, int64_t out_features, int64_t in_features,
                              int32_t r, float scale, sr_stream stream) {
     SR_REQUIRE(d_W && d_A && d_B && out_features > 0 && in_features > 0 && r > 0, "sr_lora_merge: bad argument");
     SR_REQUIRE(out_features < 65536 * 32, "sr_lora_merge: out_features too large");
+    // out_features is the grid's y dimension: what the device does not take is refused here, not by a failed launch
+    int dev = 0, max_y = 0;
+    SR_CHECK_HIP(hipGetDevice(&dev));
+    SR_CHECK_HIP(hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, dev));
+    SR_REQUIRE(out_features <= max_y, "sr_lora_merge: out_features %lld exceeds the device's grid limit maxGridSize[1] = %d",
+               (long long)out_features, max_y);
     hipLaunchKernelGGL(lora_merge_kernel, dim3((unsigned)ceil_div64(in_features, 256), (unsigned)out_features), dim3(256), 0,
                        (hipStream_t)stream, d_W, d_A, d_B, out_features, in_features, r, scale);
     SR_CHECK_LAUNCH();

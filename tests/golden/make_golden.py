@@ -28,8 +28,13 @@ What is pinned:
                   and world size patched) with a fake model that emits fixed [B, V] reps,
                   all-zero rows included, at world sizes 1 and 2: the per-term posting
                   arrays, doc_ids, nb_docs(), L0_d and the merged index are recorded.
+  * rope_hf.npz       transformers' LlamaRotaryEmbedding [3P]: inv_freq and cos / sin rows at positions up to 8191 for the
+                  Llama-3.2-1B, Llama-3.1-8B and Qwen2.5 RoPE parameters (it forms inv_freq in fp32; csrc/model_weights.hip
+                  rope_tables and the oracle form it in double and round once: up to 3 ulps apart).
+  * enc_rope_long.npz LlamaBiDense / LlamaBiSparse .doc_encode at L = 512 with the 1B RoPE parameters (inputs, outputs and
+                  r_autocast only): positions the other enc_* fixtures never reach.
 
-Usage:  python tests/golden/make_golden.py
+Usage:  python tests/golden/make_golden.py            (`index_build` / `rope` as the one argument: those fixtures only)
 """
 import json
 import os
@@ -384,13 +389,93 @@ def gen_index_build():
           "merged", out["merge01:nb_docs"])
 
 
+def gen_rope_hf():
+    """rope_hf.npz: transformers' LlamaRotaryEmbedding [3P] - inv_freq as it forms it (fp32 arithmetic, the llama3 scaling included)
+    and its cos / sin rows (first half of the duplicated head) at a few positions, for the RoPE parameters of Llama-3.2-1B,
+    Llama-3.1-8B and Qwen2.5 (tests/model_load_cases.py: ROPE_SETS, ROPE_POSITIONS)."""
+    from transformers import LlamaConfig
+    from transformers.models.llama.modeling_llama import LlamaRotaryEmbedding
+    sys.path.insert(0, os.path.dirname(OUT))
+    from model_load_cases import ROPE_POSITIONS, ROPE_SETS
+    ROPE_HF_POSITIONS = list(ROPE_POSITIONS)
+    out = {"positions": np.array(ROPE_HF_POSITIONS, np.int64)}
+    for name, s in ROPE_SETS.items():
+        hd = s["head_dim"]
+        kw = dict(vocab_size=32, hidden_size=2 * hd, intermediate_size=64, num_hidden_layers=1, num_attention_heads=2,
+                  num_key_value_heads=1, max_position_embeddings=16384, rope_theta=s["rope_theta"])
+        if s["rope_scaling"]:
+            kw["rope_scaling"] = dict(s["rope_scaling"])
+        cfg = LlamaConfig(**kw)
+        rot = LlamaRotaryEmbedding(config=cfg)
+        inv = rot.inv_freq.detach().clone()
+        assert inv.dtype == torch.float32 and inv.shape == (hd // 2,)
+        pos = torch.tensor([ROPE_HF_POSITIONS], dtype=torch.int64)
+        with torch.no_grad():
+            cos, sin = rot(torch.zeros(1, len(ROPE_HF_POSITIONS), 2 * hd), pos)
+        assert cos.dtype == torch.float32 and cos.shape == (1, len(ROPE_HF_POSITIONS), hd)
+        assert torch.equal(cos[..., :hd // 2], cos[..., hd // 2:]) and float(getattr(rot, "attention_scaling", 1.0)) == 1.0
+        out[f"{name}:inv_freq"] = inv.numpy()
+        out[f"{name}:cos"] = cos[0, :, :hd // 2].numpy()
+        out[f"{name}:sin"] = sin[0, :, :hd // 2].numpy()
+    np.savez_compressed(os.path.join(OUT, "rope_hf.npz"), **out)
+    print("rope_hf bytes", os.path.getsize(os.path.join(OUT, "rope_hf.npz")))
+
+
+# the widths of enc_tiny_a with the RoPE parameters of Llama-3.2-1B, at positions the other fixtures never reach (they stop at 70)
+ROPE_LONG_CFG = dict(vocab_size=512, hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2,
+                     num_key_value_heads=2, max_position_embeddings=16384, rope_theta=500000.0, rms_norm_eps=1e-5,
+                     tie_word_embeddings=True,
+                     rope_scaling={"rope_type": "llama3", "factor": 32.0, "low_freq_factor": 1.0, "high_freq_factor": 4.0,
+                                   "original_max_position_embeddings": 8192})
+
+
+def gen_enc_rope_long():
+    """enc_rope_long.npz: LlamaBiDense / LlamaBiSparse .doc_encode at L = 512 (inputs and outputs only, no hidden states), fp32 and
+    under bf16 autocast, plus r_autocast = the largest relative L2 between the two over heads and sides (as the Qwen2 fixtures)."""
+    from transformers import LlamaConfig, LlamaForCausalLM
+    from scaling_retriever.modeling import llm_encoder as le
+    ckw, L, lengths, seed = ROPE_LONG_CFG, 512, [512, 509, 256, 5, 1], 140
+    cfg = LlamaConfig(**ckw)
+    cfg._attn_implementation = "eager"
+    lm = LlamaForCausalLM(cfg).eval()
+    _reinit(lm, ckw, seed=seed)
+    lm.tie_weights()
+    rng = np.random.default_rng(47)
+    out = {"config_json": np.array(json.dumps(ckw)), "weight_seed": seed}
+    dense, sparse = le.LlamaBiDense(BiWrap(lm.model)), le.LlamaBiSparse(BiWrap(lm))
+    rel = lambda a, b: float(np.linalg.norm(a.astype(np.float64) - b.astype(np.float64)) / np.linalg.norm(b.astype(np.float64)))
+    r = 0.0
+    for side in ["left", "right"]:
+        ids, mask = _make_batch(rng, cfg.vocab_size, L, lengths, side, pad_id=cfg.vocab_size - 1)
+        t = dict(input_ids=torch.from_numpy(ids), attention_mask=torch.from_numpy(mask))
+        with torch.no_grad():
+            d, s = dense.doc_encode(**t), sparse.doc_encode(**t)
+            with torch.autocast("cpu", dtype=torch.bfloat16):
+                d16, s16 = dense.doc_encode(**t), sparse.doc_encode(**t)
+        assert d.dtype == torch.float32 and s.dtype == torch.float32
+        d, s, d16, s16 = d.numpy(), s.numpy(), d16.float().numpy(), s16.float().numpy()
+        r = max(r, rel(d16, d), rel(s16, s))
+        out[f"{side}:input_ids"], out[f"{side}:attention_mask"] = ids.astype(np.int16), mask.astype(np.int8)
+        out[f"{side}:dense"], out[f"{side}:sparse"] = d, s
+        out[f"{side}:dense_bf16autocast"], out[f"{side}:sparse_bf16autocast"] = d16, s16
+    out["r_autocast"] = np.float64(r)
+    np.savez_compressed(os.path.join(OUT, "enc_rope_long.npz"), **out)
+    print("enc_rope_long r_autocast %.3e" % r, "bytes", os.path.getsize(os.path.join(OUT, "enc_rope_long.npz")))
+
+
 if __name__ == "__main__":
     _install_stubs()
     torch.manual_seed(0)
     if sys.argv[1:] == ["index_build"]:                   # one fixture only
         gen_index_build()
         sys.exit(0)
+    if sys.argv[1:] == ["rope"]:                          # the two RoPE fixtures only
+        gen_rope_hf()
+        gen_enc_rope_long()
+        sys.exit(0)
     gen_encoder()
     gen_sparse_score()
     gen_plan_files()
     gen_index_build()
+    gen_rope_hf()
+    gen_enc_rope_long()

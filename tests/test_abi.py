@@ -332,3 +332,21 @@ def test_sparse_cert_readout_hook_validates_before_it_touches_a_device():
         rc = lib.sr_sparse_index_cert_readout(idx, 0, None, 0, np_)
         assert rc == _lib.SR_ERR_INVALID and b"null argument" in lib.sr_last_error()
     assert n.value == -1
+
+
+def test_model_readout_and_lora_merge_validate_before_they_touch_a_device():
+    """sr_model_readout without a model or without one of its size pointers, and sr_lora_merge with a null pointer or 2^21 rows, are
+    SR_ERR_INVALID; nothing is dereferenced."""
+    from scaling_retriever_amd import _lib
+    lib = _lib.load()
+    n, rows, elems = ctypes.c_int64(-1), ctypes.c_int64(-1), ctypes.c_int64(-1)
+    p = ctypes.c_void_p(4096)
+    for m, a, b, c in [(None, ctypes.byref(n), ctypes.byref(rows), ctypes.byref(elems)), (p, None, ctypes.byref(rows), ctypes.byref(elems)),
+                       (p, ctypes.byref(n), None, ctypes.byref(elems)), (p, ctypes.byref(n), ctypes.byref(rows), None)]:
+        rc = lib.sr_model_readout(m, -1, 0, 0, None, 0, a, b, c)
+        assert rc == _lib.SR_ERR_INVALID and b"null argument" in lib.sr_last_error()
+    assert (n.value, rows.value, elems.value) == (-1, -1, -1)
+    rc = lib.sr_lora_merge(None, p, p, 4, 4, 1, 1.0, None)
+    assert rc == _lib.SR_ERR_INVALID and b"bad argument" in lib.sr_last_error()
+    rc = lib.sr_lora_merge(p, p, p, 1 << 21, 4, 1, 1.0, None)
+    assert rc == _lib.SR_ERR_INVALID and b"too large" in lib.sr_last_error()

@@ -26,6 +26,21 @@ def test_encoder_oracle_matches_reference_heads(golden_dir, name, side):
     np.testing.assert_allclose(LB.sparse_encode(w, cfg, ids, mask), z[f"{side}:sparse"], atol=1e-5, rtol=1e-5)
 
 
+@pytest.mark.parametrize("side", ["left", "right"])
+def test_encoder_oracle_matches_reference_heads_at_long_positions(golden_dir, side):
+    """enc_rope_long: L = 512 with the 1B RoPE parameters.  The oracle forms inv_freq in double and rounds once, transformers in
+    fp32 (12 of 32 entries differ, up to 3 ulps; tests/golden/rope_hf.npz), so cos / sin differ by up to 3.1e-5 at position 511 - and
+    the heads by a relative L2 of at most 1.4e-6 per dense row (0.34 of the dense bar, 0.32 of the sparse bar at the worst
+    element), since only relative positions enter the scores.  Same bars as above."""
+    z = np.load(os.path.join(golden_dir, "enc_rope_long.npz"))
+    cfg = json.loads(str(z["config_json"]))
+    w = make_weights(cfg, int(z["weight_seed"]))
+    ids, mask = z[f"{side}:input_ids"].astype(np.int64), z[f"{side}:attention_mask"].astype(np.int64)
+    assert ids.shape == (5, 512) and sorted(mask.sum(1)) == [1, 5, 256, 509, 512]
+    np.testing.assert_allclose(LB.dense_encode(w, cfg, ids, mask), z[f"{side}:dense"], atol=1e-6, rtol=1e-5)
+    np.testing.assert_allclose(LB.sparse_encode(w, cfg, ids, mask), z[f"{side}:sparse"], atol=1e-5, rtol=1e-5)
+
+
 def test_toy_config_scores(golden_dir):
     """BASELINE config 1 shape: 2 queries x 2 passages, scores = q @ d.T (README.md:50-52)."""
     zq = np.load(os.path.join(golden_dir, "enc_toy_q.npz"))
