@@ -58,7 +58,21 @@ def parse_args(argv=None):
     ap.add_argument("--index_dtype", choices=["fp32", "fp16"], default="fp32",
                     help="retrieval: how the flat index keeps its rows. fp16 rounds the (fp32) shard files once, at ingest, and "
                          "holds half the bytes; the shard files themselves are not changed")
+    ap.add_argument("--mmr_lambda", type=float, default=None,
+                    help="retrieval task: also a diversified run - exact greedy MMR with this lambda in [0, 1] over the top "
+                         "--mmr_fetch_k of every query, top_k picks - written to mmr/run.json beside the untouched run.json")
+    ap.add_argument("--mmr_fetch_k", type=int, default=0,
+                    help="with --mmr_lambda: candidates per query, top_k <= mmr_fetch_k <= the library's sr_mmr_max_candidates()")
     args = ap.parse_args(argv)
+    if args.mmr_fetch_k and args.mmr_lambda is None:
+        ap.error("--mmr_fetch_k needs --mmr_lambda (it is the candidate depth of the MMR selection)")
+    if args.mmr_lambda is not None:
+        if args.collapse_file:
+            ap.error("--mmr_lambda cannot be combined with --collapse_file (MMR diversifies passages, a collapsed run ranks groups)")
+        if not 0.0 <= args.mmr_lambda <= 1.0:
+            ap.error(f"--mmr_lambda must be in [0, 1], got {args.mmr_lambda}")
+        if args.mmr_fetch_k < args.top_k:
+            ap.error(f"--mmr_lambda needs --mmr_fetch_k >= top_k = {args.top_k}, got {args.mmr_fetch_k}")
     if args.collapse_hits and not args.collapse_file:
         ap.error("--collapse_hits needs --collapse_file (hits are the passages inside the groups of a collapsed search)")
     if not 0 <= args.collapse_hits <= 64:
@@ -249,12 +263,36 @@ def allowed_subset_positions(path, id_files, world=1):
     return allowed_positions(read_allowed_ids_file(path), lambda d: inv.pos.get(str(d)))
 
 
+def write_mmr_run(args, index, q_reps, qids, doc_ids, subset):
+    """--mmr_lambda: mmr/run.json and mmr/q_stats.json.  utils/metrics.py ranks a run by score and a marginal value is no ranking score
+    (pick 0's may lie below pick 1's), so pick t of a query with n_selected picks carries float(n_selected - t): strictly decreasing
+    and exact, every metric sees the selection order.  q_stats.json: per query the mean marginal value and how many picks are not among
+    the plain top_k (their rank in the search at mmr_fetch_k is top_k or beyond)."""
+    from scaling_retriever_amd.utils.run_file import to_host, write_run_json
+    ids, _, mmr, pos, counts = index.search_mmr(q_reps.contiguous(), args.top_k, args.mmr_fetch_k, args.mmr_lambda, subset=subset)
+    ids, mmr, pos, counts = to_host(ids), to_host(mmr), to_host(pos), to_host(counts)
+    picked = np.arange(args.top_k)[None, :] < counts[:, None]
+    order_scores = np.where(picked, counts[:, None] - np.arange(args.top_k)[None, :], 0).astype(np.float32)
+    os.makedirs(os.path.join(args.out_dir, "mmr"), exist_ok=True)
+    write_run_json(os.path.join(args.out_dir, "mmr", "run.json"), qids, order_scores, ids, doc_ids, counts)
+    stats = {}
+    for r, qid in enumerate(qids):
+        n = int(counts[r])
+        stats[str(qid)] = {"picks": n, "mean_mmr": float(mmr[r, :n].astype(np.float64).mean()) if n else None,
+                           "picks_outside_top_k": int((pos[r, :n] >= args.top_k).sum())}
+    with open(os.path.join(args.out_dir, "mmr", "q_stats.json"), "w") as fout:
+        json.dump(stats, fout, indent=4)
+
+
 def retrieval(args):
     if args.allowed_ids_file and args.world_size > 1:           # before the model and the index shards are loaded
         raise NotImplementedError("--allowed_ids_file is not supported by the doc-sharded retrieval (world_size > 1): "
                                   "run the retrieval task on one process")
     if args.collapse_file and args.world_size > 1:
         raise NotImplementedError("--collapse_file is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
+    if args.mmr_lambda is not None and args.world_size > 1:
+        raise NotImplementedError("--mmr_lambda is not supported by the doc-sharded retrieval (world_size > 1): "
                                   "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaDenseCollectionCollator
     from scaling_retriever_amd.dataset.dataset import MSMARCOQueryDataset
@@ -321,6 +359,8 @@ def retrieval(args):
         from scaling_retriever_amd.utils.run_file import to_host, write_run_json
         doc_ids = np.concatenate([np.load(f) for f in id_files])
         write_run_json(os.path.join(args.out_dir, "run.json"), qids, to_host(scores), to_host(idx), doc_ids)
+        if args.mmr_lambda is not None:
+            write_mmr_run(args, index, q_reps, qids, doc_ids, subset)
     if world > 1:
         dist.barrier()
 

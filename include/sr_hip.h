@@ -706,6 +706,36 @@ int sr_rank_fuse(const int64_t* d_ids, const int32_t* d_counts, const float* d_s
                  int method, const float* h_weights, float c, int k, float* d_out_scores, int64_t* d_out_ids,
                  int32_t* d_out_counts, int32_t* d_out_ranks, sr_stream stream);
 
+/* ------------------------------------------------------- diversified search ---
+ * sr_dense_mmr (csrc/dense_mmr.hip): exact greedy Maximal Marginal Relevance over a candidate list per query, on the
+ * rows the dense index holds (fp32 or fp16 rows, any number of segments).  No reference counterpart.
+ * Input: d_ids int64 [nq, n] global doc indices as sr_dense_search returns them, d_rel fp32 [nq, n] the caller's relevance (a search's
+ * scores, a fused score, ...), d_counts int32 [nq] the valid prefix of each row (NULL: n).  Entry i of query q is a candidate iff
+ * i < counts[q] and ids[q, i] >= 0 (id < 0 = padding, skipped).  An id may repeat in a row: each entry is its own candidate.
+ * d_ids and d_rel must be readable for all nq * n entries, padding and the entries beyond counts included (their values are ignored).
+ * lambda in [0, 1]; mu = f32(1) - f32(lambda), computed once on the host.
+ * Similarity: sim(i, j) = the fp32 fmaf chain from +0.0f over the stored rows i and j in the exact kernel's k order (per 8 columns
+ * k = 8s + j, then 8s + 4 + j) - bit for bit what sr_dense_score_pairs returns for a query equal to row i read as fp32 and document j
+ * (fp16-stored rows are widened exactly); symmetric, because the products commute.
+ * Selection: pick 0 is the best candidate by (rel descending, id ascending, position ascending); its marginal value is f32(lambda * rel).
+ * At pick t >= 1 every unselected candidate has m_i = the largest sim(i, j) over the selected j (m = sim > m ? sim : m, from -inf) and
+ * v_i = f32( f32(lambda * rel_i) - f32(mu * m_i) ), two roundings and no contraction; the pick is the best by (v descending as floats,
+ * -0.0 equal to +0.0; id ascending; position ascending).  Selection ends after k picks or when the candidates run out.  A total order
+ * and no atomic on the result path: two calls return the same bytes.
+ * Output [nq, k]: d_out_ids int64, d_out_rel fp32 (the pick's rel, bits untouched), d_out_mmr fp32 (v at the moment of the pick),
+ * d_out_pos int32 (its position in the candidate row); d_out_counts int32 [nq] picks made; padding (-1, -FLT_MAX, -FLT_MAX, -1).
+ * lambda = 1 returns the first k candidates by (rel, id); d_out_mmr never increases from pick 1 on (m_i never decreases and every
+ * rounding is monotone); pick 0 may lie below pick 1 when similarities are negative.
+ * Contract: rel and the rows are finite and no chain overflows - a NaN or an infinity in rel, in a row or in a similarity is outside
+ * the contract (not checked).  1 <= n <= sr_mmr_max_candidates() (1024: the candidates' state lives in LDS), 1 <= k <= that cap; a bad
+ * size, lambda or pointer is SR_ERR_INVALID before any device work; nq = 0 is legal.  A candidate id that is in no segment is found on
+ * the device: SR_ERR_INVALID, sr_last_error() names query, entry and id, and NOTHING is selected (every output row is padding).
+ * One workgroup per query runs all k steps (no host round trip in between); waits for the stream once, to read the status.       */
+int sr_mmr_max_candidates(void);
+int sr_dense_mmr(sr_dense_index* idx, const int64_t* d_ids, const float* d_rel, const int32_t* d_counts, int64_t nq, int64_t n, int k,
+                 float lambda, int64_t* d_out_ids, float* d_out_rel, float* d_out_mmr, int32_t* d_out_pos, int32_t* d_out_counts,
+                 sr_stream stream);
+
 /* ---------------------------------------------------------------- encoder ---
  * Replaces LlamaBiDense / LlamaBiSparse .encode / .query_encode / .doc_encode
  * (scaling_retriever/modeling/llm_encoder.py:66-70,186-196,424-443) and the

@@ -120,6 +120,9 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_rank_fuse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, ctypes.POINTER(c_float), c_float, c_int, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_mmr_max_candidates": (c_int, []),
+    "sr_dense_mmr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p]),
     "sr_topk_collapse": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     "sr_group_members_count": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,

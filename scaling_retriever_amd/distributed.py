@@ -299,6 +299,11 @@ class ShardedDenseRetriever:
         raise NotImplementedError("ShardedDenseRetriever.search_collapsed: the collapsed search (collapse.py) is not offered on a doc-sharded "
                                   "index; search one index that holds every document with DenseIndexHIP.search_collapsed")
 
+    def search_mmr(self, *args, **kwargs):
+        raise NotImplementedError("ShardedDenseRetriever.search_mmr: the diversified search needs the rows of every candidate on one device "
+                                  "and is not offered on a doc-sharded index; search one index that holds every document with "
+                                  "DenseIndexHIP.search_mmr")
+
     def search_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedDenseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "
                                   "doc-sharded index")

@@ -458,6 +458,20 @@ class DenseFlatIndexer(DenseIndexer):
                    for i, row in enumerate(out)]
         return (out, stats) if return_stats else out
 
+    def search_mmr(self, query_reps, top_docs: int, fetch_k: int, lam=0.5, allowed_ids=None, allowed_mask=None, allowed_masks=None,
+                   query_group=None):
+        """Diversified search_knn (DenseIndexHIP.search_mmr): the top fetch_k of every query, then top_docs picks by exact
+        greedy MMR with lambda = lam over the stored rows.  Returns (list of db-id lists in selection order, relevance fp32 [nq, top_docs] =
+        the picks' search scores, marginal values fp32 [nq, top_docs]); a query with fewer picks has a shorter list and -FLT_MAX padding.
+        top_docs <= fetch_k <= sr_mmr_max_candidates(), lam in [0, 1]; filters as for search_knn."""
+        from .mmr import mmr_arguments
+        mmr_arguments("search_mmr", top_docs, fetch_k, lam, allowed_masks, query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        filt = self._resolve("search_mmr", allowed_ids, allowed_mask, allowed_masks, query_group)
+        q = _dense_queries(query_reps, self.index.device)
+        ids, rel, mmr, _, counts = self.index.search_mmr(q, top_docs, fetch_k, lam, **_collapse_filter(filt))
+        lists = self.id_lists(to_host(ids))
+        return [row[:c] for row, c in zip(lists, to_host(counts).tolist())], to_host(rel), to_host(mmr)
+
     def inverse_id_map(self):
         """str(db id) -> index position, cached with the id table (rebuilt when the list grew)."""
         from .rerank import InverseIdMap

@@ -100,6 +100,7 @@ class DenseIndexHIP:
         self._h = ctypes.c_void_p()
         _lib.check(self.lib.sr_dense_index_create(ctypes.byref(self._h), self.dim), "sr_dense_index_create")
         self._segments = []  # keeps the device tensors alive (the C side holds non-owning views)
+        self._segment_ids = []  # (id_base, id_stride) of each: mmr.stored_rows finds a document's row again
         self.precision = "fp32"          # what set_precision / set_batch_invariant last set (the C ABI has no getters)
         self.batch_invariant = False
 
@@ -155,6 +156,7 @@ class DenseIndexHIP:
         self._call("sr_dense_index_add_f16" if rows.dtype == torch.float16 else "sr_dense_index_add", _ptr(rows), rows.shape[0], int(id_base),
                    int(id_stride), stream=False)
         self._segments.append(rows)
+        self._segment_ids.append((int(id_base), int(id_stride)))
 
     def stored_dtype(self):
         """"fp32" or "fp16": what the index's rows are stored as (an empty index: "fp32")."""
@@ -447,6 +449,49 @@ class DenseIndexHIP:
         self._call("sr_dense_score_pairs", _ptr(queries), nq, _ptr(cand_indptr), _ptr(cand_ids), _ptr(out))
         return out[:total]
 
+    def mmr(self, cand_ids, cand_rel, k, lam=0.5, counts=None):
+        """Exact greedy Maximal Marginal Relevance over a candidate list per query (include/sr_hip.h sr_dense_mmr).
+        cand_ids int64 [nq, n] (the ids `search` returns; id < 0 = padding), cand_rel fp32 [nq, n] the caller's relevance - a search's
+        scores, a fused score, an RRF score; counts int32 [nq] the valid prefix of every row (None: n); 1 <= k <= n <=
+        sr_mmr_max_candidates(), lam in [0, 1].  Pick 0 is the best candidate by (rel, id, position); pick t >= 1 maximises
+        f32(f32(lam * rel_i) - f32((1 - lam) * m_i)), m_i = the largest inner product of stored row i with a selected row - every inner
+        product the bits of `score_pairs` - ties by ascending id, then position.  Returns (ids int64 [nq, k], rel fp32 [nq, k] the picks'
+        relevance, mmr fp32 [nq, k] the marginal value at the moment of each pick, pos int32 [nq, k] the picks' positions in their
+        candidate row, counts int32 [nq]) as cuda tensors, padded with (-1, -FLT_MAX, -FLT_MAX, -1).  lam = 1 returns the first k candidates
+        by (rel, id).  Rows and relevance must be finite (an overflowing inner product is outside the contract).  An id the index does
+        not hold: ValueError naming query, entry and id."""
+        from .mmr import mmr_arguments
+        ids = _to_dev(cand_ids, torch.int64, self.device)
+        rel = _to_dev(cand_rel, torch.float32, self.device)
+        if ids.dim() != 2 or rel.shape != ids.shape:
+            raise ValueError(f"expected cand_ids int64 [nq, n] and cand_rel fp32 of the same shape, got {tuple(ids.shape)} and {tuple(rel.shape)}")
+        nq, n = ids.shape
+        mmr_arguments("mmr", k, n, lam)
+        if counts is not None:
+            counts = _to_dev(counts, torch.int32, self.device)
+            if counts.dim() != 1 or counts.numel() != nq:
+                raise ValueError(f"expected {nq} counts, got {tuple(counts.shape)}")
+        out_ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        out_rel = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        out_mmr = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        out_pos = torch.empty((nq, k), dtype=torch.int32, device=self.device)
+        out_counts = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        self._call("sr_dense_mmr", _ptr(ids), _ptr(rel), _ptr(counts), nq, n, int(k), float(lam), _ptr(out_ids), _ptr(out_rel), _ptr(out_mmr),
+                   _ptr(out_pos), _ptr(out_counts))
+        return out_ids, out_rel, out_mmr, out_pos, out_counts
+
+    def search_mmr(self, queries, k, fetch_k, lam=0.5, subset=None, mask=None, masks=None, query_group=None):
+        """Diversified search: the top fetch_k of `search` (under subset= / mask=) or of `search_grouped` (masks= + query_group=), then
+        `mmr` over those rows with the search's scores as relevance.  k <= fetch_k <= sr_mmr_max_candidates().  Returns what `mmr`
+        returns; pos is the pick's rank in the plain search.  lam = 1 returns the rows of search(queries, k), bit for bit."""
+        from .mmr import mmr_arguments
+        mmr_arguments("search_mmr", k, fetch_k, lam, masks, query_group, subset=subset, mask=mask)
+        if masks is not None:
+            scores, ids = self.search_grouped(queries, int(fetch_k), masks, query_group)
+        else:
+            scores, ids = self.search(queries, int(fetch_k), subset=subset, mask=mask)
+        return self.mmr(ids, scores, k, lam)
+
     def search_begin(self, queries, k, share):
         """First half of a doc-sharded search (include/sr_hip.h sr_dense_search_begin): returns lower [nq] fp32 (cuda) - per
         query a value at least ceil(k / share) documents of this index reach exactly (-inf where the filter does not apply).
@@ -473,6 +518,7 @@ class DenseIndexHIP:
             self.lib.sr_dense_index_destroy(self._h)
             self._h = ctypes.c_void_p()
         self._segments = []
+        self._segment_ids = []
 
     def __del__(self):
         try:
