@@ -63,7 +63,24 @@ def parse_args(argv=None):
                          "--mmr_fetch_k of every query, top_k picks - written to mmr/run.json beside the untouched run.json")
     ap.add_argument("--mmr_fetch_k", type=int, default=0,
                     help="with --mmr_lambda: candidates per query, top_k <= mmr_fetch_k <= the library's sr_mmr_max_candidates()")
+    ap.add_argument("--prf_depth", type=int, default=0,
+                    help="retrieval task: also a second round with pseudo-relevance feedback (Rocchio) - every query vector rebuilt from "
+                         "its M best documents and searched again - written to prf/run.json beside the untouched run.json (0: off; at most 64)")
+    ap.add_argument("--prf_alpha", type=float, default=1.0, help="with --prf_depth: weight of the original query")
+    ap.add_argument("--prf_beta", type=float, default=0.75, help="with --prf_depth: weight of the mean of the M feedback documents")
+    ap.add_argument("--prf_gamma", type=float, default=0.0, help="with --prf_neg_depth: weight of the mean of the negative documents")
+    ap.add_argument("--prf_neg_depth", type=int, default=0,
+                    help="with --prf_depth: the G documents ranked behind the M feedback documents are the negative set (0: none; at most 64)")
     args = ap.parse_args(argv)
+    if not args.prf_depth and (args.prf_neg_depth or args.prf_gamma):
+        ap.error("--prf_neg_depth / --prf_gamma need --prf_depth (they shape the feedback of the second round)")
+    if args.prf_depth:
+        if args.collapse_file:
+            ap.error("--prf_depth cannot be combined with --collapse_file (feedback rebuilds passage queries, a collapsed run ranks groups)")
+        if not 1 <= args.prf_depth <= 64 or not 0 <= args.prf_neg_depth <= 64:
+            ap.error(f"--prf_depth must be in [1, 64] and --prf_neg_depth in [0, 64], got {args.prf_depth} and {args.prf_neg_depth}")
+        if min(args.prf_alpha, args.prf_beta, args.prf_gamma) < 0:
+            ap.error("--prf_alpha, --prf_beta and --prf_gamma must be >= 0")
     if args.mmr_fetch_k and args.mmr_lambda is None:
         ap.error("--mmr_fetch_k needs --mmr_lambda (it is the candidate depth of the MMR selection)")
     if args.mmr_lambda is not None:
@@ -294,6 +311,9 @@ def retrieval(args):
     if args.mmr_lambda is not None and args.world_size > 1:
         raise NotImplementedError("--mmr_lambda is not supported by the doc-sharded retrieval (world_size > 1): "
                                   "run the retrieval task on one process")
+    if args.prf_depth and args.world_size > 1:
+        raise NotImplementedError("--prf_depth is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaDenseCollectionCollator
     from scaling_retriever_amd.dataset.dataset import MSMARCOQueryDataset
     from scaling_retriever_amd.distributed import gather_topk, sharded_dense_search
@@ -361,6 +381,13 @@ def retrieval(args):
         write_run_json(os.path.join(args.out_dir, "run.json"), qids, to_host(scores), to_host(idx), doc_ids)
         if args.mmr_lambda is not None:
             write_mmr_run(args, index, q_reps, qids, doc_ids, subset)
+        if args.prf_depth:
+            # the second round (DenseIndexHIP.search_prf): Rocchio's rebuilt query vectors, searched under the same allow-list
+            p_scores, p_idx, _ = index.search_prf(q_reps.contiguous(), args.top_k, n_pos=args.prf_depth, n_neg=args.prf_neg_depth,
+                                                  alpha=args.prf_alpha, beta=args.prf_beta, gamma=args.prf_gamma,
+                                                  fb_depth=args.prf_depth + args.prf_neg_depth, subset=subset)
+            os.makedirs(os.path.join(args.out_dir, "prf"), exist_ok=True)
+            write_run_json(os.path.join(args.out_dir, "prf", "run.json"), qids, to_host(p_scores), to_host(p_idx), doc_ids)
     if world > 1:
         dist.barrier()
 

@@ -51,7 +51,25 @@ def parse_args(argv=None):
                          "to hits/run.json (0: off; at most 64)")
     ap.add_argument("--doc_max_terms", type=int, default=0, help="indexing task: terms indexed per document (index size)")
     ap.add_argument("--query_max_terms", type=int, default=0, help="retrieval task: terms searched per query (latency)")
+    ap.add_argument("--prf_depth", type=int, default=0,
+                    help="retrieval task: also a second round with pseudo-relevance feedback (Rocchio) - every query rebuilt from its M best "
+                         "documents and searched again - written to prf/run.json beside the untouched run.json (0: off; at most 64)")
+    ap.add_argument("--prf_alpha", type=float, default=1.0, help="with --prf_depth: weight of the original query")
+    ap.add_argument("--prf_beta", type=float, default=0.75, help="with --prf_depth: weight of the mean of the M feedback documents")
+    ap.add_argument("--prf_gamma", type=float, default=0.0, help="with --prf_neg_depth: weight of the mean of the negative documents")
+    ap.add_argument("--prf_neg_depth", type=int, default=0,
+                    help="with --prf_depth: the G documents ranked behind the M feedback documents are the negative set (0: none; at most 64)")
+    ap.add_argument("--prf_max_terms", type=int, default=128, help="with --prf_depth: terms kept per rebuilt query (0: all)")
     args = ap.parse_args(argv)
+    if not args.prf_depth and (args.prf_neg_depth or args.prf_gamma):
+        ap.error("--prf_neg_depth / --prf_gamma need --prf_depth (they shape the feedback of the second round)")
+    if args.prf_depth:
+        if args.collapse_file:
+            ap.error("--prf_depth cannot be combined with --collapse_file (feedback rebuilds passage queries, a collapsed run ranks groups)")
+        if not 1 <= args.prf_depth <= 64 or not 0 <= args.prf_neg_depth <= 64:
+            ap.error(f"--prf_depth must be in [1, 64] and --prf_neg_depth in [0, 64], got {args.prf_depth} and {args.prf_neg_depth}")
+        if min(args.prf_alpha, args.prf_beta, args.prf_gamma) < 0 or args.prf_max_terms < 0:
+            ap.error("--prf_alpha, --prf_beta, --prf_gamma and --prf_max_terms must be >= 0")
     if args.collapse_hits and not args.collapse_file:
         ap.error("--collapse_hits needs --collapse_file (hits are the passages inside the groups of a collapsed search)")
     if not 0 <= args.collapse_hits <= 64:
@@ -140,6 +158,9 @@ def sparse_retrieval(args):
     if args.collapse_file and args.world_size > 1:
         raise NotImplementedError("--collapse_file is not supported by the doc-sharded retrieval (world_size > 1): "
                                   "run the retrieval task on one process")
+    if args.prf_depth and args.world_size > 1:
+        raise NotImplementedError("--prf_depth is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaSparseCollectionCollator
     from scaling_retriever_amd.indexer import SparseRetrieval
     from scaling_retriever_amd.modeling.llm_encoder import retriever_class
@@ -175,8 +196,14 @@ def sparse_retrieval(args):
         from scaling_retriever_amd.collapse import read_collapse_file
         group_of = read_collapse_file(args.collapse_file)
         collapse = lambda d: group_of[str(d)]      # noqa: E731  (collection ids may be ints, the file's are text)
-    return retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids, collapse=collapse,
-                              hits=args.collapse_hits or None)
+    res = retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids, collapse=collapse,
+                             hits=args.collapse_hits or None)
+    if args.prf_depth:
+        # the second round, to prf/run.json: the queries are encoded again (retrieve keeps none of them)
+        retriever.retrieve_prf(q_loader, topk=args.top_k, threshold=0.0, n_pos=args.prf_depth, n_neg=args.prf_neg_depth, alpha=args.prf_alpha,
+                               beta=args.prf_beta, gamma=args.prf_gamma, max_terms=args.prf_max_terms,
+                               fb_depth=args.prf_depth + args.prf_neg_depth, allowed_ids=allowed_ids)
+    return res
 
 
 def evaluate_msmarco(args):

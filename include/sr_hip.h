@@ -736,6 +736,44 @@ int sr_dense_mmr(sr_dense_index* idx, const int64_t* d_ids, const float* d_rel, 
                  float lambda, int64_t* d_out_ids, float* d_out_rel, float* d_out_mmr, int32_t* d_out_pos, int32_t* d_out_counts,
                  sr_stream stream);
 
+/* ------------------------------------------------- pseudo-relevance feedback ---
+ * Rocchio's rebuilt query for both heads (csrc/prf.hip).  No reference counterpart.
+ * Per query, d_fb_ids int64 [nq, depth] is a ranked list (id < 0 = padding), d_counts int32 [nq] its valid prefix (NULL: depth).  Let v
+ * be the valid, non-padding entries in list order: the positive set is the first p = min(n_pos, |v|) of them, the negative set the last
+ * g = min(n_neg, |v| - p) in list order (never overlapping the positive set); a document that appears twice counts twice.
+ * cp = f32(beta / f32(p)), cn = f32(gamma / f32(g)), fp32 divisions on the host (two tables of 64 entries in the kernel arguments).
+ * For every coordinate t (a term / a column): P_t = the positive documents' values at t summed in list order from +0.0f, one rounded fp32
+ * add each (a document that does not hold t adds nothing), N_t likewise for the negative set;
+ *   w_t = f32( f32(alpha * q_t) + f32(cp * P_t) ), then w_t = f32( w_t - f32(cn * N_t) ), contraction off;
+ * q_t absent starts from +0.0f, p = 0 / g = 0 skips its step.  1 <= n_pos <= 64, 0 <= n_neg <= 64, 1 <= depth <= sr_max_topk(), alpha,
+ * beta, gamma finite and >= 0, max_terms >= 0: anything else is SR_ERR_INVALID before any device work.  nq = 0 is legal.  Values are
+ * finite (not checked).  No atomic decides an output byte: two calls return the same bytes.
+ *
+ * sr_sparse_feedback (stateless): the queries as CSR (d_q_indptr int64 [nq + 1], d_q_cols int32 strictly ascending inside a row and in
+ * [0, n_terms) - what sr_sparse_compact emits -, d_q_vals fp32) and the documents as a doc-major CSR (d_doc_indptr int64 [n_docs + 1],
+ * d_doc_cols int32 ascending inside a row, d_doc_vals fp32; trusted).  Ids are document positions.  A term is kept only if w_t > 0; of the
+ * kept terms the max_terms largest survive, by (w descending, term ascending), 0 = no limit; they are emitted with terms ascending - the
+ * conventions of sr_sparse_compact_topm.  Output CSR d_row_ptr int64 [nq + 1], d_cols int32, d_vals fp32 with capacity, *h_nnz and
+ * SR_ERR_NOMEM exactly as sr_sparse_compact (the needed size is written to *h_nnz; nothing but d_row_ptr is written when it does not fit).
+ * Found on the device, SR_ERR_INVALID and nothing written: a valid entry >= n_docs (sr_last_error() names query, entry and id - every
+ * valid entry is checked, used or not), query columns out of order or outside [0, n_terms) (names the query).  One workgroup per query
+ * merges the query row and the at most 128 document rows in LDS while they hold at most sr_prf_max_entries() entries together (8 192;
+ * the dev switch SR_PRF_MAX_ENTRIES lowers it); a query above that takes the same steps on a global-memory workspace, same bits (at most
+ * 2^25 - 1 entries: SR_ERR_UNSUPPORTED beyond).  Waits for the stream twice: the plan (status, entry counts), the total.
+ *
+ * sr_dense_feedback: d_queries fp32 [nq, dim], ids as sr_dense_search returns them (every segment's id_base / id_stride; fp32 or fp16
+ * rows, fp16 widened exactly); d_out fp32 [nq, dim] (16-byte aligned, as d_queries) := w over all columns.  An id the index does not hold
+ * is found on the device: SR_ERR_INVALID naming query, entry and id, nothing is written.  Every row is read once, as 16-byte pieces.
+ * Waits for the stream once, to read the status.                                                                                     */
+int sr_prf_max_entries(void);
+int sr_sparse_feedback(const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals, int64_t nq,
+                       const int64_t* d_doc_indptr, const int32_t* d_doc_cols, const float* d_doc_vals, int64_t n_docs, int64_t n_terms,
+                       const int64_t* d_fb_ids, const int32_t* d_counts, int64_t depth, int n_pos, int n_neg, float alpha, float beta,
+                       float gamma, int64_t max_terms, int64_t* d_row_ptr, int32_t* d_cols, float* d_vals, int64_t capacity,
+                       int64_t* h_nnz, sr_stream stream);
+int sr_dense_feedback(sr_dense_index* idx, const float* d_queries, int64_t nq, const int64_t* d_fb_ids, const int32_t* d_counts,
+                      int64_t depth, int n_pos, int n_neg, float alpha, float beta, float gamma, float* d_out, sr_stream stream);
+
 /* ---------------------------------------------------------------- encoder ---
  * Replaces LlamaBiDense / LlamaBiSparse .encode / .query_encode / .doc_encode
  * (scaling_retriever/modeling/llm_encoder.py:66-70,186-196,424-443) and the

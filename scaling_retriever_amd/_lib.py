@@ -123,6 +123,12 @@ SIGNATURES = {
     "sr_mmr_max_candidates": (c_int, []),
     "sr_dense_mmr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p]),
+    "sr_prf_max_entries": (c_int, []),
+    "sr_sparse_feedback": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                   c_int64, c_int, c_int, c_float, c_float, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                   ctypes.POINTER(c_int64), c_void_p]),
+    "sr_dense_feedback": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_float, c_void_p,
+                                  c_void_p]),
     "sr_topk_collapse": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     "sr_group_members_count": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,

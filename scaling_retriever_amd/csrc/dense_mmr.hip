@@ -35,31 +35,6 @@ struct MmrArgs {
     const PairStatus* st;
 };
 
-// the row of global doc index gid (element offset into its segment's rows), as dense_pairs_kernel finds it; false: in no segment
-__device__ inline bool mmr_row_of(const PairSeg* __restrict__ segs, int n_segs, int64_t gid, int H, int* seg, int64_t* elem) {
-    for (int sgi = 0; sgi < n_segs; ++sgi) {
-        const int64_t off = gid - segs[sgi].id_base, stride = segs[sgi].id_stride;
-        int64_t r = off;                                  // stride 1 (every segment of DenseFlatIndexer): no 64-bit divide
-        bool in_seg = off >= 0;
-        if (stride != 1) {
-            r = off / stride;
-            in_seg = in_seg && r * stride == off;
-        }
-        if (in_seg && r < segs[sgi].n) {
-            *seg = sgi;
-            *elem = r * (int64_t)H;
-            return true;
-        }
-    }
-    return false;
-}
-
-__device__ inline int mmr_count(const int32_t* __restrict__ counts, int64_t q, int n) {
-    if (!counts) return n;
-    const int c = counts[q];
-    return c < 0 ? 0 : (c > n ? n : c);
-}
-
 __global__ void mmr_check_kernel(const PairSeg* __restrict__ segs, int n_segs, int H, const int64_t* __restrict__ ids,
                                  const int32_t* __restrict__ counts, int64_t nq, int n, PairStatus* __restrict__ st) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,10 +42,10 @@ __global__ void mmr_check_kernel(const PairSeg* __restrict__ segs, int n_segs, i
     const int64_t q = p / n;
     const int i = (int)(p - q * n);
     const int64_t id = ids[p];
-    if (i >= mmr_count(counts, q, n) || id < 0) return;
+    if (i >= list_count(counts, q, n) || id < 0) return;
     int seg;
     int64_t elem;
-    if (!mmr_row_of(segs, n_segs, id, H, &seg, &elem)) atomicMin(&st->first_bad, (unsigned long long)p);
+    if (!pair_row_of(segs, n_segs, id, H, &seg, &elem)) atomicMin(&st->first_bad, (unsigned long long)p);
 }
 
 // a candidate's place in the order of a pick: larger ord first (sr_f2ord of rel or of v), then the smaller id, then the smaller position
@@ -135,7 +110,7 @@ __global__ __launch_bounds__(64 * MMR_MAX_WAVES) void dense_mmr_kernel(MmrArgs a
 
     int picked = 0;
     if (a.st->first_bad == ~0ull) {                             // the check ran before this launch on the same stream
-        const int cnt = mmr_count(a.counts, q, n);
+        const int cnt = list_count(a.counts, q, n);
         MmrKey mine;
         mine.ord = 0; mine.pos = -1; mine.id = 0;
         for (int i = tid; i < n; i += nt) {
@@ -143,7 +118,7 @@ __global__ __launch_bounds__(64 * MMR_MAX_WAVES) void dense_mmr_kernel(MmrArgs a
             const int64_t id = ids[i];
             int seg;
             int64_t elem;
-            if (i < cnt && id >= 0 && mmr_row_of(a.segs, a.n_segs, id, H, &seg, &elem)) row = static_cast<const T*>(a.segs[seg].rows) + elem;
+            if (i < cnt && id >= 0 && pair_row_of(a.segs, a.n_segs, id, H, &seg, &elem)) row = static_cast<const T*>(a.segs[seg].rows) + elem;
             const float r = rel[i];
             s_row[i] = row;
             s_id[i] = id;
@@ -277,6 +252,14 @@ __global__ __launch_bounds__(64 * MMR_MAX_WAVES) void dense_mmr_kernel(MmrArgs a
     if (tid == 0) a.out_counts[q] = picked;
 }
 
+int launch_id_list_check(const PairSeg* d_segs, int n_segs, int H, const int64_t* d_ids, const int32_t* d_counts, int64_t nq, int n,
+                         PairStatus* d_status, hipStream_t s) {
+    hipLaunchKernelGGL(mmr_check_kernel, dim3((unsigned)ceil_div64(nq * n, 256)), dim3(256), 0, s, d_segs, n_segs, H, d_ids, d_counts, nq, n,
+                       d_status);
+    SR_CHECK_LAUNCH();
+    return SR_OK;
+}
+
 extern "C" int sr_mmr_max_candidates(void) { return MMR_MAX_N; }
 
 extern "C" int sr_dense_mmr(sr_dense_index* idx, const int64_t* d_ids, const float* d_rel, const int32_t* d_counts, int64_t nq, int64_t n,
@@ -296,9 +279,7 @@ extern "C" int sr_dense_mmr(sr_dense_index* idx, const int64_t* d_ids, const flo
     SR_TRY(dense_pair_segs(idx, "sr_dense_mmr"));
     SR_TRY(subset_status_begin(&idx->pair_status, s));
     const int n_segs = (int)idx->pair_segs_n;
-    hipLaunchKernelGGL(mmr_check_kernel, dim3((unsigned)ceil_div64(nq * n, 256)), dim3(256), 0, s, idx->pair_segs.p, n_segs, idx->dim, d_ids,
-                       d_counts, nq, (int)n, idx->pair_status);
-    SR_CHECK_LAUNCH();
+    SR_TRY(launch_id_list_check(idx->pair_segs.p, n_segs, idx->dim, d_ids, d_counts, nq, (int)n, idx->pair_status, s));
 
     // as many waves as the list has tiles, up to 8, and as their 16.6 KB tiles fit beside the candidates' 24 bytes each
     int dev = 0, lds_max = 0;

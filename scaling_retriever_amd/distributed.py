@@ -257,6 +257,11 @@ class ShardedSparseRetriever:
         raise NotImplementedError("ShardedSparseRetriever.search_collapsed: the collapsed search (collapse.py) is not offered on a "
                                   "doc-sharded index; search one merged index with SparseIndexHIP.search_collapsed")
 
+    def search_prf(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetriever.search_prf: pseudo-relevance feedback needs the rows of every feedback document on "
+                                  "one device and is not offered on a doc-sharded index; search one merged index with "
+                                  "SparseIndexHIP.search_prf")
+
     def search_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedSparseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "
                                   "doc-sharded index")
@@ -303,6 +308,11 @@ class ShardedDenseRetriever:
         raise NotImplementedError("ShardedDenseRetriever.search_mmr: the diversified search needs the rows of every candidate on one device "
                                   "and is not offered on a doc-sharded index; search one index that holds every document with "
                                   "DenseIndexHIP.search_mmr")
+
+    def search_prf(self, *args, **kwargs):
+        raise NotImplementedError("ShardedDenseRetriever.search_prf: pseudo-relevance feedback needs the rows of every feedback document on "
+                                  "one device and is not offered on a doc-sharded index; search one index that holds every document with "
+                                  "DenseIndexHIP.search_prf")
 
     def search_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedDenseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "

@@ -472,6 +472,20 @@ class DenseFlatIndexer(DenseIndexer):
         lists = self.id_lists(to_host(ids))
         return [row[:c] for row, c in zip(lists, to_host(counts).tolist())], to_host(rel), to_host(mmr)
 
+    def search_prf(self, query_reps, top_docs: int, n_pos=10, n_neg=0, alpha=1.0, beta=0.75, gamma=0.0, fb_depth=None, allowed_ids=None,
+                   allowed_mask=None, allowed_masks=None, query_group=None):
+        """search_knn with pseudo-relevance feedback (DenseIndexHIP.search_prf): the top fb_depth (default n_pos) of every
+        query, Rocchio's rebuilt query from the first n_pos (and, with n_neg > 0, the last n_neg) of them, then the search at top_docs
+        with the new queries under the same filter.  Returns (list of db-id lists, fp32 scores [nq, top_docs], the new queries fp32
+        [nq, dim]) as host values; filters as for search_knn."""
+        from .prf import prf_arguments
+        prf_arguments("search_prf", n_pos, n_neg, alpha, beta, gamma, first_round=True, fb_depth=fb_depth, allowed_masks=allowed_masks,
+                      query_group=query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        filt = self._resolve("search_prf", allowed_ids, allowed_mask, allowed_masks, query_group)
+        q = _dense_queries(query_reps, self.index.device)
+        scores, ids, new = self.index.search_prf(q, top_docs, n_pos, n_neg, alpha, beta, gamma, fb_depth=fb_depth, **_collapse_filter(filt))
+        return self.id_lists(to_host(ids)), to_host(scores), to_host(new)
+
     def inverse_id_map(self):
         """str(db id) -> index position, cached with the id table (rebuilt when the list grew)."""
         from .rerank import InverseIdMap
@@ -1118,6 +1132,31 @@ class SparseRetrieval:
         return res
 
 
+    def retrieve_prf(self, q_loader, topk, threshold=0., n_pos=10, n_neg=0, alpha=1.0, beta=0.75, gamma=0.0, max_terms=128, fb_depth=None,
+                     allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
+        """`retrieve` with pseudo-relevance feedback (SparseIndexHIP.search_prf): the whole query set is encoded and
+        searched at fb_depth (default n_pos), every query is rebuilt by Rocchio from the first n_pos (and, with n_neg > 0, the last n_neg)
+        documents of its list and cut to its max_terms largest terms, and searched again at topk - all under the same filter and
+        threshold.  Writes prf/run.json and prf/q_stats.json (L0_q of the expanded queries) under the output directory; the run.json /
+        q_stats.json of a plain `retrieve` are not touched.  Returns the RunResult.  Filters as for `retrieve`; no collapse."""
+        from .prf import prf_arguments
+        prf_arguments("retrieve_prf", n_pos, n_neg, alpha, beta, gamma, max_terms, first_round=True, fb_depth=fb_depth,
+                      allowed_masks=allowed_masks, query_group=query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        filt = self._resolve("retrieve_prf", allowed_ids, allowed_mask, allowed_masks, query_group)
+        q, qids = self._generate_query_vecs(q_loader)
+        if filt is not None and filt.kind == "groups" and filt.groups.numel() != len(q):
+            raise ValueError(f"retrieve_prf: query_group must hold one group id per query ({len(q)}), got {filt.groups.numel()}")
+        scores, ids, counts, new = self.hip_index.search_prf(q.row_ptr, q.cols, q.vals, topk, n_pos, n_neg, alpha, beta, gamma, max_terms,
+                                                             fb_depth=fb_depth, threshold=threshold, **_collapse_filter(filt))
+        res = RunResult(qids, to_host(scores), to_host(ids), self.doc_id_table(), to_host(counts))
+        out_dir = os.path.join(self.out_dir, "prf")
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "q_stats.json"), "w") as handler:
+            json.dump({"L0_q": QueryCSR(*new).mean_l0()}, handler)
+        res.dump(os.path.join(out_dir, "run.json"))
+        return res
+
+
 class ShardedSparseRetrieval(SparseRetrieval):
     """Doc-sharded SparseRetrieval for world_size > 1 (the reference asserts world_size == 1, eval_sparse.py:114, and
     needs a merge_indexes pass first, scripts/eval_sparse.sh:19): rank r opens the directory `{index_dir}_{r}` the indexing
@@ -1175,6 +1214,10 @@ class ShardedSparseRetrieval(SparseRetrieval):
     def retrieve_rank_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedSparseRetrieval.retrieve_rank_fused: rank fusion of the two heads' lists is not offered on a "
                                   "doc-sharded index; use HybridRetriever over one merged index, or eval_fuse.py on the run files")
+
+    def retrieve_prf(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetrieval.retrieve_prf: pseudo-relevance feedback needs the rows of every feedback document "
+                                  "on one device and is not offered on a doc-sharded index; search one merged index with SparseRetrieval")
 
     def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
         """q_loader yields THIS rank's block of the queries (distributed.query_slice order) or all of them when
@@ -1442,6 +1485,10 @@ class HybridRetriever(SparseRetrieval):
         os.makedirs(fused_dir, exist_ok=True)
         fused_res.dump(os.path.join(fused_dir, "run.json"))
         return sparse_res, dense_res, fused_res
+
+    def retrieve_prf(self, *args, **kwargs):
+        raise NotImplementedError("HybridRetriever.retrieve_prf: pseudo-relevance feedback is offered per head (SparseRetrieval.retrieve_prf, "
+                                  "DenseFlatIndexer.search_prf), not on the hybrid retriever: fuse the two feedback runs with eval_fuse.py")
 
     def retrieve_rank_fused(self, q_loader, topk, method="rrf", c=60.0, weights=(1.0, 1.0), fused_topk=None, threshold=0., allowed_ids=None,
                             allowed_masks=None, query_group=None, collapse=None):

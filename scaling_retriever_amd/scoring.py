@@ -4,7 +4,7 @@ These hold device memory (torch tensors) and call the C ABI; all arithmetic is i
 the HIP kernels (csrc/dense_score.hip, csrc/sparse_cert.hip, csrc/sparse_score.hip, csrc/topk.hip).
 The reference-shaped classes in indexer.py are built on top of these.
 
-What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, topk_merge, hybrid_union,
+What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, sparse_feedback, topk_merge, hybrid_union,
 hybrid_rank, topk_collapse, group_members, segment_topm).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
 the status checked under that name); a filtered variant of an entry is the same call with "_subset" / "_masked" appended to the name
 and the filter's two arguments spliced in where the header puts them (_filter_args).  Each class checks its queries in one place
@@ -492,6 +492,48 @@ class DenseIndexHIP:
             scores, ids = self.search(queries, int(fetch_k), subset=subset, mask=mask)
         return self.mmr(ids, scores, k, lam)
 
+    def feedback(self, queries, fb_ids, counts=None, n_pos=10, n_neg=0, alpha=1.0, beta=0.75, gamma=0.0):
+        """Rocchio's rebuilt queries (include/sr_hip.h sr_dense_feedback): queries fp32 cuda [nq, dim]; fb_ids int64
+        [nq, depth] a ranked list per query of the ids `search` returns (id < 0 = padding), counts int32 [nq] its valid prefix (None:
+        depth).  Of the valid entries the first min(n_pos, .) are the positive set, the last min(n_neg, what is left) the negative set;
+        new = f32(f32(alpha * q) + f32(f32(beta / p) * P)), then f32(new - f32(f32(gamma / g) * N)) per column, P / N the sets' stored
+        rows (fp16 rows widened exactly) summed in list order.  Returns fp32 cuda [nq, dim].  An id the index does not hold: ValueError
+        naming query, entry and id."""
+        from .prf import feedback_depth, prf_arguments
+        prf_arguments("feedback", n_pos, n_neg, alpha, beta, gamma, depth=feedback_depth(fb_ids))
+        ids = _to_dev(fb_ids, torch.int64, self.device)
+        queries = self._queries(queries)
+        nq = queries.shape[0]
+        if ids.shape[0] != nq:
+            raise ValueError(f"expected {nq} feedback rows, got {tuple(ids.shape)}")
+        if counts is not None:
+            counts = _to_dev(counts, torch.int32, self.device)
+            if counts.dim() != 1 or counts.numel() != nq:
+                raise ValueError(f"expected {nq} counts, got {tuple(counts.shape)}")
+        out = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device)
+        self._call("sr_dense_feedback", _ptr(queries), nq, _ptr(_valid(ids)), _ptr(counts), ids.shape[1], int(n_pos), int(n_neg), float(alpha),
+                   float(beta), float(gamma), _ptr(out))
+        return out
+
+    def search_prf(self, queries, k, n_pos=10, n_neg=0, alpha=1.0, beta=0.75, gamma=0.0, fb_depth=None, subset=None, mask=None, masks=None,
+                   query_group=None):
+        """Search with pseudo-relevance feedback: the top fb_depth (default n_pos; >= n_pos + n_neg with a negative set) of `search`
+        (under subset= / mask=) or of `search_grouped` (masks= + query_group=), `feedback` over those rows, then the search at k with the
+        new queries under the same filter.  Returns (scores [nq, k], ids [nq, k], new queries [nq, dim]).  alpha = 1, beta = gamma = 0
+        returns the rows of the plain search, bit for bit."""
+        from .prf import prf_arguments
+        depth = prf_arguments("search_prf", n_pos, n_neg, alpha, beta, gamma, first_round=True, fb_depth=fb_depth, allowed_masks=masks,
+                              query_group=query_group, subset=subset, mask=mask)
+
+        def search(qs, kk):
+            if masks is not None:
+                return self.search_grouped(qs, kk, masks, query_group)
+            return self.search(qs, kk, subset=subset, mask=mask)
+        _, fb = search(queries, depth)
+        new = self.feedback(queries, fb, None, n_pos, n_neg, alpha, beta, gamma)
+        scores, ids = search(new, int(k))
+        return scores, ids, new
+
     def search_begin(self, queries, k, share):
         """First half of a doc-sharded search (include/sr_hip.h sr_dense_search_begin): returns lower [nq] fp32 (cuda) - per
         query a value at least ceil(k / share) documents of this index reach exactly (-inf where the filter does not apply).
@@ -543,6 +585,7 @@ class SparseIndexHIP:
         self.vals = _valid(_to_dev(vals, torch.float32, self.device))
         self.n_terms = self.indptr.numel() - 1
         self.n_docs = int(n_docs)
+        self._forward = None            # forward_rows(): the doc-major CSR, built on first use
         self._h = ctypes.c_void_p()
         _call(self.device, "sr_sparse_index_create", ctypes.byref(self._h), _ptr(self.indptr), _ptr(self.doc_ids), _ptr(self.vals), self.n_terms,
               self.n_docs, lib=self.lib)
@@ -737,10 +780,57 @@ class SparseIndexHIP:
         self._call("sr_sparse_score_pairs", *map(_ptr, q), nq, _ptr(cand_indptr), _ptr(cand_ids), _ptr(out))
         return out[:total]
 
+    def forward_rows(self):
+        """The index by document: (indptr int64 [n_docs + 1], terms int32 [nnz] ascending inside a document, vals fp32 [nnz]) on the device,
+        built on first use from the index's own CSR-by-term tensors with sparse_csr_expand_terms + sparse_csr_build (documents as the sort
+        key: the stable sort over term-major input leaves the terms of a document ascending) and kept: 8 bytes per posting + 8 per
+        document, until drop_forward_rows().  Independent of the certified scorer's private forward index."""
+        if self._forward is None:
+            nnz = int(self.indptr[-1])
+            terms = sparse_csr_expand_terms(self.indptr, nnz)
+            self._forward = sparse_csr_build(terms, self.doc_ids[:nnz], self.vals[:nnz], self.n_docs)
+        return self._forward
+
+    def drop_forward_rows(self):
+        """Frees what forward_rows() keeps; the next call builds it again."""
+        self._forward = None
+
+    def feedback(self, q_indptr, q_cols, q_vals, fb_ids, counts=None, n_pos=10, n_neg=0, alpha=1.0, beta=0.75, gamma=0.0, max_terms=128):
+        """Rocchio's rebuilt queries over this index's documents (sparse_feedback below, on forward_rows()): queries as CSR as for
+        `search` (columns strictly ascending inside a row), fb_ids int64 [nq, depth] document positions (a search's ids under id_base = 0,
+        id_stride = 1; < 0 = padding), counts its valid prefix.  Returns (indptr, cols, vals) of the new queries."""
+        from .prf import feedback_depth, prf_arguments
+        prf_arguments("feedback", n_pos, n_neg, alpha, beta, gamma, max_terms, depth=feedback_depth(fb_ids))
+        q, _ = self._query_csr(q_indptr, q_cols, q_vals)
+        return sparse_feedback(*q, *self.forward_rows(), self.n_terms, fb_ids, counts=counts, n_pos=n_pos, n_neg=n_neg, alpha=alpha, beta=beta,
+                               gamma=gamma, max_terms=max_terms)
+
+    def search_prf(self, q_indptr, q_cols, q_vals, k, n_pos=10, n_neg=0, alpha=1.0, beta=0.75, gamma=0.0, max_terms=128, fb_depth=None,
+                   threshold=0.0, id_base=0, id_stride=1, subset=None, mask=None, masks=None, query_group=None):
+        """Search with pseudo-relevance feedback: the first round is `search` (subset= / mask=) or `search_grouped` (masks= + query_group=)
+        at depth fb_depth (default n_pos; >= n_pos + n_neg with a negative set) in positions (id_base = 0, id_stride = 1), then `feedback`
+        over its rows and counts, then the search at k with the new queries under the same filter, threshold, id_base and id_stride.
+        Returns (scores [nq, k], ids [nq, k], counts [nq], (indptr, cols, vals) of the new queries).  With alpha = 1, beta = gamma = 0 and
+        no binding max_terms the result is `search(k)` of the queries' positive terms, bit for bit."""
+        from .prf import prf_arguments
+        depth = prf_arguments("search_prf", n_pos, n_neg, alpha, beta, gamma, max_terms, first_round=True, fb_depth=fb_depth, allowed_masks=masks,
+                              query_group=query_group, subset=subset, mask=mask)
+
+        def search(q, kk, base, stride):
+            if masks is not None:
+                return self.search_grouped(*q, kk, masks, query_group, threshold=threshold, id_base=base, id_stride=stride)
+            return self.search(*q, kk, threshold=threshold, id_base=base, id_stride=stride, subset=subset, mask=mask)
+        q, _ = self._query_csr(q_indptr, q_cols, q_vals)             # uploaded once for the three steps
+        _, fb, fb_counts = search(q, depth, 0, 1)
+        new = self.feedback(*q, fb, fb_counts, n_pos, n_neg, alpha, beta, gamma, max_terms)
+        scores, ids, counts = search(new, int(k), id_base, id_stride)
+        return scores, ids, counts, new
+
     def close(self):
         if self._h:
             self.lib.sr_sparse_index_destroy(self._h)
             self._h = ctypes.c_void_p()
+        self._forward = None
 
     def __del__(self):
         try:
@@ -774,6 +864,52 @@ def sparse_csr_expand_terms(indptr, nnz):
     out = torch.empty(max(1, int(nnz)), dtype=torch.int32, device=indptr.device)
     _call(indptr.device, "sr_sparse_csr_expand_terms", _ptr(indptr), indptr.numel() - 1, int(nnz), _ptr(out))
     return out[:int(nnz)]
+
+
+def sparse_feedback(q_indptr, q_cols, q_vals, doc_indptr, doc_cols, doc_vals, n_terms, fb_ids, counts=None, n_pos=10, n_neg=0, alpha=1.0,
+                    beta=0.75, gamma=0.0, max_terms=128):
+    """Rocchio's rebuilt sparse queries (include/sr_hip.h sr_sparse_feedback): queries as CSR (columns strictly ascending
+    inside a row), the documents as a doc-major CSR on the device (SparseIndexHIP.forward_rows()), fb_ids int64 [nq, depth] a ranked list
+    of document positions per query (< 0 = padding), counts int32 [nq] its valid prefix (None: depth).  Of the valid entries the first
+    min(n_pos, .) are the positive set, the last min(n_neg, what is left) the negative set; per term w = f32(f32(alpha * q) + f32(f32(beta
+    / p) * P)), then f32(w - f32(f32(gamma / g) * N)), P / N summed in list order; terms with w > 0 are kept, of those the max_terms
+    largest (w descending, term ascending; 0 = no limit), emitted with terms ascending.  Returns (indptr int64 [nq + 1], cols int32, vals
+    fp32) cuda tensors.  A position outside [0, n_docs) or query columns out of order: ValueError naming the place."""
+    from .prf import feedback_depth, prf_arguments
+    prf_arguments("sparse_feedback", n_pos, n_neg, alpha, beta, gamma, max_terms, depth=feedback_depth(fb_ids))
+    dev = doc_vals.device
+    fb = _to_dev(fb_ids, torch.int64, dev)
+    q_indptr = _to_dev(q_indptr, torch.int64, dev)
+    q_cols, q_vals = _valid(_to_dev(q_cols, torch.int32, dev)), _valid(_to_dev(q_vals, torch.float32, dev))
+    nq = q_indptr.numel() - 1
+    if fb.shape[0] != nq:
+        raise ValueError(f"expected {nq} feedback rows, got {tuple(fb.shape)}")
+    if counts is not None:
+        counts = _to_dev(counts, torch.int32, dev)
+        if counts.dim() != 1 or counts.numel() != nq:
+            raise ValueError(f"expected {nq} counts, got {tuple(counts.shape)}")
+    doc_indptr = _to_dev(doc_indptr, torch.int64, dev)
+    doc_cols, doc_vals = _valid(_to_dev(doc_cols, torch.int32, dev)), _valid(_to_dev(doc_vals, torch.float32, dev))
+    n_docs, max_terms = doc_indptr.numel() - 1, int(max_terms)
+    indptr = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    # a budget bounds the output; without one a guess (8 bytes each), and one more call with the size the first one names if it was short
+    cap = max(1, nq * min(max_terms, int(n_terms)) if max_terms else nq * min(int(n_terms), 4096))
+    n = ctypes.c_int64(0)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        while True:
+            cols = torch.empty(cap, dtype=torch.int32, device=dev)
+            vals = torch.empty(cap, dtype=torch.float32, device=dev)
+            rc = lib.sr_sparse_feedback(_ptr(q_indptr), _ptr(q_cols), _ptr(q_vals), nq, _ptr(doc_indptr), _ptr(doc_cols), _ptr(doc_vals), n_docs,
+                                        int(n_terms), _ptr(_valid(fb)), _ptr(counts), fb.shape[1], int(n_pos), int(n_neg), float(alpha),
+                                        float(beta), float(gamma), max_terms, _ptr(indptr), _ptr(cols), _ptr(vals), cap, ctypes.byref(n),
+                                        _lib.stream_ptr())
+            if rc == _lib.SR_ERR_NOMEM and n.value > cap:
+                cap = n.value
+                continue
+            _lib.check(rc, "sr_sparse_feedback")
+            break
+    return indptr, cols[:n.value], vals[:n.value]
 
 
 def topk_merge(scores, ids, pad_score=-3.402823466e38):
