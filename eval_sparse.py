@@ -60,7 +60,25 @@ def parse_args(argv=None):
     ap.add_argument("--prf_neg_depth", type=int, default=0,
                     help="with --prf_depth: the G documents ranked behind the M feedback documents are the negative set (0: none; at most 64)")
     ap.add_argument("--prf_max_terms", type=int, default=128, help="with --prf_depth: terms kept per rebuilt query (0: all)")
+    ap.add_argument("--mmr_lambda", type=float, default=None,
+                    help="retrieval task: also a diversified run - exact greedy MMR with this lambda in [0, 1] over the top "
+                         "--mmr_fetch_k of every query, top_k picks - written to mmr/run.json beside the untouched run.json")
+    ap.add_argument("--mmr_fetch_k", type=int, default=0,
+                    help="with --mmr_lambda: candidates per query, top_k <= mmr_fetch_k <= the library's sr_mmr_max_candidates()")
+    ap.add_argument("--mmr_sim", type=str, default="cosine", choices=["ip", "cosine"],
+                    help="with --mmr_lambda: the document-document similarity, the inner product of two documents' term rows or their cosine")
     args = ap.parse_args(argv)
+    if args.mmr_fetch_k and args.mmr_lambda is None:
+        ap.error("--mmr_fetch_k needs --mmr_lambda (it is the candidate depth of the MMR selection)")
+    if args.mmr_lambda is not None:
+        if args.collapse_file:
+            ap.error("--mmr_lambda cannot be combined with --collapse_file (MMR diversifies passages, a collapsed run ranks groups)")
+        if args.prf_depth:
+            ap.error("--mmr_lambda cannot be combined with --prf_depth (run the two second rounds one after the other)")
+        if not 0.0 <= args.mmr_lambda <= 1.0:
+            ap.error(f"--mmr_lambda must be in [0, 1], got {args.mmr_lambda}")
+        if args.mmr_fetch_k < args.top_k:
+            ap.error(f"--mmr_lambda needs --mmr_fetch_k >= top_k = {args.top_k}, got {args.mmr_fetch_k}")
     if not args.prf_depth and (args.prf_neg_depth or args.prf_gamma):
         ap.error("--prf_neg_depth / --prf_gamma need --prf_depth (they shape the feedback of the second round)")
     if args.prf_depth:
@@ -161,6 +179,9 @@ def sparse_retrieval(args):
     if args.prf_depth and args.world_size > 1:
         raise NotImplementedError("--prf_depth is not supported by the doc-sharded retrieval (world_size > 1): "
                                   "run the retrieval task on one process")
+    if args.mmr_lambda is not None and args.world_size > 1:
+        raise NotImplementedError("--mmr_lambda is not supported by the doc-sharded retrieval (world_size > 1): "
+                                  "run the retrieval task on one process")
     from scaling_retriever_amd.dataset.data_collator import LlamaSparseCollectionCollator
     from scaling_retriever_amd.indexer import SparseRetrieval
     from scaling_retriever_amd.modeling.llm_encoder import retriever_class
@@ -203,6 +224,10 @@ def sparse_retrieval(args):
         retriever.retrieve_prf(q_loader, topk=args.top_k, threshold=0.0, n_pos=args.prf_depth, n_neg=args.prf_neg_depth, alpha=args.prf_alpha,
                                beta=args.prf_beta, gamma=args.prf_gamma, max_terms=args.prf_max_terms,
                                fb_depth=args.prf_depth + args.prf_neg_depth, allowed_ids=allowed_ids)
+    if args.mmr_lambda is not None:
+        # the diversified run, to mmr/run.json: the queries are encoded again (retrieve keeps none of them)
+        retriever.retrieve_mmr(q_loader, topk=args.top_k, fetch_k=args.mmr_fetch_k, lam=args.mmr_lambda, sim=args.mmr_sim, threshold=0.0,
+                               allowed_ids=allowed_ids)
     return res
 
 

@@ -736,6 +736,31 @@ int sr_dense_mmr(sr_dense_index* idx, const int64_t* d_ids, const float* d_rel, 
                  float lambda, int64_t* d_out_ids, float* d_out_rel, float* d_out_mmr, int32_t* d_out_pos, int32_t* d_out_counts,
                  sr_stream stream);
 
+/* sr_sparse_mmr (csrc/sparse_mmr.hip): the same selection on the sparse head.  Stateless, like sr_sparse_feedback: the
+ * documents arrive as a doc-major CSR (d_doc_indptr int64 [n_docs + 1], d_doc_cols int32 ascending inside a row, d_doc_vals fp32;
+ * trusted) - what SparseIndexHIP.forward_rows() keeps.  d_ids int64 [nq, n] are document positions in [0, n_docs); d_rel, d_counts, the
+ * candidate rule (i < counts[q] and id >= 0; a repeated id is its own candidate), lambda and mu as for sr_dense_mmr; 1 <= k <= n <=
+ * sr_mmr_max_candidates().
+ * Similarity, contraction off everywhere: ip(i, j) is s = +0.0f, then for every term t that both rows hold, in ascending t,
+ * s = f32(s + f32(v_i[t] * v_j[t])) - bit for bit what sr_sparse_score_pairs returns for the query "row i" and document j; symmetric
+ * (the products commute); an empty row or a pair without a common term gives +0.0f.
+ *   sim_mode = SR_MMR_SIM_IP:      sim = ip.
+ *   sim_mode = SR_MMR_SIM_COSINE:  norm_i = f32(sqrt(ip(i, i))), den = f32(norm_i * norm_j), sim = den > 0 ? f32(ip / den) : +0.0f, the
+ *                                  square root and the division correctly rounded.  Sparse document-document inner products are far
+ *                                  larger than query-document scores (about 128 terms meet, not 32): on raw inner products no lambda
+ *                                  balances the two terms of v.
+ * Selection, the five outputs, their padding and the order of a pick are exactly sr_dense_mmr's.  A valid entry >= n_docs is found on
+ * the device (the kernel reads no row offset for it): SR_ERR_INVALID, sr_last_error() names query, entry and id, every output row is
+ * padding.  A bad size, sim_mode, lambda or pointer is SR_ERR_INVALID before any device work; nq = 0 is legal.  Non-finite values are
+ * outside the contract.  No atomic decides an output byte: two calls return the same bytes.  One workgroup per query runs all k picks;
+ * the picked row is staged in LDS in chunks of 512 entries (the dev switch SR_MMR_SPARSE_CHUNK lowers it; the bits do not depend on
+ * it).  Waits for the stream once, to read the status.                                                                            */
+#define SR_MMR_SIM_IP 0
+#define SR_MMR_SIM_COSINE 1
+int sr_sparse_mmr(const int64_t* d_doc_indptr, const int32_t* d_doc_cols, const float* d_doc_vals, int64_t n_docs, const int64_t* d_ids,
+                  const float* d_rel, const int32_t* d_counts, int64_t nq, int64_t n, int k, float lambda, int sim_mode,
+                  int64_t* d_out_ids, float* d_out_rel, float* d_out_mmr, int32_t* d_out_pos, int32_t* d_out_counts, sr_stream stream);
+
 /* ------------------------------------------------- pseudo-relevance feedback ---
  * Rocchio's rebuilt query for both heads (csrc/prf.hip).  No reference counterpart.
  * Per query, d_fb_ids int64 [nq, depth] is a ranked list (id < 0 = padding), d_counts int32 [nq] its valid prefix (NULL: depth).  Let v

@@ -262,6 +262,11 @@ class ShardedSparseRetriever:
                                   "one device and is not offered on a doc-sharded index; search one merged index with "
                                   "SparseIndexHIP.search_prf")
 
+    def search_mmr(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetriever.search_mmr: the diversified search needs the forward rows of every candidate on "
+                                  "one device and is not offered on a doc-sharded index; search one merged index with "
+                                  "SparseIndexHIP.search_mmr")
+
     def search_fused(self, *args, **kwargs):
         raise NotImplementedError("ShardedSparseRetriever.search_fused: the exact fused search (hybrid.search_fused) is not offered on a "
                                   "doc-sharded index")

@@ -1156,6 +1156,39 @@ class SparseRetrieval:
         res.dump(os.path.join(out_dir, "run.json"))
         return res
 
+    def retrieve_mmr(self, q_loader, topk, fetch_k, lam=0.5, sim="cosine", threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None,
+                     query_group=None):
+        """`retrieve` diversified (SparseIndexHIP.search_mmr): the whole query set is encoded and searched at fetch_k, and
+        exact greedy MMR with `lam` and the document-document similarity `sim` ("ip" / "cosine") selects topk of every query's rows -
+        under the same filter and threshold.  Writes mmr/run.json and mmr/q_stats.json under the output directory; the run.json /
+        q_stats.json of a plain `retrieve` are not touched.  A marginal value is no ranking score (pick 0's may lie below pick 1's), so
+        pick t of a query with n picks carries float(n - t), eval_dense.py's convention; q_stats.json holds per query the number of
+        picks, the mean marginal value and how many picks are not among the plain topk.  Returns the RunResult.  Filters as for
+        `retrieve`; no collapse."""
+        from .mmr import mmr_arguments
+        mmr_arguments("retrieve_mmr", topk, fetch_k, lam, allowed_masks, query_group, sim=sim, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        filt = self._resolve("retrieve_mmr", allowed_ids, allowed_mask, allowed_masks, query_group)
+        q, qids = self._generate_query_vecs(q_loader)
+        if filt is not None and filt.kind == "groups" and filt.groups.numel() != len(q):
+            raise ValueError(f"retrieve_mmr: query_group must hold one group id per query ({len(q)}), got {filt.groups.numel()}")
+        ids, _, mmr, pos, counts = self.hip_index.search_mmr(q.row_ptr, q.cols, q.vals, topk, fetch_k, lam, sim=sim, threshold=threshold,
+                                                             **_collapse_filter(filt))
+        ids, mmr, pos, counts = to_host(ids), to_host(mmr), to_host(pos), to_host(counts)
+        ranks = np.arange(topk)[None, :]
+        order_scores = np.where(ranks < counts[:, None], counts[:, None] - ranks, 0).astype(np.float32)
+        res = RunResult(qids, order_scores, ids, self.doc_id_table(), counts)
+        out_dir = os.path.join(self.out_dir, "mmr")
+        os.makedirs(out_dir, exist_ok=True)
+        stats = {}
+        for r, qid in enumerate(qids):
+            n = int(counts[r])
+            stats[str(qid)] = {"picks": n, "mean_mmr": float(mmr[r, :n].astype(np.float64).mean()) if n else None,
+                               "picks_outside_top_k": int((pos[r, :n] >= topk).sum())}
+        with open(os.path.join(out_dir, "q_stats.json"), "w") as handler:
+            json.dump(stats, handler, indent=4)
+        res.dump(os.path.join(out_dir, "run.json"))
+        return res
+
 
 class ShardedSparseRetrieval(SparseRetrieval):
     """Doc-sharded SparseRetrieval for world_size > 1 (the reference asserts world_size == 1, eval_sparse.py:114, and
@@ -1217,6 +1250,10 @@ class ShardedSparseRetrieval(SparseRetrieval):
 
     def retrieve_prf(self, *args, **kwargs):
         raise NotImplementedError("ShardedSparseRetrieval.retrieve_prf: pseudo-relevance feedback needs the rows of every feedback document "
+                                  "on one device and is not offered on a doc-sharded index; search one merged index with SparseRetrieval")
+
+    def retrieve_mmr(self, *args, **kwargs):
+        raise NotImplementedError("ShardedSparseRetrieval.retrieve_mmr: the diversified search needs the forward rows of every candidate "
                                   "on one device and is not offered on a doc-sharded index; search one merged index with SparseRetrieval")
 
     def retrieve(self, q_loader, topk, threshold=0., allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None, collapse=None):
@@ -1489,6 +1526,10 @@ class HybridRetriever(SparseRetrieval):
     def retrieve_prf(self, *args, **kwargs):
         raise NotImplementedError("HybridRetriever.retrieve_prf: pseudo-relevance feedback is offered per head (SparseRetrieval.retrieve_prf, "
                                   "DenseFlatIndexer.search_prf), not on the hybrid retriever: fuse the two feedback runs with eval_fuse.py")
+
+    def retrieve_mmr(self, *args, **kwargs):
+        raise NotImplementedError("HybridRetriever.retrieve_mmr: the diversified search is offered per head (SparseRetrieval.retrieve_mmr, "
+                                  "DenseFlatIndexer.search_mmr), not on the hybrid retriever: a combined dense + sparse similarity is not defined")
 
     def retrieve_rank_fused(self, q_loader, topk, method="rrf", c=60.0, weights=(1.0, 1.0), fused_topk=None, threshold=0., allowed_ids=None,
                             allowed_masks=None, query_group=None, collapse=None):

@@ -4,7 +4,7 @@ These hold device memory (torch tensors) and call the C ABI; all arithmetic is i
 the HIP kernels (csrc/dense_score.hip, csrc/sparse_cert.hip, csrc/sparse_score.hip, csrc/topk.hip).
 The reference-shaped classes in indexer.py are built on top of these.
 
-What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, sparse_feedback, topk_merge, hybrid_union,
+What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, sparse_feedback, sparse_mmr, topk_merge, hybrid_union,
 hybrid_rank, topk_collapse, group_members, segment_topm).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
 the status checked under that name); a filtered variant of an entry is the same call with "_subset" / "_masked" appended to the name
 and the filter's two arguments spliced in where the header puts them (_filter_args).  Each class checks its queries in one place
@@ -826,6 +826,30 @@ class SparseIndexHIP:
         scores, ids, counts = search(new, int(k), id_base, id_stride)
         return scores, ids, counts, new
 
+    def mmr(self, cand_ids, cand_rel, k, lam=0.5, counts=None, sim="cosine"):
+        """Exact greedy Maximal Marginal Relevance over a candidate list per query on this index's documents (sparse_mmr below, on
+        forward_rows()): cand_ids int64 [nq, n] document positions (a search's ids under id_base = 0, id_stride = 1; < 0 = padding),
+        cand_rel fp32 [nq, n], counts the valid prefix.  Returns what DenseIndexHIP.mmr returns."""
+        return sparse_mmr(*self.forward_rows(), cand_ids, cand_rel, k, lam, counts=counts, sim=sim)
+
+    def search_mmr(self, q_indptr, q_cols, q_vals, k, fetch_k, lam=0.5, sim="cosine", threshold=0.0, id_base=0, id_stride=1, subset=None,
+                   mask=None, masks=None, query_group=None):
+        """Diversified search: the top fetch_k of `search` (subset= / mask=) or of `search_grouped` (masks= + query_group=) in positions
+        (id_base = 0, id_stride = 1), then `mmr` over those rows and counts with the search's scores as relevance, then the picks' ids
+        as id_base + position * id_stride (padding stays -1).  k <= fetch_k <= sr_mmr_max_candidates().  Returns what `mmr` returns; pos
+        is the pick's rank in the plain search.  lam = 1 returns the rows of search(k) - ids and scores - bit for bit."""
+        from .mmr import mmr_arguments
+        mmr_arguments("search_mmr", k, fetch_k, lam, masks, query_group, sim=sim, subset=subset, mask=mask)
+        q, _ = self._query_csr(q_indptr, q_cols, q_vals)
+        if masks is not None:
+            scores, ids, counts = self.search_grouped(*q, int(fetch_k), masks, query_group, threshold=threshold)
+        else:
+            scores, ids, counts = self.search(*q, int(fetch_k), threshold=threshold, subset=subset, mask=mask)
+        ids, rel, mmr, pos, counts = self.mmr(ids, scores, k, lam, counts=counts, sim=sim)
+        if int(id_base) != 0 or int(id_stride) != 1:
+            ids = torch.where(ids >= 0, int(id_base) + ids * int(id_stride), ids)
+        return ids, rel, mmr, pos, counts
+
     def close(self):
         if self._h:
             self.lib.sr_sparse_index_destroy(self._h)
@@ -910,6 +934,39 @@ def sparse_feedback(q_indptr, q_cols, q_vals, doc_indptr, doc_cols, doc_vals, n_
             _lib.check(rc, "sr_sparse_feedback")
             break
     return indptr, cols[:n.value], vals[:n.value]
+
+
+def sparse_mmr(doc_indptr, doc_cols, doc_vals, cand_ids, cand_rel, k, lam=0.5, counts=None, sim="cosine"):
+    """Exact greedy Maximal Marginal Relevance on the sparse head (include/sr_hip.h sr_sparse_mmr): the documents as a
+    doc-major CSR on the device (SparseIndexHIP.forward_rows()), cand_ids int64 [nq, n] document positions (< 0 = padding), cand_rel fp32
+    [nq, n] the caller's relevance, counts int32 [nq] the valid prefix of every row (None: n); 1 <= k <= n <= sr_mmr_max_candidates(),
+    lam in [0, 1].  sim = "ip": the similarity of two documents is the term-serial chain over their common terms in ascending term
+    order - the bits of `score_pairs` with one row as the query; sim = "cosine": that over f32(norm_i * norm_j), norm = f32(sqrt(ip(i,
+    i))), +0.0 where a norm is zero.  Selection and the five returned tensors as DenseIndexHIP.mmr.  A position outside [0, n_docs):
+    ValueError naming query, entry and id."""
+    from .mmr import SIM_MODES, mmr_arguments
+    dev = doc_vals.device
+    ids = _to_dev(cand_ids, torch.int64, dev)
+    rel = _to_dev(cand_rel, torch.float32, dev)
+    if ids.dim() != 2 or rel.shape != ids.shape:
+        raise ValueError(f"expected cand_ids int64 [nq, n] and cand_rel fp32 of the same shape, got {tuple(ids.shape)} and {tuple(rel.shape)}")
+    nq, n = ids.shape
+    mmr_arguments("sparse_mmr", k, n, lam, sim=sim)
+    if counts is not None:
+        counts = _to_dev(counts, torch.int32, dev)
+        if counts.dim() != 1 or counts.numel() != nq:
+            raise ValueError(f"expected {nq} counts, got {tuple(counts.shape)}")
+    doc_indptr = _to_dev(doc_indptr, torch.int64, dev)
+    doc_cols, doc_vals = _valid(_to_dev(doc_cols, torch.int32, dev)), _valid(_to_dev(doc_vals, torch.float32, dev))
+    k = int(k)
+    out_ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_rel = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_mmr = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_pos = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    out_counts = torch.empty((nq,), dtype=torch.int32, device=dev)
+    _call(dev, "sr_sparse_mmr", _ptr(doc_indptr), _ptr(doc_cols), _ptr(doc_vals), doc_indptr.numel() - 1, _ptr(ids), _ptr(rel), _ptr(counts),
+          nq, n, k, float(lam), SIM_MODES[sim], _ptr(out_ids), _ptr(out_rel), _ptr(out_mmr), _ptr(out_pos), _ptr(out_counts))
+    return out_ids, out_rel, out_mmr, out_pos, out_counts
 
 
 def topk_merge(scores, ids, pad_score=-3.402823466e38):
