@@ -71,6 +71,10 @@ def parse_args(argv=None):
     ap.add_argument("--prf_gamma", type=float, default=0.0, help="with --prf_neg_depth: weight of the mean of the negative documents")
     ap.add_argument("--prf_neg_depth", type=int, default=0,
                     help="with --prf_depth: the G documents ranked behind the M feedback documents are the negative set (0: none; at most 64)")
+    ap.add_argument("--device_eval", action="store_true",
+                    help="evaluate on the device (scaling_retriever_amd/evaluation.py): the evaluate_msmarco / evaluate_beir tasks write the "
+                         "same perf.json from arrays; the retrieval task with --eval_qrel_path writes a perf.json beside run.json (and "
+                         "beside mmr/run.json and prf/run.json) from the result arrays")
     args = ap.parse_args(argv)
     if not args.prf_depth and (args.prf_neg_depth or args.prf_gamma):
         ap.error("--prf_neg_depth / --prf_gamma need --prf_depth (they shape the feedback of the second round)")
@@ -299,6 +303,7 @@ def write_mmr_run(args, index, q_reps, qids, doc_ids, subset):
                            "picks_outside_top_k": int((pos[r, :n] >= args.top_k).sum())}
     with open(os.path.join(args.out_dir, "mmr", "q_stats.json"), "w") as fout:
         json.dump(stats, fout, indent=4)
+    return order_scores, ids, counts
 
 
 def retrieval(args):
@@ -378,21 +383,45 @@ def retrieval(args):
         # run.json (eval_dense.py:225-241) straight from the result arrays: the bytes json.dump of the reference's nested dict gives
         from scaling_retriever_amd.utils.run_file import to_host, write_run_json
         doc_ids = np.concatenate([np.load(f) for f in id_files])
-        write_run_json(os.path.join(args.out_dir, "run.json"), qids, to_host(scores), to_host(idx), doc_ids)
+        h_scores, h_idx = to_host(scores), to_host(idx)
+        write_run_json(os.path.join(args.out_dir, "run.json"), qids, h_scores, h_idx, doc_ids)
+        perf = device_perf_writer(args, doc_ids)
+        perf("", qids, h_scores, h_idx, None)
         if args.mmr_lambda is not None:
-            write_mmr_run(args, index, q_reps, qids, doc_ids, subset)
+            perf("mmr", qids, *write_mmr_run(args, index, q_reps, qids, doc_ids, subset))
         if args.prf_depth:
             # the second round (DenseIndexHIP.search_prf): Rocchio's rebuilt query vectors, searched under the same allow-list
             p_scores, p_idx, _ = index.search_prf(q_reps.contiguous(), args.top_k, n_pos=args.prf_depth, n_neg=args.prf_neg_depth,
                                                   alpha=args.prf_alpha, beta=args.prf_beta, gamma=args.prf_gamma,
                                                   fb_depth=args.prf_depth + args.prf_neg_depth, subset=subset)
             os.makedirs(os.path.join(args.out_dir, "prf"), exist_ok=True)
-            write_run_json(os.path.join(args.out_dir, "prf", "run.json"), qids, to_host(p_scores), to_host(p_idx), doc_ids)
+            h_scores, h_idx = to_host(p_scores), to_host(p_idx)
+            write_run_json(os.path.join(args.out_dir, "prf", "run.json"), qids, h_scores, h_idx, doc_ids)
+            perf("prf", qids, h_scores, h_idx, None)
     if world > 1:
         dist.barrier()
 
 
+def device_perf_writer(args, doc_ids):
+    """--device_eval with --eval_qrel_path: a function that writes {out_dir}/{sub}/perf.json for a run held as arrays (the judgements
+    become arrays once, here); without them a function that does nothing."""
+    if not (args.device_eval and args.eval_qrel_path):
+        return lambda *a: None
+    from scaling_retriever_amd import evaluation
+    from scaling_retriever_amd.utils.run_file import RunResult
+    with open(args.eval_qrel_path) as f:
+        qrels = evaluation.Qrels(json.load(f), doc_ids)
+
+    def write(sub, qids, scores, positions, counts):
+        evaluation.write_run_perf(os.path.join(args.out_dir, sub, "perf.json"), args.eval_metric, qrels,
+                                  RunResult(qids, scores, positions, qrels.docs, counts))
+    return write
+
+
 def evaluate_msmarco(args):
+    if args.device_eval:
+        from scaling_retriever_amd.evaluation import device_eval_msmarco
+        return device_eval_msmarco(args)
     from scaling_retriever_amd.utils.metrics import load_and_evaluate
     res = {metric: load_and_evaluate(args.eval_qrel_path, args.eval_run_path, metric) for metric in args.eval_metric}
     os.makedirs(args.out_dir, exist_ok=True)
@@ -416,6 +445,9 @@ def main(argv=None):
         from scaling_retriever_amd.utils.beir import load_beir
         from scaling_retriever_amd.utils.metrics import evaluate_beir
         _, _, qrels = load_beir(args.beir_dataset_dir, args.beir_dataset, split="test")
+        if args.device_eval:
+            from scaling_retriever_amd.evaluation import device_eval_beir
+            return device_eval_beir(args, qrels)
         return evaluate_beir(args, qrels)
     else:
         raise NotImplementedError(args.task_name)

@@ -67,6 +67,10 @@ def parse_args(argv=None):
                     help="with --mmr_lambda: candidates per query, top_k <= mmr_fetch_k <= the library's sr_mmr_max_candidates()")
     ap.add_argument("--mmr_sim", type=str, default="cosine", choices=["ip", "cosine"],
                     help="with --mmr_lambda: the document-document similarity, the inner product of two documents' term rows or their cosine")
+    ap.add_argument("--device_eval", action="store_true",
+                    help="evaluate on the device (scaling_retriever_amd/evaluation.py): the evaluate_msmarco / evaluate_beir tasks write the "
+                         "same perf.json from arrays; the retrieval task with --eval_qrel_path writes a perf.json beside run.json (and "
+                         "beside prf/run.json and mmr/run.json) from the result arrays")
     args = ap.parse_args(argv)
     if args.mmr_fetch_k and args.mmr_lambda is None:
         ap.error("--mmr_fetch_k needs --mmr_lambda (it is the candidate depth of the MMR selection)")
@@ -219,19 +223,43 @@ def sparse_retrieval(args):
         collapse = lambda d: group_of[str(d)]      # noqa: E731  (collection ids may be ints, the file's are text)
     res = retriever.retrieve(q_loader, topk=args.top_k, threshold=0.0, allowed_ids=allowed_ids, collapse=collapse,
                              hits=args.collapse_hits or None)
+    perf = device_perf_writer(args)
+    perf("", res)
     if args.prf_depth:
         # the second round, to prf/run.json: the queries are encoded again (retrieve keeps none of them)
-        retriever.retrieve_prf(q_loader, topk=args.top_k, threshold=0.0, n_pos=args.prf_depth, n_neg=args.prf_neg_depth, alpha=args.prf_alpha,
-                               beta=args.prf_beta, gamma=args.prf_gamma, max_terms=args.prf_max_terms,
-                               fb_depth=args.prf_depth + args.prf_neg_depth, allowed_ids=allowed_ids)
+        perf("prf", retriever.retrieve_prf(q_loader, topk=args.top_k, threshold=0.0, n_pos=args.prf_depth, n_neg=args.prf_neg_depth,
+                                           alpha=args.prf_alpha, beta=args.prf_beta, gamma=args.prf_gamma, max_terms=args.prf_max_terms,
+                                           fb_depth=args.prf_depth + args.prf_neg_depth, allowed_ids=allowed_ids))
     if args.mmr_lambda is not None:
         # the diversified run, to mmr/run.json: the queries are encoded again (retrieve keeps none of them)
-        retriever.retrieve_mmr(q_loader, topk=args.top_k, fetch_k=args.mmr_fetch_k, lam=args.mmr_lambda, sim=args.mmr_sim, threshold=0.0,
-                               allowed_ids=allowed_ids)
+        perf("mmr", retriever.retrieve_mmr(q_loader, topk=args.top_k, fetch_k=args.mmr_fetch_k, lam=args.mmr_lambda, sim=args.mmr_sim,
+                                           threshold=0.0, allowed_ids=allowed_ids))
     return res
 
 
+def device_perf_writer(args):
+    """--device_eval with --eval_qrel_path: a function that writes {out_dir}/{sub}/perf.json from a RunResult's arrays (the judgements
+    become arrays once, over the first run's document table); without them, or for a result that is no plain run, it does nothing."""
+    if not (args.device_eval and args.eval_qrel_path):
+        return lambda *a: None
+    from scaling_retriever_amd import evaluation
+    from scaling_retriever_amd.utils.run_file import RunResult
+    state = {}
+
+    def write(sub, res):
+        if not isinstance(res, RunResult):
+            return
+        if "qrels" not in state or state["qrels"].docs is not res.docs:
+            with open(args.eval_qrel_path) as f:
+                state["qrels"] = evaluation.Qrels(json.load(f), res.docs)
+        evaluation.write_run_perf(os.path.join(args.out_dir, sub, "perf.json"), args.eval_metric, state["qrels"], res)
+    return write
+
+
 def evaluate_msmarco(args):
+    if args.device_eval:
+        from scaling_retriever_amd.evaluation import device_eval_msmarco
+        return device_eval_msmarco(args)
     from scaling_retriever_amd.utils.metrics import load_and_evaluate
     res = {metric: load_and_evaluate(args.eval_qrel_path, args.eval_run_path, metric) for metric in args.eval_metric}
     os.makedirs(args.out_dir, exist_ok=True)
@@ -257,6 +285,9 @@ def main(argv=None):
         from scaling_retriever_amd.utils.beir import load_beir
         from scaling_retriever_amd.utils.metrics import evaluate_beir
         _, _, qrels = load_beir(args.beir_dataset_dir, args.beir_dataset, split="test")
+        if args.device_eval:
+            from scaling_retriever_amd.evaluation import device_eval_beir
+            return device_eval_beir(args, qrels)
         return evaluate_beir(args, qrels)
     else:
         raise NotImplementedError(args.task_name)

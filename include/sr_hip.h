@@ -706,6 +706,58 @@ int sr_rank_fuse(const int64_t* d_ids, const int32_t* d_counts, const float* d_s
                  int method, const float* h_weights, float c, int k, float* d_out_scores, int64_t* d_out_ids,
                  int32_t* d_out_counts, int32_t* d_out_ranks, sr_stream stream);
 
+/* --------------------------------------------------------------- evaluation ---
+ * sr_eval_ranked (csrc/eval_metrics.hip): the ranking metrics of nq result lists against graded judgements, per query and
+ * as means, from the arrays a search returns.  Stateless.  No reference counterpart (its utils/metrics.py hands dicts to pytrec_eval).
+ * The list of query q: d_scores fp32 [nq, depth] (read by SR_EVAL_ORDER_SCORE only, else may be NULL), d_ids int64 [nq, depth] (id < 0 =
+ * padding), d_counts int32 [nq] (NULL: depth), d_tie_key int32 [nq, depth] with values in [0, 65536) (NULL: all 0), d_exclude int64 [nq]
+ * (NULL or a negative value: none).  Entry r is valid iff r < counts[q], ids[q, r] >= 0 and ids[q, r] != exclude[q] (BEIR's "drop the
+ * hit whose id is the query's").
+ * The judgements are a CSR over the same nq rows: d_qrel_indptr int64 [nq + 1] inside [0, n_qrel], d_qrel_ids int64 [n_qrel] strictly
+ * ascending inside a row, d_qrel_grades int32 [n_qrel], any sign; a judged document the index does not hold carries an id no list holds.
+ * Three tables depend on the judgements alone; the host computes them once and the kernel trusts them: d_n_rel int32 [nq] the number of
+ * grades > 0; d_idcg double [nq, n_cuts], for cut c the positive grades sorted descending, the first c of them, summed from 0.0 in that
+ * order as double(g) / log2(i + 2); d_log2 double [depth] = log2(i + 2).  The kernel computes no logarithm.
+ * h_cuts: HOST int32 [n_cuts], strictly ascending, each >= 1, 0 <= n_cuts <= sr_eval_max_cuts() (16).  rr_depth >= 0.
+ * Ranking: SR_EVAL_ORDER_LIST takes the valid entries in list order; SR_EVAL_ORDER_SCORE orders them by (score descending with -0.0
+ * read as +0.0, tie_key descending, list position ascending); NaN is outside the contract.  With tie_key = the rank of str(doc id) among
+ * the tied documents that is trec_eval's order.  recip_rank is computed on the list CUT FIRST to its first rr_depth valid entries in list
+ * order (0: no cut), THEN ordered.
+ * d_out double [nq, 1 + 4 n_cuts], all arithmetic in double, contraction off, `/` correctly rounded; the columns of a query that is not
+ * evaluated are 0.0:
+ *   [0]                  recip_rank = 1.0 / rank of the first entry with grade > 0, else 0.0
+ *   [1 + j]              recall  = double(h) / double(n_rel), h = the entries with grade > 0 among the first c_j ranked ones; 0.0 if n_rel == 0
+ *   [1 + n_cuts + j]     ndcg_cut = dcg / idcg, 0.0 unless idcg > 0; dcg starts from 0.0 and adds double(max(grade, 0)) / log2[i] in rank order
+ *   [1 + 2 n_cuts + j]   r_cap   = double(h) / double(min(n_rel, c_j)), 0.0 if n_rel == 0
+ *   [1 + 3 n_cuts + j]   map_cut = (the sum in rank order from 0.0 of double(hits so far) / double(rank) at every relevant entry) / double(n_rel)
+ * d_out_flags int32 [nq]: bit 0 = evaluated (the judgement row is non-empty AND the list has a valid entry), bit 1 = n_rel[q] == 0.
+ * d_out_mean double [1 + 4 n_cuts]: every column summed over the evaluated queries in ascending q from 0.0, one rounded add each, divided
+ * by their number d_out_n (int64, one word); 0.0 without an evaluated query.  No atomic decides an output byte.
+ * 1 <= depth <= sr_max_topk(): a larger depth is SR_ERR_UNSUPPORTED; a bad size, order, cut or pointer is SR_ERR_INVALID before any device
+ * work; nq = 0 is legal.  Found on the device (SR_ERR_INVALID, the outputs are then not to be used, the library stays usable): a
+ * judgement row that is not strictly ascending or leaves the arrays (sr_last_error() names the query); a tie_key outside its range
+ * at a valid entry (query, entry); a JUDGED document that occurs twice among a list's valid entries (query, entry of the repeat, id).
+ * Waits for the stream once, to read the status.                                                                                 */
+#define SR_EVAL_ORDER_SCORE 0
+#define SR_EVAL_ORDER_LIST 1
+int sr_eval_max_cuts(void);
+int sr_eval_ranked(const float* d_scores, const int64_t* d_ids, const int32_t* d_counts, const int32_t* d_tie_key, const int64_t* d_exclude,
+                   int64_t nq, int64_t depth, const int64_t* d_qrel_indptr, const int64_t* d_qrel_ids, const int32_t* d_qrel_grades,
+                   int64_t n_qrel, const int32_t* d_n_rel, const double* d_idcg, const double* d_log2, const int32_t* h_cuts, int n_cuts,
+                   int order, int64_t rr_depth, double* d_out, int32_t* d_out_flags, double* d_out_mean, int64_t* d_out_n,
+                   sr_stream stream);
+
+/* sr_eval_randomization (same file): the two-sided paired randomization test.  d_diff double [n_cols, n]: the per-query differences a - b
+ * of 1 to 8 metric columns over n paired queries.  Permutation b in [0, n_perm) flips the sign of query q iff bit (q & 63) of
+ * mix(seed + b * W + (q >> 6)) is set, W = ceil(n / 64), in wrapping uint64 arithmetic, mix the splitmix64 step (z += 0x9E3779B97F4A7C15;
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31).  The same signs serve all columns.
+ * T_b[c] = the sum over q ascending, from +0.0, of +-diff[c, q], one rounded add each; T_obs[c] the same sum without flips.
+ * d_t_obs double [n_cols]; d_count_ge int64 [n_cols] = the number of b with |T_b[c]| >= |T_obs[c]|; p = (count + 1) / (n_perm + 1) is
+ * the caller's.  n = 0 is legal (the counts are n_perm).  n_cols outside [1, 8], n_perm outside [1, 2^31) or a null pointer:
+ * SR_ERR_INVALID before any device work.  Waits for the stream once (its partial counts are freed on return).                     */
+int sr_eval_randomization(const double* d_diff, int n_cols, int64_t n, int64_t n_perm, uint64_t seed, double* d_t_obs, int64_t* d_count_ge,
+                          sr_stream stream);
+
 /* ------------------------------------------------------- diversified search ---
  * sr_dense_mmr (csrc/dense_mmr.hip): exact greedy Maximal Marginal Relevance over a candidate list per query, on the
  * rows the dense index holds (fp32 or fp16 rows, any number of segments).  No reference counterpart.

@@ -16,6 +16,7 @@ SR_OK, SR_ERR_INVALID, SR_ERR_HIP, SR_ERR_NOMEM, SR_ERR_UNSUPPORTED = 0, 1, 2, 3
 SR_DTYPE_F32, SR_DTYPE_BF16, SR_DTYPE_F16 = 0, 1, 2
 SR_FUSE_RRF, SR_FUSE_MINMAX = 0, 1              # sr_rank_fuse's methods
 SR_MMR_SIM_IP, SR_MMR_SIM_COSINE = 0, 1         # sr_sparse_mmr's similarities
+SR_EVAL_ORDER_SCORE, SR_EVAL_ORDER_LIST = 0, 1  # sr_eval_ranked's rankings
 
 c_void_p, c_int, c_int32, c_int64, c_float, c_char_p = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
                                                          ctypes.c_int64, ctypes.c_float, ctypes.c_char_p)
@@ -121,6 +122,11 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_rank_fuse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, ctypes.POINTER(c_float), c_float, c_int, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_eval_max_cuts": (c_int, []),
+    "sr_eval_ranked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                               c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int32), c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
+    "sr_eval_randomization": (c_int, [c_void_p, c_int, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "sr_mmr_max_candidates": (c_int, []),
     "sr_dense_mmr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p]),

@@ -279,3 +279,13 @@ class RunResult(Mapping):
 
     def dump(self, path, n_threads=0):
         return write_run_json(path, self.qids, self.scores, self.positions, self.docs, self.counts, n_threads=n_threads)
+
+    def evaluate(self, qrels, order="score", rr_depth=0, exclude=None, cuts=None):
+        """The run's metrics from its arrays, on the device (evaluation.evaluate_arrays; no dict, no JSON): `qrels` an
+        evaluation.Qrels built over this run's document table, or the {qid: {doc id: grade}} dict (then built here, with `cuts`).
+        Rows are queries: a run that repeats a query id is not merged the way the dict view merges it."""
+        from .. import evaluation
+        if not isinstance(qrels, evaluation.Qrels):
+            qrels = evaluation.Qrels(qrels, self.docs, evaluation.DEFAULT_CUTS if cuts is None else cuts)
+        return evaluation.evaluate_arrays(self.scores, self.positions, self.counts, qrels, self.qids, order=order, rr_depth=rr_depth,
+                                          exclude=exclude, doc_table=self.docs)
