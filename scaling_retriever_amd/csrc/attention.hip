@@ -562,12 +562,7 @@ static int launch_long(const AttnArgs& a, hipStream_t s) {
     constexpr int KC = CKB * 32;
     constexpr size_t lds = (size_t)KC * HD * 2 + (size_t)HD * (KC + 4) * 2 + KC;
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_long_kernel<HD, CKB>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, attention_long_kernel<HD, CKB>, (int)lds));
     const int max_items = (a.nh / a.nkv) * ((a.max_seqlen + 31) / 32);
     const dim3 grid((unsigned)a.B, (unsigned)a.nkv, (unsigned)((max_items + 3) / 4));
     hipLaunchKernelGGL((attention_long_kernel<HD, CKB>), grid, dim3(256), lds, s, a);
@@ -580,12 +575,7 @@ static int launch_small(const AttnArgs& a, hipStream_t s) {
     constexpr int KC = MAXKB * 32;
     constexpr size_t lds = (size_t)KC * HD * 2 + (size_t)HD * (KC + 4) * 2 + KC;
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_small_kernel<HD, MAXKB>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, attention_small_kernel<HD, MAXKB>, (int)lds));
     const int max_items = (a.nh / a.nkv) * ((a.max_seqlen + 31) / 32);
     const dim3 grid((unsigned)a.B, (unsigned)a.nkv, (unsigned)((max_items + 4 * AT_IPW - 1) / (4 * AT_IPW)));
     hipLaunchKernelGGL((attention_small_kernel<HD, MAXKB>), grid, dim3(256), lds, s, a);
@@ -597,12 +587,7 @@ template <int HD>
 static int launch_hd(const AttnArgs& a, hipStream_t s) {
     constexpr size_t lds = (size_t)AT_KC * HD * 2 + (size_t)HD * AT_VT_LD * 2 + AT_KC;
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_kernel<HD, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, attention_kernel<HD, true>, (int)lds));
     if constexpr (HD == 128) {
         if (!a.apply_rope && a.max_seqlen > 64) {
             const char* e = sr_dev_getenv("SR_ATTN_CKB");      // A/B switch: key blocks per chunk for head dim 128 (2 | 3 | 8)

@@ -513,12 +513,8 @@ __global__ __launch_bounds__(256, af_mfma_waves(HD, NKB)) void attention_f32_mfm
 template <int HD, int NKB>
 static int launch_attention_f32_mfma_cfg(const AttnF32Args& a, size_t lds, hipStream_t s) {
     static DeviceOnce attr_once;
-    if (bool* slot = attr_once.pending()) {
-        constexpr int max_sp = NKB ? 16 * NKB : 64;
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f32_mfma_kernel<HD, NKB>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * (2 * max_sp + (NKB ? 0 : 64)) * (HD + 1))));
-        *slot = true;
-    }
+    constexpr int max_sp = NKB ? 16 * NKB : 64;
+    SR_TRY(sr_allow_lds(attr_once, attention_f32_mfma_kernel<HD, NKB>, (int)(sizeof(float) * (2 * max_sp + (NKB ? 0 : 64)) * (HD + 1))));
     const dim3 grid((unsigned)a.B, (unsigned)a.nkv), block(256);
     SR_REQUIRE(grid.y <= 65535, "attention(fp32): grid too large");
     hipLaunchKernelGGL((attention_f32_mfma_kernel<HD, NKB>), grid, block, lds, s, a);

@@ -74,6 +74,16 @@ struct DeviceOnce {
         return done[d] ? nullptr : &done[d];
     }
 };
+// lets `kernel` be launched with up to `bytes` of dynamic LDS on the current device; `once` is the caller's function-local static,
+// one per kernel instantiation
+template <typename K>
+int sr_allow_lds(DeviceOnce& once, K kernel, int bytes) {
+    if (bool* slot = once.pending()) {
+        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        *slot = true;
+    }
+    return SR_OK;
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -243,6 +253,29 @@ struct CallBuf : DeviceBuf<T> {
     CallBuf() = default;
     CallBuf(const CallBuf&) = delete;
     ~CallBuf() { this->release(); }
+};
+// copies `bytes` back to host memory and waits for the stream.  It waits after a failed copy too: the caller may have queued earlier
+// copies into host memory that goes out of scope when it returns the error.
+static inline int sr_read_back(void* host, const void* dev, size_t bytes, hipStream_t s) {
+    const hipError_t copied = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s);
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    SR_CHECK_HIP(copied);
+    return SR_OK;
+}
+// The status words of one call (a struct T of unsigned long long, ~0 = nothing found): kernels record in p what is wrong with the
+// input, the host reads them once behind the last launch.  A call that returns early frees them in the destructor; hipFree waits for
+// the kernels that were launched.
+template <typename T>
+struct CallStatus : CallBuf<T> {
+    int begin(const char* who, hipStream_t s) {
+        if (this->reserve(1, nullptr) != SR_OK) {
+            sr_set_error("%s: out of device memory for %zu status bytes", who, sizeof(T));
+            return SR_ERR_NOMEM;
+        }
+        SR_CHECK_HIP(hipMemsetAsync(this->p, 0xff, sizeof(T), s));
+        return SR_OK;
+    }
+    int read(T* host, hipStream_t s) { return sr_read_back(host, this->p, sizeof(T), s); }
 };
 
 // ---- per-launch HIP event log (measurement hook of the search handles) ----

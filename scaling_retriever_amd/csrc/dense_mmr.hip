@@ -257,10 +257,7 @@ extern "C" int sr_dense_mmr(sr_dense_index* idx, const int64_t* d_ids, const flo
     a.st = idx->pair_status;
     const void* fn = idx->row_dtype == SR_DTYPE_F16 ? (const void*)dense_mmr_kernel<_Float16> : (const void*)dense_mmr_kernel<float>;
     static DeviceOnce lds_set[2];
-    if (bool* slot = lds_set[idx->row_dtype == SR_DTYPE_F16 ? 1 : 0].pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max - (int)fixed_bytes));
-        *slot = true;
-    }
+    SR_TRY(sr_allow_lds(lds_set[idx->row_dtype == SR_DTYPE_F16 ? 1 : 0], fn, lds_max - (int)fixed_bytes));
     if (idx->row_dtype == SR_DTYPE_F16)
         hipLaunchKernelGGL(dense_mmr_kernel<_Float16>, dim3((unsigned)nq), dim3(64 * nw), lds, s, a);
     else

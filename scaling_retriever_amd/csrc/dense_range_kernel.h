@@ -327,11 +327,7 @@ static int launch_dense_range_t(const DenseRangeArgs& a, int n_chunks_seg, hipSt
     const void* fn = FILL ? reinterpret_cast<const void*>(&dense_range_fill_kernel<WN, T, FILTER>)
                           : reinterpret_cast<const void*>(&dense_range_count_kernel<WN, T, FILTER>);
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, fn, (int)lds));
     dim3 grid((unsigned)ceil_div64(a.nq, TN), (unsigned)n_chunks_seg);
     if (FILL) hipLaunchKernelGGL((dense_range_fill_kernel<WN, T, FILTER>), grid, dim3(512), lds, s, a);
     else hipLaunchKernelGGL((dense_range_count_kernel<WN, T, FILTER>), grid, dim3(512), lds, s, a);

@@ -346,12 +346,7 @@ static int launch_dense_pipe_t(const DenseArgs& a, int64_t rows, hipStream_t s) 
     constexpr int TN = 128 * WN;
     constexpr size_t lds = sizeof(float) * 3 * (256 + TN) * (16 + 4);
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_score_pipe_kernel<WN, T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, dense_score_pipe_kernel<WN, T>, (int)lds));
     dim3 grid((unsigned)ceil_div64(rows, 256), (unsigned)ceil_div64(a.nq, TN));
     hipLaunchKernelGGL((dense_score_pipe_kernel<WN, T>), grid, dim3(512), lds, s, a);
     SR_CHECK_LAUNCH();
@@ -367,12 +362,7 @@ static int launch_dense_t(const DenseArgs& a, int64_t rows, hipStream_t s) {
     constexpr int TM = 32 * WM * WAVES_M, TN = 32 * WN * WAVES_N;
     constexpr size_t lds = sizeof(float) * 2 * (TM + TN) * (16 + 4);
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_score_kernel<T, WAVES_M, WAVES_N, WM, WN>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, dense_score_kernel<T, WAVES_M, WAVES_N, WM, WN>, (int)lds));
     dim3 grid((unsigned)ceil_div64(rows, TM), (unsigned)ceil_div64(a.nq, TN));
     hipLaunchKernelGGL((dense_score_kernel<T, WAVES_M, WAVES_N, WM, WN>), grid, dim3(64 * WAVES_M * WAVES_N), lds, s, a);
     SR_CHECK_LAUNCH();

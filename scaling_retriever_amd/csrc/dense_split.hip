@@ -92,15 +92,9 @@ int launch_dense_split(const DenseSplitArgs& a, hipStream_t s) {
     SR_REQUIRE(!a.mask || a.upper_bound, "dense_split: a document mask goes with the upper-bound pass only");
     SR_REQUIRE(!a.mask_qoff || a.mask, "dense_split: per-query mask offsets without a mask");
     constexpr size_t lds = 2 * (size_t)(SP_BN + SP_BM) * 128 + SP_BN * 2 * sizeof(float) + SP_BM * 4 * sizeof(float) + SP_BM * sizeof(float);
-    static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_split_kernel<false, false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_split_kernel<true, false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    static DeviceOnce attr_once[2];
+    SR_TRY(sr_allow_lds(attr_once[0], dense_split_kernel<false, false>, (int)lds));
+    SR_TRY(sr_allow_lds(attr_once[1], dense_split_kernel<true, false>, (int)lds));
     DenseSplitArgs b = a;
     if (const char* e = sr_dev_getenv("SR_SPLIT_BLOCKTEST")) if (atoi(e) == 0) b.dxy_gmax = nullptr;     // A/B switch: every bound formed
     SR_REQUIRE(!b.dxy_gmax || a.row_begin % SP_BN == 0, "dense_split: the block test needs launches that start on a tile boundary");

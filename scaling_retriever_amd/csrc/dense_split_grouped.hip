@@ -6,12 +6,7 @@
 int launch_dense_split_grouped(const DenseSplitArgs& a, unsigned grid, size_t lds, hipStream_t s) {
     SR_REQUIRE(a.upper_bound && a.mask && a.mask_qoff && a.n_pairs == 1, "dense_split(grouped): the upper-bound pass with per-query masks only");
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_split_kernel<true, true, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, dense_split_kernel<true, true, true>, (int)lds));
     hipLaunchKernelGGL((dense_split_kernel<true, true, true>), dim3(grid), dim3(512), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;

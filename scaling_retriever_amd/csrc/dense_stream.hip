@@ -136,15 +136,9 @@ static int launch_dense_stream_t(const DenseStreamArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)ceil_div64(rows, DS_TM));
     const int nqb = (a.nq + 15) / 16;
     const size_t lds = (size_t)nqb * 16 * DS_LDQ * sizeof(float);
-    static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stream_kernel<3, T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 16 * DS_LDQ * 4));
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stream_kernel<4, T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 16 * DS_LDQ * 4));
-        *attr_slot = true;
-    }
+    static DeviceOnce attr_once[2];
+    SR_TRY(sr_allow_lds(attr_once[0], dense_stream_kernel<3, T>, 3 * 16 * DS_LDQ * 4));
+    SR_TRY(sr_allow_lds(attr_once[1], dense_stream_kernel<4, T>, 4 * 16 * DS_LDQ * 4));
     switch (nqb) {
         case 1: hipLaunchKernelGGL((dense_stream_kernel<1, T>), grid, dim3(256), lds, s, a); break;
         case 2: hipLaunchKernelGGL((dense_stream_kernel<2, T>), grid, dim3(256), lds, s, a); break;

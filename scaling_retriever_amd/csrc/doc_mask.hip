@@ -130,17 +130,15 @@ extern "C" int sr_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t*
     SR_REQUIRE(m >= 0 && n_bits >= 0 && n_bits <= (1ll << 32), "sr_doc_mask_from_list: bad sizes m=%lld n_bits=%lld", (long long)m, (long long)n_bits);
     SR_REQUIRE((d_list || m == 0) && (d_words || n_bits == 0), "sr_doc_mask_from_list: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    int* d_bad = nullptr;
-    SR_CHECK_HIP(hipMalloc((void**)&d_bad, sizeof(int)));
+    CallBuf<int> d_bad;
+    SR_TRY(d_bad.reserve(1, "sr_doc_mask_from_list"));
+    SR_CHECK_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), s));
+    SR_TRY(launch_doc_mask_from_list(d_list, m, d_words, n_bits, nullptr, d_bad.p, s));
     int h_bad = 0;
-    int rc = hipMemsetAsync(d_bad, 0, sizeof(int), s) == hipSuccess ? SR_OK : SR_ERR_HIP;
-    if (rc == SR_OK) rc = launch_doc_mask_from_list(d_list, m, d_words, n_bits, nullptr, d_bad, s);
-    if (rc == SR_OK && (hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
+    if (sr_read_back(&h_bad, d_bad.p, sizeof(int), s) != SR_OK) {
         sr_set_error("sr_doc_mask_from_list: reading the status back failed");
-        rc = SR_ERR_HIP;
+        return SR_ERR_HIP;
     }
-    (void)hipFree(d_bad);
-    SR_TRY(rc);
     SR_REQUIRE(h_bad == 0, "sr_doc_mask_from_list: the list holds an entry outside [0, %lld) (the other entries were set)", (long long)n_bits);
     return SR_OK;
 }
@@ -151,15 +149,15 @@ extern "C" int sr_doc_list_from_mask(const uint32_t* d_words, int64_t n_bits, in
                (long long)n_bits, (long long)capacity);
     SR_REQUIRE((d_words || n_bits == 0) && (d_list || capacity == 0) && d_count, "sr_doc_list_from_mask: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    int64_t* d_blocks = nullptr;
-    if (n_bits > 0) SR_CHECK_HIP(hipMalloc((void**)&d_blocks, (size_t)doc_mask_blocks(n_bits) * sizeof(int64_t)));
-    int rc = launch_doc_mask_count(d_words, n_bits, d_blocks, d_count, s);
-    if (rc == SR_OK) rc = launch_doc_mask_expand(d_words, n_bits, d_blocks, d_list, capacity, s);
-    if (d_blocks) {
-        if (rc == SR_OK && hipStreamSynchronize(s) != hipSuccess) { sr_set_error("sr_doc_list_from_mask: the stream failed"); rc = SR_ERR_HIP; }
-        (void)hipFree(d_blocks);                          // the per-workgroup counts: scratch of this call
+    CallBuf<int64_t> d_blocks;                            // the per-workgroup counts: scratch of this call
+    if (n_bits > 0) SR_TRY(d_blocks.reserve(doc_mask_blocks(n_bits), "sr_doc_list_from_mask"));
+    SR_TRY(launch_doc_mask_count(d_words, n_bits, d_blocks.p, d_count, s));
+    SR_TRY(launch_doc_mask_expand(d_words, n_bits, d_blocks.p, d_list, capacity, s));
+    if (d_blocks.p && hipStreamSynchronize(s) != hipSuccess) {
+        sr_set_error("sr_doc_list_from_mask: the stream failed");
+        return SR_ERR_HIP;
     }
-    return rc;
+    return SR_OK;
 }
 
 // one thread per destination word: bit i of dst = bit map[i] of src where map[i] names a source bit, else 0

@@ -13,12 +13,12 @@
 //                          by a last pass (integer sums: the bytes do not depend on the order).
 // All arithmetic on the result path is fp64 with contraction off; `/` is the correctly rounded division.  The kernels compute no
 // logarithm: log2(i + 2) and the ideal DCGs come from the host.
-#include "hybrid_fuse.h"
+#include "block_primitives.h"
 #include <limits.h>
 
 #define EV_MAX_CUTS 16
 #define EV_MAX_COLS 8
-#define EV_THREADS HF_THREADS
+#define EV_THREADS 256                  // the four waves of sr_block_scan and sr_block_min
 #define EV_MEAN_ROWS 32                 // queries per LDS tile of the means kernel
 #define EV_CHUNK 256                    // queries per LDS tile of the randomization kernel (a multiple of 64)
 #define EV_MAX_PERM_BLOCKS 4096
@@ -40,48 +40,6 @@ struct EvalArgs {
     double* out; int32_t* flags;
     EvalStatus* st;
 };
-
-// bitonic sort of a[0, P) in LDS, descending (P a power of two >= 2), as rf_sort in rank_fuse.hip.  The caller has a barrier behind
-// its stores.
-__device__ inline void ev_sort_desc(uint64_t* a, int P) {
-    const int half = P >> 1;
-    for (int size = 2; size <= P; size <<= 1)
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < half; t += EV_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int p = i | j;
-                const bool up = (i & size) != 0;
-                const uint64_t x = a[i], y = a[p];
-                if (up ? (x > y) : (x < y)) {
-                    a[i] = y;
-                    a[p] = x;
-                }
-            }
-            __syncthreads();
-        }
-}
-
-__device__ inline int ev_pow2(int v) {
-    int p = 2;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-// smallest v over the workgroup (red: 4 LDS words).  Two barriers.
-__device__ inline int ev_block_min(int v, int* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int m = red[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) m = red[w] < m ? red[w] : m;
-    __syncthreads();
-    return m;
-}
 
 __global__ __launch_bounds__(EV_THREADS) void eval_ranked_kernel(EvalArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -125,15 +83,15 @@ __global__ __launch_bounds__(EV_THREADS) void eval_ranked_kernel(EvalArgs a) {
         }
         if (r < depth) jw[r] = j;
         int tot;
-        const int ex = hf_block_scan(j >= 0 ? 1 : 0, lw, tot);
+        const int ex = sr_block_scan(j >= 0 ? 1 : 0, lw, tot);
         if (j >= 0) keys[njud + ex] = ((uint64_t)(uint32_t)j << 32) | (uint64_t)r;
         njud += tot;
     }
     if (njud >= 2) {                                            // uniform: njud is the scan's total
-        const int P = ev_pow2(njud);
+        const int P = sr_pow2_at_least(njud, 2);
         for (int i = njud + tid; i < P; i += EV_THREADS) keys[i] = 0ull;
         __syncthreads();
-        ev_sort_desc(keys, P);
+        sr_block_sort<EV_THREADS, true>(keys, P);
         // equal indexes stand together, the later slot first: the entry in front of an equal one is a repeat
         for (int i = tid; i + 1 < njud; i += EV_THREADS) {
             const uint64_t x = keys[i];
@@ -149,7 +107,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_ranked_kernel(EvalArgs a) {
         const int r = base + tid;
         const bool valid = r < depth && jw[r] >= -1;
         int tot;
-        const int ex = hf_block_scan(valid ? 1 : 0, lw, tot);
+        const int ex = sr_block_scan(valid ? 1 : 0, lw, tot);
         if (valid) {
             const int v = nv + ex;
             uint64_t key = (uint64_t)(0xFFFF - r);
@@ -165,10 +123,10 @@ __global__ __launch_bounds__(EV_THREADS) void eval_ranked_kernel(EvalArgs a) {
         nv += tot;
     }
     if (a.order == SR_EVAL_ORDER_SCORE && nv >= 2) {
-        const int P = ev_pow2(nv);
+        const int P = sr_pow2_at_least(nv, 2);
         for (int i = nv + tid; i < P; i += EV_THREADS) keys[i] = 0ull;  // below every key: the high word of a key is never 0
         __syncthreads();
-        ev_sort_desc(keys, P);
+        sr_block_sort<EV_THREADS, true>(keys, P);
     } else {
         __syncthreads();
     }
@@ -190,17 +148,17 @@ __global__ __launch_bounds__(EV_THREADS) void eval_ranked_kernel(EvalArgs a) {
         int tot, frank = p + 1;
         if (rr_end < depth) {                                   // uniform
             int ftot;
-            frank = nflag + hf_block_scan(flag ? 1 : 0, lw, ftot) + 1;
+            frank = nflag + sr_block_scan(flag ? 1 : 0, lw, ftot) + 1;
             nflag += ftot;
         }
-        const int ex = hf_block_scan(rel ? 1 : 0, lw, tot);     // its barriers stand behind the loads of keys
+        const int ex = sr_block_scan(rel ? 1 : 0, lw, tot);     // its barriers stand behind the loads of keys
         if (rel) {
             keys[nrel + ex] = ((uint64_t)(uint32_t)(p + 1) << 32) | (uint64_t)(uint32_t)g;    // nrel + ex <= p: a slot already read
             if (flag && frank < rr_rank) rr_rank = frank;
         }
         nrel += tot;
     }
-    rr_rank = ev_block_min(rr_rank, red);                       // its barriers stand behind the stores of keys
+    rr_rank = sr_block_min(rr_rank, red);                       // its barriers stand behind the stores of keys
 
     const bool evaluated = hi > lo && nv > 0;
     const int n_rel = a.n_rel[q];
@@ -289,40 +247,26 @@ extern "C" int sr_eval_ranked(const float* d_scores, const int64_t* d_ids, const
     SR_REQUIRE(n_cuts == 0 || d_idcg, "sr_eval_ranked: null pointer (idcg)");
     hipStream_t s = (hipStream_t)stream;
     const int ncol = 1 + 4 * n_cuts;
-    EvalStatus* st = nullptr;
-    if (hipMalloc((void**)&st, sizeof(EvalStatus)) != hipSuccess) {
-        (void)hipGetLastError();
-        sr_set_error("sr_eval_ranked: out of device memory for %zu status bytes", sizeof(EvalStatus));
-        return SR_ERR_NOMEM;
-    }
+    CallStatus<EvalStatus> st;
+    SR_TRY(st.begin("sr_eval_ranked", s));
     EvalArgs a;
     a.scores = d_scores; a.ids = d_ids; a.counts = d_counts; a.tie = d_tie_key; a.exclude = d_exclude;
     a.indptr = d_qrel_indptr; a.qrel_ids = d_qrel_ids; a.grades = d_qrel_grades; a.n_qrel = n_qrel;
     a.n_rel = d_n_rel; a.idcg = d_idcg; a.log2t = d_log2;
     for (int c = 0; c < EV_MAX_CUTS; ++c) a.cuts[c] = c < n_cuts ? h_cuts[c] : 0;
-    a.n_cuts = n_cuts; a.order = order; a.depth = (int)depth; a.pmax = 2;
-    while (a.pmax < depth) a.pmax <<= 1;
+    a.n_cuts = n_cuts; a.order = order; a.depth = (int)depth; a.pmax = sr_pow2_at_least(depth, 2);
     a.rr_depth = rr_depth; a.nq = nq;
-    a.out = d_out; a.flags = d_out_flags; a.st = st;
-    EvalStatus h;
-    auto run = [&]() -> int {
-        SR_CHECK_HIP(hipMemsetAsync(st, 0xff, sizeof(EvalStatus), s));
-        if (nq > 0) {
-            const size_t lds = (size_t)a.pmax * 8 + (size_t)depth * 4;      // 48 KB at the cap
-            hipLaunchKernelGGL(eval_ranked_kernel, dim3((unsigned)nq), dim3(EV_THREADS), lds, s, a);
-            SR_CHECK_LAUNCH();
-        }
-        hipLaunchKernelGGL(eval_means_kernel, dim3(1), dim3(EV_THREADS), 0, s, (const double*)d_out, (const int32_t*)d_out_flags, nq, ncol,
-                           d_out_mean, d_out_n);
+    a.out = d_out; a.flags = d_out_flags; a.st = st.p;
+    if (nq > 0) {
+        const size_t lds = (size_t)a.pmax * 8 + (size_t)depth * 4;      // 48 KB at the cap
+        hipLaunchKernelGGL(eval_ranked_kernel, dim3((unsigned)nq), dim3(EV_THREADS), lds, s, a);
         SR_CHECK_LAUNCH();
-        SR_CHECK_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        return SR_OK;
-    };
-    const int rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    (void)hipFree(st);
-    SR_TRY(rc);
+    }
+    hipLaunchKernelGGL(eval_means_kernel, dim3(1), dim3(EV_THREADS), 0, s, (const double*)d_out, (const int32_t*)d_out_flags, nq, ncol,
+                       d_out_mean, d_out_n);
+    SR_CHECK_LAUNCH();
+    EvalStatus h;
+    SR_TRY(st.read(&h, s));
     if (h.bad_qrel != ~0ull) {
         sr_set_error("sr_eval_ranked: the judged ids of query %llu are not strictly ascending inside the judgement arrays", h.bad_qrel);
         return SR_ERR_INVALID;
@@ -414,7 +358,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_perm_kernel(const double* dif
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         int tot;
-        (void)hf_block_scan((int)cnt[c], lw, tot);              // at most 2^31 / gridDim.x permutations per thread: fits an int
+        (void)sr_block_scan((int)cnt[c], lw, tot);              // at most 2^31 / gridDim.x permutations per thread: fits an int
         if (tid == 0) part[(int64_t)blockIdx.x * NC + c] = tot;
     }
 }
@@ -448,25 +392,20 @@ extern "C" int sr_eval_randomization(const double* d_diff, int n_cols, int64_t n
     if (blocks > EV_MAX_PERM_BLOCKS) blocks = EV_MAX_PERM_BLOCKS;
     CallBuf<int64_t> part;
     SR_TRY(part.reserve(blocks * n_cols, "sr_eval_randomization"));
-    auto run = [&]() -> int {
-        hipLaunchKernelGGL(eval_tobs_kernel, dim3(1), dim3(64), 0, s, d_diff, n_cols, n, d_t_obs);
-        SR_CHECK_LAUNCH();
-        switch (n_cols) {
-            case 1: SR_TRY(launch_perm<1>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-            case 2: SR_TRY(launch_perm<2>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-            case 3: SR_TRY(launch_perm<3>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-            case 4: SR_TRY(launch_perm<4>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-            case 5: SR_TRY(launch_perm<5>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-            case 6: SR_TRY(launch_perm<6>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-            case 7: SR_TRY(launch_perm<7>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-            default: SR_TRY(launch_perm<8>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
-        }
-        hipLaunchKernelGGL(eval_count_kernel, dim3(1), dim3(64), 0, s, (const int64_t*)part.p, (int)blocks, n_cols, d_count_ge);
-        SR_CHECK_LAUNCH();
-        SR_CHECK_HIP(hipStreamSynchronize(s));                  // the partial counts are freed when the call returns
-        return SR_OK;
-    };
-    const int rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    return rc;
+    hipLaunchKernelGGL(eval_tobs_kernel, dim3(1), dim3(64), 0, s, d_diff, n_cols, n, d_t_obs);
+    SR_CHECK_LAUNCH();
+    switch (n_cols) {
+        case 1: SR_TRY(launch_perm<1>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+        case 2: SR_TRY(launch_perm<2>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+        case 3: SR_TRY(launch_perm<3>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+        case 4: SR_TRY(launch_perm<4>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+        case 5: SR_TRY(launch_perm<5>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+        case 6: SR_TRY(launch_perm<6>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+        case 7: SR_TRY(launch_perm<7>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+        default: SR_TRY(launch_perm<8>(d_diff, n, n_perm, seed, d_t_obs, part.p, (int)blocks, s)); break;
+    }
+    hipLaunchKernelGGL(eval_count_kernel, dim3(1), dim3(64), 0, s, (const int64_t*)part.p, (int)blocks, n_cols, d_count_ge);
+    SR_CHECK_LAUNCH();
+    SR_CHECK_HIP(hipStreamSynchronize(s));                  // the partial counts are freed when the call returns
+    return SR_OK;
 }

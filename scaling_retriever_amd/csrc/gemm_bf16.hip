@@ -1117,12 +1117,7 @@ static int launch_cfg(const GemmArgs& g_in, hipStream_t s) {
     constexpr int BN = 16 * NB * WAVES_N, BM = 16 * MB * WAVES_M;
     constexpr size_t lds = NS * (size_t)(BN + BM) * 128 + (KL == 1 ? 4 * 8192 : 0);     // KL = 1: + the waves' output staging (160 KB in all)
     static DeviceOnce attr_once;
-    bool* attr_slot = attr_once.pending();
-    if (attr_slot) {
-        SR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<EPI, WAVES_N, WAVES_M, NB, MB, PIPE, NS, KL>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *attr_slot = true;
-    }
+    SR_TRY(sr_allow_lds(attr_once, gemm_bf16_kernel<EPI, WAVES_N, WAVES_M, NB, MB, PIPE, NS, KL>, (int)lds));
     GemmArgs g = g_in;
     // Tile order.  Feature-tile-fastest keeps an XCD on the same 1/8 of W (good while W fits the Infinity Cache).  A weight
     // matrix far larger than that (the 525 MB vocabulary head) would be streamed from HBM once per token tile: walk the

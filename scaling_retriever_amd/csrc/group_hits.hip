@@ -13,11 +13,11 @@
 //                     take 21) and merged into them by one reversed compare and a 6-stage bitonic merge - cross-lane exchanges only,
 //                     no LDS array, no atomic.  Once m entries are held, a tile none of whose entries beats the m-th is skipped after
 //                     one ballot, which is what keeps a tenant-sized segment cheap.
-#include "common.h"
+#include "block_primitives.h"
 #include <float.h>
 #include <limits.h>
 
-#define GH_THREADS 256
+#define GH_THREADS 256                          // the four waves of sr_block_scan
 #define GH_LANES 8                              // lanes per slot
 #define GH_GROUPS (GH_THREADS / GH_LANES)       // slots a workgroup works on at a time
 #define GH_SLOTS 256                            // slots per workgroup
@@ -141,28 +141,6 @@ __global__ __launch_bounds__(GH_THREADS) void group_members_kernel(MembersArgs a
     }
 }
 
-// exclusive prefix of v over the 256 threads of a workgroup in 64 bits (lw: 4 LDS words); total = the sum.  Two barriers.
-__device__ inline long long gh_block_scan(long long v, long long* lw, long long& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const long long o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) lw[wave] = incl;
-    __syncthreads();
-    long long base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wave) base += lw[w];
-        total += lw[w];
-    }
-    __syncthreads();
-    return base + incl - v;
-}
-
 // One workgroup: sums [n_sums] -> their exclusive prefix in place; out3 = {the smallest status word, its workgroup's detail (-1 without
 // one), the sum}; *d_total (nullable) = the sum.  per_block: positions per workgroup of the kernel that wrote the status words.
 __global__ __launch_bounds__(GH_THREADS) void gh_finish_kernel(long long* sums, int64_t n_sums, const unsigned long long* status,
@@ -176,7 +154,7 @@ __global__ __launch_bounds__(GH_THREADS) void gh_finish_kernel(long long* sums, 
         const int64_t i = b0 + tid;
         const long long v = i < n_sums ? sums[i] : 0;
         long long total;
-        const long long excl = gh_block_scan(v, lw, total);
+        const long long excl = sr_block_scan(v, lw, total);
         if (i < n_sums) sums[i] = carry + excl;
         carry += total;
     }
@@ -204,7 +182,7 @@ __global__ __launch_bounds__(GH_THREADS) void group_members_offsets_kernel(const
     const int64_t slot = (int64_t)blockIdx.x * GH_SLOTS + threadIdx.x;
     const long long v = slot < n_slots ? cnt[slot] : 0;
     long long total;
-    const long long excl = gh_block_scan(v, lw, total);
+    const long long excl = sr_block_scan(v, lw, total);
     if (slot < n_slots) out_indptr[slot] = block_off[blockIdx.x] + excl;
 }
 
@@ -231,13 +209,12 @@ static int members_run(bool fill, const char* who, const int32_t* d_slot_keys, i
         return SR_OK;
     }
     const int64_t nb = ceil_div64(n_slots, GH_SLOTS);
-    // the call's scratch, freed before it returns: a count per slot (count only), then per workgroup a sum, a status word and its detail,
+    // the call's scratch, freed when it returns: a count per slot (count only), then per workgroup a sum, a status word and its detail,
     // then the three words read back
     const size_t cnt_bytes = fill ? 0 : (((size_t)n_slots * sizeof(int32_t) + 7) & ~(size_t)7);
     const size_t bytes = cnt_bytes + (size_t)nb * 24 + 3 * sizeof(long long);
-    unsigned char* scratch = nullptr;
-    if (hipMalloc((void**)&scratch, bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    CallBuf<unsigned char> scratch;
+    if (scratch.reserve((int64_t)bytes, nullptr) != SR_OK) {
         sr_set_error("%s: out of device memory for %zu scratch bytes", who, bytes);
         return SR_ERR_NOMEM;
     }
@@ -245,32 +222,24 @@ static int members_run(bool fill, const char* who, const int32_t* d_slot_keys, i
     a.slot_keys = d_slot_keys; a.n_slots = n_slots; a.kg = kg;
     a.uniq = d_uniq_keys; a.n_groups = n_groups; a.member_indptr = d_member_indptr; a.member_ids = d_member_ids; a.n_members = n_members;
     a.words = d_mask_words; a.n_masks = n_masks; a.n_bits = n_bits; a.n_words = ceil_div64(n_bits, 32); a.query_group = d_query_group;
-    a.cnt = reinterpret_cast<int32_t*>(scratch);
-    a.block_sums = reinterpret_cast<long long*>(scratch + cnt_bytes);
+    a.cnt = reinterpret_cast<int32_t*>(scratch.p);
+    a.block_sums = reinterpret_cast<long long*>(scratch.p + cnt_bytes);
     a.block_status = reinterpret_cast<unsigned long long*>(a.block_sums + nb);
     a.block_detail = reinterpret_cast<long long*>(a.block_status + nb);
     a.out_indptr = d_indptr; a.out_ids = d_out_ids; a.capacity = capacity;
     long long* d_out3 = a.block_detail + nb;
+    if (fill) hipLaunchKernelGGL(group_members_kernel<true>, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(group_members_kernel<false>, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, a);
+    SR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gh_finish_kernel, dim3(1), dim3(GH_THREADS), 0, s, a.block_sums, fill ? 0 : nb, a.block_status, a.block_detail, nb,
+                       (int64_t)GH_SLOTS, fill ? nullptr : d_indptr + n_slots, d_out3);
+    SR_CHECK_LAUNCH();
+    if (!fill) {
+        hipLaunchKernelGGL(group_members_offsets_kernel, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, a.cnt, a.block_sums, n_slots, d_indptr);
+        SR_CHECK_LAUNCH();
+    }
     long long h[3] = {-1, -1, 0};
-    auto run = [&]() -> int {
-        if (fill) hipLaunchKernelGGL(group_members_kernel<true>, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(group_members_kernel<false>, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, a);
-        SR_CHECK_LAUNCH();
-        hipLaunchKernelGGL(gh_finish_kernel, dim3(1), dim3(GH_THREADS), 0, s, a.block_sums, fill ? 0 : nb, a.block_status, a.block_detail, nb,
-                           (int64_t)GH_SLOTS, fill ? nullptr : d_indptr + n_slots, d_out3);
-        SR_CHECK_LAUNCH();
-        if (!fill) {
-            hipLaunchKernelGGL(group_members_offsets_kernel, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, a.cnt, a.block_sums, n_slots, d_indptr);
-            SR_CHECK_LAUNCH();
-        }
-        SR_CHECK_HIP(hipMemcpyAsync(h, d_out3, sizeof(h), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        return SR_OK;
-    };
-    const int rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    SR_TRY(rc);
+    SR_TRY(sr_read_back(h, d_out3, sizeof(h), s));
     if ((unsigned long long)h[0] != GH_NONE) {
         const long long slot = (long long)((unsigned long long)h[0] >> 2), q = slot / kg, j = slot % kg;
         const int code = (int)(h[0] & 3);
@@ -424,34 +393,25 @@ extern "C" int sr_segment_topm(const float* d_scores, const int64_t* d_ids, cons
     hipStream_t s = (hipStream_t)stream;
     const int64_t nb = ceil_div64(n_segs, GH_CHECK_PER);
     const size_t bytes = (size_t)nb * sizeof(unsigned long long) + 3 * sizeof(long long);
-    unsigned char* scratch = nullptr;
-    if (hipMalloc((void**)&scratch, bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    CallBuf<unsigned char> scratch;
+    if (scratch.reserve((int64_t)bytes, nullptr) != SR_OK) {
         sr_set_error("sr_segment_topm: out of device memory for %zu scratch bytes", bytes);
         return SR_ERR_NOMEM;
     }
-    unsigned long long* d_status = reinterpret_cast<unsigned long long*>(scratch);
+    unsigned long long* d_status = reinterpret_cast<unsigned long long*>(scratch.p);
     long long* d_out3 = reinterpret_cast<long long*>(d_status + nb);
     TopmArgs a;
     a.scores = d_scores; a.ids = d_ids; a.indptr = d_seg_indptr; a.n_segs = n_segs; a.m = m; a.use_threshold = use_threshold;
     a.threshold = threshold; a.pad_score = pad_score; a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.out_counts = d_out_counts;
+    hipLaunchKernelGGL(segment_check_kernel, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, d_seg_indptr, n_segs, d_status);
+    SR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gh_finish_kernel, dim3(1), dim3(GH_THREADS), 0, s, (long long*)nullptr, (int64_t)0, d_status,
+                       (const long long*)nullptr, nb, (int64_t)GH_CHECK_PER, (int64_t*)nullptr, d_out3);
+    SR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(segment_topm_kernel, dim3((unsigned)ceil_div64(n_segs, GH_THREADS / 64)), dim3(GH_THREADS), 0, s, a);
+    SR_CHECK_LAUNCH();
     long long h[3] = {-1, -1, 0};
-    auto run = [&]() -> int {
-        hipLaunchKernelGGL(segment_check_kernel, dim3((unsigned)nb), dim3(GH_THREADS), 0, s, d_seg_indptr, n_segs, d_status);
-        SR_CHECK_LAUNCH();
-        hipLaunchKernelGGL(gh_finish_kernel, dim3(1), dim3(GH_THREADS), 0, s, (long long*)nullptr, (int64_t)0, d_status,
-                           (const long long*)nullptr, nb, (int64_t)GH_CHECK_PER, (int64_t*)nullptr, d_out3);
-        SR_CHECK_LAUNCH();
-        SR_CHECK_HIP(hipMemcpyAsync(h, d_out3, sizeof(h), hipMemcpyDeviceToHost, s));
-        hipLaunchKernelGGL(segment_topm_kernel, dim3((unsigned)ceil_div64(n_segs, GH_THREADS / 64)), dim3(GH_THREADS), 0, s, a);
-        SR_CHECK_LAUNCH();
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        return SR_OK;
-    };
-    const int rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    SR_TRY(rc);
+    SR_TRY(sr_read_back(h, d_out3, sizeof(h), s));          // behind the last launch: no copy is in flight when a launch fails
     if ((unsigned long long)h[0] != GH_NONE) {
         const long long i = (long long)((unsigned long long)h[0] >> 2);
         if ((h[0] & 3) == GH_BAD_START) sr_set_error("sr_segment_topm: seg_indptr must start at 0");

@@ -6,29 +6,11 @@
 //                    of the OTHER list below it (a binary search) - so a long ascending A is only ever read, never staged.
 //   sr_hybrid_rank   per query the top-k of a ragged candidate list by (fused score descending, tie ascending): an 8-pass radix select
 //                    of the k-th largest 64-bit key, the kept keys sorted in LDS; plus the certificate flag and the range threshold.
+#include "block_primitives.h"
 #include "hybrid_fuse.h"
 #include "sparse_index.h"
 #include <float.h>
 #include <math.h>
-
-// bitonic sort, ascending, of a[0, P) in LDS (P a power of two); the caller has a barrier behind its stores
-__device__ inline void hf_sort_asc(uint32_t* a, int P) {
-    for (int size = 2; size <= P; size <<= 1)
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P; i += HF_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool asc = (i & size) == 0;
-                    const uint32_t x = a[i], y = a[ixj];
-                    if (asc ? (x > y) : (x < y)) {
-                        a[i] = y;
-                        a[ixj] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
 
 // a[0, P) ascending with HF_EMPTY slots at its end (P a power of two, <= 16 * 256) -> a[0, n) strictly ascending, in place; returns n.
 // Thread t owns slots [t * per, (t + 1) * per): it reads them (and its predecessor) before the scan's barriers and writes behind them.
@@ -49,7 +31,7 @@ __device__ inline int hf_unique(uint32_t* a, int P, int* lw) {
         prev = v[i];
     }
     int total;
-    int at = hf_block_scan(cnt, lw, total);
+    int at = sr_block_scan(cnt, lw, total);
 #pragma unroll
     for (int i = 0; i < 16; ++i)
         if (keep & (1u << i)) a[at++] = v[i];
@@ -125,7 +107,7 @@ __global__ __launch_bounds__(HF_THREADS) void hybrid_union_kernel(UnionArgs a) {
             sa[i] = v;
         }
     __syncthreads();
-    hf_sort_asc(sb, a.Pb);
+    sr_block_sort<HF_THREADS, false>(sb, a.Pb);
     const int nB = hf_unique(sb, a.Pb, lw);
     int64_t a0 = 0, nA;
     if (CSR) {
@@ -133,7 +115,7 @@ __global__ __launch_bounds__(HF_THREADS) void hybrid_union_kernel(UnionArgs a) {
         nA = a.a_indptr[q + 1] - a0;
         nA = nA < 0 ? 0 : nA;
     } else {
-        hf_sort_asc(sa, a.Pa);
+        sr_block_sort<HF_THREADS, false>(sa, a.Pa);
         nA = hf_unique(sa, a.Pa, lw);
     }
 
@@ -155,7 +137,7 @@ __global__ __launch_bounds__(HF_THREADS) void hybrid_union_kernel(UnionArgs a) {
         }
     }
     int n_only;
-    int at = hf_block_scan(cnt, lw, n_only);
+    int at = sr_block_scan(cnt, lw, n_only);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int j = b0 + i;
@@ -195,19 +177,10 @@ __global__ __launch_bounds__(HF_THREADS) void hybrid_union_kernel(UnionArgs a) {
             }
 }
 
-static int hf_next_pow2(int64_t v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 template <bool CSR, bool FILL>
 static int launch_union(const UnionArgs& a, int64_t nq, int ny, hipStream_t s) {
     static DeviceOnce lds_set;
-    if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)hybrid_union_kernel<CSR, FILL>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024 - 64));
-        *slot = true;
-    }
+    SR_TRY(sr_allow_lds(lds_set, hybrid_union_kernel<CSR, FILL>, 64 * 1024 - 64));
     const size_t lds = sizeof(uint32_t) * ((size_t)a.Pb * 2 + 1 + (CSR ? 0 : (size_t)a.Pa));     // <= 48 KB + 4
     hipLaunchKernelGGL((hybrid_union_kernel<CSR, FILL>), dim3((unsigned)nq, (unsigned)ny), dim3(HF_THREADS), lds, s, a);
     SR_CHECK_LAUNCH();
@@ -234,46 +207,36 @@ extern "C" int sr_hybrid_union(const int64_t* d_a_ids, const int64_t* d_a_indptr
         return SR_OK;
     }
     SR_REQUIRE(d_a_ids && d_b_spos && d_b_counts && d_s2d && d_d2s && d_out_dpos && d_out_spos && d_out_tie, "sr_hybrid_union: null pointer");
-    // the call's scratch: nq counts and the status words, freed before it returns (it waits for the stream to read the status)
-    unsigned char* scratch = nullptr;
-    const size_t counts_bytes = sizeof(int64_t) * (size_t)nq;
-    if (hipMalloc((void**)&scratch, counts_bytes + sizeof(HybridStatus)) != hipSuccess) {
-        (void)hipGetLastError();
-        sr_set_error("sr_hybrid_union: out of device memory for %zu scratch bytes", counts_bytes + sizeof(HybridStatus));
+    // the call's scratch: nq counts and the status words, freed when it returns (it waits for the stream to read the status)
+    CallBuf<int64_t> counts;
+    if (counts.reserve(nq, nullptr) != SR_OK) {
+        sr_set_error("sr_hybrid_union: out of device memory for %zu scratch bytes", sizeof(int64_t) * (size_t)nq);
         return SR_ERR_NOMEM;
     }
+    CallStatus<HybridStatus> st;
+    SR_TRY(st.begin("sr_hybrid_union", s));
     UnionArgs a;
     a.a_ids = d_a_ids; a.a_indptr = d_a_indptr; a.kd = d_a_indptr ? 0 : kd;
     a.b_spos = d_b_spos; a.b_counts = d_b_counts; a.ks = ks;
     a.s2d = d_s2d; a.n_s2d = n_s2d; a.d2s = d_d2s; a.n_d2s = n_d2s;
-    a.counts = reinterpret_cast<int64_t*>(scratch);
+    a.counts = counts.p;
     a.out_indptr = d_out_indptr; a.out_dpos = d_out_dpos; a.out_spos = d_out_spos; a.out_tie = d_out_tie; a.capacity = capacity;
-    a.st = reinterpret_cast<HybridStatus*>(scratch + counts_bytes);
-    a.Pa = hf_next_pow2(a.kd); a.Pb = hf_next_pow2(ks);
+    a.st = st.p;
+    a.Pa = sr_pow2_at_least(a.kd, 1); a.Pb = sr_pow2_at_least(ks, 1);
+    if (d_a_indptr) SR_TRY((launch_union<true, false>(a, nq, 1, s))); else SR_TRY((launch_union<false, false>(a, nq, 1, s)));
+    SR_TRY(sr_device_exclusive_scan_i64(a.counts, d_out_indptr, nq, s));
+    if (d_a_indptr) {
+        // a long A is spread over several workgroups per query when the queries alone do not fill the device
+        int64_t ny = (int64_t)sr_cu_count() * 4 / nq;
+        ny = ny < 1 ? 1 : (ny > 64 ? 64 : ny);
+        SR_TRY((launch_union<true, true>(a, nq, (int)ny, s)));
+    } else {
+        SR_TRY((launch_union<false, true>(a, nq, 1, s)));
+    }
     HybridStatus h;
     int64_t n_out = 0;
-    int rc = SR_OK;
-    auto run = [&]() -> int {
-        SR_CHECK_HIP(hipMemsetAsync(a.st, 0xff, sizeof(HybridStatus), s));
-        if (d_a_indptr) SR_TRY((launch_union<true, false>(a, nq, 1, s))); else SR_TRY((launch_union<false, false>(a, nq, 1, s)));
-        SR_TRY(sr_device_exclusive_scan_i64(a.counts, d_out_indptr, nq, s));
-        if (d_a_indptr) {
-            // a long A is spread over several workgroups per query when the queries alone do not fill the device
-            int64_t ny = (int64_t)sr_cu_count() * 4 / nq;
-            ny = ny < 1 ? 1 : (ny > 64 ? 64 : ny);
-            SR_TRY((launch_union<true, true>(a, nq, (int)ny, s)));
-        } else {
-            SR_TRY((launch_union<false, true>(a, nq, 1, s)));
-        }
-        SR_CHECK_HIP(hipMemcpyAsync(&h, a.st, sizeof(h), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipMemcpyAsync(&n_out, d_out_indptr + nq, sizeof(n_out), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        return SR_OK;
-    };
-    rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    SR_TRY(rc);
+    SR_CHECK_HIP(hipMemcpyAsync(&n_out, d_out_indptr + nq, sizeof(n_out), hipMemcpyDeviceToHost, s));
+    SR_TRY(st.read(&h, s));                                     // waits for both copies, also when it fails
     if (h.first_bad_b != ~0ull) {
         int64_t sp = 0;
         SR_CHECK_HIP(hipMemcpy(&sp, d_b_spos + h.first_bad_b, sizeof(sp), hipMemcpyDeviceToHost));
@@ -410,25 +373,8 @@ __global__ __launch_bounds__(HF_THREADS) void hybrid_rank_kernel(RankArgs a) {
     __syncthreads();
     int m = ctrl[2];
     m = m < k ? m : k;
-    int P = 2;
-    while (P < m) P <<= 1;
-    P = P < a.P ? P : a.P;
-    for (int size = 2; size <= P; size <<= 1)                   // bitonic, descending, the places carried along
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += HF_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i && ixj < a.P) {
-                    const bool desc = (i & size) == 0;
-                    const uint64_t x = kept[i], y = kept[ixj];
-                    if (desc ? (x < y) : (x > y)) {
-                        const uint32_t px = kept_at[i], py = kept_at[ixj];
-                        kept[i] = y; kept[ixj] = x;
-                        kept_at[i] = py; kept_at[ixj] = px;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    const int P = sr_pow2_at_least(m, 2);                       // m <= k: inside the a.P slots
+    sr_block_sort_kv<HF_THREADS, true>(kept, kept_at, P);       // descending, the places carried along
     for (int i = tid; i < k; i += HF_THREADS) {
         const int64_t o = q * k + i;
         if (i < m) {
@@ -481,39 +427,23 @@ extern "C" int sr_hybrid_rank(const int64_t* d_cand_indptr, const int64_t* d_dpo
     SR_REQUIRE(d_cand_indptr && d_dpos && d_spos && d_tie && d_dense_scores && d_sparse_scores && d_D && d_S && d_complete && d_out_scores &&
                d_out_ids && d_out_counts && d_out_certified && d_out_threshold, "sr_hybrid_rank: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    HybridStatus* st = nullptr;
-    if (hipMalloc((void**)&st, sizeof(HybridStatus)) != hipSuccess) {
-        (void)hipGetLastError();
-        sr_set_error("sr_hybrid_rank: out of device memory for %zu status bytes", sizeof(HybridStatus));
-        return SR_ERR_NOMEM;
-    }
+    CallStatus<HybridStatus> st;
+    SR_TRY(st.begin("sr_hybrid_rank", s));
     RankArgs a;
     a.indptr = d_cand_indptr; a.dpos = d_dpos; a.spos = d_spos; a.tie = d_tie; a.dense = d_dense_scores; a.sparse = d_sparse_scores;
-    a.w_d = w_d; a.w_s = w_s; a.k = k; a.P = hf_next_pow2(k < 2 ? 2 : k);
+    a.w_d = w_d; a.w_s = w_s; a.k = k; a.P = sr_pow2_at_least(k, 2);
     // 12 bytes per kept slot; the key cache takes what is left of 32 KB (3 - 4 workgroups per compute unit), nothing for a large k
     const size_t kept_bytes = (size_t)a.P * 12;
     a.n_cache = kept_bytes < 32 * 1024 ? (int)((32 * 1024 - kept_bytes) / 8) : 0;
     a.D = d_D; a.S = d_S; a.complete = d_complete; a.tie_limit = (unsigned long long)(n_s2d + id_end);
     a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.out_counts = d_out_counts; a.out_cert = d_out_certified; a.out_thr = d_out_threshold;
-    a.st = st;
+    a.st = st.p;
+    static DeviceOnce lds_set;
+    SR_TRY(sr_allow_lds(lds_set, hybrid_rank_kernel, 60 * 1024));
+    hipLaunchKernelGGL(hybrid_rank_kernel, dim3((unsigned)nq), dim3(HF_THREADS), kept_bytes + (size_t)a.n_cache * 8, s, a);
+    SR_CHECK_LAUNCH();
     HybridStatus h;
-    auto run = [&]() -> int {
-        static DeviceOnce lds_set;
-        if (bool* slot = lds_set.pending()) {
-            SR_CHECK_HIP(hipFuncSetAttribute((const void*)hybrid_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024));
-            *slot = true;
-        }
-        SR_CHECK_HIP(hipMemsetAsync(st, 0xff, sizeof(HybridStatus), s));
-        hipLaunchKernelGGL(hybrid_rank_kernel, dim3((unsigned)nq), dim3(HF_THREADS), kept_bytes + (size_t)a.n_cache * 8, s, a);
-        SR_CHECK_LAUNCH();
-        SR_CHECK_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        return SR_OK;
-    };
-    const int rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    (void)hipFree(st);
-    SR_TRY(rc);
+    SR_TRY(st.read(&h, s));
     if (h.first_bad_a != ~0ull) {
         int64_t t = 0;
         SR_CHECK_HIP(hipMemcpy(&t, d_tie + h.first_bad_a, sizeof(t), hipMemcpyDeviceToHost));

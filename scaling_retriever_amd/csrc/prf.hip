@@ -17,14 +17,14 @@
 //                       documents' pieces in list order, every row piece loaded once.
 // The coefficients f32(beta / f32(p)), f32(gamma / f32(g)) come from two host-computed tables in the kernel arguments: no division on
 // the device.  All arithmetic under contract(off): alpha * q + cp * P must stay two products and a sum.
+#include "block_primitives.h"
 #include "dense_index.h"
-#include "hybrid_fuse.h"
 #include "subset_search.h"
 #include <float.h>
 #include <math.h>
 #include <vector>
 
-#define PRF_THREADS HF_THREADS          // hf_block_scan's four waves
+#define PRF_THREADS 256                 // sr_block_scan's four waves
 #define PRF_MAX_SET 64                  // n_pos, n_neg
 #define PRF_MAX_DOCS (2 * PRF_MAX_SET)
 #define PRF_LDS_ENTRIES 8192            // sr_prf_max_entries(): 12 bytes of LDS per entry
@@ -52,7 +52,7 @@ __device__ inline void prf_sets(const int64_t* __restrict__ fb, int cnt, int n_p
     for (int i0 = 0; i0 < cnt; i0 += PRF_THREADS) {
         const int i = i0 + tid;
         int tot;
-        (void)hf_block_scan(i < cnt && fb[i] >= 0 ? 1 : 0, lw, tot);
+        (void)sr_block_scan(i < cnt && fb[i] >= 0 ? 1 : 0, lw, tot);
         nv += tot;
     }
     p = n_pos < nv ? n_pos : nv;
@@ -63,7 +63,7 @@ __device__ inline void prf_sets(const int64_t* __restrict__ fb, int cnt, int n_p
         const int i = i0 + tid;
         const int64_t id = i < cnt ? fb[i] : -1;
         int tot;
-        const int r = base + hf_block_scan(id >= 0 ? 1 : 0, lw, tot);
+        const int r = base + sr_block_scan(id >= 0 ? 1 : 0, lw, tot);
         if (id >= 0) {
             if (r < p) s_doc[r] = id;
             if (r >= neg0) s_doc[p + r - neg0] = id;
@@ -71,32 +71,6 @@ __device__ inline void prf_sets(const int64_t* __restrict__ fb, int cnt, int n_p
         base += tot;
     }
     __syncthreads();
-}
-
-// bitonic sort of a[0, P) (P a power of two >= 2), LDS or this workgroup's global workspace.  The caller has a barrier behind its stores.
-template <bool DESC>
-__device__ inline void prf_sort(uint64_t* a, int P) {
-    const int half = P >> 1;
-    for (int size = 2; size <= P; size <<= 1)
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < half; t += PRF_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int o = i | j;
-                const bool up = ((i & size) == 0) != DESC;
-                const uint64_t x = a[i], y = a[o];
-                if (up ? (x > y) : (x < y)) {
-                    a[i] = y;
-                    a[o] = x;
-                }
-            }
-            __syncthreads();
-        }
-}
-
-__device__ inline int prf_pow2(int64_t v) {
-    int p = 2;
-    while (p < v) p <<= 1;
-    return p;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ sparse: plan
@@ -132,8 +106,8 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_plan_kernel(PrfPlanArgs a) {
         if (c < 0 || c >= a.n_terms || (i > q0 && a.q_cols[i - 1] >= c)) unordered = 1;
     }
     int any_bad, any_unordered;
-    (void)hf_block_scan(bad, lw, any_bad);
-    (void)hf_block_scan(unordered, lw, any_unordered);
+    (void)sr_block_scan(bad, lw, any_bad);
+    (void)sr_block_scan(unordered, lw, any_unordered);
     if (any_unordered && tid == 0) atomicMin(&a.st->bad_query, (unsigned long long)q);
     if (any_bad || any_unordered) {                             // uniform: nothing of this query is read further
         if (tid == 0) a.ent[q] = 0;
@@ -146,8 +120,8 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_plan_kernel(PrfPlanArgs a) {
     if (tid < p + g) len = a.d_indptr[s_doc[tid] + 1] - a.d_indptr[s_doc[tid]];
     if (len < 0) len = 0;
     int lo, hi;
-    (void)hf_block_scan((int)(len & 0xffff), lw, lo);
-    (void)hf_block_scan((int)(len >> 16), lw, hi);
+    (void)sr_block_scan((int)(len & 0xffff), lw, lo);
+    (void)sr_block_scan((int)(len >> 16), lw, hi);
     if (tid == 0) a.ent[q] = (q1 - q0) + (int64_t)lo + ((int64_t)hi << 16);
 }
 
@@ -197,7 +171,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_sparse_kernel(PrfArgs a) {
         if (!FILL && tid == 0) a.row_cnt[q] = 0;
         return;
     }
-    const int P = prf_pow2(ent);
+    const int P = sr_pow2_at_least(ent, 2);
     uint64_t* keys;
     float* vals;
     if (WS) {
@@ -224,7 +198,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_sparse_kernel(PrfArgs a) {
         keys[e] = key;
     }
     __syncthreads();
-    prf_sort<false>(keys, P);
+    sr_block_sort<PRF_THREADS, false>(keys, P);
 
     // every run's head: w of its term into the head's slot (0: dropped), 0 into the other slots of the run - a slot is read and
     // written by its run's head alone
@@ -260,7 +234,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_sparse_kernel(PrfArgs a) {
         kept += keep ? 1 : 0;
     }
     int K;
-    (void)hf_block_scan(kept, lw, K);                           // its barriers stand behind the stores of vals
+    (void)sr_block_scan(kept, lw, K);                           // its barriers stand behind the stores of vals
     const bool cut = a.max_terms > 0 && K > a.max_terms;
     const int m = cut ? a.max_terms : K;
     if (!FILL) {
@@ -282,7 +256,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_sparse_kernel(PrfArgs a) {
             w = vals[(int)(e & slot_mask)];
         }
         int tot;
-        const int at = base + hf_block_scan(w > 0.0f ? 1 : 0, lw, tot);
+        const int at = base + sr_block_scan(w > 0.0f ? 1 : 0, lw, tot);
         if (w > 0.0f) {
             if (cut) {
                 keys[at] = ((uint64_t)sr_f2ord(w) << 32) | (uint64_t)(~term);
@@ -294,11 +268,11 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_sparse_kernel(PrfArgs a) {
         base += tot;
     }
     if (!cut) return;
-    const int P2 = prf_pow2(K);                                 // K <= ent: inside the words
+    const int P2 = sr_pow2_at_least(K, 2);                     // K <= ent: inside the words
     for (int i = K + tid; i < P2; i += PRF_THREADS) keys[i] = 0ull;     // below every key: the high word of a kept w is never 0
     __syncthreads();
-    prf_sort<true>(keys, P2);
-    const int P3 = prf_pow2(m);
+    sr_block_sort<PRF_THREADS, true>(keys, P2);
+    const int P3 = sr_pow2_at_least(m, 2);
     for (int i = tid; i < P3; i += PRF_THREADS) {
         uint64_t key = PRF_PAD;
         if (i < m) {
@@ -309,7 +283,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_sparse_kernel(PrfArgs a) {
         keys[i] = key;                                          // slot i is read and written by this thread alone
     }
     __syncthreads();
-    prf_sort<false>(keys, P3);
+    sr_block_sort<PRF_THREADS, false>(keys, P3);
     for (int i = tid; i < m; i += PRF_THREADS) {
         const uint64_t key = keys[i];
         a.out_cols[row + i] = (int32_t)(uint32_t)(key >> 32);
@@ -325,7 +299,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_scan_kernel(const int64_t* __
         const int64_t i = i0 + threadIdx.x;
         const int c = i < n ? (int)cnt[i] : 0;                  // a row holds fewer than 2^25 terms
         int tot;
-        const int at = hf_block_scan(c, lw, tot);
+        const int at = sr_block_scan(c, lw, tot);
         if (i < n) row_ptr[i] = base + at;
         base += tot;
     }
@@ -365,11 +339,7 @@ extern "C" int sr_prf_max_entries(void) { return prf_lds_cap(); }
 template <bool FILL, bool WS>
 static int prf_launch(const PrfArgs& a, int64_t n, size_t lds, hipStream_t s) {
     static DeviceOnce lds_set;
-    if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)prf_sparse_kernel<FILL, WS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         PRF_HEAD_BYTES + 12 * PRF_LDS_ENTRIES));
-        *slot = true;
-    }
+    SR_TRY(sr_allow_lds(lds_set, prf_sparse_kernel<FILL, WS>, PRF_HEAD_BYTES + 12 * PRF_LDS_ENTRIES));
     hipLaunchKernelGGL((prf_sparse_kernel<FILL, WS>), dim3((unsigned)n), dim3(PRF_THREADS), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;
@@ -431,8 +401,7 @@ extern "C" int sr_sparse_feedback(const int64_t* d_q_indptr, const int32_t* d_q_
         else if (ent[q] > max_small) max_small = ent[q];
     }
     const int64_t n_small = nq - (int64_t)big.size();
-    auto pow2 = [](int64_t v) { int64_t p = 2; while (p < v) p <<= 1; return p; };
-    auto ws_bytes = [&](int64_t q) { return pow2(ent[q]) * 8 + (ent[q] + 3) / 4 * 16; };
+    auto ws_bytes = [&](int64_t q) { return (int64_t)sr_pow2_at_least(ent[q], 2) * 8 + (ent[q] + 3) / 4 * 16; };
     struct Batch { int64_t first, n, bytes; };
     std::vector<Batch> batches;
     int64_t ws_max = 0;
@@ -466,7 +435,7 @@ extern "C" int sr_sparse_feedback(const int64_t* d_q_indptr, const int32_t* d_q_
     prf_coefficients(&a.coef, alpha, beta, gamma);
     a.ws = d_ws.p;
     a.row_cnt = d_cnt.p; a.row_ptr = d_row_ptr; a.out_cols = d_cols; a.out_vals = d_vals;
-    const size_t lds = (size_t)PRF_HEAD_BYTES + (size_t)pow2(max_small) * 8 + (size_t)(max_small + 3) / 4 * 16;
+    const size_t lds = (size_t)PRF_HEAD_BYTES + (size_t)sr_pow2_at_least(max_small, 2) * 8 + (size_t)(max_small + 3) / 4 * 16;
     auto pass = [&](bool fill) -> int {
         if (n_small > 0) {
             a.jobs = big.empty() ? nullptr : d_jobs.p;

@@ -6,6 +6,7 @@
 //                 walks it and adds the contributions one rounded fp32 add at a time - that fixes the order of the sum.  Every slot then
 //                 holds the key f2ord(fused) << 32 | ~id of the run it heads (0: no head), the keys are sorted descending, the first k
 //                 leave.  The id-sorted words stay resident: a binary search finds a result's run again for its per-list ranks.
+#include "block_primitives.h"
 #include "hybrid_fuse.h"
 #include <float.h>
 #include <math.h>
@@ -22,27 +23,6 @@ struct FuseArgs {
     float* out_scores; int64_t* out_ids; int32_t* out_counts; int32_t* out_ranks;
     HybridStatus* st;                   // first_bad_a: an id >= 2^32; first_bad_b: an id twice in one row (flat positions of ids)
 };
-
-// bitonic sort of a[0, P) in LDS (P a power of two >= 2): every thread owns compare-exchange pairs, none idles.  The caller has a
-// barrier behind its stores.
-template <bool DESC>
-__device__ inline void rf_sort(uint64_t* a, int P) {
-    const int half = P >> 1;
-    for (int size = 2; size <= P; size <<= 1)
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < half; t += HF_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int p = i | j;
-                const bool up = ((i & size) == 0) != DESC;
-                const uint64_t x = a[i], y = a[p];
-                if (up ? (x > y) : (x < y)) {
-                    a[i] = y;
-                    a[p] = x;
-                }
-            }
-            __syncthreads();
-        }
-}
 
 // The fused score of the run of one document that starts at ent[i]: +0.0f plus the contribution of every list that holds it, in
 // ascending list order, one rounded add each.  Plain operators under contract(off) (see hf_fuse in hybrid_fuse.hip): prev + w * norm
@@ -149,7 +129,7 @@ __global__ __launch_bounds__(HF_THREADS) void rank_fuse_kernel(FuseArgs a) {
         }
     }
     __syncthreads();
-    rf_sort<false>(ent, P);
+    sr_block_sort<HF_THREADS, false>(ent, P);
 
     // every slot: the key of the run it heads, else 0 (below every key: the high word of a key is never 0)
     int heads = 0;
@@ -167,8 +147,8 @@ __global__ __launch_bounds__(HF_THREADS) void rank_fuse_kernel(FuseArgs a) {
         keys[i] = key;
     }
     int distinct;
-    (void)hf_block_scan(heads, lw, distinct);                   // its barriers stand behind the stores of keys
-    rf_sort<true>(keys, P);
+    (void)sr_block_scan(heads, lw, distinct);                   // its barriers stand behind the stores of keys
+    sr_block_sort<HF_THREADS, true>(keys, P);
 
     const int m = distinct < k ? distinct : k;
     for (int i = tid; i < k; i += HF_THREADS) {
@@ -205,20 +185,10 @@ __global__ __launch_bounds__(HF_THREADS) void rank_fuse_kernel(FuseArgs a) {
     if (tid == 0) a.out_counts[q] = m;
 }
 
-static int rf_next_pow2(int64_t v) {
-    int p = 2;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 template <int METHOD>
 static int launch_fuse(const FuseArgs& a, hipStream_t s) {
     static DeviceOnce lds_set;
-    if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)rank_fuse_kernel<METHOD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         16 * 2 * SR_MAX_TOPK));
-        *slot = true;
-    }
+    SR_TRY(sr_allow_lds(lds_set, rank_fuse_kernel<METHOD>, 16 * 2 * SR_MAX_TOPK));
     const size_t lds = (size_t)a.P * 16;                        // 32 KB for 2 x 1000, 128 KB at the limit
     hipLaunchKernelGGL((rank_fuse_kernel<METHOD>), dim3((unsigned)a.nq), dim3(HF_THREADS), lds, s, a);
     SR_CHECK_LAUNCH();
@@ -247,31 +217,18 @@ extern "C" int sr_rank_fuse(const int64_t* d_ids, const int32_t* d_counts, const
     SR_REQUIRE(d_ids && d_out_scores && d_out_ids && d_out_counts, "sr_rank_fuse: null pointer");
     if (nq == 0) return SR_OK;
     hipStream_t s = (hipStream_t)stream;
-    HybridStatus* st = nullptr;
-    if (hipMalloc((void**)&st, sizeof(HybridStatus)) != hipSuccess) {
-        (void)hipGetLastError();
-        sr_set_error("sr_rank_fuse: out of device memory for %zu status bytes", sizeof(HybridStatus));
-        return SR_ERR_NOMEM;
-    }
+    CallStatus<HybridStatus> st;
+    SR_TRY(st.begin("sr_rank_fuse", s));
     FuseArgs a;
     a.ids = d_ids; a.counts = d_counts; a.scores = d_scores;
-    a.n_lists = n_lists; a.depth = (int)depth; a.P = rf_next_pow2((int64_t)n_lists * depth); a.k = k; a.nq = nq;
+    a.n_lists = n_lists; a.depth = (int)depth; a.P = sr_pow2_at_least((int64_t)n_lists * depth, 2); a.k = k; a.nq = nq;
     for (int l = 0; l < RF_MAX_LISTS; ++l) a.w[l] = l < n_lists ? h_weights[l] : 0.f;
     a.c = c;
     a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.out_counts = d_out_counts; a.out_ranks = d_out_ranks;
-    a.st = st;
+    a.st = st.p;
+    if (method == SR_FUSE_RRF) SR_TRY(launch_fuse<SR_FUSE_RRF>(a, s)); else SR_TRY(launch_fuse<SR_FUSE_MINMAX>(a, s));
     HybridStatus h;
-    auto run = [&]() -> int {
-        SR_CHECK_HIP(hipMemsetAsync(st, 0xff, sizeof(HybridStatus), s));
-        if (method == SR_FUSE_RRF) SR_TRY(launch_fuse<SR_FUSE_RRF>(a, s)); else SR_TRY(launch_fuse<SR_FUSE_MINMAX>(a, s));
-        SR_CHECK_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        return SR_OK;
-    };
-    const int rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    (void)hipFree(st);
-    SR_TRY(rc);
+    SR_TRY(st.read(&h, s));
     const unsigned long long bad = h.first_bad_a != ~0ull ? h.first_bad_a : h.first_bad_b;
     if (bad != ~0ull) {
         int64_t id = 0;

@@ -527,13 +527,8 @@ extern "C" int sr_sparse_csr_build(const int32_t* d_rows, const int32_t* d_cols,
             if (by_tile) {
                 constexpr size_t lds = sizeof(uint32_t) * ((SBT_THREADS / 64) + 2) * (1 << SB_MAXBITS) + 4 * (size_t)SBW_ELEMS;
                 static DeviceOnce attr_once;
-                if (bool* slot = attr_once.pending()) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&radix_scatter_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                        rc = SR_ERR_HIP;
-                        break;
-                    }
-                    *slot = true;
-                }
+                rc = sr_allow_lds(attr_once, radix_scatter_tile_kernel, (int)lds);
+                if (rc != SR_OK) break;
                 hipLaunchKernelGGL(radix_scatter_tile_kernel, dim3(xcd_contiguous_grid(n_waves)), dim3(SBT_THREADS), lds, s, a);
             } else {
                 hipLaunchKernelGGL(radix_scatter_kernel, dim3(grid), dim3(64 * SBW_WAVES), 0, s, a);

@@ -1105,10 +1105,7 @@ static int cert_launch_score_as(const CertArgs& a, unsigned grid, hipStream_t s)
     // GROUPED: the stamps' 256 bytes (used or not) and the block's 32 word offsets behind them
     const int lds = (int)(sizeof(uint32_t) * 2 * SC_SLOT_WORDS + SC_BREGION + SC_TAIL_LDS + (GROUPED ? 256 + 4 * SC_QB : (a.stamps ? 256 : 0)));
     static_assert(sizeof(uint32_t) * 2 * SC_SLOT_WORDS + SC_BREGION + SC_TAIL_LDS + 256 + 4 * SC_QB <= 160 * 1024, "LDS of a workgroup");
-    if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)cert_score_kernel<KS, MASKED, GROUPED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        *slot = true;
-    }
+    SR_TRY(sr_allow_lds(lds_set, cert_score_kernel<KS, MASKED, GROUPED>, lds));
     hipLaunchKernelGGL((cert_score_kernel<KS, MASKED, GROUPED>), dim3(grid), dim3(1024), lds, s, a);
     SR_CHECK_LAUNCH();
     return SR_OK;

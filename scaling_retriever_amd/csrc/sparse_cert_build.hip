@@ -124,6 +124,7 @@ __global__ __launch_bounds__(256) void cert_fwd_sort_kernel(const int64_t* __res
     for (int i = lane; i < P; i += 64)
         keys[i] = i < n ? fwd_tv[b + i] : ~0ull;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // not sr_block_sort (block_primitives.h): a wave sorts its own row, four rows per workgroup, behind a wavefront fence - no barrier
     for (int size = 2; size <= P; size <<= 1)
         for (int j = size >> 1; j > 0; j >>= 1) {
             for (int i = lane; i < P; i += 64) {

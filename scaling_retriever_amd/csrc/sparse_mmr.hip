@@ -250,9 +250,8 @@ extern "C" int sr_sparse_mmr(const int64_t* d_doc_indptr, const int32_t* d_doc_c
                "sr_sparse_mmr: null pointer");
     hipStream_t s = (hipStream_t)stream;
 
-    CallBuf<unsigned long long> d_status;
-    SR_TRY(d_status.reserve(1, "sr_sparse_mmr"));
-    SR_CHECK_HIP(hipMemsetAsync(d_status.p, 0xff, sizeof(unsigned long long), s));
+    CallStatus<unsigned long long> d_status;
+    SR_TRY(d_status.begin("sr_sparse_mmr", s));
     hipLaunchKernelGGL(sparse_mmr_check_kernel, dim3((unsigned)ceil_div64(nq * n, 256)), dim3(256), 0, s, d_ids, d_counts, nq, (int)n, n_docs,
                        d_status.p);
     SR_CHECK_LAUNCH();
@@ -271,8 +270,7 @@ extern "C" int sr_sparse_mmr(const int64_t* d_doc_indptr, const int32_t* d_doc_c
     SR_CHECK_LAUNCH();
 
     unsigned long long first_bad = 0;
-    SR_CHECK_HIP(hipMemcpyAsync(&first_bad, d_status.p, sizeof(first_bad), hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipStreamSynchronize(s));
+    SR_TRY(d_status.read(&first_bad, s));
     if (first_bad != ~0ull) {
         int64_t id = 0;
         SR_CHECK_HIP(hipMemcpy(&id, d_ids + first_bad, sizeof(id), hipMemcpyDeviceToHost));

@@ -12,6 +12,7 @@
 // posting.  Terms are applied in the query's term order with a barrier between
 // them and an unfused multiply-add, so every per-doc sum is bit-identical to the
 // reference's term-serial fp32 accumulation.
+#include "block_primitives.h"
 #include "sparse_index.h"
 
 #define SP_TILE 8192
@@ -852,18 +853,7 @@ __global__ __launch_bounds__(256) void sparse_block_order_kernel(const int64_t* 
             keys[ql] = ql < nqb ? (bucket << 58) | (((mask[i] >> 8) & ((1ull << 48) - 1)) << 10) | (unsigned long long)ql : ~0ull;
         }
         __syncthreads();
-        for (int size = 2; size <= SPB_SORT_MAX; size <<= 1)
-            for (int j = size >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < SPB_SORT_MAX; i += 256) {
-                    const int ixj = i ^ j;
-                    if (ixj > i) {
-                        const bool up = (i & size) == 0;
-                        const unsigned long long x = keys[i], y = keys[ixj];
-                        if (up ? (x > y) : (x < y)) { keys[i] = y; keys[ixj] = x; }
-                    }
-                }
-                __syncthreads();
-            }
+        sr_block_sort<256, false>(keys, SPB_SORT_MAX);
         for (int i = tid; i < pad; i += 256) pm[i] = keys[i] == ~0ull ? -1 : (int32_t)(keys[i] & 1023);
     } else {
         for (int i = tid; i < pad; i += 256) pm[i] = i < nqb ? i : -1;
@@ -984,11 +974,7 @@ static int sparse_plan_blocks(sr_sparse_index* idx, const SparseCall& call, int6
     SR_CHECK_HIP(hipStreamSynchronize(s));
     *any_fallback = h_bad != 0;
     static DeviceOnce lds_set;
-    if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)sparse_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(sizeof(float) * SPB_Q * SPB_TSTRIDE)));
-        *slot = true;
-    }
+    SR_TRY(sr_allow_lds(lds_set, sparse_block_kernel, (int)(sizeof(float) * SPB_Q * SPB_TSTRIDE)));
     ++idx->n_block_calls;
     if (*any_fallback) ++idx->n_fallback_calls;
     return SR_OK;

@@ -19,7 +19,7 @@
 // (indexer.py:211) and for np.argpartition in select_topk (indexer.py:315-322).
 // tests/topk_cases.py models this protocol; sr_topk_replay (topk_replay.hip)
 // runs it on a given key stream, path by path (tests/test_topk_replay_gpu.py).
-#include "common.h"
+#include "block_primitives.h"
 #include <mutex>
 
 // ------------------------------------------------------------------ reset ---
@@ -342,27 +342,10 @@ __global__ __launch_bounds__(256) void topk_sort_kernel(const uint64_t* __restri
     const int cnt = held < k ? held : k;
     const uint64_t* run = run_keys + (int64_t)q * (2 * k);
     // sort only as many slots as this query holds (a power of two, at most the P the launch reserved LDS for)
-    int Pq = 2;
-    while (Pq < held && Pq < P) Pq <<= 1;
-    P = Pq;
+    P = sr_pow2_at_least(held < P ? held : P, 2);
     for (int i = tid; i < P; i += 256) keys[i] = i < held ? run[i] : 0ull;
     __syncthreads();
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += 256) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool desc = (i & size) == 0;
-                    const uint64_t a = keys[i], b = keys[ixj];
-                    if (desc ? (a < b) : (a > b)) {
-                        keys[i] = b;
-                        keys[ixj] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    sr_block_sort<256, true>(keys, P);
     for (int i = tid; i < k; i += 256) {
         const int64_t o = (int64_t)q * k + i;
         if (i < cnt) {
@@ -400,12 +383,6 @@ __global__ void topk_pack_lists_kernel(const float* __restrict__ scores, const i
 }
 
 // ------------------------------------------------------------------- host ---
-static int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 int TopkWS::ensure_segments(int64_t nq, int kk, int64_t dense_cap, int sn) {
     // (re)allocated whenever the shape differs: the segment geometry is part of the kernels' addressing
     if (nq <= nq_cap && kk <= k && seg_n == sn && seg_off == dense_cap && seg_cnt) return SR_OK;
@@ -515,13 +492,9 @@ int topk_finalize(TopkWS& ws, int64_t nq, int k, float pad_score, float* d_out_s
                   int32_t* d_out_counts, hipStream_t s) {
     if (nq == 0) return SR_OK;
     if (k > SR_MAX_TOPK) return topk_large_finalize(ws, nq, k, pad_score, d_out_scores, d_out_ids, d_out_counts, s);
-    const int P = next_pow2(2 * k);
+    const int P = sr_pow2_at_least(2 * k, 1);
     static DeviceOnce lds_set;      // k = 4096: 8192 keys = the whole 64 KB
-    if (bool* slot = lds_set.pending()) {
-        SR_CHECK_HIP(hipFuncSetAttribute((const void*)topk_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(sizeof(uint64_t) * 2 * SR_MAX_TOPK)));
-        *slot = true;
-    }
+    SR_TRY(sr_allow_lds(lds_set, topk_sort_kernel, (int)(sizeof(uint64_t) * 2 * SR_MAX_TOPK)));
     hipLaunchKernelGGL(topk_sort_kernel, dim3((unsigned)nq), dim3(256), sizeof(uint64_t) * (size_t)P, s, ws.run_keys,
                        ws.run_count, k, P, pad_score, d_out_scores, d_out_ids, d_out_counts);
     SR_CHECK_LAUNCH();

@@ -9,12 +9,13 @@
 //                     minimum makes the outcome independent of the order in which lanes arrive: the outputs are the same bytes on every
 //                     run.  First occurrences are appended in rank order behind a block scan; the loop ends at k groups or at the row's
 //                     end.  No sort: a chunk costs O(TC_CHUNK) LDS operations and five barriers.
-#include "hybrid_fuse.h"
+#include "block_primitives.h"
 #include <float.h>
 #include <limits.h>
 
+#define TC_THREADS 256                      // the four waves of sr_block_scan
 #define TC_CHUNK 1024                       // ranks per chunk
-#define TC_PER (TC_CHUNK / HF_THREADS)      // consecutive ranks per thread: the block scan then appends in rank order
+#define TC_PER (TC_CHUNK / TC_THREADS)      // consecutive ranks per thread: the block scan then appends in rank order
 #define TC_NONE INT_MAX
 
 struct CollapseArgs {
@@ -30,7 +31,7 @@ __device__ inline int tc_home(int32_t key, int slots) {
     return (int)(((uint64_t)((uint32_t)key * 2654435761u) * (uint64_t)(uint32_t)slots) >> 32);
 }
 
-__global__ __launch_bounds__(HF_THREADS) void topk_collapse_kernel(CollapseArgs a) {
+__global__ __launch_bounds__(TC_THREADS) void topk_collapse_kernel(CollapseArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     int32_t* tkey = reinterpret_cast<int32_t*>(smem_raw);       // [slots] the key of a slot, -1: free
     int32_t* tpos = tkey + a.slots;                             // [slots] the smallest position of the row that holds it
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(HF_THREADS) void topk_collapse_kernel(CollapseArgs 
         const int64_t c = a.counts[q];
         end = c < 0 ? 0 : (c < end ? c : end);
     }
-    for (int i = tid; i < a.slots; i += HF_THREADS) {
+    for (int i = tid; i < a.slots; i += TC_THREADS) {
         tkey[i] = -1;
         tpos[i] = TC_NONE;
     }
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(HF_THREADS) void topk_collapse_kernel(CollapseArgs 
                 ++cnt;
             }
         int total;
-        int at = n_out + hf_block_scan(cnt, lw, total);
+        int at = n_out + sr_block_scan(cnt, lw, total);
 #pragma unroll
         for (int j = 0; j < TC_PER; ++j)
             if (keep & (1u << j)) {
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(HF_THREADS) void topk_collapse_kernel(CollapseArgs 
         if (tid == 0) a.status[q] = ctrl[1];
         return;
     }
-    for (int i = n_out + tid; i < k; i += HF_THREADS) {
+    for (int i = n_out + tid; i < k; i += TC_THREADS) {
         const int64_t o = q * k + i;
         a.out_scores[o] = -FLT_MAX;
         a.out_ids[o] = -1;
@@ -136,11 +137,11 @@ __global__ __launch_bounds__(HF_THREADS) void topk_collapse_kernel(CollapseArgs 
 }
 
 // out[0] = the first query whose status is set, out[1] = its status; -1, -1: none.  One workgroup.
-__global__ __launch_bounds__(HF_THREADS) void collapse_status_kernel(const int32_t* status, int64_t nq, long long* out) {
+__global__ __launch_bounds__(TC_THREADS) void collapse_status_kernel(const int32_t* status, int64_t nq, long long* out) {
     __shared__ unsigned long long first;
     if (threadIdx.x == 0) first = ~0ull;
     __syncthreads();
-    for (int64_t q = threadIdx.x; q < nq; q += HF_THREADS)
+    for (int64_t q = threadIdx.x; q < nq; q += TC_THREADS)
         if (status[q] >= 0) {
             atomicMin(&first, (unsigned long long)q);
             break;
@@ -167,11 +168,10 @@ extern "C" int sr_topk_collapse(const float* d_scores, const int64_t* d_ids, con
                "sr_topk_collapse: null pointer");
     if (nq == 0) return SR_OK;
     hipStream_t s = (hipStream_t)stream;
-    // the call's scratch: a status word per query and the two words read back, freed before it returns
+    // the call's scratch: a status word per query and the two words read back, freed when it returns
     const size_t status_bytes = (sizeof(int32_t) * (size_t)nq + 7) & ~(size_t)7;
-    unsigned char* scratch = nullptr;
-    if (hipMalloc((void**)&scratch, status_bytes + 2 * sizeof(long long)) != hipSuccess) {
-        (void)hipGetLastError();
+    CallBuf<unsigned char> scratch;
+    if (scratch.reserve((int64_t)(status_bytes + 2 * sizeof(long long)), nullptr) != SR_OK) {
         sr_set_error("sr_topk_collapse: out of device memory for %zu scratch bytes", status_bytes + 2 * sizeof(long long));
         return SR_ERR_NOMEM;
     }
@@ -180,27 +180,16 @@ extern "C" int sr_topk_collapse(const float* d_scores, const int64_t* d_ids, con
     a.keys = d_keys; a.n_keys = n_keys; a.k = k;
     a.slots = ((k + TC_CHUNK) * 3 / 2 + 255) / 256 * 256;      // <= 7680: 60 KB at k = 4096, 24 KB at k = 1000
     a.out_scores = d_out_scores; a.out_ids = d_out_ids; a.out_keys = d_out_keys; a.out_counts = d_out_counts; a.out_complete = d_out_complete;
-    a.status = reinterpret_cast<int32_t*>(scratch);
-    long long* d_first = reinterpret_cast<long long*>(scratch + status_bytes);
+    a.status = reinterpret_cast<int32_t*>(scratch.p);
+    long long* d_first = reinterpret_cast<long long*>(scratch.p + status_bytes);
+    static DeviceOnce lds_set;
+    SR_TRY(sr_allow_lds(lds_set, topk_collapse_kernel, 64 * 1024 - 64));
+    hipLaunchKernelGGL(topk_collapse_kernel, dim3((unsigned)nq), dim3(TC_THREADS), sizeof(int32_t) * 2 * (size_t)a.slots, s, a);
+    SR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(collapse_status_kernel, dim3(1), dim3(TC_THREADS), 0, s, a.status, nq, d_first);
+    SR_CHECK_LAUNCH();
     long long h[2] = {-1, -1};
-    auto run = [&]() -> int {
-        static DeviceOnce lds_set;
-        if (bool* slot = lds_set.pending()) {
-            SR_CHECK_HIP(hipFuncSetAttribute((const void*)topk_collapse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024 - 64));
-            *slot = true;
-        }
-        hipLaunchKernelGGL(topk_collapse_kernel, dim3((unsigned)nq), dim3(HF_THREADS), sizeof(int32_t) * 2 * (size_t)a.slots, s, a);
-        SR_CHECK_LAUNCH();
-        hipLaunchKernelGGL(collapse_status_kernel, dim3(1), dim3(HF_THREADS), 0, s, a.status, nq, d_first);
-        SR_CHECK_LAUNCH();
-        SR_CHECK_HIP(hipMemcpyAsync(h, d_first, sizeof(h), hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        return SR_OK;
-    };
-    const int rc = run();
-    if (rc != SR_OK) (void)hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    SR_TRY(rc);
+    SR_TRY(sr_read_back(h, d_first, sizeof(h), s));
     if (h[0] >= 0) {
         long long id = 0;
         SR_CHECK_HIP(hipMemcpy(&id, d_ids + h[0] * row_len + h[1], sizeof(id), hipMemcpyDeviceToHost));

@@ -46,7 +46,8 @@ def _check(case, cuts=CUTS, tie="str", order="score", rr_depth=0, exclude=None, 
 
 
 # ---------------------------------------------------------------------------------------------------------------- shapes ---
-@pytest.mark.parametrize("nq,depth", [(3, 1), (3, 3), (1, 64), (3, 65), (257, 37), (3, 1000), (3, 4096)])
+# depth 2, 256, 512: the ranking's sort (256 threads) over a single pair, fewer pairs than threads, one pair per thread
+@pytest.mark.parametrize("nq,depth", [(3, 1), (3, 3), (1, 64), (3, 65), (257, 37), (3, 1000), (3, 4096), (3, 2), (3, 256), (3, 512)])
 def test_shapes_with_heavy_ties(nq, depth):
     case = C.tied_case(np.random.default_rng(depth * 1000 + nq), nq, depth, max(8, 2 * depth), max_judged=min(12, depth), neg_zero=True)
     out, flags, mean, n = _check(case)

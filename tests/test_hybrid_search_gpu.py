@@ -68,14 +68,16 @@ def test_union_of_small_rectangular_lists():
 def test_union_at_the_lds_limit():
     from scaling_retriever_amd.scoring import hybrid_union
     rng = np.random.default_rng(2)
-    N, n_sparse, nq, kd, ks = 12000, 9000, 3, 4096, 4096
+    N, n_sparse, nq = 12000, 9000, 3
     d2s, s2d = _maps(rng, N, n_sparse)
-    A = np.stack([rng.choice(N, kd, replace=False) for _ in range(nq)]).astype(np.int64)
-    A[1, rng.choice(kd, 100, replace=False)] = -1
-    B = np.stack([rng.choice(n_sparse, ks, replace=False) for _ in range(nq)]).astype(np.int64)
-    counts = np.array([4096, 4095, 4096], np.int32)
-    got = hybrid_union(_cuda(A), _cuda(B), _cuda(counts), _cuda(s2d), _cuda(d2s))
-    _check_union(got, list(A), [B[q][:counts[q]] for q in range(nq)], d2s, s2d)
+    # the limit, then the other sizes of the two in-LDS sorts (256 threads): a single pair, fewer pairs than threads, one and two a thread
+    for kd, ks in ((4096, 4096), (2, 2), (256, 512), (512, 1024), (1024, 256)):
+        A = np.stack([rng.choice(N, kd, replace=False) for _ in range(nq)]).astype(np.int64)
+        A[1, rng.choice(kd, min(100, kd // 2), replace=False)] = -1
+        B = np.stack([rng.choice(n_sparse, ks, replace=False) for _ in range(nq)]).astype(np.int64)
+        counts = np.array([ks, ks - 1, ks], np.int32)
+        got = hybrid_union(_cuda(A), _cuda(B), _cuda(counts), _cuda(s2d), _cuda(d2s))
+        _check_union(got, list(A), [B[q][:counts[q]] for q in range(nq)], d2s, s2d)
     with pytest.raises(ValueError, match="4097"):                      # one more does not fit the in-LDS sort
         hybrid_union(torch.zeros((1, 4097), dtype=torch.int64, device="cuda"), _cuda(B[:1]), _cuda(counts[:1]), _cuda(s2d), _cuda(d2s))
 
@@ -121,7 +123,7 @@ def test_union_names_a_sparse_position_without_a_dense_document():
 
 # -------------------------------------------------------------------------------------------------------- rank ---
 @pytest.mark.parametrize("w", [(1.0, 1.0), (0.3, 2.0)])
-@pytest.mark.parametrize("k", [1, 10, 4096])
+@pytest.mark.parametrize("k", [1, 10, 4096, 256, 512, 1024])   # the kept keys' sort (256 threads): k = 1 is a single pair, 4096 the limit
 def test_rank_equals_lexsort_with_certificate_and_threshold(k, w):
     from scaling_retriever_amd.scoring import hybrid_rank
     rng = np.random.default_rng(10 * k + int(10 * w[0]))

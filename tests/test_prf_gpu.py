@@ -133,14 +133,19 @@ def test_sparse_kernel_on_the_full_vocabulary():
 
 
 def test_sparse_kernel_with_the_largest_sets():
-    q, d = M.small_collection()
+    """Also the sizes of the entry sort (sr_block_sort over the next power of two >= a query's entries, 256 threads): fewer pairs than
+    threads (256), one pair per thread (512), two (1024), and the LDS cap of 8192 entries with documents of up to 97 terms."""
     rng = np.random.default_rng(9)
     fb = rng.integers(0, N_DOCS, size=(NQ, 128)).astype(np.int64)
     fb[1, 5::7] = -1
     counts = np.array([128, 128, 128, 127, 100, 64], dtype=np.int32)
-    for m in (0, 32):
-        kw = dict(n_pos=64, n_neg=64, alpha=1.0, beta=0.75, gamma=0.5, max_terms=m)
-        _same_csr(_feedback(q, d, fb, counts, **kw), _model(q, d, fb, counts, **kw), m)
+    for doc_terms, n_set, slots in ((12, 64, {512, 1024}), (12, 20, {256, 512}), (97, 64, {8192})):
+        q, d = M.small_collection(doc_terms=doc_terms)
+        ent = M.entries(q[0], d[0], fb, counts, n_set, n_set)
+        assert slots <= {1 << max(1, (e - 1).bit_length()) for e in ent} and max(ent) <= 8192, ent      # the inputs reach these sizes
+        for m in (0, 32):
+            kw = dict(n_pos=n_set, n_neg=n_set, alpha=1.0, beta=0.75, gamma=0.5, max_terms=m)
+            _same_csr(_feedback(q, d, fb, counts, **kw), _model(q, d, fb, counts, **kw), (doc_terms, n_set, m))
 
 
 def test_queries_at_and_above_the_entry_cap_take_the_other_route(monkeypatch):

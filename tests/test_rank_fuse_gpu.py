@@ -83,9 +83,12 @@ def test_order_of_the_sum_and_the_id_tie_rule():
     assert a.keys() == b.keys() and any(a[key] != b[key] for key in a)     # a wrong add order cannot pass
 
 
-@pytest.mark.parametrize("L", [4, 8])
-def test_more_lists(L):
-    ids = draw_lists(np.random.default_rng(L), L, 3, 16, 40)
+# The slots of the two sorts are the next power of two >= L * depth, sorted by 256 threads: beside 64 and 128, a single pair (2), one pair
+# per thread (512) and two (1024); test_order_of_the_sum has 256 (fewer pairs than threads), test_at_the_limit the 8192 of the cap.
+@pytest.mark.parametrize("L,depth", [pytest.param(4, 16, id="4"), pytest.param(8, 16, id="8"), pytest.param(2, 1, id="slots2"),
+                                     pytest.param(2, 256, id="slots512"), pytest.param(2, 512, id="slots1024")])
+def test_more_lists(L, depth):
+    ids = draw_lists(np.random.default_rng(L), L, 3, depth, depth * 5 // 2)
     w = tuple(0.25 + 0.35 * l for l in range(L))
     _check(ids, 30, weights=w, c=0.5)
     sc = -np.sort(-np.random.default_rng(L + 1).standard_normal(ids.shape).astype(F32), axis=2)
