@@ -317,7 +317,7 @@ def _with_hits(out, hits):
 def dense_search_collapsed(dense, queries, k, keys, depths=None, fallback_bytes=1 << 30, subset=None, mask=None, masks=None, query_group=None,
                            hits=None, members=None):
     """DenseIndexHIP.search_collapsed (see there)."""
-    from .doc_filter import _subset, doc_list_from_mask, doc_mask_from_list, mask_on_device, one_filter, query_group_argument
+    from .doc_filter import _subset, check_group_ids, doc_list_from_mask, doc_mask_from_list, mask_on_device, one_filter, query_group_argument
     from .scoring import hits_argument, member_table_argument
     who = "search_collapsed"
     if dense.precision not in ("fp32", "fp32_filtered"):
@@ -359,9 +359,7 @@ def dense_search_collapsed(dense, queries, k, keys, depths=None, fallback_bytes=
             raise ValueError(f"masks of this index hold {dense.id_end} flags per group (id_end), got {n_bits}")
         words = words.reshape(-1)[:n_groups * ((n_bits + 31) // 32)].reshape(n_groups, (n_bits + 31) // 32)
         groups = (query_group if torch.is_tensor(query_group) else torch.from_numpy(np.ascontiguousarray(query_group))).to(device=dev, dtype=torch.int64)
-        bad = torch.nonzero((groups < 0) | (groups >= n_groups))
-        if bad.numel():
-            raise ValueError(f"{who}: query {int(bad[0])} is in group {int(groups[int(bad[0])])}, outside [0, {n_groups})")
+        check_group_ids(who, groups, n_groups)
 
     def search(rows, depth):
         qs = q[rows].contiguous()

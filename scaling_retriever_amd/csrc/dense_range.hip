@@ -34,6 +34,7 @@
 #include "dense_range_kernel.h"
 #include "dense_index.h"
 #include "doc_mask.h"
+#include "filter_args.h"
 #include <algorithm>
 
 // table[c][q]: counts -> exclusive prefixes over the chunks; lims[q + 1] := hits of query q (summed up by dense_range_lims_kernel)
@@ -150,8 +151,7 @@ static int dense_range_count_run(sr_dense_index* idx, const float* d_queries, in
     idx->range_kind = f.kind;
     *total = 0;
     if (nq == 0 || idx->ntotal == 0) {
-        SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
+        SR_TRY(sr_zero_lims(d_lims, nq, total, s));
         idx->range_nq = nq; idx->range_total = 0; idx->range_chunk_rows = 0;
         idx->range_segs = idx->segs.size(); idx->range_ntotal = idx->ntotal;
         return SR_OK;
@@ -235,18 +235,8 @@ extern "C" int sr_dense_range_count_masked(sr_dense_index* idx, const float* d_q
     return dense_range_count_run(idx, d_queries, nq, d_thresholds, dense_range_one_mask(d_mask_words), d_lims, total, stream);
 }
 
-// the checks the two grouped halves share, before any device work; *n_words = the words of one bitmap
-static int dense_range_group_checks(const sr_dense_index* idx, const char* who, int64_t nq, const uint32_t* d_group_words, int64_t n_groups,
-                                    int64_t n_bits, const int32_t* d_query_group, int64_t* n_words) {
-    SR_REQUIRE(n_groups >= 1, "%s: n_groups=%lld, at least one group is needed", who, (long long)n_groups);
-    SR_REQUIRE(n_bits == dense_id_end(idx), "%s: n_bits=%lld, the index numbers its documents in [0, %lld)", who, (long long)n_bits,
-               (long long)dense_id_end(idx));
-    *n_words = doc_mask_words(n_bits);
-    SR_REQUIRE(n_groups < (1ll << 32) && n_groups * *n_words < (1ll << 32), "%s: %lld groups of %lld words exceed 2^32 words", who,
-               (long long)n_groups, (long long)*n_words);
-    SR_REQUIRE(nq <= 0 || (d_query_group && (d_group_words || n_bits == 0)), "%s: null masks or query groups", who);
-    return SR_OK;
-}
+// the two grouped halves' wording for sr_group_mask_checks
+static const char* const DENSE_RANGE_BITS = "%s: n_bits=%lld, the index numbers its documents in [0, %lld)";
 
 // Range count under a bitmap per query.  Before any scoring: the group ids are read back and checked (one wait for 4 nq bytes), the
 // queries' word offsets and the union of the used groups' bitmaps go onto the handle (a second wait: the list of used groups is host
@@ -256,33 +246,30 @@ extern "C" int sr_dense_range_count_grouped(sr_dense_index* idx, const float* d_
                                             int64_t* d_lims, int64_t* total, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_range_count_grouped: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    int64_t n_words = 0;
-    SR_TRY(dense_range_group_checks(idx, "sr_dense_range_count_grouped", nq, d_group_words, n_groups, n_bits, d_query_group, &n_words));
+    const char* const who = "sr_dense_range_count_grouped";
+    SR_TRY(sr_group_mask_checks(who, n_groups, n_bits, dense_id_end(idx), DENSE_RANGE_BITS));
+    SR_TRY(sr_require_group_pointers(who, nq, d_group_words, d_query_group, n_bits));
+    const int64_t n_words = doc_mask_words(n_bits);
     SR_TRY(dense_range_count_checks(idx, d_queries, nq, d_thresholds, d_lims, total));
     hipStream_t s = (hipStream_t)stream;
     idx->range_nq = -1;                               // whatever happens below, no earlier count can be filled from
     DenseRangeFilter f;
     f.kind = SR_RANGE_KIND_GROUPED;
     f.mask = d_group_words; f.words = n_words;
-    std::vector<int32_t> grp((size_t)nq), used;
+    std::vector<int32_t> grp, used;
     if (nq > 0) {
         StreamOrder::Scope in_order(idx->order, s);
-        SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        for (int64_t q = 0; q < nq; ++q)
-            if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
-                SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
-                SR_CHECK_HIP(hipStreamSynchronize(s));
-                *total = 0;
-                sr_set_error("sr_dense_range_count_grouped: query %lld is in group %d, outside [0, %lld) (nothing was scored)", (long long)q,
-                             grp[(size_t)q], (long long)n_groups);
-                return SR_ERR_INVALID;
-            }
+        int64_t bad = -1;
+        SR_TRY(sr_read_query_groups(d_query_group, nq, n_groups, s, &grp, &bad));
+        if (bad >= 0) {
+            SR_TRY(sr_zero_lims(d_lims, nq, total, s));
+            return sr_bad_group_error(who, bad, grp[(size_t)bad], n_groups, " (nothing was scored)");
+        }
         if (idx->ntotal > 0) {
             used = grp;
             std::sort(used.begin(), used.end());
             used.erase(std::unique(used.begin(), used.end()), used.end());
-            const int64_t nq_pad = ceil_div64(nq, 256) * 256;     // the widest query tile: a lane beyond nq reads an offset of 0
+            const int64_t nq_pad = sr_query_offsets_len(nq);
             const int64_t scratch = 4 * (nq_pad + n_words + (int64_t)used.size());
             if (scratch > idx->ws_limit) {
                 sr_set_error("sr_dense_range_count_grouped: the queries' word offsets and the union bitmap need %lld bytes of workspace (limit %lld bytes)",
@@ -294,7 +281,7 @@ extern "C" int sr_dense_range_count_grouped(sr_dense_index* idx, const float* d_
             SR_TRY(idx->range_used.reserve((int64_t)used.size(), "sr_dense_range_count_grouped"));
             SR_CHECK_HIP(hipMemcpyAsync(idx->range_used.p, used.data(), used.size() * 4, hipMemcpyHostToDevice, s));
             SR_TRY(launch_doc_masks_union(d_group_words, idx->range_used.p, (int64_t)used.size(), n_bits, idx->range_union.p, s));
-            SR_TRY(launch_doc_mask_query_offsets(d_query_group, nq, nq_pad, n_bits, idx->range_qoff.p, s));
+            SR_TRY(sr_query_offsets(d_query_group, nq, n_bits, idx->range_qoff.p, s));
             SR_CHECK_HIP(hipStreamSynchronize(s));            // `used` (pageable host memory) was the source of an asynchronous copy
             f.qoff = idx->range_qoff.p; f.mask_union = idx->range_union.p;
         }
@@ -360,8 +347,9 @@ extern "C" int sr_dense_range_fill_grouped(sr_dense_index* idx, const float* d_q
                                            const int64_t* d_lims, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(idx, "sr_dense_range_fill_grouped: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    int64_t n_words = 0;
-    SR_TRY(dense_range_group_checks(idx, "sr_dense_range_fill_grouped", nq, d_group_words, n_groups, n_bits, d_query_group, &n_words));
+    SR_TRY(sr_group_mask_checks("sr_dense_range_fill_grouped", n_groups, n_bits, dense_id_end(idx), DENSE_RANGE_BITS));
+    SR_TRY(sr_require_group_pointers("sr_dense_range_fill_grouped", nq, d_group_words, d_query_group, n_bits));
+    const int64_t n_words = doc_mask_words(n_bits);
     DenseRangeFilter f;
     f.kind = SR_RANGE_KIND_GROUPED;
     f.mask = d_group_words; f.words = n_words; f.qoff = idx->range_qoff.p; f.mask_union = idx->range_union.p;

@@ -5,6 +5,7 @@
 #include "dense_filter.h"
 #include "subset_search.h"
 #include "doc_mask.h"
+#include "filter_args.h"
 #include <algorithm>
 #include <utility>
 
@@ -119,8 +120,7 @@ extern "C" int sr_dense_search_subset(sr_dense_index* idx, const float* d_querie
     SR_REQUIRE(k <= SR_MAX_TOPK || (int64_t)k - SR_MAX_TOPK <= m, "sr_dense_search_subset: k=%d exceeds %d by more than the subset's %lld documents", k,
                SR_MAX_TOPK, (long long)m);
     if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_dense_search_subset: null pointer");
-    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_subset: queries must be 16-byte aligned");
+    SR_TRY(sr_search_pointers("sr_dense_search_subset", d_queries, d_out_scores, d_out_ids, d_subset || m == 0, true));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
@@ -147,38 +147,23 @@ extern "C" int sr_dense_search_subset(sr_dense_index* idx, const float* d_querie
     return subset_status_end(idx->pair_status, d_subset, "sr_dense_search_subset", "doc index", s);
 }
 
-// every output entry := (-FLT_MAX, -1): what the selects write for a query without a candidate
-__global__ void dense_pad_rows_kernel(float* __restrict__ scores, int64_t* __restrict__ ids, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        scores[i] = -3.402823466e38f;
-        ids[i] = -1;
-    }
-}
-
 // The same search with the filter given as a bitmap.  The bitmap is expanded to the ascending list of its set bits, which goes through
 // the check kernel of sr_dense_search_subset (a set bit that names no document is found there); then the same two routes.
 extern "C" int sr_dense_search_masked(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const uint32_t* d_mask_words,
                                       int64_t n_bits, float* d_out_scores, int64_t* d_out_ids, sr_stream stream) {
-    SR_REQUIRE(idx, "sr_dense_search_masked: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search_masked: bad nq=%lld", (long long)nq);
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_dense_search_masked: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_TRY(sr_search_sizes("sr_dense_search_masked", idx, nq, k, SR_MAX_TOPK_LARGE));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     const int64_t id_end = dense_id_end(idx);
     SR_REQUIRE(n_bits == id_end, "sr_dense_search_masked: the mask holds n_bits=%lld bits, the index's document indices end at %lld", (long long)n_bits,
                (long long)id_end);
     if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && (d_mask_words || n_bits == 0), "sr_dense_search_masked: null pointer");
-    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_masked: queries must be 16-byte aligned");
+    SR_TRY(sr_search_pointers("sr_dense_search_masked", d_queries, d_out_scores, d_out_ids, d_mask_words || n_bits == 0, true));
     StreamOrder::Scope in_order(idx->order, s);
     // the list of the set bits: count (one 8-byte read-back: it sizes the list and the slabs), then expand
-    const int64_t n_blocks = doc_mask_blocks(n_bits);
-    SR_TRY(dense_mask_scratch(idx->mask_blocks, n_blocks + 1, "sr_dense_search_masked"));
-    int64_t* d_count = idx->mask_blocks.p + n_blocks;
-    SR_TRY(launch_doc_mask_count(d_mask_words, n_bits, idx->mask_blocks.p, d_count, s));
+    SR_TRY(dense_mask_scratch(idx->mask_blocks, doc_mask_blocks(n_bits) + 1, "sr_dense_search_masked"));
     int64_t m = 0;
-    SR_CHECK_HIP(hipMemcpyAsync(&m, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipStreamSynchronize(s));
+    SR_TRY(doc_mask_count_sync(d_mask_words, n_bits, idx->mask_blocks.p, s, &m));
     SR_TRY(dense_mask_scratch(idx->mask_list, m > 0 ? m : 1, "sr_dense_search_masked"));
     int64_t* const d_list = idx->mask_list.p;
     SR_TRY(launch_doc_mask_expand(d_mask_words, n_bits, idx->mask_blocks.p, d_list, m, s));
@@ -203,13 +188,8 @@ extern "C" int sr_dense_search_masked(sr_dense_index* idx, const float* d_querie
     // the gather route; after an offender it scores nothing and every output row is padding
     if (k_fits) SR_TRY(dense_subset_gather(idx, d_queries, nq, k, d_list, m, d_out_scores, d_out_ids, s, "sr_dense_search_masked"));
     if (bad) {
-        if (!k_fits) {                                    // a k no valid mask of this count could have: the rows are padded here
-            const int64_t n = nq * (int64_t)k;
-            const int64_t blocks = ceil_div64(n, 256) < 65536 ? ceil_div64(n, 256) : 65536;
-            hipLaunchKernelGGL(dense_pad_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_out_scores, d_out_ids, n);
-            SR_CHECK_LAUNCH();
-            SR_CHECK_HIP(hipStreamSynchronize(s));
-        }
+        // a k no valid mask of this count could have: the rows are padded here
+        if (!k_fits) SR_TRY(launch_pad_rows(d_out_scores, d_out_ids, nullptr, nq, k, SR_DENSE_PAD_SCORE, s));
         int64_t bit = -1;
         SR_CHECK_HIP(hipMemcpy(&bit, d_list + h.first_bad, sizeof(int64_t), hipMemcpyDeviceToHost));
         sr_set_error("sr_dense_search_masked: mask bit %lld is set but names no document of the index (nothing was searched)", (long long)bit);
@@ -231,16 +211,6 @@ static bool grouped_dense_wants_pass(int64_t pairs) {
         if (strcmp(route, "loop") == 0) return false;
     }
     return pairs >= SR_SUBSET_DENSE_CROSSOVER;
-}
-
-// every output row of the call := padding, then the stream is waited for: what an error that scores nothing leaves behind
-static int grouped_pad_rows(float* d_out_scores, int64_t* d_out_ids, int64_t nq, int k, hipStream_t s) {
-    const int64_t n = nq * (int64_t)k;
-    const int64_t blocks = ceil_div64(n, 256) < 65536 ? ceil_div64(n, 256) : 65536;
-    hipLaunchKernelGGL(dense_pad_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_out_scores, d_out_ids, n);
-    SR_CHECK_LAUNCH();
-    SR_CHECK_HIP(hipStreamSynchronize(s));
-    return SR_OK;
 }
 
 // idx->grp_valid := the bitmap of the positions that name a document, or *d_valid = null where every position below id_end does (stride-1
@@ -282,11 +252,9 @@ static int grouped_gather_group(sr_dense_index* idx, const float* d_queries, int
     SR_CHECK_HIP(hipMemcpyAsync(idx->redo_idx.p, h_members, (size_t)n * 8, hipMemcpyHostToDevice, s));
     SR_TRY(launch_filter_gather_rows(d_queries, idx->redo_idx.p, n, idx->dim, idx->redo_q.p, false, s));
     // the ascending list of the group's bits: the count is known, the scan only places the workgroups
-    const int64_t n_blocks = doc_mask_blocks(n_bits);
-    SR_TRY(dense_mask_scratch(idx->mask_blocks, n_blocks + 1, "sr_dense_search_grouped"));
+    SR_TRY(dense_mask_scratch(idx->mask_blocks, doc_mask_blocks(n_bits) + 1, "sr_dense_search_grouped"));
     SR_TRY(dense_mask_scratch(idx->mask_list, m > 0 ? m : 1, "sr_dense_search_grouped"));
-    SR_TRY(launch_doc_mask_count(d_words, n_bits, idx->mask_blocks.p, idx->mask_blocks.p + n_blocks, s));
-    SR_TRY(launch_doc_mask_expand(d_words, n_bits, idx->mask_blocks.p, idx->mask_list.p, m, s));
+    SR_TRY(doc_mask_list(d_words, n_bits, m, idx->mask_blocks.p, idx->mask_list.p, s));
     SR_TRY(dense_subset_gather(idx, idx->redo_q.p, n, k, idx->mask_list.p, m, idx->redo_scores.p, idx->redo_ids.p, s, "sr_dense_search_grouped"));
     SR_TRY(launch_filter_gather_rows(idx->redo_scores.p, idx->redo_idx.p, n, k, d_out_scores, true, s));
     return launch_filter_gather_rows(idx->redo_ids.p, idx->redo_idx.p, n, 2 * (int64_t)k, d_out_ids, true, s);
@@ -298,33 +266,23 @@ static int grouped_gather_group(sr_dense_index* idx, const float* d_queries, int
 extern "C" int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queries, int64_t nq, int k, const uint32_t* d_group_words,
                                        int64_t n_groups, int64_t n_bits, const int32_t* d_query_group, float* d_out_scores,
                                        int64_t* d_out_ids, sr_stream stream) {
-    SR_REQUIRE(idx, "sr_dense_search_grouped: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_dense_search_grouped: bad nq=%lld", (long long)nq);
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK, "sr_dense_search_grouped: k=%d outside [1, %d]", k, SR_MAX_TOPK);
-    SR_REQUIRE(n_groups >= 1, "sr_dense_search_grouped: n_groups=%lld, at least one group is needed", (long long)n_groups);
+    const char* const who = "sr_dense_search_grouped";
+    SR_TRY(sr_search_sizes(who, idx, nq, k, SR_MAX_TOPK));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
-    const int64_t id_end = dense_id_end(idx);
-    SR_REQUIRE(n_bits == id_end, "sr_dense_search_grouped: the masks hold n_bits=%lld bits each, the index's document indices end at %lld",
-               (long long)n_bits, (long long)id_end);
+    SR_TRY(sr_group_mask_checks(who, n_groups, n_bits, dense_id_end(idx), "%s: the masks hold n_bits=%lld bits each, the index's document indices end at %lld"));
     const int64_t n_words = doc_mask_words(n_bits);
-    SR_REQUIRE(n_groups < (1ll << 32) && n_groups * n_words < (1ll << 32), "sr_dense_search_grouped: %lld groups of %lld words exceed 2^32 words",
-               (long long)n_groups, (long long)n_words);
     if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_queries && d_out_scores && d_out_ids && d_query_group && (d_group_words || n_bits == 0), "sr_dense_search_grouped: null pointer");
-    SR_REQUIRE(((uintptr_t)d_queries & 15) == 0, "sr_dense_search_grouped: queries must be 16-byte aligned");
+    SR_TRY(sr_search_pointers(who, d_queries, d_out_scores, d_out_ids, d_query_group && (d_group_words || n_bits == 0), true));
     StreamOrder::Scope in_order(idx->order, s);
     // 1. the group ids: one read-back of 4 nq bytes
-    std::vector<int32_t> grp((size_t)nq);
-    SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipStreamSynchronize(s));
-    for (int64_t q = 0; q < nq; ++q)
-        if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
-            SR_TRY(grouped_pad_rows(d_out_scores, d_out_ids, nq, k, s));
-            sr_set_error("sr_dense_search_grouped: query %lld is in group %d, outside [0, %lld) (nothing was searched)", (long long)q,
-                         grp[(size_t)q], (long long)n_groups);
-            return SR_ERR_INVALID;
-        }
+    std::vector<int32_t> grp;
+    int64_t bad = -1;
+    SR_TRY(sr_read_query_groups(d_query_group, nq, n_groups, s, &grp, &bad));
+    if (bad >= 0) {
+        SR_TRY(launch_pad_rows(d_out_scores, d_out_ids, nullptr, nq, k, SR_DENSE_PAD_SCORE, s));
+        return sr_bad_group_error(who, bad, grp[(size_t)bad], n_groups, " (nothing was searched)");
+    }
     // 2. set bits per group, and the first set bit that names no document: one read-back of 8 (n_groups + 1) bytes
     const uint32_t* d_valid = nullptr;
     SR_TRY(grouped_valid_bitmap(idx, n_bits, &d_valid, s));
@@ -336,7 +294,7 @@ extern "C" int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queri
     if (counts[(size_t)n_groups] != -1) {
         const uint64_t at = (uint64_t)counts[(size_t)n_groups];
         const int64_t word = (int64_t)(at >> 5);
-        SR_TRY(grouped_pad_rows(d_out_scores, d_out_ids, nq, k, s));
+        SR_TRY(launch_pad_rows(d_out_scores, d_out_ids, nullptr, nq, k, SR_DENSE_PAD_SCORE, s));
         sr_set_error("sr_dense_search_grouped: group %lld: mask bit %lld is set but names no document of the index (nothing was searched)",
                      (long long)(word / n_words), (long long)((word % n_words) * 32 + (int64_t)(at & 31)));
         return SR_ERR_INVALID;
@@ -366,9 +324,8 @@ extern "C" int sr_dense_search_grouped(sr_dense_index* idx, const float* d_queri
     bool pass_route = idx->precision == SR_PRECISION_FP32_FILTERED && grouped_dense_wants_pass(pairs);
     if (pass_route) SR_TRY(dense_filter_applies(idx, nq, k, &kp, &pass_route, true));
     if (pass_route) {
-        const int64_t nq_pad = ceil_div64(nq, 256) * 256;  // the pass's query tile: a lane beyond nq reads an offset of 0
-        SR_TRY(dense_mask_scratch(idx->grp_qoff, nq_pad, "sr_dense_search_grouped"));
-        SR_TRY(launch_doc_mask_query_offsets(d_query_group, nq, nq_pad, n_bits, idx->grp_qoff.p, s));
+        SR_TRY(dense_mask_scratch(idx->grp_qoff, sr_query_offsets_len(nq), who));
+        SR_TRY(sr_query_offsets(d_query_group, nq, n_bits, idx->grp_qoff.p, s));
         bool done = false;
         SR_TRY(dense_filtered_candidates(idx, d_queries, nq, k, s, &done, d_group_words, idx->grp_qoff.p));
         if (done) {

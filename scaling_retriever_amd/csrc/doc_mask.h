@@ -20,6 +20,12 @@ int launch_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t* d_word
 // Bits of the last word at or beyond n_bits are ignored.
 int launch_doc_mask_count(const uint32_t* d_words, int64_t n_bits, int64_t* d_blocks, int64_t* d_count, hipStream_t s);
 int launch_doc_mask_expand(const uint32_t* d_words, int64_t n_bits, const int64_t* d_blocks, int64_t* d_list, int64_t capacity, hipStream_t s);
+// The two ways the filtered searches use them.  d_blocks [doc_mask_blocks(n_bits) + 1]: the count's scratch, then the number of set bits.
+//   count_sync  the count, and *m := the number of set bits: one 8-byte read-back, one wait
+//   list        d_list [m] := the ascending list of a bitmap whose m set bits are known: the count runs for the per-workgroup offsets
+//               the expansion starts from; no wait
+int doc_mask_count_sync(const uint32_t* d_words, int64_t n_bits, int64_t* d_blocks, hipStream_t s, int64_t* m);
+int doc_mask_list(const uint32_t* d_words, int64_t n_bits, int64_t m, int64_t* d_blocks, int64_t* d_list, hipStream_t s);
 
 // ---- filter groups (sr_dense_search_grouped): n_groups bitmaps stacked as [n_groups, W], W = doc_mask_words(n_bits) ----
 // d_valid [W] |= the positions id_base + r * id_stride, r < n, of one segment (those below n_bits; the caller has zeroed the words)

@@ -126,6 +126,19 @@ int launch_doc_mask_expand(const uint32_t* d_words, int64_t n_bits, const int64_
     return SR_OK;
 }
 
+int doc_mask_count_sync(const uint32_t* d_words, int64_t n_bits, int64_t* d_blocks, hipStream_t s, int64_t* m) {
+    int64_t* d_count = d_blocks + doc_mask_blocks(n_bits);
+    SR_TRY(launch_doc_mask_count(d_words, n_bits, d_blocks, d_count, s));
+    SR_CHECK_HIP(hipMemcpyAsync(m, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SR_CHECK_HIP(hipStreamSynchronize(s));
+    return SR_OK;
+}
+
+int doc_mask_list(const uint32_t* d_words, int64_t n_bits, int64_t m, int64_t* d_blocks, int64_t* d_list, hipStream_t s) {
+    SR_TRY(launch_doc_mask_count(d_words, n_bits, d_blocks, d_blocks + doc_mask_blocks(n_bits), s));
+    return launch_doc_mask_expand(d_words, n_bits, d_blocks, d_list, m, s);
+}
+
 extern "C" int sr_doc_mask_from_list(const int64_t* d_list, int64_t m, uint32_t* d_words, int64_t n_bits, sr_stream stream) {
     SR_REQUIRE(m >= 0 && n_bits >= 0 && n_bits <= (1ll << 32), "sr_doc_mask_from_list: bad sizes m=%lld n_bits=%lld", (long long)m, (long long)n_bits);
     SR_REQUIRE((d_list || m == 0) && (d_words || n_bits == 0), "sr_doc_mask_from_list: null pointer");

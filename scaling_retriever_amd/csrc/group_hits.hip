@@ -14,6 +14,7 @@
 //                     no LDS array, no atomic.  Once m entries are held, a tile none of whose entries beats the m-th is skipped after
 //                     one ballot, which is what keeps a tenant-sized segment cheap.
 #include "block_primitives.h"
+#include "filter_args.h"
 #include <float.h>
 #include <limits.h>
 
@@ -246,7 +247,7 @@ static int members_run(bool fill, const char* who, const int32_t* d_slot_keys, i
         if (code == GH_BAD_GROUP) {
             int32_t g = 0;
             SR_CHECK_HIP(hipMemcpy(&g, d_query_group + q, sizeof(g), hipMemcpyDeviceToHost));
-            sr_set_error("%s: query %lld is in group %d, outside [0, %lld)", who, q, (int)g, (long long)n_masks);
+            return sr_bad_group_error(who, q, g, n_masks, "");
         } else if (code == GH_BAD_KEY) {
             int32_t key = 0;
             SR_CHECK_HIP(hipMemcpy(&key, d_slot_keys + slot, sizeof(key), hipMemcpyDeviceToHost));

@@ -23,7 +23,7 @@
 // are ANDed into the step's hit ballot (sparse_range_step_hits: the one predicate of the count and of the fill).
 #include "sparse_index.h"
 #include "range_scan.h"
-#include <vector>
+#include "filter_args.h"
 
 #define SRR_TILE SR_SPARSE_TILE_DOCS
 #define SRR_SUBS (SR_SPARSE_TILE_DOCS / SR_SPARSE_SKIP_DOCS)      // skip-table entries per tile
@@ -346,9 +346,7 @@ static int sparse_range_count(sr_sparse_index* idx, const int64_t* d_q_indptr, c
     idx->range_nq = -1;
     idx->range_kind = kind;
     if (nq == 0 || idx->n_docs == 0) {
-        SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        *total = 0;
+        SR_TRY(sr_zero_lims(d_lims, nq, total, s));
         idx->range_nq = nq; idx->range_total = 0; idx->range_chunks = 0; idx->range_chunk_tiles = 0;
         return SR_OK;
     }
@@ -470,17 +468,8 @@ extern "C" int sr_sparse_range_fill_masked(sr_sparse_index* idx, const int64_t* 
 }
 
 // ---- under a bitmap per query (filter groups) ------------------------------------------------------------------------------------
-// the checks the two grouped halves share, before any device work
-static int sparse_range_group_checks(const sr_sparse_index* idx, const char* who, int64_t nq, const uint32_t* d_group_words, int64_t n_groups,
-                                     int64_t n_bits, const int32_t* d_query_group) {
-    SR_REQUIRE(n_groups >= 1, "%s: n_groups=%lld, at least one group is needed", who, (long long)n_groups);
-    SR_REQUIRE(n_bits == idx->n_docs, "%s: n_bits=%lld, the index holds %lld documents", who, (long long)n_bits, (long long)idx->n_docs);
-    const int64_t n_words = (n_bits + 31) >> 5;
-    SR_REQUIRE(n_groups < (1ll << 32) && n_groups * n_words < (1ll << 32), "%s: %lld groups of %lld words exceed 2^32 words", who,
-               (long long)n_groups, (long long)n_words);
-    SR_REQUIRE(nq <= 0 || (d_query_group && (d_group_words || n_bits == 0)), "%s: null masks or query groups", who);
-    return SR_OK;
-}
+// the two grouped halves' wording for sr_group_mask_checks
+static const char* const SPARSE_RANGE_BITS = "%s: n_bits=%lld, the index holds %lld documents";
 
 // One workgroup serves one (query, chunk), so the query's group only moves the base of the mask words (sparse_range_body<.., GROUPED>);
 // the count reads the group ids back once (4 nq bytes) and checks them before anything is launched, and keeps a copy on the handle that
@@ -490,23 +479,21 @@ extern "C" int sr_sparse_range_count_grouped(sr_sparse_index* idx, const int64_t
                                              int64_t n_bits, const int32_t* d_query_group, int64_t* d_lims, int64_t* total, sr_stream stream) {
     SR_REQUIRE(idx, "sr_sparse_range_count_grouped: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    SR_TRY(sparse_range_group_checks(idx, "sr_sparse_range_count_grouped", nq, d_group_words, n_groups, n_bits, d_query_group));
+    const char* const who = "sr_sparse_range_count_grouped";
+    SR_TRY(sr_group_mask_checks(who, n_groups, n_bits, idx->n_docs, SPARSE_RANGE_BITS));
+    SR_TRY(sr_require_group_pointers(who, nq, d_group_words, d_query_group, n_bits));
     SR_TRY(sparse_range_count_checks(nq, d_q_indptr, d_q_cols, d_q_vals, d_thresholds, d_lims, total));
     hipStream_t s = (hipStream_t)stream;
     idx->range_nq = -1;                               // whatever happens below, no earlier count can be filled from
     *total = 0;
     if (nq > 0) {
-        std::vector<int32_t> grp((size_t)nq);
-        SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        SR_CHECK_HIP(hipStreamSynchronize(s));
-        for (int64_t q = 0; q < nq; ++q)
-            if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
-                SR_CHECK_HIP(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * 8, s));
-                SR_CHECK_HIP(hipStreamSynchronize(s));
-                sr_set_error("sr_sparse_range_count_grouped: query %lld is in group %d, outside [0, %lld) (nothing was scored)", (long long)q,
-                             grp[(size_t)q], (long long)n_groups);
-                return SR_ERR_INVALID;
-            }
+        std::vector<int32_t> grp;
+        int64_t bad = -1;
+        SR_TRY(sr_read_query_groups(d_query_group, nq, n_groups, s, &grp, &bad));
+        if (bad >= 0) {
+            SR_TRY(sr_zero_lims(d_lims, nq, total, s));
+            return sr_bad_group_error(who, bad, grp[(size_t)bad], n_groups, " (nothing was scored)");
+        }
     }
     SR_TRY(idx->range_qgroup.reserve(nq > 0 ? nq : 1, "sr_sparse_range_count_grouped"));      // never null: it names the kind below
     if (nq > 0) {
@@ -523,7 +510,8 @@ extern "C" int sr_sparse_range_fill_grouped(sr_sparse_index* idx, const int64_t*
                                             int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int64_t capacity, sr_stream stream) {
     SR_REQUIRE(idx, "sr_sparse_range_fill_grouped: null index");
     std::lock_guard<std::mutex> lock(idx->mu);
-    SR_TRY(sparse_range_group_checks(idx, "sr_sparse_range_fill_grouped", nq, d_group_words, n_groups, n_bits, d_query_group));
+    SR_TRY(sr_group_mask_checks("sr_sparse_range_fill_grouped", n_groups, n_bits, idx->n_docs, SPARSE_RANGE_BITS));
+    SR_TRY(sr_require_group_pointers("sr_sparse_range_fill_grouped", nq, d_group_words, d_query_group, n_bits));
     SR_REQUIRE(idx->range_nq < 0 || idx->range_kind != SRR_KIND_GROUPED || idx->range_groups == n_groups,
                "sr_sparse_range_fill_grouped: n_groups=%lld, the preceding count had %lld", (long long)n_groups, (long long)idx->range_groups);
     return sparse_range_fill(idx, d_q_indptr, d_q_cols, d_q_vals, nq, d_thresholds, SRR_KIND_GROUPED, d_group_words, idx->range_qgroup.p, d_lims, id_base, id_stride, d_out_scores,

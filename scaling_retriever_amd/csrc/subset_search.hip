@@ -27,6 +27,7 @@
 // (cert_score_kernel<KS, true, true>), or the body of the masked search group by group.
 #include "subset_search.h"
 #include "doc_mask.h"
+#include "filter_args.h"
 #include "sparse_index.h"
 #include "sparse_pair_chain.h"
 #include <math.h>
@@ -479,15 +480,13 @@ extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_
                                        int64_t nq, int k, float threshold, const int64_t* d_subset, int64_t m, int64_t id_base,
                                        int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
                                        sr_stream stream) {
-    SR_REQUIRE(idx, "sr_sparse_search_subset: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_subset: bad nq");
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_subset: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_TRY(sr_search_sizes("sr_sparse_search_subset", idx, nq, k, SR_MAX_TOPK_LARGE));
     SR_REQUIRE(m >= 0 && m <= idx->n_docs, "sr_sparse_search_subset: a strictly ascending subset of %lld documents holds at most that many, not m=%lld",
                (long long)idx->n_docs, (long long)m);
     SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
                "sr_sparse_search_subset: global doc index exceeds 32 bits");
     if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && (d_subset || m == 0), "sr_sparse_search_subset: null pointer");
+    SR_TRY(sr_search_pointers("sr_sparse_search_subset", d_q_indptr, d_out_scores, d_out_ids, d_subset || m == 0, false));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
@@ -524,15 +523,13 @@ extern "C" int sr_sparse_search_subset(sr_sparse_index* idx, const int64_t* d_q_
 extern "C" int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                                        int64_t nq, int k, float threshold, const uint32_t* d_mask_words, int64_t n_bits, int64_t id_base,
                                        int64_t id_stride, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream) {
-    SR_REQUIRE(idx, "sr_sparse_search_masked: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_masked: bad nq");
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_masked: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
+    SR_TRY(sr_search_sizes("sr_sparse_search_masked", idx, nq, k, SR_MAX_TOPK_LARGE));
     SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_search_masked: the mask holds n_bits=%lld bits, the index %lld documents", (long long)n_bits,
                (long long)idx->n_docs);
     SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
                "sr_sparse_search_masked: global doc index exceeds 32 bits");
     if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && (d_mask_words || n_bits == 0), "sr_sparse_search_masked: null pointer");
+    SR_TRY(sr_search_pointers("sr_sparse_search_masked", d_q_indptr, d_out_scores, d_out_ids, d_mask_words || n_bits == 0, false));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
@@ -543,15 +540,11 @@ extern "C" int sr_sparse_search_masked(sr_sparse_index* idx, const int64_t* d_q_
 int sparse_masked_body(sr_sparse_index* idx, const SparseCall& call, const uint32_t* d_mask_words, hipStream_t s, const char* who) {
     const int64_t nq = call.nq, n_bits = idx->n_docs;
     const int k = call.k;
-    const int64_t n_blocks = doc_mask_blocks(n_bits);
-    SR_TRY(idx->filt_blocks.reserve(n_blocks + 1, who));
-    int64_t* d_count = idx->filt_blocks.p + n_blocks;
-    SR_TRY(launch_doc_mask_count(d_mask_words, n_bits, idx->filt_blocks.p, d_count, s));
+    SR_TRY(idx->filt_blocks.reserve(doc_mask_blocks(n_bits) + 1, who));
     SparseDocFilter f;
     f.words = d_mask_words;
     f.who = who;
-    SR_CHECK_HIP(hipMemcpyAsync(&f.m, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipStreamSynchronize(s));
+    SR_TRY(doc_mask_count_sync(d_mask_words, n_bits, idx->filt_blocks.p, s, &f.m));
     const bool array = subset_sparse_use_array(f.m, idx->n_docs);
     {   // the workspace errors of sr_sparse_search_subset for a list of this length, before any scoring
         int64_t nq_batch = 0, slab = 0;
@@ -567,15 +560,11 @@ int sparse_masked_body(sr_sparse_index* idx, const SparseCall& call, const uint3
 }
 
 int sparse_masked_lists(sr_sparse_index* idx, const SparseCall& call, const uint32_t* d_mask_words, int64_t m, hipStream_t s, const char* who) {
-    const int64_t n_blocks = doc_mask_blocks(idx->n_docs);
-    SR_TRY(idx->filt_blocks.reserve(n_blocks + 1, who));
-    // the count is known; the launch is there for the per-workgroup offsets the expansion starts from
-    SR_TRY(launch_doc_mask_count(d_mask_words, idx->n_docs, idx->filt_blocks.p, idx->filt_blocks.p + n_blocks, s));
-    SparseDocFilter f;
-    f.words = d_mask_words; f.m = m; f.who = who;
-    SR_TRY(sparse_filter_need_list(idx, &f, s));
+    SR_TRY(idx->filt_blocks.reserve(doc_mask_blocks(idx->n_docs) + 1, who));
+    SR_TRY(idx->filt_list.reserve(m > 0 ? m : 1, who));
+    SR_TRY(doc_mask_list(d_mask_words, idx->n_docs, m, idx->filt_blocks.p, idx->filt_list.p, s));
     SR_TRY(subset_status_begin(&idx->pair_status, s));
-    return sparse_subset_lists(idx, call, f.list, f.m, subset_sparse_use_array(f.m, idx->n_docs), s, who);
+    return sparse_subset_lists(idx, call, idx->filt_list.p, m, subset_sparse_use_array(m, idx->n_docs), s, who);
 }
 
 // ---- filter groups: a document bitmap per query (sr_sparse_search_grouped) --------------------------------------------
@@ -593,53 +582,34 @@ static bool grouped_sparse_wants_pass(int64_t pairs) {
     return pairs >= SR_SUBSET_SPARSE_MASK_CROSSOVER;
 }
 
-// every output row of the call := padding (0, -1), every count 0
-__global__ void sparse_pad_rows_kernel(float* __restrict__ scores, int64_t* __restrict__ ids, int32_t* __restrict__ counts, int64_t nq, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        scores[i] = 0.f;
-        ids[i] = -1;
-        if (counts && i < nq) counts[i] = 0;
-    }
-}
-
 extern "C" int sr_sparse_search_grouped(sr_sparse_index* idx, const int64_t* d_q_indptr, const int32_t* d_q_cols, const float* d_q_vals,
                                         int64_t nq, int k, float threshold, const uint32_t* d_group_words, int64_t n_groups, int64_t n_bits,
                                         const int32_t* d_query_group, int64_t id_base, int64_t id_stride, float* d_out_scores,
                                         int64_t* d_out_ids, int32_t* d_out_counts, sr_stream stream) {
-    SR_REQUIRE(idx, "sr_sparse_search_grouped: null index");
-    SR_REQUIRE(nq >= 0 && nq < (1ll << 30), "sr_sparse_search_grouped: bad nq");
-    SR_REQUIRE(k >= 1 && k <= SR_MAX_TOPK_LARGE, "sr_sparse_search_grouped: k=%d outside [1, %d]", k, SR_MAX_TOPK_LARGE);
-    SR_REQUIRE(n_bits == idx->n_docs, "sr_sparse_search_grouped: the masks hold n_bits=%lld bits each, the index %lld documents", (long long)n_bits,
-               (long long)idx->n_docs);
-    SR_REQUIRE(n_groups >= 1, "sr_sparse_search_grouped: n_groups=%lld, at least one group is needed", (long long)n_groups);
-    const int64_t n_pad = ceil_div64(n_bits, 1024) * 32;      // words of a bitmap in the score kernel's length: whole tiles of 1 024 documents
-    SR_REQUIRE(n_groups < (1ll << 32) && (n_groups + 1) * n_pad < (1ll << 32), "sr_sparse_search_grouped: %lld groups (and their union) of %lld words exceed 2^32 words",
-               (long long)n_groups, (long long)n_pad);
+    const char* const who = "sr_sparse_search_grouped";
+    SR_TRY(sr_search_sizes(who, idx, nq, k, SR_MAX_TOPK_LARGE));
+    SR_TRY(sr_require_mask_bits(who, "%s: the masks hold n_bits=%lld bits each, the index %lld documents", n_bits, idx->n_docs));
+    SR_TRY(sr_require_groups(who, n_groups));
+    // the limit counts the bitmaps and their union in the score kernel's length: whole tiles of 1 024 documents
+    SR_TRY(sr_require_group_words(who, n_groups, ceil_div64(n_bits, 1024) * 32, true));
+    const int64_t n_words = doc_mask_words(n_bits);
     SR_REQUIRE(id_stride >= 1 && id_base >= 0 && id_base + (idx->n_docs - 1) * id_stride < 0xffffffffll,
                "sr_sparse_search_grouped: global doc index exceeds 32 bits");
     if (nq == 0) return SR_OK;
-    SR_REQUIRE(d_q_indptr && d_out_scores && d_out_ids && d_query_group && (d_group_words || n_bits == 0), "sr_sparse_search_grouped: null pointer");
+    SR_TRY(sr_search_pointers(who, d_q_indptr, d_out_scores, d_out_ids, d_query_group && (d_group_words || n_bits == 0), false));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lock(idx->mu);
     StreamOrder::Scope in_order(idx->order, s);
     const SparseCall call{d_q_indptr, d_q_cols, d_q_vals, nq, k, threshold, id_base, id_stride, d_out_scores, d_out_ids, d_out_counts};
     // 1. the group ids: one read-back of 4 nq bytes
-    std::vector<int32_t> grp((size_t)nq);
-    SR_CHECK_HIP(hipMemcpyAsync(grp.data(), d_query_group, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    SR_CHECK_HIP(hipStreamSynchronize(s));
-    for (int64_t q = 0; q < nq; ++q)
-        if (grp[(size_t)q] < 0 || grp[(size_t)q] >= n_groups) {
-            const int64_t n = nq * (int64_t)k;
-            const int64_t blocks = ceil_div64(n > nq ? n : nq, 256) < 65536 ? ceil_div64(n > nq ? n : nq, 256) : 65536;
-            hipLaunchKernelGGL(sparse_pad_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_out_scores, d_out_ids, d_out_counts, nq, n);
-            SR_CHECK_LAUNCH();
-            SR_CHECK_HIP(hipStreamSynchronize(s));
-            sr_set_error("sr_sparse_search_grouped: query %lld is in group %d, outside [0, %lld) (nothing was searched)", (long long)q,
-                         grp[(size_t)q], (long long)n_groups);
-            return SR_ERR_INVALID;
-        }
+    std::vector<int32_t> grp;
+    int64_t bad = -1;
+    SR_TRY(sr_read_query_groups(d_query_group, nq, n_groups, s, &grp, &bad));
+    if (bad >= 0) {
+        SR_TRY(launch_pad_rows(d_out_scores, d_out_ids, d_out_counts, nq, k, 0.f, s));
+        return sr_bad_group_error(who, bad, grp[(size_t)bad], n_groups, " (nothing was searched)");
+    }
     // 2. set bits per group, one word-parallel pass over all bitmaps: one read-back of 8 n_groups bytes
-    const int64_t n_words = doc_mask_words(n_bits);
     SR_TRY(idx->grp_counts.reserve(n_groups + 1, "sr_sparse_search_grouped"));
     SR_TRY(launch_doc_masks_check(d_group_words, n_groups, n_bits, nullptr, idx->grp_counts.p, s));
     std::vector<int64_t> counts((size_t)n_groups);

@@ -233,6 +233,85 @@ def query_group_argument(query_group, nq):
     return query_group
 
 
+def group_ids_int32(query_group, device):
+    """Group ids as the library takes them: int32 on the device."""
+    # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
+    return _to_dev(query_group, torch.int64, device).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+
+
+def check_group_ids(who, groups, n_groups):
+    """The library's range check of the group ids, for a driver that indexes by them itself: groups an int64 tensor [nq]."""
+    bad = torch.nonzero((groups < 0) | (groups >= n_groups))
+    if bad.numel():
+        raise ValueError(f"{who}: query {int(bad[0])} is in group {int(groups[int(bad[0])])}, outside [0, {n_groups})")
+
+
+def group_argument(masks, query_group, nq_of, n_bits_of, what):
+    """The host step of a masks= / query_group= pair, in the order listed at the top: mask_argument (2-D), then nq_of() - the caller's
+    check of its queries' dtype and shape, which returns their number - then query_group_argument."""
+    masks = mask_argument(masks, n_bits_of, what, ndim=2)
+    return masks, query_group_argument(query_group, nq_of())
+
+
+def group_filter(argument, device):
+    """The device step of what group_argument returned: ("_grouped", words int32 [G, W], G, n_bits, group ids int32 [nq]), tensors on the
+    device with valid pointers."""
+    masks, query_group = argument
+    words, n_bits = mask_on_device(*masks, device)
+    return "_grouped", words, int(masks[0].shape[0]), n_bits, _valid(group_ids_int32(query_group, device))
+
+
+def range_filter_kwargs(filt, nq, n_bits, device):
+    """A resolved Filter (None: none) -> the filter keywords of the index classes' range_search over nq queries: masks / query_group for
+    groups, else mask - an allow-list becomes its bitmap over [0, n_bits) (doc_mask_from_list)."""
+    if filt is not None and filt.kind == "groups":
+        if filt.groups.numel() != nq:
+            raise ValueError(f"range_search: query_group must hold one group id per query ({nq}), got {filt.groups.numel()}")
+        return dict(masks=filt.data, query_group=filt.groups)
+    if filt is not None and filt.kind == "subset":
+        return dict(mask=doc_mask_from_list(filt.data, n_bits, device=device))
+    return dict(mask=None if filt is None else filt.data)
+
+
+class FilterKeywords:
+    """The filter keywords of the retrieval classes (allowed_ids, allowed_mask, allowed_masks + query_group), resolved and uploaded once
+    per call.  A class that mixes this in has inverse_id_map() and states _filter_space() -> (device, number of positions, what a position
+    is called in a message): DenseFlatIndexer filters index positions, SparseRetrieval the document positions of the inverted index."""
+
+    def allowed_subset(self, allowed_ids):
+        """External ids (any order, duplicates allowed) -> the sorted unique positions as an int64 tensor on the index's device: the
+        allow-list of the searches, uploaded once per call.  An unknown id: ValueError naming it."""
+        return allowed_positions_on(allowed_ids, self.inverse_id_map(), self._filter_space()[0])
+
+    def allowed_mask_words(self, allowed_mask):
+        """A boolean array / tensor with one flag per position -> the packed bitmap on the index's device, uploaded and packed once per
+        call (flags_to_words)."""
+        device, n, what = self._filter_space()
+        return flags_to_words(allowed_mask, n, what, device)
+
+    def allowed_group_words(self, allowed_masks, query_group):
+        """allowed_masks bool [G, positions] and query_group int [number of queries] (both or neither) -> (packed bitmaps int32 [G, W] on
+        the index's device, group ids int64 on the device), packed once per call (flags_to_words)."""
+        device, n, what = self._filter_space()
+        words = flags_to_words(allowed_masks, (None, n), what, device)
+        groups = query_group if isinstance(query_group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(query_group))
+        if groups.dim() != 1 or groups.dtype.is_floating_point or groups.dtype == torch.bool:
+            raise ValueError(f"query_group must hold one integer group id per query, got {groups.dtype} {tuple(groups.shape)}")
+        return words, groups.to(device=device, dtype=torch.int64)
+
+    def _resolve(self, who, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
+        """The filter keywords of a search -> a Filter on the index's device (None: no filter), resolved and uploaded once per call; the
+        argument rules (one_filter) come before anything is uploaded."""
+        one_filter(who, allowed_masks, query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
+        if allowed_ids is not None:
+            return Filter("subset", self.allowed_subset(allowed_ids))
+        if allowed_mask is not None:
+            return Filter("mask", self.allowed_mask_words(allowed_mask))
+        if allowed_masks is not None:
+            return Filter("groups", *self.allowed_group_words(allowed_masks, query_group))
+        return None
+
+
 def flags_to_words(flags, n, what, device):
     """Bool flags over positions, given by a caller of the retrieval classes -> the packed bitmap on `device`, uploaded and packed once:
     [n] flags (`allowed_mask`) -> int32 [W]; [G, n] flags with G >= 1 (`allowed_masks`) -> int32 [G, W].  `what` names a position in the

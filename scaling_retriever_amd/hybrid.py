@@ -141,7 +141,7 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
     if k > max_topk:
         raise ValueError(f"search_fused: topk = {k} is beyond sr_max_topk() = {max_topk}")
     depths = default_depths(k, max_topk) if depths is None else _check_depths(depths, k, max_topk)
-    from .doc_filter import mask_argument, mask_on_device, one_filter, query_group_argument
+    from .doc_filter import check_group_ids, mask_argument, mask_on_device, one_filter, query_group_argument
     from .scoring import doc_list_from_mask, doc_mask_remap, hybrid_union
     dev = dense.device
     one_filter("search_fused", masks, query_group, mask=mask)
@@ -182,9 +182,7 @@ def search_fused(dense, sparse, d2s, s2d, dense_queries, q_row_ptr, q_cols, q_va
         return result()
     n_allowed, sparse_mask = N, None
     if masks is not None:
-        bad = torch.nonzero((groups < 0) | (groups >= n_groups))
-        if bad.numel():
-            raise ValueError(f"search_fused: query {int(bad[0])} is in group {int(groups[int(bad[0])])}, outside [0, {n_groups})")
+        check_group_ids("search_fused", groups, n_groups)
         # m_g: counted once per call; the same filters over sparse positions, built once per call
         n_allowed = torch.tensor([doc_list_from_mask(masks[g], dense.id_end, capacity=0)[1] for g in range(n_groups)], dtype=torch.int64, device=dev)
         if sparse.n_docs > 0:

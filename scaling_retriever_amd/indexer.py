@@ -25,7 +25,7 @@ import torch
 from tqdm import tqdm
 
 from . import _lib
-from .doc_filter import Filter, allowed_positions_on, doc_mask_from_list, doc_mask_remap, flags_to_words, one_filter
+from .doc_filter import Filter, FilterKeywords, allowed_positions_on, doc_mask_remap, one_filter, range_filter_kwargs
 from .scoring import DenseIndexHIP, SparseIndexHIP, sparse_csr_build, sparse_csr_expand_terms
 from .utils.inverted_index import IndexDictOfArray
 from .utils.run_file import IdTable, PiecewiseRunWriter, RunResult, id_table, to_host, write_run_json
@@ -273,7 +273,7 @@ class DenseIndexer(object):
         return self._run_table
 
 
-class DenseFlatIndexer(DenseIndexer):
+class DenseFlatIndexer(FilterKeywords, DenseIndexer):
     """indexer.py:191-217 over a flat inner-product index resident in HBM."""
 
     def __init__(self, buffer_size: int = 50000):
@@ -324,15 +324,7 @@ class DenseFlatIndexer(DenseIndexer):
         together with a filter for all queries."""
         filt = self._resolve("range_search", allowed_ids, allowed_mask, allowed_masks, query_group)
         q = _dense_queries(query_reps, self.index.device)
-        if filt is not None and filt.kind == "groups":
-            if filt.groups.numel() != q.shape[0]:
-                raise ValueError(f"range_search: query_group must hold one group id per query ({q.shape[0]}), got {filt.groups.numel()}")
-            how = dict(masks=filt.data, query_group=filt.groups)
-        else:
-            mask = None if filt is None else filt.data
-            if filt is not None and filt.kind == "subset":
-                mask = doc_mask_from_list(filt.data, self.index.id_end, device=self.index.device)
-            how = dict(mask=mask)
+        how = range_filter_kwargs(filt, q.shape[0], self.index.id_end, self.index.device)
         lims, scores, positions = self.index.range_search(q, thresholds, sort=sort, **how)
         lims, scores = lims.cpu().numpy(), scores.cpu().numpy()
         flat = self.id_table()[positions.cpu().numpy()]
@@ -341,36 +333,8 @@ class DenseFlatIndexer(DenseIndexer):
 
     KNN_CHUNKS = 2          # search_knn pipelines the query set in this many pieces when it is large (>= 1 024 queries)
 
-    def allowed_subset(self, allowed_ids):
-        """External database ids (any order, duplicates allowed) -> the sorted unique index positions as an int64 tensor on the index's
-        device: the allow-list of search_knn / search_arrays, uploaded once per call.  An unknown id: ValueError naming it."""
-        return allowed_positions_on(allowed_ids, self.inverse_id_map(), self.index.device)
-
-    def allowed_mask_words(self, allowed_mask):
-        """A boolean array / tensor over index positions (length = the number of indexed vectors) -> the packed bitmap on the index's
-        device, uploaded and packed once per call (doc_filter.flags_to_words)."""
-        return flags_to_words(allowed_mask, self.index.id_end, "index position", self.index.device)
-
-    def allowed_group_words(self, allowed_masks, query_group):
-        """allowed_masks bool [G, index positions] and query_group int [nq] (both or neither) -> (packed bitmaps int32 [G, W] on the
-        index's device, group ids int64 on the device), packed once per call (doc_filter.flags_to_words)."""
-        words = flags_to_words(allowed_masks, (None, self.index.id_end), "index position", self.index.device)
-        groups = query_group if isinstance(query_group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(query_group))
-        if groups.dim() != 1 or groups.dtype.is_floating_point or groups.dtype == torch.bool:
-            raise ValueError(f"query_group must hold one integer group id per query, got {groups.dtype} {tuple(groups.shape)}")
-        return words, groups.to(device=self.index.device, dtype=torch.int64)
-
-    def _resolve(self, who, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
-        """The filter keywords of a search -> a doc_filter.Filter on the index's device (None: no filter), resolved and uploaded once per
-        call; the argument rules (doc_filter.one_filter) come before anything is uploaded."""
-        one_filter(who, allowed_masks, query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
-        if allowed_ids is not None:
-            return Filter("subset", self.allowed_subset(allowed_ids))
-        if allowed_mask is not None:
-            return Filter("mask", self.allowed_mask_words(allowed_mask))
-        if allowed_masks is not None:
-            return Filter("groups", *self.allowed_group_words(allowed_masks, query_group))
-        return None
+    def _filter_space(self):
+        return self.index.device, self.index.id_end, "index position"
 
     def search_knn(self, query_reps, top_docs: int, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
         """indexer.py:210-214: (list of db-id lists, fp32 scores [nq, k]); label -1 (fewer than k vectors) -> None.  allowed_ids (None:
@@ -803,7 +767,7 @@ def _doc_id_table(doc_ids, n_docs):
     return table
 
 
-class SparseRetrieval:
+class SparseRetrieval(FilterKeywords):
     """indexer.py:311-540."""
 
     _static_cache = None      # (the caller's dict - held, so its id cannot be recycled -, device index, n_terms)
@@ -951,15 +915,7 @@ class SparseRetrieval:
         (_filter: such a filter already resolved and on the device, doc_filter.Filter)."""
         filt = self._resolve("range_search", allowed_ids, allowed_mask, allowed_masks, query_group) or _filter
         q = _as_query_csr(sparse_query_vecs, self._dev)
-        if filt is not None and filt.kind == "groups":
-            if filt.groups.numel() != len(q):
-                raise ValueError(f"range_search: query_group must hold one group id per query ({len(q)}), got {filt.groups.numel()}")
-            how = dict(masks=filt.data, query_group=filt.groups)
-        else:
-            mask = None if filt is None else filt.data
-            if filt is not None and filt.kind == "subset":
-                mask = doc_mask_from_list(filt.data, self.hip_index.n_docs, device=self._dev)
-            how = dict(mask=mask)
+        how = range_filter_kwargs(filt, len(q), self.hip_index.n_docs, self._dev)
         lims, scores, positions = self.hip_index.range_search(q.row_ptr, q.cols, q.vals, thresholds, sort=sort, **how)
         lims, scores, positions = lims.cpu().numpy(), scores.cpu().numpy(), positions.cpu().numpy()
         table = self.doc_id_table()
@@ -973,36 +929,8 @@ class SparseRetrieval:
         return ([flat[a:b].tolist() for a, b in zip(lims[:-1], lims[1:])],
                 [scores[a:b] for a, b in zip(lims[:-1], lims[1:])])
 
-    def allowed_subset(self, allowed_ids):
-        """Collection ids (any order, duplicates allowed) -> the sorted unique document positions of the inverted index as an int64
-        tensor on its device: the allow-list of retrieve, uploaded once per call.  An unknown id: ValueError naming it."""
-        return allowed_positions_on(allowed_ids, self.inverse_id_map(), self._dev)
-
-    def allowed_mask_words(self, allowed_mask):
-        """A boolean array / tensor over the document positions of the inverted index (one flag per document) -> the packed bitmap on
-        its device, uploaded and packed once per call (doc_filter.flags_to_words)."""
-        return flags_to_words(allowed_mask, self.hip_index.n_docs, "document position", self._dev)
-
-    def allowed_group_words(self, allowed_masks, query_group):
-        """allowed_masks bool [G, document positions] and query_group int [number of queries] -> (packed bitmaps int32 [G, W] on the
-        index's device, group ids int64 on the device), packed once per call (doc_filter.flags_to_words)."""
-        words = flags_to_words(allowed_masks, (None, self.hip_index.n_docs), "document position", self._dev)
-        groups = query_group if isinstance(query_group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(query_group))
-        if groups.dim() != 1 or groups.dtype.is_floating_point or groups.dtype == torch.bool:
-            raise ValueError(f"query_group must hold one integer group id per query, got {groups.dtype} {tuple(groups.shape)}")
-        return words, groups.to(device=self._dev, dtype=torch.int64)
-
-    def _resolve(self, who, allowed_ids=None, allowed_mask=None, allowed_masks=None, query_group=None):
-        """The filter keywords of a search -> a doc_filter.Filter on the index's device (None: no filter), resolved and uploaded once per
-        call; the argument rules (doc_filter.one_filter) come before anything is uploaded."""
-        one_filter(who, allowed_masks, query_group, allowed_ids=allowed_ids, allowed_mask=allowed_mask)
-        if allowed_ids is not None:
-            return Filter("subset", self.allowed_subset(allowed_ids))
-        if allowed_mask is not None:
-            return Filter("mask", self.allowed_mask_words(allowed_mask))
-        if allowed_masks is not None:
-            return Filter("groups", *self.allowed_group_words(allowed_masks, query_group))
-        return None
+    def _filter_space(self):
+        return self._dev, self.hip_index.n_docs, "document position"
 
     def _search(self, q, topk, threshold, filt, row0=0):
         """One search of the query CSR `q` under a resolved filter (None: none).  Under groups the queries are rows row0 .. of the query

@@ -20,8 +20,8 @@ import torch
 
 from . import _lib
 from .doc_filter import (_call, _cuda_device, _mask_words, _ptr, _subset, _to_dev, _valid, allowed_positions, doc_list_from_mask,  # noqa: F401  (re-exported)
-                         doc_mask_from_list, doc_mask_remap, mask_argument, mask_on_device, one_filter, pack_doc_mask, pack_doc_masks,
-                         query_group_argument, read_allowed_ids_file)
+                         doc_mask_from_list, doc_mask_remap, group_argument, group_filter, group_ids_int32, mask_argument, mask_on_device,
+                         one_filter, pack_doc_mask, pack_doc_masks, query_group_argument, read_allowed_ids_file)
 
 
 def _thresholds(thresholds, nq, device):
@@ -43,6 +43,12 @@ def _filter_args(filt):
     if filt[0] == "_grouped":
         return filt[0], (_ptr(filt[1]), filt[2], filt[3], _ptr(filt[4]))
     return filt[0], (_ptr(filt[1]), filt[2])
+
+
+def _topk_outputs(nq, k, device, counts=False):
+    """The output tensors of a top-k search: (scores fp32 [nq, k], ids int64 [nq, k]), and with counts=True (counts int32 [nq],)."""
+    out = (torch.empty((nq, k), dtype=torch.float32, device=device), torch.empty((nq, k), dtype=torch.int64, device=device))
+    return out + (torch.empty((nq,), dtype=torch.int32, device=device),) if counts else out
 
 
 def _candidates(cand_indptr, cand_ids, nq, device):
@@ -310,14 +316,16 @@ class DenseIndexHIP:
         if mask is not None:
             mask = self._mask(mask)
         queries = self._queries(queries)
-        nq = queries.shape[0]
         filt = None
         if subset is not None:
             filt = ("_subset",) + _subset(subset, self.device)
         elif mask is not None:
             filt = ("_masked",) + mask_on_device(*mask, self.device)
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        return self._search(queries, k, filt)
+
+    def _search(self, queries, k, filt):
+        nq = queries.shape[0]
+        scores, ids = _topk_outputs(nq, k, self.device)
         suffix, spliced = _filter_args(filt)
         self._call("sr_dense_search" + suffix, _ptr(queries), nq, int(k), *spliced, _ptr(scores), _ptr(ids))
         return scores, ids
@@ -330,24 +338,13 @@ class DenseIndexHIP:
         word count, a length mismatch or non-integer groups: ValueError before anything is uploaded; a group id outside [0, G) or a set
         bit that names no document: ValueError naming the query / the (group, bit), every row of the result is then padding."""
         queries, filt = self._groups(masks, query_group, queries)
-        nq = queries.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        suffix, spliced = _filter_args(filt)
-        self._call("sr_dense_search" + suffix, _ptr(queries), nq, int(k), *spliced, _ptr(scores), _ptr(ids))
-        return scores, ids
+        return self._search(queries, k, filt)
 
     def _groups(self, masks, query_group, queries):
         """The checks of a masks= / query_group= pair in the order doc_filter.py lists, then its device step: (queries contiguous,
         ("_grouped", words int32 [G, W] on the device, G, n_bits, group ids int32 [nq] on the device))."""
-        masks = self._mask(masks, ndim=2)
-        nq = self._check_queries(queries)
-        query_group = query_group_argument(query_group, nq)
-        queries = self._queries(queries)
-        words, n_bits = mask_on_device(*masks, self.device)
-        # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
-        groups = _valid(_to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32))
-        return queries, ("_grouped", words, int(masks[0].shape[0]), n_bits, groups)
+        argument = group_argument(masks, query_group, lambda: self._check_queries(queries), lambda: self.id_end, "id_end")
+        return self._queries(queries), group_filter(argument, self.device)
 
     def _range_filter(self, who, queries, mask, masks, query_group):
         """(queries contiguous, the resolved filter of a range call: None, ("_masked", words, n_bits) or the tuple of _groups)."""
@@ -548,8 +545,7 @@ class DenseIndexHIP:
         """Second half: threshold [nq] fp32 = the minimum of search_begin's values over all shards (None: a plain search).
         Returns (scores [nq, k], ids [nq, k]); rows may end in padding (id -1) - the shard returns what can reach the global top-k."""
         nq = queries.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+        scores, ids = _topk_outputs(nq, k, queries.device)
         if threshold is not None:
             threshold = threshold.to(device=queries.device, dtype=torch.float32).contiguous()
         self._call("sr_dense_search_finish", _ptr(queries), nq, int(k), _ptr(threshold), _ptr(scores), _ptr(ids))
@@ -684,9 +680,10 @@ class SparseIndexHIP:
             filt = ("_masked",) + mask_on_device(*mask, self.device)
         elif subset is not None:
             filt = ("_subset",) + _subset(subset, self.device)
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        counts = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        return self._search(q, nq, k, threshold, filt, id_base, id_stride)
+
+    def _search(self, q, nq, k, threshold, filt, id_base, id_stride):
+        scores, ids, counts = _topk_outputs(nq, k, self.device, counts=True)
         suffix, spliced = _filter_args(filt)
         self._call("sr_sparse_search" + suffix, *map(_ptr, q), nq, int(k), float(threshold), *spliced, int(id_base), int(id_stride),
                    _ptr(scores), _ptr(ids), _ptr(counts))
@@ -699,19 +696,24 @@ class SparseIndexHIP:
         group's queries are exactly what search(those queries, k, mask=masks[g]) returns.  Returns (scores [nq,k], ids [nq,k], counts
         [nq]).  Wrong shapes, a wrong word count, a length mismatch or non-integer groups: ValueError before anything is uploaded; a group
         id outside [0, G): ValueError naming the query, every row of the result is then padding."""
-        masks = mask_argument(masks, lambda: self.n_docs, "n_docs", ndim=2)
-        nq = len(q_indptr) - 1
-        query_group = query_group_argument(query_group, nq)
+        q, nq, filt = self._groups(masks, query_group, q_indptr, q_cols, q_vals)
+        return self._search(q, nq, k, threshold, filt, id_base, id_stride)
+
+    def _groups(self, masks, query_group, q_indptr, q_cols, q_vals):
+        """As DenseIndexHIP._groups: (the query CSR on the device, nq, the "_grouped" filter)."""
+        argument = group_argument(masks, query_group, lambda: len(q_indptr) - 1, lambda: self.n_docs, "n_docs")
         q, nq = self._query_csr(q_indptr, q_cols, q_vals)
-        words, n_bits = mask_on_device(*masks, self.device)
-        # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
-        groups = _valid(_to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32))
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        counts = torch.empty((nq,), dtype=torch.int32, device=self.device)
-        self._call("sr_sparse_search_grouped", *map(_ptr, q), nq, int(k), float(threshold), _ptr(words), int(masks[0].shape[0]), n_bits,
-                   _ptr(groups), int(id_base), int(id_stride), _ptr(scores), _ptr(ids), _ptr(counts))
-        return scores, ids, counts
+        return q, nq, group_filter(argument, self.device)
+
+    def _range_filter(self, who, q_indptr, q_cols, q_vals, mask, masks, query_group):
+        """As DenseIndexHIP._range_filter: (the query CSR on the device, nq, the resolved filter of a range call)."""
+        one_filter(who, masks, query_group, mask=mask)
+        if masks is not None:
+            return self._groups(masks, query_group, q_indptr, q_cols, q_vals)
+        if mask is not None:
+            mask = self._mask(mask)
+        q, nq = self._query_csr(q_indptr, q_cols, q_vals)
+        return q, nq, (None if mask is None else ("_masked",) + mask_on_device(*mask, self.device))
 
     def range_search(self, q_indptr, q_cols, q_vals, thresholds, id_base=0, id_stride=1, sort=False, mask=None, masks=None, query_group=None):
         """Every document scoring above a threshold - the full list of numba_score_float (scaling_retriever/indexer.py:324-344;
@@ -725,24 +727,12 @@ class SparseIndexHIP:
         masks + query_group (not together with mask): a bitmap per group and a group id per query in the forms `search_grouped` takes -
         query q gets the documents of masks[query_group[q]] (sr_sparse_range_count_grouped / _fill_grouped): for every group exactly the
         lists of range_search(those queries, mask=masks[g]).  A group id outside [0, G): ValueError naming the query."""
-        one_filter("range_search", masks, query_group, mask=mask)
-        if mask is not None:
-            mask = self._mask(mask)
-        if masks is not None:
-            masks = mask_argument(masks, lambda: self.n_docs, "n_docs", ndim=2)
-            query_group = query_group_argument(query_group, len(q_indptr) - 1)
-        q, nq = self._query_csr(q_indptr, q_cols, q_vals)
+        q, nq, filt = self._range_filter("range_search", q_indptr, q_cols, q_vals, mask, masks, query_group)
         thr = _valid(_thresholds(thresholds, nq, self.device))
         if sort and int(id_base) + (self.n_docs - 1) * int(id_stride) >= 1 << 32:
             raise ValueError("sort=True orders by the search's 64-bit key, which holds ids below 2^32; sort the lists of larger ids yourself")
         lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
-        filt = None if mask is None else ("_masked",) + mask_on_device(*mask, self.device)
-        if masks is not None:
-            words, n_bits = mask_on_device(*masks, self.device)
-            # an id that does not fit int32 must not wrap into range: it is clamped to one the library rejects
-            groups = _valid(_to_dev(query_group, torch.int64, self.device).clamp(-1, 2 ** 31 - 1).to(torch.int32))
-            filt = ("_grouped", words, int(masks[0].shape[0]), n_bits, groups)
         suffix, spliced = _filter_args(filt)
         head = (*map(_ptr, q), nq, _ptr(thr), *spliced, _ptr(lims))
         self._call("sr_sparse_range_count" + suffix, *head, ctypes.byref(total))
@@ -1223,8 +1213,8 @@ def _members_arguments(slot_keys, members, filt):
         words = filt[0].to(dev).contiguous()
         words = words if words.dtype == torch.int32 else words.view(torch.int32)
         groups = filt[2] if len(filt) > 2 else None
-        if groups is not None:                      # an id that does not fit int32 must not wrap into range
-            groups = _to_dev(groups, torch.int64, dev).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        if groups is not None:
+            groups = group_ids_int32(groups, dev)
         filt = (words, int(filt[1]), groups)
     return slot_keys.contiguous(), members, filt
 
