@@ -1244,6 +1244,39 @@ int sr_segment_topm(const float* d_scores, const int64_t* d_ids, const int64_t* 
                     int use_threshold, float threshold, float pad_score, float* d_out_scores, int64_t* d_out_ids,
                     int32_t* d_out_counts, sr_stream stream);
 
+/* ---- lexical: BM25 from token ids (csrc/token_counts.hip, csrc/bm25_weights.hip) ------------------------------------
+ *
+ * sr_token_counts: token rows -> a term-frequency CSR.  d_ids / d_mask int64 [B, L] row-major are a loader's input_ids /
+ *   attention_mask, padding on either side; d_mask NULL = every slot is real.  A slot counts when its mask is non-zero and its id is
+ *   none of the n_skip <= 16 ids of h_skip (host memory; BOS, EOS, pad).  Masked and skipped slots are not range-checked.  Row b yields
+ *   its distinct counted ids ascending in d_cols (int32) with d_vals = f32(occurrences) (exact: L <= sr_token_counts_max_len() = 8192);
+ *   d_row_ptr int64 [B + 1] the CSR offsets; d_len int32 [B] the number of counted slots of the row (the sum of its values: BM25's
+ *   document length).  capacity, *h_nnz and SR_ERR_NOMEM exactly as sr_sparse_compact (nothing but d_row_ptr is written when it does not
+ *   fit; B * L always fits).  The call reads the total and the status back and waits for the stream once.  A counted id outside
+ *   [0, n_terms) is found on the device: SR_ERR_INVALID, sr_last_error() names row, position and id of the smallest (row, position),
+ *   d_cols / d_vals / d_len are not written.  L above the maximum, B >= 2^24 (one workgroup per row: the launch limit), n_skip outside [0, 16], n_terms outside [1, 2^31), negative sizes,
+ *   null pointers: SR_ERR_INVALID before any device call.  B == 0 or L == 0: a valid empty result (row offsets all 0, lengths 0).
+ *   32-bit keys (the id, 0xFFFFFFFF for a slot that does not count) are sorted ascending, run heads flagged, a head's frequency is the
+ *   distance to the end of its run, heads appended in order: rows of at most 256 slots by one wave each with the keys in registers
+ *   (cross-lane exchanges, no barrier; four rows per workgroup), longer rows by a workgroup each with the keys in LDS.  The sort runs
+ *   twice, for the count and for the fill.  No atomic decides an output byte: two calls return the same bytes.
+ *
+ * sr_bm25_weights: term frequencies -> BM25 weights on a term-major CSR (d_indptr int64 [n_terms + 1] from 0 to nnz, d_doc_ids int32
+ *   [nnz], d_tf fp32 [nnz]), d_doc_len int32 [n_docs], d_idf fp32 [n_terms].  Posting p of term t with document d:
+ *     K = f32(a + f32(s * f32(doc_len[d])));   w = f32(idf[t] * f32(f32(tf * numer) / f32(tf + K)))
+ *   one rounded fp32 operation at a time, contraction off, the division correctly rounded.  d_out_vals fp32 [nnz] may be d_tf.  The
+ *   scalars and the idf table come from the host (bm25.py: bm25_scalars, idf_table): no logarithm runs here.  One thread per posting,
+ *   the term found by a search of d_indptr per wave; d_doc_len is the only gathered stream.  A document id outside [0, n_docs) is found
+ *   on the device: SR_ERR_INVALID naming posting and id, the outputs then not to be used.  Null pointers, negative sizes, n_terms or
+ *   n_docs >= 2^31: SR_ERR_INVALID before any device call; nnz == 0 is legal.  Waits for the stream once, to read the status.        */
+int sr_token_counts_max_len(void);
+int sr_token_counts(const int64_t* d_ids, const int64_t* d_mask, int64_t B, int64_t L, const int32_t* h_skip, int n_skip,
+                    int64_t n_terms, int64_t* d_row_ptr, int32_t* d_cols, float* d_vals, int32_t* d_len, int64_t capacity,
+                    int64_t* h_nnz, sr_stream stream);
+int sr_bm25_weights(const int64_t* d_indptr, const int32_t* d_doc_ids, const float* d_tf, int64_t n_terms, int64_t nnz,
+                    const int32_t* d_doc_len, int64_t n_docs, const float* d_idf, float numer, float a, float s, float* d_out_vals,
+                    sr_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

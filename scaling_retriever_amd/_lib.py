@@ -193,6 +193,11 @@ SIGNATURES = {
                                   ctypes.POINTER(c_int64), c_void_p]),
     "sr_sparse_compact_topm": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                        ctypes.POINTER(c_int64), c_void_p]),
+    "sr_token_counts_max_len": (c_int, []),
+    "sr_token_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int64, ctypes.POINTER(c_int32), c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "sr_bm25_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_float, c_float, c_float,
+                                c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -775,7 +775,8 @@ class SparseRetrieval(FilterKeywords):
     def __init__(self, model, config, dim_voc, device, dataset_name=None, index_d=None, compute_stats=False,
                  is_beir=False, query_max_terms=0, **kwargs):
         self.model = model
-        self.model.eval()
+        if self.model is not None:       # None: a retriever whose queries need no encoder (bm25.Bm25Retrieval)
+            self.model.eval()
         # per-query term budget (no reference counterpart): a query is searched with its query_max_terms largest terms only
         # (sparse_reps_to_csr); 0 = all of them, the reference's behaviour
         self.query_max_terms = int(query_max_terms)
@@ -788,7 +789,8 @@ class SparseRetrieval(FilterKeywords):
             self.sparse_index = index_d["index"]
             self.doc_ids = index_d["ids_mapping"]
         self.device = device
-        self.model.to(device)
+        if self.model is not None:
+            self.model.to(device)
         dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
         self._dev = dev
         dcsr = index_d.get("device_csr") if index_d is not None else None

@@ -4,7 +4,7 @@ These hold device memory (torch tensors) and call the C ABI; all arithmetic is i
 the HIP kernels (csrc/dense_score.hip, csrc/sparse_cert.hip, csrc/sparse_score.hip, csrc/topk.hip).
 The reference-shaped classes in indexer.py are built on top of these.
 
-What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, sparse_feedback, sparse_mmr, topk_merge, hybrid_union,
+What is here: DenseIndexHIP, SparseIndexHIP and the free functions (range_sort, sparse_csr_build, token_counts, bm25_weights, sparse_feedback, sparse_mmr, topk_merge, hybrid_union,
 hybrid_rank, topk_collapse, group_members, segment_topm).  Every library call goes through one helper (`_call`: the index's device, the entry by name, torch's current stream,
 the status checked under that name); a filtered variant of an entry is the same call with "_subset" / "_masked" appended to the name
 and the filter's two arguments spliced in where the header puts them (_filter_args).  Each class checks its queries in one place
@@ -878,6 +878,77 @@ def sparse_csr_expand_terms(indptr, nnz):
     out = torch.empty(max(1, int(nnz)), dtype=torch.int32, device=indptr.device)
     _call(indptr.device, "sr_sparse_csr_expand_terms", _ptr(indptr), indptr.numel() - 1, int(nnz), _ptr(out))
     return out[:int(nnz)]
+
+
+def token_counts(input_ids, attention_mask=None, skip_ids=(), n_terms=None):
+    """Term frequencies of token rows (include/sr_hip.h sr_token_counts): input_ids int [B, L] and attention_mask [B, L]
+    (None: every slot is real) as a loader delivers them, padding on either side; a slot counts when its mask is non-zero and its id is
+    none of skip_ids (at most 16: BOS, EOS, pad).  Returns cuda tensors (row_ptr int64 [B + 1], cols int32 [nnz] - the distinct counted
+    ids of a row, ascending -, vals fp32 [nnz] - their occurrences -, lengths int32 [B] - the counted slots of a row).  A counted id
+    outside [0, n_terms): ValueError naming row, position and id.  L above sr_token_counts_max_len() (8192): ValueError."""
+    _lib.require_gpu()
+    if n_terms is None:
+        raise ValueError("token_counts: n_terms (the size of the vocabulary) must be given")
+    dev = _cuda_device(input_ids)
+    ids = _to_dev(input_ids, torch.int64, dev)
+    if ids.dim() != 2:
+        raise ValueError(f"expected input_ids [B, L], got {tuple(ids.shape)}")
+    B, L = ids.shape
+    mask = None
+    if attention_mask is not None:
+        mask = _to_dev(attention_mask, torch.int64, dev)
+        if mask.shape != ids.shape:
+            raise ValueError(f"expected an attention_mask of shape {tuple(ids.shape)}, got {tuple(mask.shape)}")
+    skip = [int(x) for x in skip_ids]
+    if any(not -2 ** 31 <= x < 2 ** 31 for x in skip):
+        raise ValueError(f"skip_ids must be int32 values, got {skip}")
+    h_skip = (ctypes.c_int32 * max(1, len(skip)))(*skip)
+    row_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    lengths = torch.empty(B, dtype=torch.int32, device=dev)
+    # a guess first, and one more call with the size the first one names if it was short, as sparse_reps_to_csr; B * L always fits
+    cap = max(1, min(B * L, 1 << 22))
+    n = ctypes.c_int64(0)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        while True:
+            cols = torch.empty(cap, dtype=torch.int32, device=dev)
+            vals = torch.empty(cap, dtype=torch.float32, device=dev)
+            rc = lib.sr_token_counts(_ptr(_valid(ids)), _ptr(mask if mask is None else _valid(mask)), B, L, h_skip, len(skip), int(n_terms),
+                                     _ptr(row_ptr), _ptr(cols), _ptr(vals), _ptr(_valid(lengths)), cap, ctypes.byref(n), _lib.stream_ptr())
+            if rc == _lib.SR_ERR_NOMEM and n.value > cap:
+                cap = n.value
+                continue
+            _lib.check(rc, "sr_token_counts")
+            break
+    return row_ptr, cols[:n.value], vals[:n.value], lengths
+
+
+def bm25_weights(indptr, doc_ids, tf, doc_len, idf, numer, a, s, out=None):
+    """BM25 weights of a term-major CSR of term frequencies (include/sr_hip.h sr_bm25_weights): indptr int64
+    [n_terms + 1], doc_ids int32 [nnz], tf fp32 [nnz], doc_len int32 [n_docs], idf fp32 [n_terms] on the device; numer, a, s the three
+    fp32 scalars of bm25.bm25_scalars.  w = f32(idf[t] * f32(f32(tf * numer) / f32(tf + f32(a + f32(s * f32(doc_len[d])))))).  out: the
+    fp32 [nnz] tensor to write (may be tf itself); None: a new one.  Returns it.  A document id outside [0, n_docs): ValueError."""
+    _lib.require_gpu()
+    dev = _cuda_device(tf)
+    indptr = _to_dev(indptr, torch.int64, dev)
+    doc_ids = _to_dev(doc_ids, torch.int32, dev)
+    tf = _to_dev(tf, torch.float32, dev)
+    doc_len = _to_dev(doc_len, torch.int32, dev)
+    idf = _to_dev(idf, torch.float32, dev)
+    nnz, n_terms = tf.numel(), indptr.numel() - 1
+    if indptr.dim() != 1 or n_terms < 0 or doc_ids.shape != tf.shape or tf.dim() != 1 or idf.shape != (max(n_terms, 0),) or doc_len.dim() != 1:
+        raise ValueError(f"expected indptr [n_terms + 1], doc_ids / tf [nnz], idf [n_terms], doc_len [n_docs]; got {tuple(indptr.shape)}, "
+                         f"{tuple(doc_ids.shape)}, {tuple(tf.shape)}, {tuple(idf.shape)}, {tuple(doc_len.shape)}")
+    # the kernel trusts indptr to end at nnz: the one thing checked here, as for candidate lists
+    if int(indptr[-1]) != nnz or int(indptr[0]) != 0:
+        raise ValueError(f"indptr runs from {int(indptr[0])} to {int(indptr[-1])}, the CSR holds {nnz} postings")
+    if out is None:
+        out = torch.empty(nnz, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == tf.shape):
+        raise ValueError("out must be a contiguous fp32 cuda tensor of tf's shape")
+    _call(dev, "sr_bm25_weights", _ptr(indptr), _ptr(_valid(doc_ids)), _ptr(_valid(tf)), n_terms, nnz, _ptr(_valid(doc_len)), doc_len.numel(),
+          _ptr(_valid(idf)), float(numer), float(a), float(s), _ptr(_valid(out)))
+    return out
 
 
 def sparse_feedback(q_indptr, q_cols, q_vals, doc_indptr, doc_cols, doc_vals, n_terms, fb_ids, counts=None, n_pos=10, n_neg=0, alpha=1.0,
